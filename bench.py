@@ -17,9 +17,13 @@ rendezvous on 127.0.0.1) when it is not already running under a launcher; under
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline        — the scan kernel: algorithmic bytes / live HIP-event duration vs 8 TB/s
+A plain run sets up, warms up, times `--steps` steps and prints that line; `--dump-outputs DIR` also writes what the
+last timed step computed as DIR/<name>.npy.  Everything else runs only with `--full`:
+  roofline.traffic measured by rocprofv3 child runs (N=1), the read-ceiling sweep next to the scan,
   cpu_baseline    — the C oracle timed on this host's cores on a bounded sample (N=1 only)
   other_workloads — (N=1 only) 4K 240x135 and 4K fine 960x540 scans, same measurement
   host_fed        — (N=1 only) PCIe-inclusive frames/s of the C++ host pipeline (never `value`)
+  and the check that the batch's flags repeat the generated tile's.
 """
 import argparse
 import json
@@ -70,6 +74,13 @@ def parse(argv=None):
                     choices=["1080p_dense8x8", "1080p_dense16", "4k_dense8x8", "4k_dense16", "4k_fine", "4k_fine_dense4", "480p_dense16",
                              "720p_dense16", "480p_dense8x8", "720p_dense8x8"])
     ap.add_argument("--params", default="code_defaults", choices=["code_defaults", "shipped_env"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: measured traffic, read-ceiling sweep, CPU baseline, "
+                         "other workloads, host-fed legs, tile-periodicity check (the --no-* / --cpu-seconds / --host-* "
+                         "options below shape those)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (flags, segments, merge results) "
+                         "as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (0 = skip)")
     ap.add_argument("--no-merge", action="store_true", help="time the scan kernel alone")
     ap.add_argument("--no-others", action="store_true", help="skip the other_workloads leg")
@@ -637,6 +648,73 @@ def roofline_of(alg_bytes, kern_ms):
             "algorithmic_bytes_per_launch": alg_bytes}
 
 
+def read_ceiling_sweep(dev, scanner, d_mv, d_off, d_flags, spec, alg_bytes):
+    """--full: the measured read ceiling next to the scan.  Returns (sweep GB/s by configuration, best GB/s, name of
+    the best configuration, GB/s of the scan re-timed right after the sweep)."""
+    import torch
+    # calibration (outside the timed region): kernels that ONLY read the same record buffer — both load shapes, three
+    # chunk sizes, 20 launches back to back each (the regime of the timed loop); the ceiling is the best of them
+    calib = load_calib()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    nbytes = (d_mv.numel() // 16) * 16
+    frame_bytes = 40 * int(spec.records_per_frame)                                # a P-frame of this workload (ragged workloads: its nominal size)
+    sweep = {}
+    configs = []
+    for shape, sname, chunks, idle in ((2, "12of40+arith", (frame_bytes, 1280 * 1024), 30), (2, "12of40+arith", (frame_bytes, 1280 * 1024), 0),
+                                       (3, "12of40+arith+lds", (frame_bytes,), 30), (1, "12of40", (1280 * 1024, 5 * 1024 * 1024), 0),
+                                       (0, "16B", (1280 * 1024, 5 * 1024 * 1024), 0)):
+        configs += [(f"{sname}/{chunk}" + (f"/idle{idle}" if idle else ""), shape, chunk, idle) for chunk in chunks
+                    if nbytes >= 256 * chunk]        # (a test-sized batch calibrates nothing: at least a workgroup per CU)
+    times = {name: [] for name, _, _, _ in configs}
+    for order in (configs, configs[::-1]):       # two passes in opposite orders: no configuration owes its figure to its place
+        for name, shape, chunk, idle in order:
+            for _ in range(2):
+                calib(dev.index, d_mv.data_ptr(), nbytes, shape, chunk, scanner.plan["lds_bytes"], idle, st)
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
+            for c0, c1 in evs:           # an event pair around every launch, exactly as the scan kernel is timed
+                c0.record()
+                calib(dev.index, d_mv.data_ptr(), nbytes, shape, chunk, scanner.plan["lds_bytes"], idle, st)
+                c1.record()
+            torch.cuda.synchronize()
+            times[name] += [c0.elapsed_time(c1) for c0, c1 in evs]
+    for name, t in times.items():
+        sweep[name] = nbytes / (max(float(np.mean(t)), 1e-6) * 1e-3) / 1e9       # (a buffer smaller than one chunk launches nothing)
+    # ... and the scan itself once more, timed the same way in the same phase of the run (clocks and the memory
+    # system's state drift over a run: the timed loop ran seconds earlier)
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
+    for c0, c1 in evs:
+        c0.record()
+        scanner.check_frames_device(d_mv, d_off, None, d_flags)
+        c1.record()
+    torch.cuda.synchronize()
+    scan_in_sweep = alg_bytes / (max(float(np.mean([c0.elapsed_time(c1) for c0, c1 in evs])), 1e-6) * 1e-3) / 1e9
+    read_ceiling_best = max(sweep, key=sweep.get) if sweep else None
+    read_ceiling = sweep[read_ceiling_best] if sweep else None
+    return sweep, read_ceiling, read_ceiling_best, scan_in_sweep
+
+
+def dump_outputs(out_dir, flags, merged, gathered, seg_cap, result_dtype):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files.  `merged` is the
+    (segments, results) pair of that step's merge (None under --no-merge); `gathered` the uint8 [world, S, packed]
+    segment lists every rank received (N > 1), which then take the place of this rank's own.  Segment slots past a
+    stream's n_segments are unspecified in the library's output and written as 0."""
+    from mvtrim_amd import dist as mdist
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"flags": flags.cpu().numpy().astype(np.float32)}
+    if merged is not None:
+        if gathered is not None:
+            seg, res = mdist.unpack_segment_lists(gathered, seg_cap)
+        else:
+            seg, res = merged[0].cpu().numpy()[None], merged[1].cpu().numpy().view(result_dtype).reshape(1, -1)
+        seg = seg.copy()
+        seg[np.arange(seg_cap)[None, None, :] >= res["n_segments"][..., None].astype(np.int64)] = 0.0
+        arrays["segments"] = seg.astype(np.float64)
+        for name in result_dtype.names:
+            arrays["merge_" + name] = res[name].astype(np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def other_workloads(dev, distinct, arena=None):
     """4K / fine-grid scans after the headline (N=1): frames/s, kernel ms, roofline fraction; every
     batch's flags are checked to be the tile's flags repeated and the tile's flags == the oracle's."""
@@ -819,6 +897,7 @@ def _run_rank(a):
         stage("process_group_ready", backend=a.backend, world=world)
 
     # ---------------- synthetic input: `distinct` generated frames, tiled to `frames`
+    # (the arena is allocated with or without --full: the headline's records then always sit in the same place)
     arena = None
     if world == 1 and not a.no_others:
         try:                        # first allocation of the process: the headline and every 21 GB leg live in it
@@ -933,44 +1012,13 @@ def _run_rank(a):
         prof = {"launches": a.steps, "scan_ms": dt_local / a.steps * 1e3, "plan_ms": 0.0}
     assert prof["launches"] == a.steps, prof
     kern_ms, plan_ms = prof["scan_ms"], prof["plan_ms"]
-    # calibration (outside the timed region): kernels that ONLY read the same record buffer — both load shapes, three
-    # chunk sizes, 20 launches back to back each (the regime of the timed loop); the ceiling is the best of them
-    calib = load_calib()
-    st = torch.cuda.current_stream(dev).cuda_stream
-    nbytes = (d_mv.numel() // 16) * 16
-    frame_bytes = 40 * int(spec.records_per_frame)                                # a P-frame of this workload (ragged workloads: its nominal size)
-    sweep = {}
-    configs = []
-    for shape, sname, chunks, idle in ((2, "12of40+arith", (frame_bytes, 1280 * 1024), 30), (2, "12of40+arith", (frame_bytes, 1280 * 1024), 0),
-                                       (3, "12of40+arith+lds", (frame_bytes,), 30), (1, "12of40", (1280 * 1024, 5 * 1024 * 1024), 0),
-                                       (0, "16B", (1280 * 1024, 5 * 1024 * 1024), 0)):
-        configs += [(f"{sname}/{chunk}" + (f"/idle{idle}" if idle else ""), shape, chunk, idle) for chunk in chunks
-                    if nbytes >= 256 * chunk]        # (a test-sized batch calibrates nothing: at least a workgroup per CU)
-    times = {name: [] for name, _, _, _ in configs}
-    for order in (configs, configs[::-1]):       # two passes in opposite orders: no configuration owes its figure to its place
-        for name, shape, chunk, idle in order:
-            for _ in range(2):
-                calib(dev.index, d_mv.data_ptr(), nbytes, shape, chunk, scanner.plan["lds_bytes"], idle, st)
-            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
-            for c0, c1 in evs:           # an event pair around every launch, exactly as the scan kernel is timed
-                c0.record()
-                calib(dev.index, d_mv.data_ptr(), nbytes, shape, chunk, scanner.plan["lds_bytes"], idle, st)
-                c1.record()
-            torch.cuda.synchronize()
-            times[name] += [c0.elapsed_time(c1) for c0, c1 in evs]
-    for name, t in times.items():
-        sweep[name] = nbytes / (max(float(np.mean(t)), 1e-6) * 1e-3) / 1e9       # (a buffer smaller than one chunk launches nothing)
-    # ... and the scan itself once more, timed the same way in the same phase of the run (clocks and the memory
-    # system's state drift over a run: the timed loop ran seconds earlier)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
-    for c0, c1 in evs:
-        c0.record()
-        scanner.check_frames_device(d_mv, d_off, None, flag_bufs[0])
-        c1.record()
-    torch.cuda.synchronize()
-    scan_in_sweep = alg_bytes / (max(float(np.mean([c0.elapsed_time(c1) for c0, c1 in evs])), 1e-6) * 1e-3) / 1e9
-    read_ceiling_best = max(sweep, key=sweep.get) if sweep else None
-    read_ceiling = sweep[read_ceiling_best] if sweep else None
+    last = (counter[0] - 1) & 1                     # the buffer set of the last timed step
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, flag_bufs[last], out, gath[last] if multi else None, SEG_CAP, m.MERGE_RESULT_DTYPE)
+    sweep, read_ceiling, read_ceiling_best, scan_in_sweep = {}, None, None, None
+    if a.full:
+        sweep, read_ceiling, read_ceiling_best, scan_in_sweep = read_ceiling_sweep(
+            dev, scanner, d_mv, d_off, flag_bufs[0], spec, alg_bytes)
     flags_host = d_flags.cpu().numpy()
 
     # what each rank held and did, gathered for the driver (N = 1: one entry)
@@ -1006,10 +1054,11 @@ def _run_rank(a):
         # the batch is the generated tile repeated: so must be its flags (checks every frame of the
         # 5 GB batch, not only the first tile, against the oracle-verified tile flags below)
         tile_flags = flags_host[: a.distinct]
-        assert np.array_equal(flags_host, np.tile(tile_flags, reps)[: a.frames]), "flags are not tile-periodic"
-        if world == 1 and a.cpu_seconds > 0:
+        if a.full:
+            assert np.array_equal(flags_host, np.tile(tile_flags, reps)[: a.frames]), "flags are not tile-periodic"
+        if a.full and world == 1 and a.cpu_seconds > 0:
             cpu = cpu_baseline(params, mv, off, tile_flags, a.cpu_seconds, a.workload)
-        if world == 1 and not a.no_host and a.workload == "1080p_dense8x8":
+        if a.full and world == 1 and not a.no_host and a.workload == "1080p_dense8x8":
             try:
                 host = host_fed_leg(spec, mv, off, a.host_runs, a.host_seconds)
             except Exception as e:          # informational leg
@@ -1028,7 +1077,7 @@ def _run_rank(a):
                         vs[f"config4_{key}_steady"] = v["frames_per_s_steady"] / ref_cpu
             vs["resident_value"] = value / ref_cpu
             host["vs_cpu_baseline_same_quota"] = vs
-        if world == 1 and not a.no_others:
+        if a.full and world == 1 and not a.no_others:
             del d_mv, d_off, w
             torch.cuda.empty_cache()
             try:
@@ -1043,17 +1092,18 @@ def _run_rank(a):
         roof.update({"plan_ms": plan_ms, "call_ms": kern_ms + plan_ms,
                      "frac_of_call": alg_bytes / ((kern_ms + plan_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS})
         roof.update({"traffic": traffic, "traffic_source": traffic_source, "traffic_detail": traffic_detail,
-                     "traffic_over_algorithmic": (traffic / alg_bytes) if traffic else None,
-                     "measured_read_ceiling": read_ceiling,
-                     "measured_read_ceiling_is": f"best of a sweep of read-only kernels on the same buffer: {read_ceiling_best} "
-                                                 "(load shape / bytes per workgroup [/ every n-th workgroup idle])",
-                     "read_ceiling_sweep_GBps": {k_: round(v_, 1) for k_, v_ in sweep.items()},
-                     "scan_rate_next_to_the_sweep_GBps": scan_in_sweep,
-                     "frac_of_measured_ceiling": scan_in_sweep / read_ceiling if read_ceiling else None,
-                     # rounds 1-4 quoted this ratio instead: the timed loop's rate over ONE read-only kernel, 16 contiguous
-                     # bytes per lane, 1.25 MiB per workgroup (not the best of a sweep, not re-timed beside it)
-                     "frac_of_16B_read_kernel_rounds_1_to_4_definition":
-                         (roof["achieved"] / sweep["16B/1310720"]) if sweep.get("16B/1310720") else None})
+                     "traffic_over_algorithmic": (traffic / alg_bytes) if traffic else None})
+        if a.full:
+            roof.update({"measured_read_ceiling": read_ceiling,
+                         "measured_read_ceiling_is": f"best of a sweep of read-only kernels on the same buffer: {read_ceiling_best} "
+                                                     "(load shape / bytes per workgroup [/ every n-th workgroup idle])",
+                         "read_ceiling_sweep_GBps": {k_: round(v_, 1) for k_, v_ in sweep.items()},
+                         "scan_rate_next_to_the_sweep_GBps": scan_in_sweep,
+                         "frac_of_measured_ceiling": scan_in_sweep / read_ceiling if read_ceiling else None,
+                         # rounds 1-4 quoted this ratio instead: the timed loop's rate over ONE read-only kernel, 16 contiguous
+                         # bytes per lane, 1.25 MiB per workgroup (not the best of a sweep, not re-timed beside it)
+                         "frac_of_16B_read_kernel_rounds_1_to_4_definition":
+                             (roof["achieved"] / sweep["16B/1310720"]) if sweep.get("16B/1310720") else None})
         line = {
             "metric": "MV-scan frames/sec at 1080p grid" if a.workload.startswith("1080p") else "MV-scan frames/sec",
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -1189,7 +1239,7 @@ def main(argv=None):
         sys.exit(launch_ranks(a, argv))
     if a.pmc_child:
         return pmc_child(a)
-    if a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.no_pmc and not a.force_dist:
+    if a.full and a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.no_pmc and not a.force_dist:
         # N = 1, and this process has not touched the GPU yet (torch is not even imported)
         a.pmc_result = measure_traffic(a, argv)
     run_rank(a)

@@ -66,4 +66,6 @@ def filter_case_ticks(g, case):
 
 
 def id_of(x):
-    return x if isinstance(x, str) else None
+    """A case's name as its pytest id; `::` (a C++ scope in a name) becomes `_`, since `::` separates the parts of a
+    test id."""
+    return x.replace("::", "_") if isinstance(x, str) else None

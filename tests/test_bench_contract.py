@@ -325,3 +325,40 @@ def test_traffic_is_measured_by_child_runs_or_the_fallback_says_why(tmp_path):
         return Ok()
     t, src, detail = bench.measure_traffic(a, [], which=lambda name: "/bin/rocprofv3", run=run_ok, tmp_root=str(tmp_path))
     assert t == 1000 * 2048.0 + 10 * 1024.0 and src.startswith("measured in this run") and detail["launches_averaged"] == [4, 4]
+
+
+def test_plain_run_is_the_default_and_dump_outputs_writes_float_arrays(tmp_path):
+    """`--full` (every leg beyond the headline) is off by default and `--dump-outputs` names no directory by default;
+    dump_outputs writes the last step's flags, segments and merge results as float32 / float64 .npy files, with the
+    segment slots past a stream's n_segments zeroed, and the gathered lists of every rank in place of its own."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    import mvtrim_amd as m
+    from mvtrim_amd import dist as mdist
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", "x"]).full and bench.parse(["--dump-outputs", "x"]).dump_outputs == "x"
+    S, cap = 3, 4
+    seg = torch.arange(S * cap * 2, dtype=torch.float64).reshape(S, cap, 2) + 0.5
+    res = np.zeros(S, dtype=m.MERGE_RESULT_DTYPE)
+    res["n_segments"], res["n_timestamps"], res["do_cut"], res["saved_pct"] = [0, 2, 4], [5, 6, 7], [0, 1, 1], [1.5, 2, 3]
+    res_t = torch.from_numpy(res.view(np.uint8).reshape(S, -1).copy())
+    flags = torch.tensor([0, 1, 1, 0, 1], dtype=torch.uint8)
+    bench.dump_outputs(str(tmp_path / "one"), flags, (seg, res_t), None, cap, m.MERGE_RESULT_DTYPE)
+    got = {f[:-4]: np.load(tmp_path / "one" / f) for f in os.listdir(tmp_path / "one")}
+    assert set(got) == {"flags", "segments"} | {"merge_" + n for n in m.MERGE_RESULT_DTYPE.names}
+    assert got["flags"].dtype == np.float32 and got["flags"].tolist() == [0, 1, 1, 0, 1]
+    assert all(v.dtype == np.float64 for k, v in got.items() if k != "flags")
+    want = seg.numpy().copy()
+    want[0, :] = 0
+    want[1, 2:] = 0
+    assert got["segments"].shape == (1, S, cap, 2) and np.array_equal(got["segments"][0], want)
+    assert got["merge_n_segments"].tolist() == [[0, 2, 4]] and got["merge_saved_pct"].tolist() == [[1.5, 2, 3]]
+    assert bench.dump_outputs(str(tmp_path / "flags_only"), flags, None, None, cap, m.MERGE_RESULT_DTYPE) is None
+    assert os.listdir(tmp_path / "flags_only") == ["flags.npy"]
+    gathered = torch.stack([mdist.pack_segment_lists(seg, res_t)] * 2)          # two ranks' lists
+    bench.dump_outputs(str(tmp_path / "two"), flags, (seg, res_t), gathered, cap, m.MERGE_RESULT_DTYPE)
+    two = np.load(tmp_path / "two" / "segments.npy")
+    assert two.shape == (2, S, cap, 2) and np.array_equal(two[1], want)

@@ -1,6 +1,6 @@
 """CPU tests of the MV file formats (mvfile.py .mtmv container, mvjson.py extract_mvs JSON)
 and of the BASELINE.json config-0 plumbing: synthetic MV frames -> JSON in the reference's
-schema -> the reference's own motion_scalar tool (golden output committed; re-run live when
+schema -> the reference's own motion_scalar tool (golden outputs committed; re-run live when
 oracle/_ref/motion_scalar exists) vs the oracle's restatement."""
 import importlib.util
 import json
@@ -49,19 +49,24 @@ def test_motion_scalar_matches_reference_golden():
 
 
 def test_motion_scalar_live_reference_tool(tmp_path):
-    ref = os.path.join(ROOT, "oracle", "_ref", "motion_scalar")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/motion_scalar not built (needs the reference tree)")
+    """A second stream through the reference's motion_scalar tool: its stdout is recorded in
+    tests/golden/reference_live_vectors.json (tests/golden/make_reference_live_vectors.py) and, where
+    oracle/_ref/motion_scalar is built, produced live again; the oracle's restatement must match it."""
+    gold = json.load(open(os.path.join(GOLD, "reference_live_vectors.json")))["motion_scalar"]
     spec = synth.StreamSpec(width=320, height=240, block=16, sub=1, fps=30.0, gop=10, seed=9, salt_p=0.05)
     spec.events = [synth.Event(3, 40, 4, 3, 5, 4, 11, -7)]
     frames = [synth.gen_frame(spec, i) for i in range(70)]
     pts = [spec.pts_seconds(i) for i in range(70)]
-    path = str(tmp_path / "mv.json")
-    m.mvjson.write_json(path, frames, pts, (1, spec.tb_den))
-    out = subprocess.run([ref, path], check=True, capture_output=True, text=True).stdout
-    rows = sorted([int(a), b] for a, b in (ln.split(",") for ln in out.strip().splitlines()[1:]))
-    assert out.splitlines()[0] == "second,motion_value"
-    assert rows == [r for r in scalar_rows(frames, pts) if r[1] != "0"]
+    assert gold["csv_header"] == "second,motion_value"
+    want = [[int(a), b] for a, b in gold["rows"]]
+    assert want and want == [r for r in scalar_rows(frames, pts) if r[1] != "0"]
+    ref = os.path.join(ROOT, "oracle", "_ref", "motion_scalar")
+    if os.path.exists(ref):
+        path = str(tmp_path / "mv.json")
+        m.mvjson.write_json(path, frames, pts, (1, spec.tb_den))
+        out = subprocess.run([ref, path], check=True, capture_output=True, text=True).stdout
+        assert out.splitlines()[0] == gold["csv_header"]
+        assert sorted([int(a), b] for a, b in (ln.split(",") for ln in out.strip().splitlines()[1:])) == want
 
 
 def test_json_roundtrip(tmp_path):

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -49,7 +50,7 @@ def _check_line(d, world, frames):
 
 
 def test_bench_line_single_gpu():
-    d = _run(QUICK)
+    d = _run(QUICK + ["--full"])
     _check_line(d, 1, 600)
     assert d["distinct_devices"] == 1 and d["ranks"][0]["pci_bus_id"]
     assert d["config"]["step"] == "scan + stream-merge kernels"
@@ -60,8 +61,31 @@ def test_bench_line_single_gpu():
     assert 0.97 < r["traffic"] / r["algorithmic_bytes_per_launch"] < 1.03 and r["traffic_detail"]["launches_averaged"] == [4, 4]
     # the scan kernel and the planning kernels ahead of it are timed separately, by the library's own events
     assert 0 < r["plan_ms"] < r["kernel_ms"] and abs(r["call_ms"] - r["plan_ms"] - r["kernel_ms"]) < 1e-9
-    d2 = _run(QUICK + ["--no-pmc"])
+    d2 = _run(QUICK + ["--full", "--no-pmc"])
     assert d2["roofline"]["traffic"] is None or "replayed" in d2["roofline"]["traffic_source"]
+
+
+def test_plain_bench_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the run is the headline alone (no rocprofv3 children, no read-ceiling sweep, no CPU / host / other
+    legs); --dump-outputs writes what the last timed step computed, and two runs with the same arguments write the
+    same arrays."""
+    dumps = [tmp_path / "a", tmp_path / "b"]
+    lines = [_run(["--steps", "3", "--warmup", "1", "--frames", "600", "--dump-outputs", str(p)]) for p in dumps]
+    for d in lines:
+        _check_line(d, 1, 600)
+        assert d["steps"] == 3 and d["cpu_baseline"] is None and d["other_workloads"] is None and d["host_fed"] is None
+        assert "measured_read_ceiling" not in d["roofline"] and d["roofline"]["traffic_detail"] is None
+    names = sorted(os.listdir(dumps[0]))
+    assert names == sorted(os.listdir(dumps[1]))
+    assert {"flags.npy", "segments.npy", "merge_n_segments.npy", "merge_do_cut.npy"} <= set(names)
+    for n in names:
+        x, y = np.load(dumps[0] / n), np.load(dumps[1] / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    flags = np.load(dumps[0] / "flags.npy")
+    assert flags.shape == (600,) and int(flags.sum()) == lines[0]["motion_frames_in_batch"]
+    seg, nseg = np.load(dumps[0] / "segments.npy"), np.load(dumps[0] / "merge_n_segments.npy")
+    streams = lines[0]["config"]["streams_per_gpu"]
+    assert seg.shape == (1, streams, 64, 2) and nseg.shape == (1, streams) and nseg.sum() > 0
 
 
 def test_bench_two_ranks_rehearsal_gloo_same_device(tmp_path):

@@ -13,7 +13,7 @@ from mvtrim_amd import synth
 import oracle_binding as ob
 from np_model import check_frame_np
 
-from golden_cases import (GOLD, build_mvs, filter_case_ticks, load_filter_cases, load_hand_cases,
+from golden_cases import (GOLD, build_mvs, filter_case_ticks, id_of, load_filter_cases, load_hand_cases,
                           load_merge_cases, load_survey_segments, merge_case_ts)
 
 
@@ -24,7 +24,7 @@ def test_hand_case_params():
         assert getattr(p, k) == v
 
 
-@pytest.mark.parametrize("name,kw,case", load_hand_cases()[1], ids=lambda x: x if isinstance(x, str) else None)
+@pytest.mark.parametrize("name,kw,case", load_hand_cases()[1], ids=id_of)
 def test_check_frame_hand_cases(name, kw, case):
     p = ob.params_from_config(**kw)
     mv = build_mvs(case)
@@ -125,7 +125,7 @@ def test_scan_frames_threads_and_null_has_sd():
 
 # ------------------------------------------------------------------ merge
 
-@pytest.mark.parametrize("name,kw,case", load_merge_cases(), ids=lambda x: x if isinstance(x, str) else None)
+@pytest.mark.parametrize("name,kw,case", load_merge_cases(), ids=id_of)
 def test_merge_hand_cases(name, kw, case):
     ts = merge_case_ts(case)
     mp = m.MergeParams(**kw)

@@ -11,12 +11,12 @@ TimeSegment layout the merge writes (a9/a10).  Replayed against
   * csrc/host/mtgpu_host.hpp       (C++ host layer, through tests/cpp/host_probe.cpp)
   * include/mt_types.h             (mt_segment == TimeSegment)
 
-and, when oracle/_ref/ref_host_probe is present (build container, or the GPU box where the built binary
-travels), live against it on fresh random inputs.
+and on seeded random inputs recorded with the reference's answers (tests/golden/reference_live_vectors.json),
+which oracle/_ref/ref_host_probe, where it is built, answers live as well.
 """
+import importlib.util
 import json
 import os
-import random
 import subprocess
 
 import numpy as np
@@ -28,6 +28,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 PKG = os.path.dirname(m.LIB_PATH)
 VEC = json.load(open(os.path.join(HERE, "golden", "reference_host_vectors.json")))
+LIVE = json.load(open(os.path.join(HERE, "golden", "reference_live_vectors.json")))
 REF_PROBE = os.path.join(ROOT, "oracle", "_ref", "ref_host_probe")
 
 GETTERS = {
@@ -216,59 +217,32 @@ def test_cpp_host_race_matches_reference(host_probe):
     assert run(host_probe, ["race", "2000", "8"]) == VEC["race"]
 
 
-def _random_env(rng):
-    pool = ["3", "4.75", "-2", " 9", "0x1F", "1e1", "12abc", "0.0625", "255", "256", ".5", "1e-3", "7."]
-    return {v: rng.choice(pool) for v in rng.sample(CONFIG_VARS, rng.randrange(1, len(CONFIG_VARS)))}
-
-
-@pytest.mark.skipif(not os.path.exists(REF_PROBE), reason="oracle/_ref/ref_host_probe not built (make -C oracle ref)")
 def test_live_against_reference_binary(host_probe):
-    rng = random.Random(7)
-    for _ in range(40):
-        env = _random_env(rng)
-        ref = run(REF_PROBE, ["config"], env)
+    """Seeded random inputs (tests/golden/reference_live_vectors.json, recorded with the reference's own answers by
+    tests/golden/make_reference_live_vectors.py) replayed against the C++ host layer and the Python mirror; where
+    oracle/_ref/ref_host_probe is built, the reference answers them live as well and must still say what it said."""
+    live = os.path.exists(REF_PROBE)
+    assert (len(LIVE["config"]), len(LIVE["queue"]), len(LIVE["memo"])) == (40, 10, 20)
+    for case in LIVE["config"]:
+        env, ref = case["env"], case["answers"]
+        if live:
+            assert run(REF_PROBE, ["config"], env) == ref, env
         assert run(host_probe, ["config"], env) == ref, env
         assert python_config_answers(env) == bits_only(ref), env
-    for _ in range(10):
-        ops, tid = [], 0
-        for _ in range(200):
-            c = rng.random()
-            if c < 0.35:
-                ops.append(f"tpush {rng.uniform(0, 9e4)!r} {rng.uniform(0, 9e4)!r} {tid}")
-                tid += 1
-            elif c < 0.6:
-                ops.append("tpop")
-            elif c < 0.75:
-                n = rng.randrange(0, 6)
-                ops.append(("radd %d %s" % (n, " ".join(repr(rng.uniform(-1, 1e5)) for _ in range(n)))).strip())
-            elif c < 0.8:
-                ops.append("rextract")
-            elif c < 0.9:
-                n = rng.randrange(0, 4)
-                ops.append(("jpush %d %d %s" % (rng.randrange(64), n, " ".join(repr(rng.uniform(0, 1e4))
-                                                                             for _ in range(2 * n)))).strip())
-            else:
-                ops.append(rng.choice(["jpop", "jdone", "jempty", "tfinish", "jfinish"]))
-        ops += ["tfinish", "tpop", "jfinish", "jpop", "rextract"]
-        script = "\n".join(ops) + "\n"
-        assert run(host_probe, ["queue"], stdin=script) == run(REF_PROBE, ["queue"], stdin=script)
-    assert run(REF_PROBE, ["layout"]) == VEC["layout"]
-    pool = ["3", "4.75", "abc", "", " 9", "0x1F", "1e400", "300", "-1", "12abc", "99999999999"]
-    for _ in range(20):
-        ops = []
-        for _ in range(40):
-            c = rng.random()
-            name = rng.choice(list(GETTERS))
-            if c < 0.5:
-                ops.append(f"get {name}")
-            elif c < 0.9:
-                ops.append(f"set {name.upper()} {rng.choice(pool)}")
-            else:
-                ops.append(f"unset {name.upper()}")
-        script = "\n".join(ops) + "\n"
-        ref = run(REF_PROBE, ["memo"], stdin=script)
-        assert run(host_probe, ["memo"], stdin=script) == ref
-        assert python_memo_answers(ops) == bits_only_mixed(ref)
+    for case in LIVE["queue"]:
+        script = "\n".join(case["script"]) + "\n"
+        if live:
+            assert run(REF_PROBE, ["queue"], stdin=script) == case["answers"]
+        assert run(host_probe, ["queue"], stdin=script) == case["answers"]
+    assert LIVE["layout"] == VEC["layout"]
+    if live:
+        assert run(REF_PROBE, ["layout"]) == VEC["layout"]
+    for case in LIVE["memo"]:
+        script = "\n".join(case["script"]) + "\n"
+        if live:
+            assert run(REF_PROBE, ["memo"], stdin=script) == case["answers"]
+        assert run(host_probe, ["memo"], stdin=script) == case["answers"]
+        assert python_memo_answers(case["script"]) == bits_only_mixed(case["answers"])
 
 
 def test_cpp_host_queues_under_thread_sanitizer(tmp_path):
@@ -341,23 +315,43 @@ def _ref_has_sizing():
         return False
 
 
-@pytest.mark.skipif(not _ref_has_sizing(), reason="oracle/_ref/ref_host_probe was built without the reference's system.cpp")
+def _check_sizing_answers(ref, ps):
+    """One `ref_host_probe sizing` answer under PARALLEL_STREAMS=ps: its own documented rule.  Returns the limit."""
+    assert len(ref) == 3 and ref[0].startswith("detect_cpu_limit ") and ref[1].startswith("calculate_parallel_streams ")
+    limit = int(ref[0].split()[1])
+    if ps == "abc":                                            # std::stoi throws in the reference; here: a configuration error
+        assert "throws" in ref[1]
+    else:
+        streams = int(ref[1].split()[1])
+        assert streams == (max(1, limit) if ps in (None, "0") else max(1, min(int(ps), limit)))
+    return limit
+
+
 def test_what_the_reference_would_choose_on_this_machine_vs_the_cpu_budget(host_probe):
-    """Row a11 (stream fan-out).  How many streams the REFERENCE starts on this machine is asked of the reference's
-    own object code (src/system.cpp compiled where it lies into oracle/_ref/ref_host_probe: detect_cpu_limit(),
+    """Row a11 (stream fan-out).  How many streams the REFERENCE starts is asked of the reference's own object code
+    (src/system.cpp compiled where it lies into oracle/_ref/ref_host_probe: detect_cpu_limit(),
     calculate_parallel_streams(), get_available_cpus(), src/system.cpp:107-197) — the product holds no restatement of
-    it.  The host layer sizes from cpu_budget() instead (the cgroup quota when there is one), which can only be
-    tighter: detect_cpu_limit() takes the LARGER of the quota and the cpuset's CPU count (:155-161)."""
+    it.  Its answers are recorded in tests/golden/reference_live_vectors.json with the CPU facts of the machine they
+    came from, and asked live on this machine where the probe is built.  The host layer sizes from cpu_budget() instead
+    (the cgroup quota when there is one), which can only be tighter: detect_cpu_limit() takes the LARGER of the quota
+    and the cpuset's CPU count (:155-161) — on a machine without the probe that is the limit the bound uses."""
     budget = int(run(host_probe, ["cpulimit"])[0])
-    for ps in (None, "0", "3", "64"):
-        env = {} if ps is None else {"PARALLEL_STREAMS": ps}
-        ref = run(REF_PROBE, ["sizing"], env)
-        assert len(ref) == 3 and ref[0].startswith("detect_cpu_limit ") and ref[1].startswith("calculate_parallel_streams ")
-        limit, streams = int(ref[0].split()[1]), int(ref[1].split()[1])
-        assert 1 <= budget <= max(limit, len(os.sched_getaffinity(0)))
-        assert streams == (max(1, limit) if ps in (None, "0") else max(1, min(int(ps), limit)))   # its own documented rule
-    for ps in ("abc",):                                        # std::stoi throws in the reference; here: a configuration error
-        assert "throws" in run(REF_PROBE, ["sizing"], {"PARALLEL_STREAMS": ps})[1]
+    rec = LIVE["sizing"]
+    assert [c["parallel_streams"] for c in rec["cases"]] == [None, "0", "3", "64", "abc"]
+    recorded = {_check_sizing_answers(c["answers"], c["parallel_streams"]) for c in rec["cases"]}
+    facts = rec["machine"]
+    assert len(recorded) == 1 and recorded.pop() >= max(facts["cgroup_quota_cpus"] or 0, facts["cgroup_cpuset_cpus"] or 0)
+    if _ref_has_sizing():
+        limit = {_check_sizing_answers(run(REF_PROBE, ["sizing"], {} if c["parallel_streams"] is None else
+                                           {"PARALLEL_STREAMS": c["parallel_streams"]}), c["parallel_streams"])
+                 for c in rec["cases"]}.pop()
+    else:
+        spec = importlib.util.spec_from_file_location("mk_live", os.path.join(HERE, "golden", "make_reference_live_vectors.py"))
+        mk = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mk)
+        here = mk.machine_facts()
+        limit = max(here["cgroup_quota_cpus"] or 0, here["cgroup_cpuset_cpus"] or 0)
+    assert 1 <= budget <= max(limit, len(os.sched_getaffinity(0)))
 
 
 def test_batch_sizing_hand_cases(host_probe):
