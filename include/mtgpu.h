@@ -47,8 +47,6 @@
  *    tests only    MTGPU_FORCE_FB=32|1|2|4|8|108, MTGPU_FORCE_BLOCK=512|1024, MTGPU_FORCE_SLICES, MTGPU_GROUP,
  *                  MTGPU_ITEM_CHUNK, MTGPU_MERGE_LARGE_MIN (reach every kernel form on small inputs),
  *                  MTGPU_INJECT_SUBMIT_FAIL / _GROW_FAIL / _COLLECT_FAIL / MTGPU_INJECT_ONCE (pipe error paths)
- *  (A/B switches of measurements exist only in the experiments build, `make -C csrc experiments`; this library
- *  ignores them.  Their table: csrc/knobs.h.)
  */
 #ifndef MTGPU_H
 #define MTGPU_H

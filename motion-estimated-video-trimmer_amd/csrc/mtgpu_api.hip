@@ -79,7 +79,6 @@ struct mtgpu_ctx {
   int device;            // physical HIP device
   int logical_device = 0;  // what the caller asked for (differs only under MTGPU_ALIAS_DEVICES)
   hipStream_t stream;    // private stream of the host-pointer entry points
-  int variant = 0;       // MTGPU_VARIANT experiment knob
   std::atomic<int> slices_request{0};  // 0 = auto, else 1/2/4/8 (mtgpu_set_slices, MTGPU_FORCE_SLICES): read once per launch,
                                        // may be set while other threads scan through this context
   int wide_chunk_rows = 0, wide_lds_bytes = 0;   // single-workgroup-per-CU layout (see make_plan)
@@ -87,7 +86,6 @@ struct mtgpu_ctx {
   int lds_max = 0;       // device limit of LDS per workgroup
   int group_request = 0; // MTGPU_GROUP: frames per workgroup, 0 = automatic
   int check_offsets = 0; // MTGPU_CHECK_OFFSETS=1: the device entry points verify "frame_off non-decreasing" first (one sync per call)
-  int min_lds_kb = 0;    // MTGPU_MIN_LDS_KB: launch with at least this much LDS (caps workgroups per CU), 0 = automatic
   // Launch scratch (work lists of the device entry points, spill queues, slice tiles, merge workspaces): a ring of
   // device blocks, each with the event of its last user.  Whoever takes a block makes ITS stream wait for that event,
   // so a block never has two users at once, whatever streams and threads the launches come from.  (Through round 5
@@ -116,9 +114,8 @@ struct mtgpu_ctx {
   // instead of a stream per batch.  Creating a HIP stream costs ~3.5 ms and the runtime serialises it: 64 workers
   // x 3 batches = 192 streams took 0.68 s of wall time and 0.35 s per worker — THE cost of creating a pipe
   // (profiles/r04_pin_probe2.json) — while the runtime maps streams onto a handful of hardware queues anyway.
-  static constexpr int kMaxPipeStreams = 32;
+  static constexpr int kMaxPipeStreams = 8;
   hipStream_t pipe_streams[kMaxPipeStreams] = {};
-  int n_pipe_streams = 8;                // MTGPU_PIPE_STREAMS (0: every batch creates its own stream, as before round 4)
   unsigned pipe_rr = 0;                  // next slot (guarded by pipe_mu)
   std::mutex pipe_mu;
   std::mutex mu;         // guards the staging buffers below
@@ -187,7 +184,6 @@ size_t lds_need(int band_rows, int chunk_rows, int gw, int W, int fb, int *cnt_w
 }
 
 using mtgpu::env_int;
-using mtgpu::exp_int;
 
 int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
   const mt_scan_params &p = c->params;
@@ -223,16 +219,10 @@ int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
   k.active_min = mode == 1 ? ((1u << vn) - 1u) : vn;         // thermometer full / binary count
 
   int band_rows = R, chunk_rows = R;
-  // MTGPU_MAX_TILE_KB (experiments): largest single tile; beyond it the grid is cut into row bands
-  long single_max = lds_max;
-  {
-    const int tkb = exp_int("MTGPU_MAX_TILE_KB", 0);
-    if (tkb > 0 && (long)tkb * 1024 < single_max) single_max = (long)tkb * 1024;
-  }
-  if (lds_need(R, R, k.gw, k.W, fb, nullptr) > (size_t)single_max) {
+  if (lds_need(R, R, k.gw, k.W, fb, nullptr) > (size_t)lds_max) {
     // 1st choice: whole grid in one tile, phase 2 in row chunks through a smaller mask buffer
     const size_t cnt_only = lds_need(R, -2, k.gw, k.W, fb, nullptr);   // counters + total
-    const long room = single_max - (long)cnt_only;
+    const long room = (long)lds_max - (long)cnt_only;
     long ch = room / (long)mask_row - 2;
     if (ch > R) ch = R;
     if (ch >= 8 || ch >= R) {
@@ -244,17 +234,10 @@ int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
       // is finished (and the next one started) in half the time two co-resident workgroups would
       // need — with 20 MB work units that halves the idle tail of a launch (960x540, 1024 frames:
       // 2 bands 6.8 TB/s vs 4 bands 6.3-6.6), and every band less is one queue replay less on
-      // vote-heavy input (pan: 5.1 vs 4.1 TB/s).  MTGPU_BAND_LDS_KB overrides the tile limit.
-      long tile_max = (long)lds_max;
-      const int fkb = exp_int("MTGPU_BAND_LDS_KB", 0);
-      if (fkb > 0) tile_max = (long)fkb * 1024 < (long)lds_max ? (long)fkb * 1024 : (long)lds_max;
+      // vote-heavy input (pan: 5.1 vs 4.1 TB/s).
       const size_t per_row = ((size_t)k.gw * (size_t)fb + 7u) / 8u + mask_row;
-      long r = 0;
-      for (int pass = 0; pass < 2 && r < 1; ++pass) {             // the tile limit first, all of LDS if a row is that wide
-        const long lim = pass == 0 ? tile_max : (long)lds_max;
-        r = (lim - 64) / (long)per_row - 2;
-        while (r >= 1 && lds_need((int)r, (int)r, k.gw, k.W, fb, nullptr) > (size_t)lim) --r;
-      }
+      long r = ((long)lds_max - 64) / (long)per_row - 2;
+      while (r >= 1 && lds_need((int)r, (int)r, k.gw, k.W, fb, nullptr) > (size_t)lds_max) --r;
       if (r < 1)
         return fail(MT_ERR_CAPACITY, "grid width %d: three counter rows do not fit %d bytes of LDS", k.gw, lds_max);
       if (r > R) r = R;
@@ -278,8 +261,6 @@ int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
       if (ch >= 8 && ch < chunk_rows) chunk_rows = (int)ch;
     }
   }
-  const int fchunk = exp_int("MTGPU_FORCE_CHUNK", 0);         // experiments: smaller mask buffer
-  if (fchunk >= 1 && fchunk < chunk_rows) { chunk_rows = fchunk; c->wide_chunk_rows = fchunk; c->wide_lds_bytes = (int)lds_need(band_rows, fchunk, k.gw, k.W, fb, nullptr); }
   k.fb = fb;
   k.band_rows = band_rows;
   k.chunk_rows = chunk_rows;
@@ -290,12 +271,11 @@ int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
   // 4 workgroups/CU (measured +2.5 % over 256 on 1080p); tiles above 48 KB run 1-2
   // workgroups/CU and take 16 waves each.
   int block = lds <= 48u * 1024u ? 512 : 1024;
-  // MTGPU_FORCE_BLOCK (tests): 512 | 1024.  The default build instantiates what the planner can choose plus that
-  // switch: 512- and 1024-thread workgroups for single tiles, 1024 for banded plans (their tiles always exceed 48 KB);
-  // 256-thread workgroups and 512-thread banded ones exist only in the experiments build.
+  // MTGPU_FORCE_BLOCK (tests): 512 | 1024.  The library instantiates what the planner can choose plus that switch:
+  // 512- and 1024-thread workgroups for single tiles, 1024 for banded plans (their tiles always exceed 48 KB).
   const int fblock = env_int("MTGPU_FORCE_BLOCK", 0);
-  if (fblock == 512 || fblock == 1024 || (mtgpu::kExperiments && fblock == 256)) block = fblock;
-  if (!mtgpu::kExperiments && k.bands > 1) block = 1024;
+  if (fblock == 512 || fblock == 1024) block = fblock;
+  if (k.bands > 1) block = 1024;
   c->plan.block_threads = block;
   c->plan.bands = k.bands;
   c->plan.band_rows = k.band_rows;
@@ -304,7 +284,6 @@ int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
   c->plan.device = c->logical_device;
   c->plan.cu_count = cu_count;
   c->plan.chunk_rows = chunk_rows;
-  c->variant = exp_int("MTGPU_VARIANT", 0);
   {
     const int fs = env_int("MTGPU_FORCE_SLICES", 0);
     c->slices_request.store((fs == 1 || fs == 2 || fs == 4 || fs == 8) ? fs : 0, std::memory_order_relaxed);
@@ -312,13 +291,8 @@ int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
   k.slices = 1;
   k.group = 1;
   k.sys_flags = 0;                                            // per launch: launch_scan_on
-  k.resident = std::min(std::max(exp_int("MTGPU_RESIDENT", 0), 0), 16);   // experiments: ticketed resident workgroups per CU
-  k.align_lines = exp_int("MTGPU_ALIGN", 1) != 0 ? 1 : 0;     // experiments: 0 = streams start wherever the frame starts
-  k.prefetch = exp_int("MTGPU_PREFETCH", 1) != 0 ? 1 : 0;      // experiments: 0 switches the next-frame prefetch off
   c->group_request = env_int("MTGPU_GROUP", 0);
-  c->min_lds_kb = exp_int("MTGPU_MIN_LDS_KB", 0);
   c->check_offsets = env_int("MTGPU_CHECK_OFFSETS", 0) != 0;
-  c->n_pipe_streams = std::min(std::max(exp_int("MTGPU_PIPE_STREAMS", 8), 0), (int)mtgpu_ctx::kMaxPipeStreams);
   c->item_chunk = env_int("MTGPU_ITEM_CHUNK", 0);
   if (c->item_chunk < 0) c->item_chunk = 0;
   {
@@ -372,7 +346,7 @@ int choose_group(const mtgpu_ctx *c, uint64_t n_records, uint32_t n_frames, int 
     // and issues the next frame's first streaming step before its cluster test (scan_kernels.hip, NextStep).
     // Round 3, 4K dense8x8 compact: 1024 frames 6.13 -> 6.39 TB/s, 4096 frames 6.54 -> 6.73; 4 MB frames
     // (960x540) and four-per-CU tiles (1080p) gain nothing or lose, 40-byte records lose 2 % (no prefetch there).
-    if (g == 1 && rec_bytes == MT_COMPACT_BYTES && c->k.prefetch && c->plan.lds_bytes > 80 * 1024 && avg <= (2ull << 20)) {
+    if (g == 1 && rec_bytes == MT_COMPACT_BYTES && c->plan.lds_bytes > 80 * 1024 && avg <= (2ull << 20)) {
       if ((uint64_t)n_frames >= cus * 4ull) g = 4;
       else if ((uint64_t)n_frames >= cus * 2ull) g = 2;
     }
@@ -385,7 +359,7 @@ int choose_group(const mtgpu_ctx *c, uint64_t n_records, uint32_t n_frames, int 
     //   40-byte records on shared tiles (1080p 1.3 MB frames, 326 KB frames): nothing or a loss — they stay at one.
     // Only where every workgroup slot of the chip is still filled twice over afterwards.
     const uint64_t per_cu = c->plan.lds_bytes <= 40 * 1024 ? 4u : (c->plan.lds_bytes <= 80 * 1024 ? 2u : 1u);
-    if (g == 1 && c->k.bands == 1 && rec_bytes == MT_COMPACT_BYTES && c->k.prefetch && avg <= (2ull << 20) &&
+    if (g == 1 && c->k.bands == 1 && rec_bytes == MT_COMPACT_BYTES && avg <= (2ull << 20) &&
         (uint64_t)n_frames >= cus * per_cu * 4ull)
       g = 2;
   }
@@ -497,7 +471,6 @@ int launch_scan_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uin
   L.rec_bytes = rec_bytes;
   L.lds_max = c->lds_max;
   L.device = c->device;
-  L.cu_count = c->plan.cu_count;
   L.mv = static_cast<const unsigned char *>(d_mv);
   L.n_records = n_records;
   L.rebase = rebase;
@@ -516,7 +489,6 @@ int launch_scan_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uin
   if ((uint64_t)n_frames * (uint64_t)L.k.slices >= (1ull << 32))
     return fail(MT_ERR_INVALID, "%u frames x %d slices: work items must stay below 2^32 per call", n_frames, L.k.slices);
   L.block = c->plan.block_threads;
-  L.variant = c->variant;
   L.item_chunk = (unsigned long long)c->item_chunk;
   L.lds_bytes = c->plan.lds_bytes;
   if (c->wide_lds_bytes > c->plan.lds_bytes &&
@@ -528,7 +500,7 @@ int launch_scan_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uin
   // several frames per workgroup: their list entries are parked in LDS behind the tile (scan_kernels.hip, stage_items)
   L.k.stage_word = 0;
   if (L.k.group > 1) {
-    const int at = (L.lds_bytes + 16 + 31) & ~31;             // (+16: the experiments build's ticket word sits right behind the tile)
+    const int at = (L.lds_bytes + 31) & ~31;
     if (at + mtgpu::kStageBytes <= c->lds_max) {
       L.k.stage_word = at / 4;
       L.lds_bytes = at + mtgpu::kStageBytes;
@@ -536,7 +508,6 @@ int launch_scan_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uin
       L.k.group = 1;                                          // a tile that fills LDS to the last 2 KB: one frame per workgroup
     }
   }
-  if (c->min_lds_kb > 0) L.lds_bytes = std::max(L.lds_bytes, std::min(c->min_lds_kb * 1024, c->lds_max));
   L.stream = st;
   // launch scratch, one stream-ordered block: [work list + planning counts | spill queue or slice tiles + tickets]
   // the caller's own block for the work list (a pipe's batch), if it is large enough: the pool then serves only
@@ -602,12 +573,10 @@ namespace mtgpu {
 // (the host copy-out loop, pack_records, lives in pack_simd.cpp: a plain host TU with per-CPU dispatch)
 int ctx_device(const mtgpu_ctx *c) { return c->device; }
 // A stream for one staging batch from the context's pool (created on first use of its slot; the caller has made
-// the context's device current), or nullptr when pooling is off or the creation failed (the batch then creates
-// a stream of its own).
+// the context's device current), or nullptr when the creation failed (the batch then creates a stream of its own).
 hipStream_t ctx_pipe_stream(mtgpu_ctx *c) {
-  if (c->n_pipe_streams <= 0) return nullptr;
   std::lock_guard<std::mutex> lock(c->pipe_mu);
-  const unsigned slot = c->pipe_rr++ % (unsigned)c->n_pipe_streams;
+  const unsigned slot = c->pipe_rr++ % (unsigned)mtgpu_ctx::kMaxPipeStreams;
   if (!c->pipe_streams[slot] &&
       hipStreamCreateWithFlags(&c->pipe_streams[slot], hipStreamNonBlocking) != hipSuccess) {
     c->pipe_streams[slot] = nullptr;
@@ -639,7 +608,7 @@ extern "C" int mtgpu_debug_set_phase_times(void *p) {      // developer build on
 extern "C" {
 
 const char *mtgpu_version(void) {
-  return mtgpu::kExperiments ? "mtgpu 0.6 (gfx950 MV scan + segment merge) +experiments" : "mtgpu 0.6 (gfx950 MV scan + segment merge)";
+  return "mtgpu 0.6 (gfx950 MV scan + segment merge)";
 }
 
 const char *mtgpu_last_error(void) { return g_err; }

@@ -15,18 +15,16 @@
 //   scalar     one 8-byte load and store per record (the round-3 loop).
 // The destination is pinned staging that the GPU reads over PCIe next; it is never read by the CPU
 // again, so the vector loops write it with NON-TEMPORAL full-line stores (no read-for-ownership of
-// the destination line, no staging in the cache hierarchy); MTGPU_PACK_NT=0 selects ordinary
-// stores, MTGPU_PACK=scalar|avx2|avx512 pins the loop, MTGPU_PACK_PREFETCH=<bytes> sets the
-// software-prefetch distance on the source (0 = off).  Head records are packed one by one until the
+// the destination line, no staging in the cache hierarchy) and issue no software prefetch;
+// MTGPU_PACK=scalar|avx2|avx512 pins the loop.  pack_records_with selects ordinary stores and a
+// software-prefetch distance on the source explicitly.  Head records are packed one by one until the
 // destination sits on a 64-byte line.
 #include <immintrin.h>
 
 #include <cstdint>
 #include <cstdlib>
-#include <algorithm>
 #include <cstring>
 
-#include "knobs.h"
 #include "pack_simd.h"
 
 namespace mtgpu {
@@ -130,12 +128,6 @@ __attribute__((target("avx512f,avx512bw"))) void pack_avx512(const unsigned char
   pack_scalar(mv + i * kRec, n - i, out + i * kOut);
 }
 
-struct Choice {
-  int impl = MT_PACK_SCALAR;
-  bool nt = true;
-  uint64_t prefetch = 0;
-};
-
 bool cpu_has(int impl) {
   switch (impl) {
     case MT_PACK_SCALAR: return true;
@@ -145,21 +137,18 @@ bool cpu_has(int impl) {
   }
 }
 
-const Choice &choice() {          // read once; thread-safe (function-local static)
-  static const Choice c = [] {
-    Choice ch;
+int choice() {                    // the loop, read once; thread-safe (function-local static)
+  static const int impl = [] {
     __builtin_cpu_init();
-    ch.impl = cpu_has(MT_PACK_AVX512) ? MT_PACK_AVX512 : cpu_has(MT_PACK_AVX2) ? MT_PACK_AVX2 : MT_PACK_SCALAR;
+    int ch = cpu_has(MT_PACK_AVX512) ? MT_PACK_AVX512 : cpu_has(MT_PACK_AVX2) ? MT_PACK_AVX2 : MT_PACK_SCALAR;
     if (const char *e = std::getenv("MTGPU_PACK")) {
       const int want = !std::strcmp(e, "scalar") ? MT_PACK_SCALAR : !std::strcmp(e, "avx2") ? MT_PACK_AVX2
                        : !std::strcmp(e, "avx512") ? MT_PACK_AVX512 : -1;
-      if (want > 0 && cpu_has(want)) ch.impl = want;     // a loop this CPU cannot run is never selected
+      if (want > 0 && cpu_has(want)) ch = want;          // a loop this CPU cannot run is never selected
     }
-    ch.nt = exp_int("MTGPU_PACK_NT", 1) != 0;                                  // experiments build only
-    ch.prefetch = (uint64_t)std::max(0, exp_int("MTGPU_PACK_PREFETCH", 0));    // experiments build only
     return ch;
   }();
-  return c;
+  return impl;
 }
 
 }  // namespace
@@ -175,11 +164,10 @@ int pack_records_with(int impl_flags, const unsigned char *mv, uint64_t n, unsig
   return 0;
 }
 
-int pack_selected() { const Choice &c = choice(); return c.impl | (c.nt && c.impl != MT_PACK_SCALAR ? MT_PACK_NT : 0); }
+int pack_selected() { const int impl = choice(); return impl | (impl != MT_PACK_SCALAR ? MT_PACK_NT : 0); }
 
 void pack_records(const unsigned char *mv, uint64_t n, unsigned char *out) {
-  const Choice &c = choice();
-  (void)pack_records_with(c.impl | (c.nt ? MT_PACK_NT : 0), mv, n, out, c.prefetch);
+  (void)pack_records_with(choice() | MT_PACK_NT, mv, n, out, 0);
 }
 
 }  // namespace mtgpu

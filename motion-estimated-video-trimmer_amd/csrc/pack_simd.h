@@ -7,7 +7,7 @@
 
 namespace mtgpu {
 // bytes 6..13 of each 40-byte record -> 8-byte compact records, with the loop chosen for this CPU
-// (MTGPU_PACK / MTGPU_PACK_NT / MTGPU_PACK_PREFETCH override, read once).
+// (MTGPU_PACK overrides, read once): non-temporal stores, no software prefetch.
 void pack_records(const unsigned char *mv, uint64_t n, unsigned char *out);
 // the same with an explicit loop: impl_flags = MT_PACK_SCALAR | MT_PACK_AVX2 | MT_PACK_AVX512, optionally
 // | MT_PACK_NT; prefetch = software-prefetch distance on the source in bytes (0 = none).

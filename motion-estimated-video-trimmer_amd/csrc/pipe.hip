@@ -35,7 +35,6 @@
 #include <vector>
 
 #include "api_internal.h"
-#include "knobs.h"
 #include "pack_simd.h"
 
 struct mtgpu_batch {
@@ -86,8 +85,6 @@ struct mtgpu_pipe {
   mtgpu_ctx *ctx = nullptr;
   int rec_bytes = MT_COMPACT_BYTES;
   bool zero_copy = false;
-  bool blocking_events = false;  // MTGPU_EVENT_BLOCKING=1: collect sleeps on the batch's event instead of polling it
-  bool eager_pin = false;        // MTGPU_PIPE_EAGER=1: pin every batch at creation (round 3 behaviour)
   long inject_submit_fail = 0;   // MTGPU_INJECT_SUBMIT_FAIL=k (tests): the k-th submit fails after its copies were queued
   long inject_collect_fail = 0;  // MTGPU_INJECT_COLLECT_FAIL=k (tests): the k-th collect's event wait "fails";
                                  // negative: its stream drain "fails" as well (the batch is poisoned)
@@ -220,8 +217,7 @@ int alloc_batch(mtgpu_batch **out, mtgpu_pipe *p, uint64_t max_records, uint32_t
   }
   // system-scope release at the event: the flag bytes a zero-copy scan wrote into pinned memory
   // are visible to the host thread that waits on it
-  PIPE_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming | hipEventReleaseToSystem |
-                                                 (p->blocking_events ? hipEventBlockingSync : 0u)));
+  PIPE_TRY(hipEventCreateWithFlags(&b->done, hipEventDisableTiming | hipEventReleaseToSystem));
   if (pin_now) {
     rc = pin_block_timed(p, b, max_records);
     if (rc != MT_OK) goto bad;
@@ -266,8 +262,6 @@ int mtgpu_pipe_create_layout(mtgpu_ctx *ctx, uint64_t max_records_per_batch, uin
   p->ctx = ctx;
   p->rec_bytes = (layout & MT_LAYOUT_AOS40) ? MT_MV_BYTES : MT_COMPACT_BYTES;
   p->zero_copy = (layout & MT_LAYOUT_ZERO_COPY) != 0;
-  p->blocking_events = mtgpu::exp_int("MTGPU_EVENT_BLOCKING", 0) != 0;     // experiments build only
-  p->eager_pin = mtgpu::exp_int("MTGPU_PIPE_EAGER", 0) != 0;                // experiments build only
   if (const char *v = std::getenv("MTGPU_INJECT_SUBMIT_FAIL")) p->inject_submit_fail = std::atol(v);
   if (const char *v = std::getenv("MTGPU_INJECT_GROW_FAIL")) p->inject_grow_fail = std::atol(v) != 0;
   if (const char *v = std::getenv("MTGPU_INJECT_COLLECT_FAIL")) p->inject_collect_fail = std::atol(v);
@@ -275,7 +269,7 @@ int mtgpu_pipe_create_layout(mtgpu_ctx *ctx, uint64_t max_records_per_batch, uin
   for (int i = 0; i < n_buffers; ++i) {
     mtgpu_batch *b = nullptr;
     // the first batch is pinned here (the caller is about to fill it), the others when they are first acquired
-    int rc = alloc_batch(&b, p, max_records_per_batch, max_frames_per_batch, i == 0 || p->eager_pin);
+    int rc = alloc_batch(&b, p, max_records_per_batch, max_frames_per_batch, i == 0);
     if (rc != MT_OK) {
       char keep[512];
       std::snprintf(keep, sizeof keep, "%s", mtgpu_last_error());

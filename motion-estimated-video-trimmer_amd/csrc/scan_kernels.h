@@ -28,10 +28,6 @@ struct ScanK {
   int group;               // consecutive work items per workgroup (>= 1; > 1 only with slices == 1)
   int stage_word;          // group > 1: LDS word (32-byte aligned offset behind the tile) where the workgroup parks the list
                            // entries of its 2nd .. group-th frame: 8 words each, kStageBytes in all
-  int align_lines;         // 40-byte records: peel < 16 head records so that the stream starts on a 128-byte line
-  int prefetch;            // compact records, group > 1: issue the next frame's first step before this frame's cluster test
-  int resident;            // experiments build only: > 0 = that many resident workgroups per CU pull work items with tickets
-                           // (one agent-scope atomic per k.group items) instead of one workgroup per k.group items
   int sys_flags;           // flags do not live in device memory (pinned host memory: the pipe's zero-copy staging, a caller's
                            // hipHostMalloc'ed buffer): result bytes leave with system-scope write-through stores
 };
@@ -62,9 +58,9 @@ inline unsigned int plan_blocks(unsigned int n_frames) {
   return (unsigned int)(((unsigned long long)n_frames + ch - 1ull) / ch);
 }
 // Launch scratch of the plan: the work list (n_frames + 1 items: the last one is always kNoFrame), one count per
-// planning block, the ticket word of the resident form.
+// planning block.
 inline size_t plan_scratch_bytes(unsigned int n_frames) {
-  return sizeof(WorkItem) * ((size_t)n_frames + 1u) + sizeof(unsigned int) * ((size_t)plan_blocks(n_frames) + 4u);
+  return sizeof(WorkItem) * ((size_t)n_frames + 1u) + sizeof(unsigned int) * (size_t)plan_blocks(n_frames);
 }
 
 constexpr int kStageBytes = 64 * 32;     // LDS behind the tile for the parked entries of a grouped workgroup (group <= 64)
@@ -82,10 +78,8 @@ struct ScanLaunch {
   void *plan_ws;                // plan_scratch_bytes(n_frames), 32-byte aligned: work list + planning counts
   unsigned long long rebase;    // records [frame_off[f], frame_off[f + 1]) live at mv + (frame_off[f] - rebase) * rec_bytes
                                 // (a host-pointer call copies only the window its offsets span); <= n_records
-  int cu_count;
   ScanK k;
   int block;
-  int variant;             // experiment knob (MTGPU_VARIANT), 0 = shipped kernel
   unsigned long long item_chunk;  // WORKGROUPS per launch (0 = 2^30; MTGPU_ITEM_CHUNK shrinks it for tests); a workgroup scans k.group items
   int lds_bytes;
   int lds_max;             // device limit of dynamic LDS per workgroup (set once per kernel instantiation)

@@ -53,7 +53,6 @@
 #include <algorithm>
 #include <atomic>
 
-#include "knobs.h"
 #include "scan_kernels.h"
 
 namespace mtgpu {
@@ -64,21 +63,10 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // Bytes 4..15 of a record: d.x = w | h<<8 | src_x<<16, d.y = src_y | dst_x<<16,
 // d.z = dst_y | pad<<16   (layout: include/mt_types.h, mt_mv).
-typedef u32x4 u32x4_a8 __attribute__((aligned(8)));
 
-// VAR bit1: 16-byte load of bytes 0..15 instead of 12 bytes at +4; bit2: default cache policy
-// instead of the streaming (nt) hint.  Experiment knobs (MTGPU_VARIANT), results in DESIGN.md.
-template <int VAR>
+// 12 bytes at +4 with the streaming (nt) hint.
 __device__ __forceinline__ u32x3 load_fields(const unsigned char *rec) {
-  if constexpr ((VAR & 2) != 0) {
-    u32x4 q;
-    if constexpr ((VAR & 4) != 0) q = *reinterpret_cast<const u32x4_a8 *>(rec);
-    else q = __builtin_nontemporal_load(reinterpret_cast<const u32x4_a8 *>(rec));
-    return (u32x3){q.y, q.z, q.w};
-  } else {
-    if constexpr ((VAR & 4) != 0) return *reinterpret_cast<const u32x3_a4 *>(rec + 4);
-    else return __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4 *>(rec + 4));
-  }
+  return __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4 *>(rec + 4));
 }
 
 // Compact record (REC 8): src_x | src_y << 16, dst_x | dst_y << 16 — bytes 6..13 of an
@@ -86,27 +74,23 @@ __device__ __forceinline__ u32x3 load_fields(const unsigned char *rec) {
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef u32x2 u32x2_a8 __attribute__((aligned(8)));
 
-template <int VAR>
 __device__ __forceinline__ u32x2 load_compact(const unsigned char *rec) {
-  if constexpr ((VAR & 4) != 0) return *reinterpret_cast<const u32x2_a8 *>(rec);
-  else return __builtin_nontemporal_load(reinterpret_cast<const u32x2_a8 *>(rec));
+  return __builtin_nontemporal_load(reinterpret_cast<const u32x2_a8 *>(rec));
 }
 
 typedef u32x4 u32x4_a16 __attribute__((aligned(16)));
 
-template <int VAR>
 __device__ __forceinline__ u32x4 load_pair(const unsigned char *two_records) {   // 16-byte aligned
-  if constexpr ((VAR & 4) != 0) return *reinterpret_cast<const u32x4_a16 *>(two_records);
-  else return __builtin_nontemporal_load(reinterpret_cast<const u32x4_a16 *>(two_records));
+  return __builtin_nontemporal_load(reinterpret_cast<const u32x4_a16 *>(two_records));
 }
 
 template <int REC> struct RawOf { typedef u32x3 type; };
 template <> struct RawOf<8> { typedef u32x2 type; };
 
-template <int VAR, int REC>
+template <int REC>
 __device__ __forceinline__ typename RawOf<REC>::type load_rec(const unsigned char *rec) {
-  if constexpr (REC == 8) return load_compact<VAR>(rec);
-  else return load_fields<VAR>(rec);
+  if constexpr (REC == 8) return load_compact(rec);
+  else return load_fields(rec);
 }
 
 struct MvFields { int src_x, src_y, dst_x, dst_y; };
@@ -533,11 +517,10 @@ __device__ __forceinline__ void vote(const MvFields m, const ScanK &k, int t0, i
   }
 }
 
-// Compact records: how many records at the start of a frame's array are scanned one by one so that the
-// 16-byte pair stream starts on a 128-byte line (align != 0; < 16 records) or at least on a 16-byte boundary.
-__device__ __forceinline__ unsigned long long compact_head(const unsigned char *base, unsigned long long n, int align) {
-  const unsigned long long a = (unsigned long long)(uintptr_t)base;
-  unsigned long long h = align ? (((0ull - a) & 127ull) >> 3) : ((a >> 3) & 1ull);
+// Compact records: how many records at the start of a frame's array (< 16) are scanned one by one so that the
+// 16-byte pair stream starts on a 128-byte line.
+__device__ __forceinline__ unsigned long long compact_head(const unsigned char *base, unsigned long long n) {
+  const unsigned long long h = ((0ull - (unsigned long long)(uintptr_t)base) & 127ull) >> 3;
   return h < n ? h : n;
 }
 
@@ -619,7 +602,7 @@ __device__ __forceinline__ unsigned int item_entry(unsigned int item, int slices
 // One work item (the list entry `me`, or a slice of it) by one workgroup.  `has_next`: the same workgroup scans
 // item + 1 (the list entry parked at `stage_next`: readable after this item's first barrier) right after this one.
 // Frames without side data (:219-221) never get here: plan_scatter_kernel has answered them.
-template <int BLOCK, int UNROLL, int FB, int MODE, int VAR, int REC, bool SPILL>
+template <int BLOCK, int UNROLL, int FB, int MODE, int REC, bool SPILL>
 __device__ __forceinline__ void scan_item(
     const unsigned char *__restrict__ mv, const WorkItem me, const unsigned int *stage_next,
     const unsigned int item, const ScanK &k, unsigned char *__restrict__ flags,
@@ -689,11 +672,11 @@ __device__ __forceinline__ void scan_item(
           // algorithmic bytes).  40 h = -start (mod 128) has a solution h < 16 whenever the start is 8-byte
           // aligned (5 * 13 = 1 mod 16): the first h records go to lanes 0..h-1, the streams start on a line.
           const unsigned int r = (unsigned int)((uintptr_t)base & 127u);
-          if (k.align_lines && (r & 7u) == 0u) {
+          if ((r & 7u) == 0u) {
             unsigned long long h = (unsigned long long)((13u * ((16u - (r >> 3)) & 15u)) & 15u);
             h = h < n ? h : n;
             if ((unsigned long long)tid < h)
-              vote<FB, MODE, SPILL>(decode(load_rec<VAR, REC>(base + (unsigned long long)tid * REC)), k, t0, t1, cnt, sq);
+              vote<FB, MODE, SPILL>(decode(load_rec<REC>(base + (unsigned long long)tid * REC)), k, t0, t1, cnt, sq);
             base += h * (unsigned long long)REC;
             n -= h;
           }
@@ -707,13 +690,13 @@ __device__ __forceinline__ void scan_item(
           // to cover the HBM latency (measured 4.96 TB/s of compact bytes on 1080p).  The pair
           // stream starts at the first record on a 128-byte line (compact_head: up to 15 head records go to
           // lanes 0..14, so that a wave instruction covers exactly 8 lines); lane 0 takes an odd last record.
-          const unsigned long long head = compact_head(base, n, k.align_lines);
+          const unsigned long long head = compact_head(base, n);
           const unsigned char *pbase = base + head * 8ull;
           const unsigned long long np = (n - head) >> 1;            // pairs
           if ((unsigned long long)tid < head)
-            vote<FB, MODE, SPILL>(decode(load_compact<VAR>(base + (unsigned long long)tid * 8ull)), k, t0, t1, cnt, sq);
+            vote<FB, MODE, SPILL>(decode(load_compact(base + (unsigned long long)tid * 8ull)), k, t0, t1, cnt, sq);
           if (tid == 0 && ((n - head) & 1ull) != 0ull)
-            vote<FB, MODE, SPILL>(decode(load_compact<VAR>(base + (n - 1ull) * 8ull)), k, t0, t1, cnt, sq);
+            vote<FB, MODE, SPILL>(decode(load_compact(base + (n - 1ull) * 8ull)), k, t0, t1, cnt, sq);
           unsigned long long p = tid;
           if (ns.have) {                       // this frame's first step (ns.frame == f, checked on entry) was issued during
             ns.have = false;                   // the previous frame's cluster test
@@ -727,7 +710,7 @@ __device__ __forceinline__ void scan_item(
           for (; p + LAST < np; p += STEP) {
             u32x4 d[UNROLL];
 #pragma unroll
-            for (int u = 0; u < UNROLL; ++u) d[u] = load_pair<VAR>(pbase + (p + (unsigned long long)u * BLOCK) * 16ull);
+            for (int u = 0; u < UNROLL; ++u) d[u] = load_pair(pbase + (p + (unsigned long long)u * BLOCK) * 16ull);
             __builtin_amdgcn_sched_barrier(0);   // every load of the step is issued before the first one is consumed
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
@@ -744,7 +727,7 @@ __device__ __forceinline__ void scan_item(
             for (int u = 0; u < UNROLL; ++u) {
               const unsigned long long q = p + (unsigned long long)u * BLOCK;
               ok[u] = q < np;
-              d[u] = ok[u] ? load_pair<VAR>(pbase + q * 16ull) : (u32x4){0u, 0u, 0u, 0u};
+              d[u] = ok[u] ? load_pair(pbase + q * 16ull) : (u32x4){0u, 0u, 0u, 0u};
             }
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u)
@@ -754,36 +737,12 @@ __device__ __forceinline__ void scan_item(
               }
           }
           i = n;                                                    // nothing left for the generic tail loop
-        } else if constexpr ((VAR & 8) != 0) {
-          // software-pipelined: the next batch of loads is issued before this batch is consumed
-          Raw cur[UNROLL], nxt[UNROLL];
-          bool have = i + LAST < n;
-          if (have) {
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) cur[u] = load_rec<VAR, REC>(base + (i + (unsigned long long)u * BLOCK) * REC);
-          }
-          while (have) {
-            const unsigned long long j = i + STEP;
-            const bool more = j + LAST < n;
-            if (more) {
-#pragma unroll
-              for (int u = 0; u < UNROLL; ++u) nxt[u] = load_rec<VAR, REC>(base + (j + (unsigned long long)u * BLOCK) * REC);
-            }
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) vote<FB, MODE, SPILL>(decode(cur[u]), k, t0, t1, cnt, sq);
-            if (more) {
-#pragma unroll
-              for (int u = 0; u < UNROLL; ++u) cur[u] = nxt[u];
-            }
-            i = j;
-            have = more;
-          }
         } else {
           // main body: UNROLL independent loads in flight per lane
           for (; i + LAST < n; i += STEP) {
             Raw d[UNROLL];
 #pragma unroll
-            for (int u = 0; u < UNROLL; ++u) d[u] = load_rec<VAR, REC>(base + (i + (unsigned long long)u * BLOCK) * REC);
+            for (int u = 0; u < UNROLL; ++u) d[u] = load_rec<REC>(base + (i + (unsigned long long)u * BLOCK) * REC);
             // (the scheduler sinks loads 2..UNROLL below the wait for load 1; forcing them up front with
             //  a sched_barrier measured -1..-2 % here, +7 % in the compact loop above: left as it is)
 #pragma unroll
@@ -800,7 +759,7 @@ __device__ __forceinline__ void scan_item(
           for (int u = 0; u < TU; ++u) {
             const unsigned long long q = i + (unsigned long long)u * BLOCK;
             ok[u] = q < n;
-            if (ok[u]) d[u] = load_rec<VAR, REC>(base + q * REC);
+            if (ok[u]) d[u] = load_rec<REC>(base + q * REC);
           }
 #pragma unroll
           for (int u = 0; u < TU; ++u)
@@ -815,13 +774,13 @@ __device__ __forceinline__ void scan_item(
           const bool sdn = nx.f != kNoFrame;
           const unsigned char *nb = mv + a * 8ull;
           const unsigned long long nn = b - a;
-          const unsigned long long nhead = compact_head(nb, nn, k.align_lines);
+          const unsigned long long nhead = compact_head(nb, nn);
           const unsigned long long nnp = (nn - nhead) >> 1;
           if (sdn && nnp >= (unsigned long long)UNROLL * BLOCK) {     // the whole first step lies inside the frame: uniform
             const unsigned char *npb = nb + nhead * 8ull;
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u)
-              ns.d[u] = load_pair<VAR>(npb + ((unsigned long long)tid + (unsigned long long)u * BLOCK) * 16ull);
+              ns.d[u] = load_pair(npb + ((unsigned long long)tid + (unsigned long long)u * BLOCK) * 16ull);
             ns.have = true;
             ns.frame = nx.f;
           }
@@ -1028,55 +987,32 @@ __device__ __forceinline__ void scan_item(
 // The grid is sized for "every frame has side data"; the workgroups past the end of the list find a kNoFrame entry
 // and leave — all of them at the END of the grid, after the last workgroup with work, whatever the stream's key-frame
 // period is.
-template <int BLOCK, int UNROLL, int FB, int MODE, int VAR, int REC, bool SPILL>
+template <int BLOCK, int UNROLL, int FB, int MODE, int REC, bool SPILL>
 __global__ __launch_bounds__(BLOCK) void scan_frames_kernel(
     const unsigned char *__restrict__ mv, const WorkItem *__restrict__ work,
     unsigned int item0, unsigned int n_items, ScanK k, unsigned char *__restrict__ flags,
-    unsigned int *spill_q, unsigned int *slice_ws, unsigned int *tickets, unsigned int *next_ticket) {
+    unsigned int *spill_q, unsigned int *slice_ws, unsigned int *tickets) {
   extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
   NextStep<UNROLL> ns;
   ns.have = false;
   ns.frame = 0u;
-  unsigned int first = item0 + blockIdx.x * (unsigned int)k.group;
-  unsigned int nextv = 0u;
-  unsigned int *slot = lds + (k.cnt_words + 2 * k.mask_rows * k.W + 4);       // (resident form: one word past the kernel's own LDS use)
-  const bool resident = kExperiments && k.resident > 0;
-  if (resident && threadIdx.x == 0)
-    nextv = __hip_atomic_fetch_add(next_ticket, (unsigned int)k.group, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (;;) {
-    if (resident) {
-      // A/B form (experiments build, MTGPU_RESIDENT = workgroups per CU): a fixed grid of workgroups pulls k.group
-      // items at a time with one agent-scope atomic; the next ticket is on its way while the current items are
-      // scanned.  The loop ends for every workgroup: tickets only grow, and the first one at or past n_items (or
-      // the end of the list) is the last this workgroup takes.
-      __syncthreads();
-      if (threadIdx.x == 0) *slot = nextv;
-      __syncthreads();
-      first = *slot;
-      if (first < n_items && threadIdx.x == 0)
-        nextv = __hip_atomic_fetch_add(next_ticket, (unsigned int)k.group, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (first >= n_items) return;
-    // the first entry is asked for before anything else is set up: its latency overlaps the kernel's scalar prologue;
-    // a workgroup that owns several frames (then slices == 1: items are list entries) fetches the others now, too
-    WorkItem me = load_item(work, item_entry<SPILL>(first, k.slices));
-    unsigned int *stage = lds + k.stage_word;
-    if (k.group > 1) {
-      if (resident) __syncthreads();                          // (the previous ticket's last reads of the staged entries)
-      stage_items(work, first, n_items, k.group, stage);      // published by the first frame's first barrier
-    }
-    for (int g = 0; g < k.group; ++g) {
-      const unsigned int item = first + (unsigned int)g;
-      if (item >= n_items || me.f == kNoFrame) return;       // kNoFrame: the list has ended, every later item is past its end too
-      const bool more = (g + 1 < k.group) && (item + 1u < n_items);
-      // (no barrier between items: every LDS read of an item precedes its last barrier, and the
-      //  next item's writes start with its own zeroing)
-      scan_item<BLOCK, UNROLL, FB, MODE, VAR, REC, SPILL>(mv, me, stage + 8u * ((unsigned int)g + 1u), item, k, flags, spill_q,
-                                                           slice_ws, tickets, lds, ns, more && k.prefetch);
-      if (!more) break;
-      me = staged_item(stage, (unsigned int)g + 1u);            // (parked before this workgroup's first barrier)
-    }
-    if (!resident) return;
+  const unsigned int first = item0 + blockIdx.x * (unsigned int)k.group;
+  if (first >= n_items) return;
+  // the first entry is asked for before anything else is set up: its latency overlaps the kernel's scalar prologue;
+  // a workgroup that owns several frames (then slices == 1: items are list entries) fetches the others now, too
+  WorkItem me = load_item(work, item_entry<SPILL>(first, k.slices));
+  unsigned int *stage = lds + k.stage_word;
+  if (k.group > 1) stage_items(work, first, n_items, k.group, stage);   // published by the first frame's first barrier
+  for (int g = 0; g < k.group; ++g) {
+    const unsigned int item = first + (unsigned int)g;
+    if (item >= n_items || me.f == kNoFrame) return;         // kNoFrame: the list has ended, every later item is past its end too
+    const bool more = (g + 1 < k.group) && (item + 1u < n_items);
+    // (no barrier between items: every LDS read of an item precedes its last barrier, and the
+    //  next item's writes start with its own zeroing)
+    scan_item<BLOCK, UNROLL, FB, MODE, REC, SPILL>(mv, me, stage + 8u * ((unsigned int)g + 1u), item, k, flags, spill_q,
+                                                   slice_ws, tickets, lds, ns, more);
+    if (!more) return;
+    me = staged_item(stage, (unsigned int)g + 1u);            // (parked before this workgroup's first barrier)
   }
 }
 
@@ -1117,8 +1053,7 @@ __global__ __launch_bounds__(kPlanBlock) void plan_count_kernel(
 __global__ __launch_bounds__(kPlanBlock) void plan_scatter_kernel(
     const unsigned long long *__restrict__ frame_off, const unsigned char *__restrict__ has_sd, unsigned long long n_records,
     unsigned long long rebase, unsigned int n_frames, unsigned int per,
-    const unsigned int *__restrict__ blk_cnt, WorkItem *__restrict__ work, unsigned char *__restrict__ flags, int sys_flags,
-    unsigned int *next_ticket) {
+    const unsigned int *__restrict__ blk_cnt, WorkItem *__restrict__ work, unsigned char *__restrict__ flags, int sys_flags) {
   constexpr unsigned int WAVES = kPlanBlock / 64u;
   __shared__ unsigned int wave_before[WAVES];    // frames with side data in the blocks before this one, as each wave counted them
   __shared__ unsigned int wave_cnt[2][WAVES];    // ... among this iteration's frames, per wave (double-buffered: one barrier per iteration)
@@ -1189,11 +1124,10 @@ __global__ __launch_bounds__(kPlanBlock) void plan_scatter_kernel(
     WorkItem it;
     it.r0 = it.r1 = 0ull; it.f = kNoFrame; it.pad[0] = it.pad[1] = it.pad[2] = 0u;
     work[n_frames] = it;                         // what the last frame's "next frame" read finds
-    *next_ticket = 0u;                           // (resident form, experiments build)
   }
 }
 
-static hipError_t launch_plan(const ScanLaunch &L, WorkItem *work, unsigned int *blk_cnt, unsigned int *next_ticket) {
+static hipError_t launch_plan(const ScanLaunch &L, WorkItem *work, unsigned int *blk_cnt) {
   const unsigned int per = plan_per(L.n_frames), blocks = plan_blocks(L.n_frames);
   const bool fused = blocks <= kPlanFused;       // (then per == 1)
   if (!fused) {
@@ -1203,7 +1137,7 @@ static hipError_t launch_plan(const ScanLaunch &L, WorkItem *work, unsigned int 
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(plan_scatter_kernel, dim3(blocks), dim3(kPlanBlock), 0, L.stream, L.frame_off, L.has_sd, L.n_records,
-                     L.rebase, L.n_frames, per, fused ? nullptr : blk_cnt, work, L.flags, L.k.sys_flags, next_ticket);
+                     L.rebase, L.n_frames, per, fused ? nullptr : blk_cnt, work, L.flags, L.k.sys_flags);
   return hipGetLastError();
 }
 
@@ -1229,9 +1163,9 @@ hipError_t launch_check_offsets(const unsigned long long *frame_off, unsigned in
 
 // ------------------------------------------------------------------ launchers
 
-template <int BLOCK, int FB, int MODE, int REC, bool SPILL, int UNROLL = 4, int VAR = 0>
+template <int BLOCK, int FB, int MODE, int REC, bool SPILL, int UNROLL = 4>
 static hipError_t launch_one(const ScanLaunch &L) {
-  auto kern = scan_frames_kernel<BLOCK, UNROLL, FB, MODE, VAR, REC, SPILL>;
+  auto kern = scan_frames_kernel<BLOCK, UNROLL, FB, MODE, REC, SPILL>;
   // Dynamic-LDS ceiling: set ONCE per instantiation and device to the device maximum (host
   // threads sharing an instantiation must not race each other with per-launch values).
   static std::atomic<unsigned long long> ready{0ull};
@@ -1244,43 +1178,19 @@ static hipError_t launch_one(const ScanLaunch &L) {
   }
   const unsigned long long items = (unsigned long long)L.n_frames * (unsigned long long)(SPILL ? 1 : L.k.slices);
   const unsigned long long group = (unsigned long long)(L.k.group > 0 ? L.k.group : 1);
-  WorkItem *work = static_cast<WorkItem *>(L.plan_ws);
-  unsigned int *next_ticket = reinterpret_cast<unsigned int *>(work + (size_t)L.n_frames + 1u) + plan_blocks(L.n_frames);
-  if (kExperiments && L.k.resident > 0) {
-    const unsigned long long want = (unsigned long long)(L.cu_count > 0 ? L.cu_count : 256) * (unsigned long long)L.k.resident;
-    const unsigned long long wgs = (items + group - 1) / group;
-    hipLaunchKernelGGL(kern, dim3((unsigned int)(wgs < want ? wgs : want)), dim3(BLOCK), L.lds_bytes + 16, L.stream, L.mv, work,
-                       0u, (unsigned int)items, L.k, L.flags, L.spill_q, L.slice_ws, L.tickets, next_ticket);
-    return hipGetLastError();
-  }
+  const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
   const unsigned long long chunk = L.item_chunk ? L.item_chunk : (1ull << 30);   // workgroups per launch: grid.x stays < 2^31
   for (unsigned long long i0 = 0; i0 < items; i0 += chunk * group) {
     const unsigned long long left = items - i0;
     const unsigned long long wgs = (left + group - 1) / group;
     const unsigned int n = (unsigned int)(wgs < chunk ? wgs : chunk);
     hipLaunchKernelGGL(kern, dim3(n), dim3(BLOCK), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0,
-                       (unsigned int)items, L.k, L.flags, L.spill_q, L.slice_ws, L.tickets, next_ticket);
+                       (unsigned int)items, L.k, L.flags, L.spill_q, L.slice_ws, L.tickets);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
-
-#ifdef MTGPU_EXPERIMENTS
-// Experiment variants of the ADD32 kernel on 40-byte records (MTGPU_VARIANT): bit0 UNROLL 8,
-// bit1 dwordx4 loads, bit2 no nt hint, bit3 software-pipelined loop.  Experiments build only.
-template <int BLOCK>
-static hipError_t launch_variant(const ScanLaunch &L) {
-  switch (L.variant & 15) {
-#define MT_VARIANT_CASE(v) case v: return launch_one<BLOCK, 32, MODE_ADD32, 40, false, ((v) & 1) ? 8 : 4, (v)>(L);
-    MT_VARIANT_CASE(1) MT_VARIANT_CASE(2) MT_VARIANT_CASE(3) MT_VARIANT_CASE(4) MT_VARIANT_CASE(5)
-    MT_VARIANT_CASE(6) MT_VARIANT_CASE(7) MT_VARIANT_CASE(8) MT_VARIANT_CASE(9) MT_VARIANT_CASE(10)
-    MT_VARIANT_CASE(11) MT_VARIANT_CASE(12) MT_VARIANT_CASE(13) MT_VARIANT_CASE(14) MT_VARIANT_CASE(15)
-#undef MT_VARIANT_CASE
-    default: return launch_one<BLOCK, 32, MODE_ADD32, 40, false>(L);
-  }
-}
-#endif
 
 template <int BLOCK, int REC, bool SPILL>
 static hipError_t launch_form(const ScanLaunch &L) {
@@ -1296,21 +1206,12 @@ static hipError_t launch_form(const ScanLaunch &L) {
   }
 }
 
-// Default build: the instantiations a plan can select — single tiles with 512 or 1024 threads, banded plans with
-// 1024 (make_plan, mtgpu_api.hip) — 36 kernels.  The experiments build adds 256-thread workgroups, 512-thread
-// banded ones and the MTGPU_VARIANT load variants (117 kernels, three times the compile time and code size).
+// The instantiations a plan can select — single tiles with 512 or 1024 threads, banded plans with 1024 (make_plan,
+// mtgpu_api.hip) — 36 kernels.
 template <int BLOCK>
 static hipError_t launch_block(const ScanLaunch &L) {
   const bool spill = L.k.bands > 1;
-#ifdef MTGPU_EXPERIMENTS
-  const int key = L.k.mode * 100 + L.k.fb;
-  if (L.rec_bytes == 40 && !spill && key == MODE_ADD32 * 100 + 32 && (L.variant & 15) != 0 && BLOCK != 1024)
-    return launch_variant<BLOCK>(L);
-  constexpr bool kSpillHere = true;
-#else
-  constexpr bool kSpillHere = BLOCK == 1024;
-#endif
-  if constexpr (kSpillHere) {
+  if constexpr (BLOCK == 1024) {
     if (spill) return L.rec_bytes == 8 ? launch_form<BLOCK, 8, true>(L) : launch_form<BLOCK, 40, true>(L);
   } else {
     if (spill) return hipErrorInvalidValue;
@@ -1339,15 +1240,12 @@ hipError_t launch_scan(const ScanLaunch &L) {
   {
     WorkItem *work = static_cast<WorkItem *>(L.plan_ws);
     unsigned int *blk_cnt = reinterpret_cast<unsigned int *>(work + (size_t)L.n_frames + 1u);
-    e = launch_plan(L, work, blk_cnt, blk_cnt + plan_blocks(L.n_frames));
+    e = launch_plan(L, work, blk_cnt);
     if (e != hipSuccess) return e;
   }
   // (profiling: the event between planning and scan)
   if (L.ev_planned && (e = hipEventRecord(L.ev_planned, L.stream)) != hipSuccess) return e;
   switch (L.block) {
-#ifdef MTGPU_EXPERIMENTS
-    case 256: e = launch_block<256>(L); break;
-#endif
     case 512: e = launch_block<512>(L); break;
     case 1024: e = launch_block<1024>(L); break;
     default: return hipErrorInvalidValue;

@@ -15,36 +15,13 @@ import mvtrim_amd as m  # noqa: E402
 from bench import make_spec  # noqa: E402
 from mvtrim_amd import synth  # noqa: E402
 
-VARIANTS_FINE = [("default", dict()), ("chunk64", dict(MTGPU_FORCE_CHUNK="64")), ("chunk128", dict(MTGPU_FORCE_CHUNK="128")),
-                 ("chunk64/b1024", dict(MTGPU_FORCE_CHUNK="64", MTGPU_FORCE_BLOCK="1024")),
-                 ("chunk32/b512", dict(MTGPU_FORCE_CHUNK="32", MTGPU_FORCE_BLOCK="512")),
-                 ("chunk160/b512", dict(MTGPU_FORCE_CHUNK="160", MTGPU_FORCE_BLOCK="512")),
-                 ("fb2", dict(MTGPU_FORCE_FB="2"))]
-VARIANTS_KERNEL = [("v%d" % v, dict(MTGPU_VARIANT=str(v))) for v in (0, 1, 2, 4, 8, 9, 10, 12, 3, 11, 6, 14)]
 VARIANTS_SLICES = [("auto", dict()), ("s1", dict(MTGPU_FORCE_SLICES="1")), ("s2", dict(MTGPU_FORCE_SLICES="2")),
                    ("s4", dict(MTGPU_FORCE_SLICES="4")), ("s8", dict(MTGPU_FORCE_SLICES="8"))]
-# row bands walked by one workgroup (spill queue): tile size / workgroup size (use with AB_VEC=4 on 4k_fine)
-VARIANTS_BANDS = [("auto", dict()), ("tile160", dict(MTGPU_BAND_LDS_KB="160")), ("tile160/b1024", dict(MTGPU_BAND_LDS_KB="160", MTGPU_FORCE_BLOCK="1024")),
-                  ("tile120/b1024", dict(MTGPU_BAND_LDS_KB="120", MTGPU_FORCE_BLOCK="1024")), ("tile80/b512", dict(MTGPU_FORCE_BLOCK="512")),
-                  ("tile80/b1024", dict(MTGPU_FORCE_BLOCK="1024")),
-                  ("tile53", dict(MTGPU_BAND_LDS_KB="53")), ("tile53/b512", dict(MTGPU_BAND_LDS_KB="53", MTGPU_FORCE_BLOCK="512")),
-                  ("tile40/b512", dict(MTGPU_BAND_LDS_KB="40", MTGPU_FORCE_BLOCK="512")),
-                  ("tile120", dict(MTGPU_BAND_LDS_KB="120"))]
-# one 160 KB tile vs two spill bands of <= 80 KB (use with AB_VEC=2 on 4k_fine)
-VARIANTS_TILE = [("single", dict()), ("bands80", dict(MTGPU_MAX_TILE_KB="80")),
-                 ("bands80/b512", dict(MTGPU_MAX_TILE_KB="80", MTGPU_FORCE_BLOCK="512")),
-                 ("bands53", dict(MTGPU_MAX_TILE_KB="53", MTGPU_BAND_LDS_KB="53"))]
 VARIANTS_GROUP = [("auto", dict()), ("g1", dict(MTGPU_GROUP="1")), ("g2", dict(MTGPU_GROUP="2")), ("g4", dict(MTGPU_GROUP="4")),
                   ("g8", dict(MTGPU_GROUP="8"))]
-# compact records: frames per workgroup x next-frame prefetch (use with AB_COMPACT=1)
-VARIANTS_PREFETCH = [("g1", dict(MTGPU_GROUP="1")), ("g2/pf", dict(MTGPU_GROUP="2")), ("g2/nopf", dict(MTGPU_GROUP="2", MTGPU_PREFETCH="0")),
-                     ("g4/pf", dict(MTGPU_GROUP="4")), ("g4/nopf", dict(MTGPU_GROUP="4", MTGPU_PREFETCH="0")),
+# compact records: frames per workgroup, each with the next-frame prefetch (use with AB_COMPACT=1)
+VARIANTS_PREFETCH = [("g1", dict(MTGPU_GROUP="1")), ("g2/pf", dict(MTGPU_GROUP="2")), ("g4/pf", dict(MTGPU_GROUP="4")),
                      ("g8/pf", dict(MTGPU_GROUP="8")), ("auto", dict())]
-# 40-byte records: streams start on a 128-byte line (head records peeled) or wherever the frame starts
-VARIANTS_ALIGN = [("aligned", dict()), ("unaligned", dict(MTGPU_ALIGN="0")), ("aligned2", dict()), ("unaligned2", dict(MTGPU_ALIGN="0"))]
-# workgroups per CU, capped through the LDS size of the launch (32-bit counters on a 1080p / 4K grid)
-VARIANTS_OCC = [("auto", dict()), ("lds40", dict(MTGPU_MIN_LDS_KB="40")), ("lds53", dict(MTGPU_MIN_LDS_KB="53")),
-                ("lds80", dict(MTGPU_MIN_LDS_KB="80")), ("lds160", dict(MTGPU_MIN_LDS_KB="160"))]
 VARIANTS = [("fb32", dict(MTGPU_FORCE_FB="32")), ("fb2", dict(MTGPU_FORCE_FB="2")),
             ("fb32/b512", dict(MTGPU_FORCE_FB="32", MTGPU_FORCE_BLOCK="512")),
             ("fb2/b512", dict(MTGPU_FORCE_FB="2", MTGPU_FORCE_BLOCK="512")),
@@ -87,12 +64,10 @@ def main():
             d_mv = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(dev).repeat(reps)[: int(off_big[-1]) * 8].contiguous()
             alg = 8 * int(off_big[-1]) + 9 * frames
         scanners = []
-        vset = {"fine": VARIANTS_FINE, "kernel": VARIANTS_KERNEL, "slices": VARIANTS_SLICES,
-                "bands": VARIANTS_BANDS, "tile": VARIANTS_TILE, "group": VARIANTS_GROUP, "occ": VARIANTS_OCC,
-                "prefetch": VARIANTS_PREFETCH, "align": VARIANTS_ALIGN}.get(os.environ.get("AB_SET"), VARIANTS)
+        vset = {"slices": VARIANTS_SLICES, "group": VARIANTS_GROUP,
+                "prefetch": VARIANTS_PREFETCH}.get(os.environ.get("AB_SET"), VARIANTS)
         for name, env in vset:
-            for k in ("MTGPU_FORCE_FB", "MTGPU_FORCE_BLOCK", "MTGPU_FORCE_CHUNK", "MTGPU_VARIANT", "MTGPU_FORCE_SLICES",
-                      "MTGPU_BAND_LDS_KB", "MTGPU_MAX_TILE_KB", "MTGPU_GROUP", "MTGPU_MIN_LDS_KB", "MTGPU_PREFETCH", "MTGPU_ALIGN"):
+            for k in ("MTGPU_FORCE_FB", "MTGPU_FORCE_BLOCK", "MTGPU_FORCE_SLICES", "MTGPU_GROUP"):
                 os.environ.pop(k, None)
             os.environ.update(env)
             try:

@@ -1,10 +1,9 @@
 #!/usr/bin/env python3
 """Scan rate against the key-frame period of the stream (frames WITHOUT side data every P frames), and on a ragged
-stream: the same records, cut into frames differently, scanned by up to three builds interleaved in ONE process —
+stream: the same records, cut into frames differently, scanned by these builds interleaved in ONE process —
     new    the library in the tree (work list: frames without side data never get a workgroup)
+    gN     the same library with MTGPU_GROUP=N, for every N in GOP_GROUPS (e.g. "1,2,8")
     prev   scripts/libmtgpu_prev.so, built from the previous round's commit (one workgroup per frame), when it exists
-    exp:K  motion-estimated-video-trimmer_amd/libmtgpu_experiments.so with MTGPU_RESIDENT=K (ticketed resident
-           workgroups, K per CU, over the same work list), for every K in GOP_RESIDENT (e.g. "2,4")
 Usage: gop_sweep.py [frames_with_records] [periods, comma separated; 0 = no key frames; r = ragged]
 The flags of every build are compared frame by frame for every case."""
 import ctypes as C
@@ -70,10 +69,6 @@ for spec_ in [x for x in os.environ.get("GOP_GROUPS", "").split(",") if x]:     
 prev = os.environ.get("GOP_PREV_LIB") or os.path.join(ROOT, "scripts", "libmtgpu_prev.so")
 if os.path.exists(prev) and os.environ.get("GOP_PREV", "1") != "0":
     builds.append(("prev", other_library(prev)))
-exp = os.path.join(ROOT, "motion-estimated-video-trimmer_amd", "libmtgpu_experiments.so")
-for k_ in [x for x in os.environ.get("GOP_RESIDENT", "").split(",") if x]:
-    if os.path.exists(exp):
-        builds.append((f"exp:{k_}", other_library(exp, {"MTGPU_RESIDENT": k_})))
 print("plan:", builds[0][1].plan, "| records", n_records, "| frames with records", M, flush=True)
 
 

@@ -20,10 +20,9 @@ def draw_head(rng, it):
               vectors_needed=int(rng.choice([1, 1, 2, 2, 3, 4, 6, 12, 255])),
               clusters_needed=int(rng.choice([1, 2, 2, 3, 10])),
               vertical_mask=float(rng.choice([0.0, 0.05, 0.2])))
-    # frames per workgroup (next-frame prefetch on compact records), line alignment: knobs read at create time
-    # (MTGPU_PREFETCH / MTGPU_ALIGN are honoured by the experiments build only)
-    knobs = {"MTGPU_GROUP": str(rng.choice(["", "", "2", "3", "8"])), "MTGPU_PREFETCH": str(rng.choice(["", "", "0"])),
-             "MTGPU_ALIGN": str(rng.choice(["", "", "0"]))}
+    # frames per workgroup (next-frame prefetch on compact records): a knob read at create time
+    knobs = {"MTGPU_GROUP": str(rng.choice(["", "", "2", "3", "8"]))}
+    rng.choice(["", "", "0"]), rng.choice(["", "", "0"])     # two retired knobs: drawn and dropped, the seeds stay valid
     return dict(w=w, h=h, kw=kw, knobs=knobs, force_fb=FORMS[it % len(FORMS)])
 
 

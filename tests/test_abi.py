@@ -148,29 +148,23 @@ def test_pack_records_known_answer():
     assert got.view(np.uint8).reshape(3, 8).tobytes() == raw[:, 6:14].tobytes()
 
 
-def test_every_environment_knob_is_in_the_headers_table():
-    """Every MTGPU_* variable the library and the C++ host layer read is listed in the class in which the code reads
-    it: supported knobs (env_int() / getenv, every build) in include/mtgpu.h "Environment"; experiment knobs (exp_int():
-    constants unless built with -DMTGPU_EXPERIMENTS) in csrc/knobs.h only — the product header does not carry them."""
+def test_every_environment_knob_is_in_the_one_headers_table():
+    """Every MTGPU_* variable the library and the C++ host layer read (env_int() / getenv) is listed in
+    include/mtgpu.h "Environment", and everything listed there is read.  There is one class of knobs: no
+    build-dependent exp_int() switch is left in the sources."""
     import re
     csrc = os.path.join(os.path.dirname(m.LIB_PATH), "csrc")
     files = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".cpp", ".h"))]
     files += [os.path.join(csrc, "host", f) for f in os.listdir(os.path.join(csrc, "host"))]
-    supported, experiments = set(), set()
+    supported = set()
     for path in files:
         text = open(path).read()
-        experiments |= set(re.findall(r'exp_int\("(MTGPU_[A-Z0-9_]+)"', text))
+        assert "exp_int(" not in text, path
         supported |= set(re.findall(r'(?:env_int|env_i|getenv)\("(MTGPU_[A-Z0-9_]+)"', text))
     header = open(os.path.join(ROOT, "include", "mtgpu.h")).read()
     table = header[header.index(" * Environment (read once"):header.index("#ifndef MTGPU_H")]
-    knobs = open(os.path.join(csrc, "knobs.h")).read()
-    exp_part = knobs[knobs.index("//    experiments   "):knobs.index("#pragma once")]
-    sup_part = table
-    listed = lambda part: set(re.findall(r"MTGPU_[A-Z0-9_]+", part.replace("MTGPU_INJECT_SUBMIT_FAIL / _GROW_FAIL / _COLLECT_FAIL",
-                                                                           "MTGPU_INJECT_SUBMIT_FAIL MTGPU_INJECT_GROW_FAIL MTGPU_INJECT_COLLECT_FAIL")))
-    assert experiments and supported and not (experiments & supported - {"MTGPU_FORCE_BLOCK"})
-    assert experiments <= listed(exp_part), sorted(experiments - listed(exp_part))
-    assert supported <= listed(sup_part) | {"MTGPU_LIBRARY"}, sorted(supported - listed(sup_part))
-    # nothing is advertised that no code reads (MTGPU_FORCE_BLOCK appears in both classes: 512 | 1024 always, 256 in the experiments build)
-    assert listed(exp_part) - {"MTGPU_FORCE_BLOCK"} <= experiments, sorted(listed(exp_part) - experiments)
-    assert listed(sup_part) <= supported, sorted(listed(sup_part) - supported)
+    listed = set(re.findall(r"MTGPU_[A-Z0-9_]+", table.replace("MTGPU_INJECT_SUBMIT_FAIL / _GROW_FAIL / _COLLECT_FAIL",
+                                                               "MTGPU_INJECT_SUBMIT_FAIL MTGPU_INJECT_GROW_FAIL MTGPU_INJECT_COLLECT_FAIL")))
+    assert supported
+    assert supported <= listed | {"MTGPU_LIBRARY"}, sorted(supported - listed)
+    assert listed <= supported, sorted(listed - supported)     # nothing is advertised that no code reads

@@ -23,7 +23,6 @@ from mvtrim_amd import dist as mdist
 from mvtrim_amd import synth
 
 import oracle_binding as ob
-from conftest import experiments_build
 from golden_cases import (build_mvs, id_of, load_filter_cases, load_hand_cases, load_merge_cases,
                           load_survey_segments, merge_case_ts)
 
@@ -833,10 +832,10 @@ def test_scan_under_reference_parsed_configs(gpu_scanner_factory):
 
 
 @pytest.mark.parametrize("layout", [m._abi.LAYOUT_COMPACT8 | m._abi.LAYOUT_ZERO_COPY, m._abi.LAYOUT_AOS40])
-def test_pipe_pins_staging_on_first_use(gpu_scanner_factory, monkeypatch, layout):
+def test_pipe_pins_staging_on_first_use(gpu_scanner_factory, layout):
     """Round 4: page-locking is the cost of creating a pipe (~0.2 ms per MiB, serialised across threads by the
     driver), so a pipe pins ONE batch at creation and every other batch when mtgpu_pipe_acquire first hands it
-    out; MTGPU_PIPE_EAGER=1 restores pin-everything-at-creation.  Results do not depend on it."""
+    out.  Results do not depend on it."""
     import ctypes as C
     p = ob.params_from_config(1920, 1080, vectors_needed=1)
     s = gpu_scanner_factory(p)
@@ -872,25 +871,13 @@ def test_pipe_pins_staging_on_first_use(gpu_scanner_factory, monkeypatch, layout
     st = stats(pipe)
     assert 2 <= st.pinned_batches <= 3 and st.pinned_bytes == st.pinned_batches * one
     pipe.close()
-    if not experiments_build():                  # MTGPU_PIPE_EAGER is an A/B knob: read by the experiments build only
-        return
-    monkeypatch.setenv("MTGPU_PIPE_EAGER", "1")
-    pipe = m.ScanPipe(s, 8160 * 4, 4, 3, layout=layout)
-    st = stats(pipe)
-    assert st.pinned_batches == 3 and st.pinned_bytes == 3 * one
-    for i in range(24):
-        fr = mv[int(off[i]):int(off[i + 1])]
-        pipe.feed(fr if sd[i] else None, float(pts[i]), tag=i)
-    assert [f for _, f, _ in pipe.drain()] == want.tolist()
-    pipe.close()
 
 
-def test_pipe_batches_run_on_the_contexts_stream_pool(gpu_scanner_factory, monkeypatch):
+def test_pipe_batches_run_on_the_contexts_stream_pool(gpu_scanner_factory):
     """Round 4: a pipe no longer creates a HIP stream per batch (3.5 ms each, serialised by the runtime — 192 of
     them were most of the 0.6 s a worker spent in mtgpu_pipe_create at 64 x 1); its batches take streams from a
     pool of 8 owned by the context.  Four pipes of 3 batches on one context: 8 pool streams + the context's own,
-    none owned by a pipe, results as before; MTGPU_PIPE_STREAMS=0 (read at mtgpu_create) gives every batch its
-    own stream again."""
+    none owned by a pipe, results as before."""
     import ctypes as C
     p = ob.params_from_config(1920, 1080, vectors_needed=1)
     lib = m.load_library()
@@ -903,21 +890,18 @@ def test_pipe_batches_run_on_the_contexts_stream_pool(gpu_scanner_factory, monke
         st = m._abi.PipeStatsC()
         m._abi.check(lib.mtgpu_pipe_get_stats(pipe._pipe, C.byref(st)))
         return st
-    for pooled in ((True, False) if experiments_build() else (True,)):     # MTGPU_PIPE_STREAMS: experiments build only
-        if not pooled:
-            monkeypatch.setenv("MTGPU_PIPE_STREAMS", "0")
-        s = gpu_scanner_factory(p)
-        pipes = [m.ScanPipe(s, 8160 * 3, 3, 3) for _ in range(4)]
-        for i in range(20):                                     # four interleaved "decoder threads"
-            fr = mv[int(off[i]):int(off[i + 1])]
-            for pp in pipes:
-                pp.feed(fr if sd[i] else None, float(pts[i]), tag=i)
+    s = gpu_scanner_factory(p)
+    pipes = [m.ScanPipe(s, 8160 * 3, 3, 3) for _ in range(4)]
+    for i in range(20):                                         # four interleaved "decoder threads"
+        fr = mv[int(off[i]):int(off[i + 1])]
         for pp in pipes:
-            assert [f for _, f, _ in pp.drain()] == want
-        assert [pipe_stats(pp).hip_streams for pp in pipes] == ([0] * 4 if pooled else [3] * 4)
-        assert s.stats()["hip_streams"] == (9 if pooled else 1)
-        for pp in pipes:
-            pp.close()
+            pp.feed(fr if sd[i] else None, float(pts[i]), tag=i)
+    for pp in pipes:
+        assert [f for _, f, _ in pp.drain()] == want
+    assert [pipe_stats(pp).hip_streams for pp in pipes] == [0] * 4
+    assert s.stats()["hip_streams"] == 9
+    for pp in pipes:
+        pp.close()
 
 
 @pytest.mark.parametrize("layout", [m._abi.LAYOUT_COMPACT8 | m._abi.LAYOUT_ZERO_COPY, m._abi.LAYOUT_AOS40 | m._abi.LAYOUT_ZERO_COPY,

@@ -11,7 +11,6 @@ import mvtrim_amd as m
 from mvtrim_amd import synth
 
 import oracle_binding as ob
-from conftest import experiments_build
 
 pytestmark = pytest.mark.gpu
 
@@ -1015,10 +1014,10 @@ def test_scan_frames_per_workgroup_grouping(gpu_scanner_factory, monkeypatch):
             assert np.array_equal(got, want), (w, g, "compact")
 
 
-def test_scan_line_aligned_streams(gpu_scanner_factory, monkeypatch):
+def test_scan_line_aligned_streams(gpu_scanner_factory):
     """The record streams start on a 128-byte line: up to 15 head records of every frame are scanned one by one
     (scan_kernels.hip, "Line alignment").  Frames whose first record sits at every possible offset inside a line
-    (40-byte records: 16 residues; compact: 16), frames shorter than their head, with the alignment on and off,
+    (40-byte records: 16 residues; compact: 16), frames shorter than their head,
     single-tile and banded plans, and voters placed exactly in the head and right behind it."""
     import torch
     rng = np.random.RandomState(5)
@@ -1051,13 +1050,10 @@ def test_scan_line_aligned_streams(gpu_scanner_factory, monkeypatch):
     rec = m.pack_records(b.mv)
     d_rec = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).cuda()
     d_off = torch.from_numpy(b.frame_off.astype(np.int64)).cuda()
-    for align in (("1", "0") if experiments_build() else ("1",)):     # MTGPU_ALIGN=0: experiments build only
-        for fb in (None, 2, 8):                                     # 32-bit single tile, packed, banded (spill queue)
-            monkeypatch.setenv("MTGPU_ALIGN", align)
-            s = gpu_scanner_factory(m.ScanParams.from_config(1920, 1080, vectors_needed=2, clusters_needed=1), force_fb=fb)
-            monkeypatch.delenv("MTGPU_ALIGN")
-            assert np.array_equal(s.check_frames(b), want), (align, fb)
-            assert np.array_equal(s.check_frames_device_compact(d_rec, d_off, None).cpu().numpy(), want), (align, fb, "compact")
+    for fb in (None, 2, 8):                                         # 32-bit single tile, packed, banded (spill queue)
+        s = gpu_scanner_factory(m.ScanParams.from_config(1920, 1080, vectors_needed=2, clusters_needed=1), force_fb=fb)
+        assert np.array_equal(s.check_frames(b), want), fb
+        assert np.array_equal(s.check_frames_device_compact(d_rec, d_off, None).cpu().numpy(), want), (fb, "compact")
 
 
 @pytest.mark.parametrize("grid", ["1080p", "4k"])
@@ -1066,7 +1062,7 @@ def test_compact_next_frame_prefetch(gpu_scanner_factory, monkeypatch, grid):
     this frame's cluster test (scan_kernels.hip, NextStep).  Frame sizes on both sides of one full step
     (4 x BLOCK pairs), odd record counts (the next frame then starts 8 bytes off a 16-byte boundary), empty
     frames, frames without side data and I-frame gaps inside a group, a group's last frame, batches that end
-    inside a group; with the prefetch on and off, the flags must be the oracle's."""
+    inside a group: the flags must be the oracle's."""
     import torch
     w, h = (1920, 1080) if grid == "1080p" else (3840, 2160)
     block = 512 if grid == "1080p" else 1024
@@ -1112,25 +1108,19 @@ def test_compact_next_frame_prefetch(gpu_scanner_factory, monkeypatch, grid):
         want_nosd = ob.scan_frames(p, b.mv, b.frame_off, None)
         if kw["vectors_needed"] == 2:
             assert want.tolist() == [1 if k == "A" else 0 for k in kinds]
-        for g, pf in ((2, 1), (3, 1), (4, 1), (8, 1), (25, 1), (64, 1), (4, 0), (1, 1)):
-            if pf == 0 and not experiments_build():           # MTGPU_PREFETCH=0 / MTGPU_ALIGN=0: experiments build only
-                continue
+        for g in (2, 3, 4, 8, 25, 64, 1):
             monkeypatch.setenv("MTGPU_GROUP", str(g))
-            monkeypatch.setenv("MTGPU_PREFETCH", str(pf))
-            monkeypatch.setenv("MTGPU_ALIGN", str(pf))            # without the prefetch also without the line alignment
             s = gpu_scanner_factory(m.ScanParams.from_config(w, h, **kw))
             monkeypatch.delenv("MTGPU_GROUP")
-            monkeypatch.delenv("MTGPU_PREFETCH")
-            monkeypatch.delenv("MTGPU_ALIGN")
             assert s.plan["block_threads"] == block and s.plan["counter_bits"] == 32
             got = s.check_frames_device_compact(d_rec, d_off, d_sd).cpu().numpy()
-            assert np.array_equal(got, want), (grid, kw, g, pf)
+            assert np.array_equal(got, want), (grid, kw, g)
             got = s.check_frames_device_compact(d_rec, d_off, None).cpu().numpy()
-            assert np.array_equal(got, want_nosd), (grid, kw, g, pf, "has_sd NULL")
+            assert np.array_equal(got, want_nosd), (grid, kw, g, "has_sd NULL")
             # a window that starts at an odd record and ends inside a group
             lo, hi = 2, len(sizes) - 3
             got = s.check_frames_device_compact(d_rec, d_off[lo:hi + 1].contiguous(), d_sd[lo:hi].contiguous()).cpu().numpy()
-            assert np.array_equal(got, want[lo:hi]), (grid, kw, g, pf, "window")
+            assert np.array_equal(got, want[lo:hi]), (grid, kw, g, "window")
 
 
 def test_scratch_pool_stats_and_trim(gpu_scanner_factory):

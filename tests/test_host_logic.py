@@ -121,7 +121,7 @@ def test_sharding_helpers():
 def test_launch_planner_known_answers_and_invariants(monkeypatch):
     """mtgpu_plan_preview: the launch planner (counter form, tile / band geometry, workgroup size)
     is host arithmetic — checked here without a GPU for the MI355X limits (160 KB LDS, 256 CUs)."""
-    for k in ("MTGPU_FORCE_FB", "MTGPU_FORCE_BLOCK", "MTGPU_FORCE_CHUNK", "MTGPU_BAND_LDS_KB", "MTGPU_MAX_TILE_KB"):
+    for k in ("MTGPU_FORCE_FB", "MTGPU_FORCE_BLOCK"):
         monkeypatch.delenv(k, raising=False)
     fine = dict(block_size=4, block_shift=2)
     cases = [
@@ -157,7 +157,7 @@ def test_launch_planner_known_answers_and_invariants(monkeypatch):
         rows = max(1, p.grid_h - 2 * p.vertical_margin)
         assert 0 < plan["lds_bytes"] <= 163840, (w, h, sh, vn, plan)
         assert plan["bands"] * plan["band_rows"] >= rows and (plan["bands"] - 1) * plan["band_rows"] < rows
-        assert 1 <= plan["chunk_rows"] <= plan["band_rows"] and plan["block_threads"] in (256, 512, 1024)
+        assert 1 <= plan["chunk_rows"] <= plan["band_rows"] and plan["block_threads"] in (512, 1024)
         if plan["counter_mode"] == 1:
             assert plan["counter_bits"] >= vn and plan["counter_bits"] in (1, 2, 4, 8)
         if plan["counter_mode"] == 2:

@@ -81,7 +81,7 @@ def test_pack_with_rejects_bad_arguments():
 
 
 def test_env_override_pins_the_loop():
-    """MTGPU_PACK / MTGPU_PACK_NT are read once per process: checked in a child."""
+    """MTGPU_PACK is read once per process: checked in a child."""
     import subprocess, sys, os
     code = ("import mvtrim_amd as m; lib = m.load_library(); print(lib.mtgpu_pack_selected())")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -92,7 +92,4 @@ def test_env_override_pins_the_loop():
     auto = sel()
     if (auto & _abi.PACK_IMPL_MASK) != _abi.PACK_SCALAR:
         assert auto & _abi.PACK_NT
-        # MTGPU_PACK_NT is an A/B knob (csrc/knobs.h): the default build ignores it
-        exp = b"+experiments" in m.load_library().mtgpu_version()
-        assert sel(MTGPU_PACK_NT="0") == ((auto & _abi.PACK_IMPL_MASK) if exp else auto)
     assert sel(MTGPU_PACK="nonsense") == auto
