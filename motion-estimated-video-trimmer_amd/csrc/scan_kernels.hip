@@ -2,18 +2,18 @@
 // (reference: src/motion_scanner.cpp:217-295).  Integer threshold / scatter /
 // stencil work: HBM-read bound, no MFMA.
 //
-// Work item = frame (or frame slice).  One workgroup per item:
-//   phase 0  zero the vote counters in LDS                         (:229 memset)
+// Work item = frame (or frame slice).  One workgroup per item (scan_item: one function per phase, named in brackets):
+//   phase 0  zero the vote counters in LDS                         (:229 memset)   [zero_tile]
 //   phase 1  stream the frame's packed records, one record per lane and load
 //            (REC 40: bytes 4..15 of each AVMotionVector = w,h,src_x,src_y,dst_x,dst_y;
 //             REC 8: the compact src_x,src_y,dst_x,dst_y form the host dispatcher stages),
-//            threshold on |d|^2, map dst to a cell, vote in LDS     (:242-268)
-//   phase 2  per chunk of rows:
+//            threshold on |d|^2, map dst to a cell, vote in LDS     (:242-268)      [stream_mv40, stream_compact; vote]
+//   phase 2  per chunk of rows:                                                     [cluster_count]
 //     2a     64-bit row masks of active cells (`count >= vectors_needed`, :282) in LDS: four
 //            lanes per mask word on 32-bit counters, one lane per word (bit-squeeze of the
-//            fields) on packed counters
+//            fields) on packed counters                                            [row_masks]
 //     2b     one lane per (row, word): shifted-mask 4-neighbour test,
-//            __popcll, LDS reduction                                 (:277-293)
+//            __popcll, LDS reduction                                 (:277-293)     [count_centres]
 //   compare the centre count with max(1, clusters_needed)           (:288)
 //
 // Vote counters come in three forms (template FB = bits per cell, MODE):
@@ -38,7 +38,7 @@
 // SAME workgroup handles one after the other (template SPILL): the records are streamed from
 // HBM exactly once, during band 0; every surviving vote that a later band needs is appended to
 // a per-frame queue in global memory (wave-aggregated append, the tails live in LDS) and bands 1.. replay that queue
-// instead of re-reading 40-byte records.  Queue entries (struct SpillQ): 4 bytes for a vote or a run of up to 4 same-cell
+// instead of re-reading 40-byte records [replay_queue].  Queue entries (struct SpillQ): 4 bytes for a vote or a run of up to 4 same-cell
 // votes, (run - 1) << 30 | gy << 15 | gx — or 8 bytes for a SPAN, three or more queued votes of one wave instruction in
 // consecutive cells of a row, which is what dense motion in raster-ordered records produces.  Typical
 // footage queues almost nothing (only votes above the threshold); when every record votes, spans keep the queue's
@@ -52,6 +52,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "scan_kernels.h"
 
@@ -301,64 +302,43 @@ struct SpillQ {
   int q_lo;               // first grid row a later band tracks (band 0's last centre row)
 };
 
-// `r` votes for each of the cells [c0, c0 + n) of the tile (consecutive cells of one row: a replayed span).  Thermometer
-// fields: a counter WORD at a time — one look, the next clear bits of every field of the word in ONE returning OR
-// (8 cells of a 4-bit form), and only the votes that lost a race to another wave settle cell by cell; other forms
-// cell by cell.  `rot`: the word the walk starts at (it wraps around) — the lanes of a wave replay consecutive spans,
-// whose words lie a fixed stride apart: started at the same relative word they would all hit a handful of LDS banks.
-template <int FB, int MODE>
-__device__ __forceinline__ void bump_cells(unsigned int *cnt, unsigned int c0, unsigned int n, unsigned int r, unsigned int cap,
-                                           unsigned int rot) {
-  if constexpr (MODE == MODE_UNARY && FB >= 2 && FB <= 8) {
-    constexpr unsigned int CPW = 32u / FB, FM = (1u << FB) - 1u;
-    if (n == 0u) return;
-    const unsigned int rr = r < cap ? r : cap;
-    constexpr unsigned int EVERY = 0xffffffffu / FM;                     // bit 0 of every field: 0x11111111 for 4-bit fields
-    const unsigned int low_rr = EVERY * ((1u << rr) - 1u), cap_ones = EVERY * ((1u << cap) - 1u);
-    const unsigned int end = c0 + n, first_w = c0 / CPW, last_w = (end - 1u) / CPW, nw = last_w - first_w + 1u;
-    unsigned int at = rot % nw;
-    for (unsigned int i = 0; i < nw; ++i) {
-      const unsigned int wi = first_w + at;
-      at = at + 1u == nw ? 0u : at + 1u;
-      const unsigned int lo = wi == first_w ? c0 - first_w * CPW : 0u, hi = wi == last_w ? end - last_w * CPW : CPW;
-      const unsigned int x = cnt[wi];
-      // every field of the word at once: a thermometer code grows by rr when it is shifted up by rr and its low rr
-      // bits are set — what the shift pushes out of a field's top lands in the low rr bits of the next field, which
-      // are set anyway — and stays within `cap` ones under the cap pattern; `sel` keeps the fields [lo, hi)
-      const unsigned int sel = (hi == CPW ? 0xffffffffu : (1u << (hi * FB)) - 1u) & ~((1u << (lo * FB)) - 1u);
-      const unsigned int m = (((x << rr) | low_rr) & cap_ones & sel) & ~x;
-      if (m != 0u) {
-        const unsigned int lost = m & atomicOr(&cnt[wi], m);       // bits somebody else set between look and OR
-        if (lost != 0u) {
-#pragma unroll
-          for (unsigned int q = 0; q < CPW; ++q) {
-            const unsigned int l = (unsigned int)__popc((lost >> (q * FB)) & FM);
-            if (l != 0u) bump_n<FB, MODE>(cnt, wi * CPW + q, l, cap);
-          }
-        }
-      }
-    }
-  } else {
-    for (unsigned int c = 0; c < n; ++c) bump_n<FB, MODE>(cnt, c0 + c, r, cap);
-  }
+// The entry format, said once.  q_key: a cell as gy << 15 | gx (gx, gy < 32768) — key + 1 is the next cell of the SAME
+// row.  q_entry: a run of 1..4 votes for that cell (two spare bits), also the first dword of a span.
+__device__ __forceinline__ unsigned int q_key(int gy, int gx) { return ((unsigned int)gy << 15) | (unsigned int)gx; }
+__device__ __forceinline__ unsigned int q_entry(unsigned int run, unsigned int key) { return ((run - 1u) << 30) | key; }
+__device__ __forceinline__ unsigned int q_run(unsigned int e) { return (e >> 30) + 1u; }
+__device__ __forceinline__ void q_cell(unsigned int e, int &gy, int &gx) { gy = (int)((e >> 15) & 0x7fffu); gx = (int)(e & 0x7fffu); }
+__device__ __forceinline__ void q_push_single(const SpillQ &sq, unsigned int at, unsigned int e) { sq.q[sq.n - 1u - at] = e; }
+__device__ __forceinline__ void q_push_span(const SpillQ &sq, unsigned int at, unsigned int e, unsigned int n_cells) { sq.q[at] = e; sq.q[at + 1u] = n_cells; }
+
+// Centres [c0,c1) and tracked counter rows [t0,t1) (one halo row each side) of a row band; a single tile is band 0.
+struct Band { int c0, c1, t0, t1; };
+
+__device__ __forceinline__ Band band_rows(const ScanK &k, int band) {
+  const int c0 = k.y_lo + band * k.band_rows, c1 = min(k.y_hi, c0 + k.band_rows);
+  return {c0, c1, max(c0 - 1, 0), min(c1 + 1, k.gh)};           // t1 - t0 may be <= 0 for an empty analysed range
+}
+// Does the band track row gy — as ONE unsigned compare, for the voters: they run only where t1 > t0 (scan_item).
+__device__ __forceinline__ bool tracks(const Band &b, int gy) { return (unsigned int)(gy - b.t0) < (unsigned int)(b.t1 - b.t0); }
+__device__ __forceinline__ unsigned int cell_of(const Band &b, const ScanK &k, int gy, int gx) {
+  return (unsigned int)((gy - b.t0) * k.gw + gx);
 }
 
-// `r` votes for each of the cells [c0, c0 + n) of the tile (n <= 64, consecutive cells of one row), by a whole wave:
-// lane i takes the i-th counter word the cells touch — the word-at-once step of bump_cells, every word in parallel.
+// Every field [lo, hi) of counter word wi grows by rr votes at once (thermometer fields, rr <= cap): one look, the next
+// clear bits of every field in ONE returning OR (8 cells of a 4-bit form), and only the votes that lost a race to
+// another wave settle cell by cell.
 template <int FB, int MODE>
-__device__ __forceinline__ void bump_cells_wave(unsigned int *cnt, unsigned int c0, unsigned int n, unsigned int r, unsigned int cap,
-                                                unsigned int lane) {
+__device__ __forceinline__ void bump_word(unsigned int *cnt, unsigned int wi, unsigned int lo, unsigned int hi, unsigned int rr,
+                                          unsigned int cap) {
   constexpr unsigned int CPW = 32u / FB, FM = (1u << FB) - 1u;
-  const unsigned int rr = r < cap ? r : cap;
-  constexpr unsigned int EVERY = 0xffffffffu / FM;                       // bit 0 of every field
+  constexpr unsigned int EVERY = 0xffffffffu / FM;                       // bit 0 of every field: 0x11111111 for 4-bit fields
   const unsigned int low_rr = EVERY * ((1u << rr) - 1u), cap_ones = EVERY * ((1u << cap) - 1u);
-  const unsigned int end = c0 + n, first_w = c0 / CPW, last_w = (end - 1u) / CPW;
-  const unsigned int wi = first_w + lane;
-  if (wi > last_w) return;
-  const unsigned int lo = wi == first_w ? c0 - first_w * CPW : 0u, hi = wi == last_w ? end - last_w * CPW : CPW;
   const unsigned int x = cnt[wi];
+  // a thermometer code grows by rr when it is shifted up by rr and its low rr bits are set — what the shift pushes out
+  // of a field's top lands in the low rr bits of the next field, which are set anyway — and stays within `cap` ones
+  // under the cap pattern; `sel` keeps the fields [lo, hi)
   const unsigned int sel = (hi == CPW ? 0xffffffffu : (1u << (hi * FB)) - 1u) & ~((1u << (lo * FB)) - 1u);
-  const unsigned int m = (((x << rr) | low_rr) & cap_ones & sel) & ~x;   // (see bump_cells)
+  const unsigned int m = (((x << rr) | low_rr) & cap_ones & sel) & ~x;
   if (m != 0u) {
     const unsigned int lost = m & atomicOr(&cnt[wi], m);                 // bits somebody else set between look and OR
     if (lost != 0u) {
@@ -371,14 +351,44 @@ __device__ __forceinline__ void bump_cells_wave(unsigned int *cnt, unsigned int 
   }
 }
 
-// Threshold + cell mapping + vote for one record (src/motion_scanner.cpp:246-267).
-// [t0,t1) = grid rows this tile tracks.
-// DENSE: try the dense-wave shortcut first — only the main streaming loop over 40-byte records asks for it (whole
-// waves, one record per lane in stream order; the compact loop holds two records per lane, head and tail calls run
-// under divergence): compiled into every call site it tripled the library's code size.
-template <int FB, int MODE, bool SPILL, bool DENSE = false>
-__device__ __forceinline__ void vote(const MvFields m, const ScanK &k, int t0, int t1,
-                                     unsigned int *cnt, const SpillQ &sq) {
+// `r` votes for each of the cells [c0, c0 + n) of the tile (consecutive cells of one row: a replayed span).  Thermometer
+// fields: a counter WORD at a time (bump_word); other forms cell by cell.  `rot`: the word the walk starts at (it wraps
+// around) — the lanes of a wave replay consecutive spans, whose words lie a fixed stride apart: started at the same
+// relative word they would all hit a handful of LDS banks.
+template <int FB, int MODE>
+__device__ __forceinline__ void bump_cells(unsigned int *cnt, unsigned int c0, unsigned int n, unsigned int r, unsigned int cap,
+                                           unsigned int rot) {
+  if constexpr (MODE == MODE_UNARY && FB >= 2 && FB <= 8) {
+    constexpr unsigned int CPW = 32u / FB;
+    if (n == 0u) return;
+    const unsigned int end = c0 + n, first_w = c0 / CPW, last_w = (end - 1u) / CPW, nw = last_w - first_w + 1u;
+    unsigned int at = rot % nw;
+    for (unsigned int i = 0; i < nw; ++i) {
+      const unsigned int wi = first_w + at;
+      at = at + 1u == nw ? 0u : at + 1u;
+      bump_word<FB, MODE>(cnt, wi, wi == first_w ? c0 - first_w * CPW : 0u, wi == last_w ? end - last_w * CPW : CPW,
+                          r < cap ? r : cap, cap);
+    }
+  } else {
+    for (unsigned int c = 0; c < n; ++c) bump_n<FB, MODE>(cnt, c0 + c, r, cap);
+  }
+}
+
+// `r` votes for each of the cells [c0, c0 + n) of the tile (n <= 64, consecutive cells of one row), by a whole wave:
+// lane i takes the i-th counter word the cells touch — bump_word, every word in parallel.
+template <int FB, int MODE>
+__device__ __forceinline__ void bump_cells_wave(unsigned int *cnt, unsigned int c0, unsigned int n, unsigned int r, unsigned int cap,
+                                                unsigned int lane) {
+  constexpr unsigned int CPW = 32u / FB;
+  const unsigned int end = c0 + n, first_w = c0 / CPW, last_w = (end - 1u) / CPW;
+  const unsigned int wi = first_w + lane;
+  if (wi > last_w) return;
+  bump_word<FB, MODE>(cnt, wi, wi == first_w ? c0 - first_w * CPW : 0u, wi == last_w ? end - last_w * CPW : CPW,
+                      r < cap ? r : cap, cap);
+}
+
+// Threshold and cell of one record (src/motion_scanner.cpp:246-262): does it vote, and where.
+__device__ __forceinline__ bool keep_and_cell(const MvFields m, const ScanK &k, int &gx, int &gy) {
   const unsigned int dx = (unsigned int)(m.dst_x - m.src_x);   // |dx| <= 65535
   const unsigned int dy = (unsigned int)(m.dst_y - m.src_y);
   // dx*dx < 2^32 exactly; the sum needs 34 bits.  (The compiler proves the operands fit 17 bits and already
@@ -386,14 +396,140 @@ __device__ __forceinline__ void vote(const MvFields m, const ScanK &k, int t0, i
   // multiplies signed ints, so the optimiser may assume dx*dx < 2^31 and drops the 33rd bit of the sum.)
   const unsigned long long mag =
       (unsigned long long)(dx * dx) + (unsigned long long)(dy * dy);
-  const int gx = m.dst_x >> k.shift;
-  const int gy = m.dst_y >> k.shift;
+  gx = m.dst_x >> k.shift;
+  gy = m.dst_y >> k.shift;
   // 0 <= gx < gw and y_lo <= gy < y_hi (:262) as two unsigned compares (y_hi >= y_lo by construction)
-  const bool in = (mag >= k.thr) & ((unsigned int)gx < (unsigned int)k.gw) &
-                  ((unsigned int)(gy - k.y_lo) < (unsigned int)(k.y_hi - k.y_lo));
+  return (mag >= k.thr) & ((unsigned int)gx < (unsigned int)k.gw) &
+         ((unsigned int)(gy - k.y_lo) < (unsigned int)(k.y_hi - k.y_lo));
+}
+
+// DENSE wave instruction — all 64 records vote (the caller's ballot) and fall, in order, into consecutive cells of one
+// grid row, R = 1, 2 or 4 records per cell: what dense motion (a camera pan) looks like in raster-ordered records.  The
+// general path (vote_runs, queue_append: a shuffle, eight ballots and 64-bit bit-scans per wave instruction) makes such
+// input instruction-bound; here the pattern is read off a few lanes (first run: lanes 0..3, run length: the second
+// cell's lanes), verified with ONE ballot, and the wave's votes are: the first cell (R - ph votes: the instruction
+// may start inside a cell — where a frame's records start, and how many head records the line alignment peeled,
+// is data), the cells in between (R each: their counter words voted in parallel, one lane per word), the last
+// cell (the rest).  The queue gets ONE span for the cells in between and a single each for a cut first / last
+// cell — what the general path would have written.  Same counter state and same replayed votes (saturating
+// counts commute).  Needs the whole wave (the calls for head records and tails do not have it).
+// Returns whether the instruction was of this kind and has been voted.
+template <int FB, int MODE, bool SPILL>
+__device__ __forceinline__ bool vote_dense_wave(const unsigned int key, const ScanK &k, const Band &b, unsigned int *cnt,
+                                                const SpillQ &sq) {
+  if (__ballot(true) != ~0ull) return false;
+  const int lane = (int)(threadIdx.x & 63u);
+  const unsigned int key0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)key);
+  const unsigned int k1 = (unsigned int)__builtin_amdgcn_readlane((int)key, 1);
+  const unsigned int k2 = (unsigned int)__builtin_amdgcn_readlane((int)key, 2);
+  const unsigned int k3 = (unsigned int)__builtin_amdgcn_readlane((int)key, 3);
+  const unsigned int L1 = k1 != key0 ? 1u : (k2 != key0 ? 2u : (k3 != key0 ? 3u : 4u));     // votes for the first cell
+  const unsigned int a1 = (unsigned int)__builtin_amdgcn_readlane((int)key, (int)L1 + 1);
+  const unsigned int a2 = (unsigned int)__builtin_amdgcn_readlane((int)key, (int)L1 + 2);
+  const unsigned int a3 = (unsigned int)__builtin_amdgcn_readlane((int)key, (int)L1 + 3);
+  const unsigned int R = a1 != key0 + 1u ? 1u : (a2 != key0 + 1u ? 2u : (a3 != key0 + 1u ? 3u : 4u));
+  if (R == 3u || L1 > R) return false;
+  const unsigned int sh = R >> 1, ph = R - L1;          // log2 R; lanes of the first cell that belong to the instruction before
+  if (__ballot(key != key0 + (((unsigned int)lane + ph) >> sh)) != 0ull) return false;
+  const unsigned int n_cells = ((63u + ph) >> sh) + 1u, last = ((63u + ph) & (R - 1u)) + 1u;
+  int gy0, gx0;
+  q_cell(key0, gy0, gx0);
+  const bool cut = ph != 0u;                            // first and last cell hold fewer than R votes
+  if (!SPILL || tracks(b, gy0)) {
+    const unsigned int c0 = cell_of(b, k, gy0, gx0);
+    if (!cut) {
+      bump_cells_wave<FB, MODE>(cnt, c0, n_cells, R, k.vec_need, (unsigned int)lane);
+    } else {
+      bump_cells_wave<FB, MODE>(cnt, c0 + 1u, n_cells - 2u, R, k.vec_need, (unsigned int)lane);
+      if (lane == 63) bump_n<FB, MODE>(cnt, c0, L1, k.vec_need);
+      if (lane == 62) bump_n<FB, MODE>(cnt, c0 + n_cells - 1u, last, k.vec_need);
+    }
+  }
+  if constexpr (SPILL) {
+    if (gy0 >= sq.q_lo && lane == 0) {
+      const unsigned int at = atomicAdd(sq.tail + 1, 2u);                                 // (n_cells - 2 >= 14: always a span)
+      q_push_span(sq, at, q_entry(R, cut ? key0 + 1u : key0), cut ? n_cells - 2u : n_cells);
+      if (cut) {
+        const unsigned int b1 = atomicAdd(sq.tail, 2u);
+        q_push_single(sq, b1, q_entry(L1, key0));
+        q_push_single(sq, b1 + 1u, q_entry(last, key0 + n_cells - 1u));
+      }
+    }
+  }
+  return true;
+}
+
+// RUNS of records that one wave instruction maps to the same cell (equal `key`) vote once, with their count.  Returns
+// whether this lane is the first of its run; `run`: the run's length.
+template <int FB, int MODE, bool SPILL>
+__device__ __forceinline__ bool vote_runs(const bool in, const unsigned int key, const int gx, const int gy, const ScanK &k,
+                                          const Band &b, unsigned int *cnt, unsigned int &run) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const unsigned int prev = (unsigned int)__shfl_up((int)key, 1);
+  // a queue entry carries a run of at most 4 (two spare bits): where a field can count beyond 4, runs are cut
+  // every 4 lanes so that no vote is lost to the entry format
+  const unsigned long long forced = (k.vec_need > 4u) ? 0x1111111111111111ull : 1ull;
+  // vote() is also called under divergence (head records, tails): a lane that is switched off ends the run
+  // below it, and the lane above it starts one (what __shfl_up brings from an inactive lane is undefined)
+  const unsigned long long off = ~__ballot(true);
+  const unsigned long long heads = __ballot(key != prev) | forced | off | (off << 1);
+  const bool head = ((heads >> lane) & 1ull) != 0ull;
+  const unsigned long long above = (lane < 63) ? (heads >> (lane + 1)) : 0ull;
+  run = above ? (unsigned int)__ffsll((long long)above) : (unsigned int)(64 - lane);
+  bool mine = in & head;                       // a band (SPILL) has to test its own rows
+  if constexpr (SPILL) mine = mine & tracks(b, gy);
+  if (mine) bump_n<FB, MODE>(cnt, cell_of(b, k, gy, gx), run, k.vec_need);
+  return head;
+}
+
+// Wave-aggregated append (see SpillQ) of the lanes with `qv`, each a run of `run` votes for cell `key`: one returning
+// LDS add per end of the queue and wave instruction.
+__device__ __forceinline__ void queue_append(const bool qv, const unsigned int key, const unsigned int run, const SpillQ &sq) {
+  const unsigned long long qm = __ballot(qv);
+  if (qm == 0ull) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int leader = __ffsll((long long)qm) - 1;
+  const unsigned int rank = (unsigned int)__popcll(qm & ((1ull << lane) - 1ull));   // queued votes below this lane
+  const unsigned int e = q_entry(min(run, 4u), key);
+  // segments: maximal stretches of queued votes whose entries count up by exactly one from vote to vote —
+  // consecutive cells (q_key: the next cell of the SAME row) with the same run length
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const unsigned int d = e - rank;
+  const unsigned long long qb = qm & below;
+  const int prev_lane = qb ? 63 - __clzll((long long)qb) : lane;              // the queued lane below this one
+  const unsigned int d_prev = (unsigned int)__shfl((int)d, prev_lane);
+  const unsigned long long sh = __ballot(qv && (qb == 0ull || d != d_prev));   // first vote of every segment
+  const unsigned long long at_or_below = sh & (below | (1ull << lane));
+  const int seg_lo = at_or_below ? 63 - __clzll((long long)at_or_below) : 0;
+  const unsigned long long heads_above = (lane < 63) ? (sh >> (lane + 1)) << (lane + 1) : 0ull;
+  const int seg_hi = heads_above ? __ffsll((long long)heads_above) - 1 : 64;   // [seg_lo, seg_hi): this lane's segment
+  const unsigned long long seg_mask = (seg_hi >= 64 ? ~0ull : ((1ull << seg_hi) - 1ull)) & ~((1ull << seg_lo) - 1ull);
+  const unsigned int seg_len = (unsigned int)__popcll(qm & seg_mask);
+  const bool span_head = qv && lane == seg_lo && seg_len >= 3u;
+  const bool single = qv && seg_len < 3u;
+  const unsigned long long spans = __ballot(span_head), singles = __ballot(single);
+  unsigned int base_s = 0u, base_1 = 0u;
+  if (lane == leader) {
+    if (spans != 0ull) base_s = atomicAdd(sq.tail + 1, 2u * (unsigned int)__popcll(spans));
+    if (singles != 0ull) base_1 = atomicAdd(sq.tail, (unsigned int)__popcll(singles));
+  }
+  base_s = (unsigned int)__builtin_amdgcn_readlane((int)base_s, leader);
+  base_1 = (unsigned int)__builtin_amdgcn_readlane((int)base_1, leader);
+  if (span_head) q_push_span(sq, base_s + 2u * (unsigned int)__popcll(spans & below), e, seg_len);
+  else if (single) q_push_single(sq, base_1 + (unsigned int)__popcll(singles & below), e);
+}
+
+// Threshold + cell mapping + vote for one record (src/motion_scanner.cpp:246-267).
+// DENSE: try the dense-wave shortcut first — only the main streaming loop over 40-byte records asks for it (whole
+// waves, one record per lane in stream order; the compact loop holds two records per lane, head and tail calls run
+// under divergence): compiled into every call site it tripled the library's code size.
+template <int FB, int MODE, bool SPILL, bool DENSE = false>
+__device__ __forceinline__ void vote(const MvFields m, const ScanK &k, const Band &b, unsigned int *cnt, const SpillQ &sq) {
+  int gx, gy;
+  const bool in = keep_and_cell(m, k, gx, gy);
   if constexpr (!SPILL && (MODE == MODE_ADD32 || (MODE == MODE_UNARY && FB == 1))) {
     // fire-and-forget LDS atomics (32-bit add, 1-bit or): a single tile tracks every analysed row
-    if (in) bump<FB, MODE>(cnt, (unsigned int)((gy - t0) * k.gw + gx), k.vec_need);
+    if (in) bump<FB, MODE>(cnt, cell_of(b, k, gy, gx), k.vec_need);
   } else {
     // Returning LDS atomics (thermometer / CAS fields) and the spill queue: RUNS of records that one wave
     // instruction maps to the same cell — codecs export several vectors per block (two prediction directions,
@@ -402,120 +538,23 @@ __device__ __forceinline__ void vote(const MvFields m, const ScanK &k, int t0, i
     // word), and each would append its own queue entry.  A wave instruction without a voter costs one ballot.
     const unsigned long long any = __ballot(in);
     if (any == 0ull) return;
-    const int lane = (int)(threadIdx.x & 63u);
-    const unsigned int key = in ? (((unsigned int)gy << 15) | (unsigned int)gx) : 0xffffffffu;   // gx, gy < 32768
+    const unsigned int key = in ? q_key(gy, gx) : 0xffffffffu;
     if constexpr (DENSE && MODE == MODE_UNARY && FB >= 2 && FB <= 8) {
-      // DENSE wave instruction — all 64 records vote and fall, in order, into consecutive cells of one grid row, R = 1, 2
-      // or 4 records per cell: what dense motion (a camera pan) looks like in raster-ordered records.  The general path
-      // below (runs, queue segments: a shuffle, eight ballots and 64-bit bit-scans per wave instruction) makes such input
-      // instruction-bound; here the pattern is read off a few lanes (first run: lanes 0..3, run length: the second
-      // cell's lanes), verified with ONE ballot, and the wave's votes are: the first cell (R - ph votes: the instruction
-      // may start inside a cell — where a frame's records start, and how many head records the line alignment peeled,
-      // is data), the cells in between (R each: their counter words voted in parallel, one lane per word), the last
-      // cell (the rest).  The queue gets ONE span for the cells in between and a single each for a cut first / last
-      // cell — what the general path would have written.  Same counter state and same replayed votes (saturating
-      // counts commute).  Needs the whole wave (the calls for head records and tails do not have it).
-      if (any == ~0ull && __ballot(true) == ~0ull) {
-        const unsigned int key0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)key);
-        const unsigned int k1 = (unsigned int)__builtin_amdgcn_readlane((int)key, 1);
-        const unsigned int k2 = (unsigned int)__builtin_amdgcn_readlane((int)key, 2);
-        const unsigned int k3 = (unsigned int)__builtin_amdgcn_readlane((int)key, 3);
-        const unsigned int L1 = k1 != key0 ? 1u : (k2 != key0 ? 2u : (k3 != key0 ? 3u : 4u));     // votes for the first cell
-        const unsigned int a1 = (unsigned int)__builtin_amdgcn_readlane((int)key, (int)L1 + 1);
-        const unsigned int a2 = (unsigned int)__builtin_amdgcn_readlane((int)key, (int)L1 + 2);
-        const unsigned int a3 = (unsigned int)__builtin_amdgcn_readlane((int)key, (int)L1 + 3);
-        const unsigned int R = a1 != key0 + 1u ? 1u : (a2 != key0 + 1u ? 2u : (a3 != key0 + 1u ? 3u : 4u));
-        if (R != 3u && L1 <= R) {
-          const unsigned int sh = R >> 1, ph = R - L1;                                              // log2 R; lanes of the first cell that belong to the instruction before
-          if (__ballot(key != key0 + (((unsigned int)lane + ph) >> sh)) == 0ull) {
-            const unsigned int n_cells = ((63u + ph) >> sh) + 1u, last = ((63u + ph) & (R - 1u)) + 1u;
-            const int gy0 = (int)(key0 >> 15), gx0 = (int)(key0 & 0x7fffu);
-            const bool cut = ph != 0u;                                                              // first and last cell hold fewer than R votes
-            if (!SPILL || (unsigned int)(gy0 - t0) < (unsigned int)(t1 - t0)) {
-              const unsigned int c0 = (unsigned int)((gy0 - t0) * k.gw + gx0);
-              if (!cut) {
-                bump_cells_wave<FB, MODE>(cnt, c0, n_cells, R, k.vec_need, (unsigned int)lane);
-              } else {
-                bump_cells_wave<FB, MODE>(cnt, c0 + 1u, n_cells - 2u, R, k.vec_need, (unsigned int)lane);
-                if (lane == 63) bump_n<FB, MODE>(cnt, c0, L1, k.vec_need);
-                if (lane == 62) bump_n<FB, MODE>(cnt, c0 + n_cells - 1u, last, k.vec_need);
-              }
-            }
-            if constexpr (SPILL) {
-              if (gy0 >= sq.q_lo && lane == 0) {
-                const unsigned int at = atomicAdd(sq.tail + 1, 2u);                                 // (n_cells - 2 >= 14: always a span)
-                sq.q[at] = ((R - 1u) << 30) | (cut ? key0 + 1u : key0);
-                sq.q[at + 1u] = cut ? n_cells - 2u : n_cells;
-                if (cut) {
-                  const unsigned int b1 = atomicAdd(sq.tail, 2u);
-                  sq.q[sq.n - 1u - b1] = ((L1 - 1u) << 30) | key0;
-                  sq.q[sq.n - 2u - b1] = ((last - 1u) << 30) | (key0 + n_cells - 1u);
-                }
-              }
-            }
-            return;
-          }
-        }
-      }
+      if (any == ~0ull && vote_dense_wave<FB, MODE, SPILL>(key, k, b, cnt, sq)) return;
     }
-    const unsigned int prev = (unsigned int)__shfl_up((int)key, 1);
-    // a queue entry carries a run of at most 4 (two spare bits): where a field can count beyond 4, runs are cut
-    // every 4 lanes so that no vote is lost to the entry format
-    const unsigned long long forced = (k.vec_need > 4u) ? 0x1111111111111111ull : 1ull;
-    // vote() is also called under divergence (head records, tails): a lane that is switched off ends the run
-    // below it, and the lane above it starts one (what __shfl_up brings from an inactive lane is undefined)
-    const unsigned long long off = ~__ballot(true);
-    const unsigned long long heads = __ballot(key != prev) | forced | off | (off << 1);
-    const bool head = ((heads >> lane) & 1ull) != 0ull;
-    const unsigned long long above = (lane < 63) ? (heads >> (lane + 1)) : 0ull;
-    const unsigned int run = above ? (unsigned int)__ffsll((long long)above) : (unsigned int)(64 - lane);
-    bool mine = in & head;                       // a band (SPILL) has to test its own rows
-    if constexpr (SPILL) mine = mine & ((unsigned int)(gy - t0) < (unsigned int)(t1 - t0));
-    if (mine) bump_n<FB, MODE>(cnt, (unsigned int)((gy - t0) * k.gw + gx), run, k.vec_need);
-    if constexpr (SPILL) {
-      // wave-aggregated append (see SpillQ): one returning LDS add per wave instruction
-      const bool qv = in & head & (gy >= sq.q_lo);
-      const unsigned long long qm = __ballot(qv);
-      if (qm != 0ull) {
-        const int leader = __ffsll((long long)qm) - 1;
-        const unsigned int rank = (unsigned int)__popcll(qm & ((1ull << lane) - 1ull));   // queued votes below this lane
-        const unsigned int r4 = min(run, 4u) - 1u;
-        const unsigned int e = (r4 << 30) | key;
-        // segments: maximal stretches of queued votes whose entries count up by exactly one from vote to vote —
-        // consecutive cells (gy << 15 | gx, gx < 32768: the next cell of the SAME row) with the same run length
-        const unsigned long long below = (1ull << lane) - 1ull;
-        const unsigned int d = e - rank;
-        const unsigned long long qb = qm & below;
-        const int prev_lane = qb ? 63 - __clzll((long long)qb) : lane;              // the queued lane below this one
-        const unsigned int d_prev = (unsigned int)__shfl((int)d, prev_lane);
-        const unsigned long long sh = __ballot(qv && (qb == 0ull || d != d_prev));   // first vote of every segment
-        const unsigned long long at_or_below = sh & (below | (1ull << lane));
-        const int seg_lo = at_or_below ? 63 - __clzll((long long)at_or_below) : 0;
-        const unsigned long long heads_above = (lane < 63) ? (sh >> (lane + 1)) << (lane + 1) : 0ull;
-        const int seg_hi = heads_above ? __ffsll((long long)heads_above) - 1 : 64;   // [seg_lo, seg_hi): this lane's segment
-        const unsigned long long seg_mask = (seg_hi >= 64 ? ~0ull : ((1ull << seg_hi) - 1ull)) & ~((1ull << seg_lo) - 1ull);
-        const unsigned int seg_len = (unsigned int)__popcll(qm & seg_mask);
-        const bool span_head = qv && lane == seg_lo && seg_len >= 3u;
-        const bool single = qv && seg_len < 3u;
-        const unsigned long long spans = __ballot(span_head), singles = __ballot(single);
-        unsigned int base_s = 0u, base_1 = 0u;
-        if (lane == leader) {
-          if (spans != 0ull) base_s = atomicAdd(sq.tail + 1, 2u * (unsigned int)__popcll(spans));
-          if (singles != 0ull) base_1 = atomicAdd(sq.tail, (unsigned int)__popcll(singles));
-        }
-        base_s = (unsigned int)__builtin_amdgcn_readlane((int)base_s, leader);
-        base_1 = (unsigned int)__builtin_amdgcn_readlane((int)base_1, leader);
-        if (span_head) {
-          const unsigned int at = base_s + 2u * (unsigned int)__popcll(spans & below);
-          sq.q[at] = e;
-          sq.q[at + 1u] = seg_len;
-        } else if (single) {
-          sq.q[sq.n - 1u - (base_1 + (unsigned int)__popcll(singles & below))] = e;
-        }
-      }
-    }
+    unsigned int run;
+    const bool head = vote_runs<FB, MODE, SPILL>(in, key, gx, gy, k, b, cnt, run);
+    if constexpr (SPILL) queue_append(in & head & (gy >= sq.q_lo), key, run, sq);
   }
 }
+
+// Both records of a 16-byte pair of compact records.
+template <int FB, int MODE, bool SPILL>
+__device__ __forceinline__ void vote_pair(const u32x4 d, const ScanK &k, const Band &b, unsigned int *cnt, const SpillQ &sq) {
+  vote<FB, MODE, SPILL>(decode((u32x2){d.x, d.y}), k, b, cnt, sq);
+  vote<FB, MODE, SPILL>(decode((u32x2){d.z, d.w}), k, b, cnt, sq);
+}
+
 
 // Compact records: how many records at the start of a frame's array (< 16) are scanned one by one so that the
 // 16-byte pair stream starts on a 128-byte line.
@@ -599,6 +638,369 @@ __device__ __forceinline__ unsigned int item_entry(unsigned int item, int slices
   return (SPILL || slices == 1) ? item : item / (unsigned int)slices;
 }
 
+// The workgroup's LDS: the counter tile, the row masks of one chunk, then four words — the centre total, the slice
+// ticket, the two queue tails (SpillQ::tail).
+struct Tile {
+  unsigned int *cnt;              // packed [trows][gw] fields
+  unsigned long long *mask;       // [chunk_rows+2][W]
+  unsigned int *total, *ticket, *tail;
+};
+
+__device__ __forceinline__ Tile carve_tile(unsigned int *lds, const ScanK &k) {
+  unsigned long long *mask = reinterpret_cast<unsigned long long *>(lds + k.cnt_words);
+  unsigned int *total = reinterpret_cast<unsigned int *>(mask + (size_t)k.mask_rows * k.W);
+  return {lds, mask, total, total + 1, total + 2};
+}
+
+// This workgroup's share [r0, r1) of the frame's records when the frame is cut into k.slices slices.
+__device__ __forceinline__ void slice_records(const ScanK &k, int slice, unsigned long long &r0, unsigned long long &r1) {
+  const unsigned long long n = r1 - r0, per = (n + (unsigned long long)k.slices - 1ull) / (unsigned long long)k.slices;
+  const unsigned long long a = r0 + min(n, per * (unsigned long long)slice);
+  const unsigned long long b = r0 + min(n, per * (unsigned long long)(slice + 1));
+  r0 = a;
+  r1 = b;
+}
+
+// ---- phase 0: zero counters (and, once per item, the centre total and the queue tails)
+template <int BLOCK>
+__device__ __forceinline__ void zero_tile(const Tile &t, const ScanK &k, bool first_band) {
+  const int tid = threadIdx.x;
+  u32x4 *c4 = reinterpret_cast<u32x4 *>(t.cnt);
+  const int n4 = k.cnt_words >> 2;
+  for (int i = tid; i < n4; i += BLOCK) c4[i] = (u32x4){0u, 0u, 0u, 0u};
+  if (first_band && tid == 0) { *t.total = 0u; t.tail[0] = 0u; t.tail[1] = 0u; }
+}
+
+// ---- phase 1, band 0: stream the records (HBM, exactly once per frame)
+
+// The rest of a stream (fewer than one step: at most UNROLL units per lane, from unit i on), every load issued before
+// the first vote — a frame smaller than one step (SD streams) costs ONE memory round trip, not one per unit.  Unit: the
+// fields of a 40-byte record (u32x3) or a pair of compact records (u32x4).
+template <typename Unit, int BLOCK, int UNROLL, int FB, int MODE, bool SPILL>
+__device__ __forceinline__ void stream_tail(const unsigned char *base, unsigned long long i, unsigned long long n, const ScanK &k,
+                                            const Band &b, unsigned int *cnt, const SpillQ &sq) {
+  constexpr bool PAIRS = std::is_same<Unit, u32x4>::value;
+  Unit d[UNROLL];
+  bool ok[UNROLL];
+#pragma unroll
+  for (int u = 0; u < UNROLL; ++u) {
+    const unsigned long long q = i + (unsigned long long)u * BLOCK;
+    ok[u] = q < n;
+    if constexpr (PAIRS) { if (ok[u]) d[u] = load_pair(base + q * 16ull); }
+    else { if (ok[u]) d[u] = load_fields(base + q * 40ull); }
+  }
+#pragma unroll
+  for (int u = 0; u < UNROLL; ++u) {
+    if constexpr (PAIRS) { if (ok[u]) vote_pair<FB, MODE, SPILL>(d[u], k, b, cnt, sq); }
+    else { if (ok[u]) vote<FB, MODE, SPILL>(decode(d[u]), k, b, cnt, sq); }
+  }
+}
+
+// 40-byte records [base, base + 40 n): lane i of a step takes record i, UNROLL independent loads in flight per lane.
+template <int BLOCK, int UNROLL, int FB, int MODE, bool SPILL>
+__device__ __forceinline__ void stream_mv40(const unsigned char *base, unsigned long long n, const ScanK &k, const Band &b,
+                                            unsigned int *cnt, const SpillQ &sq) {
+  const int tid = threadIdx.x;
+  // Line alignment.  A wave instruction of the loops below covers 64 records = 2560 bytes = exactly 20
+  // 128-byte lines IF the stream starts on a line; a frame that starts mid-line (real footage: every
+  // frame has its own record count) makes every instruction touch 21 lines, and the shared edge lines
+  // are fetched twice, by two different instructions (PMC, ragged 960x540 frames: 1.021 x the
+  // algorithmic bytes).  40 h = -start (mod 128) has a solution h < 16 whenever the start is 8-byte
+  // aligned (5 * 13 = 1 mod 16): the first h records go to lanes 0..h-1, the streams start on a line.
+  const unsigned int r = (unsigned int)((uintptr_t)base & 127u);
+  if ((r & 7u) == 0u) {
+    unsigned long long h = (unsigned long long)((13u * ((16u - (r >> 3)) & 15u)) & 15u);
+    h = h < n ? h : n;
+    if ((unsigned long long)tid < h) vote<FB, MODE, SPILL>(decode(load_fields(base + (unsigned long long)tid * 40ull)), k, b, cnt, sq);
+    base += h * 40ull;
+    n -= h;
+  }
+  unsigned long long i = tid;
+  constexpr unsigned long long STEP = (unsigned long long)UNROLL * BLOCK;
+  constexpr unsigned long long LAST = (unsigned long long)(UNROLL - 1) * BLOCK;
+  for (; i + LAST < n; i += STEP) {
+    u32x3 d[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) d[u] = load_fields(base + (i + (unsigned long long)u * BLOCK) * 40ull);
+    // (the scheduler sinks loads 2..UNROLL below the wait for load 1; forcing them up front with
+    //  a sched_barrier measured -1..-2 % here, +7 % in the compact loop: left as it is)
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) vote<FB, MODE, SPILL, true>(decode(d[u]), k, b, cnt, sq);
+  }
+  if (i < n) stream_tail<u32x3, BLOCK, UNROLL, FB, MODE, SPILL>(base, i, n, k, b, cnt, sq);
+}
+
+// Compact records [base, base + 8 n): 16-byte loads of TWO records per lane (a wave instruction covers 1 KB),
+// UNROLL pairs in flight per lane — with 8-byte loads a CU keeps too few bytes in flight
+// to cover the HBM latency (measured 4.96 TB/s of compact bytes on 1080p).  The pair
+// stream starts at the first record on a 128-byte line (compact_head: up to 15 head records go to
+// lanes 0..14, so that a wave instruction covers exactly 8 lines); lane 0 takes an odd last record.
+// `ns`: this frame's first step, if it was issued during the previous frame's cluster test.
+template <int BLOCK, int UNROLL, int FB, int MODE, bool SPILL>
+__device__ __forceinline__ void stream_compact(const unsigned char *base, unsigned long long n, const ScanK &k, const Band &b,
+                                               unsigned int *cnt, const SpillQ &sq, NextStep<UNROLL> &ns) {
+  const int tid = threadIdx.x;
+  constexpr unsigned long long STEP = (unsigned long long)UNROLL * BLOCK;
+  constexpr unsigned long long LAST = (unsigned long long)(UNROLL - 1) * BLOCK;
+  const unsigned long long head = compact_head(base, n);
+  const unsigned char *pbase = base + head * 8ull;
+  const unsigned long long np = (n - head) >> 1;            // pairs
+  if ((unsigned long long)tid < head)
+    vote<FB, MODE, SPILL>(decode(load_compact(base + (unsigned long long)tid * 8ull)), k, b, cnt, sq);
+  if (tid == 0 && ((n - head) & 1ull) != 0ull)
+    vote<FB, MODE, SPILL>(decode(load_compact(base + (n - 1ull) * 8ull)), k, b, cnt, sq);
+  unsigned long long p = tid;
+  if (ns.have) {                       // (ns.frame is this frame: scan_item checked on entry)
+    ns.have = false;
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) vote_pair<FB, MODE, SPILL>(ns.d[u], k, b, cnt, sq);
+    p += STEP;
+  }
+  for (; p + LAST < np; p += STEP) {
+    u32x4 d[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) d[u] = load_pair(pbase + (p + (unsigned long long)u * BLOCK) * 16ull);
+    __builtin_amdgcn_sched_barrier(0);   // every load of the step is issued before the first one is consumed
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) vote_pair<FB, MODE, SPILL>(d[u], k, b, cnt, sq);
+  }
+  stream_tail<u32x4, BLOCK, UNROLL, FB, MODE, SPILL>(pbase, p, np, k, b, cnt, sq);
+}
+
+// Compact records: the first step of the next frame of the list (the entry parked at `stage_next` when the workgroup
+// started) — same pair alignment as stream_compact.  See NextStep.
+template <int BLOCK, int UNROLL>
+__device__ __forceinline__ void issue_next_step(const unsigned char *__restrict__ mv, const unsigned int *stage_next,
+                                                NextStep<UNROLL> &ns) {
+  const int tid = threadIdx.x;
+  const WorkItem nx = staged_item(stage_next, 0u);
+  const unsigned char *nb = mv + nx.r0 * 8ull;
+  const unsigned long long nn = nx.r1 - nx.r0;
+  const unsigned long long nhead = compact_head(nb, nn);
+  const unsigned long long nnp = (nn - nhead) >> 1;
+  if (nx.f != kNoFrame && nnp >= (unsigned long long)UNROLL * BLOCK) {     // the whole first step lies inside the frame: uniform
+    const unsigned char *npb = nb + nhead * 8ull;
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u)
+      ns.d[u] = load_pair(npb + ((unsigned long long)tid + (unsigned long long)u * BLOCK) * 16ull);
+    ns.have = true;
+    ns.frame = nx.f;
+  }
+}
+
+// ---- phase 1, bands 1..: replay the votes band 0 queued for later bands
+
+// A single's votes, if this band tracks its row.
+template <int FB, int MODE>
+__device__ __forceinline__ void replay_single(unsigned int e, const ScanK &k, const Band &b, unsigned int *cnt) {
+  int gy, gx;
+  q_cell(e, gy, gx);
+  if (gy >= b.t0 && gy < b.t1) bump_n<FB, MODE>(cnt, cell_of(b, k, gy, gx), q_run(e), k.vec_need);
+}
+
+template <int BLOCK, int FB, int MODE>
+__device__ __forceinline__ void replay_queue(const SpillQ &sq, const ScanK &k, const Band &b, unsigned int *cnt) {
+  const unsigned int tid = threadIdx.x;
+  // singles (from the back of the queue): one entry per lane, four loads in flight
+  const unsigned int nq = sq.tail[0];
+  const unsigned int *qs = sq.q + (sq.n - nq);       // entries nq-1 .. 0 in ascending address order
+  unsigned int i = tid;
+  for (; i + 3u * BLOCK < nq; i += 4u * BLOCK) {
+    unsigned int e[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) e[u] = qs[i + (unsigned int)u * BLOCK];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) replay_single<FB, MODE>(e[u], k, b, cnt);
+  }
+  for (; i < nq; i += BLOCK) replay_single<FB, MODE>(qs[i], k, b, cnt);
+  // spans (from the front): one span per LANE, which walks the span's cells.  Neighbouring lanes then vote in
+  // different rows / far-apart columns — different LDS words — where the cells of ONE span share words (8 cells of
+  // a 4-bit form to a word): no same-word serialisation of the returning ORs, and 64 spans in flight per wave.
+  const unsigned int nspans = sq.tail[1] >> 1;
+  unsigned int sp = tid;
+  bool have = sp < nspans;
+  unsigned int h0 = have ? sq.q[2u * sp] : 0u, h1 = have ? sq.q[2u * sp + 1u] : 0u;
+  while (have) {
+    const unsigned int nx = sp + BLOCK;                // the next header is on its way while this span votes
+    const bool more = nx < nspans;
+    const unsigned int n0 = more ? sq.q[2u * nx] : 0u, n1 = more ? sq.q[2u * nx + 1u] : 0u;
+    int gy, gx;
+    q_cell(h0, gy, gx);
+    if (gy >= b.t0 && gy < b.t1) bump_cells<FB, MODE>(cnt, cell_of(b, k, gy, gx), h1, q_run(h0), k.vec_need, (tid >> 2) & 7u);
+    h0 = n0; h1 = n1; sp = nx; have = more;
+  }
+}
+
+// ---- slices: publish this partial grid; the LAST workgroup of the frame to arrive sums them
+// (no workgroup ever waits for another: nothing to deadlock on).  This is the guide's
+// Guideline 16 hand-off, recipe R1 in its counter form (MI355X_MICROARCH.md "visibility",
+// valid-forms row "ONE lane of each storing workgroup ... an agent-scope atomic add ... the
+// workgroup whose add came last, told by the value its add returned"):
+//   producer  every payload byte leaves with a 16-byte WRITE-THROUGH (sc1) store: it goes
+//             through the XCD's L2 to memory and drops the L2 line, so no release fence
+//             (buffer_wbl2) is needed; EVERY storing wave drains (s_waitcnt vmcnt(0)); the
+//             workgroup barrier orders all drains before ONE lane's agent-scope ticket add
+//             (an atomic executes at the memory side, beyond the per-XCD L2s).
+//   consumer  the last arriver learns it from the add's return value; ONE lane executes the
+//             agent-scope acquire (buffer_inv sc1: drops this CU's L1 lines — the L1 is
+//             shared by the CU's waves, the invalidate is not per wave) and waits for it
+//             (vmcnt(0)); the barrier keeps every other wave's loads behind that wait; then
+//             plain loads.  The workspace is ordinary coarse-grained device memory
+//             (the context's scratch ring) that earlier launches may have cached on this CU: the
+//             acquire is what makes those stale L1 lines unreachable.  A line of another
+//             workgroup's tile cannot sit stale in THIS XCD's L2 from inside the launch (no
+//             wave reads a tile before the ticket says it is complete), and lines cached by
+//             earlier launches were dropped by the kernel-boundary invalidate.
+// Results therefore do not depend on dispatch order or XCD placement; exercised with a warm
+// L1 and a reused workspace by tests/test_gpu_parity.py::test_scan_frame_slices_under_load.
+// Returns whether this workgroup arrived last (workgroup-uniform): its tile then holds the frame's sum and it goes on
+// to the cluster test; every other workgroup is done.  Four barriers for the last arriver, two for the others.
+template <int BLOCK, int FB, int MODE>
+__device__ __forceinline__ bool hand_over_slices(const Tile &t, const ScanK &k, unsigned int f, int slice,
+                                                 unsigned int *slice_ws, unsigned int *tickets) {
+  const int tid = threadIdx.x;
+  const size_t words = (size_t)k.cnt_words;
+  unsigned int *cnt = t.cnt;
+  unsigned int *mine = slice_ws + ((size_t)f * (size_t)k.slices + (size_t)slice) * words;
+  {
+    const u32x4 *c4 = reinterpret_cast<const u32x4 *>(cnt);
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(mine, 0, k.cnt_words * 4, 0x00020000);
+    for (int i = tid; i < (k.cnt_words >> 2); i += BLOCK)
+      __builtin_amdgcn_raw_buffer_store_b128(c4[i], rsrc, i * 16, 0, /*aux: sc1*/ 16);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0)
+    *t.ticket = __hip_atomic_fetch_add(&tickets[f], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if (*t.ticket != (unsigned int)(k.slices - 1)) return false;          // not the last: done
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __syncthreads();
+  for (int s2 = 0; s2 < k.slices; ++s2) {
+    if (s2 == slice) continue;
+    const u32x4 *g4 = reinterpret_cast<const u32x4 *>(slice_ws + ((size_t)f * (size_t)k.slices + (size_t)s2) * words);
+    u32x4 *c4 = reinterpret_cast<u32x4 *>(cnt);
+    for (int i = tid; i < (k.cnt_words >> 2); i += BLOCK) {
+      const u32x4 o = g4[i];
+      u32x4 m = c4[i];
+      m.x = combine_words<FB, MODE>(m.x, o.x, k.vec_need);
+      m.y = combine_words<FB, MODE>(m.y, o.y, k.vec_need);
+      m.z = combine_words<FB, MODE>(m.z, o.z, k.vec_need);
+      m.w = combine_words<FB, MODE>(m.w, o.w, k.vec_need);
+      c4[i] = m;
+    }
+  }
+  __syncthreads();
+  return true;
+}
+
+// ---- phase 2a: the 64-bit masks of active cells of grid rows [g0, g0 + nrows) -> mask rows 0.. (rows outside the
+// band's tracked rows, cells outside the grid: inactive)
+template <int BLOCK, int FB, int MODE>
+__device__ __forceinline__ void row_masks(const Tile &t, const ScanK &k, const Band &b, int g0, int nrows) {
+  const int tid = threadIdx.x, W = k.W;
+  const unsigned int *cnt = t.cnt;
+  unsigned long long *mask = t.mask;
+  if constexpr (FB == 32) {
+    // 32-bit counters, small grids: FOUR lanes per (mask row, word), 16 cells each, joined
+    // by two xor-shuffles.  Cells are visited in a rotated order so that the 64 lanes of a wave
+    // (16 words that lie 64 counters apart x 4 quarters) hit 64 different LDS banks per step.
+    const int lane = tid & 63;
+    const int sub = lane & 3, rot = (lane >> 2) & 15;
+    const int ntask = nrows * W * 4;
+    for (int t0q = 0; t0q < ntask; t0q += BLOCK) {             // uniform trip count: shuffles below
+      const int tk = t0q + tid;
+      const int tw = tk >> 2;
+      const int j = tw / W, w = tw - j * W;
+      const int g = g0 + j;                          // grid row of this mask row
+      const int ncell = min(64, k.gw - w * 64) - sub * 16;   // cells of this lane's quarter inside the grid
+      unsigned int q = 0u;                           // the quarter's 16 "active" bits
+      if (tk < ntask && g >= b.t0 && g < b.t1 && ncell > 0) {     // outside the grid = inactive
+        const unsigned int *row = cnt + (size_t)(g - b.t0) * k.gw + w * 64 + sub * 16;
+        const int last = min(ncell, 16) - 1;
+        // four LDS reads in flight per step; the loop is NOT fully unrolled on purpose: unrolled,
+        // the per-step lane constants (rotated column, its address, its 64-bit bit) of all 16
+        // steps were hoisted out of the task loop and held ~64 VGPRs for the whole kernel
+#pragma unroll 1
+        for (int c = 0; c < 16; c += 4) {
+          int cc[4];
+          unsigned int v[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            cc[u] = (c + u + rot) & 15;
+            v[u] = row[min(cc[u], last)];            // always inside the row: no branch around the read
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u) q |= (unsigned int)(cc[u] <= last && v[u] >= k.active_min) << cc[u];
+        }
+      }
+      unsigned long long m = (unsigned long long)q << (sub * 16);
+      m |= __shfl_xor(m, 1);
+      m |= __shfl_xor(m, 2);
+      if (tk < ntask && sub == 0) mask[(size_t)j * W + w] = m;
+    }
+  } else {
+    // packed counters, big grids: one LANE per (mask row, word) — it reads the 2*FB
+    // counter words that hold its 64 cells and squeezes the "active" bit of every field into
+    // the mask (the wave-per-word ballot form took 140 us per 960x540 frame: 17 % of the
+    // workgroup's life, un-overlapped whenever one workgroup owns the CU)
+    const int ntask = nrows * W;
+    for (int tk = tid; tk < ntask; tk += BLOCK) {
+      const int j = tk / W, w = tk - j * W;
+      const int g = g0 + j;
+      unsigned long long m = 0ull;
+      if (g >= b.t0 && g < b.t1)
+        m = mask_word<FB, MODE>(cnt, (unsigned int)((g - b.t0) * k.gw + w * 64), min(64, k.gw - w * 64), k.vec_need);
+      mask[(size_t)j * W + w] = m;
+    }
+  }
+}
+
+// ---- phase 2b: this lane's count of centre cells with an active 4-neighbour, centre rows <-> mask rows 1 .. nrows
+template <int BLOCK>
+__device__ __forceinline__ unsigned int count_centres(const unsigned long long *mask, const ScanK &k, int nrows) {
+  const int tid = threadIdx.x, W = k.W;
+  unsigned int local = 0u;
+  const int ntask = nrows * W;
+  for (int tk = tid; tk < ntask; tk += BLOCK) {
+    const int r = tk / W, w = tk - r * W;
+    const unsigned long long *mr = mask + (size_t)(r + 1) * W;
+    const unsigned long long m = mr[w];
+    if (m == 0ull) continue;
+    const unsigned long long up = mr[w - W], dn = mr[w + W];
+    const unsigned long long lcarry = (w > 0) ? (mr[w - 1] >> 63) : 0ull;
+    const unsigned long long rcarry = (w + 1 < W) ? (mr[w + 1] << 63) : 0ull;
+    const unsigned long long nb = (m << 1) | lcarry | (m >> 1) | rcarry | up | dn;
+    // centres are x in [1, gw-2]  (:280)
+    const int lo = max(1 - w * 64, 0), hi = min(k.gw - 1 - w * 64, 64);   // bits [lo,hi)
+    unsigned long long valid = 0ull;
+    if (hi > lo) {
+      valid = (hi >= 64) ? ~0ull : ((1ull << hi) - 1ull);
+      valid &= ~((1ull << lo) - 1ull);
+    }
+    local += (unsigned int)__popcll(m & nb & valid);
+  }
+  return local;
+}
+
+// ---- phase 2: chunks of centre rows [c0+q0, c0+q0+qn); mask row j <-> grid row c0+q0-1+j.  Two barriers per chunk.
+template <int BLOCK, int FB, int MODE>
+__device__ __forceinline__ unsigned int cluster_count(const Tile &t, const ScanK &k, const Band &b) {
+  unsigned int local = 0u;
+  const int crows = b.c1 - b.c0;
+  for (int q0 = 0; q0 < crows; q0 += k.chunk_rows) {
+    const int qn = min(k.chunk_rows, crows - q0);
+    row_masks<BLOCK, FB, MODE>(t, k, b, b.c0 + q0 - 1, qn + 2);
+    __syncthreads();
+    local += count_centres<BLOCK>(t.mask, k, qn);
+    __syncthreads();                                   // masks / counters are rewritten next
+  }
+  return local;
+}
+
 // One work item (the list entry `me`, or a slice of it) by one workgroup.  `has_next`: the same workgroup scans
 // item + 1 (the list entry parked at `stage_next`: readable after this item's first barrier) right after this one.
 // Frames without side data (:219-221) never get here: plan_scatter_kernel has answered them.
@@ -608,375 +1010,63 @@ __device__ __forceinline__ void scan_item(
     const unsigned int item, const ScanK &k, unsigned char *__restrict__ flags,
     unsigned int *spill_q, unsigned int *slice_ws, unsigned int *tickets, unsigned int *lds,
     NextStep<UNROLL> &ns, const bool has_next) {
-  typedef typename RawOf<REC>::type Raw;
-  const int tid = threadIdx.x;
   PT_DECL;
-  const unsigned int wi = item_entry<SPILL>(item, k.slices);
-  const int slice = (SPILL || k.slices == 1) ? 0 : (int)(item - wi * (unsigned int)k.slices);
+  const bool sliced = !SPILL && k.slices > 1;
+  const int slice = sliced ? (int)(item - item_entry<SPILL>(item, k.slices) * (unsigned int)k.slices) : 0;
   const unsigned int f = me.f;
   // A pre-issued step is consumed only by the frame it was loaded for: whatever early-out a frame takes
   // between here and its streaming loop, a step that was not consumed can never leak its votes into a LATER frame.
   if (ns.have && ns.frame != f) ns.have = false;
 
   unsigned long long r0 = me.r0, r1 = me.r1;
-  const unsigned long long q0 = r0;            // the frame's spill queue: one slot per record
-  if (!SPILL && k.slices > 1) {                // this workgroup's share of the frame's records
-    const unsigned long long n = r1 - r0, per = (n + (unsigned long long)k.slices - 1ull) / (unsigned long long)k.slices;
-    const unsigned long long a = r0 + min(n, per * (unsigned long long)slice);
-    const unsigned long long b = r0 + min(n, per * (unsigned long long)(slice + 1));
-    r0 = a;
-    r1 = b;
-  }
-  const int W = k.W;
-  unsigned int *cnt = lds;                                         // packed [trows][gw] fields
-  unsigned long long *mask =
-      reinterpret_cast<unsigned long long *>(lds + k.cnt_words);   // [chunk_rows+2][W]
-  unsigned int *total = reinterpret_cast<unsigned int *>(mask + (size_t)k.mask_rows * W);
-  unsigned int *ticket = total + 1;
+  const Tile t = carve_tile(lds, k);
   SpillQ sq;
-  sq.q = SPILL ? spill_q + q0 : nullptr;
+  sq.q = SPILL ? spill_q + r0 : nullptr;                           // the frame's spill queue: one slot per record
+  if (sliced) slice_records(k, slice, r0, r1);
   sq.n = (unsigned int)min(r1 - r0, 0xffffffffull);
-  sq.tail = total + 2;                                             // two words: singles, span dwords
+  sq.tail = t.tail;
   sq.q_lo = min(k.y_hi, k.y_lo + k.band_rows) - 1;                 // band 0's last centre row
 
   const int n_bands = SPILL ? k.bands : 1;
   unsigned int local = 0;
   for (int band = 0; band < n_bands; ++band) {
-    // Band geometry: centres [c0,c1), tracked counter rows [t0,t1) (one halo row each side).
-    const int c0 = k.y_lo + band * k.band_rows;
-    const int c1 = min(k.y_hi, c0 + k.band_rows);
-    const int t0 = max(c0 - 1, 0);
-    const int t1 = min(c1 + 1, k.gh);
-    const int trows = t1 - t0;                 // may be <= 0 for an empty analysed range
+    const Band b = band_rows(k, band);
+    const bool votes = b.t1 > b.t0 && k.vec_need != 0u;            // vec_need == 0: every cell is active anyway
 
-    // ---- phase 0: zero counters (and, once, the centre total and the queue tail)
-    {
-      u32x4 *c4 = reinterpret_cast<u32x4 *>(cnt);
-      const int n4 = k.cnt_words >> 2;
-      for (int i = tid; i < n4; i += BLOCK) c4[i] = (u32x4){0u, 0u, 0u, 0u};
-      if (band == 0 && tid == 0) { *total = 0u; sq.tail[0] = 0u; sq.tail[1] = 0u; }
-    }
+    // ---- phase 0
+    zero_tile<BLOCK>(t, k, band == 0);
     __syncthreads();
     PT_ADD(0);
 
-    // ---- phase 1
-    if (band == 0) {                           // stream the records (HBM, exactly once per frame)
-      if (trows > 0 && k.vec_need != 0u) {     // vec_need == 0: every cell is active anyway
-        const unsigned char *base = mv + r0 * (unsigned long long)REC;
-        unsigned long long n = r1 - r0;
-        if constexpr (REC == 40) {
-          // Line alignment.  A wave instruction of the loops below covers 64 records = 2560 bytes = exactly 20
-          // 128-byte lines IF the stream starts on a line; a frame that starts mid-line (real footage: every
-          // frame has its own record count) makes every instruction touch 21 lines, and the shared edge lines
-          // are fetched twice, by two different instructions (PMC, ragged 960x540 frames: 1.021 x the
-          // algorithmic bytes).  40 h = -start (mod 128) has a solution h < 16 whenever the start is 8-byte
-          // aligned (5 * 13 = 1 mod 16): the first h records go to lanes 0..h-1, the streams start on a line.
-          const unsigned int r = (unsigned int)((uintptr_t)base & 127u);
-          if ((r & 7u) == 0u) {
-            unsigned long long h = (unsigned long long)((13u * ((16u - (r >> 3)) & 15u)) & 15u);
-            h = h < n ? h : n;
-            if ((unsigned long long)tid < h)
-              vote<FB, MODE, SPILL>(decode(load_rec<REC>(base + (unsigned long long)tid * REC)), k, t0, t1, cnt, sq);
-            base += h * (unsigned long long)REC;
-            n -= h;
-          }
-        }
-        unsigned long long i = tid;
-        constexpr unsigned long long STEP = (unsigned long long)UNROLL * BLOCK;
-        constexpr unsigned long long LAST = (unsigned long long)(UNROLL - 1) * BLOCK;
-        if constexpr (REC == 8) {
-          // Compact records: 16-byte loads of TWO records per lane (a wave instruction covers 1 KB),
-          // UNROLL pairs in flight per lane — with 8-byte loads a CU keeps too few bytes in flight
-          // to cover the HBM latency (measured 4.96 TB/s of compact bytes on 1080p).  The pair
-          // stream starts at the first record on a 128-byte line (compact_head: up to 15 head records go to
-          // lanes 0..14, so that a wave instruction covers exactly 8 lines); lane 0 takes an odd last record.
-          const unsigned long long head = compact_head(base, n);
-          const unsigned char *pbase = base + head * 8ull;
-          const unsigned long long np = (n - head) >> 1;            // pairs
-          if ((unsigned long long)tid < head)
-            vote<FB, MODE, SPILL>(decode(load_compact(base + (unsigned long long)tid * 8ull)), k, t0, t1, cnt, sq);
-          if (tid == 0 && ((n - head) & 1ull) != 0ull)
-            vote<FB, MODE, SPILL>(decode(load_compact(base + (n - 1ull) * 8ull)), k, t0, t1, cnt, sq);
-          unsigned long long p = tid;
-          if (ns.have) {                       // this frame's first step (ns.frame == f, checked on entry) was issued during
-            ns.have = false;                   // the previous frame's cluster test
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-              vote<FB, MODE, SPILL>(decode((u32x2){ns.d[u].x, ns.d[u].y}), k, t0, t1, cnt, sq);
-              vote<FB, MODE, SPILL>(decode((u32x2){ns.d[u].z, ns.d[u].w}), k, t0, t1, cnt, sq);
-            }
-            p += STEP;
-          }
-          for (; p + LAST < np; p += STEP) {
-            u32x4 d[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) d[u] = load_pair(pbase + (p + (unsigned long long)u * BLOCK) * 16ull);
-            __builtin_amdgcn_sched_barrier(0);   // every load of the step is issued before the first one is consumed
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-              vote<FB, MODE, SPILL>(decode((u32x2){d[u].x, d[u].y}), k, t0, t1, cnt, sq);
-              vote<FB, MODE, SPILL>(decode((u32x2){d[u].z, d[u].w}), k, t0, t1, cnt, sq);
-            }
-          }
-          {
-            // the rest (fewer than one step: at most UNROLL pairs per lane), every load issued before the first
-            // vote — a frame smaller than one step (SD streams) costs ONE memory round trip, not one per pair
-            u32x4 d[UNROLL];
-            bool ok[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-              const unsigned long long q = p + (unsigned long long)u * BLOCK;
-              ok[u] = q < np;
-              d[u] = ok[u] ? load_pair(pbase + q * 16ull) : (u32x4){0u, 0u, 0u, 0u};
-            }
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u)
-              if (ok[u]) {
-                vote<FB, MODE, SPILL>(decode((u32x2){d[u].x, d[u].y}), k, t0, t1, cnt, sq);
-                vote<FB, MODE, SPILL>(decode((u32x2){d[u].z, d[u].w}), k, t0, t1, cnt, sq);
-              }
-          }
-          i = n;                                                    // nothing left for the generic tail loop
-        } else {
-          // main body: UNROLL independent loads in flight per lane
-          for (; i + LAST < n; i += STEP) {
-            Raw d[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) d[u] = load_rec<REC>(base + (i + (unsigned long long)u * BLOCK) * REC);
-            // (the scheduler sinks loads 2..UNROLL below the wait for load 1; forcing them up front with
-            //  a sched_barrier measured -1..-2 % here, +7 % in the compact loop above: left as it is)
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) vote<FB, MODE, SPILL, true>(decode(d[u]), k, t0, t1, cnt, sq);
-          }
-        }
-        if (i < n) {
-          // the rest (fewer than one step: at most UNROLL records per lane), every load issued before the first
-          // vote — a frame smaller than one step (SD streams) costs ONE memory round trip, not one per record
-          constexpr int TU = UNROLL > 4 ? UNROLL : 4;
-          Raw d[TU];
-          bool ok[TU];
-#pragma unroll
-          for (int u = 0; u < TU; ++u) {
-            const unsigned long long q = i + (unsigned long long)u * BLOCK;
-            ok[u] = q < n;
-            if (ok[u]) d[u] = load_rec<REC>(base + q * REC);
-          }
-#pragma unroll
-          for (int u = 0; u < TU; ++u)
-            if (ok[u]) vote<FB, MODE, SPILL>(decode(d[u]), k, t0, t1, cnt, sq);
-        }
+    // ---- phase 1: band 0 streams the records and queues what later bands need, those replay the queue
+    if (band == 0) {
+      if (votes) {
+        if constexpr (REC == 8) stream_compact<BLOCK, UNROLL, FB, MODE, SPILL>(mv + r0 * 8ull, r1 - r0, k, b, t.cnt, sq, ns);
+        else stream_mv40<BLOCK, UNROLL, FB, MODE, SPILL>(mv + r0 * 40ull, r1 - r0, k, b, t.cnt, sq);
       }
-      if constexpr (REC == 8 && !SPILL) {
-        if (has_next && k.slices == 1 && k.vec_need != 0u && trows > 0) {   // exactly when the next frame's phase 1 runs
-          // next frame of the list (parked in LDS when the workgroup started): same pair alignment as above
-          const WorkItem nx = staged_item(stage_next, 0u);
-          const unsigned long long a = nx.r0, b = nx.r1;
-          const bool sdn = nx.f != kNoFrame;
-          const unsigned char *nb = mv + a * 8ull;
-          const unsigned long long nn = b - a;
-          const unsigned long long nhead = compact_head(nb, nn);
-          const unsigned long long nnp = (nn - nhead) >> 1;
-          if (sdn && nnp >= (unsigned long long)UNROLL * BLOCK) {     // the whole first step lies inside the frame: uniform
-            const unsigned char *npb = nb + nhead * 8ull;
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u)
-              ns.d[u] = load_pair(npb + ((unsigned long long)tid + (unsigned long long)u * BLOCK) * 16ull);
-            ns.have = true;
-            ns.frame = nx.f;
-          }
-        }
+      if constexpr (REC == 8 && !SPILL) {                          // (exactly when the next frame's phase 1 runs)
+        if (has_next && k.slices == 1 && votes) issue_next_step<BLOCK, UNROLL>(mv, stage_next, ns);
       }
       // queue stores of every wave have left the CU before any wave of this workgroup replays them
       if constexpr (SPILL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {                                   // replay the votes band 0 queued for later bands
-      // singles (from the back of the queue): one entry per lane, four loads in flight
-      const unsigned int nq = sq.tail[0];
-      const unsigned int *qs = sq.q + (sq.n - nq);       // entries nq-1 .. 0 in ascending address order
-      unsigned int i = (unsigned int)tid;
-      for (; i + 3u * BLOCK < nq; i += 4u * BLOCK) {
-        unsigned int e[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) e[u] = qs[i + (unsigned int)u * BLOCK];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int gy = (int)((e[u] >> 15) & 0x7fffu), gx = (int)(e[u] & 0x7fffu);
-          if (gy >= t0 && gy < t1) bump_n<FB, MODE>(cnt, (unsigned int)((gy - t0) * k.gw + gx), (e[u] >> 30) + 1u, k.vec_need);
-        }
-      }
-      for (; i < nq; i += BLOCK) {
-        const unsigned int e = qs[i];
-        const int gy = (int)((e >> 15) & 0x7fffu), gx = (int)(e & 0x7fffu);
-        if (gy >= t0 && gy < t1) bump_n<FB, MODE>(cnt, (unsigned int)((gy - t0) * k.gw + gx), (e >> 30) + 1u, k.vec_need);
-      }
-      // spans (from the front): one span per LANE, which walks the span's cells.  Neighbouring lanes then vote in
-      // different rows / far-apart columns — different LDS words — where the cells of ONE span share words (8 cells of
-      // a 4-bit form to a word): no same-word serialisation of the returning ORs, and 64 spans in flight per wave.
-      const unsigned int nspans = sq.tail[1] >> 1;
-      unsigned int sp = (unsigned int)tid;
-      bool have = sp < nspans;
-      unsigned int h0 = have ? sq.q[2u * sp] : 0u, h1 = have ? sq.q[2u * sp + 1u] : 0u;
-      while (have) {
-        const unsigned int nx = sp + BLOCK;                // the next header is on its way while this span votes
-        const bool more = nx < nspans;
-        const unsigned int n0 = more ? sq.q[2u * nx] : 0u, n1 = more ? sq.q[2u * nx + 1u] : 0u;
-        const int gy = (int)((h0 >> 15) & 0x7fffu), gx = (int)(h0 & 0x7fffu);
-        if (gy >= t0 && gy < t1) {
-          bump_cells<FB, MODE>(cnt, (unsigned int)((gy - t0) * k.gw + gx), h1, (h0 >> 30) + 1u, k.vec_need,
-                               ((unsigned int)tid >> 2) & 7u);
-        }
-        h0 = n0; h1 = n1; sp = nx; have = more;
-      }
+    } else {
+      replay_queue<BLOCK, FB, MODE>(sq, k, b, t.cnt);
     }
     __syncthreads();
     PT_ADD(band == 0 ? 1 : 2);
 
-    // ---- slices: publish this partial grid; the LAST workgroup of the frame to arrive sums them
-    // (no workgroup ever waits for another: nothing to deadlock on).  This is the guide's
-    // Guideline 16 hand-off, recipe R1 in its counter form (MI355X_MICROARCH.md "visibility",
-    // valid-forms row "ONE lane of each storing workgroup ... an agent-scope atomic add ... the
-    // workgroup whose add came last, told by the value its add returned"):
-    //   producer  every payload byte leaves with a 16-byte WRITE-THROUGH (sc1) store: it goes
-    //             through the XCD's L2 to memory and drops the L2 line, so no release fence
-    //             (buffer_wbl2) is needed; EVERY storing wave drains (s_waitcnt vmcnt(0)); the
-    //             workgroup barrier orders all drains before ONE lane's agent-scope ticket add
-    //             (an atomic executes at the memory side, beyond the per-XCD L2s).
-    //   consumer  the last arriver learns it from the add's return value; ONE lane executes the
-    //             agent-scope acquire (buffer_inv sc1: drops this CU's L1 lines — the L1 is
-    //             shared by the CU's waves, the invalidate is not per wave) and waits for it
-    //             (vmcnt(0)); the barrier keeps every other wave's loads behind that wait; then
-    //             plain loads.  The workspace is ordinary coarse-grained device memory
-    //             (the context's scratch ring) that earlier launches may have cached on this CU: the
-    //             acquire is what makes those stale L1 lines unreachable.  A line of another
-    //             workgroup's tile cannot sit stale in THIS XCD's L2 from inside the launch (no
-    //             wave reads a tile before the ticket says it is complete), and lines cached by
-    //             earlier launches were dropped by the kernel-boundary invalidate.
-    // Results therefore do not depend on dispatch order or XCD placement; exercised with a warm
-    // L1 and a reused workspace by tests/test_gpu_parity.py::test_scan_frame_slices_under_load.
-    if (!SPILL && k.slices > 1) {
-      const size_t words = (size_t)k.cnt_words;
-      unsigned int *mine = slice_ws + ((size_t)f * (size_t)k.slices + (size_t)slice) * words;
-      {
-        const u32x4 *c4 = reinterpret_cast<const u32x4 *>(cnt);
-        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(mine, 0, k.cnt_words * 4, 0x00020000);
-        for (int i = tid; i < (k.cnt_words >> 2); i += BLOCK)
-          __builtin_amdgcn_raw_buffer_store_b128(c4[i], rsrc, i * 16, 0, /*aux: sc1*/ 16);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0)
-        *ticket = __hip_atomic_fetch_add(&tickets[f], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __syncthreads();
-      if (*ticket != (unsigned int)(k.slices - 1)) { PT_ADD(3); PT_FLUSH(); return; }   // not the last: done
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __syncthreads();
-      for (int s2 = 0; s2 < k.slices; ++s2) {
-        if (s2 == slice) continue;
-        const u32x4 *g4 = reinterpret_cast<const u32x4 *>(slice_ws + ((size_t)f * (size_t)k.slices + (size_t)s2) * words);
-        u32x4 *c4 = reinterpret_cast<u32x4 *>(cnt);
-        for (int i = tid; i < (k.cnt_words >> 2); i += BLOCK) {
-          const u32x4 o = g4[i];
-          u32x4 m = c4[i];
-          m.x = combine_words<FB, MODE>(m.x, o.x, k.vec_need);
-          m.y = combine_words<FB, MODE>(m.y, o.y, k.vec_need);
-          m.z = combine_words<FB, MODE>(m.z, o.z, k.vec_need);
-          m.w = combine_words<FB, MODE>(m.w, o.w, k.vec_need);
-          c4[i] = m;
-        }
-      }
-      __syncthreads();
-    }
-
+    // ---- slices: every workgroup of the frame but the last to arrive is done after the hand-over
+    if (sliced && !hand_over_slices<BLOCK, FB, MODE>(t, k, f, slice, slice_ws, tickets)) { PT_ADD(3); PT_FLUSH(); return; }
     PT_ADD(3);
-    // ---- phase 2: chunks of centre rows [c0+q0, c0+q0+qn); mask row j <-> grid row c0+q0-1+j
-    const int crows = c1 - c0;
-    for (int q0r = 0; q0r < crows; q0r += k.chunk_rows) {
-      const int qn = min(k.chunk_rows, crows - q0r);
-      if constexpr (FB == 32) {
-        // 2a (32-bit counters, small grids): FOUR lanes per (mask row, word), 16 cells each, joined
-        // by two xor-shuffles.  Cells are visited in a rotated order so that the 64 lanes of a wave
-        // (16 words that lie 64 counters apart x 4 quarters) hit 64 different LDS banks per step.
-        const int lane = tid & 63;
-        const int sub = lane & 3, rot = (lane >> 2) & 15;
-        const int ntask = (qn + 2) * W * 4;
-        for (int t0q = 0; t0q < ntask; t0q += BLOCK) {             // uniform trip count: shuffles below
-          const int t = t0q + tid;
-          const int tw = t >> 2;
-          const int j = tw / W, w = tw - j * W;
-          const int g = c0 + q0r - 1 + j;                // grid row of this mask row
-          const int ncell = min(64, k.gw - w * 64) - sub * 16;   // cells of this lane's quarter inside the grid
-          unsigned int q = 0u;                           // the quarter's 16 "active" bits
-          if (t < ntask && g >= t0 && g < t1 && ncell > 0) {     // outside the grid = inactive
-            const unsigned int *row = cnt + (size_t)(g - t0) * k.gw + w * 64 + sub * 16;
-            const int last = min(ncell, 16) - 1;
-            // four LDS reads in flight per step; the loop is NOT fully unrolled on purpose: unrolled,
-            // the per-step lane constants (rotated column, its address, its 64-bit bit) of all 16
-            // steps were hoisted out of the task loop and held ~64 VGPRs for the whole kernel
-#pragma unroll 1
-            for (int c = 0; c < 16; c += 4) {
-              int cc[4];
-              unsigned int v[4];
-#pragma unroll
-              for (int u = 0; u < 4; ++u) {
-                cc[u] = (c + u + rot) & 15;
-                v[u] = row[min(cc[u], last)];            // always inside the row: no branch around the read
-              }
-#pragma unroll
-              for (int u = 0; u < 4; ++u) q |= (unsigned int)(cc[u] <= last && v[u] >= k.active_min) << cc[u];
-            }
-          }
-          unsigned long long m = (unsigned long long)q << (sub * 16);
-          m |= __shfl_xor(m, 1);
-          m |= __shfl_xor(m, 2);
-          if (t < ntask && sub == 0) mask[(size_t)j * W + w] = m;
-        }
-      } else {
-        // 2a (packed counters, big grids): one LANE per (mask row, word) — it reads the 2*FB
-        // counter words that hold its 64 cells and squeezes the "active" bit of every field into
-        // the mask (the wave-per-word ballot form took 140 us per 960x540 frame: 17 % of the
-        // workgroup's life, un-overlapped whenever one workgroup owns the CU)
-        const int ntask = (qn + 2) * W;
-        for (int t = tid; t < ntask; t += BLOCK) {
-          const int j = t / W, w = t - j * W;
-          const int g = c0 + q0r - 1 + j;
-          unsigned long long m = 0ull;
-          if (g >= t0 && g < t1)
-            m = mask_word<FB, MODE>(cnt, (unsigned int)((g - t0) * k.gw + w * 64), min(64, k.gw - w * 64), k.vec_need);
-          mask[(size_t)j * W + w] = m;
-        }
-      }
-      __syncthreads();
-      {  // 2b: centre cells with an active 4-neighbour
-        const int ntask = qn * W;
-        for (int t = tid; t < ntask; t += BLOCK) {
-          const int r = t / W, w = t - r * W;            // centre row c0+q0r+r -> mask row r+1
-          const unsigned long long *mr = mask + (size_t)(r + 1) * W;
-          const unsigned long long m = mr[w];
-          if (m == 0ull) continue;
-          const unsigned long long up = mr[w - W], dn = mr[w + W];
-          const unsigned long long lcarry = (w > 0) ? (mr[w - 1] >> 63) : 0ull;
-          const unsigned long long rcarry = (w + 1 < W) ? (mr[w + 1] << 63) : 0ull;
-          const unsigned long long nb = (m << 1) | lcarry | (m >> 1) | rcarry | up | dn;
-          // centres are x in [1, gw-2]  (:280)
-          const int lo = max(1 - w * 64, 0), hi = min(k.gw - 1 - w * 64, 64);   // bits [lo,hi)
-          unsigned long long valid = 0ull;
-          if (hi > lo) {
-            valid = (hi >= 64) ? ~0ull : ((1ull << hi) - 1ull);
-            valid &= ~((1ull << lo) - 1ull);
-          }
-          local += (unsigned int)__popcll(m & nb & valid);
-        }
-      }
-      __syncthreads();                                   // masks / counters are rewritten next
-    }
+
+    // ---- phase 2
+    local += cluster_count<BLOCK, FB, MODE>(t, k, b);
     PT_ADD(4);
   }
-  if (local) atomicAdd(total, local);
+  if (local) atomicAdd(t.total, local);
   __syncthreads();
 
-  if (tid == 0) store_flag(flags, f, (*total >= k.clust_need) ? 1 : 0, k.sys_flags);
+  if (threadIdx.x == 0) store_flag(flags, f, (*t.total >= k.clust_need) ? 1 : 0, k.sys_flags);
   PT_FLUSH();
 }
 
