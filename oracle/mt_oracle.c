@@ -146,6 +146,23 @@ static int scan_range_frames(const mt_scan_params *p, const mt_mv *mv, const uin
   return MT_OK;
 }
 
+/* The same over mto_check_frame_count: centres[f] = the frame's full count, flags (may be NULL) as above. */
+static int count_range_frames(const mt_scan_params *p, const mt_mv *mv, const uint64_t *frame_off,
+                              const uint8_t *has_sd, uint32_t f0, uint32_t f1, uint8_t *flags,
+                              uint32_t *centres, uint8_t *grid) {
+  for (uint32_t f = f0; f < f1; ++f) {
+    uint64_t a = frame_off[f], b = frame_off[f + 1];
+    if (b < a) return MT_ERR_INVALID;
+    int sd = has_sd ? (has_sd[f] != 0) : (b > a);
+    int64_t n = 0;
+    int r = mto_check_frame_count(p, mv + a, (int64_t)(b - a), sd, grid, &n);
+    if (r < 0) return -r;
+    centres[f] = (uint32_t)n;
+    if (flags) flags[f] = (uint8_t)r;
+  }
+  return MT_OK;
+}
+
 int mto_scan_frames(const mt_scan_params *p, const mt_mv *mv, const uint64_t *frame_off,
                     const uint8_t *has_sd, uint32_t n_frames, uint8_t *flags) {
   if (!params_ok(p)) return MT_ERR_INVALID;
@@ -164,37 +181,45 @@ typedef struct {
   const uint64_t *frame_off;
   const uint8_t *has_sd;
   uint8_t *flags;
+  uint32_t *centres;                 /* NULL: flags only, through the early-exit path */
   uint32_t f0, f1;
   int rc;
 } mt_job;
+
+/* Static split balanced by RECORDS, so every thread streams about the same bytes: thread t of nthreads takes
+ * frames [f, split_end), where f is the end of thread t - 1 (0 for t == 0). */
+static uint32_t split_end(const uint64_t *frame_off, uint32_t n_frames, int nthreads, int t, uint32_t f) {
+  const uint64_t total = frame_off[n_frames] - frame_off[0];
+  uint64_t target = frame_off[0] + (total * (uint64_t)(t + 1)) / (uint64_t)nthreads;
+  uint32_t e = f;
+  if (t == nthreads - 1) e = n_frames;
+  else while (e < n_frames && frame_off[e + 1] <= target) ++e;
+  if (e == f && f < n_frames && (n_frames - f) > (uint32_t)(nthreads - 1 - t)) e = f + 1;
+  return e;
+}
 
 static void *mt_worker(void *arg) {
   mt_job *j = (mt_job *)arg;
   uint8_t *grid = (uint8_t *)malloc((size_t)j->p->grid_w * j->p->grid_h);
   if (!grid) { j->rc = MT_ERR_NOMEM; return NULL; }
-  j->rc = scan_range_frames(j->p, j->mv, j->frame_off, j->has_sd, j->f0, j->f1, j->flags, grid);
+  j->rc = j->centres ? count_range_frames(j->p, j->mv, j->frame_off, j->has_sd, j->f0, j->f1, j->flags, j->centres, grid)
+                     : scan_range_frames(j->p, j->mv, j->frame_off, j->has_sd, j->f0, j->f1, j->flags, grid);
   free(grid);
   return NULL;
 }
 
-int mto_scan_frames_mt(const mt_scan_params *p, const mt_mv *mv, const uint64_t *frame_off,
-                       const uint8_t *has_sd, uint32_t n_frames, uint8_t *flags, int nthreads) {
-  if (nthreads <= 1 || n_frames < 2) return mto_scan_frames(p, mv, frame_off, has_sd, n_frames, flags);
-  if (!params_ok(p) || !frame_off || !flags) return MT_ERR_INVALID;
+/* Frames split statically over `nthreads` pthreads: flags only (centres == NULL, the early-exit path) or the
+ * full centre counts. */
+static int run_split(const mt_scan_params *p, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd,
+                     uint32_t n_frames, uint8_t *flags, uint32_t *centres, int nthreads) {
   if ((uint32_t)nthreads > n_frames) nthreads = (int)n_frames;
   pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * nthreads);
   mt_job *jobs = (mt_job *)malloc(sizeof(mt_job) * nthreads);
   if (!th || !jobs) { free(th); free(jobs); return MT_ERR_NOMEM; }
-  /* Static split balanced by RECORDS, so every thread streams about the same bytes. */
-  uint64_t total = frame_off[n_frames] - frame_off[0];
   uint32_t f = 0;
   for (int t = 0; t < nthreads; ++t) {
-    uint64_t target = frame_off[0] + (total * (uint64_t)(t + 1)) / (uint64_t)nthreads;
-    uint32_t e = f;
-    if (t == nthreads - 1) e = n_frames;
-    else while (e < n_frames && frame_off[e + 1] <= target) ++e;
-    if (e == f && f < n_frames && (n_frames - f) > (uint32_t)(nthreads - 1 - t)) e = f + 1;
-    jobs[t] = (mt_job){p, mv, frame_off, has_sd, flags, f, e, MT_OK};
+    uint32_t e = split_end(frame_off, n_frames, nthreads, t, f);
+    jobs[t] = (mt_job){p, mv, frame_off, has_sd, flags, centres, f, e, MT_OK};
     f = e;
   }
   for (int t = 0; t < nthreads; ++t) pthread_create(&th[t], NULL, mt_worker, &jobs[t]);
@@ -205,6 +230,27 @@ int mto_scan_frames_mt(const mt_scan_params *p, const mt_mv *mv, const uint64_t 
   }
   free(th);
   free(jobs);
+  return rc;
+}
+
+int mto_scan_frames_mt(const mt_scan_params *p, const mt_mv *mv, const uint64_t *frame_off,
+                       const uint8_t *has_sd, uint32_t n_frames, uint8_t *flags, int nthreads) {
+  if (nthreads <= 1 || n_frames < 2) return mto_scan_frames(p, mv, frame_off, has_sd, n_frames, flags);
+  if (!params_ok(p) || !frame_off || !flags) return MT_ERR_INVALID;
+  return run_split(p, mv, frame_off, has_sd, n_frames, flags, NULL, nthreads);
+}
+
+int mto_scan_centres_mt(const mt_scan_params *p, const mt_mv *mv, const uint64_t *frame_off,
+                        const uint8_t *has_sd, uint32_t n_frames, uint8_t *flags, uint32_t *centres,
+                        int nthreads) {
+  if (!params_ok(p)) return MT_ERR_INVALID;
+  if (n_frames == 0) return MT_OK;
+  if (!frame_off || !centres) return MT_ERR_INVALID;
+  if (nthreads > 1 && n_frames > 1) return run_split(p, mv, frame_off, has_sd, n_frames, flags, centres, nthreads);
+  uint8_t *grid = (uint8_t *)malloc((size_t)p->grid_w * p->grid_h);
+  if (!grid) return MT_ERR_NOMEM;
+  int rc = count_range_frames(p, mv, frame_off, has_sd, 0, n_frames, flags, centres, grid);
+  free(grid);
   return rc;
 }
 
@@ -282,15 +328,10 @@ int mto_bench_scan(const mt_scan_params *p, const mt_mv *mv, const uint64_t *fra
   gate.go = 0;
   pthread_barrier_t bar;
   double t0 = 0.0, t1 = 0.0;
-  const uint64_t total = frame_off[n_frames] - frame_off[0];
   uint32_t f = 0;
-  for (int t = 0; t < nthreads; ++t) {               /* same record-balanced static split as mto_scan_frames_mt */
-    uint64_t target = frame_off[0] + (total * (uint64_t)(t + 1)) / (uint64_t)nthreads;
-    uint32_t e = f;
-    if (t == nthreads - 1) e = n_frames;
-    else while (e < n_frames && frame_off[e + 1] <= target) ++e;
-    if (e == f && f < n_frames && (n_frames - f) > (uint32_t)(nthreads - 1 - t)) e = f + 1;
-    jobs[t].j = (mt_job){p, mv, frame_off, has_sd, flags, f, e, MT_OK};
+  for (int t = 0; t < nthreads; ++t) {               /* the record-balanced static split of mto_scan_frames_mt */
+    uint32_t e = split_end(frame_off, n_frames, nthreads, t, f);
+    jobs[t].j = (mt_job){p, mv, frame_off, has_sd, flags, NULL, f, e, MT_OK};
     jobs[t].reps = reps; jobs[t].gate = &gate; jobs[t].bar = &bar; jobs[t].t0 = &t0; jobs[t].t1 = &t1;
     f = e;
   }

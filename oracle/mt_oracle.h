@@ -61,6 +61,13 @@ int mto_scan_frames(const mt_scan_params *p, const mt_mv *mv, const uint64_t *fr
 int mto_scan_frames_mt(const mt_scan_params *p, const mt_mv *mv, const uint64_t *frame_off,
                        const uint8_t *has_sd, uint32_t n_frames, uint8_t *flags, int nthreads);
 
+/* The batch form of mto_check_frame_count, with the same record-balanced thread split: centres[f] = the frame's
+ * full centre count (0 for a frame without side data), and, if flags != NULL, flags[f] = centres[f] >=
+ * max(1, clusters_needed), which is what mto_scan_frames' early-exit path returns.  nthreads <= 1: no thread. */
+int mto_scan_centres_mt(const mt_scan_params *p, const mt_mv *mv, const uint64_t *frame_off,
+                        const uint8_t *has_sd, uint32_t n_frames, uint8_t *flags, uint32_t *centres,
+                        int nthreads);
+
 /* bench.py's cpu_baseline leg only: every thread copies its share of the frames into memory it allocates itself
  * (NUMA-local, like a worker's own decoder output), then all threads scan their shares `reps` times between two
  * barriers; *seconds = that wall time.  flags = results of the last pass. */

@@ -34,6 +34,8 @@ def lib():
                                       C.c_uint32, C.c_void_p]
         L.mto_scan_frames_mt.restype = C.c_int
         L.mto_scan_frames_mt.argtypes = L.mto_scan_frames.argtypes + [C.c_int]
+        L.mto_scan_centres_mt.restype = C.c_int
+        L.mto_scan_centres_mt.argtypes = L.mto_scan_frames.argtypes + [C.c_void_p, C.c_int]
         L.mto_bench_scan.restype = C.c_int
         L.mto_bench_scan.argtypes = L.mto_scan_frames.argtypes + [C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.mto_frame_skip.restype = C.c_int
@@ -96,6 +98,22 @@ def scan_frames(params, mv, frame_off, has_sd=None, nthreads=1):
     if rc:
         raise ValueError(f"mto_scan_frames -> {rc}")
     return flags
+
+
+def scan_centres(params, mv, frame_off, has_sd=None, nthreads=1):
+    """(flags uint8 [F], centres uint32 [F]) of a batch in one call: every frame's full centre count
+    (mto_check_frame_count, no early exit) and the flag derived from it, which equals scan_frames()'."""
+    c = params.to_c()
+    mv = np.ascontiguousarray(mv, dtype=m.MV_DTYPE)
+    off = np.ascontiguousarray(frame_off, dtype=np.uint64)
+    sd = None if has_sd is None else np.ascontiguousarray(has_sd, dtype=np.uint8)
+    n = len(off) - 1
+    flags = np.zeros(n, dtype=np.uint8)
+    centres = np.zeros(n, dtype=np.uint32)
+    rc = lib().mto_scan_centres_mt(C.byref(c), _p(mv), _p(off), _p(sd), n, _p(flags), _p(centres), int(nthreads))
+    if rc:
+        raise ValueError(f"mto_scan_centres_mt -> {rc}")
+    return flags, centres
 
 
 def bench_scan(params, mv, frame_off, has_sd=None, nthreads=1, reps=1):

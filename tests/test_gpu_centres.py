@@ -17,6 +17,7 @@ from mvtrim_amd import _abi, synth
 
 import oracle_binding as ob
 from golden_cases import build_mvs, id_of, load_hand_cases
+from scan_checks import device_centres, to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -38,27 +39,6 @@ def oracle_centres(p, mv, off, has_sd=None):
         r, c, _ = ob.check_frame(p, mv[a:b], sd, count_centres=True)
         flags[f], centres[f] = r, c
     return flags, centres
-
-
-def to_device(mv, off, has_sd, compact):
-    import torch
-    raw = (m.pack_records(mv) if compact else np.ascontiguousarray(mv, dtype=m.MV_DTYPE)).view(np.uint8).reshape(-1)
-    d_rec = torch.from_numpy(raw.copy()).cuda() if raw.size else torch.zeros(0, dtype=torch.uint8, device="cuda")
-    d_off = torch.from_numpy(np.asarray(off).astype(np.int64)).cuda()
-    d_sd = None if has_sd is None else torch.from_numpy(np.ascontiguousarray(has_sd, dtype=np.uint8)).cuda()
-    return d_rec, d_off, d_sd
-
-
-def device_centres(s, mv, off, has_sd, compact, want_flags=True):
-    """Through mtgpu_scan_centres_device, outputs pre-filled with junk: every element must be written."""
-    import torch
-    d_rec, d_off, d_sd = to_device(mv, off, has_sd, compact)
-    n = len(off) - 1
-    flags = torch.full((n,), 9, dtype=torch.uint8, device="cuda") if want_flags else False
-    centres = torch.full((n,), -7, dtype=torch.int32, device="cuda")
-    fl, ce = s.count_centres_device(d_rec, d_off, d_sd, compact=compact, flags=flags, centres=centres)
-    torch.cuda.synchronize()
-    return (None if fl is None else fl.cpu().numpy()), ce.cpu().numpy().view(np.uint32)
 
 
 # ------------------------------------------------------------------ arguments

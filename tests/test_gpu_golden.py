@@ -25,6 +25,7 @@ from mvtrim_amd import synth
 import oracle_binding as ob
 from golden_cases import (build_mvs, id_of, load_filter_cases, load_hand_cases, load_merge_cases,
                           load_survey_segments, merge_case_ts)
+from scan_checks import assert_centres_parity, assert_counts_equal, device_centres_of
 
 pytestmark = pytest.mark.gpu
 
@@ -65,6 +66,9 @@ def test_check_frame_hand_cases_on_gpu(gpu_scanner_factory, name, kw, case, forc
     got = s.check_frames(b)
     assert got.tolist() == [case["expect"]], name
     assert scan_compact(s, b.mv, b.frame_off, b.has_sd).tolist() == [case["expect"]], name
+    po = ob.params_from_config(**kw)
+    _, want_c = assert_centres_parity(s, po, b.mv, b.frame_off, b.has_sd, plain_flags=got, what=name)
+    assert want_c.tolist() == [case["centres"] if sd else 0], name          # oracle == hand value (== GPU, above)
     if len(mv) > 1:                                    # record order must not matter
         b2 = m.FrameBatch(mv[::-1].copy(), b.frame_off, None, b.has_sd)
         assert s.check_frames(b2).tolist() == [case["expect"]]
@@ -83,8 +87,11 @@ def test_check_frame_hand_cases_one_batch(gpu_scanner_factory):
     for slices in (1, 4):
         s = gpu_scanner_factory(p)
         s.set_slices(slices)
-        assert s.check_frames(b).tolist() == want
+        got = s.check_frames(b)
+        assert got.tolist() == want
         assert scan_compact(s, b.mv, b.frame_off, b.has_sd).tolist() == want
+        _, want_c = assert_centres_parity(s, ob.params_from_config(**g["base"]), b.mv, b.frame_off, b.has_sd, plain_flags=got)
+        assert want_c.tolist() == [c["centres"] if int(c.get("has_sd", 1)) else 0 for _, c in base]
 
 
 # ------------------------------------------------------------------ merge hand cases
@@ -273,6 +280,11 @@ def test_config4_64_streams_scan_merge_gather(gpu_scanner_factory):
     got_flags = flags.cpu().numpy()
     bad = np.flatnonzero(got_flags != want_flags)
     assert bad.size == 0, (bad.size, bad[:16], got_flags[bad[:16]], want_flags[bad[:16]], int(got_flags.sum()), int(want_flags.sum()))
+    # the same batch count for count (device entry point only: the batch is on the device already)
+    want_f, want_c = ob.scan_centres(p, mv, off.astype(np.uint64), sd, nthreads=8)
+    assert np.array_equal(want_f, want_flags) and len(set(want_c.tolist())) >= 8
+    fl, ce = device_centres_of(s, d_mv, d_off, d_sd, compact=False)
+    assert_counts_equal(ce, want_c, "64 streams in one batch", s.plan, fl, want_flags)
     packed = mdist.pack_segment_lists(seg, res)
 
     lib = m.load_library()
@@ -343,10 +355,12 @@ def test_timerange_split_world_simulated(gpu_scanner_factory, world):
     want_flags = ob.scan_frames(p, mv, off, sd, nthreads=8)
     want_seg, want_res = ob.pool_and_merge(pts[want_flags != 0], mp, True)
     assert want_res["n_segments"] >= 2
+    want_f, want_c = ob.scan_centres(p, mv, off, sd, nthreads=8)
+    assert np.array_equal(want_f, want_flags)
 
     d_mv = torch.from_numpy(mv.view(np.uint8).reshape(-1)).cuda()
     off64 = off.astype(np.int64)
-    pooled, got_flags = [], []
+    pooled, got_flags, got_centres = [], [], []
     for (a, b) in mdist.shard_by_records(off64, world):
         if b == a:
             continue
@@ -355,7 +369,10 @@ def test_timerange_split_world_simulated(gpu_scanner_factory, world):
                                    torch.from_numpy(sd[a:b]).cuda()).cpu().numpy()
         got_flags.append(fl)
         pooled.append(pts[a:b][fl != 0])
+        got_centres.append(device_centres_of(s, d_mv[ra * 40: rb * 40], torch.from_numpy(off64[a:b + 1] - off64[a]).cuda(),
+                                             torch.from_numpy(sd[a:b]).cuda(), compact=False)[1])
     assert np.array_equal(np.concatenate(got_flags), want_flags)
+    assert_counts_equal(np.concatenate(got_centres), want_c, f"{world} frame ranges", s.plan)
     ts = np.concatenate(pooled[::-1])                      # any rank order: the merge sorts
     seg, res = s.merge_segments(ts, mp, True)
     assert seg.tobytes() == want_seg.tobytes()
@@ -389,12 +406,15 @@ def test_mvjson_roundtrip_feeds_the_hip_scan(gpu_scanner_factory, tmp_path):
     assert 0 < want.sum() < n
     direct = s.check_frames(b0)
     assert np.array_equal(direct, want)
+    want_fc = assert_centres_parity(s, p, b0.mv, b0.frame_off, b0.has_sd, plain_flags=direct)
+    assert np.array_equal(want_fc[0], want) and len(set(want_fc[1].tolist())) >= 3
     js = str(tmp_path / "s.json")
     m.mvjson.write_json(js, frames, pts, (1, 90000))
     f2, p2, tb = m.mvjson.read_json(js)
     b2 = m.FrameBatch.from_frames(f2)
     assert np.array_equal(s.check_frames(b2), want)
     assert np.array_equal(scan_compact(s, b2.mv, b2.frame_off, b2.has_sd), want)
+    assert_centres_parity(s, p, b2.mv, b2.frame_off, b2.has_sd, want=want_fc, what="records read back from JSON")
     # the timestamps the JSON carries (%.6f seconds) merge to the oracle's segments for those values
     mp = m.MergeParams(duration=n / 25.0, max_gap_sec=0.2, padding_sec=0.1, min_savings_pct=5.0)
     ts = [t for t, f in zip(p2, want) if f]
@@ -406,6 +426,7 @@ def test_mvjson_roundtrip_feeds_the_hip_scan(gpu_scanner_factory, tmp_path):
     _, tab, mv = m.mvfile.read_mtmv(mt)
     b1 = m.FrameBatch.from_frames(m.mvfile.frames_of(tab, mv))
     assert np.array_equal(s.check_frames(b1), want)
+    assert_centres_parity(s, p, b1.mv, b1.frame_off, b1.has_sd, want=want_fc, what="records read back from .mtmv")
 
 
 # ------------------------------------------------------------------ compact records + host dispatcher
@@ -427,9 +448,14 @@ def test_compact_records_match_aos_everywhere(gpu_scanner_factory):
             s.set_slices(slices)
         mv, off, sd = synth.random_frames(rng, 20, 6000, w, h, hot=0.5)
         want = ob.scan_frames(p, mv, off, sd)
-        assert np.array_equal(s.check_frames(m.FrameBatch(mv, off, None, sd)), want), (w, h, kw, fb)
+        got = s.check_frames(m.FrameBatch(mv, off, None, sd))
+        assert np.array_equal(got, want), (w, h, kw, fb)
         assert np.array_equal(scan_compact(s, mv, off, sd), want), (w, h, kw, fb, s.plan)
         assert np.array_equal(scan_compact(s, mv, off, None), ob.scan_frames(p, mv, off, None))
+        # and count for count: host entry, device entry on both layouts, has_sd given and NULL
+        want_f, _ = assert_centres_parity(s, p, mv, off, sd, plain_flags=got, device=True, what=f"{(w, h, kw, fb)}")
+        assert np.array_equal(want_f, want)
+        assert_centres_parity(s, p, mv, off, None, device=True, what=f"{(w, h, kw, fb)} has_sd NULL")
 
 
 def test_compact_records_any_8_byte_alignment(gpu_scanner_factory):
@@ -444,6 +470,8 @@ def test_compact_records_any_8_byte_alignment(gpu_scanner_factory):
     tiny = [mv[:0], mv[5:6], mv[10:12], mv[20:23]]                 # 0, 1, 2, 3 records
     b = m.FrameBatch.from_frames([mv[int(off[i]):int(off[i + 1])] if sd[i] else None for i in range(40)] + tiny)
     want = ob.scan_frames(p, b.mv, b.frame_off, b.has_sd)
+    want_f, want_c = ob.scan_centres(p, b.mv, b.frame_off, b.has_sd)
+    assert np.array_equal(want_f, want) and len(set(want_c.tolist())) >= 8
     rec = torch.from_numpy(m.pack_records(b.mv).view(np.uint8).reshape(-1).copy())
     d_off = torch.from_numpy(b.frame_off.astype(np.int64)).cuda()
     d_sd = torch.from_numpy(b.has_sd).cuda()
@@ -456,6 +484,8 @@ def test_compact_records_any_8_byte_alignment(gpu_scanner_factory):
             s.set_slices(slices)
             got = s.check_frames_device_compact(view, d_off, d_sd).cpu().numpy()
             assert np.array_equal(got, want), (shift, slices)
+            fl, ce = device_centres_of(s, view, d_off, d_sd, compact=True)
+            assert_counts_equal(ce, want_c, f"base shifted by {shift} bytes, slices {slices}", s.plan, fl, want)
     s.set_slices(0)
     with pytest.raises(m.MtgpuError) as ei:
         s.check_frames_device_compact(torch.zeros(rec.numel() + 8, dtype=torch.uint8, device="cuda")[4:4 + rec.numel()], d_off, d_sd)
@@ -823,8 +853,11 @@ def test_scan_under_reference_parsed_configs(gpu_scanner_factory):
             continue
         s = gpu_scanner_factory(p)
         b = m.FrameBatch(mv, off, None, has_sd)
-        assert np.array_equal(s.check_frames(b), want), case["name"]
+        got = s.check_frames(b)
+        assert np.array_equal(got, want), case["name"]
         assert np.array_equal(scan_compact(s, mv, off, has_sd), want), case["name"]
+        want_f, _ = assert_centres_parity(s, po, mv, off, has_sd, plain_flags=got, what=case["name"])
+        assert np.array_equal(want_f, want)
         ran += 1
         some_motion += int(want.any())
         s.close()

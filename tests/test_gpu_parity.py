@@ -2,7 +2,8 @@
 through the C ABI (libmtgpu.so), against the CPU oracle on identical inputs.
 
 Bar: bit-exact.  Per-frame flags are integers; segment doubles are compared by
-their 64-bit patterns.
+their 64-bit patterns.  Wherever a scan is compared with the oracle, it is compared on the per-frame centre
+count as well (tests/scan_checks.py): the flag is one bit of that count.
 """
 import numpy as np
 import pytest
@@ -11,6 +12,8 @@ import mvtrim_amd as m
 from mvtrim_amd import synth
 
 import oracle_binding as ob
+from scan_checks import (EDGE_CFGS, assert_centres_parity, assert_counts_equal, cells_frame, device_centres_of,
+                         edge_config_inputs, junk_padding, pair_centres)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,21 +22,16 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def junk_padding(mv, rng):
-    """Fill the padding bytes of the records (14-15, 34-39) with junk: the scan must ignore them."""
-    raw = mv.view(np.uint8).reshape(-1, 40)
-    if len(raw):
-        raw[:, 14:16] = rng.randint(0, 256, size=(len(raw), 2))
-        raw[:, 34:40] = rng.randint(0, 256, size=(len(raw), 6))
-    return mv
-
-
-def assert_scan_parity(scanner, params, mv, off, has_sd):
+def assert_scan_parity(scanner, params, mv, off, has_sd, with_counts=False):
     want = ob.scan_frames(params, mv, off, has_sd)
     got = scanner.check_frames(m.FrameBatch(mv, off, None, has_sd))
     bad = np.flatnonzero(want != got)
     assert bad.size == 0, f"{bad.size} frames differ, first {bad[:8]}: want {want[bad[:8]]} got {got[bad[:8]]}"
-    return want
+    # ... and count for count: host entry point always, device entry point (40-byte and compact records, junk-filled
+    # outputs) for batches within scan_checks.DEVICE_LEG_MAX_*; the flags of the centres call equal the plain call's
+    want_f, want_c = assert_centres_parity(scanner, params, mv, off, has_sd, plain_flags=got)
+    assert np.array_equal(want_f, want)              # the oracle's counting path and its early-exit path agree
+    return (want, want_c) if with_counts else want
 
 
 # ------------------------------------------------------------------ scan: streams
@@ -56,6 +54,7 @@ def test_scan_1080p_stream(gpu_scanner_factory, cfg, sub):
     # has_sd == NULL convention: side data iff >= 1 record (identical here)
     got2 = s.check_frames(m.FrameBatch(mv, off))
     assert np.array_equal(got2, want)
+    assert_centres_parity(s, p, mv, off, None, plain_flags=got2)
 
 
 @pytest.mark.parametrize("force_fb", [None, 2, 32])
@@ -128,8 +127,9 @@ def test_fine_grid_cluster_across_seams(gpu_scanner_factory, force_fb):
         mv["src_y"] = mv["dst_y"]
         frames.append(mv)
     b = m.FrameBatch.from_frames(frames)
-    want = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd)
+    want, centres = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd, with_counts=True)
     assert list(want) == [1, 1, 1, 0]
+    assert centres.tolist() == [2, 2, 2, 0]        # by hand: a vertical pair = two centres; rows seam-1 / seam+1 do not touch
 
 
 def _fine_shipped_env_scanner(gpu_scanner_factory):
@@ -203,22 +203,25 @@ def test_band_seam_cluster_needs_every_replayed_vote(gpu_scanner_factory):
             mv["src_x"][w], mv["src_y"][w] = x - d, y                      # |d|^2 = 9 >= 4
         return mv
 
-    cases = [([(400, 269, 4), (400, 270, 4)], 1),        # the seam pair: 1 centre per band
-             ([(400, 269, 4), (400, 270, 3)], 0),        # row 270 one vote short: no cell has an active neighbour
-             ([(400, 269, 3), (400, 270, 4)], 0),        # row 269 one vote short (band 1's halo, replayed)
-             ([(400, 270, 4), (400, 271, 4)], 1),        # both in band 1: only replayed votes
-             ([(400, 270, 4), (400, 271, 3), (401, 270, 3)], 0),
-             ([(400, 268, 4), (400, 269, 4)], 1),        # both in band 0; row 269 is queued as well, harmlessly
-             ([(400, 269, 4), (401, 269, 4)], 1),        # horizontal pair on band 0's last centre row
-             ([(400, 270, 4), (401, 270, 4)], 1),        # horizontal pair on band 1's first centre row
-             ([(400, 269, 4), (401, 270, 4)], 0),        # diagonal across the seam: not 4-neighbours
-             ([(400, 269, 9), (400, 270, 200)], 1),      # saturated fields (thermometer full) on both sides
-             ([(0, 269, 4), (0, 270, 4), (959, 269, 4), (959, 270, 4)], 0),   # columns 0 / gw-1 are never centres
-             ([(1, 269, 4), (0, 269, 4), (958, 270, 4), (959, 270, 4)], 1)]   # ... but they count as neighbours
-    frames = [frame(c) for c, _ in cases]
+    # (cells, flag, centre count): the count by hand from the cell list -- an active cell with an active 4-neighbour,
+    # columns 0 and gw - 1 excluded; the filler records stay below the threshold and vote nowhere
+    cases = [([(400, 269, 4), (400, 270, 4)], 1, 2),     # the seam pair: 1 centre per band
+             ([(400, 269, 4), (400, 270, 3)], 0, 0),     # row 270 one vote short: no cell has an active neighbour
+             ([(400, 269, 3), (400, 270, 4)], 0, 0),     # row 269 one vote short (band 1's halo, replayed)
+             ([(400, 270, 4), (400, 271, 4)], 1, 2),     # both in band 1: only replayed votes
+             ([(400, 270, 4), (400, 271, 3), (401, 270, 3)], 0, 0),
+             ([(400, 268, 4), (400, 269, 4)], 1, 2),     # both in band 0; row 269 is queued as well, harmlessly
+             ([(400, 269, 4), (401, 269, 4)], 1, 2),     # horizontal pair on band 0's last centre row
+             ([(400, 270, 4), (401, 270, 4)], 1, 2),     # horizontal pair on band 1's first centre row
+             ([(400, 269, 4), (401, 270, 4)], 0, 0),     # diagonal across the seam: not 4-neighbours
+             ([(400, 269, 9), (400, 270, 200)], 1, 2),   # saturated fields (thermometer full) on both sides
+             ([(0, 269, 4), (0, 270, 4), (959, 269, 4), (959, 270, 4)], 0, 0),   # columns 0 / gw-1 are never centres
+             ([(1, 269, 4), (0, 269, 4), (958, 270, 4), (959, 270, 4)], 1, 2)]   # ... but they count as neighbours: cells 1 and 958
+    frames = [frame(c) for c, _, _ in cases]
     b = m.FrameBatch.from_frames(frames)
-    want = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd)
-    assert want.tolist() == [w for _, w in cases]
+    want, centres = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd, with_counts=True)
+    assert want.tolist() == [w for _, w, _ in cases]
+    assert centres.tolist() == [c for _, _, c in cases]
     # and as 8-byte compact records through the pinned zero-copy pipe (what the host dispatcher stages)
     pipe = m.ScanPipe(s, 3 * 20100, 3, 2)
     for i, f in enumerate(frames):
@@ -240,21 +243,26 @@ def test_packed_counter_forms(gpu_scanner_factory, force_fb, vec):
     s = gpu_scanner_factory(p, force_fb=force_fb)
     assert s.plan["counter_bits"] == force_fb % 100 and s.plan["counter_mode"] == (2 if force_fb == 108 else 1)
     rng = np.random.RandomState(vec * 10 + force_fb)
-    frames = []
+    frames, hand = [], []
     for trial in range(24):
         cells = [(40 + 2 * (trial % 3), 30), (41 + 2 * (trial % 3), 30), (60, 20 + trial % 5), (60, 21 + trial % 5)]
-        parts = []
+        parts, votes = [], []
         for ci, (cx, cy) in enumerate(cells):
             n = [vec - 1, vec, vec + 1, 4 * vec + 300][rng.randint(0, 4)]
             a = np.zeros(max(n, 0), dtype=m.MV_DTYPE)
             a["dst_x"], a["dst_y"] = 16 * cx + rng.randint(0, 16, size=len(a)), 16 * cy + rng.randint(0, 16, size=len(a))
             a["src_x"], a["src_y"] = a["dst_x"] - 7, a["dst_y"] + 3
             parts.append(a)
+            votes.append(len(a))
         fr = np.concatenate(parts)
         frames.append(fr[rng.permutation(len(fr))])
+        # by hand, from the draws: the cells are a horizontal pair in row 30 and a vertical pair in column 60, far apart
+        hand.append(pair_centres([(votes[0], votes[1]), (votes[2], votes[3])], vec))
     b = m.FrameBatch.from_frames(frames)
-    want = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd)
+    want, centres = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd, with_counts=True)
     assert 0 < want.sum() < len(want)
+    assert centres.tolist() == hand and want.tolist() == [int(c >= 2) for c in hand]          # CLUSTERS_NEEDED 2
+    assert {0, 2, 4} == set(hand)
     # ragged random frames with hot spots as well
     mv, off, sd = synth.random_frames(rng, 32, 4000, 1920, 1080, hot=0.7)
     assert_scan_parity(s, p, mv, off, sd)
@@ -262,47 +270,23 @@ def test_packed_counter_forms(gpu_scanner_factory, force_fb, vec):
 
 # ------------------------------------------------------------------ scan: edge cases
 
-EDGE_CFGS = [
-    # (width, height, kwargs)
-    (1920, 1080, dict()),
-    (1920, 1080, dict(vertical_mask=0.0)),                              # margin 0: grid edges are centres
-    (1920, 1080, dict(vectors_needed=1, clusters_needed=1)),
-    (1920, 1080, dict(vectors_needed=0)),                               # every cell active
-    (1920, 1080, dict(vectors_needed=255)),
-    (1920, 1080, dict(vectors_needed=256 + 3)),                         # uint8 wrap -> 3
-    (1920, 1080, dict(clusters_needed=0)), (1920, 1080, dict(clusters_needed=-5)),
-    (1920, 1080, dict(clusters_needed=100000)),
-    (1920, 1080, dict(mv_threshold_sq=0.0)), (1920, 1080, dict(mv_threshold_sq=-1.0)),
-    (1920, 1080, dict(mv_threshold_sq=float("nan"))), (1920, 1080, dict(mv_threshold_sq=float("inf"))),
-    (1920, 1080, dict(mv_threshold_sq=24.5)), (1920, 1080, dict(mv_threshold_sq=25.0)),
-    (1920, 1080, dict(mv_threshold_sq=2.0e9)),
-    (1920, 1080, dict(vertical_mask=0.5)), (1920, 1080, dict(vertical_mask=0.6)),   # empty analysed range
-    (16, 16, dict(vertical_mask=0.0)), (32, 48, dict(vertical_mask=0.0)), (48, 48, dict(vertical_mask=0.0)),
-    (1008, 64, dict(vertical_mask=0.0)), (1024, 64, dict(vertical_mask=0.0)),       # gw 63, 64
-    (1040, 64, dict(vertical_mask=0.0)), (2064, 96, dict()),                         # gw 65, 129
-    (1920, 1080, dict(block_size=8, block_shift=3)),                                 # 240x135 on 1080p
-    (1920, 1080, dict(block_size=16, block_shift=5)),                                # size/shift mismatch
-    (640, 480, dict(block_size=1, block_shift=0, vectors_needed=1)),                 # 640x480 cells
-    (32767, 3, dict(block_size=1, block_shift=0, vectors_needed=1, vertical_mask=0.0)),   # widest legal grid
-    (3, 32767, dict(block_size=1, block_shift=0, vectors_needed=1, vertical_mask=0.0)),   # tallest: chunked masks
-    (32767, 40, dict(block_size=1, block_shift=0, vectors_needed=2, clusters_needed=1)),  # wide + row bands
-]
-
-
 @pytest.mark.parametrize("force_fb", [None, 8, 108])
 @pytest.mark.parametrize("width,height,kw", EDGE_CFGS)
 def test_scan_edge_configs(gpu_scanner_factory, width, height, kw, force_fb):
-    import zlib
-    rng = np.random.RandomState(zlib.crc32(repr((width, height, sorted(kw.items()))).encode()) % (2 ** 31))
+    """The inputs come from scan_checks.edge_config_inputs: 48 random frames per set (seeded by the set), and planted
+    frames behind them for the two sets whose random frames hold no centre at all; tests/test_scan_inputs.py checks on
+    the CPU that these inputs say something about counting."""
     p = ob.params_from_config(width, height, **kw)
     assert m.ScanParams.from_config(width, height, **kw) == p or np.isnan(p.mv_threshold_sq)
     s = gpu_scanner_factory(p, force_fb=force_fb)
-    mv, off, sd = synth.random_frames(rng, 48, 3000, width, height)
-    junk_padding(mv, rng)
-    want = assert_scan_parity(s, p, mv, off, sd)
+    mv, off, sd, planted = edge_config_inputs(width, height, kw)
+    want, centres = assert_scan_parity(s, p, mv, off, sd, with_counts=True)
+    if planted:
+        assert centres[48:].tolist() == planted            # the hand values of the planted frames
     # and with the NULL has_sd convention
     got = s.check_frames(m.FrameBatch(mv, off))
     assert np.array_equal(got, ob.scan_frames(p, mv, off, None))
+    assert_centres_parity(s, p, mv, off, None, plain_flags=got)
     del want
 
 
@@ -335,8 +319,10 @@ def test_scan_magnitude_beyond_32_bits(gpu_scanner_factory, thr):
         frames.append(mv)
         expect.append(int(all(dx * dx + dy * dy >= math.ceil(thr) for dx, dy in (da, db))))
     b = m.FrameBatch.from_frames(frames)
-    want = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd)
+    want, centres = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd, with_counts=True)
     assert want.tolist() == expect
+    # by hand: both cells active -> column 2046 is a centre (its right neighbour is active), column 2047 = gw - 1 never is
+    assert centres.tolist() == expect
     pipe = m.ScanPipe(s, 16, 8, 2)
     for i, f in enumerate(frames):
         pipe.feed(f, float(i), tag=i)
@@ -358,8 +344,9 @@ def test_scan_counter_saturation(gpu_scanner_factory):
         mv["src_y"] = mv["dst_y"]
         frames.append(mv)
     b = m.FrameBatch.from_frames(frames)
-    want = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd)
+    want, centres = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd, with_counts=True)
     assert list(want) == [0, 1, 1, 0]
+    assert centres.tolist() == [0, 2, 2, 0]        # by hand: cells (50, 30) and (51, 30), both active or no centre at all
 
 
 def test_scan_empty_and_sideless_frames(gpu_scanner_factory):
@@ -369,8 +356,10 @@ def test_scan_empty_and_sideless_frames(gpu_scanner_factory):
     b = m.FrameBatch.from_frames([None, np.zeros(0, dtype=m.MV_DTYPE), one, None])
     # vectors_needed == 0: "side data with zero records" -> phase 2 on an all-active grid -> true,
     # "no side data" -> false (reference :219-221 vs :282)
-    want = assert_scan_parity(s0, p0, b.mv, b.frame_off, b.has_sd)
+    want, centres = assert_scan_parity(s0, p0, b.mv, b.frame_off, b.has_sd, with_counts=True)
     assert list(want) == [0, 1, 1, 0]
+    every = (p0.grid_w - 2) * (p0.grid_h - 2 * p0.vertical_margin)      # every analysed cell outside columns 0 / gw - 1
+    assert centres.tolist() == [0, every, every, 0]
     assert s0.check_frames(m.FrameBatch(b.mv, np.zeros(1, dtype=np.uint64))).size == 0
 
 
@@ -383,6 +372,8 @@ def test_scan_device_resident_matches_host_path(gpu_scanner_factory):
     s = gpu_scanner_factory(p)
     want = ob.scan_frames(p, mv, off, sd)
     assert want.sum() > 0
+    want_f, want_c = assert_centres_parity(s, p, mv, off, sd)          # host path and device path, count for count
+    assert np.array_equal(want_f, want) and len(set(want_c.tolist())) >= 4
     d_mv = torch.from_numpy(mv.view(np.uint8).copy()).cuda()
     d_off = torch.from_numpy(off.astype(np.int64)).cuda()
     d_sd = torch.from_numpy(sd).cuda()
@@ -392,8 +383,10 @@ def test_scan_device_resident_matches_host_path(gpu_scanner_factory):
     side = torch.cuda.Stream()
     with torch.cuda.stream(side):
         got2 = s.check_frames_device(d_mv, d_off, None)
+        fl2, ce2 = s.count_centres_device(d_mv, d_off, None)           # has_sd NULL, on a side stream
     side.synchronize()
     assert np.array_equal(got2.cpu().numpy(), want)
+    assert_counts_equal(ce2.cpu().numpy().view(np.uint32), want_c, "side stream, has_sd NULL", s.plan, fl2.cpu().numpy(), want)
 
 
 @pytest.mark.parametrize("grid,cfg", [("1080p", "code_defaults"), ("4k", "code_defaults"), ("4k", "shipped_env")])
@@ -413,17 +406,25 @@ def test_scan_batch_properties_full_size(gpu_scanner_factory, grid, cfg):
     s = gpu_scanner_factory(p)
     want = ob.scan_frames(p, mv, off, None)
     assert 0 < want.sum() < 32
+    want_f, want_c = ob.scan_centres(p, mv, off, None)
+    assert np.array_equal(want_f, want)
     d_tile = torch.from_numpy(mv.view(np.uint8).copy()).cuda()
     d_mv = d_tile.repeat(reps)
     counts = np.diff(off.astype(np.int64))
     off_big = np.concatenate([[0], np.cumsum(np.tile(counts, reps))]).astype(np.int64)
-    got = s.check_frames_device(d_mv, torch.from_numpy(off_big).cuda()).cpu().numpy()
+    d_off_big = torch.from_numpy(off_big).cuda()
+    got = s.check_frames_device(d_mv, d_off_big).cpu().numpy()
     assert np.array_equal(got, np.tile(want, reps))
+    # the counts, through the device entry point only (no host copy of the 5.3 GB batch), junk-filled outputs
+    fl, ce = device_centres_of(s, d_mv, d_off_big, None, compact=False)
+    assert_counts_equal(ce, np.tile(want_c, reps), "tiled batch", s.plan, fl, np.tile(want, reps))
     # reversed frame order: a reversed batch needs its own packed array; built on the host for the tile only
     order = np.arange(32)[::-1]
     frames = [mv[int(off[i]):int(off[i + 1])] for i in order]
     b = m.FrameBatch.from_frames(frames)
-    assert np.array_equal(s.check_frames(m.FrameBatch(b.mv, b.frame_off)), want[order])
+    got_r = s.check_frames(m.FrameBatch(b.mv, b.frame_off))
+    assert np.array_equal(got_r, want[order])
+    assert_centres_parity(s, p, b.mv, b.frame_off, None, plain_flags=got_r, want=(want[order], want_c[order]))
 
 
 @pytest.mark.parametrize("group", ["1", ""])
@@ -460,16 +461,25 @@ def test_work_list_every_plan_size(gpu_scanner_factory, monkeypatch, n_frames, g
         got = s.check_frames(m.FrameBatch(mv, off, None, has_sd))
         bad = np.flatnonzero(want != got)
         assert bad.size == 0, (vn, bad[:8], want[bad[:8]], got[bad[:8]], kind[bad[:8]])
+        want_f, want_c = assert_centres_parity(s, p, mv, off, has_sd, plain_flags=got, nthreads=8, device=False, what=f"vn {vn}")
+        assert np.array_equal(want_f, want)
         if vn == 0:
             assert np.array_equal(want, has_sd)              # side data (even empty) -> every cell active -> true
+            assert np.array_equal(want_c, has_sd.astype(np.uint32) * ((p.grid_w - 2) * (p.grid_h - 2 * p.vertical_margin)))
         else:
             assert np.array_equal(want, (kind == 5).astype(np.uint8))
+            assert np.array_equal(want_c, 2 * (kind == 5))   # by hand: the two moving records sit in cells (50, 30) and (51, 30)
         # device entry point, has_sd == NULL (side data iff records), poisoned flags: every byte is written
         d_flags = torch.full((n_frames,), 9, dtype=torch.uint8, device="cuda")
         d_mv = torch.from_numpy(mv.view(np.uint8).copy()).cuda() if n else torch.zeros(40, dtype=torch.uint8, device="cuda")
-        s.check_frames_device(d_mv[: n * 40], torch.from_numpy(off.astype(np.int64)).cuda(), None, d_flags)
+        d_off = torch.from_numpy(off.astype(np.int64)).cuda()
+        s.check_frames_device(d_mv[: n * 40], d_off, None, d_flags)
         want2 = ob.scan_frames(p, mv, off, None, nthreads=8)
         assert np.array_equal(d_flags.cpu().numpy(), want2), vn
+        want2_f, want2_c = ob.scan_centres(p, mv, off, None, nthreads=8)
+        assert np.array_equal(want2_f, want2)
+        fl, ce = device_centres_of(s, d_mv[: n * 40], d_off, None, compact=False)
+        assert_counts_equal(ce, want2_c, f"device entry, has_sd NULL, vn {vn}", s.plan, fl, want2)
 
 
 # ------------------------------------------------------------------ merge
@@ -620,6 +630,8 @@ def test_scan_pipe_matches_oracle(gpu_scanner_factory):
     s = gpu_scanner_factory(p)
     b = m.FrameBatch.from_frames(frames)
     want = ob.scan_frames(p, b.mv, b.frame_off, b.has_sd)
+    want_f, want_c = assert_centres_parity(s, p, b.mv, b.frame_off, b.has_sd)
+    assert np.array_equal(want_f, want) and len(set(want_c.tolist())) >= 4
     for (max_rec, max_fr, nbuf) in [(8160 * 5, 7, 2), (8160 * 64, 64, 3), (8160, 1, 1), (8160 * 3 + 17, 1000, 4)]:
         pipe = m.ScanPipe(s, max_rec, max_fr, nbuf)
         for i, f in enumerate(frames):
@@ -630,6 +642,13 @@ def test_scan_pipe_matches_oracle(gpu_scanner_factory):
         assert [pt for pt, _, _ in out] == [spec.pts_seconds(i) for i in range(150)]
         assert pipe.drain() == []
         pipe.close()
+        pipe = m.ScanPipe(s, max_rec, max_fr, nbuf, centres=True)    # the same batching with the centre counts switched on
+        for i, f in enumerate(frames):
+            pipe.feed(f, spec.pts_seconds(i), tag=i)
+        out = pipe.drain_centres()
+        pipe.close()
+        assert [t for _, _, t, _ in out] == list(range(150))
+        assert_counts_equal([c for _, _, _, c in out], want_c, f"pipe {(max_rec, max_fr, nbuf)}", s.plan, [fl for _, fl, _, _ in out], want)
     pipe = m.ScanPipe(s, 100, 4, 2)                               # a frame larger than a whole batch:
     pipe.feed(frames[1], 0.0)                                     # the empty batch grows (check_frame takes any count)
     assert [fl for _, fl, _ in pipe.drain()] == [int(want[1])]
@@ -730,20 +749,29 @@ def test_scan_device_unaligned_base_and_offset_clamp(gpu_scanner_factory):
     s = gpu_scanner_factory(p)
     mv, off, sd = synth.random_frames(rng, 40, 2500, 1920, 1080)
     want = ob.scan_frames(p, mv, off, None)
+    want_f, want_c = ob.scan_centres(p, mv, off, None)
+    assert np.array_equal(want_f, want) and len(set(want_c.tolist())) >= 8
     raw = torch.from_numpy(mv.view(np.uint8).copy())
+    d_off = torch.from_numpy(off.astype(np.int64)).cuda()
     for shift in (4, 8, 12, 20):
         buf = torch.zeros(raw.numel() + 64, dtype=torch.uint8, device="cuda")
         view = buf[shift:shift + raw.numel()]
         view.copy_(raw)
         assert view.data_ptr() % 16 == shift % 16
-        got = s.check_frames_device(view, torch.from_numpy(off.astype(np.int64)).cuda())
+        got = s.check_frames_device(view, d_off)
         assert np.array_equal(got.cpu().numpy(), want), shift
+        fl, ce = device_centres_of(s, view, d_off, None, compact=False)
+        assert_counts_equal(ce, want_c, f"base shifted by {shift} bytes", s.plan, fl, want)
     # clamp: pretend the array holds only the records of the first 25 frames
     n_keep = int(off[25])
     d_mv = raw[: n_keep * 40].cuda()
-    got = s.check_frames_device(d_mv, torch.from_numpy(off.astype(np.int64)).cuda()).cpu().numpy()
+    got = s.check_frames_device(d_mv, d_off).cpu().numpy()
     off_clamped = np.minimum(off, n_keep)
     assert np.array_equal(got, ob.scan_frames(p, mv[:n_keep], off_clamped, None))
+    fl, ce = device_centres_of(s, d_mv, d_off, None, compact=False)
+    clamped_f, clamped_c = ob.scan_centres(p, mv[:n_keep], off_clamped, None)
+    assert_counts_equal(ce, clamped_c, "offsets clamped to n_records", s.plan, fl, clamped_f)
+    assert clamped_c[:25].tolist() == want_c[:25].tolist() and not clamped_c[25:].any()
     # an unaligned (odd) base is rejected, not dereferenced
     bad = torch.zeros(raw.numel() + 8, dtype=torch.uint8, device="cuda")[1:1 + raw.numel()]
     with pytest.raises(m.MtgpuError) as ei:
@@ -792,17 +820,22 @@ def test_scan_host_window_of_larger_batch(gpu_scanner_factory):
     s = gpu_scanner_factory(p)
     mv, off, sd = synth.random_frames(rng, 60, 2000, 1920, 1080)
     want = ob.scan_frames(p, mv, off, sd)
+    want_f, want_c = ob.scan_centres(p, mv, off, sd)
+    assert np.array_equal(want_f, want) and len(set(want_c.tolist())) >= 8
     for a, b in [(0, 60), (10, 35), (59, 60), (17, 17)]:
         got = s.check_frames(m.FrameBatch(mv, off[a:b + 1], None, sd[a:b]))
         assert np.array_equal(got, want[a:b]), (a, b)
+        flags2, centres = s.count_centres(m.FrameBatch(mv, off[a:b + 1], None, sd[a:b]))
+        assert_counts_equal(centres, want_c[a:b], f"window [{a}, {b})", s.plan, flags2, want[a:b])
 
 
 def test_scan_fuzz_random_configs(gpu_scanner_factory):
     """Randomised sweep: grid sizes, block settings, thresholds, vote / cluster needs, masks and
-    every counter form, each on ragged adversarial frames.  Bit-exact flags vs the oracle."""
+    every counter form, each on ragged adversarial frames.  Bit-exact flags and centre counts vs the oracle."""
     rng = np.random.RandomState(20260104)
     forms = [None, 1, 2, 4, 8, 108, 32]
     n_cfg = 120
+    counted = checked = 0
     for it in range(n_cfg):
         sh = int(rng.randint(0, 7))
         bs = int(rng.choice([1 << sh, 16, 8]))
@@ -828,7 +861,15 @@ def test_scan_fuzz_random_configs(gpu_scanner_factory):
         want = ob.scan_frames(p, mv, off, sd)
         got = s.check_frames(m.FrameBatch(mv, off, None, sd))
         assert np.array_equal(got, want), (it, w, h, kw, s.plan)
+        want_f, want_c = assert_centres_parity(s, p, mv, off, sd, plain_flags=got, what=f"configuration {it} {(w, h, kw)}")
+        assert np.array_equal(want_f, want)
+        counted += int((want_c > 0).sum())
+        checked += 1
         s.close()
+    # the sweep says something about counting only on frames that hold centres: keep a later change of the draws or of
+    # synth.random_frames from quietly emptying it (FUZZ_MEASURED frames measured on the configurations that get a plan)
+    print(f"fuzz: {checked} configurations, {counted} frames with a nonzero centre count")
+    assert counted >= 250, (checked, counted)
 
 
 @pytest.mark.parametrize("slices", [2, 4, 8])
@@ -844,7 +885,7 @@ def test_scan_frame_slices(gpu_scanner_factory, slices, force_fb):
         s = gpu_scanner_factory(p, force_fb=force_fb)
         s.set_slices(slices)
         # cells whose votes are split across slices: sitting at vec-1 / vec / above only in the SUM
-        frames = []
+        frames, hand = [], []
         for trial in range(12):
             parts = []
             for (cx, cy) in [(30, 20), (31, 20), (70, 40), (70, 41)]:
@@ -853,15 +894,22 @@ def test_scan_frame_slices(gpu_scanner_factory, slices, force_fb):
                 a["dst_x"], a["dst_y"] = 16 * cx + 3, 16 * cy + 5
                 a["src_x"], a["src_y"] = a["dst_x"] - 9, a["dst_y"]
                 parts.append(a)
+            # by hand, from the draws: a horizontal pair in row 20 and a vertical pair in column 70, far apart
+            hand.append(pair_centres([(len(parts[0]), len(parts[1])), (len(parts[2]), len(parts[3]))], vec))
             filler = np.zeros(rng.randint(0, 400), dtype=m.MV_DTYPE)      # below threshold
             filler["dst_x"], filler["dst_y"] = rng.randint(0, 1920, size=len(filler)), rng.randint(0, 1080, size=len(filler))
             filler["src_x"], filler["src_y"] = filler["dst_x"] + 1, filler["dst_y"]
             fr = np.concatenate(parts + [filler])
             frames.append(fr[rng.permutation(len(fr))])               # votes of one cell land in different slices
         frames += [None, np.zeros(0, dtype=m.MV_DTYPE), frames[0][:3].copy()]
+        # the last frame: three records of frame 0; its voters (dst - src = 9) are counted per cell here
+        first3 = [int(((frames[-1]["dst_x"] == 16 * cx + 3) & (frames[-1]["dst_y"] == 16 * cy + 5) &
+                       (frames[-1]["dst_x"] - frames[-1]["src_x"] == 9)).sum()) for cx, cy in [(30, 20), (31, 20), (70, 40), (70, 41)]]
+        hand += [0, 0, pair_centres([(first3[0], first3[1]), (first3[2], first3[3])], vec)]
         b = m.FrameBatch.from_frames(frames)
-        want = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd)
+        want, centres = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd, with_counts=True)
         assert 0 < want.sum() < len(want)
+        assert centres.tolist() == hand and want.tolist() == [int(c >= clus) for c in hand]
         mv, off, sd = synth.random_frames(rng, 24, 6000, 1920, 1080, hot=0.6)
         assert_scan_parity(s, p, mv, off, sd)
         s.close()
@@ -875,10 +923,14 @@ def test_scan_frame_slices_big_grids_and_auto(gpu_scanner_factory):
     mv, off, pts, sd = synth.gen_stream(spec, 8)
     p = ob.params_from_config(3840, 2160)
     want = ob.scan_frames(p, mv, off, sd)
+    want_fc = ob.scan_centres(p, mv, off, sd)
+    assert np.array_equal(want_fc[0], want) and want_fc[1].max() >= 8
     for S in (0, 1, 4, 8):                                          # 0 = auto (8 frames << 512 slots: slices)
         s = gpu_scanner_factory(p)
         s.set_slices(S)
-        assert np.array_equal(s.check_frames(m.FrameBatch(mv, off, None, sd)), want), S
+        got = s.check_frames(m.FrameBatch(mv, off, None, sd))
+        assert np.array_equal(got, want), S
+        assert_centres_parity(s, p, mv, off, sd, plain_flags=got, want=want_fc, device=True, what=f"slices {S}")
     # 960x540 grid, 1-bit and 2-bit thermometer tiles, sliced; device-resident entry point
     specf = synth.spec_4k_fine(seed=9)
     specf.events = [synth.Event(1, 3, 300, 200, 6, 6, 9, 3), synth.Event(1, 4, 100, 250, 3, 120, 9, 0)]
@@ -886,13 +938,18 @@ def test_scan_frame_slices_big_grids_and_auto(gpu_scanner_factory):
     for vec, fb in ((1, None), (1, 2), (2, None)):
         pf = ob.params_from_config(3840, 2160, block_size=4, block_shift=2, vectors_needed=vec)
         wantf = ob.scan_frames(pf, mvf, offf, sdf)
+        wantf_f, wantf_c = ob.scan_centres(pf, mvf, offf, sdf)
+        assert np.array_equal(wantf_f, wantf)
+        assert wantf_c.max() >= 8 if vec == 1 else not wantf_c.any()      # one record per cell: 2 votes are never reached
+        d_mvf = torch.from_numpy(mvf.view(np.uint8).copy()).cuda()
+        d_offf, d_sdf = torch.from_numpy(offf.astype(np.int64)).cuda(), torch.from_numpy(sdf).cuda()
         for S in (0, 2, 8):
             s = gpu_scanner_factory(pf, force_fb=fb)
             s.set_slices(S)
-            got = s.check_frames_device(torch.from_numpy(mvf.view(np.uint8).copy()).cuda(),
-                                        torch.from_numpy(offf.astype(np.int64)).cuda(),
-                                        torch.from_numpy(sdf).cuda())
+            got = s.check_frames_device(d_mvf, d_offf, d_sdf)
             assert np.array_equal(got.cpu().numpy(), wantf), (vec, fb, S)
+            fl, ce = device_centres_of(s, d_mvf, d_offf, d_sdf, compact=False)
+            assert_counts_equal(ce, wantf_c, f"fine grid, vec {vec}, form {fb}, slices {S}", s.plan, fl, wantf)
     with pytest.raises(m.MtgpuError):
         s.set_slices(3)
 
@@ -945,7 +1002,10 @@ def test_scan_frame_slices_under_load(gpu_scanner_factory):
         spec = synth.spec_1080p(seed=50 + t, sub=2)
         spec.events = synth.scripted_events(spec, 24, seed=t)
         mv, off, pts, sd = synth.gen_stream(spec, 24)
-        tiles.append((mv, off, ob.scan_frames(p, mv, off, None)))
+        want_f, want_c = ob.scan_centres(p, mv, off, None)
+        tiles.append((mv, off, ob.scan_frames(p, mv, off, None), want_c))
+        assert np.array_equal(want_f, tiles[-1][2])
+    assert any(t[3].any() for t in tiles)                     # (one of the batches holds no centre at all)
     s1 = gpu_scanner_factory(p)
     s1.set_slices(1)
     s8 = gpu_scanner_factory(p)
@@ -954,7 +1014,7 @@ def test_scan_frame_slices_under_load(gpu_scanner_factory):
     s2.set_slices(4)
     reps = 80                                                 # 1920 frames, 15 360 workgroups with 8 slices
     for rnd in range(3):
-        for (mv, off, want) in tiles:
+        for (mv, off, want, want_c) in tiles:
             d_mv = torch.from_numpy(mv.view(np.uint8).copy()).cuda().repeat(reps)
             counts = np.tile(np.diff(off.astype(np.int64)), reps)
             d_off = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)).cuda()
@@ -962,6 +1022,8 @@ def test_scan_frame_slices_under_load(gpu_scanner_factory):
             for sc in (s8, s1, s2, s8):
                 got = sc.check_frames_device(d_mv, d_off).cpu().numpy()
                 assert np.array_equal(got, big), (rnd, sc.plan)
+                fl, ce = device_centres_of(sc, d_mv, d_off, None, compact=False)      # a vote lost in a hand-over shows in the count
+                assert_counts_equal(ce, np.tile(want_c, reps), f"round {rnd}", sc.plan, fl, big)
     del rng
 
 
@@ -988,6 +1050,8 @@ def test_scan_launch_chunking(gpu_scanner_factory):
             s.set_slices(slices)
         got = s.check_frames(m.FrameBatch(mv, off, None, sd))
         assert np.array_equal(got, want), (fb, slices, s.plan)
+        want_f, _ = assert_centres_parity(s, p, mv, off, sd, plain_flags=got, what=f"item chunk 7, form {fb}, slices {slices}")
+        assert np.array_equal(want_f, want)
 
 
 def test_scan_frames_per_workgroup_grouping(gpu_scanner_factory, monkeypatch):
@@ -1001,17 +1065,35 @@ def test_scan_frames_per_workgroup_grouping(gpu_scanner_factory, monkeypatch):
     for w, h, kw, fb in cases:
         p = ob.params_from_config(w, h, **kw)
         mv, off, sd = synth.random_frames(rng, 53, 1800, w, h, hot=0.4)
+        if w == 3840:
+            # on the fine grid the random frames never put 4 votes into two adjacent cells: their counts are all 0.  Seven
+            # planted frames follow them: frame k holds k vertical pairs of cells with 4 or 5 votes each, in columns 100
+            # apart, on the rows around the band seam (269 | 270) and elsewhere -- 2 k centres
+            planted = [cells_frame([(4 * (50 + 100 * i) + 1, 4 * (r + d) + 2, 4 + (i + d) % 2) for i, r in
+                                    enumerate([269, 268, 270, 100, 400, 269, 511][:k]) for d in (0, 1)]) for k in range(1, 8)]
+            tail = m.FrameBatch.from_frames(planted)
+            mv, sd = np.concatenate([mv, tail.mv]), np.concatenate([sd, tail.has_sd])
+            off = np.concatenate([off, off[-1] + tail.frame_off[1:]]).astype(np.uint64)
         want = ob.scan_frames(p, mv, off, sd)
+        want_fc = ob.scan_centres(p, mv, off, sd)
+        assert np.array_equal(want_fc[0], want)
+        if w == 1920:
+            assert len(set(want_fc[1].tolist())) >= 8
+        else:                                   # by hand: k vertical pairs, 2 centres each, behind 53 frames without a centre
+            assert want_fc[1].tolist() == [0] * 53 + [2 * k for k in range(1, 8)]
         for g in (1, 2, 3, 7, 64):
             monkeypatch.setenv("MTGPU_GROUP", str(g))
             s = gpu_scanner_factory(m.ScanParams.from_config(w, h, **kw), force_fb=fb)
             monkeypatch.delenv("MTGPU_GROUP")
-            assert np.array_equal(s.check_frames(m.FrameBatch(mv, off, None, sd)), want), (w, g)
+            got = s.check_frames(m.FrameBatch(mv, off, None, sd))
+            assert np.array_equal(got, want), (w, g)
             rec = m.pack_records(mv)
             got = s.check_frames_device_compact(torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).cuda(),
                                                 torch.from_numpy(off.astype(np.int64)).cuda(),
                                                 torch.from_numpy(sd).cuda()).cpu().numpy()
             assert np.array_equal(got, want), (w, g, "compact")
+            # host entry, device entry on 40-byte and on compact records: count for count
+            assert_centres_parity(s, p, mv, off, sd, plain_flags=got, want=want_fc, device=True, what=f"{w} group {g}")
 
 
 def test_scan_line_aligned_streams(gpu_scanner_factory):
@@ -1047,13 +1129,20 @@ def test_scan_line_aligned_streams(gpu_scanner_factory):
     assert len({(int(o) * 40) % 128 for o in b.frame_off[:-1]}) >= 12 and len({(int(o) * 8) % 128 for o in b.frame_off[:-1]}) >= 12
     want = ob.scan_frames(p, b.mv, b.frame_off, b.has_sd)
     assert want.tolist() == [1 if k == "A" else 0 for k in kinds]
+    want_fc = ob.scan_centres(p, b.mv, b.frame_off, b.has_sd)
+    # by hand: an "A" frame holds one horizontal pair of cells with 2 votes each (2 centres), every other frame no active pair
+    assert want_fc[1].tolist() == [2 if k == "A" else 0 for k in kinds] and np.array_equal(want_fc[0], want)
     rec = m.pack_records(b.mv)
     d_rec = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).cuda()
     d_off = torch.from_numpy(b.frame_off.astype(np.int64)).cuda()
     for fb in (None, 2, 8):                                         # 32-bit single tile, packed, banded (spill queue)
         s = gpu_scanner_factory(m.ScanParams.from_config(1920, 1080, vectors_needed=2, clusters_needed=1), force_fb=fb)
-        assert np.array_equal(s.check_frames(b), want), fb
+        got = s.check_frames(b)
+        assert np.array_equal(got, want), fb
         assert np.array_equal(s.check_frames_device_compact(d_rec, d_off, None).cpu().numpy(), want), (fb, "compact")
+        assert_centres_parity(s, p, b.mv, b.frame_off, b.has_sd, plain_flags=got, want=want_fc, device=True, what=f"form {fb}")
+        fl, ce = device_centres_of(s, d_rec, d_off, None, compact=True)               # has_sd NULL, as above
+        assert_counts_equal(ce, want_fc[1], f"form {fb}, compact, has_sd NULL", s.plan, fl, want)
 
 
 @pytest.mark.parametrize("grid", ["1080p", "4k"])
@@ -1106,8 +1195,12 @@ def test_compact_next_frame_prefetch(gpu_scanner_factory, monkeypatch, grid):
         p = ob.params_from_config(w, h, **kw)
         want = ob.scan_frames(p, b.mv, b.frame_off, b.has_sd)
         want_nosd = ob.scan_frames(p, b.mv, b.frame_off, None)
+        want_f, want_c = ob.scan_centres(p, b.mv, b.frame_off, b.has_sd, nthreads=4)
+        nosd_f, nosd_c = ob.scan_centres(p, b.mv, b.frame_off, None, nthreads=4)
+        assert np.array_equal(want_f, want) and np.array_equal(nosd_f, want_nosd)
         if kw["vectors_needed"] == 2:
             assert want.tolist() == [1 if k == "A" else 0 for k in kinds]
+            assert want_c.tolist() == [2 if k == "A" else 0 for k in kinds]    # by hand: one horizontal pair, 2 votes per cell
         for g in (2, 3, 4, 8, 25, 64, 1):
             monkeypatch.setenv("MTGPU_GROUP", str(g))
             s = gpu_scanner_factory(m.ScanParams.from_config(w, h, **kw))
@@ -1115,12 +1208,18 @@ def test_compact_next_frame_prefetch(gpu_scanner_factory, monkeypatch, grid):
             assert s.plan["block_threads"] == block and s.plan["counter_bits"] == 32
             got = s.check_frames_device_compact(d_rec, d_off, d_sd).cpu().numpy()
             assert np.array_equal(got, want), (grid, kw, g)
+            fl, ce = device_centres_of(s, d_rec, d_off, d_sd, compact=True)
+            assert_counts_equal(ce, want_c, f"{grid} {kw} group {g}", s.plan, fl, want)
             got = s.check_frames_device_compact(d_rec, d_off, None).cpu().numpy()
             assert np.array_equal(got, want_nosd), (grid, kw, g, "has_sd NULL")
+            fl, ce = device_centres_of(s, d_rec, d_off, None, compact=True)
+            assert_counts_equal(ce, nosd_c, f"{grid} {kw} group {g}, has_sd NULL", s.plan, fl, want_nosd)
             # a window that starts at an odd record and ends inside a group
             lo, hi = 2, len(sizes) - 3
             got = s.check_frames_device_compact(d_rec, d_off[lo:hi + 1].contiguous(), d_sd[lo:hi].contiguous()).cpu().numpy()
             assert np.array_equal(got, want[lo:hi]), (grid, kw, g, "window")
+            fl, ce = device_centres_of(s, d_rec, d_off[lo:hi + 1].contiguous(), d_sd[lo:hi].contiguous(), compact=True)
+            assert_counts_equal(ce, want_c[lo:hi], f"{grid} {kw} group {g}, window", s.plan, fl, want[lo:hi])
 
 
 def test_scratch_pool_stats_and_trim(gpu_scanner_factory):
@@ -1594,12 +1693,14 @@ def test_same_cell_runs_every_length_and_alignment(gpu_scanner_factory, force_fb
     rng = np.random.RandomState(1000 * force_fb + vec)
     frames = _run_frames(rng, 1920, 1080, 4, vec, 96, 3)
     b = m.FrameBatch.from_frames(frames)
-    want = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd)
+    want, centres = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd, with_counts=True)
     assert 5 < want.sum() < len(want) - 5
     rec8 = torch.from_numpy(m.pack_records(b.mv).view(np.uint8).copy()).cuda()
-    got8 = s.check_frames_device_compact(rec8, torch.from_numpy(b.frame_off.astype(np.int64)).cuda(),
-                                         torch.from_numpy(b.has_sd.astype(np.uint8)).cuda())
+    d_off, d_sd = torch.from_numpy(b.frame_off.astype(np.int64)).cuda(), torch.from_numpy(b.has_sd.astype(np.uint8)).cuda()
+    got8 = s.check_frames_device_compact(rec8, d_off, d_sd)
     assert np.array_equal(got8.cpu().numpy(), want)
+    fl, ce = device_centres_of(s, rec8, d_off, d_sd, compact=True)      # whatever the size of the batch
+    assert_counts_equal(ce, centres, "compact records", s.plan, fl, want)
 
 
 def test_same_cell_runs_across_the_band_seam(gpu_scanner_factory):
@@ -1669,6 +1770,8 @@ def test_recorded_wrong_flag_configuration_through_every_path(gpu_scanner_factor
     mv, off, sd = tail["mv"], tail["off"], tail["sd"]
     want = ob.scan_frames(p, mv, off, sd)
     assert want[33] == 1 and want[32] == 1
+    want_fc = ob.scan_centres(p, mv, off, sd)
+    assert np.array_equal(want_fc[0], want)
     for k_, v_ in head["knobs"].items():
         if v_:
             monkeypatch.setenv(k_, v_)
@@ -1682,11 +1785,15 @@ def test_recorded_wrong_flag_configuration_through_every_path(gpu_scanner_factor
     d_off = torch.from_numpy(off.astype(np.int64)).cuda()
     d_sd = torch.from_numpy(sd).cuda()
     for rep in range(3):
-        assert np.array_equal(s.check_frames(m.FrameBatch(mv, off, None, sd)), want), rep
+        got = s.check_frames(m.FrameBatch(mv, off, None, sd))
+        assert np.array_equal(got, want), rep
         assert np.array_equal(s.check_frames_device_compact(d_rec, d_off, d_sd).cpu().numpy(), want), ("compact", rep)
+        assert_centres_parity(s, p, mv, off, sd, plain_flags=got, want=want_fc, device=True, what=f"rep {rep}")
         # the second half alone, as the pipe's second batch shipped it (frame 33 = item 1 of the launch)
         got = s.check_frames_device_compact(d_rec, d_off[32:].contiguous(), d_sd[32:].contiguous()).cpu().numpy()
         assert np.array_equal(got, want[32:]), ("compact, frames 32..63", rep)
+        fl, ce = device_centres_of(s, d_rec, d_off[32:].contiguous(), d_sd[32:].contiguous(), compact=True)
+        assert_counts_equal(ce, want_fc[1][32:], f"compact, frames 32..63, rep {rep}", s.plan, fl, want[32:])
         pipe = m.ScanPipe(s, *tail["pipe"])
         for f in range(tail["n_frames"]):
             fr = mv[int(off[f]):int(off[f + 1])]
@@ -1694,6 +1801,13 @@ def test_recorded_wrong_flag_configuration_through_every_path(gpu_scanner_factor
         out = pipe.drain()
         pipe.close()
         assert [fl for _, fl, _ in out] == want.tolist(), ("pipe", rep)
+        pipe = m.ScanPipe(s, *tail["pipe"], centres=True)               # the same geometry with the counts switched on
+        for f in range(tail["n_frames"]):
+            fr = mv[int(off[f]):int(off[f + 1])]
+            pipe.feed(fr if sd[f] else None, float(f), tag=f)
+        out = pipe.drain_centres()
+        pipe.close()
+        assert_counts_equal([c for _, _, _, c in out], want_fc[1], f"pipe, rep {rep}", s.plan, [fl for _, fl, _, _ in out], want)
 
 
 def _raster_frame(rows, gw, mult, special=(), drop=(), lead=0, shift=2, step_px=3):
@@ -1743,11 +1857,17 @@ def test_dense_raster_votes_travel_as_spans_and_count_exactly(gpu_scanner_factor
         frames.append(_raster_frame(rows, gw, mult, lead=lead))
         expect.append(1 if mult >= 4 else 0)
     b = m.FrameBatch.from_frames(frames)
-    want = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd)
+    want, centres = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd, with_counts=True)
     assert want.tolist() == expect
+    # by hand: the pair frames hold exactly the pair (2), the frames without it nothing (3 votes everywhere), and with 4 / 5
+    # records per cell every cell of the 18 rows outside columns 0 and 959 is a centre
+    assert centres.tolist() == [2, 0] * len(spots) + [0, 0, 18 * 958, 18 * 958]
     rec8 = torch.from_numpy(m.pack_records(b.mv).view(np.uint8).copy()).cuda()
-    got8 = s.check_frames_device_compact(rec8, torch.from_numpy(b.frame_off.astype(np.int64)).cuda(), None)
+    d_off = torch.from_numpy(b.frame_off.astype(np.int64)).cuda()
+    got8 = s.check_frames_device_compact(rec8, d_off, None)
     assert got8.cpu().numpy().tolist() == expect
+    fl, ce = device_centres_of(s, rec8, d_off, None, compact=True)
+    assert_counts_equal(ce, centres, "compact records, has_sd NULL", s.plan, fl, want)
 
 
 @pytest.mark.parametrize("vec,force_fb", [(3, None), (6, None), (8, None), (12, None), (4, 32)])
@@ -1772,8 +1892,9 @@ def test_spans_on_other_banded_counter_forms(gpu_scanner_factory, vec, force_fb)
         frames.append(_raster_frame(rows, 960, vec - 1, lead=5 * i + 1))
         expect.append(0)
     b = m.FrameBatch.from_frames(frames)
-    want = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd)
+    want, centres = assert_scan_parity(s, p, b.mv, b.frame_off, b.has_sd, with_counts=True)
     assert want.tolist() == expect
+    assert centres.tolist() == [2, 0] * 5          # by hand: the pair and nothing else reaches VECTORS_NEEDED
 
 
 def test_device_entry_points_with_flags_in_pinned_host_memory(gpu_scanner_factory):
@@ -1850,14 +1971,21 @@ def test_work_list_skips_frames_without_side_data(gpu_scanner_factory, monkeypat
     b = m.FrameBatch.from_frames(frames)
     want = ob.scan_frames(p, b.mv, b.frame_off, b.has_sd)
     assert 10 < want.sum() < 150
+    want_fc = ob.scan_centres(p, b.mv, b.frame_off, b.has_sd)
+    assert np.array_equal(want_fc[0], want)
     rec8 = torch.from_numpy(m.pack_records(b.mv).view(np.uint8).copy()).cuda()
     d_off = torch.from_numpy(b.frame_off.astype(np.int64)).cuda()
     d_sd = torch.from_numpy(b.has_sd.astype(np.uint8)).cuda()
     for _ in range(2):                                      # twice: the scratch of the first launch is reused
-        assert np.array_equal(s.check_frames(b), want)
+        got = s.check_frames(b)
+        assert np.array_equal(got, want)
         assert np.array_equal(s.check_frames_device_compact(rec8, d_off, d_sd).cpu().numpy(), want), "compact"
+        # host entry, device entry on 40-byte and compact records: count for count, also the frames the planning kernels answer
+        assert_centres_parity(s, p, b.mv, b.frame_off, b.has_sd, plain_flags=got, want=want_fc, device=True)
     # has_sd == NULL: side data iff records (with vectors_needed >= 1 a frame with empty side data is false either way)
     assert np.array_equal(s.check_frames_device_compact(rec8, d_off, None).cpu().numpy(), want), "compact, has_sd NULL"
+    fl, ce = device_centres_of(s, rec8, d_off, None, compact=True)
+    assert_counts_equal(ce, want_fc[1], "compact, has_sd NULL", s.plan, fl, want)
     # every flag is WRITTEN, also the ones the planning kernels answer: start from a poisoned buffer
     d_flags = torch.full((203,), 7, dtype=torch.uint8, device="cuda")
     s.check_frames_device_compact(rec8, d_off, d_sd, d_flags)

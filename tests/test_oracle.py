@@ -123,6 +123,52 @@ def test_scan_frames_threads_and_null_has_sd():
     assert np.array_equal(ob.scan_frames(p, mv, off, None), a)
 
 
+@pytest.mark.parametrize("w,h,kw", [
+    (1920, 1080, dict()), (1920, 1080, dict(vertical_mask=0.0)), (1920, 1080, dict(vectors_needed=0, clusters_needed=3)),
+    (1920, 1080, dict(vectors_needed=1, clusters_needed=1)), (1920, 1080, dict(vectors_needed=255)),
+    (1280, 720, dict(block_size=4, block_shift=2, vectors_needed=1, clusters_needed=7)),              # fine grid
+    (640, 480, dict(block_size=1, block_shift=0, vectors_needed=1, vertical_mask=0.0)),
+    (1040, 64, dict(vertical_mask=0.0, clusters_needed=-2))])
+def test_batch_centre_counts_equal_the_per_frame_count(w, h, kw):
+    """ob.scan_centres (mto_scan_centres_mt): on ragged random frames its counts equal the per-frame
+    mto_check_frame_count and the independent numpy model, and its flags equal mto_scan_frames' (the early-exit
+    path) -- with has_sd given and None, on 1 and on 8 threads.  This is what lets a GPU test take flags and
+    counts from one oracle pass."""
+    import zlib
+    rng = np.random.RandomState(zlib.crc32(repr((w, h, sorted(kw.items()))).encode()) % (2 ** 31))
+    p = ob.params_from_config(w, h, **kw)
+    mv, off, sd = synth.random_frames(rng, 37, 2500, w, h, hot=0.5)
+    sd[5] = 1                                                     # side data ...
+    off[6:] -= off[6] - off[5]                                    # ... with zero records (frame 5 loses its records)
+    seen = set()
+    for has_sd in (sd, None):
+        per_frame, model = [], []
+        for f in range(37):
+            fr = mv[int(off[f]):int(off[f + 1])]
+            on = bool(sd[f]) if has_sd is not None else len(fr) > 0
+            flag, centres, _ = ob.check_frame(p, fr, on, count_centres=True)
+            per_frame.append((flag, centres))
+            model.append(check_frame_np(p, fr, on))
+        assert per_frame == model
+        early = ob.scan_frames(p, mv, off, has_sd)
+        for nt in (1, 8):
+            flags, centres = ob.scan_centres(p, mv, off, has_sd, nthreads=nt)
+            assert centres.dtype == np.uint32 and flags.dtype == np.uint8
+            assert centres.tolist() == [c for _, c in per_frame], (nt, has_sd is None)
+            assert flags.tolist() == [f for f, _ in per_frame] and np.array_equal(flags, early), (nt, has_sd is None)
+        seen |= set(centres.tolist())
+    if kw.get("vectors_needed", 2) not in (0, 255):               # (0: every cell is active; 255: hardly any)
+        assert len(seen) >= 6, sorted(seen)                       # the input says something about counting
+    # no frames, one frame, and the arguments the C function refuses
+    f0, c0 = ob.scan_centres(p, mv[:0], np.zeros(1, dtype=np.uint64), None, nthreads=8)
+    assert f0.size == 0 and c0.size == 0
+    f1, c1 = ob.scan_centres(p, mv, off[:2], None, nthreads=8)
+    assert (int(f1[0]), int(c1[0])) == per_frame[0]
+    import ctypes as C
+    c = p.to_c()
+    assert ob.lib().mto_scan_centres_mt(C.byref(c), None, off.ctypes.data_as(C.c_void_p), None, 3, None, None, 1) != 0
+
+
 # ------------------------------------------------------------------ merge
 
 @pytest.mark.parametrize("name,kw,case", load_merge_cases(), ids=id_of)
