@@ -437,4 +437,9 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
 #ifdef __cplusplus
 }
 #endif
+
+/* The per-second motion scalar (tools/motion_scalar.cpp:61-84) — three more entry points of this ABI, declared in a
+ * header of their own that every includer of this one gets. */
+#include "mtgpu_motion.h"
+
 #endif /* MTGPU_H */

@@ -137,6 +137,16 @@ ABI = {
     "mtgpu_gather_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_motion.h declares (the motion scalar; mtgpu.h includes it).
+ABI_MOTION = {
+    "mtgpu_motion_scores_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "mtgpu_motion_bins_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtgpu_motion_scalar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -166,7 +176,7 @@ def load_library(path=None):
             f"{p} not found: build it with `make -C {os.path.join(PKG_DIR, 'csrc')}` "
             "(or __graft_entry__.build()).  There is no fallback path.")
     lib = C.CDLL(p)
-    for name, (res, args) in ABI.items():
+    for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

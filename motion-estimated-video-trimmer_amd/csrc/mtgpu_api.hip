@@ -20,6 +20,7 @@
 #include "knobs.h"
 #include "pack_simd.h"
 #include "merge_kernels.h"
+#include "scalar_kernels.h"
 #include "scan_kernels.h"
 
 namespace {
@@ -1174,6 +1175,140 @@ int mtgpu_merge_segments(mtgpu_ctx *c, const double *ts, uint64_t n, const mt_me
   }
   if (res->n_segments > cap) return fail(MT_ERR_CAPACITY, "need %llu segments, capacity %llu",
                                          (unsigned long long)res->n_segments, (unsigned long long)cap);
+  return MT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- motion scalar (tools/motion_scalar.cpp:61-84)
+
+namespace {
+
+// scores (+ terms) of a device-resident batch on `st`: launch scratch for the work list, the planner, the kernel.
+// sys_*: 1 = the output is not device memory, 0 = device memory, -1 = ask the runtime
+int motion_scores_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
+                     uint32_t n_frames, double *d_scores, uint32_t *d_terms, hipStream_t st, int sys_scores, int sys_terms) {
+  mtgpu::ScoresLaunch L;
+  L.mv = static_cast<const unsigned char *>(d_mv);
+  L.n_records = n_records;
+  L.rebase = rebase;
+  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
+  L.n_frames = n_frames;
+  L.scores = d_scores;
+  L.terms = d_terms;
+  L.sys_scores = sys_scores < 0 ? result_memory_is_sys(d_scores) : sys_scores;
+  L.sys_terms = d_terms ? (sys_terms < 0 ? result_memory_is_sys(d_terms) : sys_terms) : 0;
+  L.stream = st;
+  void *scratch = nullptr;
+  int slot = -1;
+  const int rc0 = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
+  if (rc0 != MT_OK) return rc0;
+  L.plan_ws = scratch;
+  const hipError_t e = mtgpu::launch_motion_scores(L);
+  scratch_release(c, slot, st);
+  if (e != hipSuccess) return hip_fail(e, "motion scores launch");
+  return MT_OK;
+}
+
+int motion_bins_on(const double *d_scores, const uint32_t *d_terms, const double *d_pts, const uint64_t *d_stream_off,
+                   uint32_t n_streams, uint32_t n_sec, double *d_acc, uint64_t *d_bin_terms, hipStream_t st, int sys_acc,
+                   int sys_bin_terms) {
+  mtgpu::BinsLaunch L;
+  L.scores = d_scores;
+  L.terms = d_terms;
+  L.pts = d_pts;
+  L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
+  L.n_streams = n_streams;
+  L.n_sec = n_sec;
+  L.acc = d_acc;
+  L.bin_terms = reinterpret_cast<unsigned long long *>(d_bin_terms);
+  L.sys_acc = sys_acc < 0 ? result_memory_is_sys(d_acc) : sys_acc;
+  L.sys_bin_terms = d_bin_terms ? (sys_bin_terms < 0 ? result_memory_is_sys(d_bin_terms) : sys_bin_terms) : 0;
+  L.stream = st;
+  const hipError_t e = mtgpu::launch_motion_bins(L);
+  if (e != hipSuccess) return hip_fail(e, "motion bins launch");
+  return MT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtgpu_motion_scores_device(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uint64_t *d_frame_off,
+                               uint32_t n_frames, double *d_scores, uint32_t *d_terms, void *stream) {
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  if (n_frames == 0) return MT_OK;
+  if (!d_frame_off || !d_scores) return fail(MT_ERR_INVALID, "d_frame_off/d_scores is NULL");
+  if (n_records > 0 && !d_mv) return fail(MT_ERR_INVALID, "d_mv is NULL with n_records > 0");
+  if (((uintptr_t)d_mv & 3u) != 0) return fail(MT_ERR_INVALID, "d_mv must be 4-byte aligned");
+  if (((uintptr_t)d_scores & 7u) != 0) return fail(MT_ERR_INVALID, "d_scores must be 8-byte aligned");
+  if (((uintptr_t)d_terms & 3u) != 0) return fail(MT_ERR_INVALID, "d_terms must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  return motion_scores_on(c, d_mv, n_records, 0, d_frame_off, n_frames, d_scores, d_terms, static_cast<hipStream_t>(stream),
+                          -1, -1);
+}
+
+int mtgpu_motion_bins_device(mtgpu_ctx *c, const double *d_scores, const uint32_t *d_terms, const double *d_pts,
+                             const uint64_t *d_stream_off, uint32_t n_streams, uint32_t n_sec, double *d_acc,
+                             uint64_t *d_bin_terms, void *stream) {
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  if (n_sec == 0) return fail(MT_ERR_INVALID, "n_sec is 0");
+  if (n_streams == 0) return MT_OK;
+  if (!d_scores || !d_pts || !d_stream_off || !d_acc) return fail(MT_ERR_INVALID, "d_scores/d_pts/d_stream_off/d_acc is NULL");
+  if (d_bin_terms && !d_terms) return fail(MT_ERR_INVALID, "d_bin_terms needs d_terms");
+  if ((((uintptr_t)d_acc | (uintptr_t)d_bin_terms | (uintptr_t)d_scores | (uintptr_t)d_pts) & 7u) != 0)
+    return fail(MT_ERR_INVALID, "d_scores, d_pts, d_acc and d_bin_terms must be 8-byte aligned");
+  if (((uint64_t)n_sec + mtgpu::kBinsBlock - 1) / mtgpu::kBinsBlock * (uint64_t)n_streams >= (1ull << 31))
+    return fail(MT_ERR_INVALID, "%u streams x %u seconds: too many bins for one call", n_streams, n_sec);
+  HIP_TRY(hipSetDevice(c->device));
+  return motion_bins_on(d_scores, d_terms, d_pts, d_stream_off, n_streams, n_sec, d_acc, d_bin_terms,
+                        static_cast<hipStream_t>(stream), -1, -1);
+}
+
+int mtgpu_motion_scalar(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const double *pts, uint32_t n_frames,
+                        uint32_t n_sec, double *acc, uint64_t *bin_terms) {
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  if (n_sec == 0) return fail(MT_ERR_INVALID, "n_sec is 0");
+  if (!acc) return fail(MT_ERR_INVALID, "acc is NULL");
+  if (n_frames > 0 && (!frame_off || !pts)) return fail(MT_ERR_INVALID, "frame_off/pts is NULL");
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
+  const uint64_t r_begin = n_frames ? frame_off[0] : 0, r_end = n_frames ? frame_off[n_frames] : 0;
+  const uint64_t n_records = r_end - r_begin;
+  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
+
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
+  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
+  // one staging block: stream_off[2] | pts[F] | scores[F] | acc[n_sec] | bin_terms[n_sec] | terms[F]
+  const size_t o_soff = 0, o_pts = 16, o_scores = o_pts + sizeof(double) * (size_t)n_frames;
+  const size_t o_acc = o_scores + sizeof(double) * (size_t)n_frames, o_bt = o_acc + sizeof(double) * (size_t)n_sec;
+  const size_t o_terms = o_bt + sizeof(uint64_t) * (size_t)n_sec, total = o_terms + sizeof(uint32_t) * (size_t)n_frames;
+  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
+  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
+  hipStream_t st = c->stream;
+  DrainOnExit drain{st};
+  const uint64_t soff[2] = {0, n_frames};
+  HIP_TRY(hipMemcpyAsync(d + o_soff, soff, sizeof soff, hipMemcpyHostToDevice, st));
+  if (n_frames) {
+    if (n_records)
+      HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_pts, pts, sizeof(double) * (size_t)n_frames, hipMemcpyHostToDevice, st));
+    // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
+    rc = motion_scores_on(c, c->d_mv.p, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p), n_frames,
+                          reinterpret_cast<double *>(d + o_scores), reinterpret_cast<uint32_t *>(d + o_terms), st, 0, 0);
+    if (rc != MT_OK) return rc;
+  }
+  rc = motion_bins_on(reinterpret_cast<const double *>(d + o_scores), reinterpret_cast<const uint32_t *>(d + o_terms),
+                      reinterpret_cast<const double *>(d + o_pts), reinterpret_cast<const uint64_t *>(d + o_soff), 1, n_sec,
+                      reinterpret_cast<double *>(d + o_acc), reinterpret_cast<uint64_t *>(d + o_bt), st, 0, 0);
+  if (rc != MT_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(acc, d + o_acc, sizeof(double) * (size_t)n_sec, hipMemcpyDeviceToHost, st));
+  if (bin_terms) HIP_TRY(hipMemcpyAsync(bin_terms, d + o_bt, sizeof(uint64_t) * (size_t)n_sec, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return MT_OK;
 }
 

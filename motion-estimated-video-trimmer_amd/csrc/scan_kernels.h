@@ -92,6 +92,13 @@ struct ScanLaunch {
 };
 
 hipError_t launch_scan(const ScanLaunch &L);
+// The planning kernels alone (what launch_scan runs ahead of the scan): the work list of the frames WITH side data into
+// work[0 .. n_frames] and, where `flags` / `centres` are not null, the answer of every other frame.  blk_cnt: one count
+// per planning block (both inside plan_scratch_bytes(n_frames)).  For launches that walk the same list with a kernel of
+// their own (scalar_kernels.hip).
+hipError_t launch_plan(const unsigned long long *frame_off, const unsigned char *has_sd, unsigned long long n_records,
+                       unsigned long long rebase, unsigned int n_frames, unsigned char *flags, int sys_flags,
+                       unsigned int *centres, int sys_centres, WorkItem *work, unsigned int *blk_cnt, hipStream_t stream);
 // *first_bad (device, pre-set to 0xffffffff) = smallest f with frame_off[f] > frame_off[f + 1]
 hipError_t launch_check_offsets(const unsigned long long *frame_off, unsigned int n_frames, unsigned int *first_bad,
                                 hipStream_t stream);

@@ -1232,18 +1232,19 @@ __global__ __launch_bounds__(kPlanBlock) void plan_scatter_kernel(
   }
 }
 
-static hipError_t launch_plan(const ScanLaunch &L, WorkItem *work, unsigned int *blk_cnt) {
-  const unsigned int per = plan_per(L.n_frames), blocks = plan_blocks(L.n_frames);
+hipError_t launch_plan(const unsigned long long *frame_off, const unsigned char *has_sd, unsigned long long n_records,
+                       unsigned long long rebase, unsigned int n_frames, unsigned char *flags, int sys_flags,
+                       unsigned int *centres, int sys_centres, WorkItem *work, unsigned int *blk_cnt, hipStream_t stream) {
+  const unsigned int per = plan_per(n_frames), blocks = plan_blocks(n_frames);
   const bool fused = blocks <= kPlanFused;       // (then per == 1)
   if (!fused) {
-    hipLaunchKernelGGL(plan_count_kernel, dim3(blocks), dim3(kPlanBlock), 0, L.stream, L.frame_off, L.has_sd, L.n_records,
-                       L.n_frames, per, blk_cnt);
+    hipLaunchKernelGGL(plan_count_kernel, dim3(blocks), dim3(kPlanBlock), 0, stream, frame_off, has_sd, n_records,
+                       n_frames, per, blk_cnt);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(plan_scatter_kernel, dim3(blocks), dim3(kPlanBlock), 0, L.stream, L.frame_off, L.has_sd, L.n_records,
-                     L.rebase, L.n_frames, per, fused ? nullptr : blk_cnt, work, L.flags, L.k.sys_flags,
-                     L.centres, L.k.sys_centres);
+  hipLaunchKernelGGL(plan_scatter_kernel, dim3(blocks), dim3(kPlanBlock), 0, stream, frame_off, has_sd, n_records,
+                     rebase, n_frames, per, fused ? nullptr : blk_cnt, work, flags, sys_flags, centres, sys_centres);
   return hipGetLastError();
 }
 
@@ -1347,7 +1348,8 @@ hipError_t launch_scan(const ScanLaunch &L) {
   {
     WorkItem *work = static_cast<WorkItem *>(L.plan_ws);
     unsigned int *blk_cnt = reinterpret_cast<unsigned int *>(work + (size_t)L.n_frames + 1u);
-    e = launch_plan(L, work, blk_cnt);
+    e = launch_plan(L.frame_off, L.has_sd, L.n_records, L.rebase, L.n_frames, L.flags, L.k.sys_flags, L.centres,
+                    L.k.sys_centres, work, blk_cnt, L.stream);
     if (e != hipSuccess) return e;
   }
   // (profiling: the event between planning and scan)

@@ -404,6 +404,98 @@ class MotionScanner:
         self._held.append((ev, ws))
         return seg, res
 
+    # ------------------------------------------------------- motion scalar
+    def motion_scores(self, batch: FrameBatch) -> Tuple[np.ndarray, np.ndarray]:
+        """Per-frame motion scores of a host batch (tools/motion_scalar.cpp:68-83 for every frame): the sum of
+        sqrt(dx^2 + dy^2) * w * h over the frame's records with motion_scale != 0, and the number of those records.
+        Returns (scores float64 [F], terms uint32 [F])."""
+        n = batch.n_frames
+        if n <= 0:
+            return np.zeros(0, dtype=np.float64), np.zeros(0, dtype=np.uint32)
+        import torch
+        dev = torch.device("cuda", self.device)
+        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        d_mv = torch.from_numpy(mv.view(np.uint8).reshape(-1).copy()).to(dev)
+        d_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+        scores, terms = self.motion_scores_device(d_mv, d_off)
+        torch.cuda.synchronize(dev)
+        return scores.cpu().numpy(), terms.cpu().numpy().view(np.uint32)
+
+    def motion_scores_device(self, records, frame_off, scores=None, terms=None, stream=None):
+        """Device-resident batch (torch CUDA tensors) -> (scores float64 [F], terms int32 [F], the bits of the library's
+        uint32 counts).  records: the packed 40-byte records, frame_off: int64 [F+1].  terms=False: only the scores
+        are computed (returns (scores, None)).  Asynchronous on `stream` (default: torch's current stream)."""
+        import torch
+        n_frames = frame_off.numel() - 1
+        dev = frame_off.device
+        if scores is None:
+            scores = torch.empty(max(n_frames, 0), dtype=torch.float64, device=dev)
+        if terms is None:
+            terms = torch.empty(max(n_frames, 0), dtype=torch.int32, device=dev)
+        elif terms is False:
+            terms = None
+        if n_frames <= 0:
+            return scores, terms
+        assert records.is_contiguous() and frame_off.is_contiguous() and scores.is_contiguous()
+        assert frame_off.dtype == torch.int64 and scores.dtype == torch.float64 and scores.numel() >= n_frames
+        assert terms is None or (terms.dtype == torch.int32 and terms.is_contiguous() and terms.numel() >= n_frames)
+        n_records = (records.numel() * records.element_size()) // 40
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(self._lib.mtgpu_motion_scores_device(
+            self._ctx, records.data_ptr() if n_records else None, n_records, frame_off.data_ptr(), n_frames,
+            scores.data_ptr(), None if terms is None else terms.data_ptr(), st))
+        return scores, terms
+
+    def motion_bins_device(self, scores, terms, pts, stream_off, n_sec: int, acc=None, bin_terms=None, stream=None):
+        """Per-second bins of S streams (tools/motion_scalar.cpp:62-66, :82) from per-frame scores: scores float64 [F],
+        terms int32 [F] or None, pts float64 [F] (seconds; negative, NaN and >= n_sec are skipped), stream_off int64
+        [S+1].  Returns (acc float64 [S, n_sec], bin_terms int64 [S, n_sec] or None without terms): every bin adds
+        its frames' scores in ascending frame order.  Asynchronous on `stream`."""
+        import torch
+        dev = pts.device
+        n_streams = stream_off.numel() - 1
+        n_sec = int(n_sec)
+        if acc is None:
+            acc = torch.empty((max(n_streams, 0), n_sec), dtype=torch.float64, device=dev)
+        if bin_terms is None and terms is not None:
+            bin_terms = torch.empty((max(n_streams, 0), n_sec), dtype=torch.int64, device=dev)
+        elif bin_terms is False:
+            bin_terms = None
+        assert scores.dtype == torch.float64 and pts.dtype == torch.float64 and stream_off.dtype == torch.int64
+        assert scores.is_contiguous() and pts.is_contiguous() and stream_off.is_contiguous() and acc.is_contiguous()
+        assert acc.dtype == torch.float64 and acc.numel() >= max(n_streams, 0) * n_sec
+        assert terms is None or (terms.dtype == torch.int32 and terms.is_contiguous())
+        assert bin_terms is None or (bin_terms.dtype == torch.int64 and bin_terms.is_contiguous()
+                                     and bin_terms.numel() >= max(n_streams, 0) * n_sec)
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(self._lib.mtgpu_motion_bins_device(
+            self._ctx, scores.data_ptr(), None if terms is None else terms.data_ptr(), pts.data_ptr(),
+            stream_off.data_ptr(), max(n_streams, 0), n_sec, acc.data_ptr(),
+            None if bin_terms is None else bin_terms.data_ptr(), st))
+        return acc, bin_terms
+
+    def motion_scalar(self, batch: FrameBatch, pts_seconds, n_sec: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """tools/motion_scalar.cpp:61-84 for one stream in host memory: (acc float64 [n_sec], bin_terms uint64 [n_sec]).
+        pts_seconds[f]: the frame's timestamp in seconds, None (or negative) = null: the frame is skipped.  n_sec None:
+        one more than the largest second that occurs.  A second has a row in the reference tool's output iff
+        bin_terms[second] > 0."""
+        pts = np.array([-1.0 if p is None else float(p) for p in pts_seconds], dtype=np.float64)
+        n = batch.n_frames
+        if len(pts) != max(n, 0):
+            raise ValueError(f"{len(pts)} timestamps for {n} frames")
+        if n_sec is None:
+            ok = pts[np.isfinite(pts) & (pts >= 0)]
+            n_sec = int(np.floor(ok.max())) + 1 if len(ok) else 1
+        n_sec = int(n_sec)
+        acc = np.zeros(max(n_sec, 0), dtype=np.float64)
+        bin_terms = np.zeros(max(n_sec, 0), dtype=np.uint64)
+        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        check(self._lib.mtgpu_motion_scalar(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(pts), max(n, 0),
+                                            n_sec, _ptr(acc) if n_sec > 0 else None, _ptr(bin_terms) if n_sec > 0 else None))
+        return acc, bin_terms
+
     def scan_range(self, frame_pts: Sequence[int], frames: Sequence[Optional[np.ndarray]],
                    time_base: float, start: float, end: float, video_fps: float,
                    target_fps: Optional[float] = None) -> List[float]:
