@@ -134,7 +134,7 @@ enum {
   MT_ERR_DEVICE = 3,    /* HIP runtime error (see *_last_error())              */
   MT_ERR_NOMEM = 4,
   MT_ERR_BUSY = 5,      /* every staging buffer of a pipe is in flight: collect first */
-  MT_ERR_UNSUPPORTED = 6 /* the host CPU lacks the instruction set that was asked for      */
+  MT_ERR_UNSUPPORTED = 6 /* the host CPU lacks the instruction set that was asked for; the sweep has no form for this grid */
 };
 
 #ifdef __cplusplus

@@ -442,4 +442,8 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * header of their own that every includer of this one gets. */
 #include "mtgpu_motion.h"
 
+/* One scan for a grid of (MV_THRESHOLD_SQ, VECTORS_NEEDED) settings (src/motion_scanner.cpp:246-294) — three more entry
+ * points, declared the same way. */
+#include "mtgpu_sweep.h"
+
 #endif /* MTGPU_H */

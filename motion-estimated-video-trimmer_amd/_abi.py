@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libmtgpu.so")
 
 LAYOUT_COMPACT8, LAYOUT_AOS40, LAYOUT_ZERO_COPY, LAYOUT_CENTRES = 0, 1, 2, 4
 SWEEP_MAX_LEVELS = 16
+SWEEP_MAX_THRESHOLDS, SWEEP_MAX_VECTORS = 8, 8      # include/mtgpu_sweep.h
 COMPACT_DTYPE = np.dtype([("src_x", "<i2"), ("src_y", "<i2"), ("dst_x", "<i2"), ("dst_y", "<i2")])
 MT_OK, MT_ERR_INVALID, MT_ERR_CAPACITY, MT_ERR_DEVICE, MT_ERR_NOMEM, MT_ERR_BUSY, MT_ERR_UNSUPPORTED = 0, 1, 2, 3, 4, 5, 6
 # copy-out loops of mtgpu_pack_records_with (include/mtgpu.h)
@@ -61,6 +62,11 @@ class PlanC(C.Structure):
                 ("lds_bytes", C.c_int32), ("counter_bits", C.c_int32), ("device", C.c_int32),
                 ("cu_count", C.c_int32), ("chunk_rows", C.c_int32),
                 ("counter_mode", C.c_int32), ("_pad", C.c_int32)]
+
+
+class SweepPlanC(C.Structure):
+    _fields_ = [("thresholds_per_pass", C.c_int32), ("passes", C.c_int32), ("lds_bytes", C.c_int32),
+                ("counter_bits", C.c_int32)]
 
 
 class CtxStatsC(C.Structure):
@@ -147,6 +153,16 @@ ABI_MOTION = {
                                       C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_sweep.h declares (the setting sweep; mtgpu.h includes it).
+ABI_SWEEP = {
+    "mtgpu_scan_sweep_preview": (C.c_int, [C.POINTER(ScanParamsC), C.c_int, C.c_uint32, C.c_uint32, C.POINTER(SweepPlanC)]),
+    "mtgpu_scan_sweep_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                          C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, C.c_void_p,
+                                          C.c_void_p]),
+    "mtgpu_scan_frames_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double),
+                                          C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -176,7 +192,7 @@ def load_library(path=None):
             f"{p} not found: build it with `make -C {os.path.join(PKG_DIR, 'csrc')}` "
             "(or __graft_entry__.build()).  There is no fallback path.")
     lib = C.CDLL(p)
-    for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()):
+    for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -22,6 +22,7 @@
 #include "merge_kernels.h"
 #include "scalar_kernels.h"
 #include "scan_kernels.h"
+#include "sweep_kernels.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -1308,6 +1309,214 @@ int mtgpu_motion_scalar(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off
   if (rc != MT_OK) return rc;
   HIP_TRY(hipMemcpyAsync(acc, d + o_acc, sizeof(double) * (size_t)n_sec, hipMemcpyDeviceToHost, st));
   if (bin_terms) HIP_TRY(hipMemcpyAsync(bin_terms, d + o_bt, sizeof(uint64_t) * (size_t)n_sec, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- setting sweep (src/motion_scanner.cpp:246-294 for every
+// (MV_THRESHOLD_SQ, VECTORS_NEEDED) pair from one read of the records; include/mtgpu_sweep.h)
+
+namespace {
+
+static_assert(MT_SWEEP_MAX_THRESHOLDS == mtgpu::kSweepMaxThr && MT_SWEEP_MAX_VECTORS == mtgpu::kSweepMaxVec, "sweep limits");
+
+// How the thresholds of a call are spread over launches for this grid and this much LDS: as many tiles per pass as
+// fit next to a mask buffer of min(R, 8) + 2 rows (next to three rows if not even one tile fits that way), the passes
+// balanced, and whatever room is left goes to the mask buffer.  *chunk_rows: centre rows per phase-2 chunk.
+int sweep_plan(const mt_scan_params &p, int lds_max, uint32_t n_thr, uint32_t n_vec, mtgpu_sweep_plan *out, int *chunk_rows) {
+  const int y_lo = p.vertical_margin;
+  int y_hi = p.grid_h - p.vertical_margin;
+  if (y_hi < y_lo) y_hi = y_lo;
+  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const long long tile = (long long)mtgpu::sweep_tile_words(p.grid_w, R) * 4;
+  const long long mask_row = (long long)((p.grid_w + 63) / 64) * 8 * (long long)n_vec;
+  const long long fixed = (long long)mtgpu::kSweepMaxThr * mtgpu::kSweepMaxVec * 4;
+  const auto fits = [&](long long n, long long rows) { return n * tile + (rows + 2) * mask_row + fixed <= (long long)lds_max; };
+  if (!fits(1, 1))
+    return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows (%lld bytes) and a three-row mask buffer "
+                "do not fit %d bytes of LDS; the sweep has no banded form (scan one setting per context instead)",
+                p.grid_w, p.grid_h, R + 2, tile, lds_max);
+  const long long want = R < 8 ? R : 8;
+  long long fit = 0;
+  for (long long n = n_thr; n >= 1 && fit == 0; --n) if (fits(n, want)) fit = n;
+  for (long long n = n_thr; n >= 1 && fit == 0; --n) if (fits(n, 1)) fit = n;
+  const long long passes = ((long long)n_thr + fit - 1) / fit, per = ((long long)n_thr + passes - 1) / passes;
+  long long ch = ((long long)lds_max - per * tile - fixed) / mask_row - 2;
+  if (ch > R) ch = R;
+  out->thresholds_per_pass = (int32_t)per;
+  out->passes = (int32_t)passes;
+  out->lds_bytes = (int32_t)mtgpu::sweep_lds_bytes(p.grid_w, R, (int)per, (int)n_vec, (int)ch);
+  out->counter_bits = 32;
+  if (chunk_rows) *chunk_rows = (int)ch;
+  return MT_OK;
+}
+
+int sweep_counts_ok(uint32_t n_thresholds, uint32_t n_vectors) {
+  if (n_thresholds < 1 || n_thresholds > MT_SWEEP_MAX_THRESHOLDS)
+    return fail(MT_ERR_INVALID, "n_thresholds %u outside [1,%d]", n_thresholds, MT_SWEEP_MAX_THRESHOLDS);
+  if (n_vectors < 1 || n_vectors > MT_SWEEP_MAX_VECTORS)
+    return fail(MT_ERR_INVALID, "n_vectors %u outside [1,%d]", n_vectors, MT_SWEEP_MAX_VECTORS);
+  return MT_OK;
+}
+
+// The sweep of a device-resident batch on `st`: plan, launch scratch for the work list, the kernels.  The arguments
+// have been validated.  centres_sys: 1 = the output is not device memory, 0 = device memory, -1 = ask the runtime
+int sweep_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
+             const uint8_t *d_sd, uint32_t n_frames, const double *thresholds, uint32_t n_thr, const int32_t *vectors,
+             uint32_t n_vec, uint32_t *d_centres, hipStream_t st, int centres_sys) {
+  mtgpu_sweep_plan sp;
+  int chunk_rows = 0;
+  int rc = sweep_plan(c->params, c->lds_max, n_thr, n_vec, &sp, &chunk_rows);
+  if (rc != MT_OK) return rc;
+  mtgpu::SweepLaunch L;
+  L.mv = static_cast<const unsigned char *>(d_rec);
+  L.n_records = n_records;
+  L.rebase = rebase;
+  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
+  L.has_sd = d_sd;
+  L.n_frames = n_frames;
+  L.rec_bytes = rec_bytes;
+  L.centres = d_centres;
+  L.n_thr_all = (int)n_thr;
+  L.thr_per_pass = sp.thresholds_per_pass;
+  // ascending, as integers (stable: equal thresholds keep the caller's order; each gets a tile of its own)
+  for (uint32_t i = 0; i < n_thr; ++i) {
+    const unsigned long long t = threshold_to_int(thresholds[i]);
+    uint32_t at = i;
+    while (at > 0 && L.thr_sorted[at - 1] > t) { L.thr_sorted[at] = L.thr_sorted[at - 1]; L.thr_index[at] = L.thr_index[at - 1]; --at; }
+    L.thr_sorted[at] = t;
+    L.thr_index[at] = i;
+  }
+  for (uint32_t i = n_thr; i < (uint32_t)mtgpu::kSweepMaxThr; ++i) { L.thr_sorted[i] = ~0ull; L.thr_index[i] = 0u; }
+  mtgpu::SweepK &k = L.k;
+  std::memset(&k, 0, sizeof k);
+  for (uint32_t v = 0; v < (uint32_t)mtgpu::kSweepMaxVec; ++v)
+    k.vec[v] = v < n_vec ? (unsigned int)(uint8_t)vectors[v] : 0xffffffffu;     // :186, config.hpp:75 — uint8
+  k.n_vec = (int)n_vec;
+  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
+  const int R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
+  k.tile_words = (int)mtgpu::sweep_tile_words(k.gw, R);
+  k.chunk_rows = chunk_rows;
+  k.mask_rows = chunk_rows + 2;
+  k.sys = centres_sys < 0 ? result_memory_is_sys(d_centres) : centres_sys;
+  L.lds_bytes = sp.lds_bytes;
+  L.lds_max = c->lds_max;
+  L.device = c->device;
+  L.stream = st;
+  L.ev_planned = nullptr;
+  void *scratch = nullptr;
+  int slot = -1;
+  rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
+  if (rc != MT_OK) return rc;
+  L.plan_ws = scratch;
+  hipError_t e = hipSuccess;
+  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
+    mtgpu_ctx::Profile &pf = c->prof;
+    std::lock_guard<std::mutex> lock(pf.mu);
+    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
+    if (e == hipSuccess && pf.created) {
+      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
+      e = hipEventRecord(t[0], st);
+      L.ev_planned = t[1];
+      if (e == hipSuccess) e = mtgpu::launch_sweep_scan(L);
+      if (e == hipSuccess) e = hipEventRecord(t[2], st);
+      if (e == hipSuccess) ++pf.count;
+    } else if (e == hipSuccess) {
+      e = mtgpu::launch_sweep_scan(L);
+    }
+  } else {
+    e = mtgpu::launch_sweep_scan(L);
+  }
+  scratch_release(c, slot, st);
+  if (e != hipSuccess) return hip_fail(e, "sweep scan launch");
+  return MT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtgpu_scan_sweep_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, uint32_t n_thresholds, uint32_t n_vectors,
+                             mtgpu_sweep_plan *out) {
+  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
+  int rc = validate_params(p);
+  if (rc != MT_OK) return rc;
+  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
+  if ((rc = sweep_counts_ok(n_thresholds, n_vectors)) != MT_OK) return rc;
+  mtgpu_sweep_plan sp;
+  if ((rc = sweep_plan(*p, lds_bytes_per_workgroup, n_thresholds, n_vectors, &sp, nullptr)) != MT_OK) return rc;
+  *out = sp;
+  return MT_OK;
+}
+
+int mtgpu_scan_sweep_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
+                            const uint8_t *d_has_sd, uint32_t n_frames, const double *thresholds, uint32_t n_thresholds,
+                            const int32_t *vectors, uint32_t n_vectors, uint32_t *d_centres, void *stream) {
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
+    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
+  const int rc = sweep_counts_ok(n_thresholds, n_vectors);
+  if (rc != MT_OK) return rc;
+  if (!thresholds) return fail(MT_ERR_INVALID, "thresholds is NULL");
+  if (!vectors) return fail(MT_ERR_INVALID, "vectors is NULL");
+  if (n_frames == 0) return MT_OK;
+  if (!d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
+  if (!d_centres) return fail(MT_ERR_INVALID, "d_centres is NULL");
+  if (n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
+  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)d_rec & 7u) != 0)
+    return fail(MT_ERR_INVALID, "d_rec: compact records must be 8-byte aligned");
+  if (((uintptr_t)d_rec & 3u) != 0) return fail(MT_ERR_INVALID, "d_rec must be 4-byte aligned");
+  if (((uintptr_t)d_centres & 3u) != 0) return fail(MT_ERR_INVALID, "d_centres must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->check_offsets) {
+    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
+    if (rc2 != MT_OK) return rc2;
+  }
+  return sweep_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, thresholds, n_thresholds, vectors,
+                  n_vectors, d_centres, static_cast<hipStream_t>(stream), -1);
+}
+
+int mtgpu_scan_frames_sweep(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
+                            const double *thresholds, uint32_t n_thresholds, const int32_t *vectors, uint32_t n_vectors,
+                            uint32_t *centres) {
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  int rc = sweep_counts_ok(n_thresholds, n_vectors);
+  if (rc != MT_OK) return rc;
+  if (!thresholds) return fail(MT_ERR_INVALID, "thresholds is NULL");
+  if (!vectors) return fail(MT_ERR_INVALID, "vectors is NULL");
+  if (n_frames == 0) return MT_OK;
+  if (!frame_off || !centres) return fail(MT_ERR_INVALID, "frame_off/centres is NULL");
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
+  const uint64_t r_begin = frame_off[0], r_end = frame_off[n_frames];
+  const uint64_t n_records = r_end - r_begin;
+  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
+  {
+    mtgpu_sweep_plan sp;                                   // a grid without a sweep form: before anything is staged
+    if ((rc = sweep_plan(c->params, c->lds_max, n_thresholds, n_vectors, &sp, nullptr)) != MT_OK) return rc;
+  }
+
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t out_bytes = sizeof(uint32_t) * (size_t)n_thresholds * (size_t)n_vectors * (size_t)n_frames;
+  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
+  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
+  if ((rc = c->d_flags.reserve(out_bytes)) != MT_OK) return rc;
+  if (has_sd && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
+  hipStream_t st = c->stream;
+  DrainOnExit drain{st};
+  if (n_records)
+    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
+  if (has_sd) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
+  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
+  rc = sweep_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
+                has_sd ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames, thresholds, n_thresholds, vectors,
+                n_vectors, static_cast<uint32_t *>(c->d_flags.p), st, 0);
+  if (rc != MT_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(centres, c->d_flags.p, out_bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return MT_OK;
 }

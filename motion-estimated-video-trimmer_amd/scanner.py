@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _abi, config
 from ._abi import (COMPACT_DTYPE, LAYOUT_AOS40, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
-                   MV_DTYPE, SEGMENT_DTYPE, MergeParamsC, MergeResultC, PlanC, ScanParamsC, check,
+                   MV_DTYPE, SEGMENT_DTYPE, MergeParamsC, MergeResultC, PlanC, ScanParamsC, SweepPlanC, check,
                    load_library)
 
 
@@ -181,6 +181,27 @@ def plan_preview(params: "ScanParams", lds_bytes: int = 163840, cu_count: int = 
     c = params.to_c()
     check(load_library().mtgpu_plan_preview(C.byref(c), int(lds_bytes), int(cu_count), C.byref(p)))
     return {n: getattr(p, n) for n, _ in PlanC._fields_ if not n.startswith("_")}
+
+
+def sweep_preview(params: "ScanParams", n_thresholds: int, n_vectors: int, lds_bytes: int = 163840) -> dict:
+    """How a sweep of n_thresholds x n_vectors settings would run on the grid of `params` with that much LDS per
+    workgroup (mtgpu_scan_sweep_preview): tiles per launch, launches (= reads of the records), LDS bytes.  Host
+    arithmetic only: works without a GPU.  MtgpuError(MT_ERR_UNSUPPORTED) for a grid the sweep has no form for."""
+    p = SweepPlanC()
+    c = params.to_c()
+    check(load_library().mtgpu_scan_sweep_preview(C.byref(c), int(lds_bytes), int(n_thresholds), int(n_vectors), C.byref(p)))
+    return {n: getattr(p, n) for n, _ in SweepPlanC._fields_}
+
+
+def _sweep_settings(thresholds, vectors):
+    """The two HOST arrays of a sweep call as ctypes arrays (at least one element each, so that a count of 0 still
+    reaches the library's own check)."""
+    th = [float(t) for t in thresholds]
+    ve = [int(v) for v in vectors]
+    for v in ve:
+        if not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError(f"vector level {v} does not fit int32")
+    return (C.c_double * max(len(th), 1))(*th), len(th), (C.c_int32 * max(len(ve), 1))(*ve), len(ve)
 
 
 def pack_records(mv: np.ndarray) -> np.ndarray:
@@ -403,6 +424,44 @@ class MotionScanner:
         self._held = [(e, w) for e, w in getattr(self, "_held", []) if not e.query()]
         self._held.append((ev, ws))
         return seg, res
+
+    # ------------------------------------------------------- setting sweep
+    def sweep_centres(self, batch: FrameBatch, thresholds, vectors) -> np.ndarray:
+        """The centre counts of every frame of a host batch for every (MV_THRESHOLD_SQ, VECTORS_NEEDED) pair, from
+        one read of the records per pass (mtgpu_scan_frames_sweep): uint32 [T, V, F], in the caller's order.
+        out[t, v] is what count_centres returns through a scanner created with thresholds[t] and vectors[v];
+        the scanner's own threshold, vectors and clusters play no part."""
+        c_th, n_th, c_ve, n_ve = _sweep_settings(thresholds, vectors)
+        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
+        n = max(len(off) - 1, 0)
+        out = np.zeros((n_th, n_ve, n), dtype=np.uint32)
+        check(self._lib.mtgpu_scan_frames_sweep(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, c_th, n_th,
+                                                c_ve, n_ve, _ptr(out) if out.size else None))
+        return out
+
+    def sweep_centres_device(self, records, frame_off, has_sd, thresholds, vectors, compact=False, out=None, stream=None):
+        """Device-resident batch (torch CUDA tensors) -> int32 [T, V, F] CUDA tensor (the bits of the library's uint32
+        counts): out[t, v] is the centres tensor of count_centres_device through a scanner created with
+        thresholds[t] and vectors[v], ready for flags_from_centres / sweep_streams_device.  records: the packed
+        40-byte records, or the 8-byte compact ones with compact=True.  Asynchronous on `stream` (default: torch's
+        current stream)."""
+        import torch
+        c_th, n_th, c_ve, n_ve = _sweep_settings(thresholds, vectors)
+        n_frames = max(frame_off.numel() - 1, 0)
+        dev = frame_off.device
+        if out is None:
+            out = torch.empty((n_th, n_ve, n_frames), dtype=torch.int32, device=dev)
+        assert records.is_contiguous() and frame_off.is_contiguous() and out.is_contiguous()
+        assert frame_off.dtype == torch.int64 and out.dtype == torch.int32 and out.numel() >= n_th * n_ve * n_frames
+        rec_bytes = 8 if compact else 40
+        n_records = (records.numel() * records.element_size()) // rec_bytes
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(self._lib.mtgpu_scan_sweep_device(
+            self._ctx, records.data_ptr() if n_records else None, rec_bytes, n_records, frame_off.data_ptr(),
+            None if has_sd is None else has_sd.data_ptr(), n_frames, c_th, n_th, c_ve, n_ve, out.data_ptr(), st))
+        return out
 
     # ------------------------------------------------------- motion scalar
     def motion_scores(self, batch: FrameBatch) -> Tuple[np.ndarray, np.ndarray]:
