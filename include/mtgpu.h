@@ -446,4 +446,8 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * points, declared the same way. */
 #include "mtgpu_sweep.h"
 
+/* Per-stream activity maps: per grid cell, the frames in which it was active and a centre (src/motion_scanner.cpp:
+ * 242-292) — three more entry points, declared the same way. */
+#include "mtgpu_activity.h"
+
 #endif /* MTGPU_H */

@@ -69,6 +69,10 @@ class SweepPlanC(C.Structure):
                 ("counter_bits", C.c_int32)]
 
 
+class ActivityPlanC(C.Structure):
+    _fields_ = [("lds_bytes", C.c_int32), ("acc_bits", C.c_int32), ("max_run", C.c_int32), ("workgroup", C.c_int32)]
+
+
 class CtxStatsC(C.Structure):
     _fields_ = [("staging_device_bytes", C.c_uint64), ("pool_reserved_bytes", C.c_uint64),
                 ("pool_reserved_high", C.c_uint64), ("hip_streams", C.c_uint32), ("private_pool", C.c_uint32)]
@@ -163,6 +167,16 @@ ABI_SWEEP = {
                                           C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_activity.h declares (the activity maps; mtgpu.h includes it).
+ABI_ACTIVITY = {
+    "mtgpu_activity_preview": (C.c_int, [C.POINTER(ScanParamsC), C.c_int, C.POINTER(ActivityPlanC)]),
+    "mtgpu_activity_map_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "mtgpu_activity_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -192,7 +206,8 @@ def load_library(path=None):
             f"{p} not found: build it with `make -C {os.path.join(PKG_DIR, 'csrc')}` "
             "(or __graft_entry__.build()).  There is no fallback path.")
     lib = C.CDLL(p)
-    for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()):
+    for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
+            list(ABI_ACTIVITY.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -23,6 +23,7 @@
 #include "scalar_kernels.h"
 #include "scan_kernels.h"
 #include "sweep_kernels.h"
+#include "activity_kernels.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -1517,6 +1518,230 @@ int mtgpu_scan_frames_sweep(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame
                 n_vectors, static_cast<uint32_t *>(c->d_flags.p), st, 0);
   if (rc != MT_OK) return rc;
   HIP_TRY(hipMemcpyAsync(centres, c->d_flags.p, out_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- activity maps (src/motion_scanner.cpp:242-292 per frame,
+// summed per stream and grid cell; include/mtgpu_activity.h)
+
+namespace {
+
+// Which form a grid gets with this much LDS: the tile, the frame's two mask planes, and two accumulator planes where
+// they fit.  A workgroup has 1024 lanes, so at most two are resident per CU: accumulators that leave room for two
+// workgroups are preferred over wider ones that do not (1080p: 16-bit fields, 61 KB, two per CU; 32-bit fields
+// would take 90 KB and leave one).  Without room for 16-bit fields there are none and every frame flushes (4K).
+int activity_plan(const mt_scan_params &p, int lds_max, mtgpu_activity_plan *out) {
+  const int y_lo = p.vertical_margin;
+  int y_hi = p.grid_h - p.vertical_margin;
+  if (y_hi < y_lo) y_hi = y_lo;
+  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const long long none = (long long)mtgpu::act_lds_bytes(p.grid_w, R, 0);
+  const long long b16 = (long long)mtgpu::act_lds_bytes(p.grid_w, R, 16), b32 = (long long)mtgpu::act_lds_bytes(p.grid_w, R, 32);
+  if (none > (long long)lds_max)
+    return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows and the frame's mask planes (%lld bytes) "
+                "do not fit %d bytes of LDS; the activity map has no banded form", p.grid_w, p.grid_h, R + 2, none, lds_max);
+  int bits = 0;
+  if (2 * b32 <= (long long)lds_max) bits = 32;
+  else if (2 * b16 <= (long long)lds_max) bits = 16;
+  else if (b32 <= (long long)lds_max) bits = 32;
+  else if (b16 <= (long long)lds_max) bits = 16;
+  out->lds_bytes = (int32_t)(bits == 32 ? b32 : bits == 16 ? b16 : none);
+  out->acc_bits = bits;
+  out->max_run = bits == 32 ? 0x7fffffff : bits == 16 ? 65535 : 1;
+  out->workgroup = mtgpu::kActBlock;
+  return MT_OK;
+}
+
+// Is p memory of the context's device (the flush uses global atomics)?
+bool on_ctx_device(const mtgpu_ctx *c, const void *p) {
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof at);
+  const hipError_t qe = hipPointerGetAttributes(&at, p);
+  if (qe != hipSuccess) { (void)hipGetLastError(); return false; }
+  return at.type == hipMemoryTypeDevice && at.device == c->device;
+}
+
+// The map of a device-resident batch on `st`.  The arguments have been validated.
+int activity_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
+                const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, uint32_t min_centres,
+                uint32_t run_frames, uint32_t *d_active, uint32_t *d_centre, uint32_t *d_frames, hipStream_t st) {
+  mtgpu_activity_plan ap;
+  int rc = activity_plan(c->params, c->lds_max, &ap);
+  if (rc != MT_OK) return rc;
+  mtgpu::ActLaunch L;
+  L.mv = static_cast<const unsigned char *>(d_rec);
+  L.n_records = n_records;
+  L.rebase = rebase;
+  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
+  L.has_sd = d_sd;
+  L.n_frames = n_frames;
+  L.rec_bytes = rec_bytes;
+  L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
+  L.n_streams = n_streams;
+  L.active = d_active; L.centre = d_centre; L.frames = d_frames;
+  mtgpu::ActK &k = L.k;
+  std::memset(&k, 0, sizeof k);
+  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.min_centres = min_centres;
+  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
+  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
+  k.tile_words = (int)mtgpu::act_tile_words(k.gw, k.R);
+  k.gwp = mtgpu::act_gwp(k.gw);
+  k.max_run = ap.max_run;
+  {
+    // the planner's run: about four rounds of workgroups on a chip that holds two per CU, at most 64 frames
+    const uint64_t slots = 2u * (uint64_t)(c->plan.cu_count > 0 ? c->plan.cu_count : 256);
+    uint64_t run = run_frames ? run_frames : (uint64_t)n_frames / (4u * slots);
+    if (!run_frames && run > 64u) run = 64u;
+    if (run < 1u) run = 1u;
+    if (run > (uint64_t)ap.max_run) run = (uint64_t)ap.max_run;
+    k.run = (int)run;
+  }
+  L.acc_bits = ap.acc_bits;
+  L.lds_bytes = ap.lds_bytes;
+  L.lds_max = c->lds_max;
+  L.device = c->device;
+  L.stream = st;
+  L.ev_planned = nullptr;
+  L.plan_ws = nullptr;
+  hipError_t e = hipSuccess;
+  if (n_frames == 0 || n_streams == 0) {                       // only the clear
+    e = mtgpu::launch_activity_map(L);
+    if (e != hipSuccess) return hip_fail(e, "activity map launch");
+    return MT_OK;
+  }
+  void *scratch = nullptr;
+  int slot = -1;
+  rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
+  if (rc != MT_OK) return rc;
+  L.plan_ws = scratch;
+  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
+    mtgpu_ctx::Profile &pf = c->prof;
+    std::lock_guard<std::mutex> lock(pf.mu);
+    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
+    if (e == hipSuccess && pf.created) {
+      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
+      e = hipEventRecord(t[0], st);
+      L.ev_planned = t[1];
+      if (e == hipSuccess) e = mtgpu::launch_activity_map(L);
+      if (e == hipSuccess) e = hipEventRecord(t[2], st);
+      if (e == hipSuccess) ++pf.count;
+    } else if (e == hipSuccess) {
+      e = mtgpu::launch_activity_map(L);
+    }
+  } else {
+    e = mtgpu::launch_activity_map(L);
+  }
+  scratch_release(c, slot, st);
+  if (e != hipSuccess) return hip_fail(e, "activity map launch");
+  return MT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtgpu_activity_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_activity_plan *out) {
+  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
+  int rc = validate_params(p);
+  if (rc != MT_OK) return rc;
+  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
+  mtgpu_activity_plan ap;
+  if ((rc = activity_plan(*p, lds_bytes_per_workgroup, &ap)) != MT_OK) return rc;
+  *out = ap;
+  return MT_OK;
+}
+
+int mtgpu_activity_map_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
+                              const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
+                              uint32_t min_centres, uint32_t run_frames, uint32_t *d_active, uint32_t *d_centre,
+                              uint32_t *d_frames, void *stream) {
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
+    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
+  if (!d_active && !d_centre && !d_frames) return fail(MT_ERR_INVALID, "d_active, d_centre and d_frames are all NULL");
+  if (n_frames > 0 && !d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
+  if (n_frames > 0 && n_streams > 0 && !d_stream_off) return fail(MT_ERR_INVALID, "d_stream_off is NULL");
+  if (((uintptr_t)d_frame_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_frame_off must be 8-byte aligned");
+  if (((uintptr_t)d_stream_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_stream_off must be 8-byte aligned");
+  if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
+  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)d_rec & 7u) != 0)
+    return fail(MT_ERR_INVALID, "d_rec: compact records must be 8-byte aligned");
+  if (((uintptr_t)d_rec & 3u) != 0) return fail(MT_ERR_INVALID, "d_rec must be 4-byte aligned");
+  if (((uintptr_t)d_active & 3u) != 0) return fail(MT_ERR_INVALID, "d_active must be 4-byte aligned");
+  if (((uintptr_t)d_centre & 3u) != 0) return fail(MT_ERR_INVALID, "d_centre must be 4-byte aligned");
+  if (((uintptr_t)d_frames & 3u) != 0) return fail(MT_ERR_INVALID, "d_frames must be 4-byte aligned");
+  {
+    mtgpu_activity_plan ap;                                  // a grid without a form: before any HIP call
+    const int rc = activity_plan(c->params, c->lds_max, &ap);
+    if (rc != MT_OK) return rc;
+  }
+  if (n_streams == 0) return MT_OK;                          // no stream owns an output element
+  HIP_TRY(hipSetDevice(c->device));
+  if (d_active && !on_ctx_device(c, d_active)) return fail(MT_ERR_INVALID, "d_active is not memory of device %d (global atomics)", c->device);
+  if (d_centre && !on_ctx_device(c, d_centre)) return fail(MT_ERR_INVALID, "d_centre is not memory of device %d (global atomics)", c->device);
+  if (d_frames && !on_ctx_device(c, d_frames)) return fail(MT_ERR_INVALID, "d_frames is not memory of device %d (global atomics)", c->device);
+  if (c->check_offsets && n_frames > 0) {
+    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
+    if (rc2 != MT_OK) return rc2;
+  }
+  return activity_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, min_centres,
+                     run_frames, d_active, d_centre, d_frames, static_cast<hipStream_t>(stream));
+}
+
+int mtgpu_activity_map(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
+                       const uint64_t *stream_off, uint32_t n_streams, uint32_t min_centres, uint32_t *active, uint32_t *centre,
+                       uint32_t *frames) {
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  if (!active && !centre && !frames) return fail(MT_ERR_INVALID, "active, centre and frames are all NULL");
+  if (!stream_off) return fail(MT_ERR_INVALID, "stream_off is NULL");
+  if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
+  for (uint32_t s = 0; s < n_streams; ++s)
+    if (stream_off[s + 1] < stream_off[s]) return fail(MT_ERR_INVALID, "stream_off not monotonic at stream %u", s);
+  if (stream_off[n_streams] != (uint64_t)n_frames)
+    return fail(MT_ERR_INVALID, "stream_off[%u] is %llu, not n_frames %u", n_streams, (unsigned long long)stream_off[n_streams], n_frames);
+  const uint64_t r_begin = n_frames ? frame_off[0] : 0, r_end = n_frames ? frame_off[n_frames] : 0;
+  const uint64_t n_records = r_end - r_begin;
+  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
+  int rc;
+  {
+    mtgpu_activity_plan ap;                                  // a grid without a form: before anything is staged
+    if ((rc = activity_plan(c->params, c->lds_max, &ap)) != MT_OK) return rc;
+  }
+  if (n_streams == 0) return MT_OK;
+
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t plane = sizeof(uint32_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.gw;
+  const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
+  const size_t o_soff = 0, o_act = o_soff + up(sizeof(uint64_t) * ((size_t)n_streams + 1)), o_cen = o_act + (active ? up(plane) : 0),
+               o_fr = o_cen + (centre ? up(plane) : 0), total = o_fr + up(sizeof(uint32_t) * (size_t)n_streams);
+  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
+  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
+  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
+  if (has_sd && n_frames && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
+  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
+  hipStream_t st = c->stream;
+  DrainOnExit drain{st};
+  if (n_records)
+    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
+  if (n_frames) HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
+  if (has_sd && n_frames) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d + o_soff, stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1), hipMemcpyHostToDevice, st));
+  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
+  rc = activity_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
+                   (has_sd && n_frames) ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames,
+                   reinterpret_cast<const uint64_t *>(d + o_soff), n_streams, min_centres, 0,
+                   active ? reinterpret_cast<uint32_t *>(d + o_act) : nullptr, centre ? reinterpret_cast<uint32_t *>(d + o_cen) : nullptr,
+                   frames ? reinterpret_cast<uint32_t *>(d + o_fr) : nullptr, st);
+  if (rc != MT_OK) return rc;
+  if (active) HIP_TRY(hipMemcpyAsync(active, d + o_act, plane, hipMemcpyDeviceToHost, st));
+  if (centre) HIP_TRY(hipMemcpyAsync(centre, d + o_cen, plane, hipMemcpyDeviceToHost, st));
+  if (frames) HIP_TRY(hipMemcpyAsync(frames, d + o_fr, sizeof(uint32_t) * (size_t)n_streams, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return MT_OK;
 }

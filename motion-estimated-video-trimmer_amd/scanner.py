@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _abi, config
 from ._abi import (COMPACT_DTYPE, LAYOUT_AOS40, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
-                   MV_DTYPE, SEGMENT_DTYPE, MergeParamsC, MergeResultC, PlanC, ScanParamsC, SweepPlanC, check,
+                   MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PlanC, ScanParamsC, SweepPlanC, check,
                    load_library)
 
 
@@ -191,6 +191,28 @@ def sweep_preview(params: "ScanParams", n_thresholds: int, n_vectors: int, lds_b
     c = params.to_c()
     check(load_library().mtgpu_scan_sweep_preview(C.byref(c), int(lds_bytes), int(n_thresholds), int(n_vectors), C.byref(p)))
     return {n: getattr(p, n) for n, _ in SweepPlanC._fields_}
+
+
+def activity_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
+    """The form the activity map takes on the grid of `params` with that much LDS per workgroup
+    (mtgpu_activity_preview): LDS bytes, width of the LDS accumulators (32, 16, or 0 = every frame flushes), the most
+    frames a workgroup accumulates before it flushes, lanes.  Host arithmetic only: works without a GPU.
+    MtgpuError(MT_ERR_UNSUPPORTED) for a grid the map has no form for."""
+    p = ActivityPlanC()
+    c = params.to_c()
+    check(load_library().mtgpu_activity_preview(C.byref(c), int(lds_bytes), C.byref(p)))
+    return {n: getattr(p, n) for n, _ in ActivityPlanC._fields_}
+
+
+ACTIVITY_OUTPUTS = ("active", "centre", "frames")
+
+
+def _activity_want(want):
+    want = tuple(want)
+    for w in want:
+        if w not in ACTIVITY_OUTPUTS:
+            raise ValueError(f"want: {w!r} is not one of {ACTIVITY_OUTPUTS}")
+    return want
 
 
 def _sweep_settings(thresholds, vectors):
@@ -462,6 +484,65 @@ class MotionScanner:
             self._ctx, records.data_ptr() if n_records else None, rec_bytes, n_records, frame_off.data_ptr(),
             None if has_sd is None else has_sd.data_ptr(), n_frames, c_th, n_th, c_ve, n_ve, out.data_ptr(), st))
         return out
+
+    # ------------------------------------------------------- activity maps
+    def activity_map(self, batch: FrameBatch, stream_off, min_centres: int = 0, want=ACTIVITY_OUTPUTS):
+        """Per-stream activity maps of a host batch (mtgpu_activity_map): (active uint32 [S, gh, gw], centre uint32
+        [S, gh, gw], frames uint32 [S]) — per grid cell, the contributing frames of stream s in which the cell was
+        active / one of the centres src/motion_scanner.cpp:277-292 counts; frames[s]: the contributing frames.  A
+        frame contributes iff it has side data and its centre count is >= min_centres.  stream_off: S + 1 frame
+        offsets.  An output left out of `want` is not computed and comes back as None."""
+        want = _activity_want(want)
+        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
+        soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
+        n, ns = max(len(off) - 1, 0), max(len(soff) - 1, 0)
+        gh, gw = self.params.grid_h, self.params.grid_w
+        active = np.zeros((ns, gh, gw), dtype=np.uint32) if "active" in want else None
+        centre = np.zeros((ns, gh, gw), dtype=np.uint32) if "centre" in want else None
+        frames = np.zeros(ns, dtype=np.uint32) if "frames" in want else None
+        check(self._lib.mtgpu_activity_map(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n,
+                                           _ptr(soff) if len(soff) else None, ns, int(min_centres), _ptr(active),
+                                           _ptr(centre), _ptr(frames)))
+        return active, centre, frames
+
+    def activity_map_device(self, d_rec, d_off, d_sd, d_stream_off, min_centres: int = 0, run_frames: int = 0,
+                            want=ACTIVITY_OUTPUTS, compact=False, out=None, stream=None):
+        """Device-resident batch (torch CUDA tensors) -> (active int32 [S, gh, gw], centre int32 [S, gh, gw], frames
+        int32 [S]) CUDA tensors (the bits of the library's uint32 counts; None for an output not in `want`).  d_rec:
+        the packed 40-byte records, or the 8-byte compact ones with compact=True; d_off int64 [F + 1]; d_sd uint8 [F]
+        or None; d_stream_off int64 [S + 1].  run_frames: work-list entries per workgroup, 0 = the planner chooses;
+        the maps do not depend on it.  out: a dict of preallocated tensors by name.  Asynchronous on `stream`
+        (default: torch's current stream)."""
+        import torch
+        want = _activity_want(want)
+        dev = d_off.device
+        n_frames = max(d_off.numel() - 1, 0)
+        ns = max(d_stream_off.numel() - 1, 0)
+        gh, gw = self.params.grid_h, self.params.grid_w
+        res = {}
+        for name in ACTIVITY_OUTPUTS:
+            if name not in want:
+                res[name] = None
+                continue
+            shape = (ns,) if name == "frames" else (ns, gh, gw)
+            t = (out or {}).get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=torch.int32, device=dev)
+            assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape, name
+            res[name] = t
+        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_stream_off.is_contiguous()
+        assert d_off.dtype == torch.int64 and d_stream_off.dtype == torch.int64
+        rec_bytes = 8 if compact else 40
+        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+        check(self._lib.mtgpu_activity_map_device(
+            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
+            None if d_sd is None else d_sd.data_ptr(), n_frames, d_stream_off.data_ptr(), ns, int(min_centres),
+            int(run_frames), ptr(res["active"]), ptr(res["centre"]), ptr(res["frames"]), st))
+        return res["active"], res["centre"], res["frames"]
 
     # ------------------------------------------------------- motion scalar
     def motion_scores(self, batch: FrameBatch) -> Tuple[np.ndarray, np.ndarray]:
