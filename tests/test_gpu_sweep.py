@@ -117,7 +117,7 @@ def test_profiled_sweep_records_one_triple_per_call(gpu_scanner_factory):
 
 def test_callers_order_duplicates_specials_two_passes(gpu_scanner_factory):
     """Thresholds [nan, 24.5, 25.0, inf, -1.0, 25.0] (NaN and <= 0 keep everything, +inf nothing, 24.5 == 25.0 on integer
-    |d|^2; six tiles: a second pass on 1080p, where four fit) x vectors [0, 1, 255, 259] (0: every cell active, 259 wraps
+    |d|^2; six tiles: two passes of three on 1080p, where five fit) x vectors [0, 1, 255, 259] (0: every cell active, 259 wraps
     to 3), 24 random frames and one frame with side data but no records (level 0 counts on its empty grid)."""
     thr = [float("nan"), 24.5, 25.0, float("inf"), -1.0, 25.0]
     vec = [0, 1, 255, 259]
