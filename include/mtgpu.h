@@ -450,4 +450,8 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * 242-292) — three more entry points, declared the same way. */
 #include "mtgpu_activity.h"
 
+/* Ignore zones: the centre scan with a per-stream keep mask over the grid cells (src/motion_scanner.cpp:237-238, 262,
+ * 277-292) — three more entry points, declared the same way. */
+#include "mtgpu_zones.h"
+
 #endif /* MTGPU_H */

@@ -73,6 +73,11 @@ class ActivityPlanC(C.Structure):
     _fields_ = [("lds_bytes", C.c_int32), ("acc_bits", C.c_int32), ("max_run", C.c_int32), ("workgroup", C.c_int32)]
 
 
+class ZonesPlanC(C.Structure):
+    _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("keep_words_per_row", C.c_int32),
+                ("keep_words_per_stream", C.c_int32)]
+
+
 class CtxStatsC(C.Structure):
     _fields_ = [("staging_device_bytes", C.c_uint64), ("pool_reserved_bytes", C.c_uint64),
                 ("pool_reserved_high", C.c_uint64), ("hip_streams", C.c_uint32), ("private_pool", C.c_uint32)]
@@ -177,6 +182,15 @@ ABI_ACTIVITY = {
                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_zones.h declares (the ignore zones; mtgpu.h includes it).
+ABI_ZONES = {
+    "mtgpu_zones_preview": (C.c_int, [C.POINTER(ScanParamsC), C.c_int, C.POINTER(ZonesPlanC)]),
+    "mtgpu_scan_zones_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtgpu_scan_frames_zones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -207,7 +221,7 @@ def load_library(path=None):
             "(or __graft_entry__.build()).  There is no fallback path.")
     lib = C.CDLL(p)
     for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
-            list(ABI_ACTIVITY.items()):
+            list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,66 @@
+// zones_kernels.h — launch interface between the C ABI (mtgpu_api.hip) and the gfx950 ignore-zone kernel
+// (zones_kernels.hip): the centre counts of src/motion_scanner.cpp:272-294 with a per-stream keep mask ANDed into
+// the active cells of the analysed rows (:282).  Internal; not part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "scan_kernels.h"
+
+namespace mtgpu {
+
+constexpr int kZoneBlock = 1024;    // lanes per workgroup
+constexpr int kZoneUnroll = 4;      // independent record loads in flight per lane
+
+// LDS of one workgroup, in this order (R = analysed rows, at least 1; W = 64-bit words per mask row):
+//   tile     (R + 2) x gw u32, padded to 4 words   vote counters: the analysed rows and one halo row each side
+//   keep     R x W u64                             the stream's keep words of the analysed rows; row r <-> grid row y_lo + r
+//   kmask    (R + 2) x W u64                       the frame's active cells AND keep; mask row j <-> grid row y_lo - 1 + j
+//   umask    (R + 2) x W u64                       the frame's active cells without the mask (written only for centres_all)
+//   total    4 u32                                 [0]: the masked centre count, [1]: the unmasked one
+inline size_t zone_tile_words(int gw, int R) {
+  const size_t w = (size_t)(R + 2) * (size_t)gw;
+  return (w + 3u) & ~(size_t)3u;
+}
+inline size_t zone_lds_bytes(int gw, int R) {
+  const size_t W = ((size_t)gw + 63u) / 64u;
+  return zone_tile_words(gw, R) * 4u + (size_t)(3 * R + 4) * W * 8u + 16u;
+}
+
+// Kernel-side parameter block.
+struct ZoneK {
+  unsigned long long thr;        // keep a record iff |d|^2 >= thr (ScanK::thr, :251)
+  unsigned int vec_need;         // a cell is active iff votes >= vec_need (:282) and, on an analysed row, its keep bit is set
+  unsigned int clust_need;       // flags[f] = centres[f] >= clust_need = max(1, clusters_needed) (:288)
+  int shift, gw, gh, y_lo, y_hi; // as ScanK (y_hi >= y_lo)
+  int W;                         // 64-bit words per mask row
+  int R;                         // max(1, y_hi - y_lo): rows the LDS layout is sized for
+  int tile_words;                // zone_tile_words
+};
+
+struct ZoneLaunch {
+  const unsigned char *mv;
+  unsigned long long n_records;           // frame_off entries are clamped to this (before `rebase`)
+  unsigned long long rebase;
+  const unsigned long long *frame_off;    // n_frames + 1
+  const unsigned char *has_sd;            // n_frames or null
+  unsigned int n_frames;
+  int rec_bytes;                          // 40 or 8
+  const unsigned long long *stream_off;   // n_streams + 1
+  unsigned int n_streams;
+  const unsigned long long *keep;         // n_streams x gh x W
+  unsigned char *flags;                   // n_frames bytes, device memory, or null
+  unsigned int *centres, *centres_all;    // n_frames words each, device memory, or null
+  ZoneK k;
+  int lds_bytes;
+  int lds_max;                            // device limit of dynamic LDS per workgroup
+  int device;
+  void *plan_ws;                          // plan_scratch_bytes(n_frames), 32-byte aligned
+  hipStream_t stream;
+  hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the zone kernel; else nullptr
+};
+
+// Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.
+hipError_t launch_zone_scan(const ZoneLaunch &L);
+
+}  // namespace mtgpu

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _abi, config
 from ._abi import (COMPACT_DTYPE, LAYOUT_AOS40, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
-                   MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PlanC, ScanParamsC, SweepPlanC, check,
+                   MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PlanC, ScanParamsC, SweepPlanC, ZonesPlanC, check,
                    load_library)
 
 
@@ -202,6 +202,16 @@ def activity_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     c = params.to_c()
     check(load_library().mtgpu_activity_preview(C.byref(c), int(lds_bytes), C.byref(p)))
     return {n: getattr(p, n) for n, _ in ActivityPlanC._fields_}
+
+
+def zones_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
+    """How the masked scan runs on the grid of `params` with that much LDS per workgroup (mtgpu_zones_preview): LDS
+    bytes, lanes, and the sizes of a keep mask: uint64 words per grid row and per stream.  Host arithmetic only: works
+    without a GPU.  MtgpuError(MT_ERR_UNSUPPORTED) for a grid the masked scan has no form for."""
+    p = ZonesPlanC()
+    c = params.to_c()
+    check(load_library().mtgpu_zones_preview(C.byref(c), int(lds_bytes), C.byref(p)))
+    return {n: getattr(p, n) for n, _ in ZonesPlanC._fields_}
 
 
 ACTIVITY_OUTPUTS = ("active", "centre", "frames")
@@ -543,6 +553,77 @@ class MotionScanner:
             None if d_sd is None else d_sd.data_ptr(), n_frames, d_stream_off.data_ptr(), ns, int(min_centres),
             int(run_frames), ptr(res["active"]), ptr(res["centre"]), ptr(res["frames"]), st))
         return res["active"], res["centre"], res["frames"]
+
+    # -------------------------------------------------------- ignore zones
+    def _keep_words(self, keep, n_streams):
+        """uint64 [S, gh, W] from a packed mask (zones.pack_keep), one per stream or one for all of them."""
+        gh, W = self.params.grid_h, (self.params.grid_w + 63) // 64
+        keep = np.ascontiguousarray(keep, dtype=np.uint64)
+        if keep.shape == (gh, W):
+            keep = np.ascontiguousarray(np.broadcast_to(keep, (n_streams, gh, W)))
+        if keep.shape != (n_streams, gh, W):
+            raise ValueError(f"keep has shape {keep.shape}, not {(n_streams, gh, W)} (or {(gh, W)} for every stream)")
+        return keep
+
+    def scan_zones(self, batch: FrameBatch, stream_off, keep, want_all: bool = False):
+        """The centre scan of a host batch under per-stream keep masks (mtgpu_scan_frames_zones): on the analysed rows
+        a cell is active iff votes >= vectors_needed (src/motion_scanner.cpp:282) AND its keep bit is set.  stream_off:
+        S + 1 frame offsets; keep: uint64 [S, gh, W] from zones.pack_keep (or [gh, W]: the same mask for every stream).
+        Returns (flags uint8 [F], centres uint32 [F], centres_all): centres_all is the count without the mask from the
+        same votes (uint32 [F]) with want_all=True, else None."""
+        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
+        soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
+        n, ns = max(len(off) - 1, 0), max(len(soff) - 1, 0)
+        keep = self._keep_words(keep, ns)
+        flags = np.zeros(n, dtype=np.uint8)
+        centres = np.zeros(n, dtype=np.uint32)
+        call = np.zeros(n, dtype=np.uint32) if want_all else None
+        check(self._lib.mtgpu_scan_frames_zones(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n,
+                                                _ptr(soff) if len(soff) else None, ns, _ptr(keep) if keep.size else None,
+                                                _ptr(flags), _ptr(centres), _ptr(call)))
+        return flags, centres, call
+
+    def scan_zones_device(self, d_rec, d_off, d_sd, d_stream_off, d_keep, compact=False, flags=None, centres=None,
+                          centres_all=None, stream=None):
+        """Device-resident batch (torch CUDA tensors) -> (flags uint8 [F], centres int32 [F], centres_all int32 [F]), the
+        bits of the library's uint32 counts.  d_rec: the packed 40-byte records, or the 8-byte compact ones with
+        compact=True; d_off int64 [F + 1]; d_sd uint8 [F] or None; d_stream_off int64 [S + 1]; d_keep int64 [S, gh, W]
+        (the bits of zones.pack_keep's uint64 words).  flags / centres: None = allocated, False = not computed, or a
+        tensor to fill; centres_all: None or False = not computed, True = allocated, or a tensor to fill.
+        Asynchronous on `stream` (default: torch's current stream)."""
+        import torch
+        dev = d_off.device
+        n_frames = max(d_off.numel() - 1, 0)
+        ns = max(d_stream_off.numel() - 1, 0)
+        if flags is None:
+            flags = torch.empty(n_frames, dtype=torch.uint8, device=dev)
+        elif flags is False:
+            flags = None
+        if centres is None:
+            centres = torch.empty(n_frames, dtype=torch.int32, device=dev)
+        elif centres is False:
+            centres = None
+        if centres_all is True:
+            centres_all = torch.empty(n_frames, dtype=torch.int32, device=dev)
+        elif centres_all is False:
+            centres_all = None
+        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_stream_off.is_contiguous() and d_keep.is_contiguous()
+        assert d_off.dtype == torch.int64 and d_stream_off.dtype == torch.int64 and d_keep.dtype == torch.int64
+        assert d_keep.numel() == ns * self.params.grid_h * ((self.params.grid_w + 63) // 64)
+        assert flags is None or (flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() >= n_frames)
+        for t in (centres, centres_all):
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n_frames)
+        rec_bytes = 8 if compact else 40
+        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+        check(self._lib.mtgpu_scan_zones_device(
+            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
+            None if d_sd is None else d_sd.data_ptr(), n_frames, d_stream_off.data_ptr(), ns, d_keep.data_ptr(),
+            ptr(flags), ptr(centres), ptr(centres_all), st))
+        return flags, centres, centres_all
 
     # ------------------------------------------------------- motion scalar
     def motion_scores(self, batch: FrameBatch) -> Tuple[np.ndarray, np.ndarray]:
