@@ -1,0 +1,392 @@
+"""Inputs of tests/test_gpu_derived_cliff.py: the grids on which the sweep, the activity map and the masked scan fill
+their LDS to the last row or column, found with the previews (host arithmetic, no GPU), and a small batch for each with
+the values derived BY HAND from its construction.  tests/test_derived_cliff_host.py proves without a GPU that every shape
+sits on the limit, that the batches carry centres and that two independent expected-value sources agree on them.
+
+Every shape has vertical_mask 0 (R = grid_h) and block_shift 1, which keeps every pixel coordinate inside int16 — but for
+the sweep's two-column grids: 20 000 rows of two-pixel cells reach past 32 767, so those two use block_shift 0, where a
+pixel coordinate is the cell index itself.  Nothing below is a literal size; bisection over the previews at import time
+(under functools.lru_cache) finds, at 163 840 bytes of LDS per workgroup:
+
+    kernel        gw=2   gw=3   gw=65  gw=193  | gh=1    gh=3    (largest gh / largest gw; one more is MT_ERR_UNSUPPORTED)
+    zones         5118   4548   530    186     | 12722   7572
+    activity      6824   5849   559    194     | 13105   7800
+    sweep 1 x 1   20442  13627  626    209     | 13217   8028
+    sweep 8 x 8   20422  13614  625    208     | 10896   7104
+
+    activity at gw = 120 (every plan outcome is reachable there; the rows are the largest gh of the outcome and, as the
+    row after it, the smallest gh that no longer has it — both are shapes):
+    32-bit two per CU 54 | 16-bit two per CU 81 | 32-bit alone 110 | 16-bit alone 164 | no accumulators 318 | 319: none
+
+(A record of what the bisection found when this was written; no code reads it.)  gw = 3 is not asked for by
+anything but the rule for centres: a column in [1, gw - 2] exists from gw = 3 on, so the two-column grids — five keep
+words per lane in the masked scan — can hold active cells and no centre; the three-column ones can hold both.
+
+The batch of a shape (12 frames) is made of
+    E   pairs of neighbouring cells in the four corners, on the first and last row, in the first and last column and
+        across the row where the masked scan's keep staging starts its second trip (word 1024)
+    H   horizontal pairs across the grid's 64-cell word seams — the first, a middle and the last one on wide grids
+        (three and four columns: the right corners, which touch the left corners' pairs of E)
+    VL  vertical pairs in the column left of those seams,  VR  in the column right of them
+    B.  30 blobs of zones_inputs.clustered_frame, anywhere in the grid
+    N   a blob frame without side data,  Z  a frame with side data and no record
+with junk in the padding bytes of the 40-byte records.
+
+Hand values.  Every pair of a planted frame (E, H, VL, VR) is ISOLATED: no cell of it equals or touches (4-neighbourhood)
+a cell of another pair of that frame — plant() refuses a pair that would.  Both cells of pair i get k = 2 + i % 3 votes of
+|d|^2 = 25 (i even) or 9 (i odd).  So under a threshold T and a level V >= 1
+    a pair is active iff k >= V and |d|^2 >= T, each of its cells then has exactly one active neighbour, the other one,
+    and it adds one centre per cell whose column lies in [1, gw - 2]  (vertical_mask 0: every row is analysed);
+    with one cell ignored by a keep mask the other cell has no active neighbour left: the pair adds 0;
+    at level 0 every cell of the grid is active, whatever the records: gh * (gw - 2) centres from gw = 3 on
+    (gh = 1: the horizontal neighbours suffice), in the frame without records too.
+hand_count() is that rule and nothing else."""
+import functools
+
+import numpy as np
+
+import mvtrim_amd as m
+from mvtrim_amd import _abi
+
+import oracle_binding as ob
+import zones_inputs as zi
+from derived_edge_inputs import MI355X_LDS, frozen, sweep_chunk_rows, voters
+from scan_checks import junk_padding
+
+KERNELS = ("zones", "activity", "sweep1", "sweep8")
+TALL_GW = (2, 3, 65, 193)
+WIDE_GH = (1, 3)
+ACT_GW = 120
+# (acc_bits, two workgroups per CU) in the order activity_plan falls through them as the grid grows
+ACT_OUTCOMES = ((32, True), (16, True), (32, False), (16, False), (0, False))
+KEEP_TRIP = 1024                      # lanes of zones_frames_kernel: keep word 1024 is the first of the second trip
+
+
+# ------------------------------------------------------------------ the grids
+
+def shift_of(gw, gh):
+    return 1 if (max(gw, gh) << 1) <= 32767 else 0
+
+
+def grid_params(gw, gh, **kw):
+    sh = shift_of(gw, gh)
+    p = m.ScanParams.from_config(gw << sh, gh << sh, block_size=1 << sh, block_shift=sh, vertical_mask=0.0, **kw)
+    assert (p.grid_w, p.grid_h, p.vertical_margin, p.block_shift) == (gw, gh, 0, sh)
+    return p
+
+
+def kernel_preview(kernel, p, lds=MI355X_LDS):
+    """The kernel's own preview -> its dict, or None where it answers MT_ERR_UNSUPPORTED (any other error raises)."""
+    try:
+        if kernel == "zones":
+            return m.zones_preview(p, lds)
+        if kernel == "activity":
+            return m.activity_preview(p, lds)
+        n = 1 if kernel == "sweep1" else 8
+        return m.sweep_preview(p, n, n, lds)
+    except m.MtgpuError as e:
+        if e.code != _abi.MT_ERR_UNSUPPORTED:
+            raise
+        return None
+
+
+def creatable(p):
+    try:
+        m.plan_preview(p)
+        return True
+    except m.MtgpuError as e:
+        assert e.code == _abi.MT_ERR_CAPACITY
+        return False
+
+
+def largest(ok, hi=32767):
+    """The largest n in [1, hi] with ok(n), for an ok() that holds up to some n and not beyond."""
+    assert ok(1)
+    lo = 1
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if ok(mid):
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+@functools.lru_cache(maxsize=None)
+def tallest(kernel, gw):
+    return largest(lambda gh: kernel_preview(kernel, grid_params(gw, gh)) is not None)
+
+
+@functools.lru_cache(maxsize=None)
+def widest(kernel, gh):
+    def ok(gw):
+        p = grid_params(gw, gh)
+        return creatable(p) and kernel_preview(kernel, p) is not None
+    return largest(ok, 16383)
+
+
+def act_outcome(gh, gw=ACT_GW):
+    """Index into ACT_OUTCOMES of the plan of a gw x gh grid; len(ACT_OUTCOMES) where the map is unsupported."""
+    pv = kernel_preview("activity", grid_params(gw, gh))
+    return len(ACT_OUTCOMES) if pv is None else ACT_OUTCOMES.index((pv["acc_bits"], 2 * pv["lds_bytes"] <= MI355X_LDS))
+
+
+@functools.lru_cache(maxsize=None)
+def act_last(outcome):
+    return largest(lambda gh: act_outcome(gh) <= outcome)
+
+
+@functools.lru_cache(maxsize=None)
+def shapes(kernel):
+    """{name: (gw, gh, kind)}; kind "tall": one more is gh + 1, "wide": gw + 1, "plan": a plan outcome of the activity
+    map that is not the last one — one more row is supported and has the next outcome."""
+    out = {}
+    for gw in TALL_GW:
+        out[f"tall-{gw}x{tallest(kernel, gw)}"] = (gw, tallest(kernel, gw), "tall")
+    for gh in WIDE_GH:
+        out[f"wide-{widest(kernel, gh)}x{gh}"] = (widest(kernel, gh), gh, "wide")
+    if kernel == "activity":
+        for i, (bits, two) in enumerate(ACT_OUTCOMES):
+            last = i == len(ACT_OUTCOMES) - 1
+            out[f"plan-{bits}bit-{'two' if two else 'one'}-{ACT_GW}x{act_last(i)}"] = (ACT_GW, act_last(i), "tall" if last else "plan")
+            if not last:
+                out[f"plan-past-{bits}bit-{'two' if two else 'one'}-{ACT_GW}x{act_last(i) + 1}"] = (ACT_GW, act_last(i) + 1, "plan")
+    return out
+
+
+def one_more(gw, gh, kind):
+    return (gw + 1, gh) if kind == "wide" else (gw, gh + 1)
+
+
+# The three LDS formulas, restated from the layout comments of csrc/zones_kernels.h, csrc/activity_kernels.h and
+# csrc/sweep_kernels.h (tile: (R + 2) x gw 32-bit counters padded to 16 bytes; W 64-bit words per mask row).  A grid past
+# the limit has no preview to ask, so "what one more row or column would add" comes from these; the host test holds
+# them to the previews' lds_bytes on every shape.
+def _tile(gw, R):
+    return 4 * (((R + 2) * gw + 3) & ~3)
+
+
+def lds_need(kernel, gw, gh):
+    """The LEAST the kernel needs on a gw x gh grid (vertical_mask 0): zones has one form; the activity map's smallest
+    is the one without accumulators; the sweep's is one tile and the three-row mask buffer per level."""
+    W = (gw + 63) // 64
+    if kernel == "zones":
+        return _tile(gw, gh) + (3 * gh + 4) * W * 8 + 16
+    if kernel == "activity":
+        return _tile(gw, gh) + (2 * gh + 2) * W * 8 + 16
+    return _tile(gw, gh) + (1 if kernel == "sweep1" else 8) * 3 * W * 8 + 256
+
+
+def act_lds(gw, gh, bits):
+    return lds_need("activity", gw, gh) + 2 * gh * ((gw + 3) & ~3) * bits // 8
+
+
+# ------------------------------------------------------------------ planted pairs
+
+def seams_of(gw):
+    """The seams s (columns 64 s - 1 | 64 s) the planted pairs sit on: all of them, or the first, a middle and the last."""
+    last = (gw - 1) // 64
+    return sorted({s for s in (1, (last + 1) // 2, last) if 1 <= s <= last}) if last > 3 else list(range(1, last + 1))
+
+
+def plant(candidates, gw, gh):
+    """[((xa, ya), (xb, yb))] -> the pairs that lie in the grid and are isolated from the ones taken before them."""
+    taken, cells = [], set()
+    for a, b in candidates:
+        if not all(0 <= x < gw and 0 <= y < gh for x, y in (a, b)) or a == b:
+            continue
+        near = {(x + dx, y + dy) for x, y in (a, b) for dx, dy in ((0, 0), (1, 0), (-1, 0), (0, 1), (0, -1))}
+        if near & cells:
+            continue
+        taken.append((a, b))
+        cells |= {a, b}
+    return taken
+
+
+def planted_frames(gw, gh):
+    """{"E" | "H" | "VL" | "VR": [pairs]} (see the module docstring).  Rows of the seam pairs: spread over the grid."""
+    W = (gw + 63) // 64
+    trip = KEEP_TRIP // W                                     # keep word 1024 is word (1024 % W) of this row
+    xm, ym = gw // 2, gh // 2
+    E = [((0, 0), (1, 0)), ((gw - 2, 0), (gw - 1, 0)), ((0, gh - 1), (1, gh - 1)), ((gw - 2, gh - 1), (gw - 1, gh - 1)),
+         ((xm, 0), (xm + 1, 0)), ((xm + 3, gh - 1), (xm + 4, gh - 1)),                  # first and last row
+         ((0, ym), (0, ym + 1)), ((gw - 1, ym + 3), (gw - 1, ym + 4)),                  # first and last column
+         ((0, gh - 2), (0, gh - 1)), ((gw - 1, 0), (gw - 1, 1)),                        # corners again, vertically (narrow grids)
+         ((min(1, gw - 1), trip - 1), (min(1, gw - 1), trip)), ((gw - 2, trip + 2), (gw - 1, trip + 2)),
+         ((xm, 2 * trip - 1), (xm, 2 * trip)), ((xm, 4 * trip - 1), (xm, 4 * trip))]
+    H, VL, VR = [], [], []
+    for i, s in enumerate(seams_of(gw)):
+        y = (gh - 1) * (i + 1) // (len(seams_of(gw)) + 1)
+        H += [((64 * s - 1, y), (64 * s, y)), ((64 * s - 1, (y + trip) % gh), (64 * s, (y + trip) % gh))]
+        VL += [((64 * s - 1, y), (64 * s - 1, y + 1)), ((64 * s - 1, trip - 1), (64 * s - 1, trip))]
+        VR += [((64 * s, y), (64 * s, y + 1)), ((64 * s, trip - 1), (64 * s, trip))]
+    if 3 <= gw <= 4:                  # the right corners touch the left corners' pairs: they go to the seamless grid's empty H
+        H += [((gw - 1, 0), (gw - 1, 1)), ((gw - 1, gh - 2), (gw - 1, gh - 1))]
+    return {n: plant(c, gw, gh) for n, c in (("E", E), ("H", H), ("VL", VL), ("VR", VR))}
+
+
+def pair_votes(i):
+    return 2 + i % 3
+
+
+def pair_d(i):
+    return 5 if i % 2 == 0 else 3
+
+
+def pairs_records(pairs, shift):
+    return voters([(x, y, pair_votes(i), pair_d(i), 0) for i, pr in enumerate(pairs) for x, y in pr], shift)
+
+
+def hand_count(pairs, gw, gh, thr, level, cleared=()):
+    """Centres of a planted frame by the rule of the module docstring.  cleared: cells a keep mask ignores (the rule for
+    level 0 is stated without a mask: no caller combines the two)."""
+    if level == 0:
+        assert not cleared
+        return gh * (gw - 2) if gw >= 3 else 0
+    n = 0
+    for i, pr in enumerate(pairs):
+        if pair_votes(i) >= level and not pair_d(i) ** 2 < thr and not set(pr) & set(cleared):
+            n += sum(1 for x, _ in pr if 1 <= x <= gw - 2)
+    return n
+
+
+# ------------------------------------------------------------------ the batch of a shape
+
+ORDER = ("E", "B1", "H", "N", "B2", "B3", "E", "H", "VL", "VR", "B4", "Z")
+N_BLOBS = 30
+ZONE_SOFF = (0, 4, 7, 12)            # stream 0: all ones; 1: 30 % cleared at random; 2: one cell of every seam pair cleared
+ACT_SOFF = (0, 6, 12)                # two streams split mid-batch
+ACT_RUN = 4                          # runs [0, 4) [4, 8) ...: the stream boundary at 6 lies inside the second one
+
+
+@functools.lru_cache(maxsize=None)
+def batch(gw, gh):
+    """(mv, off, sd, planted): the 12 frames of ORDER (E and H appear twice, for the masked scan's streams)."""
+    sh = shift_of(gw, gh)
+    p = grid_params(gw, gh)
+    rng = np.random.RandomState(gw * 40009 + gh)
+    planted = planted_frames(gw, gh)
+    frames, sd = [], []
+    for name in ORDER:
+        if name in planted:
+            f = pairs_records(planted[name], sh)
+        elif name == "Z":
+            f = np.zeros(0, dtype=m.MV_DTYPE)
+        else:
+            f = zi.clustered_frame(rng, p, N_BLOBS)
+        frames.append(f[rng.permutation(len(f))])
+        sd.append(0 if name == "N" else 1)
+    b = m.FrameBatch.from_frames(frames)
+    mv = np.ascontiguousarray(b.mv, dtype=m.MV_DTYPE).copy()
+    junk_padding(mv, rng)
+    return frozen(mv, np.ascontiguousarray(b.frame_off, dtype=np.uint64), np.array(sd, dtype=np.uint8)) + (planted,)
+
+
+def frames_named(name):
+    return [i for i, n in enumerate(ORDER) if n == name]
+
+
+# the context of the masked scan and of the activity map: every planted pair (k >= 2, |d|^2 >= 9) and every blob cell
+# with two votes or more (|d|^2 = 25) is active; the blobs' still records (|d|^2 = 2) are not kept
+CTX_KW = dict(vectors_needed=2, mv_threshold_sq=4.0, clusters_needed=2)
+
+
+# ------------------------------------------------------------------ zones
+
+@functools.lru_cache(maxsize=None)
+def zones_case(name):
+    """(params, mv, off, sd, soff, keeps bool [3, gh, gw], hand {frame: (centres, centres_all)}).  CTX_KW: every planted
+    pair is active.  Stream 2 ignores the LEFT cell of the horizontal seam pairs and the UPPER
+    cell of the vertical ones: its three seam frames count 0, and centres_all still counts them."""
+    gw, gh, _ = shapes("zones")[name]
+    p = grid_params(gw, gh, **CTX_KW)
+    mv, off, sd, planted = batch(gw, gh)
+    keeps = np.ones((3, gh, gw), dtype=bool)
+    keeps[1] = np.random.RandomState(gw + gh).rand(gh, gw) >= 0.3
+    cleared = [pr[0] for n in ("H", "VL", "VR") for pr in planted[n]]
+    for x, y in cleared:
+        keeps[2, y, x] = False
+    st = zi.stream_of_frames(ZONE_SOFF, len(ORDER))
+    hand = {}
+    for f, n in enumerate(ORDER):
+        if n in planted and st[f] != 1:
+            full = hand_count(planted[n], gw, gh, 4.0, 2)
+            hand[f] = (hand_count(planted[n], gw, gh, 4.0, 2, cleared=cleared) if st[f] == 2 else full, full)
+    return (p, mv, off, sd) + frozen(np.array(ZONE_SOFF, dtype=np.uint64), keeps) + (hand,)
+
+
+def zones_expected(p, mv, off, sd, soff, keeps):
+    """((flags, centres, centres_all) of the oracle on filtered records, (centres, centres_all) of the numpy AND rule)."""
+    return zi.oracle_batch(p, mv, off, sd, soff, keeps), zi.model_batch(p, mv, off, sd, soff, keeps)
+
+
+# ------------------------------------------------------------------ activity
+
+@functools.lru_cache(maxsize=None)
+def activity_case(name):
+    gw, gh, _ = shapes("activity")[name]
+    mv, off, sd, planted = batch(gw, gh)
+    return (grid_params(gw, gh, **CTX_KW),) + (mv, off, sd) + frozen(np.array(ACT_SOFF, dtype=np.uint64)) + (planted,)
+
+
+@functools.lru_cache(maxsize=None)
+def activity_planted_case(name):
+    """(mv, off, sd, soff, hand active [1, gh, gw], hand centre, hand frames): the four planted frames alone, one stream.
+    Every cell of a pair is active in its frame (CTX_KW) and a centre iff its column lies
+    in [1, gw - 2]; a cell reads the number of planted frames that hold it."""
+    gw, gh, _ = shapes("activity")[name]
+    planted = planted_frames(gw, gh)
+    sh = shift_of(gw, gh)
+    b = m.FrameBatch.from_frames([pairs_records(planted[n], sh) for n in ("E", "H", "VL", "VR")])
+    active, centre = np.zeros((1, gh, gw), dtype=np.uint32), np.zeros((1, gh, gw), dtype=np.uint32)
+    for n in ("E", "H", "VL", "VR"):
+        for pr in planted[n]:
+            for x, y in pr:
+                active[0, y, x] += 1
+                centre[0, y, x] += 1 <= x <= gw - 2
+    return frozen(np.ascontiguousarray(b.mv, dtype=m.MV_DTYPE), np.ascontiguousarray(b.frame_off, dtype=np.uint64),
+                  np.ones(4, dtype=np.uint8), np.array([0, 4], dtype=np.uint64), active, centre, np.array([4], dtype=np.uint32))
+
+
+# ------------------------------------------------------------------ sweep
+
+# the caller's order, neither ascending nor descending, 25.0 and level 3 twice, levels 0 and 255
+THR8 = [25.0, 9.5, 26.0, 9.0, 0.0, 25.0, 4.0, 4294967296.0]
+VEC8 = [2, 0, 255, 3, 1, 4, 3, 5]
+CALLS1 = [([16.0], [2]), ([9.0], [0]), ([25.0], [255]), ([9.5], [3])]          # 1 x 1: one call per setting
+
+
+def sweep_calls(kernel):
+    return CALLS1 if kernel == "sweep1" else [(THR8, VEC8)]
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_setting(gw, gh, thr, vec):
+    """(oracle counts [F], numpy counts [F]) of one setting on the shape's batch."""
+    mv, off, sd, _ = batch(gw, gh)
+    p = grid_params(gw, gh, mv_threshold_sq=thr, vectors_needed=vec)
+    ones = np.ones((gh, gw), dtype=bool)
+    model = np.array([zi.zone_counts_np(p, mv[int(off[f]):int(off[f + 1])], ones)[1] if sd[f] else 0 for f in range(len(sd))],
+                     dtype=np.uint32)
+    return frozen(ob.scan_centres(p, mv, off, sd, nthreads=4)[1].copy(), model)
+
+
+def sweep_expected(kernel, name, thr, vec, which=0):
+    gw, gh, _ = shapes(kernel)[name]
+    return np.stack([np.stack([sweep_setting(gw, gh, float(t), int(v))[which] for v in vec]) for t in thr])
+
+
+def sweep_hand(kernel, name, thr, vec):
+    """{frame: uint32 [T, V]} of the planted frames."""
+    gw, gh, _ = shapes(kernel)[name]
+    planted = batch(gw, gh)[3]
+    return {f: np.array([[hand_count(planted[n], gw, gh, t, v & 0xFF) for v in vec] for t in thr], dtype=np.uint32)
+            for f, n in enumerate(ORDER) if n in planted}
+
+
+def sweep_path(kernel, name):
+    """(passes, chunk_rows, R) of the shape's plan."""
+    gw, gh, _ = shapes(kernel)[name]
+    n = 1 if kernel == "sweep1" else 8
+    ch, R, _, pv = sweep_chunk_rows(grid_params(gw, gh), n, n)
+    return pv["passes"], ch, R

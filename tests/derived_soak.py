@@ -1,0 +1,198 @@
+"""The random stream of tests/test_gpu_derived_soak.py — the soak of the sweep, the activity map and the masked scan — and
+its expected values, usable without a GPU (tests/test_derived_cliff_host.py replays the first iterations):
+
+    d = draw(rng, it)                 # grid, parameters, batch, streams, masks, settings, record layout, base alignment
+    e = expected(d, kernel)           # kernel in KERNELS, where d["support"][kernel]
+    d = replay(seed, it)              # iteration `it` of the soak with `seed`, rebuilt on the CPU
+
+The grid comes from w, h in [64, 3900] x [64, 2200] and block_shift 1 .. 5 as in tests/soak_replay.py, but the shifts are
+not equally likely: a derived kernel holds a whole frame's counters in LDS and supports about 37 000 cells, which a
+grid of 2- or 4-pixel cells rarely stays under.  With the weights of SHIFT_P each kernel is supported in at least three
+quarters of the draws (asserted on the CPU); the rest checks that an unsupported grid is refused and touches nothing."""
+import numpy as np
+
+import mvtrim_amd as m
+from mvtrim_amd import _abi, synth
+
+import oracle_binding as ob
+import zones_inputs as zi
+from activity_model import assert_oracle_identities, model_maps
+from derived_edge_inputs import MI355X_LDS, UNALIGNED_SHIFTS
+from scan_checks import junk_padding
+
+KERNELS = ("sweep", "activity", "zones")
+DEFAULT_SEED = 24680
+SHIFT_P = [0.04, 0.08, 0.18, 0.35, 0.35]                 # block_shift 1 .. 5
+THR_POOL = [0.0, 4.0, 9.5, 16.0, 25.0, 37.0, 4294967296.0, float("inf")]
+VEC_POOL = [0, 1, 2, 3, 4, 6, 12, 255]
+
+
+def _preview(fn, *a):
+    try:
+        fn(*a)
+        return True
+    except m.MtgpuError as e:
+        assert e.code == _abi.MT_ERR_UNSUPPORTED, e
+        return False
+
+
+def support_of(p, n_thr, n_vec, lds=MI355X_LDS):
+    return {"sweep": _preview(m.sweep_preview, p, n_thr, n_vec, lds), "activity": _preview(m.activity_preview, p, lds),
+            "zones": _preview(m.zones_preview, p, lds)}
+
+
+def draw(rng, it):
+    """One iteration's inputs.  "creatable": False where mtgpu_create refuses the grid (nothing else is drawn then)."""
+    sh = int(rng.choice([1, 2, 3, 4, 5], p=SHIFT_P))
+    w, h = int(rng.randint(64, 3900)), int(rng.randint(64, 2200))
+    kw = dict(mv_threshold_sq=float(rng.choice([16.0, 4.0, 0.0, 9.5, 4294967296.0], p=[0.3, 0.3, 0.15, 0.15, 0.1])),
+              block_size=1 << sh, block_shift=sh,
+              vectors_needed=int(rng.choice([1, 1, 2, 2, 3, 4, 6, 12, 255, 0])),
+              clusters_needed=int(rng.choice([1, 2, 2, 3, 10])),
+              vertical_mask=float(rng.choice([0.0, 0.05, 0.2, 0.5], p=[0.4, 0.3, 0.2, 0.1])))
+    p = ob.params_from_config(w, h, **kw)
+    d = dict(it=it, w=w, h=h, kw=kw, params=p, creatable=True)
+    try:
+        m.plan_preview(p)
+    except m.MtgpuError as e:
+        assert e.code == _abi.MT_ERR_CAPACITY
+        d.update(creatable=False, support={k: False for k in KERNELS}, mv=np.zeros(0, dtype=m.MV_DTYPE))
+        return d
+    # the sweep's settings, unsorted, with duplicates
+    thr = [float(x) for x in rng.choice(THR_POOL, size=int(rng.randint(1, 9)))]
+    vec = [int(x) for x in rng.choice(VEC_POOL, size=int(rng.randint(1, 9)))]
+    support = support_of(p, len(thr), len(vec))
+    # the batch: ragged random frames with blobs added, so that centres exist; runs on every other iteration
+    F = int(rng.choice([3, 9, 17, 40, 64]))
+    fewer = 1 if any(support.values()) else 8                # nothing reads the records of a grid no kernel supports
+    mv, off, _ = synth.random_frames(rng, F, int(rng.choice([200, 3000, 8000])) // fewer, w, h, hot=float(rng.choice([0.05, 0.5, 0.95])))
+    n_blobs = int(rng.choice([0, 4, 12, 30]))
+    frames = [np.concatenate([mv[int(off[f]):int(off[f + 1])], zi.clustered_frame(rng, p, n_blobs + f % 3)]) for f in range(F)]
+    frames = [f[rng.permutation(len(f))] for f in frames]
+    if rng.rand() < 0.3:
+        frames[int(rng.randint(0, F))] = np.zeros(0, dtype=m.MV_DTYPE)
+    off = np.concatenate([[0], np.cumsum([len(f) for f in frames])]).astype(np.uint64)
+    mv = np.ascontiguousarray(np.concatenate(frames), dtype=m.MV_DTYPE)
+    if it % 2 == 0 and len(mv):                              # tests/soak_replay.py, draw_tail: every record 1 .. 6 times
+        r = rng.randint(1, 7, size=len(mv))
+        csum = np.concatenate([[0], np.cumsum(r)])
+        off = csum[off.astype(np.int64)].astype(np.uint64)
+        mv = np.repeat(mv, r)
+    junk_padding(mv, rng)
+    sd = (rng.rand(F) < 0.85).astype(np.uint8)
+    # streams: 1 .. 5 at random cut points, empty ones allowed; the masked scan sometimes leaves frames behind the last
+    S = int(rng.randint(1, 6))
+    soff = np.array([0] + sorted(int(x) for x in rng.randint(0, F + 1, size=S - 1)) + [F], dtype=np.uint64)
+    behind = int(rng.choice([0, 0, 1, 2]))
+    zsoff = np.minimum(soff, F - behind).astype(np.uint64)
+    dens = [float(x) for x in rng.choice([0.0, 0.3, 0.9, 1.0], size=S)]
+    keeps = np.stack([rng.rand(p.grid_h, p.grid_w) < q for q in dens]) if support["zones"] else None
+    window = None
+    if it % 3 == 0:
+        window = (int(rng.choice(UNALIGNED_SHIFTS)), 8 * int(rng.randint(0, 16)))     # 40-byte shift, compact residue
+    d.update(support=support, mv=mv, off=off, sd=sd, thr=thr, vec=vec, soff=soff, zsoff=zsoff, keep_density=dens, keeps=keeps,
+             min_centres=int(rng.choice([0, 1, 2])), run_frames=int(rng.choice([0, 1, 3, 17])), compact=bool(it % 2), window=window)
+    return d
+
+
+def replay(seed, target):
+    rng = np.random.RandomState(seed)
+    for it in range(1, target + 1):
+        d = draw(rng, it)
+    return d
+
+
+def _setting_params(d, thr, vec):
+    kw = dict(d["kw"], mv_threshold_sq=thr, vectors_needed=vec)
+    return ob.params_from_config(d["w"], d["h"], **kw)
+
+
+def sweep_counts_np(p, mv, off, sd, thrs, vecs):
+    """{(thr, vec): uint32 [F]}: the centre counts of every setting by the numpy rule, restated here for a block of
+    settings (zones_inputs.zone_counts_np states it for one): per frame one histogram per threshold — kept records with a
+    destination cell on an analysed row — saturated at 255, `>= vec` per level, and a centre is an active cell of an
+    analysed row and an inner column with an active 4-neighbour.  A frame without side data counts 0."""
+    gw, gh, mg, F = p.grid_w, p.grid_h, p.vertical_margin, len(sd)
+    rows = np.zeros((gh, 1), dtype=bool)
+    rows[min(mg, gh):max(gh - mg, min(mg, gh))] = True
+    out = {(t, v): np.zeros(F, dtype=np.uint32) for t in thrs for v in vecs}
+    for f in range(F):
+        if not sd[f]:
+            continue
+        r = mv[int(off[f]):int(off[f + 1])]
+        d2 = ((r["dst_x"].astype(np.int64) - r["src_x"]) ** 2 + (r["dst_y"].astype(np.int64) - r["src_y"]) ** 2).astype(np.float64)
+        gx, gy = r["dst_x"].astype(np.int64) >> p.block_shift, r["dst_y"].astype(np.int64) >> p.block_shift
+        inside = (gx >= 0) & (gx < gw) & (gy >= 0) & (gy < gh)
+        inside &= rows[np.clip(gy, 0, gh - 1), 0]
+        cell = gy * gw + gx
+        for t in thrs:
+            ok = inside & ~(d2 < t)
+            votes = np.minimum(np.bincount(cell[ok], minlength=gw * gh).reshape(gh, gw), 255)
+            for v in vecs:
+                act = votes >= (v & 0xFF)
+                z = np.pad(act, 1)
+                nb = z[1:-1, :-2] | z[1:-1, 2:] | z[:-2, 1:-1] | z[2:, 1:-1]
+                out[t, v][f] = int((act & nb & rows)[:, 1:gw - 1].sum())
+    return out
+
+
+def zones_vn0_count(p, keep):
+    """The masked centre count of ANY frame with side data under vectors_needed 0, cell by cell in plain Python (the
+    records play no part): a cell of the grid is active iff its row is not analysed or its keep bit is set; a centre is
+    an active cell of an analysed row, x in [1, gw - 2], with an active 4-neighbour inside the grid."""
+    gw, gh, mg = p.grid_w, p.grid_h, p.vertical_margin
+    lo, hi = min(mg, gh), max(gh - mg, min(mg, gh))
+    keep = np.asarray(keep, dtype=bool).tolist()
+
+    def active(x, y):
+        return 0 <= x < gw and 0 <= y < gh and (not lo <= y < hi or keep[y][x])
+    n = 0
+    for y in range(lo, hi):
+        for x in range(1, gw - 1):
+            n += active(x, y) and (active(x - 1, y) or active(x + 1, y) or active(x, y - 1) or active(x, y + 1))
+    return int(n)
+
+
+def expected(d, kernel, check_sources=False):
+    """The expected outputs of `kernel` on draw d and "total", the sum of the centre counts they hold.  check_sources:
+    assert that the second, independent source agrees — the sweep: the oracle and sweep_counts_np on every setting; the
+    activity map: the numpy model and the oracle's identities; the masked scan (always checked): the numpy AND rule
+    against the oracle on filtered records, or under vectors_needed 0 against zones_vn0_count, and centres_all against
+    the oracle on the records as they are."""
+    p, mv, off, sd = d["params"], d["mv"], d["off"], d["sd"]
+    if kernel == "sweep":
+        T, V, F = len(d["thr"]), len(d["vec"]), len(sd)
+        want, memo = np.zeros((T, V, F), dtype=np.uint32), {}
+        for t, thr in enumerate(d["thr"]):
+            for v, vec in enumerate(d["vec"]):
+                if (thr, vec) not in memo:
+                    memo[thr, vec] = ob.scan_centres(_setting_params(d, thr, vec), mv, off, sd, nthreads=8)[1]
+                want[t, v] = memo[thr, vec]
+        if check_sources:                                    # the numpy rule on every distinct setting of the block
+            model = sweep_counts_np(p, mv, off, sd, sorted({t for t, _ in memo}), sorted({v for _, v in memo}))
+            for key, oracle in memo.items():
+                assert oracle.tolist() == model[key].tolist(), ("sweep", d["it"], key)
+        return dict(centres=want, total=int(want.sum(dtype=np.uint64)))
+    if kernel == "activity":
+        a, c, fr, counts = model_maps(p, mv, off, sd, d["soff"], d["min_centres"])
+        if check_sources:
+            oc = assert_oracle_identities(p, mv, off, sd, d["soff"], d["min_centres"], c, fr, ("activity", d["it"]))
+            assert np.array_equal(oc[sd != 0], counts[sd != 0])
+        return dict(maps=(a, c, fr), total=int(counts.sum()))
+    assert kernel == "zones"
+    soff, keeps = d["zsoff"], d["keeps"]
+    mc, mca = zi.model_batch(p, mv, off, sd, soff, keeps)
+    oca = ob.scan_centres(p, mv, off, sd, nthreads=8)[1].copy()
+    oca[zi.stream_of_frames(soff, len(sd)) >= len(keeps)] = 0
+    assert np.array_equal(oca, mca), ("zones centres_all", d["it"])
+    if (p.vectors_needed & 0xFF) == 0:                       # the oracle on filtered records has no vectors_needed 0:
+        per_stream = [zones_vn0_count(p, k) for k in keeps]  # zones_vn0_count stands in for it     
+        st = zi.stream_of_frames(soff, len(sd))
+        loop = [per_stream[st[f]] if sd[f] and 0 <= st[f] < len(keeps) else 0 for f in range(len(sd))]
+        assert mc.tolist() == loop, ("zones centres, vectors_needed 0", d["it"])
+    else:
+        fl, oc, _ = zi.oracle_batch(p, mv, off, sd, soff, keeps)
+        assert np.array_equal(oc, mc), ("zones centres", d["it"])
+        assert np.array_equal(fl, (mc >= max(1, p.clusters_needed)).astype(np.uint8))
+    return dict(flags=(mc >= max(1, p.clusters_needed)).astype(np.uint8), centres=mc, centres_all=mca,
+                total=int(mca.sum(dtype=np.uint64)))

@@ -1,0 +1,144 @@
+"""GPU tier (`-m gpu`): the sweep, the activity map and the masked scan on the last grids their LDS layouts hold — two,
+three, 65 and 193 columns at the largest height, one and three rows at the largest width, and for the activity map the
+last and the first grid of every plan outcome — through the C ABI's device entry points on both record layouts.
+
+The shapes, the batches and the values derived by hand come from tests/derived_cliff_inputs.py, which finds the shapes
+with the previews at 163 840 bytes of LDS; tests/test_derived_cliff_host.py proves without a GPU that they sit on the
+limit and that two independent sources agree on every expected value.  Here every comparison is exact, outputs are
+pre-filled with junk, and the grid one row or column past each shape must be refused with every output byte untouched.
+Every test first asserts that the context's LDS limit is the one the shapes were derived for."""
+import re
+
+import numpy as np
+import pytest
+
+import mvtrim_amd as m
+from mvtrim_amd import _abi
+
+import derived_cliff_inputs as dci
+from activity_model import model_maps
+from scan_checks import assert_counts_equal, to_device
+from test_gpu_activity import assert_maps_equal, device_maps, junk_maps
+from test_gpu_activity import JUNK as MAP_JUNK
+from test_gpu_sweep import JUNK as SWEEP_JUNK
+from test_gpu_sweep import device_sweep, junk_out
+from test_gpu_zones import JUNK, JUNK_FLAG, keep_tensor, soff_tensor, zones_both_layouts
+
+pytestmark = pytest.mark.gpu
+
+_limit = []
+
+
+def assert_lds_limit(gpu_scanner_factory):
+    """The context's own limit, read from the message of a call it refuses: on another device the shapes below are not
+    the last ones, and the tests must fail here instead of running off the limit."""
+    if not _limit:
+        big = gpu_scanner_factory(m.ScanParams.from_config(3840, 2160, block_size=4, block_shift=2))
+        with pytest.raises(m.MtgpuError) as ei:
+            big.scan_zones(m.FrameBatch(np.zeros(3, dtype=m.MV_DTYPE), np.array([0, 3], dtype=np.uint64)), [0, 1],
+                           np.zeros((1, 540, 15), dtype=np.uint64))
+        assert ei.value.code == _abi.MT_ERR_UNSUPPORTED
+        found = re.search(r"fit (\d+) bytes of LDS", str(ei.value))
+        assert found is not None, f"the refusal no longer states the context's LDS limit: {ei.value}"
+        _limit.append(int(found.group(1)))
+    assert _limit[0] == dci.MI355X_LDS, f"LDS per workgroup is {_limit[0]}: the limit shapes were derived for {dci.MI355X_LDS}"
+
+
+def refused(call):
+    import torch
+    with pytest.raises(m.MtgpuError) as ei:
+        call()
+    torch.cuda.synchronize()
+    assert ei.value.code == _abi.MT_ERR_UNSUPPORTED, ei.value
+
+
+def untouched(t, junk):
+    return int((t != junk).sum()) == 0
+
+
+# ------------------------------------------------------------------ the masked scan
+
+@pytest.mark.parametrize("name", list(dci.shapes("zones")))
+def test_zones_at_the_lds_limit(gpu_scanner_factory, name):
+    """Three streams — all ones, 30 % cleared at random, one cell of every seam pair cleared — flags, centres and
+    centres_all against the oracle on filtered records (== the numpy AND rule, on the CPU) and the planted frames
+    against their hand values.  Two, three and 65 columns: the keep words take a second trip of the staging loop."""
+    import torch
+    assert_lds_limit(gpu_scanner_factory)
+    p, mv, off, sd, soff, keeps, hand = dci.zones_case(name)
+    (want_f, want_c, want_all), _ = dci.zones_expected(p, mv, off, sd, soff, keeps)
+    s = gpu_scanner_factory(p)
+    for label, fl, ce, ca in zones_both_layouts(s, mv, off, sd, soff, keeps, name):
+        assert_counts_equal(ce, want_c, label, got_f=fl, want_f=want_f)
+        assert_counts_equal(ca, want_all, label + " centres_all")
+        for f, (hc, hca) in hand.items():
+            assert (int(ce[f]), int(ca[f])) == (hc, hca), (label, "planted frame", f)
+    gw, gh, kind = dci.shapes("zones")[name]
+    mw, mh = dci.one_more(gw, gh, kind)
+    more = gpu_scanner_factory(dci.grid_params(mw, mh, **dci.CTX_KW))
+    d_rec, d_off, d_sd = to_device(mv, off, sd, True)
+    F = len(sd)
+    fl = torch.full((F,), JUNK_FLAG, dtype=torch.uint8, device="cuda")
+    ce, ca = (torch.full((F,), JUNK, dtype=torch.int32, device="cuda") for _ in range(2))
+    d_keep = keep_tensor(np.ones((3, mh, mw), dtype=bool))
+    refused(lambda: more.scan_zones_device(d_rec, d_off, d_sd, soff_tensor(soff), d_keep, compact=True, flags=fl, centres=ce,
+                                           centres_all=ca))
+    assert untouched(fl, JUNK_FLAG) and untouched(ce, JUNK) and untouched(ca, JUNK)
+
+
+# ------------------------------------------------------------------ the activity map
+
+@pytest.mark.parametrize("name", list(dci.shapes("activity")))
+def test_activity_at_the_lds_limit(gpu_scanner_factory, name):
+    """Two streams split mid-batch, min_centres 0 and 1, run_frames 0 and one that puts the stream boundary inside a run,
+    against the numpy model (== the oracle's identities, on the CPU); then the planted frames alone against per-cell hand
+    values.  The "plan" shapes are the last and the first grid of each outcome of activity_plan."""
+    assert_lds_limit(gpu_scanner_factory)
+    p, mv, off, sd, soff, _ = dci.activity_case(name)
+    gw, gh, kind = dci.shapes("activity")[name]
+    pv = m.activity_preview(p)
+    s = gpu_scanner_factory(p)
+    wants = {mc: model_maps(p, mv, off, sd, soff, mc)[:3] for mc in (0, 1)}
+    pmv, poff, psd, psoff, ha, hc, hf = dci.activity_planted_case(name)
+    for compact in (False, True):
+        d_rec, d_off, d_sd = to_device(mv, off, sd, compact)
+        for mc in (0, 1):
+            for run in (0, dci.ACT_RUN):
+                got = device_maps(s, d_rec, d_off, d_sd, soff_tensor(soff), compact, min_centres=mc, run_frames=run)
+                assert_maps_equal(got, wants[mc], f"{name} {pv} compact {compact} min_centres {mc} run_frames {run}")
+        d_rec, d_off, d_sd = to_device(pmv, poff, psd, compact)
+        got = device_maps(s, d_rec, d_off, d_sd, soff_tensor(psoff), compact)
+        assert_maps_equal(got, (ha, hc, hf), f"{name} planted frames by hand, compact {compact}")
+    if kind == "plan":
+        return
+    more = gpu_scanner_factory(dci.grid_params(*dci.one_more(gw, gh, kind), **dci.CTX_KW))
+    outs = junk_maps(more, 2)
+    refused(lambda: more.activity_map_device(d_rec, d_off, d_sd, soff_tensor([0, 2, 4]), compact=True, out=outs))
+    assert all(untouched(t, MAP_JUNK) for t in outs.values())
+
+
+# ------------------------------------------------------------------ the sweep
+
+@pytest.mark.parametrize("kernel,name", [(k, n) for k in ("sweep1", "sweep8") for n in dci.shapes(k)])
+def test_sweep_at_the_lds_limit(gpu_scanner_factory, kernel, name):
+    """1 x 1: the tile and a mask buffer fill the LDS, one call per setting (levels 0 and 255 among them).  8 x 8: eight
+    passes of one tile next to a mask buffer of three rows or little more, thresholds and levels in the caller's order
+    with duplicates.  Against the oracle per setting (== the numpy rule, on the CPU) and the planted frames' hand values."""
+    assert_lds_limit(gpu_scanner_factory)
+    gw, gh, kind = dci.shapes(kernel)[name]
+    mv, off, sd, _ = dci.batch(gw, gh)
+    s = gpu_scanner_factory(dci.grid_params(gw, gh))
+    more = gpu_scanner_factory(dci.grid_params(*dci.one_more(gw, gh, kind)))
+    print(kernel, name, "passes, chunk_rows, R", dci.sweep_path(kernel, name))
+    for compact in (False, True):
+        d_rec, d_off, d_sd = to_device(mv, off, sd, compact)
+        for thr, vec in dci.sweep_calls(kernel):
+            want = dci.sweep_expected(kernel, name, thr, vec)
+            got = device_sweep(s, d_rec, d_off, d_sd, thr, vec, compact)
+            assert_counts_equal(got.reshape(-1), want.reshape(-1), f"{kernel} {name} {thr} x {vec} compact {compact}")
+            for f, h in dci.sweep_hand(kernel, name, thr, vec).items():
+                assert np.array_equal(got[:, :, f], h), (kernel, name, "planted frame", f, thr, vec)
+    thr, vec = dci.sweep_calls(kernel)[0]
+    out = junk_out(len(thr), len(vec), len(sd))
+    refused(lambda: more.sweep_centres_device(d_rec, d_off, d_sd, thr, vec, compact=True, out=out))
+    assert untouched(out, SWEEP_JUNK)

@@ -1,0 +1,137 @@
+"""Soak of the derived kernels: randomised parity of the sweep, the activity map and the masked scan for
+MTGPU_SOAK_SECONDS (default 4 s; set it to minutes to hunt rare faults).  Every iteration draws a grid, a parameter set,
+a ragged batch with runs and blobs, streams with empty ones, keep masks, sweep settings, a record layout and — every
+third time — a record base inside a larger buffer (tests/derived_soak.py, which also computes the expected values from
+the oracle and the numpy models and rebuilds any iteration on the CPU: derived_soak.replay(seed, it)).  Every
+comparison is exact; a kernel whose preview says unsupported must answer MT_ERR_UNSUPPORTED and touch nothing."""
+import os
+import time
+
+import numpy as np
+import pytest
+
+import mvtrim_amd as m
+from mvtrim_amd import _abi
+
+import derived_soak as dsoak
+from scan_checks import assert_counts_equal
+from test_gpu_activity import assert_maps_equal, junk_maps
+from test_gpu_derived_cliff import assert_lds_limit
+from test_gpu_derived_edges import shifted
+from test_gpu_zones import keep_tensor, soff_tensor
+
+pytestmark = pytest.mark.gpu
+
+JUNK, JUNK_FLAG = -7, 9
+
+
+def records_on_device(d):
+    """The records in the draw's layout; on a window iteration inside a larger buffer: 40-byte records shifted by 4, 12 or
+    20 bytes, compact ones with the first record on the drawn 8-byte residue of a 128-byte line."""
+    import torch
+    mv, compact = d["mv"], d["compact"]
+    raw = (m.pack_records(mv) if compact else np.ascontiguousarray(mv, dtype=m.MV_DTYPE)).view(np.uint8).reshape(-1)
+    host = torch.from_numpy(raw.copy())
+    if d["window"] is None or raw.size == 0:
+        return host.cuda() if raw.size else torch.zeros(0, dtype=torch.uint8, device="cuda")
+    if not compact:
+        return shifted(host, d["window"][0])
+    buf = torch.zeros(raw.size + 256, dtype=torch.uint8, device="cuda")
+    at = (d["window"][1] - buf.data_ptr()) % 128
+    view = buf[at:at + raw.size]
+    view.copy_(host)
+    assert view.data_ptr() % 128 == d["window"][1]
+    return view
+
+
+def expect_unsupported(call, outs, junks, what):
+    import torch
+    with pytest.raises(m.MtgpuError) as ei:
+        call()
+    torch.cuda.synchronize()
+    assert ei.value.code == _abi.MT_ERR_UNSUPPORTED, (what, ei.value)
+    for t, j in zip(outs, junks):
+        assert int((t != j).sum()) == 0, (what, "a refused call wrote to an output")
+
+
+def check_draw(s, d, where):
+    import torch
+    F, compact = len(d["sd"]), d["compact"]
+    d_rec = records_on_device(d)
+    d_off = torch.from_numpy(d["off"].astype(np.int64)).cuda()
+    d_sd = torch.from_numpy(d["sd"]).cuda()
+    gh, gw = d["params"].grid_h, d["params"].grid_w
+    # the sweep
+    out = torch.full((len(d["thr"]), len(d["vec"]), F), JUNK, dtype=torch.int32, device="cuda")
+    call = lambda: s.sweep_centres_device(d_rec, d_off, d_sd, d["thr"], d["vec"], compact=compact, out=out)   # noqa: E731
+    if d["support"]["sweep"]:
+        call()
+        torch.cuda.synchronize()
+        want = dsoak.expected(d, "sweep")["centres"]
+        assert_counts_equal(out.cpu().numpy().view(np.uint32).reshape(-1), want.reshape(-1), f"sweep {d['thr']} x {d['vec']}, {where}")
+    else:
+        expect_unsupported(call, [out], [JUNK], "sweep, " + where)
+    # the activity map
+    outs = junk_maps(s, len(d["soff"]) - 1)
+    call = lambda: s.activity_map_device(d_rec, d_off, d_sd, soff_tensor(d["soff"]), min_centres=d["min_centres"],   # noqa: E731
+                                         run_frames=d["run_frames"], compact=compact, out=outs)
+    if d["support"]["activity"]:
+        call()
+        torch.cuda.synchronize()
+        got = tuple(outs[n].cpu().numpy().view(np.uint32) for n in ("active", "centre", "frames"))
+        assert_maps_equal(got, dsoak.expected(d, "activity")["maps"],
+                          f"activity min_centres {d['min_centres']} run_frames {d['run_frames']} streams {d['soff'].tolist()}, {where}")
+    else:
+        expect_unsupported(call, list(outs.values()), [JUNK] * 3, "activity, " + where)
+    # the masked scan
+    fl = torch.full((F,), JUNK_FLAG, dtype=torch.uint8, device="cuda")
+    ce, ca = (torch.full((F,), JUNK, dtype=torch.int32, device="cuda") for _ in range(2))
+    S = len(d["zsoff"]) - 1
+    keeps = d["keeps"] if d["keeps"] is not None else np.ones((S, gh, gw), dtype=bool)
+    d_keep = keep_tensor(keeps)
+    call = lambda: s.scan_zones_device(d_rec, d_off, d_sd, soff_tensor(d["zsoff"]), d_keep, compact=compact, flags=fl,   # noqa: E731
+                                       centres=ce, centres_all=ca)
+    if d["support"]["zones"]:
+        call()
+        torch.cuda.synchronize()
+        e = dsoak.expected(d, "zones")
+        what = f"zones streams {d['zsoff'].tolist()} densities {d['keep_density']}, {where}"
+        assert_counts_equal(ce.cpu().numpy().view(np.uint32), e["centres"], what, got_f=fl.cpu().numpy(), want_f=e["flags"])
+        assert_counts_equal(ca.cpu().numpy().view(np.uint32), e["centres_all"], what + " centres_all")
+    else:
+        expect_unsupported(call, [fl, ce, ca], [JUNK_FLAG, JUNK, JUNK], "zones, " + where)
+
+
+def test_soak_derived_kernels(gpu_scanner_factory):
+    assert_lds_limit(gpu_scanner_factory)
+    budget = float(os.environ.get("MTGPU_SOAK_SECONDS", "4"))
+    seed = int(os.environ.get("MTGPU_SOAK_SEED", str(dsoak.DEFAULT_SEED)))
+    rng = np.random.RandomState(seed)
+    t_end = time.time() + budget
+    it = done = 0
+    ran = {k: 0 for k in dsoak.KERNELS}
+    while time.time() < t_end:
+        it += 1
+        d = dsoak.draw(rng, it)
+        if not d["creatable"]:
+            continue
+        p = d["params"]
+        where = (f"seed {seed} iteration {it} grid {p.grid_w}x{p.grid_h} {(d['w'], d['h'], d['kw'])} compact {d['compact']} "
+                 f"window {d['window']}")
+        s = gpu_scanner_factory(p)
+        try:
+            check_draw(s, d, where)
+        except (AssertionError, m.MtgpuError, pytest.fail.Exception) as e:
+            raise AssertionError(f"{where} (derived_soak.replay({seed}, {it}) rebuilds the inputs): {e}") from e
+        finally:
+            s.close()
+        done += 1
+        for k in dsoak.KERNELS:
+            ran[k] += d["support"][k]
+    # The budget is looked at between draws: a run overshoots it by at most one draw.  The costliest draw — the oracle on
+    # 64 settings of 64 frames of 8000 records repeated 3.5 times, about 10^8 record visits on eight threads, and the numpy
+    # models on 64 frames — takes about two seconds of CPU time, the average one a tenth of a second.  A second draw
+    # starts whenever the first one ends inside the budget, so four seconds hold at least two; fewer means that the
+    # expected values, not the kernels, have become the cost.
+    assert done >= (2 if budget >= 4 else 1), f"only {done} configurations in {budget:.0f} s"
+    print(f"derived soak: {done} random configurations checked in {budget:.0f} s, kernels run {ran}")
