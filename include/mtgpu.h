@@ -454,4 +454,8 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * 277-292) — three more entry points, declared the same way. */
 #include "mtgpu_zones.h"
 
+/* The keep mask on the decode path: a pipe that runs the masked scan for every batch (src/motion_scanner.cpp:282 at the
+ * call site of :375-383) — two more entry points, declared the same way. */
+#include "mtgpu_pipe_zones.h"
+
 #endif /* MTGPU_H */

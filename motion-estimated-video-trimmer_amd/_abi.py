@@ -191,6 +191,12 @@ ABI_ZONES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_pipe_zones.h declares (the keep mask of a pipe; mtgpu.h includes it).
+ABI_PIPE_ZONES = {
+    "mtgpu_pipe_set_keep": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mtgpu_pipe_has_keep": (C.c_int, [C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -221,7 +227,7 @@ def load_library(path=None):
             "(or __graft_entry__.build()).  There is no fallback path.")
     lib = C.CDLL(p)
     for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
-            list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()):
+            list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

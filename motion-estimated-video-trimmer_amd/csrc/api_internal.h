@@ -28,5 +28,18 @@ int ctx_launch_scan(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const ui
                     const uint8_t *d_sd, uint32_t n_frames, uint8_t *d_flags, hipStream_t st, int rec_bytes,
                     int flags_in_host_memory, void *plan_ws, size_t plan_ws_bytes, uint32_t *d_centres = nullptr);
 size_t ctx_plan_ws_bytes(uint32_t n_frames);
+// Launch the masked scan (zones_kernels.hip, the pipe form) for a pipe's staging batch on `st`: as ctx_launch_scan, with
+// d_keep = ONE keep plane (gh * W words, include/mtgpu_zones.h) in device memory that serves every frame of the batch.
+// plan_ws / plan_ws_bytes are REQUIRED (the batch's own block): the launch takes nothing from the context's scratch
+// ring.  outputs_in_host_memory: d_flags / d_centres are pinned host memory (zero-copy staging) and are stored at
+// system scope; frames without side data are answered by the planning kernel at the same scope.  With
+// mtgpu_profile_enable on it records the same event triple as ctx_launch_scan.  MT_ERR_UNSUPPORTED as
+// mtgpu_zones_preview.
+int ctx_launch_zones(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
+                     uint32_t n_frames, const uint64_t *d_keep, uint8_t *d_flags, uint32_t *d_centres, hipStream_t st, int rec_bytes,
+                     int outputs_in_host_memory, void *plan_ws, size_t plan_ws_bytes);
+// *words = uint64 words of one keep plane (gh * W) of the context's grid; MT_ERR_UNSUPPORTED (the grid is named) when
+// the masked scan has no form for it.  No HIP call.
+int ctx_zones_keep_words(const mtgpu_ctx *c, uint64_t *words);
 
 }  // namespace mtgpu

@@ -505,6 +505,61 @@ class MtmvSource : public FrameSource {
   }
 };
 
+// ---------------------------------------------------------------- keep masks (ignore zones)
+// A `.mtkeep` file: the keep mask of include/mtgpu_zones.h as text a user can edit (python -m mvtrim_amd.zones
+// --save-mask x.mtkeep writes it).  Line 1 `mtkeep 1`; line 2 `<grid_w> <grid_h>`; then grid_h lines of grid_w
+// characters, `1` = the cell is analysed, `0` = ignored (src/motion_scanner.cpp:282 gets one more term).
+// load_keep parses `path` for a gw x gh grid into gh * W words (W = (gw + 63) / 64; cell (x, y) is bit x & 63 of word
+// y * W + (x >> 6); bits at x >= gw are 0) — what GpuMotionScanner::set_keep and mtgpu_pipe_set_keep take.  false, with
+// the line named in `err`: another first line, a grid that is not gw x gh, a short file, a row of another length, any
+// character but 0 / 1, text behind the last row.  `words` is left empty then.
+inline bool load_keep(const std::string &path, int gw, int gh, std::vector<uint64_t> &words, std::string &err) {
+  words.clear();
+  std::ifstream in(path, std::ios::binary);
+  if (!in) { err = path + ": cannot open"; return false; }
+  std::string text((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+  std::vector<std::string> lines;
+  for (size_t at = 0; at < text.size();) {
+    size_t nl = text.find('\n', at);
+    if (nl == std::string::npos) nl = text.size();
+    std::string ln = text.substr(at, nl - at);
+    if (!ln.empty() && ln.back() == '\r') ln.pop_back();
+    lines.push_back(std::move(ln));
+    at = nl + 1;
+  }
+  auto bad = [&](size_t line, const std::string &what) { err = path + ": line " + std::to_string(line) + ": " + what; words.clear(); return false; };
+  if (lines.empty() || lines[0] != "mtkeep 1") return bad(1, "want 'mtkeep 1'");
+  long fw = -1, fh = -1;
+  if (lines.size() > 1) {
+    const std::string &d = lines[1];
+    const size_t sp = d.find(' ');
+    auto number = [](const std::string &t) -> long {
+      if (t.empty() || t.size() > 6) return -1;
+      long v = 0;
+      for (char ch : t) { if (ch < '0' || ch > '9') return -1; v = v * 10 + (ch - '0'); }
+      return v;
+    };
+    if (sp != std::string::npos) { fw = number(d.substr(0, sp)); fh = number(d.substr(sp + 1)); }
+  }
+  if (fw < 1 || fh < 1) return bad(2, "want '<grid_w> <grid_h>'");
+  if (gw < 1 || gh < 1 || fw != gw || fh != gh)
+    return bad(2, "the mask is for a " + std::to_string(fw) + "x" + std::to_string(fh) + " grid, this one is " + std::to_string(gw) + "x" + std::to_string(gh));
+  const size_t W = ((size_t)gw + 63u) / 64u;
+  words.assign((size_t)gh * W, 0ull);
+  for (size_t y = 0; y < (size_t)gh; ++y) {
+    const size_t n = 3 + y;
+    if (n > lines.size()) return bad(n, "the file ends after " + std::to_string(y) + " of " + std::to_string(gh) + " rows");
+    const std::string &row = lines[n - 1];
+    if (row.size() != (size_t)gw) return bad(n, std::to_string(row.size()) + " characters, want " + std::to_string(gw));
+    for (size_t x = 0; x < (size_t)gw; ++x) {
+      if (row[x] == '1') words[y * W + (x >> 6)] |= 1ull << (x & 63u);
+      else if (row[x] != '0') return bad(n, "character " + std::to_string(x + 1) + " is neither 0 nor 1");
+    }
+  }
+  if (lines.size() > 2 + (size_t)gh) return bad(3 + (size_t)gh, "text behind the last of " + std::to_string(gh) + " rows");
+  return true;
+}
+
 // ---------------------------------------------------------------- scanner
 // The GPU side of one worker: a scan context (cfg + launch plan) and its pinned pipe.  Kept
 // separate from the decoder-facing scanner so that a batch worker can reuse it for the next
@@ -664,6 +719,7 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   bool device_error_ = false;                         // a submit / collect / release failed: the pipe's state is unknown
   bool keep_centres_ = false;                          // keep_centres(): the pipe carries centre counts, scan_range keeps them
   std::vector<std::pair<double, uint32_t>> last_centres_;
+  std::vector<uint64_t> keep_;                         // set_keep(): the keep mask initialize() hands to the pipe; empty: none
   bool ok(int rc) {
     if (rc == MT_OK) return true;
     err_ = mtgpu_last_error();
@@ -762,6 +818,11 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   // scan_range's signature and result stay the reference's.
   void keep_centres(bool on) { keep_centres_ = on; }
   const std::vector<std::pair<double, uint32_t>> &last_centres() const { return last_centres_; }
+  // Call before initialize().  The keep mask of this video (include/mtgpu_zones.h: gh * W words, load_keep's result):
+  // every check_frame of scan_range (:375-383) then runs under it — :282 ANDed with the keep bit.  Empty: no mask.
+  // initialize() ALWAYS settles the pipe's mask — it sets this one or clears whatever the pipe carries: a GpuBackend
+  // lives on from one video to the next, and the next video must never inherit the previous one's zones.
+  void set_keep(std::vector<uint64_t> words) { keep_ = std::move(words); }
 
   // batch_records == 0: sized from the source and the staging layout — MTGPU_BATCH_MB MiB of
   // pinned staging per batch, and never less than two frames of one record per 4x4 block (the
@@ -776,6 +837,27 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
     }
     if (!be_->ensure(src_.width(), src_.height(), device_, batch_records, batch_frames, n_buffers, err_, keep_centres_)) return false;
     pipe_ = be_->pipe();
+    // the pipe is idle here (a previous scanner on this backend left nothing in flight, or the backend was rebuilt)
+    if (keep_.empty()) {
+      if (mtgpu_pipe_set_keep(pipe_, nullptr) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
+    } else {
+      mt_scan_params p;
+      if (mtgpu_get_params(be_->ctx(), &p) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
+      const size_t want = (size_t)p.grid_h * (((size_t)p.grid_w + 63u) / 64u);
+      if (keep_.size() != want) {
+        err_ = "keep mask: " + std::to_string(keep_.size()) + " words, the " + std::to_string(p.grid_w) + "x" +
+               std::to_string(p.grid_h) + " grid takes " + std::to_string(want);
+        (void)mtgpu_pipe_set_keep(pipe_, nullptr);             // whatever fails here, no stale mask stays behind
+        pipe_ = nullptr;
+        return false;
+      }
+      if (mtgpu_pipe_set_keep(pipe_, keep_.data()) != MT_OK) {
+        err_ = mtgpu_last_error();
+        (void)mtgpu_pipe_set_keep(pipe_, nullptr);
+        pipe_ = nullptr;
+        return false;
+      }
+    }
     return true;
   }
   double get_duration() { return src_.duration(); }
@@ -861,6 +943,9 @@ struct PipelineResult {
   std::vector<std::pair<double, uint32_t>> centres;
   struct SweepEntry { int clusters_needed = 0; std::vector<mt_segment> segments; mt_merge_result merge{}; };
   std::vector<SweepEntry> sweep;
+  // In: the keep mask of this video (GpuMotionScanner::set_keep; load_keep's words), handed to every worker's scanner.
+  // Empty: none — and a pooled backend that carried another video's mask is cleared.
+  std::vector<uint64_t> keep;
   std::string error;
 };
 
@@ -941,6 +1026,7 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
         GpuBackend *shared = (pool && (size_t)i < pool->size()) ? (*pool)[i].get() : nullptr;
         scanners[i] = std::make_unique<GpuMotionScanner>(*sources[i], dev, shared);
         scanners[i]->keep_centres(keep_centres);
+        scanners[i]->set_keep(out.keep);
         if (!scanners[i]->initialize()) {                                // :198-199 (here: reported)
           fail_with(scanners[i]->error());
           return;
@@ -1028,6 +1114,7 @@ struct ScanJob {
   int stream_id = -1;
   std::string input_path, output_path;
   std::vector<mt_segment> segments;
+  std::vector<uint64_t> keep;          // the keep mask this video was scanned under (process_batch's keep_for); empty: none
   PipelineResult result;
 };
 
@@ -1098,10 +1185,15 @@ struct BatchSummary {   // what a whole process_batch run did and what it held (
   Resources held;                                          // summed over the S x T backends alive at the end
 };
 
-template <class OpenSource>
+// keep_for(path) -> the keep mask of that video (load_keep's words; empty: none), called after open_source(path) and
+// before the scan; it may throw: the video then fails with that message and the others go on.  One mask per video,
+// applied by every worker of its pipeline.
+struct NoKeep { std::vector<uint64_t> operator()(const std::string &) const { return {}; } };
+
+template <class OpenSource, class KeepFor = NoKeep>
 int process_batch(const std::vector<std::string> &files, const std::string &output_dir, int parallel_streams,
                   int threads_per_stream, OpenSource open_source, JobQueue &jobs, std::vector<std::string> *errors,
-                  BatchSummary *summary = nullptr) {
+                  BatchSummary *summary = nullptr, KeepFor keep_for = KeepFor()) {
   parallel_streams = std::max(1, std::min<int>(parallel_streams, (int)files.size()));
   threads_per_stream = std::max(1, threads_per_stream);
   std::mutex q_mu, e_mu, s_mu;
@@ -1163,6 +1255,8 @@ int process_batch(const std::vector<std::string> &files, const std::string &outp
         int rc = 1;
         try {
           auto factory = open_source(in);
+          job.result.keep = keep_for(in);
+          job.keep = job.result.keep;
           rc = run_scan_pipeline(factory, threads_per_stream, job.result, s * threads_per_stream, &pool);
         } catch (const std::exception &e) {
           job.result.error = e.what();

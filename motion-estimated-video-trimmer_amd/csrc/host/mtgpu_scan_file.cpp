@@ -1,7 +1,7 @@
 // mtgpu_scan_file — the scan + merge half of `motion_trim` on the GPU, reading extracted motion
 // vectors from .mtmv containers instead of decoding with FFmpeg:
 //   mtgpu_scan_file stream.mtmv [more.mtmv ...] [--threads T] [--streams S] [--outdir DIR] [--timestamps] [--summary]
-//                   [--centres] [--sweep K1,K2,...]
+//                   [--centres] [--sweep K1,K2,...] [--keep MASK.mtkeep]
 //   (--streams 0 / --threads 0: the reference's own sizing from PARALLEL_STREAMS / THREADS_PER_STREAM and the CPU limit)
 // One file: like `motion_trim in out` (single ProcessingPipeline).  Several files: like
 // `motion_trim in_dir out_dir` (BatchProcessor): S streams x T workers, jobs consumed by one
@@ -12,6 +12,10 @@
 // motion_scanner.cpp:272-294 without its early return), sorted by pts.  --sweep 1,2,4,8: also "sweep": one entry per
 // value k with the segments / do_cut / saved_pct / n_timestamps this tool prints when run with CLUSTERS_NEEDED=k —
 // from the one scan.  Without the two options the output is unchanged.
+// --keep MASK.mtkeep: ignore zones — every input is scanned under the keep mask of that file (mtgpu_host::load_keep;
+// written by `python -m mvtrim_amd.zones --save-mask MASK.mtkeep`): check_frame's :282 gets one more term, so the
+// segments are those of the recording without the ignored cells.  An input whose grid is not the mask's fails with the
+// parser's message, the others go on.  The printed job gains "ignored_cells": N; without the option nothing changes.
 // --summary (several files): one more line {"batch_summary": ...} — frames scanned, wall time, worker-time
 // breakdown and what the S x T workers held (contexts, pipes, HIP streams, pinned / device bytes).
 #include <cmath>
@@ -68,8 +72,34 @@ class RepeatSource : public FrameSource {
 static bool g_summary = false;    // --summary
 static bool g_print_ts = false;   // --timestamps: also print the pooled motion timestamps, sorted (%.17g)
 static bool g_print_centres = false;   // --centres
+static std::string g_keep_path;        // --keep
 
-static void print_job(const std::string &input, const PipelineResult &r, const std::vector<mt_segment> &segs) {
+// The keep mask of g_keep_path for a width x height input; throws with load_keep's message (the line is named) when the
+// file is malformed or made for another grid.
+static std::vector<uint64_t> keep_for_size(int width, int height) {
+  Config::load_all();
+  mt_scan_params p;
+  if (mtgpu_params_from_config(&p, width, height, Config::mv_threshold_sq(), Config::block_size(), Config::block_shift(),
+                               Config::vectors_needed(), Config::clusters_needed(), Config::vertical_mask()) != MT_OK)
+    throw std::runtime_error(mtgpu_last_error());
+  std::vector<uint64_t> words;
+  std::string err;
+  if (!load_keep(g_keep_path, p.grid_w, p.grid_h, words, err)) throw std::runtime_error("--keep: " + err);
+  return words;
+}
+
+static unsigned long long ignored_cells(const std::vector<uint64_t> &keep, int width, int height) {
+  mt_scan_params p;
+  if (mtgpu_params_from_config(&p, width, height, Config::mv_threshold_sq(), Config::block_size(), Config::block_shift(),
+                               Config::vectors_needed(), Config::clusters_needed(), Config::vertical_mask()) != MT_OK)
+    return 0;
+  unsigned long long kept = 0;
+  for (uint64_t w : keep) kept += (unsigned long long)__builtin_popcountll(w);
+  return (unsigned long long)p.grid_w * (unsigned long long)p.grid_h - kept;
+}
+
+static void print_job(const std::string &input, const PipelineResult &r, const std::vector<mt_segment> &segs, int width = 0,
+                      int height = 0) {
   std::printf("{\"input\": \"%s\", \"chunks\": %d, \"threads\": %d, \"frames_scanned\": %llu, \"motion_frames\": %zu, \"n_timestamps\": %llu, "
               "\"do_cut\": %d, \"time_removed\": %.17g, \"saved_pct\": %.17g, \"seek_us\": %ld, "
               "\"decode_us\": %ld, \"analyze_us\": %ld, \"init_us\": %ld, \"scan_wall_us\": %ld, \"scan_work_us\": %ld, "
@@ -81,6 +111,7 @@ static void print_job(const std::string &input, const PipelineResult &r, const s
   for (size_t i = 0; i < segs.size(); ++i)
     std::printf("%s[%.17g, %.17g]", i ? ", " : "", segs[i].start, segs[i].end);
   std::printf("]");
+  if (!g_keep_path.empty()) std::printf(", \"ignored_cells\": %llu", ignored_cells(r.keep, width, height));
   if (g_print_ts) {
     std::vector<double> ts = r.timestamps;
     std::sort(ts.begin(), ts.end());
@@ -132,6 +163,10 @@ int main(int argc, char **argv) {
       }
     }
     else if (!std::strcmp(argv[i], "--repeat") && i + 1 < argc) repeat = std::atol(argv[++i]);
+    else if (!std::strcmp(argv[i], "--keep")) {
+      if (i + 1 >= argc) { std::fprintf(stderr, "error: --keep takes the path of a .mtkeep file\n"); return 2; }
+      g_keep_path = argv[++i];
+    }
     else files.push_back(argv[i]);
   }
   // --streams 0 / --threads 0: sized from the CPU budget, the devices and the number of videos (default_batch_sizing,
@@ -157,12 +192,13 @@ int main(int argc, char **argv) {
     if (files.size() == 1) {
       MtmvFile file(files[0]);
       PipelineResult r;
+      if (!g_keep_path.empty()) r.keep = keep_for_size((int)file.hdr->width, (int)file.hdr->height);
       int rc = run_scan_pipeline([&]() -> std::unique_ptr<FrameSource> {
         if (repeat > 1) return std::unique_ptr<FrameSource>(new RepeatSource(file, (uint64_t)repeat));
         return std::unique_ptr<FrameSource>(new MtmvSource(file));
       }, threads, r);
       if (rc != 0) { std::fprintf(stderr, "error: %s\n", r.error.c_str()); return 1; }
-      print_job(files[0], r, r.segments);
+      print_job(files[0], r, r.segments, (int)file.hdr->width, (int)file.hdr->height);
       return 0;
     }
     // batch: mmaps are shared by the workers of a stream and kept until the end
@@ -176,13 +212,29 @@ int main(int argc, char **argv) {
         return std::unique_ptr<FrameSource>(new MtmvSource(*f));
       };
     };
+    auto size_of = [&](const std::string &path, int &w, int &h) {
+      std::lock_guard<std::mutex> l(mm);
+      const auto it = open_files.find(path);
+      w = it == open_files.end() ? 0 : (int)it->second->hdr->width;
+      h = it == open_files.end() ? 0 : (int)it->second->hdr->height;
+    };
+    auto keep_for = [&](const std::string &path) -> std::vector<uint64_t> {
+      if (g_keep_path.empty()) return {};
+      int w = 0, h = 0;
+      size_of(path, w, h);
+      return keep_for_size(w, h);
+    };
     JobQueue jobs;
     std::vector<std::string> errors;
     int failed = 0;
     BatchSummary sum;
-    std::thread producer([&] { failed = process_batch(files, outdir, streams, threads, open_source, jobs, &errors, &sum); });
+    std::thread producer([&] { failed = process_batch(files, outdir, streams, threads, open_source, jobs, &errors, &sum, keep_for); });
     ScanJob job;                                   // the single consumer (batch_processor.cpp:138-150)
-    while (jobs.pop(job)) print_job(job.input_path, job.result, job.segments);
+    while (jobs.pop(job)) {
+      int w = 0, h = 0;
+      size_of(job.input_path, w, h);
+      print_job(job.input_path, job.result, job.segments, w, h);
+    }
     producer.join();
     if (g_summary) {
       const Resources &h = sum.held;

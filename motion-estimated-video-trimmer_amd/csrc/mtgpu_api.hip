@@ -1773,9 +1773,13 @@ int zones_plan(const mt_scan_params &p, int lds_max, mtgpu_zones_plan *out) {
 }
 
 // The masked scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
+// own_plan_ws: the caller's own block for the work list (a pipe's batch; ctx_plan_ws_bytes(n_frames) bytes, 256-byte
+// aligned) — the launch then takes NOTHING from the context's scratch ring — and the pipe form of the launch: one plane,
+// no clear kernel, outputs stored at system scope when `outputs_in_host_memory`.  nullptr: the ring, the stream form.
 int zones_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
              const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, const uint64_t *d_keep,
-             uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_centres_all, hipStream_t st) {
+             uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_centres_all, hipStream_t st, void *own_plan_ws = nullptr,
+             int outputs_in_host_memory = 0) {
   mtgpu_zones_plan zp;
   int rc = zones_plan(c->params, c->lds_max, &zp);
   if (rc != MT_OK) return rc;
@@ -1804,9 +1808,16 @@ int zones_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records,
   L.ev_planned = nullptr;
   void *scratch = nullptr;
   int slot = -1;
-  rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-  if (rc != MT_OK) return rc;
-  L.plan_ws = scratch;
+  if (own_plan_ws) {
+    L.pipe = 1;
+    L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
+    L.sys_centres = (d_centres && outputs_in_host_memory) ? 1 : 0;
+    L.plan_ws = own_plan_ws;
+  } else {
+    rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
+    if (rc != MT_OK) return rc;
+    L.plan_ws = scratch;
+  }
   hipError_t e = hipSuccess;
   if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
     mtgpu_ctx::Profile &pf = c->prof;
@@ -1825,12 +1836,32 @@ int zones_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records,
   } else {
     e = mtgpu::launch_zone_scan(L);
   }
-  scratch_release(c, slot, st);
+  if (slot >= 0) scratch_release(c, slot, st);
   if (e != hipSuccess) return hip_fail(e, "zone scan launch");
   return MT_OK;
 }
 
 }  // namespace
+
+namespace mtgpu {
+int ctx_zones_keep_words(const mtgpu_ctx *c, uint64_t *words) {
+  mtgpu_zones_plan zp;
+  const int rc = zones_plan(c->params, c->lds_max, &zp);
+  if (rc != MT_OK) return rc;
+  *words = (uint64_t)zp.keep_words_per_stream;
+  return MT_OK;
+}
+int ctx_launch_zones(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
+                     uint32_t n_frames, const uint64_t *d_keep, uint8_t *d_flags, uint32_t *d_centres, hipStream_t st, int rec_bytes,
+                     int outputs_in_host_memory, void *plan_ws, size_t plan_ws_bytes) {
+  if (n_frames == 0) return MT_OK;
+  if (!d_keep) return fail(MT_ERR_INVALID, "masked pipe scan without a keep plane");
+  if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
+    return fail(MT_ERR_INVALID, "masked pipe scan: the batch's work-list block is missing, misaligned or too small");
+  return zones_on(c, d_rec, rec_bytes, n_records, 0, d_off, d_sd, n_frames, nullptr, 1, d_keep, d_flags, d_centres, nullptr, st,
+                  plan_ws, outputs_in_host_memory ? 1 : 0);
+}
+}  // namespace mtgpu
 
 extern "C" {
 

@@ -100,6 +100,13 @@ struct mtgpu_pipe {
   bool inject_grow_fail = false; // MTGPU_INJECT_GROW_FAIL=1 (tests): growing a batch for an oversize frame fails
   std::atomic<uint64_t> pin_us{0};   // time spent page-locking staging blocks (creation + first uses + growth); add_frame
                                      // grows a batch without the pipe lock, get_stats reads under it: atomic
+  // mtgpu_pipe_set_keep (include/mtgpu_zones.h): ONE keep plane in device memory, owned by the pipe.  `masked`: every
+  // submit runs the masked scan (ctx_launch_zones) instead of the plain one.  Both change only while no batch is being
+  // filled or in flight.  The plane, once allocated, lives until the pipe is destroyed: dropping the mask only clears
+  // `masked`, so a retired batch (state 4) whose kernel may still run never reads freed memory.
+  uint64_t *d_keep = nullptr;
+  uint64_t keep_words = 0;
+  bool masked = false;
   std::vector<mtgpu_batch *> bufs;
   std::deque<mtgpu_batch *> inflight;
   std::mutex mu;
@@ -300,6 +307,7 @@ void mtgpu_pipe_destroy(mtgpu_pipe *p) {
   if (!p) return;
   (void)hipSetDevice(mtgpu::ctx_device(p->ctx));
   for (mtgpu_batch *b : p->bufs) free_batch(b);      // drains every batch's stream first
+  if (p->d_keep) (void)hipFree(p->d_keep);
   delete p;
 }
 
@@ -384,8 +392,12 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
       rc = fail(MT_ERR_DEVICE, "injected submit failure (MTGPU_INJECT_SUBMIT_FAIL)");
       goto bad;
     }
-    rc = mtgpu::ctx_launch_scan(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, b->d_flags, st,
-                                b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes, b->d_centres);
+    if (p->masked)   // mtgpu_pipe_set_keep: the masked scan, its work list in the batch's own block like the plain one's
+      rc = mtgpu::ctx_launch_zones(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->d_keep, b->d_flags,
+                                   b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
+    else
+      rc = mtgpu::ctx_launch_scan(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, b->d_flags, st,
+                                  b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes, b->d_centres);
     if (rc != MT_OK) goto bad;
     if (!b->zero_copy) {
       PIPE_TRY(hipMemcpyAsync(b->h_flags, b->d_flags, b->n_frames, hipMemcpyDeviceToHost, st));
@@ -481,6 +493,40 @@ int mtgpu_pipe_get_stats(mtgpu_pipe *p, mtgpu_pipe_stats *out) {
   out->layout = (p->rec_bytes == MT_MV_BYTES ? MT_LAYOUT_AOS40 : MT_LAYOUT_COMPACT8) | (p->zero_copy ? MT_LAYOUT_ZERO_COPY : 0) |
                 (p->centres ? MT_LAYOUT_CENTRES : 0);
   return MT_OK;
+}
+
+int mtgpu_pipe_set_keep(mtgpu_pipe *p, const uint64_t *keep) {
+  if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
+  std::lock_guard<std::mutex> lock(p->mu);
+  for (const mtgpu_batch *b : p->bufs)
+    if (b->state == 1 || b->state == 2)
+      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the keep mask",
+                  b->state == 1 ? "being filled" : "in flight");
+  if (!keep) { p->masked = false; return MT_OK; }           // the plain scan again; the plane stays allocated (see mtgpu_pipe)
+  uint64_t words = 0;
+  int rc = mtgpu::ctx_zones_keep_words(p->ctx, &words);      // MT_ERR_UNSUPPORTED, the grid named: nothing changes
+  if (rc != MT_OK) return rc;
+  hipError_t e = use_device(mtgpu::ctx_device(p->ctx));
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  if (!p->d_keep) {
+    void *d = nullptr;
+    if ((e = hipMalloc(&d, sizeof(uint64_t) * (size_t)words)) != hipSuccess) return hip_fail(e, "hipMalloc (keep plane)");
+    p->d_keep = static_cast<uint64_t *>(d);
+    p->keep_words = words;
+  }
+  // synchronous: no kernel of this pipe is queued or running (no batch in state 2), the next submit finds the plane complete
+  if ((e = hipMemcpy(p->d_keep, keep, sizeof(uint64_t) * (size_t)words, hipMemcpyHostToDevice)) != hipSuccess) {
+    p->masked = false;                                       // the plane's contents are unknown: never scan with it
+    return hip_fail(e, "hipMemcpy (keep plane)");
+  }
+  p->masked = true;
+  return MT_OK;
+}
+
+int mtgpu_pipe_has_keep(const mtgpu_pipe *p) {
+  if (!p) return -1;
+  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
+  return p->masked ? 1 : 0;
 }
 
 int mtgpu_pipe_release(mtgpu_pipe *p, mtgpu_batch *b) {

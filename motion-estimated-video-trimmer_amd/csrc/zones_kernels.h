@@ -46,11 +46,19 @@ struct ZoneLaunch {
   const unsigned char *has_sd;            // n_frames or null
   unsigned int n_frames;
   int rec_bytes;                          // 40 or 8
-  const unsigned long long *stream_off;   // n_streams + 1
+  const unsigned long long *stream_off;   // n_streams + 1 (pipe form: not read)
   unsigned int n_streams;
-  const unsigned long long *keep;         // n_streams x gh x W
-  unsigned char *flags;                   // n_frames bytes, device memory, or null
-  unsigned int *centres, *centres_all;    // n_frames words each, device memory, or null
+  const unsigned long long *keep;         // n_streams x gh x W, device memory (pipe form: one plane)
+  unsigned char *flags;                   // n_frames bytes, device memory (pipe form: or pinned host memory), or null
+  unsigned int *centres, *centres_all;    // n_frames words each, as flags, or null (pipe form: centres_all is null)
+  // The pipe form (pipe.hip's staging batches): ONE plane serves every frame — no stream lookup; no clear kernel —
+  // launch_plan gets the outputs and answers the frames without side data; the results are stored at system scope where
+  // sys_flags / sys_centres say that the array is not device memory (a zero-copy batch's pinned block).  There is no
+  // centres_all in the pipe: the pinned block has no third result array, and "what did the zones remove" is the study
+  // tool's question (mtgpu_scan_zones_device, python -m mvtrim_amd.zones).  0: the form of mtgpu_scan_zones_device —
+  // plain stores, sys_* must be 0.
+  int pipe = 0;
+  int sys_flags = 0, sys_centres = 0;
   ZoneK k;
   int lds_bytes;
   int lds_max;                            // device limit of dynamic LDS per workgroup
@@ -60,7 +68,8 @@ struct ZoneLaunch {
   hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the zone kernel; else nullptr
 };
 
-// Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.
+// Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.  Pipe form: no
+// zero fill — the planner answers the frames without side data.
 hipError_t launch_zone_scan(const ZoneLaunch &L);
 
 }  // namespace mtgpu

@@ -20,6 +20,13 @@
 //   Every output element has one writer after the clear: lane 0 of the frame's workgroup, plain vector stores, no global
 //   atomics.
 //
+// The pipe form (template argument PIPE; ZoneLaunch::pipe) serves a staging batch of pipe.hip:
+//     stream      none: a pipe feeds one recording, plane 0 serves every frame — the search and its loads are compiled out.
+//     outputs     flags / centres may be a zero-copy batch's pinned block: lane 0 stores them at system scope when the
+//                 launch says so (store_flag / store_centres, the scan's helpers); device memory keeps the plain store.
+//     no clear    launch_plan is handed the outputs and answers the frames without side data itself, as in launch_scan:
+//                 planning + one kernel.  No centres_all.
+//
 // Carries its own copies of the few record helpers (as scalar_kernels.hip, sweep_kernels.hip and activity_kernels.hip
 // do) and calls launch_plan as it is: no other translation unit's device code changes.
 #if !defined(__HIP_DEVICE_COMPILE__) || defined(__gfx950__)
@@ -76,6 +83,19 @@ __device__ __forceinline__ WorkItem load_item(const WorkItem *__restrict__ work,
   it.f = raw[4];
   it.pad[0] = it.pad[1] = it.pad[2] = 0u;
   return it;
+}
+
+// The frame's result byte and its centre count in the pipe form: the scan's store_flag / store_centres
+// (scan_kernels.hip).  `sys`: the destination is pinned host memory (a zero-copy staging block) — a system-scope
+// write-through store, so that no cache between this workgroup and the host may hold the line; device memory takes the
+// plain store.
+__device__ __forceinline__ void store_flag(unsigned char *flags, unsigned int f, unsigned char v, int sys) {
+  if (sys) __hip_atomic_store(&flags[f], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  else flags[f] = v;
+}
+__device__ __forceinline__ void store_centres(unsigned int *centres, unsigned int f, unsigned int v, int sys) {
+  if (sys) __hip_atomic_store(&centres[f], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  else centres[f] = v;
 }
 
 // One record (src/motion_scanner.cpp:246-268): threshold, cell, bounds — the scan's keep_and_cell — then one vote.
@@ -258,11 +278,15 @@ __global__ __launch_bounds__(256) void zones_clear_kernel(unsigned char *__restr
 // Waves per SIMD: a workgroup is 16 waves, four per SIMD.  A 1080p workgroup takes about 36 KB of LDS, so the lane
 // limit (2048 per CU), not LDS, decides: two workgroups per CU, eight waves per SIMD and so at most 64 VGPRs.  The 4K
 // workgroup (about 141 KB) sits alone on its CU and loses nothing by the same limit.
-template <int BLOCK, int UNROLL, int REC>
+// PIPE: the form for a pipe's staging batch — stream_off / n_streams / centres_all are not read (null / 1 / null), plane 0
+// of `keep` serves every frame, and the two results leave through store_flag / store_centres with sys_flags /
+// sys_centres.  !PIPE: sys_* are not read (0).
+template <int BLOCK, int UNROLL, int REC, bool PIPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void zones_frames_kernel(
     const unsigned char *__restrict__ mv, const WorkItem *__restrict__ work, unsigned int item0, unsigned int n_items, ZoneK k,
     const unsigned long long *__restrict__ stream_off, unsigned int n_streams, const unsigned long long *__restrict__ keep,
-    unsigned char *__restrict__ flags, unsigned int *__restrict__ centres, unsigned int *__restrict__ centres_all) {
+    unsigned char *__restrict__ flags, unsigned int *__restrict__ centres, unsigned int *__restrict__ centres_all, int sys_flags,
+    int sys_centres) {
   extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
   const unsigned int item = item0 + blockIdx.x;
   if (item >= n_items) return;
@@ -281,15 +305,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   // values: scalar code).  s == n_streams: the frame lies behind the last stream and keeps the zeros of the clear.
   const unsigned int f = __builtin_amdgcn_readfirstlane(me.f);
   unsigned int s = 0u;
-  {
+  if constexpr (!PIPE) {
     unsigned int lo = 0u, hi = n_streams;
     while (lo < hi) {
       const unsigned int mid = lo + ((hi - lo) >> 1);
       if (stream_off[mid + 1u] <= (unsigned long long)f) lo = mid + 1u; else hi = mid;
     }
     s = lo;
+    if (s >= n_streams) return;
   }
-  if (s >= n_streams) return;
 
   // ---- the keep words of the analysed rows, one contiguous block of the stream's plane.  The first word of every
   // lane is on its way while the tile is zeroed (1080p and 4K: there is no second one).
@@ -313,7 +337,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   }
   __syncthreads();
   // ---- the masks, then the centre counts: masked, and (one uniform branch) unmasked from the same tile
-  const bool want_all = centres_all != nullptr;
+  const bool want_all = !PIPE && centres_all != nullptr;
   row_masks<BLOCK>(tile, klds, kmask, want_all ? umask : nullptr, k, t0, t1, k.y_lo - 1, crows + 2);
   __syncthreads();
   count_centres<BLOCK>(kmask, &total[0], k, crows);
@@ -321,17 +345,22 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   __syncthreads();
   if (tid == 0) {
     const unsigned int c = total[0];
-    if (centres) centres[f] = c;
-    if (flags) flags[f] = (unsigned char)(c >= k.clust_need ? 1 : 0);
-    if (want_all) centres_all[f] = total[1];
+    if constexpr (PIPE) {
+      if (centres) store_centres(centres, f, c, sys_centres);
+      if (flags) store_flag(flags, f, (unsigned char)(c >= k.clust_need ? 1 : 0), sys_flags);
+    } else {
+      if (centres) centres[f] = c;
+      if (flags) flags[f] = (unsigned char)(c >= k.clust_need ? 1 : 0);
+      if (want_all) centres_all[f] = total[1];
+    }
   }
 }
 
 namespace {
 
-template <int REC>
+template <int REC, bool PIPE>
 hipError_t launch_frames(const ZoneLaunch &L) {
-  auto kern = zones_frames_kernel<kZoneBlock, kZoneUnroll, REC>;
+  auto kern = zones_frames_kernel<kZoneBlock, kZoneUnroll, REC, PIPE>;
   // Dynamic-LDS ceiling: set once per instantiation and device to the device maximum (scan_kernels.hip, launch_one)
   static std::atomic<unsigned long long> ready{0ull};
   const unsigned long long bit = 1ull << (L.device & 63);
@@ -346,7 +375,7 @@ hipError_t launch_frames(const ZoneLaunch &L) {
     const unsigned long long left = (unsigned long long)L.n_frames - i0;
     hipLaunchKernelGGL(kern, dim3((unsigned int)(left < chunk ? left : chunk)), dim3(kZoneBlock), L.lds_bytes, L.stream, L.mv,
                        work, (unsigned int)i0, L.n_frames, L.k, L.stream_off, L.n_streams, L.keep, L.flags, L.centres,
-                       L.centres_all);
+                       L.centres_all, L.sys_flags, L.sys_centres);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -359,12 +388,25 @@ hipError_t launch_zone_scan(const ZoneLaunch &L) {
   if (L.n_frames == 0) return hipSuccess;
   if (L.rec_bytes != 40 && L.rec_bytes != 8) return hipErrorInvalidValue;
   if (!L.flags && !L.centres && !L.centres_all) return hipErrorInvalidValue;
-  if (!L.frame_off || !L.stream_off || !L.keep || L.n_streams == 0 || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u ||
+  if (L.pipe ? (L.centres_all != nullptr) : (L.sys_flags != 0 || L.sys_centres != 0 || !L.stream_off || L.n_streams == 0))
+    return hipErrorInvalidValue;
+  if (!L.frame_off || !L.keep || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u ||
       L.rebase > L.n_records)
     return hipErrorInvalidValue;
   if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.lds_bytes > L.lds_max ||
       (size_t)L.lds_bytes < zone_lds_bytes(L.k.gw, L.k.R))
     return hipErrorInvalidValue;
+  if (L.pipe) {
+    // The planner is handed the outputs and answers every frame without side data itself (plan_scatter_kernel, at the
+    // outputs' scope), as in launch_scan: no clear kernel — planning + one kernel.
+    WorkItem *work = static_cast<WorkItem *>(L.plan_ws);
+    unsigned int *blk_cnt = reinterpret_cast<unsigned int *>(work + (size_t)L.n_frames + 1u);
+    hipError_t e = launch_plan(L.frame_off, L.has_sd, L.n_records, L.rebase, L.n_frames, L.flags, L.sys_flags, L.centres,
+                               L.sys_centres, work, blk_cnt, L.stream);
+    if (e != hipSuccess) return e;
+    if (L.ev_planned && (e = hipEventRecord(L.ev_planned, L.stream)) != hipSuccess) return e;
+    return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
+  }
   {
     const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
     hipLaunchKernelGGL(zones_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream,
@@ -379,7 +421,7 @@ hipError_t launch_zone_scan(const ZoneLaunch &L) {
                              L.stream);
   if (e != hipSuccess) return e;
   if (L.ev_planned && (e = hipEventRecord(L.ev_planned, L.stream)) != hipSuccess) return e;
-  return L.rec_bytes == 8 ? launch_frames<8>(L) : launch_frames<40>(L);
+  return L.rec_bytes == 8 ? launch_frames<8, false>(L) : launch_frames<40, false>(L);
 }
 
 }  // namespace mtgpu

@@ -844,6 +844,33 @@ class ScanPipe:
         except Exception:
             pass
 
+    def set_keep(self, keep):
+        """Ignore zones on the decode path (mtgpu_pipe_set_keep): from now on every batch of this pipe runs the masked
+        scan — on the analysed rows a cell is active iff votes >= vectors_needed (src/motion_scanner.cpp:282) AND its keep
+        bit is set.  keep: bool [grid_h, grid_w] (True = analysed), packed uint64 [grid_h, W] words (zones.pack_keep), or
+        None: drop the mask, the plain scan again.  Only while no batch is being filled or in flight (call drain()
+        first): otherwise MtgpuError(MT_ERR_BUSY) and nothing changes."""
+        if keep is None:
+            check(self._lib.mtgpu_pipe_set_keep(self._pipe, None))
+            return
+        p = self._scanner.params
+        gh, gw, W = p.grid_h, p.grid_w, (p.grid_w + 63) // 64
+        a = np.asarray(keep)
+        if a.dtype != np.uint64:
+            if a.shape != (gh, gw):
+                raise ValueError(f"keep has shape {a.shape}, not {(gh, gw)} (or packed uint64 {(gh, W)})")
+            from .zones import pack_keep
+            a = pack_keep(a)
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        if a.shape != (gh, W):
+            raise ValueError(f"packed keep has shape {a.shape}, not {(gh, W)}")
+        check(self._lib.mtgpu_pipe_set_keep(self._pipe, _ptr(a)))
+
+    @property
+    def has_keep(self) -> bool:
+        """True while the pipe's submits run the masked scan (mtgpu_pipe_has_keep)."""
+        return self._lib.mtgpu_pipe_has_keep(self._pipe) == 1
+
     def _collect_one(self):
         b, fl, pts, tags, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32()
         rc = self._lib.mtgpu_pipe_collect(self._pipe, C.byref(b), C.byref(fl), C.byref(pts), C.byref(tags),

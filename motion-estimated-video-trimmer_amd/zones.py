@@ -1,4 +1,4 @@
-"""`python -m mvtrim_amd.zones FILE [--ignore X0,Y0,X1,Y1]... [--ignore-busy SHARE] [--mask-npy PATH] [--save-mask PATH] [--json]`
+"""`python -m mvtrim_amd.zones FILE [--ignore X0,Y0,X1,Y1]... [--ignore-busy SHARE] [--mask-npy PATH] [--mask PATH.mtkeep] [--save-mask PATH] [--json]`
 
 Ignore zones: what the trimmer keeps of one recording when some grid cells are not analysed.  The reference can only
 mask full-width strips (VERTICAL_MASK, src/motion_scanner.cpp:237-238, 262); a keep mask removes single cells — a
@@ -7,7 +7,10 @@ burnt-in clock, a road at one side, a neighbour's window.  FILE is the JSON that
 
 The mask is the intersection of what the options give: --ignore rectangles (pixels by default, see --unit; a rectangle
 ignores every cell its blocks intersect), --ignore-busy SHARE (one activity map first: every cell that was a centre in
-more than SHARE of the frames with side data is ignored) and --mask-npy (a [grid_h, grid_w] array, non-zero = keep).
+more than SHARE of the frames with side data is ignored), --mask-npy (a [grid_h, grid_w] array, non-zero = keep) and
+--mask (a `.mtkeep` text file).  --save-mask PATH.mtkeep writes the mask used in the form `mtgpu_scan_file --keep` and
+ScanPipe.set_keep(load_keep(PATH)) take: `zones --ignore-busy 0.5 --save-mask cam3.mtkeep`, then
+`mtgpu_scan_file --keep cam3.mtkeep` trims with it.
 One masked scan (MotionScanner.scan_zones_device) returns every frame's centre count with and without the zones from one
 read of the records; the existing merge runs on both.  Printed: frames kept and segments without and with the zones,
 and the ignored share of the analysed cells.
@@ -15,7 +18,7 @@ and the ignored share of the analysed cells.
 Width, height and duration come from a `.mtmv` header or from --width / --height / --duration.  Everything but the mask
 arithmetic is computed by libmtgpu; without a usable device the command fails, there is no CPU path.
 
-The helpers below (pack_keep, unpack_keep, keep_from_rects, keep_from_activity) are pure numpy.
+The helpers below (pack_keep, unpack_keep, save_keep, load_keep, keep_from_rects, keep_from_activity) are pure numpy.
 """
 import argparse
 import json
@@ -54,6 +57,56 @@ def unpack_keep(words, gw):
         raise ValueError(f"words has shape {words.shape}, want [grid_h, {(gw + 63) // 64}]")
     x = np.arange(gw)
     return ((words[:, x >> 6] >> (x & 63).astype(np.uint64)) & np.uint64(1)).astype(bool)
+
+
+MTKEEP_MAGIC = "mtkeep 1"
+
+
+def save_keep(path, keep):
+    """Write a bool [grid_h, grid_w] mask (True = analysed) as a `.mtkeep` text file: line 1 `mtkeep 1`, line 2
+    `<grid_w> <grid_h>`, then grid_h lines of grid_w characters, `1` analysed, `0` ignored.  What mtgpu_scan_file --keep
+    and load_keep read; plain text, so that a mask can be edited by hand."""
+    keep = np.asarray(keep)
+    if keep.ndim != 2 or keep.shape[0] < 1 or keep.shape[1] < 1:
+        raise ValueError(f"keep has shape {keep.shape}, want [grid_h, grid_w]")
+    gh, gw = keep.shape
+    rows = ["".join("1" if v else "0" for v in row) for row in (keep != 0)]
+    with open(path, "w", encoding="ascii", newline="\n") as f:
+        f.write(f"{MTKEEP_MAGIC}\n{gw} {gh}\n" + "\n".join(rows) + "\n")
+
+
+def load_keep(path, grid=None):
+    """Read a `.mtkeep` file -> bool [grid_h, grid_w].  grid: (grid_w, grid_h) the file must match, or None.  ValueError
+    names the line of anything else: another first line, a grid that does not match, a short file, a row of another
+    length, a character other than 0 / 1, lines behind the last row."""
+    with open(path, "r", encoding="ascii", errors="replace", newline="") as f:
+        lines = f.read().split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()                                        # the final newline
+    lines = [ln[:-1] if ln.endswith("\r") else ln for ln in lines]
+    if not lines or lines[0] != MTKEEP_MAGIC:
+        raise ValueError(f"{path}: line 1: want '{MTKEEP_MAGIC}'")
+    dims = lines[1].split(" ") if len(lines) > 1 else []
+    if len(dims) != 2 or not all(d.isascii() and d.isdigit() and len(d) <= 6 for d in dims) or int(dims[0]) < 1 or int(dims[1]) < 1:
+        raise ValueError(f"{path}: line 2: want '<grid_w> <grid_h>'")
+    gw, gh = int(dims[0]), int(dims[1])
+    if grid is not None and (gw, gh) != (int(grid[0]), int(grid[1])):
+        raise ValueError(f"{path}: line 2: the mask is for a {gw}x{gh} grid, this one is {int(grid[0])}x{int(grid[1])}")
+    keep = np.zeros((gh, gw), dtype=bool)
+    for y in range(gh):
+        n = 3 + y
+        if n > len(lines):
+            raise ValueError(f"{path}: line {n}: the file ends after {y} of {gh} rows")
+        row = lines[n - 1]
+        if len(row) != gw:
+            raise ValueError(f"{path}: line {n}: {len(row)} characters, want {gw}")
+        for x, ch in enumerate(row):
+            if ch not in "01":
+                raise ValueError(f"{path}: line {n}: character {x + 1} is neither 0 nor 1")
+        keep[y] = np.frombuffer(row.encode("ascii"), dtype=np.uint8) == ord("1")
+    if len(lines) > 2 + gh:
+        raise ValueError(f"{path}: line {3 + gh}: text behind the last of {gh} rows")
+    return keep
 
 
 def keep_from_rects(params, rects, unit="px", size=None):
@@ -144,7 +197,9 @@ def parser():
     ap.add_argument("--ignore-busy", type=_share, metavar="SHARE",
                     help="ignore every cell that is a centre in more than SHARE of the frames with side data (one activity map first)")
     ap.add_argument("--mask-npy", metavar="PATH", help="a [grid_h, grid_w] array, non-zero = keep")
-    ap.add_argument("--save-mask", metavar="PATH", help="write the mask used as a bool [grid_h, grid_w] .npy")
+    ap.add_argument("--mask", metavar="PATH.mtkeep", help="a .mtkeep text mask (save_keep / --save-mask), 1 = keep")
+    ap.add_argument("--save-mask", metavar="PATH", help="write the mask used: a .mtkeep text file when PATH ends in .mtkeep "
+                    "(what mtgpu_scan_file --keep reads), else a bool [grid_h, grid_w] .npy")
     ap.add_argument("--width", type=int)
     ap.add_argument("--height", type=int)
     ap.add_argument("--duration", type=float, help="seconds")
@@ -223,6 +278,8 @@ def main(argv=None):
         batch, pts, hdr = tune.load(path)
         path = a.mask_npy
         given = None if path is None else np.load(path)
+        path = a.mask
+        given_text = None if path is None else load_keep(path)
     except (OSError, ValueError, KeyError) as e:
         print(f"zones: cannot read {path}: {e}", file=sys.stderr)
         return 1
@@ -239,6 +296,10 @@ def main(argv=None):
         if given.shape != keep.shape:
             ap.error(f"--mask-npy: shape {given.shape}, the grid is {keep.shape}")
         keep &= given != 0
+    if given_text is not None:
+        if given_text.shape != keep.shape:
+            ap.error(f"--mask: the mask is for a {given_text.shape[1]}x{given_text.shape[0]} grid, this one is {keep.shape[1]}x{keep.shape[0]}")
+        keep &= given_text
     mp = MergeParams(duration=float(duration), max_gap_sec=a.max_gap_sec, padding_sec=a.padding_sec,
                      min_savings_pct=a.min_savings_pct)
     try:
@@ -248,7 +309,10 @@ def main(argv=None):
         print(f"zones: {e}", file=sys.stderr)
         return 1
     if a.save_mask:
-        np.save(a.save_mask, keep)
+        if a.save_mask.endswith(".mtkeep"):
+            save_keep(a.save_mask, keep)
+        else:
+            np.save(a.save_mask, keep)
     share = ignored_share(keep, params.vertical_margin)
     if a.json:
         print(json.dumps({"file": a.file, "width": width, "height": height, "grid_w": params.grid_w, "grid_h": params.grid_h,
