@@ -23,8 +23,9 @@
 //   Integer adds commute: the maps are bit-reproducible whatever the run length, the launch grid or the order in which
 //   workgroups arrive.  That is why this is integer atomics and not a slab reducer: nothing has to be ordered.
 //
-// Carries its own copies of the few record helpers (as scalar_kernels.hip and sweep_kernels.hip do) and calls
-// launch_plan as it is: no other translation unit's device code changes.
+// The record loads, the streamers, the vote, the row masks and the centre test of a word are those of record_stream.h,
+// shared with sweep_kernels.hip and zones_kernels.hip and instantiated here with this kernel's functors; the launch
+// helpers are those of scan_kernels.h.  A change there must leave this file's device assembly as it was.
 #if !defined(__HIP_DEVICE_COMPILE__) || defined(__gfx950__)
 #else
 #error "activity_kernels.hip is written for gfx950 only (wave64, 160 KB LDS)"
@@ -35,182 +36,11 @@
 #include <atomic>
 
 #include "activity_kernels.h"
+#include "record_stream.h"
 
 namespace mtgpu {
 
 namespace {
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x2 u32x2_a8 __attribute__((aligned(8)));
-typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
-typedef u32x4 u32x4_a16 __attribute__((aligned(16)));
-
-// The record forms of the scan (scan_kernels.hip): bytes 4..15 of a 40-byte record — d.x = w | h<<8 | src_x<<16,
-// d.y = src_y | dst_x<<16, d.z = dst_y | pad<<16 — or a compact record, src_x | src_y<<16, dst_x | dst_y<<16.  All with
-// the streaming (nt) hint: every record is read once.
-__device__ __forceinline__ u32x3 load_fields(const unsigned char *rec) {
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4 *>(rec + 4));
-}
-__device__ __forceinline__ u32x2 load_compact(const unsigned char *rec) {
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x2_a8 *>(rec));
-}
-__device__ __forceinline__ u32x4 load_pair(const unsigned char *two_records) {   // 16-byte aligned
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x4_a16 *>(two_records));
-}
-
-struct MvFields { int src_x, src_y, dst_x, dst_y; };
-
-__device__ __forceinline__ MvFields decode(const u32x3 d) {
-  return {(int)d.x >> 16, (int)(short)(d.y & 0xffffu), (int)d.y >> 16, (int)(short)(d.z & 0xffffu)};
-}
-__device__ __forceinline__ MvFields decode(const u32x2 d) {
-  return {(int)(short)(d.x & 0xffffu), (int)d.x >> 16, (int)(short)(d.y & 0xffffu), (int)d.y >> 16};
-}
-
-// An entry of the work list with one 32-byte load (workgroup-uniform address: a scalar load), as the scan reads it.
-__device__ __forceinline__ WorkItem load_item(const WorkItem *__restrict__ work, unsigned long long wi) {
-  typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
-  const u32x8 raw = *reinterpret_cast<const u32x8 *>(work + wi);
-  WorkItem it;
-  it.r0 = (unsigned long long)raw[0] | ((unsigned long long)raw[1] << 32);
-  it.r1 = (unsigned long long)raw[2] | ((unsigned long long)raw[3] << 32);
-  it.f = raw[4];
-  it.pad[0] = it.pad[1] = it.pad[2] = 0u;
-  return it;
-}
-
-// One record (src/motion_scanner.cpp:246-268): threshold, cell, bounds — the scan's keep_and_cell — then one vote.
-// t0: the grid row of tile row 0.  gy in [y_lo, y_hi) and t0 <= y_lo: the index stays inside the tile.
-__device__ __forceinline__ void vote(const MvFields m, const ActK &k, int t0, unsigned int *tile) {
-  const unsigned int dx = (unsigned int)(m.dst_x - m.src_x);   // |dx| <= 65535
-  const unsigned int dy = (unsigned int)(m.dst_y - m.src_y);
-  // dx*dx < 2^32 exactly; the sum needs 34 bits
-  const unsigned long long mag = (unsigned long long)(dx * dx) + (unsigned long long)(dy * dy);
-  const int gx = m.dst_x >> k.shift, gy = m.dst_y >> k.shift;
-  // 0 <= gx < gw and y_lo <= gy < y_hi (:262) as two unsigned compares (y_hi >= y_lo by construction)
-  const bool in = ((unsigned int)gx < (unsigned int)k.gw) & ((unsigned int)(gy - k.y_lo) < (unsigned int)(k.y_hi - k.y_lo));
-  if (in && mag >= k.thr) atomicAdd(&tile[(unsigned int)((gy - t0) * k.gw + gx)], 1u);
-}
-
-__device__ __forceinline__ void vote_pair(const u32x4 d, const ActK &k, int t0, unsigned int *tile) {
-  vote(decode((u32x2){d.x, d.y}), k, t0, tile);
-  vote(decode((u32x2){d.z, d.w}), k, t0, tile);
-}
-
-// 40-byte records [base, base + 40 n): the sweep's stream_mv40 — up to 15 head records so that the steps start on a
-// 128-byte line (40 h = -start mod 128 has a solution h < 16 whenever the start is 8-byte aligned), then lane i of a
-// step takes record i with UNROLL independent loads in flight, then the rest with every load issued before the
-// first vote.
-template <int BLOCK, int UNROLL>
-__device__ __forceinline__ void stream_mv40(const unsigned char *base, unsigned long long n, const ActK &k, int t0,
-                                            unsigned int *tile) {
-  const int tid = threadIdx.x;
-  const unsigned int r = (unsigned int)((uintptr_t)base & 127u);
-  if ((r & 7u) == 0u) {
-    unsigned long long h = (unsigned long long)((13u * ((16u - (r >> 3)) & 15u)) & 15u);
-    h = h < n ? h : n;
-    if ((unsigned long long)tid < h) vote(decode(load_fields(base + (unsigned long long)tid * 40ull)), k, t0, tile);
-    base += h * 40ull;
-    n -= h;
-  }
-  unsigned long long i = tid;
-  constexpr unsigned long long STEP = (unsigned long long)UNROLL * BLOCK;
-  constexpr unsigned long long LAST = (unsigned long long)(UNROLL - 1) * BLOCK;
-  for (; i + LAST < n; i += STEP) {
-    u32x3 d[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) d[u] = load_fields(base + (i + (unsigned long long)u * BLOCK) * 40ull);
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) vote(decode(d[u]), k, t0, tile);
-  }
-  if (i < n) {
-    u32x3 d[UNROLL];
-    bool ok[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const unsigned long long q = i + (unsigned long long)u * BLOCK;
-      ok[u] = q < n;
-      if (ok[u]) d[u] = load_fields(base + q * 40ull);
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (ok[u]) vote(decode(d[u]), k, t0, tile);
-  }
-}
-
-// Compact records [base, base + 8 n), 8-byte aligned: the sweep's stream_compact — up to 15 head records one per lane
-// so that the 16-byte pair stream starts on a 128-byte line, lane 0 takes an odd last record.
-template <int BLOCK, int UNROLL>
-__device__ __forceinline__ void stream_compact(const unsigned char *base, unsigned long long n, const ActK &k, int t0,
-                                               unsigned int *tile) {
-  const int tid = threadIdx.x;
-  constexpr unsigned long long STEP = (unsigned long long)UNROLL * BLOCK;
-  constexpr unsigned long long LAST = (unsigned long long)(UNROLL - 1) * BLOCK;
-  unsigned long long head = ((0ull - (unsigned long long)(uintptr_t)base) & 127ull) >> 3;
-  head = head < n ? head : n;
-  const unsigned char *pbase = base + head * 8ull;
-  const unsigned long long np = (n - head) >> 1;            // pairs
-  if ((unsigned long long)tid < head) vote(decode(load_compact(base + (unsigned long long)tid * 8ull)), k, t0, tile);
-  if (tid == 0 && ((n - head) & 1ull) != 0ull) vote(decode(load_compact(base + (n - 1ull) * 8ull)), k, t0, tile);
-  unsigned long long p = tid;
-  for (; p + LAST < np; p += STEP) {
-    u32x4 d[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) d[u] = load_pair(pbase + (p + (unsigned long long)u * BLOCK) * 16ull);
-    __builtin_amdgcn_sched_barrier(0);   // every load of the step is issued before the first one is consumed
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) vote_pair(d[u], k, t0, tile);
-  }
-  if (p < np) {
-    u32x4 d[UNROLL];
-    bool ok[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const unsigned long long q = p + (unsigned long long)u * BLOCK;
-      ok[u] = q < np;
-      if (ok[u]) d[u] = load_pair(pbase + q * 16ull);
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (ok[u]) vote_pair(d[u], k, t0, tile);
-  }
-}
-
-// ---- the 64-bit masks of the active cells of mask rows [0, nrows): mask row j <-> grid row g0 + j.  Rows outside the
-// tracked rows [t0, t1) and cells outside the grid are inactive, with vectors_needed == 0 too (:282 with
-// vectors_needed == 0: every cell OF THE GRID is active).  Four lanes per (mask row, word), 16 cells each, as the
-// sweep's row_masks: the cells are read in a rotated order (the 64 lanes of a wave hit 64 different LDS banks per step).
-template <int BLOCK>
-__device__ __forceinline__ void row_masks(const unsigned int *cnt, unsigned long long *mask, const ActK &k, int t0, int t1,
-                                          int g0, int nrows) {
-  const int tid = threadIdx.x, W = k.W;
-  const int lane = tid & 63;
-  const int sub = lane & 3, rot = (lane >> 2) & 15;
-  const int ntask = nrows * W * 4;
-  for (int t0q = 0; t0q < ntask; t0q += BLOCK) {               // uniform trip count: shuffles below
-    const int tk = t0q + tid;
-    const int tw = tk >> 2;
-    const int j = tw / W, w = tw - j * W;
-    const int g = g0 + j;
-    const int ncell = min(64, k.gw - w * 64) - sub * 16;       // cells of this lane's quarter inside the grid
-    const bool live = tk < ntask && g >= t0 && g < t1 && ncell > 0;
-    const int last = min(ncell, 16) - 1;
-    unsigned int q = 0u;                                       // bit u: the cell read u-th, i.e. cell (u + rot) & 15
-    if (live) {
-      const unsigned int *row = cnt + (size_t)(g - t0) * k.gw + w * 64 + sub * 16;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) q |= (row[min((u + rot) & 15, last)] >= k.vec_need ? 1u : 0u) << u;   // always inside the row
-    }
-    const unsigned int valid = live ? ((2u << last) - 1u) : 0u;               // bits 0 .. last
-    q = ((q << rot) | (q >> (16 - rot))) & 0xffffu & valid;    // rotate the 16 bits into cell order
-    unsigned long long m = (unsigned long long)q << (sub * 16);
-    m |= __shfl_xor(m, 1);
-    m |= __shfl_xor(m, 2);
-    if (tk < ntask && sub == 0) mask[(size_t)j * W + w] = m;
-  }
-}
 
 // ---- the centres (:277-293), one task per (analysed row, word): analysed row r <-> mask row r + 1; x in [1, gw-2]
 // (:280); neighbours across word and row boundaries; outside the grid: inactive.  The sweep's count_centres, which
@@ -222,22 +52,7 @@ __device__ __forceinline__ void centre_masks(const unsigned long long *amask, un
   const int ntask = crows * W;
   for (int tk = threadIdx.x; tk < ntask; tk += BLOCK) {
     const int r = tk / W, w = tk - r * W;
-    const unsigned long long *mr = amask + (size_t)(r + 1) * W;
-    const unsigned long long m = mr[w];
-    unsigned long long cm = 0ull;
-    if (m != 0ull) {
-      const unsigned long long up = mr[w - W], dn = mr[w + W];
-      const unsigned long long lcarry = (w > 0) ? (mr[w - 1] >> 63) : 0ull;
-      const unsigned long long rcarry = (w + 1 < W) ? (mr[w + 1] << 63) : 0ull;
-      const unsigned long long nb = (m << 1) | lcarry | (m >> 1) | rcarry | up | dn;
-      const int lo = max(1 - w * 64, 0), hi = min(k.gw - 1 - w * 64, 64);   // bits [lo,hi)
-      unsigned long long valid = 0ull;
-      if (hi > lo) {
-        valid = (hi >= 64) ? ~0ull : ((1ull << hi) - 1ull);
-        valid &= ~((1ull << lo) - 1ull);
-      }
-      cm = m & nb & valid;
-    }
+    const unsigned long long cm = centre_word(amask + (size_t)(r + 1) * W, w, W, k.gw);
     cmask[tk] = cm;
     const unsigned int c = (unsigned int)__popcll(cm);
     if (c) atomicAdd(total, c);
@@ -391,12 +206,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ACC != 0 
     __syncthreads();
     // ---- the votes (an empty analysed range keeps nothing: nothing to read)
     if (crows > 0) {
-      if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + it.r0 * 8ull, it.r1 - it.r0, k, t0, tile);
-      else stream_mv40<BLOCK, UNROLL>(mv + it.r0 * 40ull, it.r1 - it.r0, k, t0, tile);
+      const auto one = [=, &k](const MvFields m) { vote(m, k, t0, tile); };
+      if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + it.r0 * 8ull, it.r1 - it.r0, one);
+      else stream_mv40<BLOCK, UNROLL>(mv + it.r0 * 40ull, it.r1 - it.r0, one);
     }
     __syncthreads();
     // ---- the masks and the frame's centre count
-    row_masks<BLOCK>(tile, amask, k, t0, t1, k.y_lo - 1, crows + 2);
+    row_masks<BLOCK>(tile, k, t0, t1, k.y_lo - 1, crows + 2,
+                     [=, &k](int j, int w, int, unsigned long long m) { amask[(size_t)j * k.W + w] = m; });
     if (tid == 0) total[0] = 0u;
     __syncthreads();
     centre_masks<BLOCK>(amask, cmask, total, k, crows);
@@ -421,25 +238,15 @@ namespace {
 template <int REC, int ACC>
 hipError_t launch_map(const ActLaunch &L) {
   auto kern = activity_frames_kernel<kActBlock, kActUnroll, REC, ACC>;
-  // Dynamic-LDS ceiling: set once per instantiation and device to the device maximum (scan_kernels.hip, launch_one)
   static std::atomic<unsigned long long> ready{0ull};
-  const unsigned long long bit = 1ull << (L.device & 63);
-  if ((ready.load(std::memory_order_acquire) & bit) == 0ull) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L.lds_max);
-    if (e != hipSuccess) return e;
-    ready.fetch_or(bit, std::memory_order_release);
-  }
+  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
+  if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
   const unsigned long long groups = ((unsigned long long)L.n_frames + (unsigned long long)L.k.run - 1ull) / (unsigned long long)L.k.run;
-  const unsigned long long chunk = 1ull << 30;             // workgroups per launch: grid.x stays < 2^31
-  for (unsigned long long g0 = 0; g0 < groups; g0 += chunk) {
-    const unsigned long long left = groups - g0;
-    hipLaunchKernelGGL(kern, dim3((unsigned int)(left < chunk ? left : chunk)), dim3(kActBlock), L.lds_bytes, L.stream, L.mv,
-                       work, (unsigned int)g0, L.n_frames, L.k, L.stream_off, L.n_streams, L.active, L.centre, L.frames);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return launch_chunked(groups, kGridChunk, [&](unsigned long long g0, unsigned int n) {
+    hipLaunchKernelGGL(kern, dim3(n), dim3(kActBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)g0, L.n_frames, L.k,
+                       L.stream_off, L.n_streams, L.active, L.centre, L.frames);
+  });
 }
 
 template <int REC>
@@ -473,12 +280,9 @@ hipError_t launch_activity_map(const ActLaunch &L) {
   if (L.n_frames == 0 || L.n_streams == 0) return hipSuccess;
   if (!L.frame_off || !L.stream_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records)
     return hipErrorInvalidValue;
-  WorkItem *work = static_cast<WorkItem *>(L.plan_ws);
-  unsigned int *blk_cnt = reinterpret_cast<unsigned int *>(work + (size_t)L.n_frames + 1u);
   // flags / centres null: the planner answers nothing itself
-  e = launch_plan(L.frame_off, L.has_sd, L.n_records, L.rebase, L.n_frames, nullptr, 0, nullptr, 0, work, blk_cnt, L.stream);
+  e = plan_work_list(L, nullptr, 0, nullptr, 0);
   if (e != hipSuccess) return e;
-  if (L.ev_planned && (e = hipEventRecord(L.ev_planned, L.stream)) != hipSuccess) return e;
   return L.rec_bytes == 8 ? launch_map_acc<8>(L) : launch_map_acc<40>(L);
 }
 

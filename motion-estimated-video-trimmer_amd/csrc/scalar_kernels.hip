@@ -25,13 +25,11 @@
 #include <stdint.h>
 
 #include "scalar_kernels.h"
+#include "record_stream.h"
 
 namespace mtgpu {
 
 namespace {
-
-typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
 
 // What a term needs of a record (layout: include/mt_types.h, mt_mv): bytes 4-5 (w, h; the dword at +4 also carries
 // src_x) and bytes 24-33 (motion_x, motion_y, motion_scale; the three dwords at +24 also carry two padding bytes).
@@ -82,24 +80,6 @@ __device__ __forceinline__ void add_term_any(const RecFields &r, bool ok, double
   else { if (ok) add_term<false>(r, acc, cnt); }
 }
 
-// An entry of the work list with one 32-byte load (workgroup-uniform address: a scalar load), as the scan reads it.
-__device__ __forceinline__ WorkItem load_item(const WorkItem *__restrict__ work, unsigned int wi) {
-  typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
-  const u32x8 raw = *reinterpret_cast<const u32x8 *>(work + wi);
-  WorkItem it;
-  it.r0 = (unsigned long long)raw[0] | ((unsigned long long)raw[1] << 32);
-  it.r1 = (unsigned long long)raw[2] | ((unsigned long long)raw[3] << 32);
-  it.f = raw[4];
-  it.pad[0] = it.pad[1] = it.pad[2] = 0u;
-  return it;
-}
-
-template <typename T>
-__device__ __forceinline__ void store_result(T *p, T v, int sys) {
-  if (sys) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  else *p = v;
-}
-
 }  // namespace
 
 // scores[f] = +0.0, terms[f] = 0 for every frame, ahead of the scores kernel on the same stream: the planner lists
@@ -129,6 +109,9 @@ __global__ __launch_bounds__(BLOCK) void motion_scores_kernel(
   unsigned long long n = me.r1 - me.r0;
   double acc = 0.0;
   unsigned int cnt = 0u;
+  // The streaming loop is this kernel's own, not record_stream.h's: it reads other fields of a record, chooses its
+  // arithmetic per wave instruction with __all — so every lane of a wave must make every trip — and its summation
+  // order is part of the result.
   // Head peel, as the scan's stream_mv40: a wave instruction of the loop below covers 64 records = 2560 bytes =
   // exactly 20 128-byte lines if the stream starts on a line.  40 h = -start (mod 128) has a solution h < 16 whenever
   // the start is 8-byte aligned (5 * 13 = 1 mod 16): the first h records go to lanes 0..h-1.
@@ -249,22 +232,15 @@ hipError_t launch_motion_scores(const ScoresLaunch &L) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  WorkItem *work = static_cast<WorkItem *>(L.plan_ws);
-  unsigned int *blk_cnt = reinterpret_cast<unsigned int *>(work + (size_t)L.n_frames + 1u);
   // has_sd == null: a frame is listed iff it has records; flags / centres null: the planner answers nothing itself
-  hipError_t e = launch_plan(L.frame_off, nullptr, L.n_records, L.rebase, L.n_frames, nullptr, 0, nullptr, 0, work,
-                             blk_cnt, L.stream);
+  hipError_t e = plan_work_list(L.frame_off, nullptr, L.n_records, L.rebase, L.n_frames, L.plan_ws, L.stream, nullptr, nullptr, 0,
+                                nullptr, 0);
   if (e != hipSuccess) return e;
-  const unsigned long long chunk = 1ull << 30;             // workgroups per launch: grid.x stays < 2^31
-  for (unsigned long long i0 = 0; i0 < L.n_frames; i0 += chunk) {
-    const unsigned long long left = (unsigned long long)L.n_frames - i0;
-    hipLaunchKernelGGL((motion_scores_kernel<kScoresBlock, kScoresUnroll>), dim3((unsigned int)(left < chunk ? left : chunk)),
-                       dim3(kScoresBlock), 0, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.scores, L.terms,
-                       L.sys_scores, L.sys_terms);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
+  return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
+    hipLaunchKernelGGL((motion_scores_kernel<kScoresBlock, kScoresUnroll>), dim3(n), dim3(kScoresBlock), 0, L.stream, L.mv, work,
+                       (unsigned int)i0, L.n_frames, L.scores, L.terms, L.sys_scores, L.sys_terms);
+  });
 }
 
 hipError_t launch_motion_bins(const BinsLaunch &L) {

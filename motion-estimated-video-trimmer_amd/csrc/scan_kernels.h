@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 namespace mtgpu {
 
 // Kernel-side parameter block, derived on the host from mt_scan_params
@@ -102,5 +104,56 @@ hipError_t launch_plan(const unsigned long long *frame_off, const unsigned char 
 // *first_bad (device, pre-set to 0xffffffff) = smallest f with frame_off[f] > frame_off[f + 1]
 hipError_t launch_check_offsets(const unsigned long long *frame_off, unsigned int n_frames, unsigned int *first_bad,
                                 hipStream_t stream);
+
+// ---- what every launcher of a kernel over the work list does on the host
+
+// launch_plan into the scratch of a launch: the work list at the front of plan_ws, blk_cnt behind its n_frames + 1
+// entries; then the profiling event between planning and the kernel that walks the list, where there is one.
+// flags / centres null: the planner answers nothing itself (the caller has cleared its outputs).
+inline hipError_t plan_work_list(const unsigned long long *frame_off, const unsigned char *has_sd, unsigned long long n_records,
+                                 unsigned long long rebase, unsigned int n_frames, void *plan_ws, hipStream_t stream,
+                                 hipEvent_t ev_planned, unsigned char *flags, int sys_flags, unsigned int *centres,
+                                 int sys_centres) {
+  WorkItem *work = static_cast<WorkItem *>(plan_ws);
+  unsigned int *blk_cnt = reinterpret_cast<unsigned int *>(work + (size_t)n_frames + 1u);
+  hipError_t e = launch_plan(frame_off, has_sd, n_records, rebase, n_frames, flags, sys_flags, centres, sys_centres, work,
+                             blk_cnt, stream);
+  if (e != hipSuccess) return e;
+  return ev_planned ? hipEventRecord(ev_planned, stream) : hipSuccess;
+}
+// The same from a launch block with the usual fields (ScanLaunch, SweepLaunch, ActLaunch, ZoneLaunch).
+template <class Launch>
+hipError_t plan_work_list(const Launch &L, unsigned char *flags, int sys_flags, unsigned int *centres, int sys_centres) {
+  return plan_work_list(L.frame_off, L.has_sd, L.n_records, L.rebase, L.n_frames, L.plan_ws, L.stream, L.ev_planned, flags,
+                        sys_flags, centres, sys_centres);
+}
+
+// Dynamic-LDS ceiling of a kernel: set ONCE per instantiation and device to the device maximum (host threads sharing
+// an instantiation must not race each other with per-launch values).  `ready`: the instantiation's own bit set, one bit
+// per device.
+template <class Kern>
+hipError_t raise_lds_limit_once(Kern kern, std::atomic<unsigned long long> &ready, int device, int lds_max) {
+  const unsigned long long bit = 1ull << (device & 63);
+  if ((ready.load(std::memory_order_acquire) & bit) == 0ull) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    if (e != hipSuccess) return e;
+    ready.fetch_or(bit, std::memory_order_release);
+  }
+  return hipSuccess;
+}
+
+// `total` workgroups in launches of at most `chunk` (2^30: grid.x stays < 2^31): launch(first, n) starts workgroups
+// [first, first + n) and is followed by hipGetLastError.
+constexpr unsigned long long kGridChunk = 1ull << 30;
+template <class F>
+hipError_t launch_chunked(unsigned long long total, unsigned long long chunk, F launch) {
+  for (unsigned long long i0 = 0; i0 < total; i0 += chunk) {
+    const unsigned long long left = total - i0;
+    launch(i0, (unsigned int)(left < chunk ? left : chunk));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 }  // namespace mtgpu

@@ -56,35 +56,9 @@
 #include <type_traits>
 
 #include "scan_kernels.h"
+#include "record_stream.h"
 
 namespace mtgpu {
-
-typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// Bytes 4..15 of a record: d.x = w | h<<8 | src_x<<16, d.y = src_y | dst_x<<16,
-// d.z = dst_y | pad<<16   (layout: include/mt_types.h, mt_mv).
-
-// 12 bytes at +4 with the streaming (nt) hint.
-__device__ __forceinline__ u32x3 load_fields(const unsigned char *rec) {
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4 *>(rec + 4));
-}
-
-// Compact record (REC 8): src_x | src_y << 16, dst_x | dst_y << 16 — bytes 6..13 of an
-// AVMotionVector, packed by the host dispatcher (pipe.hip) or mtgpu_pack_records.
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef u32x2 u32x2_a8 __attribute__((aligned(8)));
-
-__device__ __forceinline__ u32x2 load_compact(const unsigned char *rec) {
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x2_a8 *>(rec));
-}
-
-typedef u32x4 u32x4_a16 __attribute__((aligned(16)));
-
-__device__ __forceinline__ u32x4 load_pair(const unsigned char *two_records) {   // 16-byte aligned
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x4_a16 *>(two_records));
-}
 
 template <int REC> struct RawOf { typedef u32x3 type; };
 template <> struct RawOf<8> { typedef u32x2 type; };
@@ -93,15 +67,6 @@ template <int REC>
 __device__ __forceinline__ typename RawOf<REC>::type load_rec(const unsigned char *rec) {
   if constexpr (REC == 8) return load_compact(rec);
   else return load_fields(rec);
-}
-
-struct MvFields { int src_x, src_y, dst_x, dst_y; };
-
-__device__ __forceinline__ MvFields decode(const u32x3 d) {
-  return {(int)d.x >> 16, (int)(short)(d.y & 0xffffu), (int)d.y >> 16, (int)(short)(d.z & 0xffffu)};
-}
-__device__ __forceinline__ MvFields decode(const u32x2 d) {
-  return {(int)(short)(d.x & 0xffffu), (int)d.x >> 16, (int)(short)(d.y & 0xffffu), (int)d.y >> 16};
 }
 
 enum { MODE_ADD32 = 0, MODE_UNARY = 1, MODE_CAS = 2 };
@@ -267,25 +232,6 @@ __device__ __forceinline__ unsigned int combine_words(unsigned int a, unsigned i
     }
     return r;
   }
-}
-
-// The one result byte of a frame.  `sys` (ScanK::sys_flags, set by the host when `flags` is not device memory — the
-// pipe's zero-copy staging, a caller's hipHostMalloc'ed buffer): a SYSTEM-scope store (global_store_byte ... sc0 sc1:
-// write-through past the XCD's L2, byte-masked) — the kernel then writes pinned host memory over PCIe next to bytes
-// that other workgroups, on other XCDs, write into the same line at other times, so no cache on the way may hold the
-// line and merge it back later.  Device memory takes the plain store: a write-through store is only acknowledged from
-// the memory side, and a workgroup cannot retire before that — measured against round 4's library in one process,
-// system-scope stores for EVERY frame cost 1.2 % on 1080p (16 384 flags per launch) and 4 % on 480p (262 144).
-__device__ __forceinline__ void store_flag(unsigned char *flags, unsigned int f, unsigned char v, int sys) {
-  if (sys) __hip_atomic_store(&flags[f], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  else flags[f] = v;
-}
-
-// The frame's centre count (ScanLaunch::centres), when the caller asked for it: store_flag's sibling — one lane, one
-// 32-bit store, system-scope write-through when the destination is not device memory (`sys`: ScanK::sys_centres).
-__device__ __forceinline__ void store_centres(unsigned int *centres, unsigned int f, unsigned int v, int sys) {
-  if (sys) __hip_atomic_store(&centres[f], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  else centres[f] = v;
 }
 
 // Where a spilling workgroup (SPILL) keeps the votes later bands need: the frame's queue, one dword per record of the
@@ -592,21 +538,6 @@ __device__ __forceinline__ bool plan_frame(const unsigned long long *__restrict_
   r1 = r1 < n_records ? r1 : n_records;
   r0 = r0 < r1 ? r0 : r1;
   return has_sd ? (has_sd[f] != 0) : (r1 > r0);
-}
-
-// An entry of the work list with ONE 32-byte load — r0, r1 and f arrive together (read field by field the compiler
-// fetches f first, tests it, and only then asks for r0 / r1: two memory round trips at the start of every workgroup's
-// life instead of one; the list was just written by another kernel, so the first touch of a line comes from beyond
-// this XCD's L2).  The address is workgroup-uniform: a scalar load.
-__device__ __forceinline__ WorkItem load_item(const WorkItem *__restrict__ work, unsigned int wi) {
-  typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
-  const u32x8 raw = *reinterpret_cast<const u32x8 *>(work + wi);
-  WorkItem it;
-  it.r0 = (unsigned long long)raw[0] | ((unsigned long long)raw[1] << 32);
-  it.r1 = (unsigned long long)raw[2] | ((unsigned long long)raw[3] << 32);
-  it.f = raw[4];
-  it.pad[0] = it.pad[1] = it.pad[2] = 0u;
-  return it;
 }
 
 // The entries a workgroup that owns several frames needs after its first: fetched by lanes 1 .. group-1 when the
@@ -976,20 +907,8 @@ __device__ __forceinline__ unsigned int count_centres(const unsigned long long *
   for (int tk = tid; tk < ntask; tk += BLOCK) {
     const int r = tk / W, w = tk - r * W;
     const unsigned long long *mr = mask + (size_t)(r + 1) * W;
-    const unsigned long long m = mr[w];
-    if (m == 0ull) continue;
-    const unsigned long long up = mr[w - W], dn = mr[w + W];
-    const unsigned long long lcarry = (w > 0) ? (mr[w - 1] >> 63) : 0ull;
-    const unsigned long long rcarry = (w + 1 < W) ? (mr[w + 1] << 63) : 0ull;
-    const unsigned long long nb = (m << 1) | lcarry | (m >> 1) | rcarry | up | dn;
-    // centres are x in [1, gw-2]  (:280)
-    const int lo = max(1 - w * 64, 0), hi = min(k.gw - 1 - w * 64, 64);   // bits [lo,hi)
-    unsigned long long valid = 0ull;
-    if (hi > lo) {
-      valid = (hi >= 64) ? ~0ull : ((1ull << hi) - 1ull);
-      valid &= ~((1ull << lo) - 1ull);
-    }
-    local += (unsigned int)__popcll(m & nb & valid);
+    if (mr[w] == 0ull) continue;                               // no popcount, no add: most words of most frames
+    local += (unsigned int)__popcll(centre_word(mr, w, W, k.gw));
   }
   return local;
 }
@@ -1273,30 +1192,16 @@ hipError_t launch_check_offsets(const unsigned long long *frame_off, unsigned in
 template <int BLOCK, int FB, int MODE, int REC, bool SPILL, int UNROLL = 4>
 static hipError_t launch_one(const ScanLaunch &L) {
   auto kern = scan_frames_kernel<BLOCK, UNROLL, FB, MODE, REC, SPILL>;
-  // Dynamic-LDS ceiling: set ONCE per instantiation and device to the device maximum (host
-  // threads sharing an instantiation must not race each other with per-launch values).
   static std::atomic<unsigned long long> ready{0ull};
-  const unsigned long long bit = 1ull << (L.device & 63);
-  if ((ready.load(std::memory_order_acquire) & bit) == 0ull) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, L.lds_max);
-    if (e != hipSuccess) return e;
-    ready.fetch_or(bit, std::memory_order_release);
-  }
+  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
+  if (e != hipSuccess) return e;
   const unsigned long long items = (unsigned long long)L.n_frames * (unsigned long long)(SPILL ? 1 : L.k.slices);
-  const unsigned long long group = (unsigned long long)(L.k.group > 0 ? L.k.group : 1);
+  const unsigned long long group = (unsigned long long)(L.k.group > 0 ? L.k.group : 1);   // a workgroup scans `group` items
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
-  const unsigned long long chunk = L.item_chunk ? L.item_chunk : (1ull << 30);   // workgroups per launch: grid.x stays < 2^31
-  for (unsigned long long i0 = 0; i0 < items; i0 += chunk * group) {
-    const unsigned long long left = items - i0;
-    const unsigned long long wgs = (left + group - 1) / group;
-    const unsigned int n = (unsigned int)(wgs < chunk ? wgs : chunk);
-    hipLaunchKernelGGL(kern, dim3(n), dim3(BLOCK), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0,
+  return launch_chunked((items + group - 1) / group, L.item_chunk ? L.item_chunk : kGridChunk, [&](unsigned long long wg0, unsigned int n) {
+    hipLaunchKernelGGL(kern, dim3(n), dim3(BLOCK), L.lds_bytes, L.stream, L.mv, work, (unsigned int)(wg0 * group),
                        (unsigned int)items, L.k, L.flags, L.centres, L.spill_q, L.slice_ws, L.tickets);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 template <int BLOCK, int REC, bool SPILL>
@@ -1345,15 +1250,9 @@ hipError_t launch_scan(const ScanLaunch &L) {
     if (e != hipSuccess) return e;
   }
   if (!L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || !L.frame_off || L.rebase > L.n_records) return hipErrorInvalidValue;
-  {
-    WorkItem *work = static_cast<WorkItem *>(L.plan_ws);
-    unsigned int *blk_cnt = reinterpret_cast<unsigned int *>(work + (size_t)L.n_frames + 1u);
-    e = launch_plan(L.frame_off, L.has_sd, L.n_records, L.rebase, L.n_frames, L.flags, L.k.sys_flags, L.centres,
-                    L.k.sys_centres, work, blk_cnt, L.stream);
-    if (e != hipSuccess) return e;
-  }
-  // (profiling: the event between planning and scan)
-  if (L.ev_planned && (e = hipEventRecord(L.ev_planned, L.stream)) != hipSuccess) return e;
+  // (profiling: ev_planned lies between planning and scan)
+  e = plan_work_list(L, L.flags, L.k.sys_flags, L.centres, L.k.sys_centres);
+  if (e != hipSuccess) return e;
   switch (L.block) {
     case 512: e = launch_block<512>(L); break;
     case 1024: e = launch_block<1024>(L); break;

@@ -25,6 +25,11 @@
 //
 // A grid whose thresholds do not fit LDS together is swept in several launches, each over a contiguous run of the
 // sorted thresholds (mtgpu_api.hip, sweep_plan): every launch reads the records again.
+//
+// The record loads, the streamers (with vote<NT> as their functor), the centre test of a word and the result store are
+// those of record_stream.h, shared with activity_kernels.hip and zones_kernels.hip; the launch helpers are those of
+// scan_kernels.h.  vote<NT> and the multi-level row_masks are this file's own.  A change to the shared header must leave
+// this file's device assembly as it was, or be timed against the build before it.
 #if !defined(__HIP_DEVICE_COMPILE__) || defined(__gfx950__)
 #else
 #error "sweep_kernels.hip is written for gfx950 only (wave64, 160 KB LDS, sc1 write-through stores)"
@@ -35,56 +40,11 @@
 #include <atomic>
 
 #include "sweep_kernels.h"
+#include "record_stream.h"
 
 namespace mtgpu {
 
 namespace {
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x2 u32x2_a8 __attribute__((aligned(8)));
-typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
-typedef u32x4 u32x4_a16 __attribute__((aligned(16)));
-
-// The record forms of the scan (scan_kernels.hip): bytes 4..15 of a 40-byte record — d.x = w | h<<8 | src_x<<16,
-// d.y = src_y | dst_x<<16, d.z = dst_y | pad<<16 — or a compact record, src_x | src_y<<16, dst_x | dst_y<<16.  All with
-// the streaming (nt) hint: every record is read once per pass.
-__device__ __forceinline__ u32x3 load_fields(const unsigned char *rec) {
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4 *>(rec + 4));
-}
-__device__ __forceinline__ u32x2 load_compact(const unsigned char *rec) {
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x2_a8 *>(rec));
-}
-__device__ __forceinline__ u32x4 load_pair(const unsigned char *two_records) {   // 16-byte aligned
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x4_a16 *>(two_records));
-}
-
-struct MvFields { int src_x, src_y, dst_x, dst_y; };
-
-__device__ __forceinline__ MvFields decode(const u32x3 d) {
-  return {(int)d.x >> 16, (int)(short)(d.y & 0xffffu), (int)d.y >> 16, (int)(short)(d.z & 0xffffu)};
-}
-__device__ __forceinline__ MvFields decode(const u32x2 d) {
-  return {(int)(short)(d.x & 0xffffu), (int)d.x >> 16, (int)(short)(d.y & 0xffffu), (int)d.y >> 16};
-}
-
-// An entry of the work list with one 32-byte load (workgroup-uniform address: a scalar load), as the scan reads it.
-__device__ __forceinline__ WorkItem load_item(const WorkItem *__restrict__ work, unsigned int wi) {
-  typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
-  const u32x8 raw = *reinterpret_cast<const u32x8 *>(work + wi);
-  WorkItem it;
-  it.r0 = (unsigned long long)raw[0] | ((unsigned long long)raw[1] << 32);
-  it.r1 = (unsigned long long)raw[2] | ((unsigned long long)raw[3] << 32);
-  it.f = raw[4];
-  it.pad[0] = it.pad[1] = it.pad[2] = 0u;
-  return it;
-}
-
-__device__ __forceinline__ void store_count(unsigned int *p, unsigned int v, int sys) {
-  if (sys) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  else *p = v;
-}
 
 // The workgroup's view of its frame's grid: tracked rows [t0, t1) = the analysed rows [y_lo, y_hi) and one halo row
 // each side (inside the grid), centres [y_lo, y_hi).
@@ -109,91 +69,6 @@ __device__ __forceinline__ void vote(const MvFields m, const SweepK &k, const Ro
     atomicAdd(&tiles[(size_t)(passed - 1u) * (unsigned int)k.tile_words + (unsigned int)((gy - b.t0) * k.gw + gx)], 1u);
 }
 
-template <int NT>
-__device__ __forceinline__ void vote_pair(const u32x4 d, const SweepK &k, const Rows &b, unsigned int *tiles) {
-  vote<NT>(decode((u32x2){d.x, d.y}), k, b, tiles);
-  vote<NT>(decode((u32x2){d.z, d.w}), k, b, tiles);
-}
-
-// 40-byte records [base, base + 40 n): the scan's stream_mv40 — up to 15 head records so that the steps start on a
-// 128-byte line (40 h = -start mod 128 has a solution h < 16 whenever the start is 8-byte aligned), then lane i of a
-// step takes record i with UNROLL independent loads in flight, then the rest with every load issued before the
-// first vote.
-template <int BLOCK, int UNROLL, int NT>
-__device__ __forceinline__ void stream_mv40(const unsigned char *base, unsigned long long n, const SweepK &k, const Rows &b,
-                                            unsigned int *tiles) {
-  const int tid = threadIdx.x;
-  const unsigned int r = (unsigned int)((uintptr_t)base & 127u);
-  if ((r & 7u) == 0u) {
-    unsigned long long h = (unsigned long long)((13u * ((16u - (r >> 3)) & 15u)) & 15u);
-    h = h < n ? h : n;
-    if ((unsigned long long)tid < h) vote<NT>(decode(load_fields(base + (unsigned long long)tid * 40ull)), k, b, tiles);
-    base += h * 40ull;
-    n -= h;
-  }
-  unsigned long long i = tid;
-  constexpr unsigned long long STEP = (unsigned long long)UNROLL * BLOCK;
-  constexpr unsigned long long LAST = (unsigned long long)(UNROLL - 1) * BLOCK;
-  for (; i + LAST < n; i += STEP) {
-    u32x3 d[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) d[u] = load_fields(base + (i + (unsigned long long)u * BLOCK) * 40ull);
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) vote<NT>(decode(d[u]), k, b, tiles);
-  }
-  if (i < n) {
-    u32x3 d[UNROLL];
-    bool ok[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const unsigned long long q = i + (unsigned long long)u * BLOCK;
-      ok[u] = q < n;
-      if (ok[u]) d[u] = load_fields(base + q * 40ull);
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (ok[u]) vote<NT>(decode(d[u]), k, b, tiles);
-  }
-}
-
-// Compact records [base, base + 8 n), 8-byte aligned: the scan's stream_compact without the look-ahead — up to 15 head
-// records one per lane so that the 16-byte pair stream starts on a 128-byte line, lane 0 takes an odd last record.
-template <int BLOCK, int UNROLL, int NT>
-__device__ __forceinline__ void stream_compact(const unsigned char *base, unsigned long long n, const SweepK &k, const Rows &b,
-                                               unsigned int *tiles) {
-  const int tid = threadIdx.x;
-  constexpr unsigned long long STEP = (unsigned long long)UNROLL * BLOCK;
-  constexpr unsigned long long LAST = (unsigned long long)(UNROLL - 1) * BLOCK;
-  unsigned long long head = ((0ull - (unsigned long long)(uintptr_t)base) & 127ull) >> 3;
-  head = head < n ? head : n;
-  const unsigned char *pbase = base + head * 8ull;
-  const unsigned long long np = (n - head) >> 1;            // pairs
-  if ((unsigned long long)tid < head) vote<NT>(decode(load_compact(base + (unsigned long long)tid * 8ull)), k, b, tiles);
-  if (tid == 0 && ((n - head) & 1ull) != 0ull) vote<NT>(decode(load_compact(base + (n - 1ull) * 8ull)), k, b, tiles);
-  unsigned long long p = tid;
-  for (; p + LAST < np; p += STEP) {
-    u32x4 d[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) d[u] = load_pair(pbase + (p + (unsigned long long)u * BLOCK) * 16ull);
-    __builtin_amdgcn_sched_barrier(0);   // every load of the step is issued before the first one is consumed
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) vote_pair<NT>(d[u], k, b, tiles);
-  }
-  if (p < np) {
-    u32x4 d[UNROLL];
-    bool ok[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const unsigned long long q = p + (unsigned long long)u * BLOCK;
-      ok[u] = q < np;
-      if (ok[u]) d[u] = load_pair(pbase + q * 16ull);
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (ok[u]) vote_pair<NT>(d[u], k, b, tiles);
-  }
-}
-
 // ---- fold: tile i becomes the votes of threshold i = the sum of tiles i .. n_thr-1.  Every lane owns its 16-byte
 // columns through all tiles: no barrier between the tiles.
 template <int BLOCK>
@@ -212,7 +87,8 @@ __device__ __forceinline__ void fold_tiles(unsigned int *tiles, const SweepK &k)
 // ---- phase 2a: the 64-bit masks of active cells of grid rows [g0, g0 + nrows), one plane per vector level: plane v,
 // mask row j <-> grid row g0 + j.  Rows outside the tracked rows and cells outside the grid are inactive at every
 // level, level 0 included (:282 with vectors_needed == 0: every cell OF THE GRID is active).
-// Four lanes per (mask row, word), 16 cells each, as the scan's row_masks: the cells are read ONCE, in a rotated order
+// Four lanes per (mask row, word), 16 cells each, as the scan's row_masks (record_stream.h has the single-level form;
+// this one holds the cells in registers across the levels): the cells are read ONCE, in a rotated order
 // (the 64 lanes of a wave hit 64 different LDS banks per step), and compared against each level in registers.
 template <int BLOCK>
 __device__ __forceinline__ void row_masks(const unsigned int *cnt, unsigned long long *mask, const SweepK &k, const Rows &b,
@@ -263,19 +139,8 @@ __device__ __forceinline__ void count_centres(const unsigned long long *mask, un
     const int v = tk / per, rw = tk - v * per;
     const int r = rw / W, w = rw - r * W;
     const unsigned long long *mr = mask + ((size_t)v * k.mask_rows + r + 1) * W;
-    const unsigned long long m = mr[w];
-    if (m == 0ull) continue;
-    const unsigned long long up = mr[w - W], dn = mr[w + W];
-    const unsigned long long lcarry = (w > 0) ? (mr[w - 1] >> 63) : 0ull;
-    const unsigned long long rcarry = (w + 1 < W) ? (mr[w + 1] << 63) : 0ull;
-    const unsigned long long nb = (m << 1) | lcarry | (m >> 1) | rcarry | up | dn;
-    const int lo = max(1 - w * 64, 0), hi = min(k.gw - 1 - w * 64, 64);   // bits [lo,hi)
-    unsigned long long valid = 0ull;
-    if (hi > lo) {
-      valid = (hi >= 64) ? ~0ull : ((1ull << hi) - 1ull);
-      valid &= ~((1ull << lo) - 1ull);
-    }
-    const unsigned int c = (unsigned int)__popcll(m & nb & valid);
+    if (mr[w] == 0ull) continue;                               // no popcount, no add: most words of most frames
+    const unsigned int c = (unsigned int)__popcll(centre_word(mr, w, W, k.gw));
     if (c) atomicAdd(&totals[v], c);
   }
 }
@@ -284,7 +149,7 @@ __device__ __forceinline__ void count_centres(const unsigned long long *mask, un
 
 __global__ __launch_bounds__(256) void sweep_clear_kernel(unsigned int *__restrict__ centres, unsigned long long n, int sys) {
   for (unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256ull)
-    store_count(&centres[i], 0u, sys);
+    store_result(&centres[i], 0u, sys);
 }
 
 template <int BLOCK, int UNROLL, int REC, int NT>
@@ -313,8 +178,9 @@ __global__ __launch_bounds__(BLOCK) void sweep_frames_kernel(
 
   // ---- phase 1 (an empty analysed range keeps nothing: nothing to read)
   if (k.y_hi > k.y_lo) {
-    if constexpr (REC == 8) stream_compact<BLOCK, UNROLL, NT>(mv + me.r0 * 8ull, me.r1 - me.r0, k, b, tiles);
-    else stream_mv40<BLOCK, UNROLL, NT>(mv + me.r0 * 40ull, me.r1 - me.r0, k, b, tiles);
+    const auto one = [=, &k](const MvFields m) { vote<NT>(m, k, b, tiles); };
+    if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + me.r0 * 8ull, me.r1 - me.r0, one);
+    else stream_mv40<BLOCK, UNROLL>(mv + me.r0 * 40ull, me.r1 - me.r0, one);
   }
   __syncthreads();
   if (k.n_thr > 1) {
@@ -338,7 +204,7 @@ __global__ __launch_bounds__(BLOCK) void sweep_frames_kernel(
   if (tid < k.n_thr * k.n_vec) {
     const int i = tid / k.n_vec, v = tid - i * k.n_vec;
     const unsigned long long at = ((unsigned long long)k.out_t[i] * (unsigned int)k.n_vec + (unsigned int)v) * n_frames + me.f;
-    store_count(&centres[at], totals[i * kSweepMaxVec + v], k.sys);
+    store_result(&centres[at], totals[i * kSweepMaxVec + v], k.sys);
   }
 }
 
@@ -347,24 +213,14 @@ namespace {
 template <int REC, int NT>
 hipError_t launch_pass(const SweepLaunch &L, const SweepK &k) {
   auto kern = sweep_frames_kernel<kSweepBlock, kSweepUnroll, REC, NT>;
-  // Dynamic-LDS ceiling: set once per instantiation and device to the device maximum (scan_kernels.hip, launch_one)
   static std::atomic<unsigned long long> ready{0ull};
-  const unsigned long long bit = 1ull << (L.device & 63);
-  if ((ready.load(std::memory_order_acquire) & bit) == 0ull) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L.lds_max);
-    if (e != hipSuccess) return e;
-    ready.fetch_or(bit, std::memory_order_release);
-  }
+  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
+  if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
-  const unsigned long long chunk = 1ull << 30;             // workgroups per launch: grid.x stays < 2^31
-  for (unsigned long long i0 = 0; i0 < L.n_frames; i0 += chunk) {
-    const unsigned long long left = (unsigned long long)L.n_frames - i0;
-    hipLaunchKernelGGL(kern, dim3((unsigned int)(left < chunk ? left : chunk)), dim3(kSweepBlock), L.lds_bytes, L.stream, L.mv,
-                       work, (unsigned int)i0, L.n_frames, k, L.centres, L.n_frames);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
+    hipLaunchKernelGGL(kern, dim3(n), dim3(kSweepBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, k,
+                       L.centres, L.n_frames);
+  });
 }
 
 // The instantiations: two record forms x 1, 2, 4 or 8 threshold compares per record.
@@ -394,13 +250,9 @@ hipError_t launch_sweep_scan(const SweepLaunch &L) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  WorkItem *work = static_cast<WorkItem *>(L.plan_ws);
-  unsigned int *blk_cnt = reinterpret_cast<unsigned int *>(work + (size_t)L.n_frames + 1u);
   // flags / centres null: the planner answers nothing itself (the block is zero already)
-  hipError_t e = launch_plan(L.frame_off, L.has_sd, L.n_records, L.rebase, L.n_frames, nullptr, 0, nullptr, 0, work, blk_cnt,
-                             L.stream);
+  hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
   if (e != hipSuccess) return e;
-  if (L.ev_planned && (e = hipEventRecord(L.ev_planned, L.stream)) != hipSuccess) return e;
   for (int t0 = 0; t0 < L.n_thr_all; t0 += L.thr_per_pass) {
     SweepK k = L.k;
     k.n_thr = L.n_thr_all - t0 < L.thr_per_pass ? L.n_thr_all - t0 : L.thr_per_pass;

@@ -1,6 +1,6 @@
 """Inputs of tests/test_gpu_derived_edges.py: the record-level and plan-level edge cases of the scan's suite, rebuilt for
-the kernels that carry private copies of the scan's record machinery (sweep_frames_kernel, activity_frames_kernel,
-motion_scores_kernel).  Every builder returns its input together with the values derived BY HAND from its construction;
+the kernels that stream records with csrc/record_stream.h's shared streamers as each of them instantiates them
+(sweep_frames_kernel, activity_frames_kernel) or with a loop of their own (motion_scores_kernel).  Every builder returns its input together with the values derived BY HAND from its construction;
 tests/test_derived_edges_host.py checks those against the oracle (and the numpy model of the maps) without a GPU, and
 that the plans reach the forms the GPU tests rely on.  Everything is built once per process and handed out read-only."""
 import functools

@@ -1,6 +1,7 @@
-"""GPU tier (`-m gpu`): the record-level and plan-level edge cases of the scan's suite, held against the kernels that carry
-private copies of the scan's record machinery — sweep_frames_kernel (csrc/sweep_kernels.hip), activity_frames_kernel
-(csrc/activity_kernels.hip) and, for the unaligned base, motion_scores_kernel (csrc/scalar_kernels.hip).
+"""GPU tier (`-m gpu`): the record-level and plan-level edge cases of the scan's suite, held against the shared
+streamers of csrc/record_stream.h (head peel, steps, tail) as each kernel instantiates them with its own vote —
+sweep_frames_kernel (csrc/sweep_kernels.hip), activity_frames_kernel (csrc/activity_kernels.hip) — and, for the unaligned
+base, against motion_scores_kernel's own loop (csrc/scalar_kernels.hip).
 
 The inputs and the values derived by hand from their construction come from tests/derived_edge_inputs.py;
 tests/test_derived_edges_host.py holds them against the oracle without a GPU.  Here every comparison is exact (integers,
