@@ -458,4 +458,8 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * call site of :375-383) — two more entry points, declared the same way. */
 #include "mtgpu_pipe_zones.h"
 
+/* Motion blobs: the connected components of a frame's centre cells (src/motion_scanner.cpp:272-294), their number, the
+ * largest one's size and box, and a minimum-object-size flag — three more entry points, declared the same way. */
+#include "mtgpu_blobs.h"
+
 #endif /* MTGPU_H */

@@ -32,6 +32,8 @@ MV_DTYPE = np.dtype(
     }
 )
 SEGMENT_DTYPE = np.dtype([("start", "<f8"), ("end", "<f8")])
+# mt_blob_box (include/mtgpu_blobs.h): inclusive cell bounds of a frame's largest blob, all 0xFFFF: no blob
+BLOB_BOX_DTYPE = np.dtype([("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2")])
 MERGE_PARAMS_DTYPE = np.dtype([("max_gap_sec", "<f8"), ("padding_sec", "<f8"),
                                ("duration", "<f8"), ("min_savings_pct", "<f8")])
 MERGE_RESULT_DTYPE = np.dtype([("n_timestamps", "<u8"), ("n_segments", "<u8"),
@@ -74,6 +76,11 @@ class ActivityPlanC(C.Structure):
 
 
 class ZonesPlanC(C.Structure):
+    _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("keep_words_per_row", C.c_int32),
+                ("keep_words_per_stream", C.c_int32)]
+
+
+class BlobsPlanC(C.Structure):
     _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("keep_words_per_row", C.c_int32),
                 ("keep_words_per_stream", C.c_int32)]
 
@@ -197,6 +204,16 @@ ABI_PIPE_ZONES = {
     "mtgpu_pipe_has_keep": (C.c_int, [C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_blobs.h declares (the motion blobs; mtgpu.h includes it).
+ABI_BLOBS = {
+    "mtgpu_blobs_preview": (C.c_int, [C.POINTER(ScanParamsC), C.c_int, C.POINTER(BlobsPlanC)]),
+    "mtgpu_scan_blobs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtgpu_scan_frames_blobs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -227,7 +244,7 @@ def load_library(path=None):
             "(or __graft_entry__.build()).  There is no fallback path.")
     lib = C.CDLL(p)
     for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
-            list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()):
+            list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,76 @@
+// blobs_kernels.h — launch interface between the C ABI (mtgpu_api.hip) and the gfx950 motion-blob kernel
+// (blobs_kernels.hip): the centre cells of src/motion_scanner.cpp:272-294, with or without a per-stream keep mask
+// ANDed into the active cells of the analysed rows (:282), labelled into 4-connected components per frame.
+// Internal; not part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "scan_kernels.h"
+
+namespace mtgpu {
+
+constexpr int kBlobBlock = 1024;    // lanes per workgroup (a multiple of 64: a wave owns one 64-cell word of a row)
+constexpr int kBlobUnroll = 4;      // independent record loads in flight per lane
+
+// LDS of one workgroup, in this order (R = analysed rows, at least 1; W = 64-bit words per mask row):
+//   tile     (R + 2) x gw u32, padded to 4 words   vote counters: the analysed rows and one halo row each side.  Dead
+//                                                  once the masks exist: its first R x gw words then hold the labels,
+//                                                  word r * gw + x for the cell (x, y_lo + r)
+//   keep     R x W u64                             the stream's keep words of the analysed rows; row r <-> grid row
+//                                                  y_lo + r.  Dead once the masks exist: the centre plane takes its
+//                                                  place, R x W u64, bit x & 63 of word x >> 6 of row r
+//   amask    (R + 2) x W u64                       the frame's active cells (AND keep); mask row j <-> grid row y_lo - 1 + j
+//   total    8 u32                                 [0] centres, [1] blobs, [2..3] the winner's key (u64), [4..7] its box
+inline size_t blob_tile_words(int gw, int R) {
+  const size_t w = (size_t)(R + 2) * (size_t)gw;
+  return (w + 3u) & ~(size_t)3u;
+}
+inline size_t blob_lds_bytes(int gw, int R) {
+  const size_t W = ((size_t)gw + 63u) / 64u;
+  return blob_tile_words(gw, R) * 4u + (size_t)(2 * R + 2) * W * 8u + 32u;
+}
+
+// mt_blob_box of include/mtgpu_blobs.h, as the kernel stores it (2-byte aligned, as the C struct: four 16-bit stores)
+struct BlobBox { unsigned short x0, y0, x1, y1; };
+
+// Kernel-side parameter block.
+struct BlobK {
+  unsigned long long thr;        // keep a record iff |d|^2 >= thr (ScanK::thr, :251)
+  unsigned int vec_need;         // a cell is active iff votes >= vec_need (:282) and, under a mask on an analysed row, its keep bit is set
+  unsigned int clust_need;       // max(1, clusters_needed) (:288)
+  unsigned int blob_need;        // max(1, min_blob_cells): flags[f] = centres[f] >= clust_need && largest[f] >= blob_need
+  int shift, gw, gh, y_lo, y_hi; // as ScanK (y_hi >= y_lo)
+  int W;                         // 64-bit words per mask row
+  int R;                         // max(1, y_hi - y_lo): rows the LDS layout is sized for
+  int tile_words;                // blob_tile_words
+};
+
+struct BlobLaunch {
+  const unsigned char *mv;
+  unsigned long long n_records;           // frame_off entries are clamped to this (before `rebase`)
+  unsigned long long rebase;
+  const unsigned long long *frame_off;    // n_frames + 1
+  const unsigned char *has_sd;            // n_frames or null
+  unsigned int n_frames;
+  int rec_bytes;                          // 40 or 8
+  const unsigned long long *stream_off;   // n_streams + 1; null iff keep is null
+  unsigned int n_streams;                 // 0 iff keep is null
+  const unsigned long long *keep;         // n_streams x gh x W, device memory; null: no mask, no stream lookup
+  unsigned char *flags;                   // n_frames bytes, device memory, or null
+  unsigned int *centres, *blobs, *largest;  // n_frames words each, or null
+  BlobBox *box;                           // n_frames boxes, or null
+  BlobK k;
+  int lds_bytes;
+  int lds_max;                            // device limit of dynamic LDS per workgroup
+  int device;
+  void *plan_ws;                          // plan_scratch_bytes(n_frames), 32-byte aligned
+  hipStream_t stream;
+  hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the blob kernel; else nullptr
+};
+
+// Fills the non-null outputs with the answer of a frame without a blob (0; an all-0xFFFF box), builds the work list
+// (launch_plan), then one workgroup per entry.
+hipError_t launch_blob_scan(const BlobLaunch &L);
+
+}  // namespace mtgpu

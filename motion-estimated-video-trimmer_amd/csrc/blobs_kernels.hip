@@ -1,0 +1,327 @@
+// blobs_kernels.hip — motion blobs: the 4-connected components of a frame's centre cells.  The centre test is that of
+// src/motion_scanner.cpp:272-294 (without the early return), on the active cells of mtgpu_scan_centres_device or, with
+// a keep mask, of mtgpu_scan_zones_device; what is new is the labelling of the centre plane in LDS.
+//
+//   blobs_clear_kernel    fills the non-null outputs ahead of the scan kernel with the answer of a frame without a blob
+//                         (0 everywhere, an all-0xFFFF box): a frame without side data, and a frame behind the last
+//                         stream, has no workgroup.
+//   blobs_frames_kernel   one workgroup per entry of the scan's work list, as zones_frames_kernel:
+//     stream, keep, votes, masks   as there (no mask: every keep word reads as ones, no stream lookup)
+//     centres     centre_word() of every (analysed row, word) into a centre plane — it takes the place of the staged
+//                 keep words, which are dead by then — and the frame's centre count.
+//     no centre   a workgroup-uniform test: lane 0 stores the zeros and the workgroup ends.  Most frames of a
+//                 surveillance stream end here, at the cost of the centre scan.
+//     labels      the vote tile is dead once the masks exist: word r * gw + x of it is the label of centre (x, y_lo + r).
+//                 A root holds kRoot | (cells - 1), every other cell the index of a cell of its component with a smaller
+//                 index.  Union-find, no round-by-round propagation:
+//         init      a cell points at the first cell of its horizontal run (bit scan over the row's words): a run is
+//                   one tree of depth 1 before the first union
+//         unite     one union per segment in which two runs of neighbouring rows overlap: find both roots, link the
+//                   larger index to the smaller with one LDS atomicMin, go on with whatever the atomic displaced.
+//                   Lock-free, no barrier inside, ends when both cells have one root.
+//         flatten   every cell finds its root, stores it, and adds itself to the root's count — one LDS add per
+//                   (wave, distinct root): a wave owns one 64-cell word of one row, which is rarely more than one blob.
+//         winner    roots: one add for the number of blobs, one 64-bit atomicMax on cells << 32 | ~root — the root is
+//                   the smallest cell index of its blob, so the larger key among equal sizes is the blob that holds the
+//                   smaller y * gw + x.
+//         box       LDS min / max over the winner's cells, one set of four per wave that holds any.
+//     Every loop with a barrier inside has a trip count computed from workgroup-uniform values; no loop has an
+//     iteration cap: find walks strictly decreasing indices, unite ends when the roots are equal.
+//   Every output element has one writer after the clear: lane 0 of the frame's workgroup, plain vector stores, no global
+//   atomics.
+//
+// The record loads, the streamers, the vote, the row masks and the centre test of a word are those of record_stream.h,
+// unchanged; the launch helpers are those of scan_kernels.h.
+#if !defined(__HIP_DEVICE_COMPILE__) || defined(__gfx950__)
+#else
+#error "blobs_kernels.hip is written for gfx950 only (wave64, 160 KB LDS)"
+#endif
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <atomic>
+
+#include "blobs_kernels.h"
+#include "record_stream.h"
+
+namespace mtgpu {
+
+namespace {
+
+constexpr unsigned int kRoot = 0x80000000u;    // label word of a root: kRoot | (cells of the tree - 1)
+
+// The root of cell x: labels below kRoot are cell indices smaller than the cell that holds them.
+__device__ __forceinline__ unsigned int find_root(unsigned int *L, unsigned int x) {
+  for (;;) {
+    const unsigned int v = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (v & kRoot) return x;
+    x = v;
+  }
+}
+
+// Joins the trees of cells a and b.  Runs concurrently in every lane; only roots are linked, always towards the smaller
+// index.  When the atomic finds that `a` has been linked by another lane in the meantime, label[a] is min(old, b) now,
+// and old and b are what remains to be joined.
+__device__ __forceinline__ void unite(unsigned int *L, unsigned int a, unsigned int b) {
+  for (;;) {
+    a = find_root(L, a);
+    b = find_root(L, b);
+    if (a == b) return;
+    if (a < b) { const unsigned int t = a; a = b; b = t; }
+    const unsigned int old = atomicMin(&L[a], b);
+    if (old & kRoot) return;
+    a = old;
+  }
+}
+
+// f(r, w, cw, tw) for every non-empty word cw = cpl[tw] of the centre plane, tw = r * W + w; a wave per word, lane =
+// bit.  The trip count depends on the wave alone.
+template <int BLOCK, class F>
+__device__ __forceinline__ void for_centre_words(const unsigned long long *cpl, int crows, int W, F f) {
+  const int nw = crows * W;
+  for (int tw = (int)(threadIdx.x >> 6); tw < nw; tw += BLOCK / 64) {
+    const unsigned long long cw = cpl[tw];
+    if (cw == 0ull) continue;
+    const int r = tw / W;
+    f(r, tw - r * W, cw, tw);
+  }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void blobs_clear_kernel(unsigned char *__restrict__ flags, unsigned int *__restrict__ centres,
+                                                          unsigned int *__restrict__ blobs, unsigned int *__restrict__ largest,
+                                                          BlobBox *__restrict__ box, unsigned int n) {
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256ull) {
+    if (flags) flags[i] = (unsigned char)0;
+    if (centres) centres[i] = 0u;
+    if (blobs) blobs[i] = 0u;
+    if (largest) largest[i] = 0u;
+    if (box) box[i] = BlobBox{0xffffu, 0xffffu, 0xffffu, 0xffffu};
+  }
+}
+
+// Waves per SIMD: as zones_frames_kernel — a 1080p workgroup takes about 35 KB of LDS, two workgroups of 16 waves share
+// a CU, eight waves per SIMD and so at most 64 VGPRs; the 4K workgroup sits alone on its CU.
+template <int BLOCK, int UNROLL, int REC>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void blobs_frames_kernel(
+    const unsigned char *__restrict__ mv, const WorkItem *__restrict__ work, unsigned int item0, unsigned int n_items, BlobK k,
+    const unsigned long long *__restrict__ stream_off, unsigned int n_streams, const unsigned long long *__restrict__ keep,
+    unsigned char *__restrict__ flags, unsigned int *__restrict__ centres, unsigned int *__restrict__ blobs,
+    unsigned int *__restrict__ largest, BlobBox *__restrict__ box) {
+  static_assert(BLOCK % 64 == 0, "a wave owns one word of the centre plane");
+  extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
+  const unsigned int item = item0 + blockIdx.x;
+  if (item >= n_items) return;
+  const WorkItem me = load_item(work, item);
+  if (me.f == kNoFrame) return;                 // the list has ended (every later entry is past its end too)
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  unsigned int *tile = lds;
+  unsigned long long *klds = reinterpret_cast<unsigned long long *>(lds + k.tile_words);
+  unsigned long long *amask = klds + (size_t)k.R * k.W;
+  unsigned int *total = reinterpret_cast<unsigned int *>(amask + (size_t)(k.R + 2) * k.W);
+  const int t0 = max(k.y_lo - 1, 0), t1 = min(k.y_hi + 1, k.gh);
+  const int crows = k.y_hi - k.y_lo;
+  const int W = k.W, gw = k.gw;
+
+  // The frame's stream, under a mask only: s = the number of streams that end at or before frame f (binary search on
+  // workgroup-uniform values).  s == n_streams: the frame lies behind the last stream and keeps what the clear wrote.
+  const unsigned int f = __builtin_amdgcn_readfirstlane(me.f);
+  const bool masked = keep != nullptr;
+  unsigned int s = 0u;
+  if (masked) {
+    unsigned int lo = 0u, hi = n_streams;
+    while (lo < hi) {
+      const unsigned int mid = lo + ((hi - lo) >> 1);
+      if (stream_off[mid + 1u] <= (unsigned long long)f) lo = mid + 1u; else hi = mid;
+    }
+    s = lo;
+    if (s >= n_streams) return;
+  }
+
+  // ---- the keep words of the analysed rows (no mask: ones), the first word of a lane on its way while the tile is zeroed
+  const int nkeep = crows * W;
+  const unsigned long long *kp = masked ? keep + ((size_t)s * (size_t)k.gh + (size_t)k.y_lo) * (size_t)W : nullptr;
+  const unsigned long long k0 = (masked && tid < nkeep) ? kp[tid] : ~0ull;
+  {
+    u32x4 *c4 = reinterpret_cast<u32x4 *>(tile);
+    const int n4 = k.tile_words >> 2;
+    for (int j = tid; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
+    if (tid < 8) total[tid] = (tid == 4 || tid == 5) ? 0xffffffffu : 0u;   // [4], [5]: minima
+  }
+  if (tid < nkeep) klds[tid] = k0;
+  for (int j = tid + BLOCK; j < nkeep; j += BLOCK) klds[j] = masked ? kp[j] : ~0ull;
+  __syncthreads();
+  // ---- the votes (an empty analysed range keeps nothing: nothing to read)
+  if (crows > 0) {
+    const auto one = [=, &k](const MvFields m) { vote(m, k, t0, tile); };
+    if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + me.r0 * 8ull, me.r1 - me.r0, one);
+    else stream_mv40<BLOCK, UNROLL>(mv + me.r0 * 40ull, me.r1 - me.r0, one);
+  }
+  __syncthreads();
+  // ---- the masks: the word of an analysed row [y_lo, y_hi) is ANDed with the keep word (keep row r <-> grid row y_lo + r)
+  row_masks<BLOCK>(tile, k, t0, t1, k.y_lo - 1, crows + 2, [=, &k](int j, int w, int g, unsigned long long m) {
+    const bool analysed = g >= k.y_lo && g < k.y_hi;           // then 0 <= g - y_lo < R: inside the staged keep rows
+    const unsigned long long kw = analysed ? klds[(size_t)(g - k.y_lo) * k.W + w] : ~0ull;
+    amask[(size_t)j * k.W + w] = m & kw;
+  });
+  __syncthreads();
+  // ---- the centre plane (over the keep words, dead now) and the count.  Every word is written, the empty ones too.
+  unsigned long long *cpl = klds;
+  for (int tk = tid; tk < nkeep; tk += BLOCK) {
+    const int r = tk / W, w = tk - r * W;
+    const unsigned long long c = centre_word(amask + (size_t)(r + 1) * W, w, W, gw);
+    cpl[tk] = c;
+    if (c) atomicAdd(&total[0], (unsigned int)__popcll(c));
+  }
+  __syncthreads();
+  const unsigned int ncentres = total[0];
+  if (ncentres == 0u) {                                       // workgroup-uniform: most frames of most streams
+    if (tid == 0) {
+      if (centres) centres[f] = 0u;
+      if (blobs) blobs[f] = 0u;
+      if (largest) largest[f] = 0u;
+      if (box) box[f] = BlobBox{0xffffu, 0xffffu, 0xffffu, 0xffffu};
+      if (flags) flags[f] = (unsigned char)0;
+    }
+    return;
+  }
+
+  // ---- labels.  L[r * gw + x], r < crows <= R: inside the tile's (R + 2) * gw words.
+  unsigned int *L = tile;
+  // init: the first cell of a horizontal run is a root, the others point at it.  Column 0 is never a centre, so the
+  // scan to the left ends at a clear bit; `ww >= 0` bounds it all the same.
+  for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
+    if (((cw >> lane) & 1ull) == 0ull) return;
+    const unsigned long long below = ~cw & ((1ull << lane) - 1ull);        // clear bits to the left of this cell, in its word
+    int xs;
+    if (below != 0ull) {
+      xs = w * 64 + 64 - __clzll((long long)below);
+    } else {
+      xs = w * 64;
+      for (int ww = w - 1; ww >= 0; --ww) {
+        const unsigned long long nz = ~cpl[tw - w + ww];
+        if (nz != 0ull) { xs = ww * 64 + 64 - __clzll((long long)nz); break; }
+        xs = ww * 64;
+      }
+    }
+    const int x = w * 64 + lane;
+    L[r * gw + x] = (x == xs) ? kRoot : (unsigned int)(r * gw + xs);
+  });
+  __syncthreads();
+  // unite: the first cell of every segment in which this row's centres lie under the row above's (per word: a segment
+  // that crosses a word seam is joined twice)
+  for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
+    if (r == 0) return;
+    const unsigned long long both = cw & cpl[tw - W];
+    const unsigned long long first = both & ~(both << 1);
+    if ((first >> lane) & 1ull) {
+      const unsigned int i = (unsigned int)(r * gw + w * 64 + lane);
+      unite(L, i, i - (unsigned int)gw);
+    }
+  });
+  __syncthreads();
+  // flatten and count: a cell that is no root stores its root and adds 1 to it — one add per (wave, distinct root)
+  for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
+    const unsigned int i = (unsigned int)(r * gw + w * 64 + lane);
+    unsigned int p = 0u;
+    bool todo = false;
+    if ((cw >> lane) & 1ull) {
+      p = find_root(L, i);
+      todo = p != i;
+      if (todo) __hip_atomic_store(&L[i], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    unsigned long long b;
+    while ((b = __ballot(todo)) != 0ull) {
+      const int leader = __ffsll((long long)b) - 1;
+      const unsigned int p0 = (unsigned int)__shfl((int)p, leader);
+      const bool same = todo && p == p0;
+      const unsigned long long sb = __ballot(same);
+      if (lane == leader) atomicAdd(&L[p0], (unsigned int)__popcll(sb));
+      todo = todo && !same;
+    }
+  });
+  __syncthreads();
+  // winner: the number of roots, and the largest (cells, smallest root index first)
+  unsigned long long *best = reinterpret_cast<unsigned long long *>(total + 2);
+  for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
+    const unsigned int i = (unsigned int)(r * gw + w * 64 + lane);
+    unsigned int v = 0u;
+    if ((cw >> lane) & 1ull) v = L[i];
+    const bool root = (v & kRoot) != 0u;
+    const unsigned long long rb = __ballot(root);
+    if (root) {
+      if (lane == __ffsll((long long)rb) - 1) atomicAdd(&total[1], (unsigned int)__popcll(rb));
+      atomicMax(best, ((unsigned long long)((v & ~kRoot) + 1u) << 32) | (unsigned long long)(0xffffffffu - i));
+    }
+  });
+  __syncthreads();
+  const unsigned long long key = *best;
+  const unsigned int win = 0xffffffffu - (unsigned int)(key & 0xffffffffull);
+  // box: LDS min / max over the winner's cells (its root, and every cell whose label is the root)
+  for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
+    const unsigned int i = (unsigned int)(r * gw + w * 64 + lane);
+    bool mine = false;
+    if ((cw >> lane) & 1ull) mine = i == win || L[i] == win;
+    const unsigned long long mb = __ballot(mine);
+    if (mine && lane == __ffsll((long long)mb) - 1) {
+      atomicMin(&total[4], (unsigned int)(w * 64 + lane));
+      atomicMax(&total[6], (unsigned int)(w * 64 + 63 - __clzll((long long)mb)));
+      atomicMin(&total[5], (unsigned int)r);
+      atomicMax(&total[7], (unsigned int)r);
+    }
+  });
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned int big = (unsigned int)(key >> 32);
+    if (centres) centres[f] = ncentres;
+    if (blobs) blobs[f] = total[1];
+    if (largest) largest[f] = big;
+    if (box) box[f] = BlobBox{(unsigned short)total[4], (unsigned short)(total[5] + (unsigned int)k.y_lo), (unsigned short)total[6],
+                              (unsigned short)(total[7] + (unsigned int)k.y_lo)};
+    if (flags) flags[f] = (unsigned char)((ncentres >= k.clust_need && big >= k.blob_need) ? 1 : 0);
+  }
+}
+
+namespace {
+
+template <int REC>
+hipError_t launch_frames(const BlobLaunch &L) {
+  auto kern = blobs_frames_kernel<kBlobBlock, kBlobUnroll, REC>;
+  static std::atomic<unsigned long long> ready{0ull};
+  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
+  if (e != hipSuccess) return e;
+  const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
+  return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
+    hipLaunchKernelGGL(kern, dim3(n), dim3(kBlobBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.k,
+                       L.stream_off, L.n_streams, L.keep, L.flags, L.centres, L.blobs, L.largest, L.box);
+  });
+}
+
+}  // namespace
+
+hipError_t launch_blob_scan(const BlobLaunch &L) {
+  if (L.n_frames == 0) return hipSuccess;
+  if (L.rec_bytes != 40 && L.rec_bytes != 8) return hipErrorInvalidValue;
+  if (!L.flags && !L.centres && !L.blobs && !L.largest && !L.box) return hipErrorInvalidValue;
+  if (L.keep ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0)) return hipErrorInvalidValue;
+  if (!L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records) return hipErrorInvalidValue;
+  if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.lds_bytes > L.lds_max ||
+      (size_t)L.lds_bytes < blob_lds_bytes(L.k.gw, L.k.R) || (size_t)L.k.tile_words != blob_tile_words(L.k.gw, L.k.R) ||
+      L.k.W != (L.k.gw + 63) / 64)
+    return hipErrorInvalidValue;
+  {
+    const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
+    hipLaunchKernelGGL(blobs_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream,
+                       L.flags, L.centres, L.blobs, L.largest, L.box, L.n_frames);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  // flags / centres null: the planner answers nothing itself (the outputs hold the clear's values already)
+  hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
+  if (e != hipSuccess) return e;
+  return L.rec_bytes == 8 ? launch_frames<8>(L) : launch_frames<40>(L);
+}
+
+}  // namespace mtgpu
