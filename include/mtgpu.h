@@ -462,4 +462,9 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * largest one's size and box, and a minimum-object-size flag — three more entry points, declared the same way. */
 #include "mtgpu_blobs.h"
 
+/* Motion blobs on the decode path: a pipe that applies the minimum blob size — with or without its keep mask — to every
+ * batch, and reports the centre count or the largest blob in its one count array (src/motion_scanner.cpp:272-294 at the
+ * call site of :375-383) — two more entry points, declared the same way. */
+#include "mtgpu_pipe_blobs.h"
+
 #endif /* MTGPU_H */

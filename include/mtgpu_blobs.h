@@ -50,7 +50,8 @@
  * (960x540 cells, 32767-wide grids: the grids the plain scan cuts into row bands) is MT_ERR_UNSUPPORTED.
  *
  * Out of scope: there is no pipe form (mtgpu_pipe_*), no mtgpu_scan_file option and no decode-path scanner for blobs;
- * a blob scan is a call on a batch.
+ * a blob scan is a call on a batch.  (That holds for the entry points of THIS header.  The decode path has its own:
+ * mtgpu_pipe_blobs.h puts the flag rule and one of the two counts into a pipe.)
  */
 #ifndef MTGPU_BLOBS_H
 #define MTGPU_BLOBS_H

@@ -214,6 +214,13 @@ ABI_BLOBS = {
                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_pipe_blobs.h declares (the blob setting of a pipe; mtgpu.h includes it).
+ABI_PIPE_BLOBS = {
+    "mtgpu_pipe_set_blobs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int]),
+    "mtgpu_pipe_blobs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+}
+MT_PIPE_REPORT_CENTRES, MT_PIPE_REPORT_LARGEST = 0, 1
+
 _lib = None
 
 
@@ -244,7 +251,8 @@ def load_library(path=None):
             "(or __graft_entry__.build()).  There is no fallback path.")
     lib = C.CDLL(p)
     for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
-            list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()):
+            list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
+            list(ABI_PIPE_BLOBS.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

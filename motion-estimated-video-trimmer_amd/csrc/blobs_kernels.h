@@ -54,12 +54,19 @@ struct BlobLaunch {
   const unsigned char *has_sd;            // n_frames or null
   unsigned int n_frames;
   int rec_bytes;                          // 40 or 8
-  const unsigned long long *stream_off;   // n_streams + 1; null iff keep is null
-  unsigned int n_streams;                 // 0 iff keep is null
-  const unsigned long long *keep;         // n_streams x gh x W, device memory; null: no mask, no stream lookup
-  unsigned char *flags;                   // n_frames bytes, device memory, or null
-  unsigned int *centres, *blobs, *largest;  // n_frames words each, or null
-  BlobBox *box;                           // n_frames boxes, or null
+  const unsigned long long *stream_off;   // n_streams + 1; null iff keep is null (pipe form: not read)
+  unsigned int n_streams;                 // 0 iff keep is null (pipe form: not read)
+  const unsigned long long *keep;         // n_streams x gh x W, device memory (pipe form: one plane); null: no mask, no stream lookup
+  unsigned char *flags;                   // n_frames bytes, device memory (pipe form: or pinned host memory), or null
+  unsigned int *centres, *blobs, *largest;  // n_frames words each, as flags, or null (pipe form: blobs is null, and at most one of centres / largest is given)
+  BlobBox *box;                           // n_frames boxes, or null (pipe form: null)
+  // The pipe form (pipe.hip's staging batches): ONE plane serves every frame — no stream lookup; no clear kernel —
+  // launch_plan gets flags and the one count array and answers the frames without side data; the results are stored at
+  // system scope where sys_flags / sys_centres say that the array is not device memory (a zero-copy batch's pinned
+  // block; sys_centres speaks of whichever of centres / largest is given).  The staging block has one count array: no
+  // blobs, no box, not both counts.  0: the form of mtgpu_scan_blobs_device — plain stores, sys_* must be 0.
+  int pipe = 0;
+  int sys_flags = 0, sys_centres = 0;
   BlobK k;
   int lds_bytes;
   int lds_max;                            // device limit of dynamic LDS per workgroup
@@ -70,7 +77,7 @@ struct BlobLaunch {
 };
 
 // Fills the non-null outputs with the answer of a frame without a blob (0; an all-0xFFFF box), builds the work list
-// (launch_plan), then one workgroup per entry.
+// (launch_plan), then one workgroup per entry.  Pipe form: no fill — the planner answers the frames without side data.
 hipError_t launch_blob_scan(const BlobLaunch &L);
 
 }  // namespace mtgpu

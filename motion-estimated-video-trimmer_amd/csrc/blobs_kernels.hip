@@ -30,6 +30,16 @@
 //   Every output element has one writer after the clear: lane 0 of the frame's workgroup, plain vector stores, no global
 //   atomics.
 //
+// The pipe form (template argument PIPE; BlobLaunch::pipe) serves a staging batch of pipe.hip, as zones_frames_kernel's:
+//     stream      none: a pipe feeds one recording, plane 0 of `keep` serves every frame — the search and its loads are
+//                 compiled out.  keep == nullptr is still "no mask".
+//     outputs     flags and ONE count array (centres or largest, the other null; no blobs, no box: the staging block has
+//                 one count array).  Either may be a zero-copy batch's pinned block: lane 0 stores them at system scope
+//                 when the launch says so (store_flag / store_centres of record_stream.h) — on BOTH exits, the early
+//                 `no centre` one too: in a reused pinned block it overwrites the previous batch's values.
+//     no clear    launch_plan is handed the outputs and answers the frames without side data itself, as in launch_scan:
+//                 planning + one kernel.
+//
 // The record loads, the streamers, the vote, the row masks and the centre test of a word are those of record_stream.h,
 // unchanged; the launch helpers are those of scan_kernels.h.
 #if !defined(__HIP_DEVICE_COMPILE__) || defined(__gfx950__)
@@ -103,12 +113,16 @@ __global__ __launch_bounds__(256) void blobs_clear_kernel(unsigned char *__restr
 
 // Waves per SIMD: as zones_frames_kernel — a 1080p workgroup takes about 35 KB of LDS, two workgroups of 16 waves share
 // a CU, eight waves per SIMD and so at most 64 VGPRs; the 4K workgroup sits alone on its CU.
-template <int BLOCK, int UNROLL, int REC>
+// PIPE: the form for a pipe's staging batch — stream_off / n_streams / blobs / box are not read (null / 0 / null / null),
+// plane 0 of `keep` serves every frame, at most one of centres / largest is given, and the results leave through
+// store_flag / store_centres with sys_flags / sys_centres (sys_centres: whichever count is given).  !PIPE: sys_* are not
+// read (0).
+template <int BLOCK, int UNROLL, int REC, bool PIPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void blobs_frames_kernel(
     const unsigned char *__restrict__ mv, const WorkItem *__restrict__ work, unsigned int item0, unsigned int n_items, BlobK k,
     const unsigned long long *__restrict__ stream_off, unsigned int n_streams, const unsigned long long *__restrict__ keep,
     unsigned char *__restrict__ flags, unsigned int *__restrict__ centres, unsigned int *__restrict__ blobs,
-    unsigned int *__restrict__ largest, BlobBox *__restrict__ box) {
+    unsigned int *__restrict__ largest, BlobBox *__restrict__ box, int sys_flags, int sys_centres) {
   static_assert(BLOCK % 64 == 0, "a wave owns one word of the centre plane");
   extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
   const unsigned int item = item0 + blockIdx.x;
@@ -130,7 +144,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const unsigned int f = __builtin_amdgcn_readfirstlane(me.f);
   const bool masked = keep != nullptr;
   unsigned int s = 0u;
-  if (masked) {
+  if (!PIPE && masked) {
     unsigned int lo = 0u, hi = n_streams;
     while (lo < hi) {
       const unsigned int mid = lo + ((hi - lo) >> 1);
@@ -179,11 +193,17 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const unsigned int ncentres = total[0];
   if (ncentres == 0u) {                                       // workgroup-uniform: most frames of most streams
     if (tid == 0) {
-      if (centres) centres[f] = 0u;
-      if (blobs) blobs[f] = 0u;
-      if (largest) largest[f] = 0u;
-      if (box) box[f] = BlobBox{0xffffu, 0xffffu, 0xffffu, 0xffffu};
-      if (flags) flags[f] = (unsigned char)0;
+      if constexpr (PIPE) {                                     // a reused pinned block holds the previous batch's values
+        if (centres) store_centres(centres, f, 0u, sys_centres);
+        if (largest) store_centres(largest, f, 0u, sys_centres);
+        if (flags) store_flag(flags, f, (unsigned char)0, sys_flags);
+      } else {
+        if (centres) centres[f] = 0u;
+        if (blobs) blobs[f] = 0u;
+        if (largest) largest[f] = 0u;
+        if (box) box[f] = BlobBox{0xffffu, 0xffffu, 0xffffu, 0xffffu};
+        if (flags) flags[f] = (unsigned char)0;
+      }
     }
     return;
   }
@@ -259,7 +279,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   __syncthreads();
   const unsigned long long key = *best;
   const unsigned int win = 0xffffffffu - (unsigned int)(key & 0xffffffffull);
-  // box: LDS min / max over the winner's cells (its root, and every cell whose label is the root)
+  // box: LDS min / max over the winner's cells (its root, and every cell whose label is the root).  In the PIPE form
+  // nothing reads the box or the blob count total[1]: both are computed all the same, on purpose — the five passes are
+  // those of the resident form, unchanged.
   for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
     const unsigned int i = (unsigned int)(r * gw + w * 64 + lane);
     bool mine = false;
@@ -275,27 +297,33 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   __syncthreads();
   if (tid == 0) {
     const unsigned int big = (unsigned int)(key >> 32);
-    if (centres) centres[f] = ncentres;
-    if (blobs) blobs[f] = total[1];
-    if (largest) largest[f] = big;
-    if (box) box[f] = BlobBox{(unsigned short)total[4], (unsigned short)(total[5] + (unsigned int)k.y_lo), (unsigned short)total[6],
-                              (unsigned short)(total[7] + (unsigned int)k.y_lo)};
-    if (flags) flags[f] = (unsigned char)((ncentres >= k.clust_need && big >= k.blob_need) ? 1 : 0);
+    if constexpr (PIPE) {
+      if (centres) store_centres(centres, f, ncentres, sys_centres);
+      if (largest) store_centres(largest, f, big, sys_centres);
+      if (flags) store_flag(flags, f, (unsigned char)((ncentres >= k.clust_need && big >= k.blob_need) ? 1 : 0), sys_flags);
+    } else {
+      if (centres) centres[f] = ncentres;
+      if (blobs) blobs[f] = total[1];
+      if (largest) largest[f] = big;
+      if (box) box[f] = BlobBox{(unsigned short)total[4], (unsigned short)(total[5] + (unsigned int)k.y_lo), (unsigned short)total[6],
+                                (unsigned short)(total[7] + (unsigned int)k.y_lo)};
+      if (flags) flags[f] = (unsigned char)((ncentres >= k.clust_need && big >= k.blob_need) ? 1 : 0);
+    }
   }
 }
 
 namespace {
 
-template <int REC>
+template <int REC, bool PIPE>
 hipError_t launch_frames(const BlobLaunch &L) {
-  auto kern = blobs_frames_kernel<kBlobBlock, kBlobUnroll, REC>;
+  auto kern = blobs_frames_kernel<kBlobBlock, kBlobUnroll, REC, PIPE>;
   static std::atomic<unsigned long long> ready{0ull};
   hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
   if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
   return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
     hipLaunchKernelGGL(kern, dim3(n), dim3(kBlobBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.k,
-                       L.stream_off, L.n_streams, L.keep, L.flags, L.centres, L.blobs, L.largest, L.box);
+                       L.stream_off, L.n_streams, L.keep, L.flags, L.centres, L.blobs, L.largest, L.box, L.sys_flags, L.sys_centres);
   });
 }
 
@@ -305,12 +333,24 @@ hipError_t launch_blob_scan(const BlobLaunch &L) {
   if (L.n_frames == 0) return hipSuccess;
   if (L.rec_bytes != 40 && L.rec_bytes != 8) return hipErrorInvalidValue;
   if (!L.flags && !L.centres && !L.blobs && !L.largest && !L.box) return hipErrorInvalidValue;
-  if (L.keep ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0)) return hipErrorInvalidValue;
+  if (L.pipe) {
+    if (L.blobs || L.box || (L.centres && L.largest)) return hipErrorInvalidValue;
+  } else {
+    if (L.sys_flags != 0 || L.sys_centres != 0) return hipErrorInvalidValue;
+    if (L.keep ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0)) return hipErrorInvalidValue;
+  }
   if (!L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records) return hipErrorInvalidValue;
   if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.lds_bytes > L.lds_max ||
       (size_t)L.lds_bytes < blob_lds_bytes(L.k.gw, L.k.R) || (size_t)L.k.tile_words != blob_tile_words(L.k.gw, L.k.R) ||
       L.k.W != (L.k.gw + 63) / 64)
     return hipErrorInvalidValue;
+  if (L.pipe) {
+    // The planner is handed the outputs and answers every frame without side data itself (at the outputs' scope), as in
+    // launch_scan and launch_zone_scan: no clear kernel — planning + one kernel.  Its count array is whichever is given.
+    hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres ? L.centres : L.largest, L.sys_centres);
+    if (e != hipSuccess) return e;
+    return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
+  }
   {
     const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
     hipLaunchKernelGGL(blobs_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream,
@@ -321,7 +361,7 @@ hipError_t launch_blob_scan(const BlobLaunch &L) {
   // flags / centres null: the planner answers nothing itself (the outputs hold the clear's values already)
   hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
   if (e != hipSuccess) return e;
-  return L.rec_bytes == 8 ? launch_frames<8>(L) : launch_frames<40>(L);
+  return L.rec_bytes == 8 ? launch_frames<8, false>(L) : launch_frames<40, false>(L);
 }
 
 }  // namespace mtgpu

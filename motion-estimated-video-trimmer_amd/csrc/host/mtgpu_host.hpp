@@ -720,6 +720,8 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   bool keep_centres_ = false;                          // keep_centres(): the pipe carries centre counts, scan_range keeps them
   std::vector<std::pair<double, uint32_t>> last_centres_;
   std::vector<uint64_t> keep_;                         // set_keep(): the keep mask initialize() hands to the pipe; empty: none
+  int min_blob_cells_ = 0;                             // set_min_blob_cells(): the pipe's blob setting; 0: off
+  bool report_largest_ = false;                        // report_largest(): last_centres() holds the largest blob, not the centres
   bool ok(int rc) {
     if (rc == MT_OK) return true;
     err_ = mtgpu_last_error();
@@ -823,6 +825,14 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   // initialize() ALWAYS settles the pipe's mask — it sets this one or clears whatever the pipe carries: a GpuBackend
   // lives on from one video to the next, and the next video must never inherit the previous one's zones.
   void set_keep(std::vector<uint64_t> words) { keep_ = std::move(words); }
+  // Call before initialize().  A minimum blob size for this video (include/mtgpu_pipe_blobs.h): every check_frame of
+  // scan_range (:375-383) then also asks that the largest 4-connected blob of the frame's centres (:272-294) has at
+  // least n cells.  0: off.  report_largest(true): last_centres() returns {pts, largest blob} in place of the centre
+  // counts (needs keep_centres(true): the pipe has ONE count array); the blob scan is then on at n = max(1, n), and
+  // n <= 1 leaves the flags those of the plain scan (mtgpu_blobs.h, Consequences).  Like the mask, initialize() ALWAYS
+  // settles the pipe's blob setting — it sets this one or turns off whatever a pooled pipe carries.
+  void set_min_blob_cells(int n) { min_blob_cells_ = n; }
+  void report_largest(bool on) { report_largest_ = on; }
 
   // batch_records == 0: sized from the source and the staging layout — MTGPU_BATCH_MB MiB of
   // pinned staging per batch, and never less than two frames of one record per 4x4 block (the
@@ -838,6 +848,17 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
     if (!be_->ensure(src_.width(), src_.height(), device_, batch_records, batch_frames, n_buffers, err_, keep_centres_)) return false;
     pipe_ = be_->pipe();
     // the pipe is idle here (a previous scanner on this backend left nothing in flight, or the backend was rebuilt)
+    {
+      if (min_blob_cells_ < 0) { err_ = "min_blob_cells is " + std::to_string(min_blob_cells_); (void)mtgpu_pipe_set_blobs(pipe_, 0, 0); pipe_ = nullptr; return false; }
+      if (report_largest_ && !keep_centres_) { err_ = "report_largest needs keep_centres: the largest blob travels in the pipe's count array"; (void)mtgpu_pipe_set_blobs(pipe_, 0, 0); pipe_ = nullptr; return false; }
+      const int n = report_largest_ ? std::max(1, min_blob_cells_) : min_blob_cells_;
+      if (mtgpu_pipe_set_blobs(pipe_, n, n > 0 && report_largest_ ? MT_PIPE_REPORT_LARGEST : MT_PIPE_REPORT_CENTRES) != MT_OK) {
+        err_ = mtgpu_last_error();
+        (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);               // whatever fails here, no stale setting stays behind
+        pipe_ = nullptr;
+        return false;
+      }
+    }
     if (keep_.empty()) {
       if (mtgpu_pipe_set_keep(pipe_, nullptr) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
     } else {
@@ -946,8 +967,22 @@ struct PipelineResult {
   // In: the keep mask of this video (GpuMotionScanner::set_keep; load_keep's words), handed to every worker's scanner.
   // Empty: none — and a pooled backend that carried another video's mask is cleared.
   std::vector<uint64_t> keep;
+  // Blobs (GpuMotionScanner::set_min_blob_cells / report_largest; include/mtgpu_pipe_blobs.h).  In: min_blob_cells (0:
+  // off) — `segments` are then those of frames whose largest blob has at least that many cells; blob_sweep_levels —
+  // every worker's pipe reports the largest blob in place of the centre count (the pipe has ONE count array: not
+  // together with keep_centres / sweep_levels), `centres` then holds {pts, largest} and `blob_sweep` = for every level
+  // L >= max(1, CLUSTERS_NEEDED) what this result's segments / merge would be with min_blob_cells = L, from the ONE scan
+  // (mtgpu_blobs.h: largest >= L implies centres >= L).  -1 / empty: blob_options().
+  int min_blob_cells = -1;
+  std::vector<int> blob_sweep_levels;
+  std::vector<SweepEntry> blob_sweep;                  // SweepEntry::clusters_needed holds the level L
   std::string error;
 };
+
+// Process-wide defaults for PipelineResult::min_blob_cells / blob_sweep_levels (a front end's --min-blob-cells /
+// --sweep-blobs): set before the first pipeline starts, read by every run_scan_pipeline.
+struct BlobOptions { int min_blob_cells = 0; std::vector<int> sweep_levels; };
+inline BlobOptions &blob_options() { static BlobOptions o; return o; }
 
 // Process-wide defaults for PipelineResult::keep_centres / sweep_levels (a front end's --centres / --sweep): set before
 // the first pipeline starts, read by every run_scan_pipeline.
@@ -989,7 +1024,19 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
   std::atomic<uint64_t> frames_scanned{0};
   std::atomic<long> worker_cpu_us{0};
   if (out.sweep_levels.empty()) out.sweep_levels = centre_options().sweep_levels;
-  const bool keep_centres = out.keep_centres || centre_options().keep || !out.sweep_levels.empty();
+  if (out.min_blob_cells < 0) out.min_blob_cells = blob_options().min_blob_cells;
+  if (out.blob_sweep_levels.empty()) out.blob_sweep_levels = blob_options().sweep_levels;
+  const bool report_largest = !out.blob_sweep_levels.empty();
+  if (report_largest && (out.keep_centres || centre_options().keep || !out.sweep_levels.empty())) {
+    out.error = "blob_sweep_levels together with keep_centres / sweep_levels: the pipe has one count array";
+    return 1;
+  }
+  for (int level : out.blob_sweep_levels)
+    if (level < std::max(1, (int)Config::clusters_needed())) {
+      out.error = "blob sweep level " + std::to_string(level) + " is below max(1, CLUSTERS_NEEDED)";
+      return 1;
+    }
+  const bool keep_centres = out.keep_centres || centre_options().keep || !out.sweep_levels.empty() || report_largest;
   std::mutex centres_mu;
   const auto wall0 = std::chrono::high_resolution_clock::now();
   std::mutex err_mu;
@@ -1027,6 +1074,8 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
         scanners[i] = std::make_unique<GpuMotionScanner>(*sources[i], dev, shared);
         scanners[i]->keep_centres(keep_centres);
         scanners[i]->set_keep(out.keep);
+        scanners[i]->set_min_blob_cells(out.min_blob_cells);
+        scanners[i]->report_largest(report_largest);
         if (!scanners[i]->initialize()) {                                // :198-199 (here: reported)
           fail_with(scanners[i]->error());
           return;
@@ -1092,7 +1141,9 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
   out.segments.resize(out.merge.n_segments);
   std::stable_sort(out.centres.begin(), out.centres.end(),
                    [](const std::pair<double, uint32_t> &a, const std::pair<double, uint32_t> &b) { return a.first < b.first; });
-  for (int level : out.sweep_levels) {                                   // the same merge on each level's timestamps
+  // the same merge on each level's timestamps: `centres` holds the centre counts (sweep_levels) or the largest blobs
+  // (blob_sweep_levels), never both
+  for (int level : report_largest ? out.blob_sweep_levels : out.sweep_levels) {
     PipelineResult::SweepEntry e;
     e.clusters_needed = level;
     const uint32_t need = level < 1 ? 1u : (uint32_t)level;              // motion_scanner.cpp:288
@@ -1102,7 +1153,7 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
     rc = mtgpu_merge_segments(merge_ctx, ts.data(), ts.size(), &mp, 1, e.segments.data(), e.segments.size(), &e.merge);
     if (rc != MT_OK) { out.error = mtgpu_last_error(); return 1; }
     e.segments.resize(e.merge.n_segments);
-    out.sweep.push_back(std::move(e));
+    (report_largest ? out.blob_sweep : out.sweep).push_back(std::move(e));
   }
   return 0;
 }

@@ -1,7 +1,7 @@
 // mtgpu_scan_file — the scan + merge half of `motion_trim` on the GPU, reading extracted motion
 // vectors from .mtmv containers instead of decoding with FFmpeg:
 //   mtgpu_scan_file stream.mtmv [more.mtmv ...] [--threads T] [--streams S] [--outdir DIR] [--timestamps] [--summary]
-//                   [--centres] [--sweep K1,K2,...] [--keep MASK.mtkeep]
+//                   [--centres] [--sweep K1,K2,...] [--keep MASK.mtkeep] [--min-blob-cells N] [--sweep-blobs L1,L2,...]
 //   (--streams 0 / --threads 0: the reference's own sizing from PARALLEL_STREAMS / THREADS_PER_STREAM and the CPU limit)
 // One file: like `motion_trim in out` (single ProcessingPipeline).  Several files: like
 // `motion_trim in_dir out_dir` (BatchProcessor): S streams x T workers, jobs consumed by one
@@ -16,6 +16,13 @@
 // written by `python -m mvtrim_amd.zones --save-mask MASK.mtkeep`): check_frame's :282 gets one more term, so the
 // segments are those of the recording without the ignored cells.  An input whose grid is not the mask's fails with the
 // parser's message, the others go on.  The printed job gains "ignored_cells": N; without the option nothing changes.
+// --min-blob-cells N: a minimum object size (include/mtgpu_pipe_blobs.h) — a frame has motion iff its centre count
+// reaches CLUSTERS_NEEDED AND the largest 4-connected blob of its centres has at least N cells; under --keep both are
+// taken on the masked cells.  --sweep-blobs 8,12,20: the pipes report every frame's largest blob; the job gains
+// "largest": [[pts, n], ...] and "sweep_blobs": one entry per level L, in the format of "sweep", with the segments this
+// tool prints when run with --min-blob-cells L — from the one scan.  A level must be at least max(1, CLUSTERS_NEEDED).
+// --sweep-blobs together with --centres or --sweep is refused: a pipe has one count array.  Without the two options
+// the output is unchanged.
 // --summary (several files): one more line {"batch_summary": ...} — frames scanned, wall time, worker-time
 // breakdown and what the S x T workers held (contexts, pipes, HIP streams, pinned / device bytes).
 #include <cmath>
@@ -73,6 +80,7 @@ static bool g_summary = false;    // --summary
 static bool g_print_ts = false;   // --timestamps: also print the pooled motion timestamps, sorted (%.17g)
 static bool g_print_centres = false;   // --centres
 static std::string g_keep_path;        // --keep
+static bool g_print_largest = false;   // --sweep-blobs
 
 // The keep mask of g_keep_path for a width x height input; throws with load_keep's message (the line is named) when the
 // file is malformed or made for another grid.
@@ -124,18 +132,25 @@ static void print_job(const std::string &input, const PipelineResult &r, const s
     for (size_t i = 0; i < r.centres.size(); ++i) std::printf("%s[%.17g, %u]", i ? ", " : "", r.centres[i].first, r.centres[i].second);
     std::printf("]");
   }
-  if (!r.sweep.empty()) {
-    std::printf(", \"sweep\": [");
-    for (size_t k = 0; k < r.sweep.size(); ++k) {
-      const PipelineResult::SweepEntry &e = r.sweep[k];
-      std::printf("%s{\"clusters_needed\": %d, \"segments\": [", k ? ", " : "", e.clusters_needed);
+  if (g_print_largest) {
+    std::printf(", \"largest\": [");
+    for (size_t i = 0; i < r.centres.size(); ++i) std::printf("%s[%.17g, %u]", i ? ", " : "", r.centres[i].first, r.centres[i].second);
+    std::printf("]");
+  }
+  const auto print_sweep = [](const char *name, const char *level, const std::vector<PipelineResult::SweepEntry> &sweep) {
+    std::printf(", \"%s\": [", name);
+    for (size_t k = 0; k < sweep.size(); ++k) {
+      const PipelineResult::SweepEntry &e = sweep[k];
+      std::printf("%s{\"%s\": %d, \"segments\": [", k ? ", " : "", level, e.clusters_needed);
       for (size_t i = 0; i < e.segments.size(); ++i)
         std::printf("%s[%.17g, %.17g]", i ? ", " : "", e.segments[i].start, e.segments[i].end);
       std::printf("], \"do_cut\": %d, \"saved_pct\": %.17g, \"n_timestamps\": %llu}", e.merge.do_cut, e.merge.saved_pct,
                   (unsigned long long)e.merge.n_timestamps);
     }
     std::printf("]");
-  }
+  };
+  if (!r.sweep.empty()) print_sweep("sweep", "clusters_needed", r.sweep);
+  if (!r.blob_sweep.empty()) print_sweep("sweep_blobs", "min_blob_cells", r.blob_sweep);
   std::printf("}\n");
   std::fflush(stdout);
 }
@@ -167,7 +182,47 @@ int main(int argc, char **argv) {
       if (i + 1 >= argc) { std::fprintf(stderr, "error: --keep takes the path of a .mtkeep file\n"); return 2; }
       g_keep_path = argv[++i];
     }
+    else if (!std::strcmp(argv[i], "--min-blob-cells")) {
+      char *end = nullptr;
+      const long v = i + 1 < argc ? std::strtol(argv[i + 1], &end, 10) : -1;
+      if (i + 1 >= argc || end == argv[i + 1] || *end || v < 0 || v > 0x7fffffffL) {
+        std::fprintf(stderr, "error: --min-blob-cells takes a cell count >= 0\n");
+        return 2;
+      }
+      ++i;
+      blob_options().min_blob_cells = (int)v;
+    }
+    else if (!std::strcmp(argv[i], "--sweep-blobs")) {
+      const char *q = i + 1 < argc ? argv[++i] : "";
+      if (!*q) { std::fprintf(stderr, "error: --sweep-blobs takes a comma-separated list of integers\n"); return 2; }
+      while (*q) {
+        char *end = nullptr;
+        const long v = std::strtol(q, &end, 10);
+        if (end == q || (*end && (*end != ',' || !end[1])) || v > 0x7fffffffL || v < -0x7fffffffL) {
+          std::fprintf(stderr, "error: --sweep-blobs takes a comma-separated list of integers\n");
+          return 2;
+        }
+        blob_options().sweep_levels.push_back((int)v);
+        q = *end ? end + 1 : end;
+      }
+      g_print_largest = true;
+    }
     else files.push_back(argv[i]);
+  }
+  // what the blob options cannot be combined with: answered here, before any device call
+  if (g_print_largest) {
+    if (g_print_centres || !centre_options().sweep_levels.empty()) {
+      std::fprintf(stderr, "error: --sweep-blobs cannot be combined with --centres or --sweep: a pipe has one count array\n");
+      return 2;
+    }
+    int need = 1;
+    try { need = std::max(1, Config::clusters_needed()); }
+    catch (const std::exception &e) { std::fprintf(stderr, "error: configuration: %s\n", e.what()); return 1; }
+    for (int level : blob_options().sweep_levels)
+      if (level < need) {
+        std::fprintf(stderr, "error: --sweep-blobs level %d is below max(1, CLUSTERS_NEEDED) = %d\n", level, need);
+        return 2;
+      }
   }
   // --streams 0 / --threads 0: sized from the CPU budget, the devices and the number of videos (default_batch_sizing,
   // mtgpu_host.hpp — deliberately not the reference's CPU-only rule, src/system.cpp:186-197); PARALLEL_STREAMS /

@@ -2007,10 +2007,14 @@ int blobs_plan(const mt_scan_params &p, int lds_max, mtgpu_blobs_plan *out) {
 }
 
 // The blob scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
+// own_plan_ws: the caller's own block for the work list (a pipe's batch; ctx_plan_ws_bytes(n_frames) bytes, 256-byte
+// aligned) — the launch then takes NOTHING from the context's scratch ring — and the pipe form of the launch: one plane
+// or none, no clear kernel, flags and one count stored at system scope when `outputs_in_host_memory`.  nullptr: the
+// ring, the stream form.
 int blobs_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
              const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, const uint64_t *d_keep,
              int32_t min_blob_cells, uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_blobs, uint32_t *d_largest,
-             mt_blob_box *d_box, hipStream_t st) {
+             mt_blob_box *d_box, hipStream_t st, void *own_plan_ws = nullptr, int outputs_in_host_memory = 0) {
   mtgpu_blobs_plan bp;
   int rc = blobs_plan(c->params, c->lds_max, &bp);
   if (rc != MT_OK) return rc;
@@ -2041,9 +2045,16 @@ int blobs_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records,
   L.ev_planned = nullptr;
   void *scratch = nullptr;
   int slot = -1;
-  rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-  if (rc != MT_OK) return rc;
-  L.plan_ws = scratch;
+  if (own_plan_ws) {
+    L.pipe = 1;
+    L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
+    L.sys_centres = ((d_centres || d_largest) && outputs_in_host_memory) ? 1 : 0;
+    L.plan_ws = own_plan_ws;
+  } else {
+    rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
+    if (rc != MT_OK) return rc;
+    L.plan_ws = scratch;
+  }
   hipError_t e = hipSuccess;
   if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
     mtgpu_ctx::Profile &pf = c->prof;
@@ -2068,6 +2079,25 @@ int blobs_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records,
 }
 
 }  // namespace
+
+namespace mtgpu {
+int ctx_blobs_supported(const mtgpu_ctx *c) {
+  mtgpu_blobs_plan bp;
+  return blobs_plan(c->params, c->lds_max, &bp);
+}
+int ctx_launch_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
+                     uint32_t n_frames, const uint64_t *d_keep, int32_t min_blob_cells, int report_largest, uint8_t *d_flags,
+                     uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
+                     size_t plan_ws_bytes) {
+  if (n_frames == 0) return MT_OK;
+  if (min_blob_cells < 1) return fail(MT_ERR_INVALID, "blob pipe scan with min_blob_cells %d", (int)min_blob_cells);
+  if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
+    return fail(MT_ERR_INVALID, "blob pipe scan: the batch's work-list block is missing, misaligned or too small");
+  return blobs_on(c, d_rec, rec_bytes, n_records, 0, d_off, d_sd, n_frames, nullptr, 0, d_keep, min_blob_cells, d_flags,
+                  report_largest ? nullptr : d_count, nullptr, report_largest ? d_count : nullptr, nullptr, st, plan_ws,
+                  outputs_in_host_memory ? 1 : 0);
+}
+}  // namespace mtgpu
 
 extern "C" {
 

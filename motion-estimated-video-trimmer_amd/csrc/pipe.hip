@@ -107,6 +107,11 @@ struct mtgpu_pipe {
   uint64_t *d_keep = nullptr;
   uint64_t keep_words = 0;
   bool masked = false;
+  // mtgpu_pipe_set_blobs (include/mtgpu_pipe_blobs.h): min_blob > 0: every submit runs the blob scan (ctx_launch_blobs),
+  // under the keep plane when `masked`; `report`: which count the batch's one count array receives
+  // (MT_PIPE_REPORT_*).  Both change only while no batch is being filled or in flight.
+  int32_t min_blob = 0;
+  int report = 0;
   std::vector<mtgpu_batch *> bufs;
   std::deque<mtgpu_batch *> inflight;
   std::mutex mu;
@@ -392,7 +397,11 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
       rc = fail(MT_ERR_DEVICE, "injected submit failure (MTGPU_INJECT_SUBMIT_FAIL)");
       goto bad;
     }
-    if (p->masked)   // mtgpu_pipe_set_keep: the masked scan, its work list in the batch's own block like the plain one's
+    if (p->min_blob > 0)   // mtgpu_pipe_set_blobs: the blob scan, under the pipe's keep plane when it has a mask
+      rc = mtgpu::ctx_launch_blobs(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
+                                   p->min_blob, p->report == MT_PIPE_REPORT_LARGEST ? 1 : 0, b->d_flags, b->d_centres, st,
+                                   b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
+    else if (p->masked)   // mtgpu_pipe_set_keep: the masked scan, its work list in the batch's own block like the plain one's
       rc = mtgpu::ctx_launch_zones(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->d_keep, b->d_flags,
                                    b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
     else
@@ -527,6 +536,37 @@ int mtgpu_pipe_has_keep(const mtgpu_pipe *p) {
   if (!p) return -1;
   std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
   return p->masked ? 1 : 0;
+}
+
+int mtgpu_pipe_set_blobs(mtgpu_pipe *p, int32_t min_blob_cells, int report) {
+  if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
+  if (min_blob_cells < 0) return fail(MT_ERR_INVALID, "min_blob_cells is %d: want 0 (off) or a cell count >= 1", (int)min_blob_cells);
+  if (min_blob_cells > 0) {
+    if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_LARGEST)
+      return fail(MT_ERR_INVALID, "report is %d: want MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_LARGEST", report);
+    if (report == MT_PIPE_REPORT_LARGEST && !p->centres)
+      return fail(MT_ERR_INVALID, "MT_PIPE_REPORT_LARGEST needs a pipe with MT_LAYOUT_CENTRES: the largest blob travels in its count array");
+  }
+  std::lock_guard<std::mutex> lock(p->mu);
+  for (const mtgpu_batch *b : p->bufs)
+    if (b->state == 1 || b->state == 2)
+      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the blob setting",
+                  b->state == 1 ? "being filled" : "in flight");
+  if (min_blob_cells == 0) { p->min_blob = 0; p->report = 0; return MT_OK; }
+  const int rc = mtgpu::ctx_blobs_supported(p->ctx);         // MT_ERR_UNSUPPORTED, the grid named: nothing changes
+  if (rc != MT_OK) return rc;
+  p->min_blob = min_blob_cells;
+  p->report = report;
+  return MT_OK;
+}
+
+int mtgpu_pipe_blobs(const mtgpu_pipe *p, int32_t *min_blob_cells, int *report) {
+  if (!p) return -1;
+  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
+  if (p->min_blob <= 0) return 0;
+  if (min_blob_cells) *min_blob_cells = p->min_blob;
+  if (report) *report = p->report;
+  return 1;
 }
 
 int mtgpu_pipe_release(mtgpu_pipe *p, mtgpu_batch *b) {

@@ -955,6 +955,26 @@ class ScanPipe:
         """True while the pipe's submits run the masked scan (mtgpu_pipe_has_keep)."""
         return self._lib.mtgpu_pipe_has_keep(self._pipe) == 1
 
+    def set_blobs(self, min_blob_cells: int, report: str = "centres"):
+        """A minimum blob size on the decode path (mtgpu_pipe_set_blobs): from now on every batch of this pipe runs the
+        blob scan — flag = centres >= max(1, clusters_needed) AND largest blob >= min_blob_cells (the centres of
+        src/motion_scanner.cpp:272-294, under the keep mask if the pipe has one).  min_blob_cells 0: off, the pipe as it
+        was.  report: which count drain_centres() returns, "centres" or "largest" (the staging block has one count
+        array; "largest" needs centres=True).  Only while no batch is being filled or in flight (call drain() first):
+        otherwise MtgpuError(MT_ERR_BUSY) and nothing changes."""
+        codes = {"centres": _abi.MT_PIPE_REPORT_CENTRES, "largest": _abi.MT_PIPE_REPORT_LARGEST}
+        if report not in codes:
+            raise ValueError(f"report is {report!r}, not 'centres' or 'largest'")
+        check(self._lib.mtgpu_pipe_set_blobs(self._pipe, int(min_blob_cells), codes[report]))
+
+    @property
+    def blobs(self) -> Optional[Tuple[int, str]]:
+        """None, or (min_blob_cells, report) while the pipe's submits run the blob scan (mtgpu_pipe_blobs)."""
+        n, r = C.c_int32(), C.c_int()
+        if self._lib.mtgpu_pipe_blobs(self._pipe, C.byref(n), C.byref(r)) != 1:
+            return None
+        return int(n.value), ("largest" if r.value == _abi.MT_PIPE_REPORT_LARGEST else "centres")
+
     def _collect_one(self):
         b, fl, pts, tags, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32()
         rc = self._lib.mtgpu_pipe_collect(self._pipe, C.byref(b), C.byref(fl), C.byref(pts), C.byref(tags),
@@ -1027,7 +1047,8 @@ class ScanPipe:
         return out
 
     def drain_centres(self) -> List[Tuple[float, int, int, int]]:
-        """drain() of a pipe created with centres=True: (pts, flag, tag, centres) in submission order."""
+        """drain() of a pipe created with centres=True: (pts, flag, tag, count) in submission order — the centre count,
+        or the largest blob's cell count after set_blobs(n, report="largest")."""
         if not self._centres:
             raise _abi.MtgpuError(_abi.MT_ERR_INVALID, "the pipe was created without centres=True / LAYOUT_CENTRES")
         out = self.drain()
