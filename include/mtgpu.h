@@ -467,4 +467,8 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * call site of :375-383) — two more entry points, declared the same way. */
 #include "mtgpu_pipe_blobs.h"
 
+/* Global-motion compensation: the centre scan on the residuals of each frame's dominant vector
+ * (src/motion_scanner.cpp:246-251 thresholds a vector's own magnitude) — three more entry points, declared the same way. */
+#include "mtgpu_gmc.h"
+
 #endif /* MTGPU_H */

@@ -34,6 +34,10 @@ MV_DTYPE = np.dtype(
 SEGMENT_DTYPE = np.dtype([("start", "<f8"), ("end", "<f8")])
 # mt_blob_box (include/mtgpu_blobs.h): inclusive cell bounds of a frame's largest blob, all 0xFFFF: no blob
 BLOB_BOX_DTYPE = np.dtype([("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2")])
+# mt_gmc_info (include/mtgpu_gmc.h): the applied vector, the modes of the two axes, the counted records, the modes' counts
+GMC_INFO_DTYPE = np.dtype([("gx", "<i2"), ("gy", "<i2"), ("mode_x", "<i2"), ("mode_y", "<i2"), ("n_in", "<u4"), ("n_x", "<u4"),
+                           ("n_y", "<u4")])
+GMC_MAX_SHIFT, GMC_DEFAULT_MAX_SHIFT, GMC_DEFAULT_MIN_SHARE_Q8 = 127, 16, 128
 MERGE_PARAMS_DTYPE = np.dtype([("max_gap_sec", "<f8"), ("padding_sec", "<f8"),
                                ("duration", "<f8"), ("min_savings_pct", "<f8")])
 MERGE_RESULT_DTYPE = np.dtype([("n_timestamps", "<u8"), ("n_segments", "<u8"),
@@ -83,6 +87,10 @@ class ZonesPlanC(C.Structure):
 class BlobsPlanC(C.Structure):
     _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("keep_words_per_row", C.c_int32),
                 ("keep_words_per_stream", C.c_int32)]
+
+
+class GmcPlanC(C.Structure):
+    _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("hist_bins", C.c_int32), ("info_bytes", C.c_int32)]
 
 
 class CtxStatsC(C.Structure):
@@ -221,6 +229,15 @@ ABI_PIPE_BLOBS = {
 }
 MT_PIPE_REPORT_CENTRES, MT_PIPE_REPORT_LARGEST = 0, 1
 
+# name -> (restype, argtypes): every symbol include/mtgpu_gmc.h declares (global-motion compensation; mtgpu.h includes it).
+ABI_GMC = {
+    "mtgpu_gmc_preview": (C.c_int, [C.POINTER(ScanParamsC), C.c_int, C.POINTER(GmcPlanC)]),
+    "mtgpu_scan_gmc_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtgpu_scan_frames_gmc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -252,7 +269,7 @@ def load_library(path=None):
     lib = C.CDLL(p)
     for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
             list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
-            list(ABI_PIPE_BLOBS.items()):
+            list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

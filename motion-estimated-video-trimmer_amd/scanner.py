@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _abi, config
 from ._abi import (BLOB_BOX_DTYPE, BlobsPlanC, COMPACT_DTYPE, LAYOUT_AOS40, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
+                   GMC_DEFAULT_MAX_SHIFT, GMC_DEFAULT_MIN_SHARE_Q8, GMC_INFO_DTYPE, GmcPlanC,
                    MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PlanC, ScanParamsC, SweepPlanC, ZonesPlanC, check,
                    load_library)
 
@@ -222,6 +223,16 @@ def blobs_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     c = params.to_c()
     check(load_library().mtgpu_blobs_preview(C.byref(c), int(lds_bytes), C.byref(p)))
     return {n: getattr(p, n) for n, _ in BlobsPlanC._fields_}
+
+
+def gmc_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
+    """How the compensated scan runs on the grid of `params` with that much LDS per workgroup (mtgpu_gmc_preview): LDS
+    bytes, lanes, histogram bins per axis, bytes of one GMC_INFO_DTYPE element.  Host arithmetic only: works without a
+    GPU.  MtgpuError(MT_ERR_UNSUPPORTED) for a grid the compensated scan has no form for."""
+    p = GmcPlanC()
+    c = params.to_c()
+    check(load_library().mtgpu_gmc_preview(C.byref(c), int(lds_bytes), C.byref(p)))
+    return {n: getattr(p, n) for n, _ in GmcPlanC._fields_}
 
 
 ACTIVITY_OUTPUTS = ("active", "centre", "frames")
@@ -635,6 +646,60 @@ class MotionScanner:
             None if d_sd is None else d_sd.data_ptr(), n_frames, d_stream_off.data_ptr(), ns, d_keep.data_ptr(),
             ptr(flags), ptr(centres), ptr(centres_all), st))
         return flags, centres, centres_all
+
+    # -------------------------------------------------------- global-motion compensation
+    def scan_gmc(self, batch: FrameBatch, max_shift: int = GMC_DEFAULT_MAX_SHIFT, min_share_q8: int = GMC_DEFAULT_MIN_SHARE_Q8):
+        """The centre scan of a host batch on the residuals of each frame's dominant vector (mtgpu_scan_frames_gmc): the
+        per-axis mode of the displacements of the records inside the analysed rows, within +-max_shift, is subtracted
+        where at least min_share_q8 / 256 of those records agree on it; then src/motion_scanner.cpp:246-292 as
+        count_centres runs it.  Returns (flags uint8 [F], centres uint32 [F], info GMC_INFO_DTYPE [F])."""
+        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
+        n = max(len(off) - 1, 0)
+        flags = np.zeros(n, dtype=np.uint8)
+        centres = np.zeros(n, dtype=np.uint32)
+        info = np.zeros(n, dtype=GMC_INFO_DTYPE)
+        check(self._lib.mtgpu_scan_frames_gmc(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, int(max_shift),
+                                              int(min_share_q8), _ptr(flags), _ptr(centres), _ptr(info)))
+        return flags, centres, info
+
+    def scan_gmc_device(self, d_rec, d_off, d_sd, max_shift: int = GMC_DEFAULT_MAX_SHIFT,
+                        min_share_q8: int = GMC_DEFAULT_MIN_SHARE_Q8, compact=False, flags=None, centres=None, info=None,
+                        stream=None):
+        """Device-resident batch (torch CUDA tensors) -> (flags uint8 [F], centres int32 [F], info int32 [F, 5]): the
+        bits of the library's uint32 counts and of its mt_gmc_info elements (info.cpu().numpy().view(GMC_INFO_DTYPE)).
+        d_rec: the packed 40-byte records, or the 8-byte compact ones with compact=True; d_off int64 [F + 1]; d_sd uint8
+        [F] or None.  flags / centres / info: None = allocated, False = not computed, or a tensor to fill.
+        Asynchronous on `stream` (default: torch's current stream)."""
+        import torch
+        dev = d_off.device
+        n_frames = max(d_off.numel() - 1, 0)
+        if flags is None:
+            flags = torch.empty(n_frames, dtype=torch.uint8, device=dev)
+        elif flags is False:
+            flags = None
+        if centres is None:
+            centres = torch.empty(n_frames, dtype=torch.int32, device=dev)
+        elif centres is False:
+            centres = None
+        if info is None:
+            info = torch.empty((n_frames, 5), dtype=torch.int32, device=dev)
+        elif info is False:
+            info = None
+        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_off.dtype == torch.int64
+        assert flags is None or (flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() >= n_frames)
+        assert centres is None or (centres.dtype == torch.int32 and centres.is_contiguous() and centres.numel() >= n_frames)
+        assert info is None or (info.dtype == torch.int32 and info.is_contiguous() and info.numel() >= 5 * n_frames)
+        rec_bytes = 8 if compact else 40
+        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+        check(self._lib.mtgpu_scan_gmc_device(
+            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
+            None if d_sd is None else d_sd.data_ptr(), n_frames, int(max_shift), int(min_share_q8), ptr(flags), ptr(centres),
+            ptr(info), st))
+        return flags, centres, info
 
     # -------------------------------------------------------- motion blobs
     def scan_blobs(self, batch: FrameBatch, min_blob_cells: int = 1, stream_off=None, keep=None) -> dict:

@@ -68,6 +68,10 @@ class StreamSpec:
     # 4 = two directions (source -1 / +1) x two partitions: the only way a one-record-per-4x4-block stream can
     # reach VECTORS_NEEDED = 4 of the shipped env (config/motion_trim.env:75).  Frames then differ in size.
     event_records: int = 1
+    # camera shake: every frame with side data gets one displacement (a, b), each drawn from U{-shake .. shake} by the
+    # stream's own hash (camera_shift), that is added to every record's src: the whole picture moves by (-a, -b) on
+    # top of whatever the records did.  0: off, the stream is byte-identical to one without the option.
+    shake: int = 0
 
     @property
     def cells_x(self) -> int:
@@ -127,6 +131,16 @@ def scripted_events(spec: StreamSpec, n_frames: int, seed: Optional[int] = None)
         f += length + int((8.0 if long_gap else 3.0) * spec.fps)
         long_gap = not long_gap
     return ev
+
+
+def camera_shift(spec: StreamSpec, f: int) -> Tuple[int, int]:
+    """The camera displacement (a, b) of frame f under spec.shake: what gen_frame adds to every record's src.
+    (0, 0) with shake == 0."""
+    if spec.shake <= 0:
+        return 0, 0
+    h = int(_hash(spec.seed, f, np.zeros(1, dtype=np.int64), 7)[0])
+    span = 2 * int(spec.shake) + 1
+    return h % span - int(spec.shake), (h >> 20) % span - int(spec.shake)
 
 
 def gen_frame(spec: StreamSpec, f: int) -> Optional[np.ndarray]:
@@ -190,6 +204,10 @@ def gen_frame(spec: StreamSpec, f: int) -> Optional[np.ndarray]:
         source = np.where(multi & (j % 2 == 1), 1, source)
         dst_x = np.where(multi, mx[idx] * blk + ((j // 2) * 2 + 1) % blk, dst_x)
         n = len(idx)
+
+    if spec.shake > 0:
+        cam_x, cam_y = camera_shift(spec, f)
+        dx, dy = dx - cam_x, dy - cam_y                  # src = dst - d: the camera's (a, b) is added to every src
 
     out = np.zeros(n, dtype=MV_DTYPE)
     out["source"] = source.astype(np.int32)

@@ -1,0 +1,386 @@
+"""CPU tier: global-motion compensation (include/mtgpu_gmc.h) exists at every layer — header, library, ctypes table,
+Python package, command, example — sizes its launch with host arithmetic alone, rejects bad arguments before any HIP
+call and has no fallback without a device; the numpy restatement of tests/gmc_model.py reproduces every hand-derived
+number of tests/gmc_inputs.py and, through consequences A and C of the header, the unchanged oracle; and the camera
+shake of synth.StreamSpec leaves default streams as they were."""
+import ctypes as C
+import hashlib
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import mvtrim_amd as m
+from mvtrim_amd import _abi, config, gmc, synth
+
+import gmc_inputs as gi
+import gmc_model as gm
+import oracle_binding as ob
+import derived_edge_inputs as dei
+from golden_cases import load_hand_cases
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MI355X_LDS = 163840
+
+NEW_SYMBOLS = ["mtgpu_gmc_preview", "mtgpu_scan_frames_gmc", "mtgpu_scan_gmc_device"]
+
+
+def gmc_header():
+    return open(os.path.join(ROOT, "include", "mtgpu_gmc.h")).read()
+
+
+def vp(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# ------------------------------------------------------------------ symbols, headers, example
+
+def test_entry_points_are_declared_exported_and_prototyped():
+    lib = m.load_library()
+    hdr = gmc_header()
+    declared = sorted(set(re.findall(r"\b(mtgpu_[a-z_]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))))
+    assert declared == NEW_SYMBOLS == sorted(_abi.ABI_GMC)
+    for n in NEW_SYMBOLS:
+        fn = getattr(lib, n)                      # AttributeError: not exported by libmtgpu.so
+        assert fn.restype is C.c_int and fn.argtypes == _abi.ABI_GMC[n][1], n
+        assert n not in _abi.ABI                  # mtgpu.h's own text does not declare it
+        at = hdr.index("int " + n + "(")
+        assert "src/motion_scanner.cpp:" in hdr[hdr.rindex("\n/*", 0, at):at], n
+    assert C.sizeof(_abi.GmcPlanC) == 16
+    assert [f for f, _ in _abi.GmcPlanC._fields_] == ["lds_bytes", "workgroup", "hist_bins", "info_bytes"]
+    assert _abi.GMC_INFO_DTYPE.itemsize == 20 and _abi.GMC_INFO_DTYPE.names == gi.INFO_FIELDS
+    assert [_abi.GMC_INFO_DTYPE.fields[k][1] for k in gi.INFO_FIELDS] == [0, 2, 4, 6, 8, 12, 16]
+    assert '#include "mtgpu_gmc.h"' in open(os.path.join(ROOT, "include", "mtgpu.h")).read()
+    # the header states the defaults, the four consequences and what is out of scope
+    flat = " ".join(hdr.replace("*", " ").split())
+    assert "#define MTGPU_GMC_DEFAULT_MAX_SHIFT 16" in hdr and "#define MTGPU_GMC_DEFAULT_MIN_SHARE_Q8 128" in hdr
+    assert (_abi.GMC_MAX_SHIFT, _abi.GMC_DEFAULT_MAX_SHIFT, _abi.GMC_DEFAULT_MIN_SHARE_Q8) == (127, 16, 128)
+    for text in ("A. max_shift == 0 equals mtgpu_scan_centres_device bit for bit", "B. Translation invariance",
+                 "C. A frame's centres equals the plain centre count", "D. vn == 0", "Out of scope: keep masks; blobs; the pipe form"):
+        assert text in flat, text
+    # no new environment variable
+    assert "getenv" not in open(os.path.join(ROOT, "motion-estimated-video-trimmer_amd", "csrc", "gmc_kernels.hip")).read()
+    # the kernels are in the library, and nothing of the checker is
+    blob = open(_abi.LIB_PATH, "rb").read()
+    assert b"gmc_frames_kernel" in blob and b"gmc_clear_kernel" in blob
+    syms = subprocess.check_output(["nm", "-D", "--defined-only", _abi.LIB_PATH]).decode()
+    assert "mto_" not in syms
+
+
+def test_headers_compile_as_c_and_cpp_either_one_first(tmp_path):
+    body = ("int use(mtgpu_ctx *c) {\n"
+            "  mtgpu_gmc_plan p;\n"
+            "  mt_gmc_info i;\n"
+            "  typedef char info_is_20_bytes[sizeof(mt_gmc_info) == 20 ? 1 : -1];\n"
+            "  i.gx = i.gy = i.mode_x = i.mode_y = 0; i.n_in = i.n_x = i.n_y = 0;\n"
+            "  return mtgpu_gmc_preview(0, 163840, &p)\n"
+            "       + mtgpu_scan_gmc_device(c, 0, 40, 0, 0, 0, 0, MTGPU_GMC_DEFAULT_MAX_SHIFT, MTGPU_GMC_DEFAULT_MIN_SHARE_Q8, 0, 0, &i, 0)\n"
+            "       + mtgpu_scan_frames_gmc(c, 0, 0, 0, 0, MTGPU_GMC_MAX_SHIFT, 256, 0, 0, &i)\n"
+            "       + p.lds_bytes + p.workgroup + p.hist_bins + p.info_bytes + (int)sizeof(info_is_20_bytes);\n}\n")
+    for first in ("mtgpu.h", "mtgpu_gmc.h"):
+        src = tmp_path / ("use_" + first.replace(".", "_") + ".c")
+        src.write_text('#include "%s"\n%s' % (first, body))
+        for comp, flag, lang in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "c++")):
+            subprocess.check_call([comp, flag, "-Wall", "-Werror", "-fsyntax-only", "-x", lang,
+                                   "-I" + os.path.join(ROOT, "include"), str(src)])
+
+
+def test_plain_c_example_compiles():
+    """examples/gmc_example.c against the headers as they are (it runs in the GPU tier)."""
+    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "gmc_example.c")])
+
+
+def test_package_exports_the_methods():
+    for name in ("scan_gmc", "scan_gmc_device"):
+        assert callable(getattr(m.MotionScanner, name)), name
+    assert callable(m.gmc_preview) and "gmc_preview" in m.__all__ and m.GMC_INFO_DTYPE is _abi.GMC_INFO_DTYPE
+    for name in ("main", "measure", "parser", "share_q8"):
+        assert callable(getattr(gmc, name)), name
+
+
+# ------------------------------------------------------------------ preview
+
+def preview(params, lds=MI355X_LDS):
+    p = _abi.GmcPlanC()
+    c = params.to_c()
+    rc = m.load_library().mtgpu_gmc_preview(C.byref(c), lds, C.byref(p))
+    return rc, p, m.load_library().mtgpu_last_error().decode()
+
+
+def lds_by_hand(gw, R):
+    """csrc/gmc_kernels.h: the tile, one plane of R + 2 mask rows, two histograms of 256 bins, 32 bytes of results."""
+    W = (gw + 63) // 64
+    return 4 * (((R + 2) * gw + 3) & ~3) + (R + 2) * W * 8 + 2 * 256 * 4 + 32
+
+
+def test_preview_sizes_the_launch():
+    for (w, h, kw), (gw, gh, R) in [((1920, 1080, config.CODE_DEFAULTS), (120, 68, 62)), ((3840, 2160, config.CODE_DEFAULTS), (240, 135, 123)),
+                                     ((3840, 2160, dict(vertical_mask=0.0)), (240, 135, 135)), ((48, 48, dict(vertical_mask=0.0)), (3, 3, 3))]:
+        params = m.ScanParams.from_config(w, h, **kw)
+        assert (params.grid_w, params.grid_h) == (gw, gh)
+        assert max(1, gh - 2 * params.vertical_margin) == R
+        rc, p, msg = preview(params)
+        assert rc == _abi.MT_OK, msg
+        assert (p.workgroup, p.hist_bins, p.info_bytes) == (1024, 256, 20)
+        assert p.lds_bytes == lds_by_hand(gw, R) <= MI355X_LDS
+        assert m.gmc_preview(params) == {"lds_bytes": p.lds_bytes, "workgroup": 1024, "hist_bins": 256, "info_bytes": 20}
+    # the histograms hold every max_shift a call may name
+    assert 2 * _abi.GMC_MAX_SHIFT + 1 <= 256
+    # two 1080p workgroups per CU are limited by lanes, not LDS; 4K sits alone on its CU
+    assert 2 * preview(m.ScanParams.from_config(1920, 1080))[1].lds_bytes <= MI355X_LDS
+    assert 2 * preview(m.ScanParams.from_config(3840, 2160))[1].lds_bytes > MI355X_LDS
+    # the grids the plain scan cuts into row bands have no form; nor has 1080p on a device with 32 KB
+    rc, _, msg = preview(m.ScanParams.from_config(3840, 2160, block_size=4, block_shift=2))
+    assert rc == _abi.MT_ERR_UNSUPPORTED and "960x540" in msg
+    rc, _, msg = preview(m.ScanParams.from_config(32767, 3, block_size=1, block_shift=0, vertical_mask=0.0))
+    assert rc == _abi.MT_ERR_UNSUPPORTED and "32767x3" in msg
+    rc, _, msg = preview(m.ScanParams.from_config(1920, 1080), 32768)
+    assert rc == _abi.MT_ERR_UNSUPPORTED and "120x68" in msg
+    with pytest.raises(m.MtgpuError) as ei:
+        m.gmc_preview(m.ScanParams.from_config(3840, 2160, block_size=4, block_shift=2))
+    assert ei.value.code == _abi.MT_ERR_UNSUPPORTED
+    # invalid
+    lib = m.load_library()
+    c = m.ScanParams.from_config(1920, 1080).to_c()
+    assert lib.mtgpu_gmc_preview(None, MI355X_LDS, C.byref(_abi.GmcPlanC())) == _abi.MT_ERR_INVALID
+    assert lib.mtgpu_gmc_preview(C.byref(c), MI355X_LDS, None) == _abi.MT_ERR_INVALID
+    assert lib.mtgpu_gmc_preview(C.byref(c), 100, C.byref(_abi.GmcPlanC())) == _abi.MT_ERR_INVALID
+
+
+# ------------------------------------------------------------------ error paths that need no device
+
+def test_invalid_arguments_are_rejected_without_a_device():
+    """Everything the arguments alone decide is answered before the context is looked at: no HIP call, no byte written."""
+    lib = m.load_library()
+    inv = _abi.MT_ERR_INVALID
+    one = C.c_void_p(64)          # never dereferenced
+    odd = C.c_void_p(68)
+
+    def err():
+        return lib.mtgpu_last_error().decode()
+
+    def dev(rec=one, rb=40, nrec=1, off=one, n=1, ms=16, q8=128, fl=one, ce=one, info=one):
+        return lib.mtgpu_scan_gmc_device(None, rec, rb, nrec, off, None, n, ms, q8, fl, ce, info, None)
+
+    for rb in (0, 7, 16, 39, 41, -8):
+        assert dev(rb=rb) == inv and "rec_bytes" in err()
+    for ms in (-1, 128, 1000):
+        assert dev(ms=ms) == inv and "max_shift" in err()
+    for q8 in (-1, 257, 65536):
+        assert dev(q8=q8) == inv and "min_share_q8" in err()
+    assert dev(fl=None, ce=None, info=None) == inv and "all NULL" in err()
+    assert dev(off=None) == inv and "d_frame_off" in err()
+    assert dev(off=odd) == inv and "d_frame_off" in err() and "aligned" in err()
+    assert dev(rec=None) == inv and "d_rec" in err()
+    assert dev(rec=odd, rb=8) == inv and "d_rec" in err() and "8-byte" in err()
+    assert dev(rec=C.c_void_p(66)) == inv and "d_rec" in err()
+    assert dev(ce=C.c_void_p(66)) == inv and "d_centres" in err()
+    assert dev(info=C.c_void_p(66)) == inv and "d_info" in err() and "aligned" in err()
+    assert dev() == inv and "ctx" in err()
+    assert dev(ms=0, q8=0) == inv and "ctx" in err() and dev(ms=127, q8=256) == inv and "ctx" in err()
+
+    out = np.full(3, 7, dtype=np.uint32)
+    fl = np.full(3, 7, dtype=np.uint8)
+    info = np.full(3 * 5, 7, dtype=np.uint32)
+    mv = np.zeros(8, dtype=m.MV_DTYPE)
+    good_off = np.array([0, 4, 8], dtype=np.uint64)
+
+    def host(off=good_off, ms=16, q8=128, f=fl, c=out, i=info, recs=mv):
+        return lib.mtgpu_scan_frames_gmc(None, vp(recs), vp(off), None, 2, ms, q8, vp(f), vp(c), vp(i))
+
+    assert host(ms=128) == inv and "max_shift" in err()
+    assert host(q8=257) == inv and "min_share_q8" in err()
+    assert host(f=None, c=None, i=None) == inv and "all NULL" in err()
+    assert host(off=None) == inv and "frame_off" in err()
+    assert host(off=np.array([0, 9, 8], dtype=np.uint64)) == inv and "frame_off not monotonic" in err()
+    assert host(recs=None) == inv and "mv is NULL" in err()
+    assert host() == inv and "ctx" in err()
+    assert out.tolist() == [7, 7, 7] and fl.tolist() == [7, 7, 7] and (info == 7).all()
+
+
+def test_no_fallback_without_a_device(tmp_path):
+    """A context cannot be created without a device, and the command, given a readable file, prints its document with a
+    device and fails with the library's message without one."""
+    mv = gi.hand_frame("pan_plus_object")
+    path = str(tmp_path / "pan.mtmv")
+    m.mvfile.write_mtmv(path, 128, 96, 1, 1000, 25.0, 1.0, [0, 40], [mv, None])
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    out = subprocess.run([sys.executable, "-m", "mvtrim_amd.gmc", path, "--mv-threshold-sq", "16", "--vectors-needed", "1",
+                          "--clusters-needed", "1", "--vertical-mask", "0", "--json"],
+                         capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
+    if m.load_library().mtgpu_device_count() > 0:
+        import json
+        assert out.returncode == 0, out.stderr
+        doc = json.loads(out.stdout)
+        assert doc["without_gmc"]["centres"] == 36 and doc["with_gmc"]["centres"] == 4 and doc["vectors"] == [[5, 0, 1]]
+        return
+    assert out.returncode != 0 and out.stdout == ""
+    assert "no CPU fallback" in out.stderr
+
+
+@pytest.mark.parametrize("bad", [["--max-shift", "-1"], ["--max-shift", "128"], ["--max-shift", "x"], ["--max-shift", "1.5"],
+                                 ["--min-share", "-0.1"], ["--min-share", "1.5"], ["--min-share", "nan"], ["--min-share", ""]])
+def test_gmc_bad_options_exit_2_before_any_device_is_touched(bad, monkeypatch, capsys):
+    def boom(*a, **k):
+        raise AssertionError("touched before the arguments were valid")
+    monkeypatch.setattr(gmc, "MotionScanner", boom)
+    monkeypatch.setattr(gmc.tune, "load", boom)
+    with pytest.raises(SystemExit) as ei:
+        gmc.main(["nothing_here.mtmv"] + bad)
+    assert ei.value.code == 2 and bad[0] in capsys.readouterr().err
+
+
+def test_gmc_options_parse():
+    a = gmc.parser().parse_args(["f.mtmv"])
+    assert (a.max_shift, a.min_share, a.json) == (16, 0.5, False) and gmc.share_q8(a.min_share) == 128
+    a = gmc.parser().parse_args(["f.mtmv", "--max-shift", "127", "--min-share", "1", "--json"])
+    assert (a.max_shift, gmc.share_q8(a.min_share), a.json) == (127, 256, True)
+    assert gmc.share_q8(0.0) == 0 and gmc.share_q8(0.25) == 64
+    assert gmc.main([os.path.join(ROOT, "nothing_here.json")]) == 1
+
+
+# ------------------------------------------------------------------ the model against the hand values
+
+def test_walk_order():
+    assert gm.walk(0) == [0] and gm.walk(3) == [0, -1, 1, -2, 2, -3, 3] and len(gm.walk(127)) == 255
+
+
+@pytest.mark.parametrize("name", list(gi.HAND))
+def test_model_reproduces_the_hand_values(name):
+    thr, margin, cells, ms, q8, info, centres, plain = gi.HAND[name]
+    p = gi.hand_params(thr, margin)
+    mv = gi.hand_frame(name)
+    got_c, got_i = gm.gmc_frame(p, mv, ms, q8)
+    assert tuple(got_i[k] for k in gi.INFO_FIELDS) == info, name
+    assert got_c == centres, name
+    # the uncompensated count, by hand too: the oracle's
+    off = np.array([0, len(mv)], dtype=np.uint64)
+    assert int(ob.scan_centres(p, mv, off, np.ones(1, dtype=np.uint8))[1][0]) == plain, name
+    # consequence C: the oracle on the records with (gx, gy) added to every src
+    moved = gm.shift_src(mv, off, [info[0]], [info[1]])
+    assert int(ob.scan_centres(p, moved, off, np.ones(1, dtype=np.uint8))[1][0]) == centres, name
+
+
+def test_hand_batches_cover_the_cases_and_the_model_agrees():
+    seen = []
+    for (thr, margin, ms, q8), names, mv, off, sd, want_c, want_i, plain in gi.hand_batches():
+        p = gi.hand_params(thr, margin)
+        fl, ce, info = gm.gmc_batch(p, mv, off, sd, ms, q8)
+        assert ce.tolist() == want_c.tolist() and gi.info_rows(info).tolist() == want_i.tolist(), names
+        assert fl.tolist() == (want_c >= 1).astype(np.uint8).tolist()
+        assert ob.scan_centres(p, mv, off, sd)[1].tolist() == plain.tolist(), names
+        assert sd.tolist() == [1, 0] * len(names) and int(np.diff(off.astype(np.int64))[1]) == 48
+        seen += list(names)
+    assert sorted(seen) == sorted(gi.HAND) and len(seen) == 17
+    # the pan is what the plain scan flags and the compensated scan does not
+    assert gi.HAND["pure_pan"][7] == 36 and gi.HAND["pure_pan"][6] == 0
+
+
+def test_big_residual_hand_values():
+    mv, off, sd = gi.big_frame()
+    assert gi.BIG_R2 == 4311498244 > 2 ** 32 and gi.BIG_R2 % 2 ** 32 == 16530948
+    for thr, want in gi.BIG_THRESHOLDS:
+        p = m.ScanParams.from_config(32768, 32768, mv_threshold_sq=thr, vectors_needed=1, **dei.BIG_KW)
+        c, info = gm.gmc_frame(p, mv, 127, 128)
+        assert c == want and tuple(info[k] for k in gi.INFO_FIELDS) == gi.BIG_INFO, thr
+        # a product truncated to 32 bits would fall below every one of these thresholds
+        assert gi.BIG_R2 % 2 ** 32 < thr
+    assert [w for _, w in gi.BIG_THRESHOLDS] == [1, 1, 1, 0]
+
+
+# ------------------------------------------------------------------ the model against the oracle
+
+def test_model_with_max_shift_0_is_the_oracle():
+    """Consequence A on the 30 hand-derived check_frame cases (vectors_needed 0 and a margin included) and on random
+    frames: with max_shift 0 nothing is subtracted."""
+    _, cases = load_hand_cases()
+    assert len(cases) == 30
+    for name, kw, case in cases:
+        mv, off, sd, hand = dei.hand_case_batch(case)
+        for vn in (kw["vectors_needed"], 0, 255):
+            p = m.ScanParams.from_config(**dict(kw, vectors_needed=vn))
+            fl, ce, info = gm.gmc_batch(p, mv, off, sd, 0, 128)
+            wf, wc = ob.scan_centres(p, mv, off, sd)
+            assert ce.tolist() == wc.tolist() and fl.tolist() == wf.tolist(), (name, vn)
+            assert not info["gx"].any() and not info["gy"].any() and not info["mode_x"].any()
+    rng = np.random.RandomState(5)
+    mv, off, sd = synth.random_frames(rng, 24, 600, 1920, 1080)
+    for vn in (0, 1, 2):
+        p = m.ScanParams.from_config(1920, 1080, vectors_needed=vn)
+        fl, ce, _ = gm.gmc_batch(p, mv, off, sd, 0, 0)
+        wf, wc = ob.scan_centres(p, mv, off, sd)
+        assert ce.tolist() == wc.tolist() and fl.tolist() == wf.tolist()
+        assert vn == 0 or int((wc > 0).sum()) >= 6
+        # consequence D: vn == 0 is the plain scan whatever is subtracted
+        if vn == 0:
+            assert gm.gmc_batch(p, mv, off, sd, 16, 0)[1].tolist() == wc.tolist()
+
+
+def test_model_is_the_oracle_on_src_shifted_records():
+    """Consequence C on the random pans of the GPU tier and on synth.random_frames: centres == the plain count of the
+    frame with (gx, gy) added to every src; and the pans are found."""
+    mv, off, sd, pans, shifts = gi.pan_batch()
+    for vn in (1, 2):
+        p = m.ScanParams.from_config(1920, 1080, vectors_needed=vn)
+        fl, ce, info = gm.gmc_batch(p, mv, off, sd, gi.PAN_MAX_SHIFT, 128)
+        moved = gm.shift_src(mv, off, info["gx"], info["gy"])
+        wf, wc = ob.scan_centres(p, moved, off, sd)
+        assert ce.tolist() == wc.tolist() and fl.tolist() == wf.tolist()
+        plain = ob.scan_centres(p, mv, off, sd)[1]
+        big = (np.diff(off.astype(np.int64)) >= 4095) & (sd != 0)
+        assert big.sum() >= 4 and (info["gx"][big] == pans[big, 0]).all() and (info["gy"][big] == pans[big, 1]).all()
+        moving = big & ((pans ** 2).sum(axis=1) >= 16)                     # a pan the plain threshold (16) keeps
+        assert moving.sum() >= 3 and (ce[moving] < plain[moving]).all() and (ce[big] > 0).all()
+    assert not ce[sd == 0].any() and not gi.info_rows(info)[sd == 0].any()
+    counts = sorted(set(np.diff(off.astype(np.int64)).tolist()))
+    assert counts == gi.PAN_COUNTS
+    rng = np.random.RandomState(11)
+    mv, off, sd = synth.random_frames(rng, 64, 150, 1920, 1080)
+    p = m.ScanParams.from_config(1920, 1080, vectors_needed=1)
+    fl, ce, info = gm.gmc_batch(p, mv, off, sd, 6, 0)
+    assert (info["gx"] != 0).any() and (info["gy"] != 0).any()
+    checked = 0
+    for f in range(64):                                                    # wherever the shifted src stays inside int16
+        o = off[f:f + 2]
+        moved = gm.shift_src(mv, o, info["gx"][f:f + 1], info["gy"][f:f + 1])
+        if moved is not None:
+            assert int(ce[f]) == int(ob.scan_centres(p, moved, o, sd[f:f + 1])[1][0]), f
+            checked += 1
+    assert checked >= 8
+
+
+# ------------------------------------------------------------------ the synthetic camera
+
+def stream_digest(spec, n):
+    mv, off, pts, sd = synth.gen_stream(spec, n)
+    return hashlib.sha256(mv.tobytes() + off.tobytes() + pts.tobytes() + sd.tobytes()).hexdigest()
+
+
+def test_default_streams_are_byte_identical_and_shake_moves_every_src():
+    assert synth.StreamSpec().shake == 0 and synth.camera_shift(synth.spec_1080p(seed=3), 7) == (0, 0)
+    spec = synth.spec_1080p(seed=2, sub=1)
+    spec.events = [synth.Event(2, 9, 40, 30, 4, 3, 9, 2)]
+    # the digest of this stream as the generator made it before the option existed
+    assert stream_digest(spec, 12) == DIGEST_1080P_SEED2
+    still = synth.gen_stream(spec, 12)
+    shaken_spec = synth.spec_1080p(seed=2, sub=1, shake=6)
+    shaken_spec.events = spec.events
+    shaken = synth.gen_stream(shaken_spec, 12)
+    assert np.array_equal(still[1], shaken[1]) and np.array_equal(still[3], shaken[3])
+    seen = set()
+    for f in range(12):
+        a, b = synth.camera_shift(shaken_spec, f)
+        assert -6 <= a <= 6 and -6 <= b <= 6
+        s, t = still[0][int(still[1][f]):int(still[1][f + 1])], shaken[0][int(still[1][f]):int(still[1][f + 1])]
+        assert np.array_equal(s["dst_x"], t["dst_x"]) and np.array_equal(s["dst_y"], t["dst_y"])
+        assert (t["src_x"].astype(np.int64) - s["src_x"] == a).all() and (t["src_y"].astype(np.int64) - s["src_y"] == b).all()
+        if len(s):
+            seen.add((a, b))
+    assert len(seen) >= 6                                                  # the camera does move
+
+
+DIGEST_1080P_SEED2 = "869643a4f0b0cd836aa33fd3de5914ce60c2e21f88421318bd02ebde113553c9"
