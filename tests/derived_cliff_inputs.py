@@ -1,7 +1,7 @@
-"""Inputs of tests/test_gpu_derived_cliff.py: the grids on which the sweep, the activity map and the masked scan fill
-their LDS to the last row or column, found with the previews (host arithmetic, no GPU), and a small batch for each with
-the values derived BY HAND from its construction.  tests/test_derived_cliff_host.py proves without a GPU that every shape
-sits on the limit, that the batches carry centres and that two independent expected-value sources agree on them.
+"""Inputs of tests/test_gpu_derived_cliff.py: the grids on which the sweep, the activity map, the masked scan and the
+compensated scan fill their LDS to the last row or column, found with the previews (host arithmetic, no GPU), and a
+small batch for each with the values derived BY HAND from its construction.  tests/test_derived_cliff_host.py proves
+without a GPU that every shape sits on the limit, that the batches carry centres and that two independent expected-value sources agree on them.
 
 Every shape has vertical_mask 0 (R = grid_h) and block_shift 1, which keeps every pixel coordinate inside int16 — but for
 the sweep's two-column grids: 20 000 rows of two-pixel cells reach past 32 767, so those two use block_shift 0, where a
@@ -13,6 +13,7 @@ pixel coordinate is the cell index itself.  Nothing below is a literal size; bis
     activity      6824   5849   559    194     | 13105   7800
     sweep 1 x 1   20442  13627  626    209     | 13217   8028
     sweep 8 x 8   20422  13614  625    208     | 10896   7104
+    gmc           10108  8086   584    199     | 13069   7841
 
     activity at gw = 120 (every plan outcome is reachable there; the rows are the largest gh of the outcome and, as the
     row after it, the smallest gh that no longer has it — both are shapes):
@@ -53,7 +54,7 @@ import zones_inputs as zi
 from derived_edge_inputs import MI355X_LDS, frozen, sweep_chunk_rows, voters
 from scan_checks import junk_padding
 
-KERNELS = ("zones", "activity", "sweep1", "sweep8")
+KERNELS = ("zones", "activity", "sweep1", "sweep8", "gmc")
 TALL_GW = (2, 3, 65, 193)
 WIDE_GH = (1, 3)
 ACT_GW = 120
@@ -82,6 +83,8 @@ def kernel_preview(kernel, p, lds=MI355X_LDS):
             return m.zones_preview(p, lds)
         if kernel == "activity":
             return m.activity_preview(p, lds)
+        if kernel == "gmc":
+            return m.gmc_preview(p, lds)
         n = 1 if kernel == "sweep1" else 8
         return m.sweep_preview(p, n, n, lds)
     except m.MtgpuError as e:
@@ -158,8 +161,9 @@ def one_more(gw, gh, kind):
     return (gw + 1, gh) if kind == "wide" else (gw, gh + 1)
 
 
-# The three LDS formulas, restated from the layout comments of csrc/zones_kernels.h, csrc/activity_kernels.h and
-# csrc/sweep_kernels.h (tile: (R + 2) x gw 32-bit counters padded to 16 bytes; W 64-bit words per mask row).  A grid past
+# The four LDS formulas, restated from the layout comments of csrc/zones_kernels.h, csrc/activity_kernels.h,
+# csrc/sweep_kernels.h and csrc/gmc_kernels.h (tile: (R + 2) x gw 32-bit counters padded to 16 bytes; W 64-bit words per
+# mask row; the compensated scan: the tile, one plane of R + 2 mask rows, two histograms of 256 bins, eight result words).  A grid past
 # the limit has no preview to ask, so "what one more row or column would add" comes from these; the host test holds
 # them to the previews' lds_bytes on every shape.
 def _tile(gw, R):
@@ -167,13 +171,16 @@ def _tile(gw, R):
 
 
 def lds_need(kernel, gw, gh):
-    """The LEAST the kernel needs on a gw x gh grid (vertical_mask 0): zones has one form; the activity map's smallest
-    is the one without accumulators; the sweep's is one tile and the three-row mask buffer per level."""
+    """The LEAST the kernel needs on a gw x gh grid (vertical_mask 0): zones and the compensated scan have one form; the
+    activity map's smallest is the one without accumulators; the sweep's is one tile and the three-row mask buffer per
+    level."""
     W = (gw + 63) // 64
     if kernel == "zones":
         return _tile(gw, gh) + (3 * gh + 4) * W * 8 + 16
     if kernel == "activity":
         return _tile(gw, gh) + (2 * gh + 2) * W * 8 + 16
+    if kernel == "gmc":
+        return _tile(gw, gh) + (gh + 2) * W * 8 + 2 * 256 * 4 + 32
     return _tile(gw, gh) + (1 if kernel == "sweep1" else 8) * 3 * W * 8 + 256
 
 
@@ -390,3 +397,74 @@ def sweep_path(kernel, name):
     n = 1 if kernel == "sweep1" else 8
     ch, R, _, pv = sweep_chunk_rows(grid_params(gw, gh), n, n)
     return pv["passes"], ch, R
+
+
+# ------------------------------------------------------------------ the compensated scan
+
+GMC_SETTINGS = ((0, 128), (16, 128))          # (max_shift, min_share_q8): the plain scan (consequence A), and the default
+GMC_PAN = (7, -3)
+GMC_PAN_KW = dict(vectors_needed=3, mv_threshold_sq=16.0, clusters_needed=2)   # pairs of 3 votes and more with |d|^2 = 25
+GMC_PAN_MAX_SHIFT = 16                        # the pairs' own displacements, 7 + 5 and 7 + 3, are inside the bins
+
+
+@functools.lru_cache(maxsize=None)
+def gmc_expected(gw, gh, ms, q8):
+    """(flags, centres, info rows int64 [F, 7]) of tests/gmc_model.py on the shape's batch under CTX_KW."""
+    import gmc_inputs as gi
+    import gmc_model as gm
+    mv, off, sd, _ = batch(gw, gh)
+    fl, ce, info = gm.gmc_batch(grid_params(gw, gh, **CTX_KW), mv, off, sd, ms, q8)
+    return frozen(fl, ce, gi.info_rows(info))
+
+
+def gmc_oracle_c(gw, gh, info_rows):
+    """Consequence C: (frames checked bool [F], the oracle's plain counts of the batch with (gx, gy) added to every src).
+    A frame whose shifted src leaves int16 is not checked (its records keep their src)."""
+    import gmc_model as gm
+    mv, off, sd, _ = batch(gw, gh)
+    F = len(sd)
+    fits = np.array([gm.shift_src(mv, off[f:f + 2], info_rows[f:f + 1, 0], info_rows[f:f + 1, 1]) is not None for f in range(F)])
+    moved = gm.shift_src(mv, off, np.where(fits, info_rows[:, 0], 0), np.where(fits, info_rows[:, 1], 0))
+    return fits, ob.scan_centres(grid_params(gw, gh, **CTX_KW), moved, off, sd, nthreads=4)[1].copy()
+
+
+def gmc_filler_rows(gh):
+    return sorted({0, gh // 2, gh - 1})
+
+
+@functools.lru_cache(maxsize=None)
+def gmc_pan_case(name):
+    """(params, mv, off, sd, hand centres uint32 [2], hand info rows int64 [2, 7]): two frames, the pairs of planted
+    frame E and of planted frame H, every pair moving by (pair_d(i) + 7, -3), on top of fillers moving by the pan (7, -3)
+    in every cell of the first, a middle and the last row (vertical_mask 0: every row is analysed).
+
+    The rule the hand values follow.  The mode is the pan on both axes — the fillers outnumber the pair records
+    (asserted) and every record moves by -3 on y — and it is supported: n_x = the fillers > n / 2.  A pair's residual is
+    (pair_d(i), 0), so a pair counts what it counts in the plain scan of its own frame: hand_count, unchanged.  A
+    filler's residual is (0, 0) and the threshold is 16 > 0: a filler casts NO vote, wherever it lies, so the fillers
+    share rows and cells with the pairs (on the corners they must: both sit on the first and the last row) without
+    touching the count.  One filler per cell, but for the grids of two and three columns, where three rows hold fewer
+    cells than the pairs hold records: there every cell gets the smallest number of fillers that outnumbers them."""
+    gw, gh, _ = shapes("gmc")[name]
+    sh = shift_of(gw, gh)
+    p = grid_params(gw, gh, **GMC_PAN_KW)
+    assert p.mv_threshold_sq > 0.0
+    planted = planted_frames(gw, gh)
+    rng = np.random.RandomState(gw * 7 + gh)
+    frames, centres, info = [], [], []
+    for n in ("E", "H"):
+        pairs = planted[n]
+        pr = voters([(x, y, pair_votes(i), pair_d(i) + GMC_PAN[0], GMC_PAN[1]) for i, q in enumerate(pairs) for x, y in q], sh)
+        cells = [(x, y) for y in gmc_filler_rows(gh) for x in range(gw)]
+        per_cell = 1 + len(pr) // len(cells)
+        fill = voters([(x, y, per_cell) + GMC_PAN for x, y in cells], sh)
+        assert len(fill) > len(pr) and (per_cell == 1 or gw <= 3), (name, n, len(fill), len(pr))
+        f = np.concatenate([pr, fill])
+        frames.append(f[rng.permutation(len(f))])
+        centres.append(hand_count(pairs, gw, gh, 16.0, 3))
+        info.append(GMC_PAN + GMC_PAN + (len(f), len(fill), len(f)))
+    b = m.FrameBatch.from_frames(frames)
+    mv = np.ascontiguousarray(b.mv, dtype=m.MV_DTYPE).copy()
+    junk_padding(mv, rng)
+    return (p,) + frozen(mv, np.ascontiguousarray(b.frame_off, dtype=np.uint64), np.ones(2, dtype=np.uint8),
+                         np.array(centres, dtype=np.uint32), np.array(info, dtype=np.int64))

@@ -1,9 +1,14 @@
-"""The random stream of tests/test_gpu_derived_soak.py — the soak of the sweep, the activity map and the masked scan — and
-its expected values, usable without a GPU (tests/test_derived_cliff_host.py replays the first iterations):
+"""The random stream of tests/test_gpu_derived_soak.py — the soak of the sweep, the activity map, the masked scan and the
+compensated scan — and its expected values, usable without a GPU (tests/test_derived_cliff_host.py replays the first
+iterations):
 
-    d = draw(rng, it)                 # grid, parameters, batch, streams, masks, settings, record layout, base alignment
+    d = draw(rng, it, seed)           # grid, parameters, batch, streams, masks, settings, record layout, base alignment
     e = expected(d, kernel)           # kernel in KERNELS, where d["support"][kernel]
     d = replay(seed, it)              # iteration `it` of the soak with `seed`, rebuilt on the CPU
+
+What the compensated scan alone needs (max_shift, min_share_q8, a pan per frame and its own copy of the records, in which
+a share of every frame's records follows the pan) comes from a RandomState of its own, seeded from (seed, it): the
+stream `rng` and everything drawn from it are what they were before that kernel joined.
 
 The grid comes from w, h in [64, 3900] x [64, 2200] and block_shift 1 .. 5 as in tests/soak_replay.py, but the shifts are
 not equally likely: a derived kernel holds a whole frame's counters in LDS and supports about 37 000 cells, which a
@@ -14,17 +19,24 @@ import numpy as np
 import mvtrim_amd as m
 from mvtrim_amd import _abi, synth
 
+import gmc_model as gm
 import oracle_binding as ob
 import zones_inputs as zi
 from activity_model import assert_oracle_identities, model_maps
 from derived_edge_inputs import MI355X_LDS, UNALIGNED_SHIFTS
 from scan_checks import junk_padding
 
-KERNELS = ("sweep", "activity", "zones")
+KERNELS = ("sweep", "activity", "zones", "gmc")
 DEFAULT_SEED = 24680
 SHIFT_P = [0.04, 0.08, 0.18, 0.35, 0.35]                 # block_shift 1 .. 5
 THR_POOL = [0.0, 4.0, 9.5, 16.0, 25.0, 37.0, 4294967296.0, float("inf")]
 VEC_POOL = [0, 1, 2, 3, 4, 6, 12, 255]
+GMC_SHIFT_POOL = [0, 1, 6, 16, 127]
+GMC_SHARE_Q8_POOL = [0, 77, 128, 256]
+GMC_FOLLOW_POOL = [0.0, 0.4, 0.6, 0.95]                  # the share of a frame's records that follow its pan
+GMC_SHIFT_P = [0.1, 0.15, 0.25, 0.3, 0.2]
+GMC_SHARE_Q8_P = [0.25, 0.3, 0.3, 0.15]
+GMC_FOLLOW_P = [0.1, 0.25, 0.3, 0.35]
 
 
 def _preview(fn, *a):
@@ -41,7 +53,26 @@ def support_of(p, n_thr, n_vec, lds=MI355X_LDS):
             "zones": _preview(m.zones_preview, p, lds)}
 
 
-def draw(rng, it):
+def draw_gmc(seed, it, p, mv, off):
+    """The compensated scan's own inputs of iteration `it`: max_shift, min_share_q8, a pan (a, b) per frame within
+    +-(max_shift + 2) — some fall outside the bins — and gmc_mv, a copy of the records in which a share of every frame's
+    records has its src overwritten with dst - pan, clipped to int16."""
+    rng = np.random.RandomState([int(seed) & 0xFFFFFFFF, int(it)])
+    ms = int(rng.choice(GMC_SHIFT_POOL, p=GMC_SHIFT_P))
+    q8 = int(rng.choice(GMC_SHARE_Q8_POOL, p=GMC_SHARE_Q8_P))
+    F = len(off) - 1
+    pans = rng.randint(-(ms + 2), ms + 3, size=(F, 2)).astype(np.int64)
+    follow = float(rng.choice(GMC_FOLLOW_POOL, p=GMC_FOLLOW_P))
+    out = mv.copy()
+    fr = np.repeat(np.arange(F), np.diff(off.astype(np.int64)))
+    who = rng.rand(len(mv)) < follow
+    out["src_x"][who] = np.clip(mv["dst_x"][who].astype(np.int64) - pans[fr[who], 0], -32768, 32767)
+    out["src_y"][who] = np.clip(mv["dst_y"][who].astype(np.int64) - pans[fr[who], 1], -32768, 32767)
+    return dict(gmc_max_shift=ms, gmc_share_q8=q8, gmc_pans=pans, gmc_follow=follow, gmc_mv=out,
+                support_gmc=_preview(m.gmc_preview, p, MI355X_LDS))
+
+
+def draw(rng, it, seed=DEFAULT_SEED):
     """One iteration's inputs.  "creatable": False where mtgpu_create refuses the grid (nothing else is drawn then)."""
     sh = int(rng.choice([1, 2, 3, 4, 5], p=SHIFT_P))
     w, h = int(rng.randint(64, 3900)), int(rng.randint(64, 2200))
@@ -92,13 +123,16 @@ def draw(rng, it):
         window = (int(rng.choice(UNALIGNED_SHIFTS)), 8 * int(rng.randint(0, 16)))     # 40-byte shift, compact residue
     d.update(support=support, mv=mv, off=off, sd=sd, thr=thr, vec=vec, soff=soff, zsoff=zsoff, keep_density=dens, keeps=keeps,
              min_centres=int(rng.choice([0, 1, 2])), run_frames=int(rng.choice([0, 1, 3, 17])), compact=bool(it % 2), window=window)
+    g = draw_gmc(seed, it, p, mv, off)                       # not from `rng`: see the module docstring
+    support["gmc"] = g.pop("support_gmc")
+    d.update(g)
     return d
 
 
 def replay(seed, target):
     rng = np.random.RandomState(seed)
     for it in range(1, target + 1):
-        d = draw(rng, it)
+        d = draw(rng, it, seed)
     return d
 
 
@@ -153,13 +187,70 @@ def zones_vn0_count(p, keep):
     return int(n)
 
 
+def gmc_counts_np(p, mv, off, sd, max_shift, min_share_q8):
+    """(centres uint32 [F], info rows int64 [F, 7] in the order gx, gy, mode_x, mode_y, n_in, n_x, n_y): include/mtgpu_gmc.h
+    restated for a batch with one bincount per histogram — the bins in the order of the walk 0, -1, +1, ..., the first
+    maximum of that row is the mode — and one bincount for the residual votes.  A frame without side data reads 0."""
+    gw, gh, mg, F = p.grid_w, p.grid_h, p.vertical_margin, len(sd)
+    rows = np.zeros((gh, 1), dtype=bool)
+    rows[min(mg, gh):max(gh - mg, min(mg, gh))] = True
+    order = np.array(gm.walk(max_shift), dtype=np.int64) + max_shift
+    thr = gm.threshold_int(p.mv_threshold_sq)
+    centres, info = np.zeros(F, dtype=np.uint32), np.zeros((F, 7), dtype=np.int64)
+    for f in range(F):
+        if not sd[f]:
+            continue
+        r = mv[int(off[f]):int(off[f + 1])]
+        d = [r["dst_x"].astype(np.int64) - r["src_x"], r["dst_y"].astype(np.int64) - r["src_y"]]
+        cx, cy = r["dst_x"].astype(np.int64) >> p.block_shift, r["dst_y"].astype(np.int64) >> p.block_shift
+        inside = (cx >= 0) & (cx < gw) & (cy >= mg) & (cy < gh - mg)
+        n_in = int(inside.sum())
+        g = [0, 0]
+        for ax in (0, 1):
+            v = d[ax][inside]
+            h = np.bincount(v[np.abs(v) <= max_shift] + max_shift, minlength=2 * max_shift + 1)[order]
+            o = int(np.argmax(h))                            # the first maximum in walk order
+            mode, n = int(order[o]) - max_shift, int(h[o])
+            g[ax] = mode if n * 256 >= min_share_q8 * n_in else 0
+            info[f, 2 + ax], info[f, 5 + ax] = mode, n
+        info[f, 0], info[f, 1], info[f, 4] = g[0], g[1], n_in
+        votes = np.zeros((gh, gw), dtype=np.int64)
+        if thr is not None and n_in:
+            rx, ry = d[0] - g[0], d[1] - g[1]
+            ok = inside & (rx * rx + ry * ry >= thr)
+            votes = np.bincount((cy * gw + cx)[ok], minlength=gw * gh).reshape(gh, gw)
+        act = np.minimum(votes, 255) >= (p.vectors_needed & 0xFF)
+        z = np.pad(act, 1)
+        nb = z[1:-1, :-2] | z[1:-1, 2:] | z[:-2, 1:-1] | z[2:, 1:-1]
+        centres[f] = int((act & nb & rows)[:, 1:gw - 1].sum())
+    return centres, info
+
+
 def expected(d, kernel, check_sources=False):
     """The expected outputs of `kernel` on draw d and "total", the sum of the centre counts they hold.  check_sources:
     assert that the second, independent source agrees — the sweep: the oracle and sweep_counts_np on every setting; the
     activity map: the numpy model and the oracle's identities; the masked scan (always checked): the numpy AND rule
     against the oracle on filtered records, or under vectors_needed 0 against zones_vn0_count, and centres_all against
-    the oracle on the records as they are."""
+    the oracle on the records as they are; the compensated scan (on d["gmc_mv"]): gmc_counts_np against tests/gmc_model.py
+    with its candidate-by-candidate mode_of, and consequence C of include/mtgpu_gmc.h against the oracle on every frame
+    whose src + (gx, gy) stays in int16.  The compensated scan adds "compensated" (frames with gx or gy != 0),
+    "compensated_with_centres" and "found_not_applied" (a mode != 0 on an axis whose g is 0)."""
     p, mv, off, sd = d["params"], d["mv"], d["off"], d["sd"]
+    if kernel == "gmc":
+        mv, ms, q8 = d["gmc_mv"], d["gmc_max_shift"], d["gmc_share_q8"]
+        ce, rows = gmc_counts_np(p, mv, off, sd, ms, q8)
+        if check_sources:
+            _, mc, mi = gm.gmc_batch(p, mv, off, sd, ms, q8)
+            assert mc.tolist() == ce.tolist(), ("gmc centres", d["it"])
+            assert np.stack([mi[k].astype(np.int64) for k in mi.dtype.names], axis=1).tolist() == rows.tolist(), ("gmc info", d["it"])
+            fits = np.array([gm.shift_src(mv, off[f:f + 2], rows[f:f + 1, 0], rows[f:f + 1, 1]) is not None for f in range(len(sd))])
+            moved = gm.shift_src(mv, off, np.where(fits, rows[:, 0], 0), np.where(fits, rows[:, 1], 0))
+            oc = ob.scan_centres(p, moved, off, sd, nthreads=8)[1]
+            assert oc[fits].tolist() == ce[fits].tolist(), ("gmc consequence C", d["it"])
+        comp = (rows[:, 0] != 0) | (rows[:, 1] != 0)
+        lost = ((rows[:, 2] != 0) & (rows[:, 0] == 0)) | ((rows[:, 3] != 0) & (rows[:, 1] == 0))
+        return dict(flags=(ce >= max(1, p.clusters_needed)).astype(np.uint8), centres=ce, info=rows, total=int(ce.sum(dtype=np.uint64)),
+                    compensated=int(comp.sum()), compensated_with_centres=int((comp & (ce > 0)).sum()), found_not_applied=int(lost.sum()))
     if kernel == "sweep":
         T, V, F = len(d["thr"]), len(d["vec"]), len(sd)
         want, memo = np.zeros((T, V, F), dtype=np.uint32), {}

@@ -83,26 +83,7 @@ def hand_batches():
     """The cases grouped by what one call shares: [((thr, margin, max_shift, q8), names, mv, off, sd, want_centres,
     want_info rows, plain centres)].  Behind every case's frame stands a frame WITHOUT side data that owns records
     (a pan of 9): it reads 0 in every output."""
-    groups = {}
-    for name, (thr, margin, _cells, ms, q8, _info, _c, _pl) in HAND.items():
-        groups.setdefault((thr, margin, ms, q8), []).append(name)
-    out = []
-    for key, names in groups.items():
-        frames, sd, centres, info, plain = [], [], [], [], []
-        rng = np.random.RandomState(len(out) + 17)
-        for n in names:
-            f = hand_frame(n)
-            frames += [f[rng.permutation(len(f))], voters(_pan(9, 0), 4)]
-            sd += [1, 0]
-            centres += [HAND[n][6], 0]
-            info += [HAND[n][5], (0,) * 7]
-            plain += [HAND[n][7], 0]
-        off = np.concatenate([[0], np.cumsum([len(f) for f in frames])]).astype(np.uint64)
-        mv = np.concatenate(frames) if frames else np.zeros(0, dtype=m.MV_DTYPE)
-        arrays = frozen(mv, off, np.array(sd, dtype=np.uint8), np.array(centres, dtype=np.uint32),
-                        np.array(info, dtype=np.int64), np.array(plain, dtype=np.uint32))
-        out.append((key, tuple(names)) + arrays)
-    return out
+    return _batches(HAND)
 
 
 def info_rows(info):
@@ -176,3 +157,140 @@ def pan_batch():
     shifts = rng.randint(-4, 5, size=(len(counts), 2))
     shifts[shifts.any(axis=1) == 0] = (3, -2)
     return frozen(np.concatenate(frames), off, sd, pans.astype(np.int64), shifts.astype(np.int64))
+
+
+# ------------------------------------------------------------------ the pick across lanes and trips
+
+# max_shift 127: 255 candidates; pick_mode gives lane l the walk indices l, l + 64, l + 128, l + 192.  Walk index -> value:
+# 0 -> 0, 3 -> -2, 64 -> +32, 65 -> -33, 67 -> -34, 130 -> +65, 254 -> +127.  Three patterns of bin counts on an axis:
+#   A   -2 (index 3: lane 3, trip 0), -34 (index 67: lane 3, trip 1) and +65 (index 130: lane 2, trip 2) tie: -2 wins
+#   B   +127 (index 254: lane 62, trip 3) holds one record more than 0 (index 0: lane 0, trip 0): +127 wins
+#   C   +32 (index 64: lane 0, trip 1) ties with -33 (index 65: lane 1, trip 1): +32 wins
+# Each frame carries one pattern on x and another on y.  Same tuple as HAND; threshold 16, vectors_needed 1.  A group of
+# records is laid out as a run of neighbouring cells in columns 1 .. 6, so it adds one centre per cell while its
+# residual passes and nothing once the applied vector cancels it; a lone cell adds nothing either way.
+_AB = [(1, 1, 2, -2, 127), (2, 1, 2, -2, 127),                                 # G1: the winner of both axes, 2 cells
+       (4, 1, 2, -34, 127), (5, 1, 1, -34, 127), (6, 1, 1, -34, 127),          # G2: 3 cells
+       (1, 4, 1, 65, 0), (2, 4, 1, 65, 0), (3, 4, 1, 65, 0), (4, 4, 1, 65, 0),  # G3: 4 cells
+       (6, 3, 1, 1, 0), (7, 5, 1, 2, 0), (0, 3, 1, 3, 0)]                      # lone cells: dy 0 seven times, dy 127 eight
+_BC = [(1, 1, 2, 127, 32), (2, 1, 1, 127, 32),                                 # H1: the winner of both axes, 2 cells
+       (4, 1, 1, 127, -33), (5, 1, 1, 0, -33), (6, 1, 1, 0, -33),              # H2, H3: 3 cells in a row
+       (6, 3, 1, 0, 5)]                                                        # dx 127 four times, 0 three times
+_CA = [(1, 1, 1, 32, -2), (2, 1, 1, 32, -2),                                   # K1: the winner of both axes
+       (4, 1, 1, -33, -34), (5, 1, 1, -33, -34),                               # K2
+       (1, 4, 1, 7, 65), (2, 4, 1, 9, 65)]                                     # K3
+LANES = {
+    # x: A, y: B.  Applied (-2, 127): G1 cancels, G2 keeps (-32, 0): 3, G3 keeps (67, -127): 4.  With -34 on x: 2 + 0 + 4;
+    # with +65: 2 + 3 + 4; with 0 on y: 2 + 3 + 4.  Unsupported from 69 on x (4 * 256 < 69 * 15) and from 137 on y
+    # (8 * 256 = 2048 >= 136 * 15 = 2040 and < 137 * 15 = 2055); with gx 0 alone G1 keeps (-2, 0): 4 < 16, still nothing
+    "lanes_A_on_x_B_on_y": (16, 0, _AB, 127, 0, (-2, 127, -2, 127, 15, 4, 8), 7, 9),
+    "lanes_A_on_x_B_on_y_y_just_met": (16, 0, _AB, 127, 136, (0, 127, -2, 127, 15, 4, 8), 7, 9),
+    "lanes_A_on_x_B_on_y_share_missed": (16, 0, _AB, 127, 137, (0, 0, -2, 127, 15, 4, 8), 9, 9),
+    # x: B, y: C.  Applied (127, 32): H1 cancels, H2 + H3 keep (0, -65), (-127, -65): 3.  With 0 on x: 2 + 3; with -33 on
+    # y: H1 keeps (0, 65): 2, H2 cancels, H3 keeps its two cells: 2.  x unsupported from 147 (4 * 256 = 1024 < 147 * 7 = 1029)
+    "lanes_B_on_x_C_on_y": (16, 0, _BC, 127, 0, (127, 32, 127, 32, 7, 4, 3), 3, 5),
+    "lanes_B_on_x_C_on_y_share_missed": (16, 0, _BC, 127, 147, (0, 0, 127, 32, 7, 4, 3), 5, 5),
+    # x: C, y: A.  Applied (32, -2): K1 cancels, K2 keeps (-65, -32): 2, K3: 2.  Any other winner on either axis leaves a
+    # residual of 32 or more on K1: 6.  Unsupported from 86 (2 * 256 = 512 < 86 * 6 = 516)
+    "lanes_C_on_x_A_on_y": (16, 0, _CA, 127, 0, (32, -2, 32, -2, 6, 2, 2), 4, 6),
+    "lanes_C_on_x_A_on_y_share_missed": (16, 0, _CA, 127, 86, (0, 0, 32, -2, 6, 2, 2), 6, 6),
+}
+LANE_WALK = {-2: 3, -34: 67, 65: 130, 127: 254, 0: 0, 32: 64, -33: 65}          # value -> walk index, as stated above
+
+
+def _batches(cases):
+    groups = {}
+    for name, (thr, margin, _cells, ms, q8, _info, _c, _pl) in cases.items():
+        groups.setdefault((thr, margin, ms, q8), []).append(name)
+    out = []
+    for key, names in groups.items():
+        frames, sd, centres, info, plain = [], [], [], [], []
+        rng = np.random.RandomState(len(out) + 17)
+        for n in names:
+            f = voters(cases[n][2], 4)
+            frames += [f[rng.permutation(len(f))], voters(_pan(9, 0), 4)]
+            sd += [1, 0]
+            centres += [cases[n][6], 0]
+            info += [cases[n][5], (0,) * 7]
+            plain += [cases[n][7], 0]
+        off = np.concatenate([[0], np.cumsum([len(f) for f in frames])]).astype(np.uint64)
+        arrays = frozen(np.concatenate(frames), off, np.array(sd, dtype=np.uint8), np.array(centres, dtype=np.uint32),
+                        np.array(info, dtype=np.int64), np.array(plain, dtype=np.uint32))
+        out.append((key, tuple(names)) + arrays)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def lane_batches():
+    """LANES in the form of hand_batches(): one batch per setting, a pan of 9 without side data behind every case."""
+    return _batches(LANES)
+
+
+# ------------------------------------------------------------------ has_sd == NULL: the frame owns no record
+
+def follower_by_hand(margin, ms):
+    """(centres, info) of hand_batches()' frames WITHOUT side data once has_sd is NULL and they are scanned: one record
+    per cell moving by (9, 0).  Within max_shift the pan is found, fully supported (every counted record) and cancelled;
+    beyond it no x bin holds anything, nothing is applied and all 8 x (6 - 2 margin) analysed cells are active: columns
+    1 .. 6 of them are centres."""
+    n = GW * (GH - 2 * margin)
+    if ms >= 9:
+        return 0, (9, 0, 9, 0, n, n, n)
+    return (GW - 2) * (GH - 2 * margin), (0, 0, 0, 0, n, 0, n)
+
+
+# ------------------------------------------------------------------ 2^24 records in a frame
+
+# The smallest frame at which the support test and the pick's key differ from 32-bit arithmetic.  2^24 + 1 records move
+# by (5, -3), alternating between cells (1, 1) and (2, 1); the last record of the frame, in (2, 1), moves by (6, -3).
+# n_in = 2^24 + 2, n_x = 2^24 + 1, n_y = n_in.  min_share_q8 256: n_x * 256 = 2^32 + 256 < 256 * n_in = 2^32 + 512: x is
+# not supported, gx 0, the residuals (5, 0) and (6, 0) pass 16, both cells are active neighbours in inner columns: 2.
+# In 32 bits the two sides read 256 and 512 (still unsupported) if BOTH wrap, but `n_x << 8` alone wrapping, or the
+# pick's count << 8 losing its top bits, gives other answers; 255: 255 * n_in = 2^32 - 2^24 + 510 <= n_x * 256: supported,
+# gx 5, the residuals are (0, 0) and (1, 0): 0.
+HUGE_N = 2 ** 24 + 2
+HUGE_TRIPLE = [(1, 1, 1, 5, -3), (2, 1, 1, 5, -3), (2, 1, 1, 6, -3)]            # the records A, B and the odd one
+HUGE = {256: ((0, -3, 5, -3, HUGE_N, HUGE_N - 1, HUGE_N), 2), 255: ((5, -3, 5, -3, HUGE_N, HUGE_N - 1, HUGE_N), 0)}
+
+
+# ------------------------------------------------------------------ more frames than one trip of the clear kernels
+
+CLEAR_TRIP = 1024 * 256               # lanes of gmc_clear_kernel, zones_clear_kernel and blobs_clear_kernel: one element each
+CLEAR_FRAMES = CLEAR_TRIP + 300
+CLEAR_CASE = "pan_plus_object"        # compensated: 4 centres, info (5, 0, 5, 0, 48, 44, 48); plain: 36, one blob of 6 x 6
+CLEAR_BOX = (1, 0, 6, 5)              # the plain scan's centres: columns 1 .. 6 of every row, one component of 36 cells
+
+
+@functools.lru_cache(maxsize=None)
+def clear_batch():
+    """(mv, off, sd, planted frame indices): CLEAR_FRAMES frames that own no record and have no side data, but CLEAR_CASE
+    at frames 0, CLEAR_TRIP - 1, CLEAR_TRIP (the first element of the clear's second trip) and the last one, and frames
+    WITHOUT side data that own a pan of 9 next to them: 1, CLEAR_TRIP + 1 and the one before the last (CLEAR_TRIP - 1
+    and CLEAR_TRIP are neighbours: the frame behind the two serves both)."""
+    planted = (0, CLEAR_TRIP - 1, CLEAR_TRIP, CLEAR_FRAMES - 1)
+    pans = (1, CLEAR_TRIP + 1, CLEAR_FRAMES - 2)
+    counts = np.zeros(CLEAR_FRAMES, dtype=np.int64)
+    one, pan = hand_frame(CLEAR_CASE), voters(_pan(9, 0), 4)
+    counts[list(planted)], counts[list(pans)] = len(one), len(pan)
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+    mv = np.concatenate([one if f in planted else pan for f in sorted(planted + pans)])
+    sd = np.zeros(CLEAR_FRAMES, dtype=np.uint8)
+    sd[list(planted)] = 1
+    return frozen(mv, off, sd) + (planted,)
+
+
+# ------------------------------------------------------------------ a host batch that does not start at record 0
+
+REBASE = 4097
+
+
+@functools.lru_cache(maxsize=None)
+def embedded_pan_batch():
+    """(mv, off): pan_batch()'s records behind REBASE records that move by up to +-40 in the picture's middle and in front
+    of 1000 more of them; off = pan_batch()'s + REBASE.  A scan that read from record 0, or past off[-1], would count them."""
+    mv, off, sd, _, _ = pan_batch()
+    rng = np.random.RandomState(7)
+    pad = np.zeros(REBASE + 1000, dtype=m.MV_DTYPE)
+    pad["dst_x"], pad["dst_y"] = rng.randint(600, 1300, size=len(pad)), rng.randint(300, 800, size=len(pad))
+    pad["src_x"], pad["src_y"] = pad["dst_x"] - rng.randint(-40, 41, size=len(pad)), pad["dst_y"] - rng.randint(-40, 41, size=len(pad))
+    return frozen(np.concatenate([pad[:REBASE], mv, pad[REBASE:]]), (off + np.uint64(REBASE)).astype(np.uint64))

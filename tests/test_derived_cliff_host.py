@@ -59,7 +59,7 @@ def test_shape_is_the_last_one_that_fits(kernel, name):
         W = (gw + 63) // 64
         assert spv["thresholds_per_pass"] == 1 and need == spv["lds_bytes"] - n * (ch - 1) * W * 8
         assert LDS - spv["lds_bytes"] < n * W * 8 or ch == R          # the buffer took all the room a whole row fits in
-    elif kernel == "zones":
+    elif kernel in ("zones", "gmc"):
         assert need == pv["lds_bytes"]
     else:
         assert pv["acc_bits"] == 0 and need == pv["lds_bytes"]
@@ -204,6 +204,49 @@ def test_sweep_expected_values(kernel, name):
         assert 2 * int((first[rec] > 0).sum()) >= int(rec.sum())
 
 
+def test_gmc_shapes_are_the_ones_worked_by_hand():
+    """16 (gh + 2) + 2080 <= 163 840 on two columns (tile and mask plane take eight bytes a row each); 20 (gh + 2) on
+    three; (4 * 65 + 16) (gh + 2) and (4 * 193 + 32) (gh + 2), less the tile's padding, on 65 and 193."""
+    tall = {gw: gh for gw, gh, kind in dci.shapes("gmc").values() if kind == "tall"}
+    assert tall == {2: 10108, 3: 8086, 65: 584, 193: 199}
+    assert len(dci.shapes("gmc")) == len(dci.shapes("zones")) == 6
+    # a mask plane that starts on an odd number of 64-bit words is among them
+    assert any(((gh + 2) * ((gw + 63) // 64)) % 2 for gw, gh, _ in dci.shapes("gmc").values())
+
+
+@pytest.mark.parametrize("name", list(dci.shapes("gmc")))
+def test_gmc_expected_values(name):
+    """The numpy model and the oracle (consequence C) agree on the shape's batch under both settings; the planted pan
+    frames have their hand values in the model and in the oracle."""
+    import gmc_inputs as gi
+    import gmc_model as gm
+    import oracle_binding as ob
+    gw, gh, _ = dci.shapes("gmc")[name]
+    mv, off, sd, planted = dci.batch(gw, gh)
+    planted_is_planted(gw, gh, planted)
+    p = dci.grid_params(gw, gh, **dci.CTX_KW)
+    for ms, q8 in dci.GMC_SETTINGS:
+        fl, ce, rows = dci.gmc_expected(gw, gh, ms, q8)
+        fits, oc = dci.gmc_oracle_c(gw, gh, rows)
+        assert fits.all() and np.array_equal(oc, ce), (name, ms)      # every shifted src stays in int16 on these shapes
+        assert np.array_equal(fl, (ce >= 2).astype(np.uint8)) and not ce[sd == 0].any() and not rows[sd == 0].any()
+        if ms == 0:
+            assert not rows[:, :4].any() and np.array_equal(ce, ob.scan_centres(p, mv, off, sd, nthreads=4)[1])
+            assert gw == 2 or 2 * int((ce[with_records(off)] > 0).sum()) >= int(with_records(off).sum())
+        else:                                                         # a blob frame's movers can be its mode: fewer centres
+            assert gw == 2 or ce.any()
+            print(name, "max_shift", ms, "centres", ce.tolist(), "applied", rows[:, :2].tolist())
+    pp, pmv, poff, psd, hc, hi = dci.gmc_pan_case(name)
+    fl, ce, info = gm.gmc_batch(pp, pmv, poff, psd, dci.GMC_PAN_MAX_SHIFT, 128)
+    assert ce.tolist() == hc.tolist() and gi.info_rows(info).tolist() == hi.tolist(), name
+    assert (2 * hi[:, 5] > hi[:, 4]).all()                            # the fillers outnumber the pair records
+    moved = gm.shift_src(pmv, poff, hi[:, 0], hi[:, 1])
+    assert ob.scan_centres(pp, moved, poff, psd)[1].tolist() == hc.tolist()
+    plain = ob.scan_centres(pp, pmv, poff, psd)[1]
+    assert gw == 2 or (hc[0] > 0 and (plain >= hc).all())             # without compensation every pair passes the threshold
+    assert gm.gmc_batch(pp, pmv, poff, psd, 0, 128)[1].tolist() == plain.tolist()
+
+
 # ------------------------------------------------------------------ the soak's draws
 
 SOAK_REPLAYED = 40
@@ -229,6 +272,70 @@ def test_soak_draws_reach_the_kernels_and_carry_centres():
         assert 4 * supported[k] >= 3 * SOAK_REPLAYED, (k, supported)
         assert 2 * nonzero[k] >= supported[k], (k, nonzero, supported)
     assert min(supported.values()) < SOAK_REPLAYED                   # the unsupported answer is drawn too
+
+
+# sha256 (first 16 hex digits) over mv, off, thr, vec and keeps of the default seed's first eight draws, as draw() made
+# them before the compensated scan joined the soak
+DRAWS_BEFORE_GMC = ["675b176ee95000a1", "182bcdb169c4ea7b", "9adf7a58e431347b", "4aa1079ab9b30ab6", "5846d0fb9f3d8f54",
+                    "8ed9b9450ac5b6ea", "6ad47eaf9a24b42f", "23ad4b31b8bf6116"]
+
+
+def draw_digest(d):
+    import hashlib
+    h = hashlib.sha256()
+    for k in ("mv", "off", "thr", "vec", "keeps"):
+        v = d.get(k)
+        h.update(v.tobytes() if isinstance(v, np.ndarray) else repr(v).encode())
+    return h.hexdigest()[:16]
+
+
+def test_soak_draws_are_what_they_were_before_the_compensated_scan_joined():
+    """replay() and the recorded figures of docs/rounds/r07_derived_limits.md depend on the stream: the compensated scan's
+    inputs come from a RandomState of their own, and its copy of the records leaves d["mv"] alone."""
+    rng = np.random.RandomState(dsoak.DEFAULT_SEED)
+    for it, want in enumerate(DRAWS_BEFORE_GMC, start=1):
+        d = dsoak.draw(rng, it)
+        assert draw_digest(d) == want, it
+        if d["creatable"] and len(d["mv"]) and d["gmc_follow"] > 0:
+            assert d["gmc_mv"] is not d["mv"] and not np.array_equal(d["gmc_mv"], d["mv"])
+            for k in ("dst_x", "dst_y"):
+                assert np.array_equal(d["gmc_mv"][k], d["mv"][k])
+    # another seed draws other pans for the same iteration, and the same seed the same ones
+    a, b = dsoak.replay(dsoak.DEFAULT_SEED, 4), dsoak.replay(dsoak.DEFAULT_SEED, 4)
+    assert np.array_equal(a["gmc_pans"], b["gmc_pans"]) and np.array_equal(a["gmc_mv"], b["gmc_mv"])
+    c = dsoak.draw_gmc(dsoak.DEFAULT_SEED + 1, 4, a["params"], a["mv"], a["off"])
+    assert not np.array_equal(a["gmc_pans"], c["gmc_pans"])
+
+
+GMC_REPLAYED = 60
+
+
+def test_soak_draws_reach_the_compensated_scan():
+    """The default seed's first 60 iterations, from the reference alone: the compensated scan is supported in at least
+    three quarters of the creatable draws; in at least a third of the supported ones some frame is compensated on some
+    axis, in at least a third a compensated frame still has centres, and at least once a mode is found and not applied.
+    (test_soak_draws_reach_the_kernels_and_carry_centres holds the two sources against each other on the first 40.)"""
+    rng = np.random.RandomState(dsoak.DEFAULT_SEED)
+    creatable = supported = compensated = with_centres = lost = 0
+    shifts, shares, outside = set(), set(), 0
+    for it in range(1, GMC_REPLAYED + 1):
+        d = dsoak.draw(rng, it)
+        creatable += d["creatable"]
+        if not d["support"].get("gmc"):
+            continue
+        supported += 1
+        e = dsoak.expected(d, "gmc")
+        compensated += e["compensated"] > 0
+        with_centres += e["compensated_with_centres"] > 0
+        lost += e["found_not_applied"] > 0
+        shifts.add(d["gmc_max_shift"])
+        shares.add(d["gmc_share_q8"])
+        outside += bool((np.abs(d["gmc_pans"]) > d["gmc_max_shift"]).any())
+        assert (np.abs(d["gmc_pans"]) <= d["gmc_max_shift"] + 2).all()
+    print("creatable", creatable, "supported", supported, "compensated", compensated, "with centres", with_centres, "found, not applied", lost)
+    assert 4 * supported >= 3 * creatable and supported < creatable
+    assert 3 * compensated >= supported and 3 * with_centres >= supported and lost >= 1
+    assert shifts == set(dsoak.GMC_SHIFT_POOL) and shares == set(dsoak.GMC_SHARE_Q8_POOL) and outside >= 5
 
 
 def test_soak_preview_says_unsupported_as_the_library_does():

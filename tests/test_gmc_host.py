@@ -292,6 +292,107 @@ def test_big_residual_hand_values():
     assert [w for _, w in gi.BIG_THRESHOLDS] == [1, 1, 1, 0]
 
 
+# ------------------------------------------------------------------ the edge inputs of the GPU tier, by hand
+
+@pytest.mark.parametrize("name", list(gi.LANES))
+def test_model_reproduces_the_lane_cases(name):
+    """The ties and the near-tie between candidates of different lanes and trips of pick_mode: the bins hold what the
+    comments of gmc_inputs.LANES say, the model and the oracle (consequence C) give the hand values."""
+    thr, margin, cells, ms, q8, info, centres, plain = gi.LANES[name]
+    assert ms == 127 and all(gm.walk(127)[o] == v for v, o in gi.LANE_WALK.items())
+    p = gi.hand_params(thr, margin)
+    mv = voters_of(cells)
+    dx, dy = gm.displacements(mv)
+    bins = {"A": {-2, -34, 65}, "B": {127, 0}, "C": {32, -33}}
+    on = dict(zip("xy", re.match(r"lanes_(\w)_on_x_(\w)_on_y", name).groups()))
+    for axis, d in (("x", dx), ("y", dy)):
+        pattern = on[axis]
+        n = {v: int((d == v).sum()) for v in bins[pattern]}
+        top = max(int((d == v).sum()) for v in set(d.tolist()))
+        if pattern == "B":
+            assert n[127] == n[0] + 1 == top
+        else:
+            assert len(set(n.values())) == 1 and n[min(bins[pattern], key=abs)] == top
+    got_c, got_i = gm.gmc_frame(p, mv, ms, q8)
+    assert tuple(got_i[k] for k in gi.INFO_FIELDS) == info and got_c == centres, name
+    off, sd = np.array([0, len(mv)], dtype=np.uint64), np.ones(1, dtype=np.uint8)
+    assert int(ob.scan_centres(p, mv, off, sd)[1][0]) == plain
+    assert int(ob.scan_centres(p, gm.shift_src(mv, off, [info[0]], [info[1]]), off, sd)[1][0]) == centres
+    if q8 == 0:
+        # every other candidate of the tie, applied, counts something else: the centres show the winner
+        for ax, v in [(0, v) for v in bins[on["x"]]] + [(1, v) for v in bins[on["y"]]]:
+            g = list(info[:2])
+            if g[ax] != v:
+                g[ax] = v
+                assert gm.residual_centres(p, mv, g[0], g[1]) != centres, (name, ax, v)
+
+
+def voters_of(cells):
+    return dei.voters(cells, 4)
+
+
+def test_lane_batches_and_followers_by_hand():
+    seen = []
+    for (thr, margin, ms, q8), names, mv, off, sd, want_c, want_i, plain in gi.lane_batches():
+        p = gi.hand_params(thr, margin)
+        fl, ce, info = gm.gmc_batch(p, mv, off, sd, ms, q8)
+        assert ce.tolist() == want_c.tolist() and gi.info_rows(info).tolist() == want_i.tolist(), names
+        seen += list(names)
+    assert sorted(seen) == sorted(gi.LANES) and len(seen) == 7
+    # has_sd == NULL: "the frame owns no record" — the frames behind the hand cases are scanned then
+    empty = 0
+    for batches in (gi.hand_batches(), gi.lane_batches()):
+        for (thr, margin, ms, q8), names, mv, off, sd, want_c, want_i, plain in batches:
+            fl, ce, info = gm.gmc_batch(gi.hand_params(thr, margin), mv, off, None, ms, q8)
+            fc, fi = gi.follower_by_hand(margin, ms)
+            assert ce[0::2].tolist() == want_c[0::2].tolist() and gi.info_rows(info)[0::2].tolist() == want_i[0::2].tolist()
+            assert ce[1::2].tolist() == [fc] * len(names) and gi.info_rows(info)[1::2].tolist() == [list(fi)] * len(names)
+            empty += int((np.diff(off.astype(np.int64)) == 0).sum())
+    assert empty == 1                                                 # "no_records": reads 0 with and without has_sd
+
+
+def test_huge_frame_arithmetic_by_hand():
+    """2^24 + 2 records: the figures of gmc_inputs.HUGE from exact Python integers, what 32-bit products would give, and
+    the model on the three distinct records in the same proportions it can hold (support is a ratio)."""
+    n_in, n_x = gi.HUGE_N, gi.HUGE_N - 1
+    assert n_x * 256 == 2 ** 32 + 256 < 256 * n_in == 2 ** 32 + 512 and n_x * 256 >= 255 * n_in
+    assert (n_x << 8) % 2 ** 32 == 256 < 1 * n_in                                        # a wrapped left side fails even q8 = 1
+    assert (256 * n_in) % 2 ** 32 == 512 <= n_x * 256                                    # a wrapped right side passes q8 = 256
+    p = gi.hand_params(16.0, 0)
+    mv = voters_of(gi.HUGE_TRIPLE)
+    assert gm.residual_centres(p, mv, 0, -3) == gi.HUGE[256][1] == 2 and gm.residual_centres(p, mv, 5, -3) == gi.HUGE[255][1] == 0
+    c, info = gm.gmc_frame(p, mv, 16, 256)                            # 2 of 3 records: unsupported at 256, as 2^24 + 1 of 2^24 + 2
+    assert (c, info["gx"], info["gy"], info["mode_x"]) == (2, 0, -3, 5)
+    assert gi.HUGE[256][0][:4] == (0, -3, 5, -3) and gi.HUGE[255][0][:4] == (5, -3, 5, -3)
+
+
+def test_clear_batch_by_hand():
+    mv, off, sd, planted = gi.clear_batch()
+    F = gi.CLEAR_FRAMES
+    assert gi.CLEAR_TRIP == 262144 and F == 262444 and len(off) == F + 1 and planted == (0, 262143, 262144, F - 1)
+    n = np.diff(off.astype(np.int64))
+    assert n[list(planted)].tolist() == [48] * 4 and int((n > 0).sum()) == 7 and int(sd.sum()) == 4
+    assert not sd[[1, gi.CLEAR_TRIP + 1, F - 2]].any() and n[[1, gi.CLEAR_TRIP + 1, F - 2]].tolist() == [48] * 3
+    p = gi.hand_params(16.0, 0)
+    want = gi.HAND[gi.CLEAR_CASE]
+    for f in planted:
+        r = mv[int(off[f]):int(off[f + 1])]
+        c, info = gm.gmc_frame(p, r, want[3], want[4])
+        assert c == want[6] == 4 and tuple(info[k] for k in gi.INFO_FIELDS) == want[5]
+        assert int(ob.scan_centres(p, r, np.array([0, 48], dtype=np.uint64), np.ones(1, dtype=np.uint8))[1][0]) == want[7] == 36
+    assert gi.CLEAR_BOX == (1, 0, gi.GW - 2, gi.GH - 1) and want[7] == (gi.GW - 2) * gi.GH
+
+
+def test_embedded_batch_is_the_pan_batch_behind_4097_records():
+    mv, off, sd, _, _ = gi.pan_batch()
+    big, off2 = gi.embedded_pan_batch()
+    assert int(off2[0]) == gi.REBASE == 4097 and len(big) == len(mv) + 4097 + 1000 and int(off2[-1]) < len(big)
+    assert np.array_equal(big[4097:4097 + len(mv)], mv) and np.array_equal(off2 - off2[0], off)
+    # the records around the batch would be counted if they were read
+    p = m.ScanParams.from_config(1920, 1080, vectors_needed=1)
+    assert int(gm.counted(p, big[:4097]).sum()) == 4097 and int(gm.counted(p, big[-1000:]).sum()) == 1000
+
+
 # ------------------------------------------------------------------ the model against the oracle
 
 def test_model_with_max_shift_0_is_the_oracle():

@@ -1,6 +1,7 @@
-"""GPU tier (`-m gpu`): the sweep, the activity map and the masked scan on the last grids their LDS layouts hold — two,
-three, 65 and 193 columns at the largest height, one and three rows at the largest width, and for the activity map the
-last and the first grid of every plan outcome — through the C ABI's device entry points on both record layouts.
+"""GPU tier (`-m gpu`): the sweep, the activity map, the masked scan and the compensated scan on the last grids their LDS
+layouts hold — two, three, 65 and 193 columns at the largest height, one and three rows at the largest width, and for
+the activity map the last and the first grid of every plan outcome — through the C ABI's device entry points on both
+record layouts.
 
 The shapes, the batches and the values derived by hand come from tests/derived_cliff_inputs.py, which finds the shapes
 with the previews at 163 840 bytes of LDS; tests/test_derived_cliff_host.py proves without a GPU that they sit on the
@@ -142,3 +143,39 @@ def test_sweep_at_the_lds_limit(gpu_scanner_factory, kernel, name):
     out = junk_out(len(thr), len(vec), len(sd))
     refused(lambda: more.sweep_centres_device(d_rec, d_off, d_sd, thr, vec, compact=True, out=out))
     assert untouched(out, SWEEP_JUNK)
+
+
+# ------------------------------------------------------------------ the compensated scan
+
+@pytest.mark.parametrize("name", list(dci.shapes("gmc")))
+def test_gmc_at_the_lds_limit(gpu_scanner_factory, name):
+    """The histograms and the result words are the last things in the LDS, behind the tile and the mask plane: on the
+    last grid that fits, the shape's batch with max_shift 0 and with the defaults — centres, flags and info against the
+    numpy model, centres against the oracle on src-shifted records (consequence C; == the model, on the CPU) — then two
+    planted frames under a pan of (7, -3) against their hand values, then the grid one row or column further."""
+    import torch
+    from test_gpu_gmc import assert_info_equal, gmc_both_layouts
+    assert_lds_limit(gpu_scanner_factory)
+    gw, gh, kind = dci.shapes("gmc")[name]
+    mv, off, sd, _ = dci.batch(gw, gh)
+    s = gpu_scanner_factory(dci.grid_params(gw, gh, **dci.CTX_KW))
+    for ms, q8 in dci.GMC_SETTINGS:
+        want_f, want_c, want_i = dci.gmc_expected(gw, gh, ms, q8)
+        fits, oracle_c = dci.gmc_oracle_c(gw, gh, want_i)
+        for label, fl, ce, info in gmc_both_layouts(s, mv, off, sd, ms, q8, f"{name} max_shift {ms}"):
+            assert_counts_equal(ce, want_c, label, got_f=fl, want_f=want_f)
+            assert_info_equal(info, want_i, label)
+            assert_counts_equal(ce[fits], oracle_c[fits], label + " (C)")
+    pp, pmv, poff, psd, hand_c, hand_i = dci.gmc_pan_case(name)
+    ps = gpu_scanner_factory(pp)
+    for label, fl, ce, info in gmc_both_layouts(ps, pmv, poff, psd, dci.GMC_PAN_MAX_SHIFT, 128, name + " planted pan"):
+        assert_counts_equal(ce, hand_c, label, got_f=fl, want_f=(hand_c >= 2).astype(np.uint8))
+        assert_info_equal(info, hand_i, label)
+    more = gpu_scanner_factory(dci.grid_params(*dci.one_more(gw, gh, kind), **dci.CTX_KW))
+    d_rec, d_off, d_sd = to_device(mv, off, sd, True)
+    F = len(sd)
+    fl = torch.full((F,), JUNK_FLAG, dtype=torch.uint8, device="cuda")
+    ce = torch.full((F,), JUNK, dtype=torch.int32, device="cuda")
+    inf = torch.full((F, 5), JUNK, dtype=torch.int32, device="cuda")
+    refused(lambda: more.scan_gmc_device(d_rec, d_off, d_sd, 16, 128, compact=True, flags=fl, centres=ce, info=inf))
+    assert untouched(fl, JUNK_FLAG) and untouched(ce, JUNK) and untouched(inf, JUNK)

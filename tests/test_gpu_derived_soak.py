@@ -1,9 +1,10 @@
-"""Soak of the derived kernels: randomised parity of the sweep, the activity map and the masked scan for
-MTGPU_SOAK_SECONDS (default 4 s; set it to minutes to hunt rare faults).  Every iteration draws a grid, a parameter set,
-a ragged batch with runs and blobs, streams with empty ones, keep masks, sweep settings, a record layout and — every
-third time — a record base inside a larger buffer (tests/derived_soak.py, which also computes the expected values from
-the oracle and the numpy models and rebuilds any iteration on the CPU: derived_soak.replay(seed, it)).  Every
-comparison is exact; a kernel whose preview says unsupported must answer MT_ERR_UNSUPPORTED and touch nothing."""
+"""Soak of the derived kernels: randomised parity of the sweep, the activity map, the masked scan and the compensated
+scan for MTGPU_SOAK_SECONDS (default 4 s; set it to minutes to hunt rare faults).  Every iteration draws a grid, a
+parameter set, a ragged batch with runs and blobs, streams with empty ones, keep masks, sweep settings, a pan per frame
+with max_shift and min_share_q8, a record layout and — every third time — a record base inside a larger buffer
+(tests/derived_soak.py, which also computes the expected values from the oracle and the numpy models and rebuilds any
+iteration on the CPU: derived_soak.replay(seed, it)).  Every comparison is exact; a kernel whose preview says
+unsupported must answer MT_ERR_UNSUPPORTED and touch nothing."""
 import os
 import time
 
@@ -18,6 +19,7 @@ from scan_checks import assert_counts_equal
 from test_gpu_activity import assert_maps_equal, junk_maps
 from test_gpu_derived_cliff import assert_lds_limit
 from test_gpu_derived_edges import shifted
+from test_gpu_gmc import assert_info_equal
 from test_gpu_zones import keep_tensor, soff_tensor
 
 pytestmark = pytest.mark.gpu
@@ -25,11 +27,12 @@ pytestmark = pytest.mark.gpu
 JUNK, JUNK_FLAG = -7, 9
 
 
-def records_on_device(d):
-    """The records in the draw's layout; on a window iteration inside a larger buffer: 40-byte records shifted by 4, 12 or
-    20 bytes, compact ones with the first record on the drawn 8-byte residue of a 128-byte line."""
+def records_on_device(d, mv=None):
+    """The records (mv: another copy of them, record for record) in the draw's layout; on a window iteration inside a
+    larger buffer: 40-byte records shifted by 4, 12 or 20 bytes, compact ones with the first record on the drawn 8-byte
+    residue of a 128-byte line."""
     import torch
-    mv, compact = d["mv"], d["compact"]
+    mv, compact = d["mv"] if mv is None else mv, d["compact"]
     raw = (m.pack_records(mv) if compact else np.ascontiguousarray(mv, dtype=m.MV_DTYPE)).view(np.uint8).reshape(-1)
     host = torch.from_numpy(raw.copy())
     if d["window"] is None or raw.size == 0:
@@ -100,6 +103,23 @@ def check_draw(s, d, where):
         assert_counts_equal(ca.cpu().numpy().view(np.uint32), e["centres_all"], what + " centres_all")
     else:
         expect_unsupported(call, [fl, ce, ca], [JUNK_FLAG, JUNK, JUNK], "zones, " + where)
+    # the compensated scan, on its own copy of the records at the same base
+    g_rec = records_on_device(d, d["gmc_mv"])
+    fl = torch.full((F,), JUNK_FLAG, dtype=torch.uint8, device="cuda")
+    ce = torch.full((F,), JUNK, dtype=torch.int32, device="cuda")
+    inf = torch.full((F, 5), JUNK, dtype=torch.int32, device="cuda")
+    call = lambda: s.scan_gmc_device(g_rec, d_off, d_sd, d["gmc_max_shift"], d["gmc_share_q8"], compact=compact, flags=fl,   # noqa: E731
+                                     centres=ce, info=inf)
+    if d["support"]["gmc"]:
+        call()
+        torch.cuda.synchronize()
+        e = dsoak.expected(d, "gmc")
+        what = f"gmc max_shift {d['gmc_max_shift']} min_share_q8 {d['gmc_share_q8']} follow {d['gmc_follow']}, {where}"
+        assert_counts_equal(ce.cpu().numpy().view(np.uint32), e["centres"], what, got_f=fl.cpu().numpy(), want_f=e["flags"])
+        assert_info_equal(inf.cpu().numpy().reshape(-1).view(_abi.GMC_INFO_DTYPE), e["info"], what)
+        return e
+    expect_unsupported(call, [fl, ce, inf], [JUNK_FLAG, JUNK, JUNK], "gmc, " + where)
+    return None
 
 
 def test_soak_derived_kernels(gpu_scanner_factory):
@@ -110,9 +130,10 @@ def test_soak_derived_kernels(gpu_scanner_factory):
     t_end = time.time() + budget
     it = done = 0
     ran = {k: 0 for k in dsoak.KERNELS}
+    gmc = dict(compensated=0, compensated_with_centres=0, found_not_applied=0)
     while time.time() < t_end:
         it += 1
-        d = dsoak.draw(rng, it)
+        d = dsoak.draw(rng, it, seed)
         if not d["creatable"]:
             continue
         p = d["params"]
@@ -120,7 +141,7 @@ def test_soak_derived_kernels(gpu_scanner_factory):
                  f"window {d['window']}")
         s = gpu_scanner_factory(p)
         try:
-            check_draw(s, d, where)
+            g = check_draw(s, d, where)
         except (AssertionError, m.MtgpuError, pytest.fail.Exception) as e:
             raise AssertionError(f"{where} (derived_soak.replay({seed}, {it}) rebuilds the inputs): {e}") from e
         finally:
@@ -128,10 +149,13 @@ def test_soak_derived_kernels(gpu_scanner_factory):
         done += 1
         for k in dsoak.KERNELS:
             ran[k] += d["support"][k]
+        for k in gmc:
+            gmc[k] += g is not None and g[k] > 0
     # The budget is looked at between draws: a run overshoots it by at most one draw.  The costliest draw — the oracle on
     # 64 settings of 64 frames of 8000 records repeated 3.5 times, about 10^8 record visits on eight threads, and the numpy
     # models on 64 frames — takes about two seconds of CPU time, the average one a tenth of a second.  A second draw
     # starts whenever the first one ends inside the budget, so four seconds hold at least two; fewer means that the
     # expected values, not the kernels, have become the cost.
     assert done >= (2 if budget >= 4 else 1), f"only {done} configurations in {budget:.0f} s"
-    print(f"derived soak: {done} random configurations checked in {budget:.0f} s, kernels run {ran}")
+    print(f"derived soak: {done} random configurations checked in {budget:.0f} s, kernels run {ran}, the compensated scan's "
+          f"draws with a frame compensated / one that keeps centres / a mode found and not applied: {gmc}")

@@ -373,3 +373,139 @@ def test_end_to_end_command_on_a_shaken_stream(tmp_path):
             assert abs(int(info["gx"][f]) + cams[f][0]) <= 1 and abs(int(info["gy"][f]) + cams[f][1]) <= 1, f
     top = doc["vectors"][0]
     assert top[2] == int(((info["gx"] == top[0]) & (info["gy"] == top[1]) & (np.asarray(batch.has_sd) != 0)).sum())
+
+
+# ------------------------------------------------------------------ 8. the pick across lanes and trips
+
+def test_pick_across_lanes_and_trips(gpu_scanner_factory):
+    """gi.LANES, max_shift 127: ties between walk indices 3, 67 and 130, between 64 and 65, and index 254 one record ahead
+    of index 0 — candidates that pick_mode meets in different lanes and in different trips of its loop — a different
+    pattern on each axis of a frame; applied (min_share_q8 0) and with a share just missed.  Hand values."""
+    seen = 0
+    for (thr, margin, ms, q8), names, mv, off, sd, want_c, want_i, plain in gi.lane_batches():
+        s = gpu_scanner_factory(gi.hand_params(thr, margin))
+        for label, fl, ce, info in gmc_both_layouts(s, mv, off, sd, ms, q8, "/".join(names)):
+            assert_counts_equal(ce, want_c, label, got_f=fl, want_f=(want_c >= 1).astype(np.uint8))
+            assert_info_equal(info, want_i, label)
+        hf, hc, hi = s.scan_gmc(m.FrameBatch(mv, off, None, sd), ms, q8)
+        assert_counts_equal(hc, want_c, "host entry " + "/".join(names), got_f=hf, want_f=(want_c >= 1).astype(np.uint8))
+        assert_info_equal(hi, want_i, "host entry " + "/".join(names))
+        seen += len(names)
+    assert seen == len(gi.LANES) == 7
+
+
+# ------------------------------------------------------------------ 9. has_sd == NULL
+
+def test_has_sd_null_scans_every_frame_that_owns_records(gpu_scanner_factory):
+    """include/mtgpu_gmc.h: "has_sd == NULL: the frame owns no record".  The hand batches without has_sd on both entry
+    points: the hand cases as before, the pans of 9 behind them by gi.follower_by_hand, the empty frame 0 everywhere."""
+    for batches in (gi.hand_batches(), gi.lane_batches()):
+        for (thr, margin, ms, q8), names, mv, off, sd, want_c, want_i, plain in batches:
+            fc, fi = gi.follower_by_hand(margin, ms)
+            want_c, want_i = want_c.copy(), want_i.copy()
+            want_c[1::2], want_i[1::2] = fc, fi
+            want_f = (want_c >= 1).astype(np.uint8)
+            s = gpu_scanner_factory(gi.hand_params(thr, margin))
+            for label, fl, ce, info in gmc_both_layouts(s, mv, off, None, ms, q8, "no has_sd " + "/".join(names)):
+                assert_counts_equal(ce, want_c, label, got_f=fl, want_f=want_f)
+                assert_info_equal(info, want_i, label)
+            hf, hc, hi = s.scan_gmc(m.FrameBatch(mv, off, None, None), ms, q8)
+            assert_counts_equal(hc, want_c, "host entry, no has_sd " + "/".join(names), got_f=hf, want_f=want_f)
+            assert_info_equal(hi, want_i, "host entry, no has_sd " + "/".join(names))
+            if "no_records" in names:
+                f = 2 * names.index("no_records")
+                assert int(off[f]) == int(off[f + 1]) and not gi.info_rows(hi)[f].any() and hc[f] == 0 and hf[f] == 0
+
+
+# ------------------------------------------------------------------ 10. the host entry on a batch that starts at record 4097
+
+def test_host_entry_rebases_the_records(gpu_scanner_factory):
+    """mtgpu_scan_frames_gmc copies only the records frame_off spans and plans with rebase = frame_off[0]: pan_batch()
+    inside a larger array, frame_off[0] == 4097 and 1000 records behind frame_off[-1], equals the call on the batch alone
+    and the model."""
+    mv, off, sd, _, _ = gi.pan_batch()
+    big, off2 = gi.embedded_pan_batch()
+    p = m.ScanParams.from_config(1920, 1080, vectors_needed=1)
+    s = gpu_scanner_factory(p)
+    want_f, want_c, want_i = gm.gmc_batch(p, mv, off, sd, gi.PAN_MAX_SHIFT, 128)
+    af, ac, ai = s.scan_gmc(m.FrameBatch(mv, off, None, sd), gi.PAN_MAX_SHIFT, 128)
+    gf, gc, gi_ = s.scan_gmc(m.FrameBatch(big, off2, None, sd), gi.PAN_MAX_SHIFT, 128)
+    assert_counts_equal(gc, want_c, "embedded batch against the model", got_f=gf, want_f=want_f)
+    assert_info_equal(gi_, gi.info_rows(want_i), "embedded batch against the model")
+    assert_counts_equal(gc, ac, "embedded batch against the aligned call", got_f=gf, want_f=af)
+    assert gi_.tobytes() == ai.tobytes()
+    # and without has_sd: the same frames own the same records
+    nf, nc, ni = s.scan_gmc(m.FrameBatch(big, off2, None, None), gi.PAN_MAX_SHIFT, 128)
+    wf, wc, wi = gm.gmc_batch(p, mv, off, None, gi.PAN_MAX_SHIFT, 128)
+    assert_counts_equal(nc, wc, "embedded batch without has_sd", got_f=nf, want_f=wf)
+    assert_info_equal(ni, gi.info_rows(wi), "embedded batch without has_sd")
+
+
+# ------------------------------------------------------------------ 11. 2^24 records in one frame
+
+def test_support_and_pick_in_64_bits_on_2_pow_24_records(gpu_scanner_factory):
+    """gi.HUGE: n_x * 256 = 2^32 + 256 against 256 * n_in = 2^32 + 512 — unsupported, centres 2 — and against 255 * n_in —
+    supported, centres 0.  Compact records, repeated on the device from two 8-byte patterns (134 MB; the host never
+    holds them); one workgroup streams the frame twice."""
+    import time
+    import torch
+    a, b, c = m.pack_records(dei.voters(gi.HUGE_TRIPLE, 4)).view(np.int64).tolist()
+    d_rec = torch.empty(gi.HUGE_N, dtype=torch.int64, device="cuda")
+    d_rec[0::2], d_rec[1::2] = a, b
+    d_rec[-1] = c
+    d_off = torch.tensor([0, gi.HUGE_N], dtype=torch.int64, device="cuda")
+    d_sd = torch.ones(1, dtype=torch.uint8, device="cuda")
+    s = gpu_scanner_factory(gi.hand_params(16.0, 0))
+    for q8, (want_i, want_c) in gi.HUGE.items():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fl, ce, info = device_gmc(s, d_rec, d_off, d_sd, 16, q8, True)
+        print(f"2^24 + 2 records, min_share_q8 {q8}: {1e3 * (time.perf_counter() - t0):.1f} ms for the call")
+        assert_info_equal(info, [want_i], f"2^24 + 2 records, min_share_q8 {q8}")
+        assert_counts_equal(ce, [want_c], f"2^24 + 2 records, min_share_q8 {q8}", got_f=fl, want_f=[int(want_c >= 1)])
+
+
+# ------------------------------------------------------------------ 12. more frames than one trip of the clear kernels
+
+@pytest.mark.parametrize("which", ["gmc", "zones", "blobs"])
+def test_clear_kernels_second_trip(gpu_scanner_factory, which):
+    """gi.clear_batch(): 262 144 + 300 frames, so that gmc_clear_kernel (1024 x 256 lanes) writes the elements from
+    262 144 on in a second trip of its loop; all of them read 0 only because of it, but the four planted frames (0, the
+    last of the first trip, the first of the second, the last), which read the hand values.  gmc: all three outputs,
+    then centres alone.  zones, blobs: the same batch through the masked scan (one stream, every cell kept) and the
+    blobs, whose clear kernels have the same loop, against the plain scan's hand values of those frames."""
+    import torch
+    from test_gpu_blobs import JUNK_BOX, device_blobs
+    from test_gpu_zones import device_zones, keep_tensor, soff_tensor
+    mv, off, sd, planted = gi.clear_batch()
+    F, idx = gi.CLEAR_FRAMES, list(planted)
+    thr, margin, _, ms, q8, info1, c1, plain1 = gi.HAND[gi.CLEAR_CASE]
+    s = gpu_scanner_factory(gi.hand_params(thr, margin))
+    want_c, want_i, want_p = np.zeros(F, dtype=np.uint32), np.zeros((F, 7), dtype=np.int64), np.zeros(F, dtype=np.uint32)
+    want_c[idx], want_i[idx], want_p[idx] = c1, info1, plain1
+    want_box = np.full((F, 4), 0xFFFF, dtype=np.int64)
+    want_box[idx] = gi.CLEAR_BOX
+    assert JUNK_BOX != 0xFFFF
+    for compact in (False, True):
+        label = f"{F} frames, {'compact' if compact else '40-byte'}"
+        d_rec, d_off, d_sd = to_device(mv, off, sd, compact)
+        if which == "gmc":
+            fl, ce, info = device_gmc(s, d_rec, d_off, d_sd, ms, q8, compact)
+            assert_counts_equal(ce, want_c, label, got_f=fl, want_f=(want_c >= 1).astype(np.uint8))
+            assert_info_equal(info, want_i, label)
+            alone = torch.full((F,), JUNK, dtype=torch.int32, device="cuda")
+            s.scan_gmc_device(d_rec, d_off, d_sd, ms, q8, compact=compact, flags=False, centres=alone, info=False)
+            torch.cuda.synchronize()
+            assert_counts_equal(alone.cpu().numpy().view(np.uint32), want_c, label + ", centres alone")
+        elif which == "zones":
+            d_soff, d_keep = soff_tensor([0, F]), keep_tensor(np.ones((1, gi.GH, gi.GW), dtype=bool))
+            zf, zc, za = device_zones(s, d_rec, d_off, d_sd, d_soff, d_keep, compact)
+            assert_counts_equal(zc, want_p, label + ", masked scan", got_f=zf, want_f=(want_p >= 1).astype(np.uint8))
+            assert_counts_equal(za, want_p, label + ", masked scan centres_all")
+        else:
+            got = device_blobs(s, d_rec, d_off, d_sd, compact)
+            for k, w in (("centres", want_p), ("blobs", want_p > 0), ("largest", want_p)):
+                assert_counts_equal(got[k], w, f"{label}, blobs: {k}")
+            assert np.array_equal(got["flags"], (want_p >= 1).astype(np.uint8)), label + ", blobs: flags"
+            bad = np.flatnonzero((got["box"].astype(np.int64).reshape(-1, 4) != want_box).any(axis=1))
+            assert bad.size == 0, (label, "blobs: boxes differ at", bad[:8].tolist(), got["box"].reshape(-1, 4)[bad[:4]].tolist())
