@@ -471,4 +471,9 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * (src/motion_scanner.cpp:246-251 thresholds a vector's own magnitude) — three more entry points, declared the same way. */
 #include "mtgpu_gmc.h"
 
+/* Global-motion compensation on the decode path: a pipe that runs the compensated scan for every batch, its estimate
+ * and its vote under the pipe's keep mask where it has one (src/motion_scanner.cpp:246-292 on the residuals at the call
+ * site of :375-383) — two more entry points, declared the same way. */
+#include "mtgpu_pipe_gmc.h"
+
 #endif /* MTGPU_H */

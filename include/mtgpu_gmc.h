@@ -49,9 +49,10 @@
  *     wherever that stays inside int16.
  *  D. vn == 0: the result equals the plain centre scan (every cell of the grid is active whatever the votes are).
  *
- * Out of scope: keep masks; blobs; the pipe form and mtgpu_scan_file; the row-banded grids (960x540, 32767-wide), which
- * are MT_ERR_UNSUPPORTED with the grid named, as for the zones and the blobs; rotation or zoom models — this is a
- * translation only; any use of neighbouring frames — frames stay independent.
+ * Out of scope: keep masks; blobs; the pipe form and mtgpu_scan_file — of THESE entry points: the decode path has its own
+ * two, which honour the pipe's keep mask in the estimate and in the vote (mtgpu_pipe_gmc.h), still without blobs; the
+ * row-banded grids (960x540, 32767-wide), which are MT_ERR_UNSUPPORTED with the grid named, as for the zones and the
+ * blobs; rotation or zoom models — this is a translation only; any use of neighbouring frames — frames stay independent.
  *
  * Kernel (csrc/gmc_kernels.hip): one workgroup per frame with side data; a first pass over the frame's records fills two
  * histograms in LDS, one wave picks the modes, a second pass over the same records votes the residuals into one tile of

@@ -56,5 +56,19 @@ int ctx_launch_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const 
 // MT_OK when the blob scan has a form for the context's grid; MT_ERR_UNSUPPORTED (the grid is named) as
 // mtgpu_blobs_preview otherwise.  No HIP call.
 int ctx_blobs_supported(const mtgpu_ctx *c);
+// Launch the compensated scan (gmc_kernels.hip, the pipe form) for a pipe's staging batch on `st`: as ctx_launch_zones,
+// with d_keep = ONE keep plane in device memory or nullptr (no mask), max_shift in [0, 127], min_share_q8 in [0, 256] and
+// d_count = the batch's ONE count array or nullptr, which receives (uint16)gx | (uint16)gy << 16 when report_vector
+// (d_count is then required), else the frame's centre count.  plan_ws / plan_ws_bytes are REQUIRED (the batch's own
+// block): nothing is taken from the context's scratch ring.  outputs_in_host_memory: d_flags / d_count are pinned host
+// memory and are stored at system scope, the planner's answers for frames without side data too.  With
+// mtgpu_profile_enable on it records the same event triple as ctx_launch_scan.  MT_ERR_UNSUPPORTED as mtgpu_gmc_preview.
+int ctx_launch_gmc(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
+                   uint32_t n_frames, const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int report_vector,
+                   uint8_t *d_flags, uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
+                   size_t plan_ws_bytes);
+// MT_OK when the compensated scan has a form for the context's grid; MT_ERR_UNSUPPORTED (the grid is named) as
+// mtgpu_gmc_preview otherwise.  No HIP call.
+int ctx_gmc_supported(const mtgpu_ctx *c);
 
 }  // namespace mtgpu

@@ -19,7 +19,9 @@ constexpr int kGmcInfoWords = 5;     // mt_gmc_info: 20 bytes
 
 // LDS of one workgroup, in this order (R = analysed rows, at least 1; W = 64-bit words per mask row):
 //   tile     (R + 2) x gw u32, padded to 4 words   vote counters: the analysed rows and one halo row each side
-//   amask    (R + 2) x W u64                       the frame's active cells; mask row j <-> grid row y_lo - 1 + j
+//   amask    (R + 2) x W u64                       the frame's active cells; mask row j <-> grid row y_lo - 1 + j.  Dead
+//                                                  until the masks are built: the pipe form keeps the keep words of the
+//                                                  analysed rows in rows 1 .. R until then (keep row r <-> mask row r + 1)
 //   hist     2 x kGmcHistBins u32                  hx, hy: bin v + max_shift holds the records displaced by v
 //   res      8 u32                                 [0] centres, [1] n_in, [2] gx, [3] gy, [4] mode_x, [5] mode_y, [6] n_x, [7] n_y
 inline size_t gmc_tile_words(int gw, int R) {
@@ -55,6 +57,15 @@ struct GmcLaunch {
   unsigned char *flags;                   // n_frames bytes, device memory, or null
   unsigned int *centres;                  // n_frames words, or null
   unsigned int *info;                     // n_frames x kGmcInfoWords words (mt_gmc_info), or null
+  // The pipe form (pipe.hip's staging batches; include/mtgpu_pipe_gmc.h): no clear kernel — launch_plan gets flags and
+  // centres and answers the frames without side data; the results are stored at system scope where sys_flags /
+  // sys_centres say that the array is not device memory (a zero-copy batch's pinned block); `keep`: ONE plane of gh x W
+  // words in device memory, or null — counted records and active cells of the analysed rows need their keep bit;
+  // report_vector: centres receives (uint16)gx | (uint16)gy << 16 in place of the centre count.  No info.
+  // 0: the form of mtgpu_scan_gmc_device — plain stores; keep must be null, sys_* and report_vector 0.
+  int pipe = 0;
+  const unsigned long long *keep = nullptr;
+  int sys_flags = 0, sys_centres = 0, report_vector = 0;
   GmcK k;
   int lds_bytes;
   int lds_max;                            // device limit of dynamic LDS per workgroup
@@ -64,7 +75,8 @@ struct GmcLaunch {
   hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the scan kernel; else nullptr
 };
 
-// Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.
+// Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.  Pipe form: no fill —
+// the planner answers the frames without side data.
 hipError_t launch_gmc_scan(const GmcLaunch &L);
 
 }  // namespace mtgpu

@@ -24,6 +24,15 @@
 //   Every output element has one writer after the clear: lane 0 of the frame's workgroup, plain vector stores, no global
 //   atomics.
 //
+// The pipe form (PIPE, include/mtgpu_pipe_gmc.h): no clear kernel — the planner answers the frames without side data and
+// every listed frame's workgroup stores the flag and ONE count on the kernel's one exit, through store_flag /
+// store_centres at the outputs' scope; no info.  With a keep plane the estimate counts a record only where the keep bit
+// of its destination cell is set, and the active plane is the masked one of the zones kernel.  The keep words of the
+// analysed rows take no LDS of their own: they are staged into the amask rows they will be ANDed into (keep row r <->
+// mask row r + 1), which are dead until row_masks writes them; row_masks visits every (row, word) once, and the lane that
+// stores a word is the one that reads the keep word under it.  keep == nullptr is a workgroup-uniform branch around the
+// staging and around the per-record lookup.
+//
 // record_stream.h is used as it is; nothing here changes the siblings' device code.  Both passes read with the
 // streaming hint: with or without it the second pass comes from HBM (docs/rounds/r10_gmc.md).
 #if !defined(__HIP_DEVICE_COMPILE__) || defined(__gfx950__)
@@ -100,10 +109,14 @@ __global__ __launch_bounds__(256) void gmc_clear_kernel(unsigned char *__restric
 
 // Waves per SIMD as for the zones kernel: 1080p takes about 35 KB of LDS, the lane limit decides (two workgroups per CU,
 // eight waves per SIMD, at most 64 VGPRs); the 4K workgroup sits alone on its CU.
-template <int BLOCK, int UNROLL, int REC>
+// PIPE: the form for a pipe's staging batch — `info` is not read (null), `keep` is ONE plane (gh x W words) or null, the
+// results leave through store_flag / store_centres with sys_flags / sys_centres, and with report_vector the count is the
+// applied vector, (uint16)gx | (uint16)gy << 16.  !PIPE: keep / sys_* / report_vector are not read (null / 0).
+template <int BLOCK, int UNROLL, int REC, bool PIPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void gmc_frames_kernel(
     const unsigned char *__restrict__ mv, const WorkItem *__restrict__ work, unsigned int item0, unsigned int n_items, GmcK k,
-    unsigned char *__restrict__ flags, unsigned int *__restrict__ centres, unsigned int *__restrict__ info) {
+    unsigned char *__restrict__ flags, unsigned int *__restrict__ centres, unsigned int *__restrict__ info,
+    const unsigned long long *__restrict__ keep, int sys_flags, int sys_centres, int report_vector) {
   extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
   const unsigned int item = item0 + blockIdx.x;
   if (item >= n_items) return;
@@ -129,6 +142,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     for (int j = tid; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
     if (tid < 2 * kGmcHistBins + 8) hx[tid] = 0u;              // hx, hy and res are contiguous
   }
+  if constexpr (PIPE) {
+    // the keep words of the analysed rows into mask rows 1 .. crows (crows <= R: inside the (R + 2) x W plane); keep row
+    // y_lo + r, r < crows, lies inside the gh x W plane
+    if (keep != nullptr) {
+      const unsigned long long *kp = keep + (size_t)k.y_lo * (size_t)k.W;
+      const int nkeep = crows * k.W;
+      for (int j = tid; j < nkeep; j += BLOCK) amask[(size_t)k.W + j] = kp[j];
+    }
+  }
   __syncthreads();
   // ---- the estimate (an empty analysed range counts nothing: nothing to read)
   if (crows > 0) {
@@ -142,8 +164,30 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
       hist_add(hx, dx + ms, in && (unsigned int)(dx + ms) <= (unsigned int)(2 * ms));
       hist_add(hy, dy + ms, in && (unsigned int)(dy + ms) <= (unsigned int)(2 * ms));
     };
-    if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(recs, nrec, one);
-    else stream_mv40<BLOCK, UNROLL>(recs, nrec, one);
+    if constexpr (PIPE) {
+      if (keep != nullptr) {
+        // counted: inside the bounds AND the keep bit of the destination cell (one LDS read per counted record; a record
+        // outside the bounds reads nothing)
+        const unsigned long long *kl = amask + k.W;
+        const auto onek = [=, &k, &mine](const MvFields m) {
+          const int gx = m.dst_x >> k.shift, gy = m.dst_y >> k.shift;
+          bool in = ((unsigned int)gx < (unsigned int)k.gw) & ((unsigned int)(gy - k.y_lo) < (unsigned int)(k.y_hi - k.y_lo));
+          if (in) in = ((kl[(gy - k.y_lo) * k.W + (gx >> 6)] >> (gx & 63)) & 1ull) != 0ull;
+          const int dx = m.dst_x - m.src_x, dy = m.dst_y - m.src_y;
+          mine += in ? 1u : 0u;
+          hist_add(hx, dx + ms, in && (unsigned int)(dx + ms) <= (unsigned int)(2 * ms));
+          hist_add(hy, dy + ms, in && (unsigned int)(dy + ms) <= (unsigned int)(2 * ms));
+        };
+        if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(recs, nrec, onek);
+        else stream_mv40<BLOCK, UNROLL>(recs, nrec, onek);
+      } else {
+        if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(recs, nrec, one);
+        else stream_mv40<BLOCK, UNROLL>(recs, nrec, one);
+      }
+    } else {
+      if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(recs, nrec, one);
+      else stream_mv40<BLOCK, UNROLL>(recs, nrec, one);
+    }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
     if ((tid & 63) == 0 && mine) atomicAdd(&res[1], mine);
@@ -166,7 +210,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   __syncthreads();
   const int cgx = __builtin_amdgcn_readfirstlane((int)res[2]), cgy = __builtin_amdgcn_readfirstlane((int)res[3]);
   // ---- the votes on the residuals
-  if (crows > 0) {
+  int vrows = crows;
+  // pipe form: the test is taken anew (else its 64-bit result is held across the estimate, in VGPR lanes: an SGPR spill)
+  if constexpr (PIPE) vrows = __builtin_amdgcn_readfirstlane(crows);
+  if (vrows > 0) {
     const auto one = [=, &k](const MvFields m) {
       const int rx = (m.dst_x - m.src_x) - cgx, ry = (m.dst_y - m.src_y) - cgy;   // |r| <= 65535 + 127
       const unsigned int ax = (unsigned int)(rx < 0 ? -rx : rx), ay = (unsigned int)(ry < 0 ? -ry : ry);
@@ -181,8 +228,18 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   }
   __syncthreads();
   // ---- the masks, then the centre count (the zones kernel's, one plane)
-  row_masks<BLOCK>(tile, k, t0, t1, k.y_lo - 1, crows + 2,
-                   [=, &k](int j, int w, int g, unsigned long long m) { amask[(size_t)j * k.W + w] = m; });
+  if constexpr (PIPE) {
+    // an analysed row's word is ANDed with the keep word it overwrites (staged above); halo rows are stored as they come
+    const bool masked = keep != nullptr;
+    row_masks<BLOCK>(tile, k, t0, t1, k.y_lo - 1, crows + 2, [=, &k](int j, int w, int g, unsigned long long m) {
+      unsigned long long *slot = amask + (size_t)j * k.W + w;
+      const bool analysed = masked && g >= k.y_lo && g < k.y_hi;
+      *slot = analysed ? (m & *slot) : m;
+    });
+  } else {
+    row_masks<BLOCK>(tile, k, t0, t1, k.y_lo - 1, crows + 2,
+                     [=, &k](int j, int w, int g, unsigned long long m) { amask[(size_t)j * k.W + w] = m; });
+  }
   __syncthreads();
   {
     const int W = k.W;
@@ -198,6 +255,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   __syncthreads();
   if (tid == 0) {
     const unsigned int c = res[0];
+    if constexpr (PIPE) {                                       // the one exit: a reused pinned block holds the previous batch's values
+      if (centres) store_centres(centres, f, report_vector ? ((res[2] & 0xffffu) | (res[3] << 16)) : c, sys_centres);
+      if (flags) store_flag(flags, f, (unsigned char)(c >= k.clust_need ? 1 : 0), sys_flags);
+      return;
+    }
     if (centres) centres[f] = c;
     if (flags) flags[f] = (unsigned char)(c >= k.clust_need ? 1 : 0);
     if (info) {
@@ -213,16 +275,16 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 
 namespace {
 
-template <int REC>
+template <int REC, bool PIPE>
 hipError_t launch_frames(const GmcLaunch &L) {
-  auto kern = gmc_frames_kernel<kGmcBlock, kGmcUnroll, REC>;
+  auto kern = gmc_frames_kernel<kGmcBlock, kGmcUnroll, REC, PIPE>;
   static std::atomic<unsigned long long> ready{0ull};
   hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
   if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
   return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
     hipLaunchKernelGGL(kern, dim3(n), dim3(kGmcBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.k,
-                       L.flags, L.centres, L.info);
+                       L.flags, L.centres, L.info, L.keep, L.sys_flags, L.sys_centres, L.report_vector);
   });
 }
 
@@ -232,11 +294,26 @@ hipError_t launch_gmc_scan(const GmcLaunch &L) {
   if (L.n_frames == 0) return hipSuccess;
   if (L.rec_bytes != 40 && L.rec_bytes != 8) return hipErrorInvalidValue;
   if (!L.flags && !L.centres && !L.info) return hipErrorInvalidValue;
+  if (L.pipe) {
+    if (L.info || (L.report_vector && !L.centres)) return hipErrorInvalidValue;
+  } else {
+    if (L.keep || L.sys_flags != 0 || L.sys_centres != 0 || L.report_vector != 0) return hipErrorInvalidValue;
+  }
   if (!L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records) return hipErrorInvalidValue;
   if (L.k.max_shift < 0 || L.k.max_shift > kGmcMaxShift || L.k.min_share_q8 > 256u) return hipErrorInvalidValue;
   if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.lds_bytes > L.lds_max ||
       (size_t)L.lds_bytes < gmc_lds_bytes(L.k.gw, L.k.R))
     return hipErrorInvalidValue;
+  if (L.pipe) {
+    // The keep rows are staged into the mask plane and indexed by the kernel: the block's layout fields must be the grid's.
+    if ((size_t)L.k.tile_words != gmc_tile_words(L.k.gw, L.k.R) || L.k.W != (L.k.gw + 63) / 64 || L.k.y_lo < 0 || L.k.y_hi > L.k.gh)
+      return hipErrorInvalidValue;
+    // The planner is handed the outputs and answers every frame without side data itself (at the outputs' scope), as in
+    // launch_scan, launch_zone_scan and launch_blob_scan: no clear kernel — planning + one kernel.
+    hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres, L.sys_centres);
+    if (e != hipSuccess) return e;
+    return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
+  }
   {
     const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
     hipLaunchKernelGGL(gmc_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream,
@@ -247,7 +324,7 @@ hipError_t launch_gmc_scan(const GmcLaunch &L) {
   // flags / centres null: the planner answers nothing itself (the outputs are zero already)
   hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
   if (e != hipSuccess) return e;
-  return L.rec_bytes == 8 ? launch_frames<8>(L) : launch_frames<40>(L);
+  return L.rec_bytes == 8 ? launch_frames<8, false>(L) : launch_frames<40, false>(L);
 }
 
 }  // namespace mtgpu

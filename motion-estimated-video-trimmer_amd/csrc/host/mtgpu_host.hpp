@@ -30,6 +30,7 @@
 #include <cstring>
 #include <fstream>
 #include <memory>
+#include <map>
 #include <mutex>
 #include <queue>
 #include <stdexcept>
@@ -722,6 +723,8 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   std::vector<uint64_t> keep_;                         // set_keep(): the keep mask initialize() hands to the pipe; empty: none
   int min_blob_cells_ = 0;                             // set_min_blob_cells(): the pipe's blob setting; 0: off
   bool report_largest_ = false;                        // report_largest(): last_centres() holds the largest blob, not the centres
+  int gmc_max_shift_ = -1, gmc_min_share_q8_ = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;   // set_gmc(): the pipe's compensation; max_shift < 0: off
+  bool report_vector_ = false;                         // report_vector(): last_centres() holds the packed applied vector
   bool ok(int rc) {
     if (rc == MT_OK) return true;
     err_ = mtgpu_last_error();
@@ -833,6 +836,15 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   // settles the pipe's blob setting — it sets this one or turns off whatever a pooled pipe carries.
   void set_min_blob_cells(int n) { min_blob_cells_ = n; }
   void report_largest(bool on) { report_largest_ = on; }
+  // Call before initialize().  Global-motion compensation for this video (include/mtgpu_pipe_gmc.h): every check_frame
+  // of scan_range (:375-383) thresholds the residuals of the frame's dominant vector, estimated within +-max_shift from
+  // the records of kept cells (set_keep) and applied where min_share_q8 / 256 of them agree.  max_shift < 0: off.
+  // report_vector(true): last_centres() returns {pts, (uint16)gx | (uint16)gy << 16} in place of the centre counts
+  // (needs keep_centres(true): the pipe has ONE count array).  Not together with set_min_blob_cells(n > 0) or
+  // report_largest.  Like the mask, initialize() ALWAYS settles the pipe's setting — it sets this one or turns off
+  // whatever a pooled pipe carries.
+  void set_gmc(int max_shift, int min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8) { gmc_max_shift_ = max_shift; gmc_min_share_q8_ = min_share_q8; }
+  void report_vector(bool on) { report_vector_ = on; }
 
   // batch_records == 0: sized from the source and the staging layout — MTGPU_BATCH_MB MiB of
   // pinned staging per batch, and never less than two frames of one record per 4x4 block (the
@@ -848,6 +860,8 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
     if (!be_->ensure(src_.width(), src_.height(), device_, batch_records, batch_frames, n_buffers, err_, keep_centres_)) return false;
     pipe_ = be_->pipe();
     // the pipe is idle here (a previous scanner on this backend left nothing in flight, or the backend was rebuilt)
+    // compensation off first: a pooled pipe that carries it would refuse the blob setting below
+    if (mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
     {
       if (min_blob_cells_ < 0) { err_ = "min_blob_cells is " + std::to_string(min_blob_cells_); (void)mtgpu_pipe_set_blobs(pipe_, 0, 0); pipe_ = nullptr; return false; }
       if (report_largest_ && !keep_centres_) { err_ = "report_largest needs keep_centres: the largest blob travels in the pipe's count array"; (void)mtgpu_pipe_set_blobs(pipe_, 0, 0); pipe_ = nullptr; return false; }
@@ -855,6 +869,19 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
       if (mtgpu_pipe_set_blobs(pipe_, n, n > 0 && report_largest_ ? MT_PIPE_REPORT_LARGEST : MT_PIPE_REPORT_CENTRES) != MT_OK) {
         err_ = mtgpu_last_error();
         (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);               // whatever fails here, no stale setting stays behind
+        pipe_ = nullptr;
+        return false;
+      }
+    }
+    if (gmc_max_shift_ >= 0 || report_vector_) {
+      const char *bad = nullptr;
+      if (gmc_max_shift_ < 0) bad = "report_vector needs set_gmc: there is no applied vector without compensation";
+      else if (min_blob_cells_ > 0 || report_largest_) bad = "compensation and blobs are not together yet";
+      else if (report_vector_ && !keep_centres_) bad = "report_vector needs keep_centres: the applied vector travels in the pipe's count array";
+      if (bad || mtgpu_pipe_set_gmc(pipe_, 1, gmc_max_shift_, gmc_min_share_q8_,
+                                    report_vector_ ? MT_PIPE_REPORT_VECTOR : MT_PIPE_REPORT_CENTRES) != MT_OK) {
+        err_ = bad ? bad : mtgpu_last_error();
+        (void)mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0);             // whatever fails here, no stale setting stays behind
         pipe_ = nullptr;
         return false;
       }
@@ -976,6 +1003,19 @@ struct PipelineResult {
   int min_blob_cells = -1;
   std::vector<int> blob_sweep_levels;
   std::vector<SweepEntry> blob_sweep;                  // SweepEntry::clusters_needed holds the level L
+  // Global-motion compensation (GpuMotionScanner::set_gmc / report_vector; include/mtgpu_pipe_gmc.h).  In:
+  // gmc_max_shift >= 0: on — `segments` are those of the residual scan, under `keep` where there is one; -1: take
+  // gmc_options(); -2: off whatever gmc_options() says.  gmc_min_share_q8 (with gmc_max_shift >= 0).  gmc_vectors: every
+  // worker's pipe reports the applied vector in place of the centre count (the pipe has ONE count array: not together
+  // with keep_centres / sweep_levels / blob_sweep_levels); `centres` then holds {pts, (uint16)gx | (uint16)gy << 16}.
+  // Out, with gmc_vectors: gmc_moved_frames = scanned frames whose applied vector is not (0, 0), gmc_top = the applied
+  // vectors by falling frame count (then by gx, gy), at most 8.  Not together with min_blob_cells > 0 / blob_sweep_levels.
+  int gmc_max_shift = -1;
+  int gmc_min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
+  bool gmc_vectors = false;
+  struct GmcVector { int gx, gy; uint64_t frames; };
+  uint64_t gmc_moved_frames = 0;
+  std::vector<GmcVector> gmc_top;
   std::string error;
 };
 
@@ -983,6 +1023,12 @@ struct PipelineResult {
 // --sweep-blobs): set before the first pipeline starts, read by every run_scan_pipeline.
 struct BlobOptions { int min_blob_cells = 0; std::vector<int> sweep_levels; };
 inline BlobOptions &blob_options() { static BlobOptions o; return o; }
+
+// Process-wide defaults for PipelineResult::gmc_max_shift / gmc_min_share_q8 / gmc_vectors (a front end's --gmc,
+// --gmc-max-shift, --gmc-min-share-q8, --gmc-vectors): set before the first pipeline starts, read by every
+// run_scan_pipeline.  max_shift < 0: off.
+struct GmcOptions { int max_shift = -1; int min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8; bool vectors = false; };
+inline GmcOptions &gmc_options() { static GmcOptions o; return o; }
 
 // Process-wide defaults for PipelineResult::keep_centres / sweep_levels (a front end's --centres / --sweep): set before
 // the first pipeline starts, read by every run_scan_pipeline.
@@ -1036,7 +1082,26 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
       out.error = "blob sweep level " + std::to_string(level) + " is below max(1, CLUSTERS_NEEDED)";
       return 1;
     }
-  const bool keep_centres = out.keep_centres || centre_options().keep || !out.sweep_levels.empty() || report_largest;
+  if (out.gmc_max_shift == -1) {
+    out.gmc_max_shift = gmc_options().max_shift < 0 ? -2 : gmc_options().max_shift;
+    out.gmc_min_share_q8 = gmc_options().min_share_q8;
+    out.gmc_vectors = out.gmc_vectors || gmc_options().vectors;
+  }
+  const bool gmc_on = out.gmc_max_shift >= 0;
+  if (out.gmc_vectors && !gmc_on) { out.error = "gmc_vectors without compensation (gmc_max_shift)"; return 1; }
+  if (gmc_on && (out.gmc_max_shift > MTGPU_GMC_MAX_SHIFT || out.gmc_min_share_q8 < 0 || out.gmc_min_share_q8 > 256)) {
+    out.error = "gmc_max_shift must be in [0, 127] and gmc_min_share_q8 in [0, 256]";
+    return 1;
+  }
+  if (gmc_on && (out.min_blob_cells > 0 || report_largest)) {
+    out.error = "compensation together with min_blob_cells / blob_sweep_levels: not together yet";
+    return 1;
+  }
+  if (out.gmc_vectors && (out.keep_centres || centre_options().keep || !out.sweep_levels.empty() || report_largest)) {
+    out.error = "gmc_vectors together with keep_centres / sweep_levels / blob_sweep_levels: the pipe has one count array";
+    return 1;
+  }
+  const bool keep_centres = out.keep_centres || centre_options().keep || !out.sweep_levels.empty() || report_largest || out.gmc_vectors;
   std::mutex centres_mu;
   const auto wall0 = std::chrono::high_resolution_clock::now();
   std::mutex err_mu;
@@ -1076,6 +1141,8 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
         scanners[i]->set_keep(out.keep);
         scanners[i]->set_min_blob_cells(out.min_blob_cells);
         scanners[i]->report_largest(report_largest);
+        scanners[i]->set_gmc(gmc_on ? out.gmc_max_shift : -1, out.gmc_min_share_q8);
+        scanners[i]->report_vector(out.gmc_vectors);
         if (!scanners[i]->initialize()) {                                // :198-199 (here: reported)
           fail_with(scanners[i]->error());
           return;
@@ -1141,6 +1208,18 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
   out.segments.resize(out.merge.n_segments);
   std::stable_sort(out.centres.begin(), out.centres.end(),
                    [](const std::pair<double, uint32_t> &a, const std::pair<double, uint32_t> &b) { return a.first < b.first; });
+  if (out.gmc_vectors) {                                                 // `centres` holds the packed applied vectors
+    std::map<uint32_t, uint64_t> seen;
+    out.gmc_moved_frames = 0;
+    for (const auto &c : out.centres)
+      if (c.second != 0u) { ++seen[c.second]; ++out.gmc_moved_frames; }
+    out.gmc_top.clear();
+    for (const auto &kv : seen) out.gmc_top.push_back({(int)(int16_t)(kv.first & 0xffffu), (int)(int16_t)(kv.first >> 16), kv.second});
+    std::sort(out.gmc_top.begin(), out.gmc_top.end(), [](const PipelineResult::GmcVector &a, const PipelineResult::GmcVector &b) {
+      return a.frames != b.frames ? a.frames > b.frames : (a.gx != b.gx ? a.gx < b.gx : a.gy < b.gy);
+    });
+    if (out.gmc_top.size() > 8) out.gmc_top.resize(8);
+  }
   // the same merge on each level's timestamps: `centres` holds the centre counts (sweep_levels) or the largest blobs
   // (blob_sweep_levels), never both
   for (int level : report_largest ? out.blob_sweep_levels : out.sweep_levels) {

@@ -2,6 +2,7 @@
 // vectors from .mtmv containers instead of decoding with FFmpeg:
 //   mtgpu_scan_file stream.mtmv [more.mtmv ...] [--threads T] [--streams S] [--outdir DIR] [--timestamps] [--summary]
 //                   [--centres] [--sweep K1,K2,...] [--keep MASK.mtkeep] [--min-blob-cells N] [--sweep-blobs L1,L2,...]
+//                   [--gmc] [--gmc-max-shift N] [--gmc-min-share-q8 Q] [--gmc-vectors]
 //   (--streams 0 / --threads 0: the reference's own sizing from PARALLEL_STREAMS / THREADS_PER_STREAM and the CPU limit)
 // One file: like `motion_trim in out` (single ProcessingPipeline).  Several files: like
 // `motion_trim in_dir out_dir` (BatchProcessor): S streams x T workers, jobs consumed by one
@@ -23,6 +24,15 @@
 // tool prints when run with --min-blob-cells L — from the one scan.  A level must be at least max(1, CLUSTERS_NEEDED).
 // --sweep-blobs together with --centres or --sweep is refused: a pipe has one count array.  Without the two options
 // the output is unchanged.
+// --gmc: global-motion compensation (include/mtgpu_pipe_gmc.h) — every frame is scanned against its own dominant
+// vector, estimated within +-16 pixels and applied where half of the counted records agree; --gmc-max-shift N (0 .. 127)
+// and --gmc-min-share-q8 Q (0 .. 256) change the two and each imply --gmc.  Under --keep the estimate counts only records
+// of kept cells and the ignored cells are not active: a burnt-in clock neither votes for the vector nor shows as
+// motion once the vector is subtracted.  --gmc-vectors (implies --gmc): the pipes report every frame's applied vector;
+// the job gains "gmc": {"frames", "compensated_frames", "compensated_share" (of the frames scanned), "vectors":
+// [[gx, gy, frames], ...] most frequent first}.  It combines with --keep, --centres and --sweep; --gmc-vectors does not
+// combine with --centres or --sweep (a pipe has one count array); none of it combines with --min-blob-cells N > 0 or
+// --sweep-blobs.  Without these options the output is unchanged.
 // --summary (several files): one more line {"batch_summary": ...} — frames scanned, wall time, worker-time
 // breakdown and what the S x T workers held (contexts, pipes, HIP streams, pinned / device bytes).
 #include <cmath>
@@ -81,6 +91,7 @@ static bool g_print_ts = false;   // --timestamps: also print the pooled motion 
 static bool g_print_centres = false;   // --centres
 static std::string g_keep_path;        // --keep
 static bool g_print_largest = false;   // --sweep-blobs
+static bool g_print_gmc = false;       // --gmc-vectors
 
 // The keep mask of g_keep_path for a width x height input; throws with load_keep's message (the line is named) when the
 // file is malformed or made for another grid.
@@ -149,6 +160,13 @@ static void print_job(const std::string &input, const PipelineResult &r, const s
     }
     std::printf("]");
   };
+  if (g_print_gmc) {
+    std::printf(", \"gmc\": {\"frames\": %zu, \"compensated_frames\": %llu, \"compensated_share\": %.17g, \"vectors\": [", r.centres.size(),
+                (unsigned long long)r.gmc_moved_frames, r.centres.empty() ? 0.0 : (double)r.gmc_moved_frames / (double)r.centres.size());
+    for (size_t i = 0; i < r.gmc_top.size(); ++i)
+      std::printf("%s[%d, %d, %llu]", i ? ", " : "", r.gmc_top[i].gx, r.gmc_top[i].gy, (unsigned long long)r.gmc_top[i].frames);
+    std::printf("]}");
+  }
   if (!r.sweep.empty()) print_sweep("sweep", "clusters_needed", r.sweep);
   if (!r.blob_sweep.empty()) print_sweep("sweep_blobs", "min_blob_cells", r.blob_sweep);
   std::printf("}\n");
@@ -207,7 +225,42 @@ int main(int argc, char **argv) {
       }
       g_print_largest = true;
     }
+    else if (!std::strcmp(argv[i], "--gmc")) {
+      if (gmc_options().max_shift < 0) gmc_options().max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT;
+    }
+    else if (!std::strcmp(argv[i], "--gmc-vectors")) {
+      if (gmc_options().max_shift < 0) gmc_options().max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT;
+      gmc_options().vectors = true;
+      g_print_gmc = true;
+    }
+    else if (!std::strcmp(argv[i], "--gmc-max-shift") || !std::strcmp(argv[i], "--gmc-min-share-q8")) {
+      const bool shift = !std::strcmp(argv[i], "--gmc-max-shift");
+      const long hi = shift ? MTGPU_GMC_MAX_SHIFT : 256;
+      char *end = nullptr;
+      const long v = i + 1 < argc ? std::strtol(argv[i + 1], &end, 10) : -1;
+      if (i + 1 >= argc || end == argv[i + 1] || *end || v < 0 || v > hi) {
+        std::fprintf(stderr, "error: %s takes an integer in [0, %ld]\n", argv[i], hi);
+        return 2;
+      }
+      ++i;
+      if (shift) gmc_options().max_shift = (int)v;
+      else {
+        gmc_options().min_share_q8 = (int)v;
+        if (gmc_options().max_shift < 0) gmc_options().max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT;
+      }
+    }
     else files.push_back(argv[i]);
+  }
+  // what compensation cannot be combined with: answered here, before any device call
+  if (gmc_options().max_shift >= 0) {
+    if (blob_options().min_blob_cells > 0 || g_print_largest) {
+      std::fprintf(stderr, "error: --gmc cannot be combined with --min-blob-cells or --sweep-blobs: compensation and blobs are not together yet\n");
+      return 2;
+    }
+    if (g_print_gmc && (g_print_centres || !centre_options().sweep_levels.empty())) {
+      std::fprintf(stderr, "error: --gmc-vectors cannot be combined with --centres or --sweep: a pipe has one count array\n");
+      return 2;
+    }
   }
   // what the blob options cannot be combined with: answered here, before any device call
   if (g_print_largest) {

@@ -112,6 +112,12 @@ struct mtgpu_pipe {
   // (MT_PIPE_REPORT_*).  Both change only while no batch is being filled or in flight.
   int32_t min_blob = 0;
   int report = 0;
+  // mtgpu_pipe_set_gmc (include/mtgpu_pipe_gmc.h): gmc != 0: every submit runs the compensated scan (ctx_launch_gmc),
+  // estimate and vote under the keep plane when `masked`; gmc_report: MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_VECTOR.
+  // Never together with min_blob > 0.  They change only while no batch is being filled or in flight.
+  int gmc = 0;
+  int32_t gmc_max_shift = 0, gmc_min_share_q8 = 0;
+  int gmc_report = 0;
   std::vector<mtgpu_batch *> bufs;
   std::deque<mtgpu_batch *> inflight;
   std::mutex mu;
@@ -397,7 +403,11 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
       rc = fail(MT_ERR_DEVICE, "injected submit failure (MTGPU_INJECT_SUBMIT_FAIL)");
       goto bad;
     }
-    if (p->min_blob > 0)   // mtgpu_pipe_set_blobs: the blob scan, under the pipe's keep plane when it has a mask
+    if (p->gmc)   // mtgpu_pipe_set_gmc: the compensated scan, estimate and vote under the pipe's keep plane when it has a mask
+      rc = mtgpu::ctx_launch_gmc(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
+                                 p->gmc_max_shift, p->gmc_min_share_q8, p->gmc_report == MT_PIPE_REPORT_VECTOR ? 1 : 0, b->d_flags,
+                                 b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
+    else if (p->min_blob > 0)   // mtgpu_pipe_set_blobs: the blob scan, under the pipe's keep plane when it has a mask
       rc = mtgpu::ctx_launch_blobs(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
                                    p->min_blob, p->report == MT_PIPE_REPORT_LARGEST ? 1 : 0, b->d_flags, b->d_centres, st,
                                    b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
@@ -553,6 +563,9 @@ int mtgpu_pipe_set_blobs(mtgpu_pipe *p, int32_t min_blob_cells, int report) {
       return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the blob setting",
                   b->state == 1 ? "being filled" : "in flight");
   if (min_blob_cells == 0) { p->min_blob = 0; p->report = 0; return MT_OK; }
+  if (p->gmc)
+    return fail(MT_ERR_UNSUPPORTED, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): blobs and compensation are "
+                "not together yet");
   const int rc = mtgpu::ctx_blobs_supported(p->ctx);         // MT_ERR_UNSUPPORTED, the grid named: nothing changes
   if (rc != MT_OK) return rc;
   p->min_blob = min_blob_cells;
@@ -566,6 +579,45 @@ int mtgpu_pipe_blobs(const mtgpu_pipe *p, int32_t *min_blob_cells, int *report) 
   if (p->min_blob <= 0) return 0;
   if (min_blob_cells) *min_blob_cells = p->min_blob;
   if (report) *report = p->report;
+  return 1;
+}
+
+int mtgpu_pipe_set_gmc(mtgpu_pipe *p, int enable, int32_t max_shift, int32_t min_share_q8, int report) {
+  if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
+  if (enable) {
+    if (max_shift < 0 || max_shift > MTGPU_GMC_MAX_SHIFT)
+      return fail(MT_ERR_INVALID, "max_shift must be in [0, %d], not %d", MTGPU_GMC_MAX_SHIFT, (int)max_shift);
+    if (min_share_q8 < 0 || min_share_q8 > 256) return fail(MT_ERR_INVALID, "min_share_q8 must be in [0, 256], not %d", (int)min_share_q8);
+    if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_VECTOR)
+      return fail(MT_ERR_INVALID, "report is %d: want MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_VECTOR", report);
+    if (report == MT_PIPE_REPORT_VECTOR && !p->centres)
+      return fail(MT_ERR_INVALID, "MT_PIPE_REPORT_VECTOR needs a pipe with MT_LAYOUT_CENTRES: the applied vector travels in its count array");
+  }
+  std::lock_guard<std::mutex> lock(p->mu);
+  for (const mtgpu_batch *b : p->bufs)
+    if (b->state == 1 || b->state == 2)
+      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the compensation setting",
+                  b->state == 1 ? "being filled" : "in flight");
+  if (!enable) { p->gmc = 0; p->gmc_max_shift = 0; p->gmc_min_share_q8 = 0; p->gmc_report = 0; return MT_OK; }
+  if (p->min_blob > 0)
+    return fail(MT_ERR_UNSUPPORTED, "this pipe runs the blob scan (mtgpu_pipe_set_blobs): blobs and compensation are not "
+                "together yet");
+  const int rc = mtgpu::ctx_gmc_supported(p->ctx);           // MT_ERR_UNSUPPORTED, the grid named: nothing changes
+  if (rc != MT_OK) return rc;
+  p->gmc = 1;
+  p->gmc_max_shift = max_shift;
+  p->gmc_min_share_q8 = min_share_q8;
+  p->gmc_report = report;
+  return MT_OK;
+}
+
+int mtgpu_pipe_gmc(const mtgpu_pipe *p, int32_t *max_shift, int32_t *min_share_q8, int *report) {
+  if (!p) return -1;
+  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
+  if (!p->gmc) return 0;
+  if (max_shift) *max_shift = p->gmc_max_shift;
+  if (min_share_q8) *min_share_q8 = p->gmc_min_share_q8;
+  if (report) *report = p->gmc_report;
   return 1;
 }
 

@@ -1040,6 +1040,37 @@ class ScanPipe:
             return None
         return int(n.value), ("largest" if r.value == _abi.MT_PIPE_REPORT_LARGEST else "centres")
 
+    def set_gmc(self, max_shift: int = _abi.GMC_DEFAULT_MAX_SHIFT, min_share_q8: int = _abi.GMC_DEFAULT_MIN_SHARE_Q8,
+                report: str = "centres"):
+        """Global-motion compensation on the decode path (mtgpu_pipe_set_gmc): from now on every batch of this pipe is
+        scanned against each frame's dominant vector (src/motion_scanner.cpp:246-292 on the residuals); under the keep
+        mask, if the pipe has one, the estimate counts only records of kept cells and the active plane is the masked
+        one.  report: what drain_centres() returns per frame, "centres" or "vector" — the applied vector packed as
+        (uint16)gx | (uint16)gy << 16 (unpack_gmc_vector); "vector" needs centres=True.  Only while no batch is being
+        filled or in flight (call drain() first): otherwise MtgpuError(MT_ERR_BUSY) and nothing changes.  Not together
+        with set_blobs: MtgpuError(MT_ERR_UNSUPPORTED)."""
+        codes = {"centres": _abi.MT_PIPE_REPORT_CENTRES, "vector": _abi.MT_PIPE_REPORT_VECTOR}
+        if report not in codes:
+            raise ValueError(f"report is {report!r}, not 'centres' or 'vector'")
+        check(self._lib.mtgpu_pipe_set_gmc(self._pipe, 1, int(max_shift), int(min_share_q8), codes[report]))
+
+    def clear_gmc(self):
+        """Compensation off (mtgpu_pipe_set_gmc with enable 0): the pipe is the plain or masked pipe it was before."""
+        check(self._lib.mtgpu_pipe_set_gmc(self._pipe, 0, 0, 0, 0))
+
+    def gmc(self) -> Optional[Tuple[int, int, str]]:
+        """None, or (max_shift, min_share_q8, report) while the pipe's submits run the compensated scan (mtgpu_pipe_gmc)."""
+        ms, q8, r = C.c_int32(), C.c_int32(), C.c_int()
+        if self._lib.mtgpu_pipe_gmc(self._pipe, C.byref(ms), C.byref(q8), C.byref(r)) != 1:
+            return None
+        return int(ms.value), int(q8.value), ("vector" if r.value == _abi.MT_PIPE_REPORT_VECTOR else "centres")
+
+    @staticmethod
+    def unpack_gmc_vector(word: int) -> Tuple[int, int]:
+        """(gx, gy) of a count reported under set_gmc(report="vector"): two signed 16-bit halves."""
+        gx, gy = int(word) & 0xFFFF, (int(word) >> 16) & 0xFFFF
+        return (gx - 0x10000 if gx >= 0x8000 else gx), (gy - 0x10000 if gy >= 0x8000 else gy)
+
     def _collect_one(self):
         b, fl, pts, tags, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32()
         rc = self._lib.mtgpu_pipe_collect(self._pipe, C.byref(b), C.byref(fl), C.byref(pts), C.byref(tags),
