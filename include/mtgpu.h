@@ -476,4 +476,9 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * site of :375-383) — two more entry points, declared the same way. */
 #include "mtgpu_pipe_gmc.h"
 
+/* The compensated blob scan: motion blobs on the residuals of each frame's dominant vector, with or without per-stream
+ * keep masks in the estimate and in the vote (src/motion_scanner.cpp:246-294 on the residuals, then the components of
+ * the centres) — three more entry points, declared the same way. */
+#include "mtgpu_gmc_blobs.h"
+
 #endif /* MTGPU_H */

@@ -51,7 +51,8 @@
  *
  * Out of scope: there is no pipe form (mtgpu_pipe_*), no mtgpu_scan_file option and no decode-path scanner for blobs;
  * a blob scan is a call on a batch.  (That holds for the entry points of THIS header.  The decode path has its own:
- * mtgpu_pipe_blobs.h puts the flag rule and one of the two counts into a pipe.)
+ * mtgpu_pipe_blobs.h puts the flag rule and one of the two counts into a pipe.)  No compensation either: blobs on the
+ * residuals of each frame's dominant vector are the resident scan of mtgpu_gmc_blobs.h; the pipe still refuses the pair.
  */
 #ifndef MTGPU_BLOBS_H
 #define MTGPU_BLOBS_H

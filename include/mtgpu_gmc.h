@@ -49,8 +49,9 @@
  *     wherever that stays inside int16.
  *  D. vn == 0: the result equals the plain centre scan (every cell of the grid is active whatever the votes are).
  *
- * Out of scope: keep masks; blobs; the pipe form and mtgpu_scan_file — of THESE entry points: the decode path has its own
- * two, which honour the pipe's keep mask in the estimate and in the vote (mtgpu_pipe_gmc.h), still without blobs; the
+ * Out of scope: keep masks; blobs; the pipe form and mtgpu_scan_file — of THESE entry points: the resident scan with
+ * blobs and per-stream keep masks is mtgpu_gmc_blobs.h, and the decode path has its own two entry points, which honour
+ * the pipe's keep mask in the estimate and in the vote (mtgpu_pipe_gmc.h) and still refuse blobs next to them; the
  * row-banded grids (960x540, 32767-wide), which are MT_ERR_UNSUPPORTED with the grid named, as for the zones and the
  * blobs; rotation or zoom models — this is a translation only; any use of neighbouring frames — frames stay independent.
  *

@@ -93,6 +93,11 @@ class GmcPlanC(C.Structure):
     _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("hist_bins", C.c_int32), ("info_bytes", C.c_int32)]
 
 
+class GmcBlobsPlanC(C.Structure):
+    _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("keep_words_per_row", C.c_int32),
+                ("keep_words_per_stream", C.c_int32), ("hist_bins", C.c_int32), ("info_bytes", C.c_int32)]
+
+
 class CtxStatsC(C.Structure):
     _fields_ = [("staging_device_bytes", C.c_uint64), ("pool_reserved_bytes", C.c_uint64),
                 ("pool_reserved_high", C.c_uint64), ("hip_streams", C.c_uint32), ("private_pool", C.c_uint32)]
@@ -245,6 +250,17 @@ ABI_PIPE_GMC = {
 }
 MT_PIPE_REPORT_VECTOR = 2
 
+# name -> (restype, argtypes): every symbol include/mtgpu_gmc_blobs.h declares (the compensated blob scan; mtgpu.h includes it).
+ABI_GMC_BLOBS = {
+    "mtgpu_gmc_blobs_preview": (C.c_int, [C.POINTER(ScanParamsC), C.c_int, C.POINTER(GmcBlobsPlanC)]),
+    "mtgpu_scan_gmc_blobs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                              C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtgpu_scan_frames_gmc_blobs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                              C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -276,7 +292,7 @@ def load_library(path=None):
     lib = C.CDLL(p)
     for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
             list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
-            list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()):
+            list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()) + list(ABI_GMC_BLOBS.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,95 @@
+// gmc_blobs_kernels.h — launch interface between the C ABI (mtgpu_api.hip) and the gfx950 compensated blob scan
+// (gmc_blobs_kernels.hip): every frame's dominant vector is estimated from its own records — under a per-stream keep
+// mask, from the records in kept cells — and subtracted; the threshold, the vote and the centres of
+// src/motion_scanner.cpp:246-292 run on the residuals, and the centres are labelled into 4-connected components
+// (include/mtgpu_gmc_blobs.h).  Internal; not part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "blobs_kernels.h"
+#include "gmc_kernels.h"
+#include "scan_kernels.h"
+
+namespace mtgpu {
+
+constexpr int kGmcBlobBlock = 1024;    // lanes per workgroup (a multiple of 64: a wave owns one 64-cell word of a row)
+constexpr int kGmcBlobUnroll = 4;      // independent record loads in flight per lane
+
+// LDS of one workgroup, in this order (R = analysed rows, at least 1; W = 64-bit words per mask row):
+//   tile     (R + 2) x gw u32, padded to 4 words   vote counters of the residual vote; the labels once the masks exist
+//   keep     R x W u64                             the stream's keep words of the analysed rows (no mask: ones), read by
+//                                                  the masked estimate and by the masks; the centre plane later
+//   amask    (R + 2) x W u64                       the frame's active cells (AND keep); mask row j <-> grid row y_lo - 1 + j
+//   hist     2 x kGmcHistBins u32                  hx, hy: bin v + max_shift holds the counted records displaced by v
+//   res      8 u32                                 [1] n_in, [2] gx, [3] gy, [4] mode_x, [5] mode_y, [6] n_x, [7] n_y
+//   total    8 u32                                 [0] centres, [1] blobs, [2..3] the winner's key (u64), [4..7] its box
+// The first three regions are the blob scan's, so the u64 key of `total` is 8-byte aligned as there.
+inline size_t gmc_blobs_lds_bytes(int gw, int R) {
+  return blob_lds_bytes(gw, R) + 2u * (size_t)kGmcHistBins * 4u + 32u;
+}
+
+// Kernel-side parameter block.
+struct GmcBlobK {
+  unsigned long long thr;        // keep a record iff |residual|^2 >= thr (ScanK::thr, :251)
+  unsigned int vec_need;         // a cell is active iff votes >= vec_need (:282) and, under a mask on an analysed row, its keep bit is set
+  unsigned int clust_need;       // max(1, clusters_needed) (:288)
+  unsigned int blob_need;        // max(1, min_blob_cells): flags[f] = centres[f] >= clust_need && largest[f] >= blob_need
+  int shift, gw, gh, y_lo, y_hi; // as ScanK (y_hi >= y_lo)
+  int W;                         // 64-bit words per mask row
+  int R;                         // max(1, y_hi - y_lo): rows the LDS layout is sized for
+  int tile_words;                // blob_tile_words
+  int max_shift;                 // [0, kGmcMaxShift]: displacements beyond it are in no bin
+  unsigned int min_share_q8;     // [0, 256]: a mode is applied iff n * 256 >= min_share_q8 * n_in
+};
+
+// The six outputs of a launch, each device memory or null.
+struct GmcBlobOut {
+  unsigned char *flags;                   // n_frames bytes
+  unsigned int *centres, *blobs, *largest;  // n_frames words each
+  BlobBox *box;                           // n_frames boxes
+  unsigned int *info;                     // n_frames x kGmcInfoWords words (mt_gmc_info)
+};
+
+// The ONE argument of gmc_blobs_frames_kernel: it starts the kernel-argument segment, where the kernel reads `out` a
+// second time, late (gmc_blobs_kernels.hip).
+struct GmcBlobArgs {
+  const unsigned char *mv;
+  const WorkItem *work;
+  unsigned int item0, n_items;            // this launch serves entries [item0, n_items) of the list, one per workgroup
+  GmcBlobK k;
+  const unsigned long long *stream_off;
+  unsigned int n_streams;
+  const unsigned long long *keep;
+  GmcBlobOut out;
+};
+
+struct GmcBlobLaunch {
+  const unsigned char *mv;
+  unsigned long long n_records;           // frame_off entries are clamped to this (before `rebase`)
+  unsigned long long rebase;
+  const unsigned long long *frame_off;    // n_frames + 1
+  const unsigned char *has_sd;            // n_frames or null
+  unsigned int n_frames;
+  int rec_bytes;                          // 40 or 8
+  const unsigned long long *stream_off;   // n_streams + 1; null iff keep is null
+  unsigned int n_streams;                 // 0 iff keep is null
+  const unsigned long long *keep;         // n_streams x gh x W, device memory; null: no mask, no stream lookup
+  unsigned char *flags;                   // n_frames bytes, device memory, or null
+  unsigned int *centres, *blobs, *largest;  // n_frames words each, or null
+  BlobBox *box;                           // n_frames boxes, or null
+  unsigned int *info;                     // n_frames x kGmcInfoWords words (mt_gmc_info), or null
+  GmcBlobK k;
+  int lds_bytes;
+  int lds_max;                            // device limit of dynamic LDS per workgroup
+  int device;
+  void *plan_ws;                          // plan_scratch_bytes(n_frames), 32-byte aligned
+  hipStream_t stream;
+  hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the scan kernel; else nullptr
+};
+
+// Fills the non-null outputs with the answer of a frame without a blob (0; an all-0xFFFF box; a zero info), builds the
+// work list (launch_plan), then one workgroup per entry.
+hipError_t launch_gmc_blob_scan(const GmcBlobLaunch &L);
+
+}  // namespace mtgpu

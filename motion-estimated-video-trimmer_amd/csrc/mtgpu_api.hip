@@ -27,6 +27,7 @@
 #include "zones_kernels.h"
 #include "blobs_kernels.h"
 #include "gmc_kernels.h"
+#include "gmc_blobs_kernels.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -2450,6 +2451,240 @@ int mtgpu_scan_frames_gmc(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_o
   if (rc != MT_OK) return rc;
   if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_fl, n_frames, hipMemcpyDeviceToHost, st));
   if (centres) HIP_TRY(hipMemcpyAsync(centres, d + o_cen, words, hipMemcpyDeviceToHost, st));
+  if (info) HIP_TRY(hipMemcpyAsync(info, d + o_info, info_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the compensated blob scan (src/motion_scanner.cpp:246-294
+// per frame on the residuals of the frame's dominant vector, then the components of the centres; include/mtgpu_gmc_blobs.h)
+
+namespace {
+
+// One form: the blob scan's layout and the two histograms.  It fits or the grid is unsupported.
+int gmc_blobs_plan(const mt_scan_params &p, int lds_max, mtgpu_gmc_blobs_plan *out) {
+  const int y_lo = p.vertical_margin;
+  int y_hi = p.grid_h - p.vertical_margin;
+  if (y_hi < y_lo) y_hi = y_lo;
+  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const long long need = (long long)mtgpu::gmc_blobs_lds_bytes(p.grid_w, R);
+  if (need > (long long)lds_max)
+    return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows, the keep rows, one mask plane and the "
+                "histograms (%lld bytes) do not fit %d bytes of LDS; the compensated blob scan has no banded form", p.grid_w,
+                p.grid_h, R + 2, need, lds_max);
+  const long long W = ((long long)p.grid_w + 63) / 64;
+  out->lds_bytes = (int32_t)need;
+  out->workgroup = mtgpu::kGmcBlobBlock;
+  out->keep_words_per_row = (int32_t)W;
+  out->keep_words_per_stream = (int32_t)(W * (long long)p.grid_h);
+  out->hist_bins = mtgpu::kGmcHistBins;
+  out->info_bytes = (int32_t)sizeof(mt_gmc_info);
+  return MT_OK;
+}
+
+// The compensated blob scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
+int gmc_blobs_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
+                 const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, const uint64_t *d_keep,
+                 int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells, uint8_t *d_flags, uint32_t *d_centres,
+                 uint32_t *d_blobs, uint32_t *d_largest, mt_blob_box *d_box, mt_gmc_info *d_info, hipStream_t st) {
+  mtgpu_gmc_blobs_plan gp;
+  int rc = gmc_blobs_plan(c->params, c->lds_max, &gp);
+  if (rc != MT_OK) return rc;
+  mtgpu::GmcBlobLaunch L;
+  L.mv = static_cast<const unsigned char *>(d_rec);
+  L.n_records = n_records;
+  L.rebase = rebase;
+  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
+  L.has_sd = d_sd;
+  L.n_frames = n_frames;
+  L.rec_bytes = rec_bytes;
+  L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
+  L.n_streams = n_streams;
+  L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
+  L.flags = d_flags; L.centres = d_centres; L.blobs = d_blobs; L.largest = d_largest;
+  L.box = reinterpret_cast<mtgpu::BlobBox *>(d_box);
+  L.info = reinterpret_cast<unsigned int *>(d_info);
+  mtgpu::GmcBlobK &k = L.k;
+  std::memset(&k, 0, sizeof k);
+  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.clust_need = c->k.clust_need;
+  k.blob_need = min_blob_cells < 1 ? 1u : (unsigned int)min_blob_cells;
+  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
+  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
+  k.tile_words = (int)mtgpu::blob_tile_words(k.gw, k.R);
+  k.max_shift = (int)max_shift;
+  k.min_share_q8 = (unsigned int)min_share_q8;
+  L.lds_bytes = gp.lds_bytes;
+  L.lds_max = c->lds_max;
+  L.device = c->device;
+  L.stream = st;
+  L.ev_planned = nullptr;
+  void *scratch = nullptr;
+  int slot = -1;
+  rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
+  if (rc != MT_OK) return rc;
+  L.plan_ws = scratch;
+  hipError_t e = hipSuccess;
+  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
+    mtgpu_ctx::Profile &pf = c->prof;
+    std::lock_guard<std::mutex> lock(pf.mu);
+    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
+    if (e == hipSuccess && pf.created) {
+      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
+      e = hipEventRecord(t[0], st);
+      L.ev_planned = t[1];
+      if (e == hipSuccess) e = mtgpu::launch_gmc_blob_scan(L);
+      if (e == hipSuccess) e = hipEventRecord(t[2], st);
+      if (e == hipSuccess) ++pf.count;
+    } else if (e == hipSuccess) {
+      e = mtgpu::launch_gmc_blob_scan(L);
+    }
+  } else {
+    e = mtgpu::launch_gmc_blob_scan(L);
+  }
+  if (slot >= 0) scratch_release(c, slot, st);
+  if (e != hipSuccess) return hip_fail(e, "compensated blob scan launch");
+  return MT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtgpu_gmc_blobs_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_gmc_blobs_plan *out) {
+  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
+  int rc = validate_params(p);
+  if (rc != MT_OK) return rc;
+  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
+  mtgpu_gmc_blobs_plan gp;
+  if ((rc = gmc_blobs_plan(*p, lds_bytes_per_workgroup, &gp)) != MT_OK) return rc;
+  *out = gp;
+  return MT_OK;
+}
+
+int mtgpu_scan_gmc_blobs_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
+                                const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
+                                const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells,
+                                uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_blobs, uint32_t *d_largest, mt_blob_box *d_box,
+                                mt_gmc_info *d_info, void *stream) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
+    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
+  int rc = gmc_check_settings(max_shift, min_share_q8);
+  if (rc != MT_OK) return rc;
+  if (!d_flags && !d_centres && !d_blobs && !d_largest && !d_box && !d_info)
+    return fail(MT_ERR_INVALID, "d_flags, d_centres, d_blobs, d_largest, d_box and d_info are all NULL");
+  if (n_frames > 0 && !d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
+  if (d_keep && !d_stream_off) return fail(MT_ERR_INVALID, "d_stream_off is NULL with d_keep given");
+  if (d_keep && n_streams == 0) return fail(MT_ERR_INVALID, "n_streams is 0 with d_keep given");
+  if (!d_keep && d_stream_off) return fail(MT_ERR_INVALID, "d_keep is NULL with d_stream_off given");
+  if (!d_keep && n_streams != 0) return fail(MT_ERR_INVALID, "d_keep is NULL with n_streams %u", n_streams);
+  if (((uintptr_t)d_frame_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_frame_off must be 8-byte aligned");
+  if (((uintptr_t)d_stream_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_stream_off must be 8-byte aligned");
+  if (((uintptr_t)d_keep & 7u) != 0) return fail(MT_ERR_INVALID, "d_keep must be 8-byte aligned");
+  if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
+  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)d_rec & 7u) != 0)
+    return fail(MT_ERR_INVALID, "d_rec: compact records must be 8-byte aligned");
+  if (((uintptr_t)d_rec & 3u) != 0) return fail(MT_ERR_INVALID, "d_rec must be 4-byte aligned");
+  if (((uintptr_t)d_centres & 3u) != 0) return fail(MT_ERR_INVALID, "d_centres must be 4-byte aligned");
+  if (((uintptr_t)d_blobs & 3u) != 0) return fail(MT_ERR_INVALID, "d_blobs must be 4-byte aligned");
+  if (((uintptr_t)d_largest & 3u) != 0) return fail(MT_ERR_INVALID, "d_largest must be 4-byte aligned");
+  if (((uintptr_t)d_box & 1u) != 0) return fail(MT_ERR_INVALID, "d_box must be 2-byte aligned");
+  if (((uintptr_t)d_info & 3u) != 0) return fail(MT_ERR_INVALID, "d_info must be 4-byte aligned");
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  {
+    mtgpu_gmc_blobs_plan gp;                                 // a grid without a form: before any HIP call
+    if ((rc = gmc_blobs_plan(c->params, c->lds_max, &gp)) != MT_OK) return rc;
+  }
+  if (n_frames == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  if (d_keep && !on_ctx_device(c, d_keep)) return fail(MT_ERR_INVALID, "d_keep is not memory of device %d", c->device);
+  if (d_flags && !on_ctx_device(c, d_flags)) return fail(MT_ERR_INVALID, "d_flags is not memory of device %d", c->device);
+  if (d_centres && !on_ctx_device(c, d_centres)) return fail(MT_ERR_INVALID, "d_centres is not memory of device %d", c->device);
+  if (d_blobs && !on_ctx_device(c, d_blobs)) return fail(MT_ERR_INVALID, "d_blobs is not memory of device %d", c->device);
+  if (d_largest && !on_ctx_device(c, d_largest)) return fail(MT_ERR_INVALID, "d_largest is not memory of device %d", c->device);
+  if (d_box && !on_ctx_device(c, d_box)) return fail(MT_ERR_INVALID, "d_box is not memory of device %d", c->device);
+  if (d_info && !on_ctx_device(c, d_info)) return fail(MT_ERR_INVALID, "d_info is not memory of device %d", c->device);
+  if (c->check_offsets) {
+    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
+    if (rc2 != MT_OK) return rc2;
+  }
+  return gmc_blobs_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_keep,
+                      max_shift, min_share_q8, min_blob_cells, d_flags, d_centres, d_blobs, d_largest, d_box, d_info,
+                      static_cast<hipStream_t>(stream));
+}
+
+int mtgpu_scan_frames_gmc_blobs(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
+                                const uint64_t *stream_off, uint32_t n_streams, const uint64_t *keep, int32_t max_shift,
+                                int32_t min_share_q8, int32_t min_blob_cells, uint8_t *flags, uint32_t *centres, uint32_t *blobs,
+                                uint32_t *largest, mt_blob_box *box, mt_gmc_info *info) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  int rc = gmc_check_settings(max_shift, min_share_q8);
+  if (rc != MT_OK) return rc;
+  if (!flags && !centres && !blobs && !largest && !box && !info)
+    return fail(MT_ERR_INVALID, "flags, centres, blobs, largest, box and info are all NULL");
+  if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
+  if (keep && !stream_off) return fail(MT_ERR_INVALID, "stream_off is NULL with keep given");
+  if (keep && n_streams == 0) return fail(MT_ERR_INVALID, "n_streams is 0 with keep given");
+  if (!keep && stream_off) return fail(MT_ERR_INVALID, "keep is NULL with stream_off given");
+  if (!keep && n_streams != 0) return fail(MT_ERR_INVALID, "keep is NULL with n_streams %u", n_streams);
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
+  if (keep) {
+    for (uint32_t s = 0; s < n_streams; ++s)
+      if (stream_off[s + 1] < stream_off[s]) return fail(MT_ERR_INVALID, "stream_off not monotonic at stream %u", s);
+    if (stream_off[n_streams] != (uint64_t)n_frames)
+      return fail(MT_ERR_INVALID, "stream_off[%u] is %llu, not n_frames %u", n_streams, (unsigned long long)stream_off[n_streams], n_frames);
+  }
+  const uint64_t r_begin = n_frames ? frame_off[0] : 0, r_end = n_frames ? frame_off[n_frames] : 0;
+  const uint64_t n_records = r_end - r_begin;
+  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  {
+    mtgpu_gmc_blobs_plan gp;                                 // a grid without a form: before anything is staged
+    if ((rc = gmc_blobs_plan(c->params, c->lds_max, &gp)) != MT_OK) return rc;
+  }
+  if (n_frames == 0) return MT_OK;
+
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t keep_bytes = keep ? sizeof(uint64_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.W : 0;
+  const size_t soff_bytes = keep ? sizeof(uint64_t) * ((size_t)n_streams + 1) : 0;
+  const size_t words = sizeof(uint32_t) * (size_t)n_frames, info_bytes = sizeof(mt_gmc_info) * (size_t)n_frames;
+  const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
+  const size_t o_soff = 0, o_keep = o_soff + up(soff_bytes), o_fl = o_keep + up(keep_bytes), o_cen = o_fl + (flags ? up(n_frames) : 0),
+               o_bl = o_cen + (centres ? up(words) : 0), o_lg = o_bl + (blobs ? up(words) : 0), o_box = o_lg + (largest ? up(words) : 0),
+               o_info = o_box + (box ? up(sizeof(mt_blob_box) * (size_t)n_frames) : 0), total = o_info + (info ? up(info_bytes) : 0);
+  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
+  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
+  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
+  if (has_sd && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
+  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
+  hipStream_t st = c->stream;
+  DrainOnExit drain{st};
+  if (n_records)
+    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
+  if (has_sd) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
+  if (keep) {
+    HIP_TRY(hipMemcpyAsync(d + o_soff, stream_off, soff_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_keep, keep, keep_bytes, hipMemcpyHostToDevice, st));
+  }
+  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
+  rc = gmc_blobs_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
+                    has_sd ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames,
+                    keep ? reinterpret_cast<const uint64_t *>(d + o_soff) : nullptr, keep ? n_streams : 0u,
+                    keep ? reinterpret_cast<const uint64_t *>(d + o_keep) : nullptr, max_shift, min_share_q8, min_blob_cells,
+                    flags ? d + o_fl : nullptr, centres ? reinterpret_cast<uint32_t *>(d + o_cen) : nullptr,
+                    blobs ? reinterpret_cast<uint32_t *>(d + o_bl) : nullptr, largest ? reinterpret_cast<uint32_t *>(d + o_lg) : nullptr,
+                    box ? reinterpret_cast<mt_blob_box *>(d + o_box) : nullptr, info ? reinterpret_cast<mt_gmc_info *>(d + o_info) : nullptr, st);
+  if (rc != MT_OK) return rc;
+  if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_fl, n_frames, hipMemcpyDeviceToHost, st));
+  if (centres) HIP_TRY(hipMemcpyAsync(centres, d + o_cen, words, hipMemcpyDeviceToHost, st));
+  if (blobs) HIP_TRY(hipMemcpyAsync(blobs, d + o_bl, words, hipMemcpyDeviceToHost, st));
+  if (largest) HIP_TRY(hipMemcpyAsync(largest, d + o_lg, words, hipMemcpyDeviceToHost, st));
+  if (box) HIP_TRY(hipMemcpyAsync(box, d + o_box, sizeof(mt_blob_box) * (size_t)n_frames, hipMemcpyDeviceToHost, st));
   if (info) HIP_TRY(hipMemcpyAsync(info, d + o_info, info_bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return MT_OK;

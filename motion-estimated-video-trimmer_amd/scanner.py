@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _abi, config
 from ._abi import (BLOB_BOX_DTYPE, BlobsPlanC, COMPACT_DTYPE, LAYOUT_AOS40, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
-                   GMC_DEFAULT_MAX_SHIFT, GMC_DEFAULT_MIN_SHARE_Q8, GMC_INFO_DTYPE, GmcPlanC,
+                   GMC_DEFAULT_MAX_SHIFT, GMC_DEFAULT_MIN_SHARE_Q8, GMC_INFO_DTYPE, GmcBlobsPlanC, GmcPlanC,
                    MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PlanC, ScanParamsC, SweepPlanC, ZonesPlanC, check,
                    load_library)
 
@@ -235,8 +235,20 @@ def gmc_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     return {n: getattr(p, n) for n, _ in GmcPlanC._fields_}
 
 
+def gmc_blobs_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
+    """How the compensated blob scan runs on the grid of `params` with that much LDS per workgroup
+    (mtgpu_gmc_blobs_preview): LDS bytes, lanes, the sizes of a keep mask (uint64 words per grid row and per stream),
+    histogram bins per axis, bytes of one GMC_INFO_DTYPE element.  Host arithmetic only: works without a GPU.
+    MtgpuError(MT_ERR_UNSUPPORTED) for a grid the scan has no form for."""
+    p = GmcBlobsPlanC()
+    c = params.to_c()
+    check(load_library().mtgpu_gmc_blobs_preview(C.byref(c), int(lds_bytes), C.byref(p)))
+    return {n: getattr(p, n) for n, _ in GmcBlobsPlanC._fields_}
+
+
 ACTIVITY_OUTPUTS = ("active", "centre", "frames")
 BLOB_OUTPUTS = ("flags", "centres", "blobs", "largest", "box")
+GMC_BLOB_OUTPUTS = BLOB_OUTPUTS + ("info",)
 
 
 def _activity_want(want):
@@ -772,6 +784,82 @@ class MotionScanner:
             self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
             None if d_sd is None else d_sd.data_ptr(), n_frames, ptr(d_stream_off), ns, ptr(d_keep), int(min_blob_cells),
             *(ptr(res[k]) for k in BLOB_OUTPUTS), st))
+        return res
+
+    # -------------------------------------------------------- motion blobs on compensated residuals
+    def scan_gmc_blobs(self, batch: FrameBatch, max_shift: int = GMC_DEFAULT_MAX_SHIFT, min_share_q8: int = GMC_DEFAULT_MIN_SHARE_Q8,
+                       min_blob_cells: int = 1, stream_off=None, keep=None) -> dict:
+        """The compensated blob scan of a host batch (mtgpu_scan_frames_gmc_blobs): each frame's dominant vector is
+        estimated as scan_gmc does — under keep masks, from the records in kept cells only — and subtracted; the residual
+        vote's centre cells are labelled as scan_blobs does.  Returns a dict of numpy arrays over the frames: the five
+        outputs of scan_blobs plus info (GMC_INFO_DTYPE: the applied vector, the modes, the counted records and the
+        modes' counts).  stream_off / keep: per-stream keep masks as for scan_zones, both or neither."""
+        if (stream_off is None) != (keep is None):
+            raise ValueError("stream_off and keep go together: give both or neither")
+        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
+        n = max(len(off) - 1, 0)
+        soff, ns = None, 0
+        if keep is not None:
+            soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
+            ns = max(len(soff) - 1, 0)
+            keep = self._keep_words(keep, ns)
+        out = {"flags": np.zeros(n, dtype=np.uint8), "centres": np.zeros(n, dtype=np.uint32), "blobs": np.zeros(n, dtype=np.uint32),
+               "largest": np.zeros(n, dtype=np.uint32), "box": np.full(n, 0xFFFF, dtype=np.uint16).repeat(4).view(BLOB_BOX_DTYPE),
+               "info": np.zeros(n, dtype=GMC_INFO_DTYPE)}
+        check(self._lib.mtgpu_scan_frames_gmc_blobs(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, _ptr(soff), ns,
+                                                    _ptr(keep), int(max_shift), int(min_share_q8), int(min_blob_cells),
+                                                    *(_ptr(out[k]) for k in GMC_BLOB_OUTPUTS)))
+        return out
+
+    def scan_gmc_blobs_device(self, d_rec, d_off, d_sd, max_shift: int = GMC_DEFAULT_MAX_SHIFT,
+                              min_share_q8: int = GMC_DEFAULT_MIN_SHARE_Q8, min_blob_cells: int = 1, d_stream_off=None, d_keep=None,
+                              compact=False, want=GMC_BLOB_OUTPUTS, out=None, stream=None) -> dict:
+        """Device-resident batch (torch CUDA tensors) -> a dict of CUDA tensors over the frames: flags uint8, centres /
+        blobs / largest int32, box int16 [F, 4] as scan_blobs_device returns them, info int32 [F, 5] (the bits of the
+        library's mt_gmc_info elements: info.cpu().numpy().view(GMC_INFO_DTYPE)); None for an output not in `want`.
+        d_rec / d_off / d_sd / d_stream_off / d_keep / compact as for scan_blobs_device.  `largest` is ready for
+        sweep_streams_device: level L there is flags at min_blob_cells = L.  out: a dict of preallocated tensors by
+        name.  Asynchronous on `stream` (default: torch's current stream)."""
+        import torch
+        want = tuple(want)
+        for w in want:
+            if w not in GMC_BLOB_OUTPUTS:
+                raise ValueError(f"want: {w!r} is not one of {GMC_BLOB_OUTPUTS}")
+        if (d_stream_off is None) != (d_keep is None):
+            raise ValueError("d_stream_off and d_keep go together: give both or neither")
+        dev = d_off.device
+        n_frames = max(d_off.numel() - 1, 0)
+        res = {}
+        for name in GMC_BLOB_OUTPUTS:
+            if name not in want:
+                res[name] = None
+                continue
+            dtype = torch.uint8 if name == "flags" else torch.int16 if name == "box" else torch.int32
+            shape = (n_frames, 4) if name == "box" else (n_frames, 5) if name == "info" else (n_frames,)
+            t = (out or {}).get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, name
+            res[name] = t
+        if n_frames == 0:              # nothing to write (an empty tensor has no address to hand over)
+            return res
+        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_off.dtype == torch.int64
+        ns = 0
+        if d_keep is not None:
+            ns = max(d_stream_off.numel() - 1, 0)
+            assert d_stream_off.is_contiguous() and d_keep.is_contiguous()
+            assert d_stream_off.dtype == torch.int64 and d_keep.dtype == torch.int64
+            assert d_keep.numel() == ns * self.params.grid_h * ((self.params.grid_w + 63) // 64)
+        rec_bytes = 8 if compact else 40
+        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+        check(self._lib.mtgpu_scan_gmc_blobs_device(
+            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
+            None if d_sd is None else d_sd.data_ptr(), n_frames, ptr(d_stream_off), ns, ptr(d_keep), int(max_shift),
+            int(min_share_q8), int(min_blob_cells), *(ptr(res[k]) for k in GMC_BLOB_OUTPUTS), st))
         return res
 
     # ------------------------------------------------------- motion scalar
