@@ -1,6 +1,6 @@
 """The random stream of tests/test_gpu_derived_soak.py — the soak of the sweep, the activity map, the masked scan and the
 compensated scan — and its expected values, usable without a GPU (tests/test_derived_cliff_host.py replays the first
-iterations):
+iterations).  No labelling kernel is in it: the blob scans meet random connectivity in tests/test_gpu_blob_planes.py.
 
     d = draw(rng, it, seed)           # grid, parameters, batch, streams, masks, settings, record layout, base alignment
     e = expected(d, kernel)           # kernel in KERNELS, where d["support"][kernel]
