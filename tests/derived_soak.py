@@ -1,6 +1,7 @@
-"""The random stream of tests/test_gpu_derived_soak.py — the soak of the sweep, the activity map, the masked scan and the
-compensated scan — and its expected values, usable without a GPU (tests/test_derived_cliff_host.py replays the first
-iterations).  No labelling kernel is in it: the blob scans meet random connectivity in tests/test_gpu_blob_planes.py.
+"""The random stream of tests/test_gpu_derived_soak.py — the soak of the sweep, the activity map, the masked scan, the
+compensated scan, the blob scan and the compensated blob scan — and its expected values, usable without a GPU
+(tests/test_derived_cliff_host.py replays the first iterations).  The two labelling kernels meet any grid width and
+height here, with the LDS layout that follows from it; random connectivity is the business of tests/test_gpu_blob_planes.py.
 
     d = draw(rng, it, seed)           # grid, parameters, batch, streams, masks, settings, record layout, base alignment
     e = expected(d, kernel)           # kernel in KERNELS, where d["support"][kernel]
@@ -8,7 +9,10 @@ iterations).  No labelling kernel is in it: the blob scans meet random connectiv
 
 What the compensated scan alone needs (max_shift, min_share_q8, a pan per frame and its own copy of the records, in which
 a share of every frame's records follows the pan) comes from a RandomState of its own, seeded from (seed, it): the
-stream `rng` and everything drawn from it are what they were before that kernel joined.
+stream `rng` and everything drawn from it are what they were before that kernel joined.  What the two blob scans alone
+need (min_blob_cells, whether the call is masked) comes from a third RandomState, seeded from (seed, it) and BLOBS_SALT:
+`rng` and draw_gmc's state are what they were before the blob scans joined.  The blob scan runs on d["mv"], the
+compensated one on d["gmc_mv"] with draw_gmc's settings; masked, both use d["zsoff"] and d["keeps"].
 
 The grid comes from w, h in [64, 3900] x [64, 2200] and block_shift 1 .. 5 as in tests/soak_replay.py, but the shifts are
 not equally likely: a derived kernel holds a whole frame's counters in LDS and supports about 37 000 cells, which a
@@ -19,14 +23,17 @@ import numpy as np
 import mvtrim_amd as m
 from mvtrim_amd import _abi, synth
 
+import blobs_model as bm
+import gmc_blobs_inputs as gbi
 import gmc_model as gm
 import oracle_binding as ob
+import pipe_gmc_inputs as pgi
 import zones_inputs as zi
 from activity_model import assert_oracle_identities, model_maps
 from derived_edge_inputs import MI355X_LDS, UNALIGNED_SHIFTS
 from scan_checks import junk_padding
 
-KERNELS = ("sweep", "activity", "zones", "gmc")
+KERNELS = ("sweep", "activity", "zones", "gmc", "blobs", "gmc_blobs")
 DEFAULT_SEED = 24680
 SHIFT_P = [0.04, 0.08, 0.18, 0.35, 0.35]                 # block_shift 1 .. 5
 THR_POOL = [0.0, 4.0, 9.5, 16.0, 25.0, 37.0, 4294967296.0, float("inf")]
@@ -37,6 +44,8 @@ GMC_FOLLOW_POOL = [0.0, 0.4, 0.6, 0.95]                  # the share of a frame'
 GMC_SHIFT_P = [0.1, 0.15, 0.25, 0.3, 0.2]
 GMC_SHARE_Q8_P = [0.25, 0.3, 0.3, 0.15]
 GMC_FOLLOW_P = [0.1, 0.25, 0.3, 0.35]
+BLOBS_SALT = 0xB10B                                      # the third state's seed is (seed, it, BLOBS_SALT); draw_gmc's is (seed, it)
+MIN_BLOB_POOL = [0, 1, 2, 3, 5, 12, 40, 3000]            # 0 and 1 change no flag; 40 and 3000 lie above most blobs' sizes
 
 
 def _preview(fn, *a):
@@ -70,6 +79,20 @@ def draw_gmc(seed, it, p, mv, off):
     out["src_y"][who] = np.clip(mv["dst_y"][who].astype(np.int64) - pans[fr[who], 1], -32768, 32767)
     return dict(gmc_max_shift=ms, gmc_share_q8=q8, gmc_pans=pans, gmc_follow=follow, gmc_mv=out,
                 support_gmc=_preview(m.gmc_preview, p, MI355X_LDS))
+
+
+def draw_blobs(seed, it, p):
+    """The blob scans' own inputs of iteration `it`: min_blob_cells, and whether the two calls carry the draw's streams and
+    keep masks (they run unmasked where the draw has no masks: see blob_masks)."""
+    rng = np.random.RandomState([int(seed) & 0xFFFFFFFF, int(it), BLOBS_SALT])
+    return dict(min_blob_cells=int(rng.choice(MIN_BLOB_POOL)), blob_masked=bool(rng.rand() < 0.5),
+                support_blobs=_preview(m.blobs_preview, p, MI355X_LDS), support_gmc_blobs=_preview(m.gmc_blobs_preview, p, MI355X_LDS))
+
+
+def blob_masks(d):
+    """(stream_off, keeps) of the blob scans' calls on draw d, or (None, None): unmasked by the draw, or masked by the
+    draw on a grid the masked scan does not support, for which no keeps were drawn."""
+    return (d["zsoff"], d["keeps"]) if d["blob_masked"] and d["keeps"] is not None else (None, None)
 
 
 def draw(rng, it, seed=DEFAULT_SEED):
@@ -126,6 +149,9 @@ def draw(rng, it, seed=DEFAULT_SEED):
     g = draw_gmc(seed, it, p, mv, off)                       # not from `rng`: see the module docstring
     support["gmc"] = g.pop("support_gmc")
     d.update(g)
+    b = draw_blobs(seed, it, p)                              # nor from draw_gmc's state
+    support["blobs"], support["gmc_blobs"] = b.pop("support_blobs"), b.pop("support_gmc_blobs")
+    d.update(b)
     return d
 
 
@@ -226,6 +252,83 @@ def gmc_counts_np(p, mv, off, sd, max_shift, min_share_q8):
     return centres, info
 
 
+def _same_partition(cen, lab):
+    """blobs_model.label's partition of the plane is scipy.ndimage.label's (4-neighbourhood); True where scipy is absent."""
+    try:
+        from scipy import ndimage
+    except ImportError:
+        return True
+    ref, n = ndimage.label(cen, structure=np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]]))
+    pairs = set(zip(ref[cen].tolist(), lab[cen].tolist()))
+    return int(lab.max()) == n == len(pairs) == len({a for a, _ in pairs}) == len({b for _, b in pairs}) and not lab[~cen].any()
+
+
+def blob_batch(p, mv, off, sd, soff=None, keeps=None, gmc=None, check_labels=False):
+    """blobs_model.model_batch (gmc None) or gmc_blobs_inputs.model_batch (gmc = (max_shift, min_share_q8)), frame for
+    frame and line for line, with blobs_model.blob_stats memoised per distinct centre plane: under vectors_needed 0 the
+    64 frames of a draw share one plane per stream — one blob of up to 37 000 cells, seconds of flood fill each.  Every
+    frame is still checked.  check_labels: every distinct plane's labelling is also held against scipy's."""
+    F = len(off) - 1
+    has = zi.has_side_data(off, sd)
+    st = zi.stream_of_frames(soff, F) if keeps is not None else np.zeros(F, dtype=np.int64)
+    out = {k: np.zeros(F, dtype=np.uint32) for k in ("centres", "blobs", "largest")}
+    out["box"] = np.full((F, 4), 0xFFFF, dtype=np.uint16)
+    if gmc is not None:
+        out["info"] = np.zeros((F, 7), dtype=np.int64)
+    memo = {}
+    for f in range(F):
+        if not has[f] or (keeps is not None and not 0 <= st[f] < len(keeps)):
+            continue
+        fr, keep = mv[int(off[f]):int(off[f + 1])], None if keeps is None else keeps[st[f]]
+        if gmc is None:
+            cen = bm.centre_plane(p, fr, keep)
+        else:
+            gx, gy, n_in, mx, nx, my, ny = pgi.estimate(p, fr, gmc[0], gmc[1], keep)
+            cen = gbi.centre_plane(p, fr, gx, gy, keep)
+            out["info"][f] = (gx, gy, mx, my, n_in, nx, ny)
+        key = np.packbits(cen).tobytes()
+        if key not in memo:
+            memo[key] = bm.blob_stats(cen)
+            assert not check_labels or _same_partition(cen, bm.label(cen)), ("labelling", f)
+        out["centres"][f], out["blobs"][f], out["largest"][f], out["box"][f] = memo[key]
+    return out
+
+
+def _expected_blobs(d, kernel, check_sources):
+    """The expected outputs of the blob scan (on d["mv"]) or the compensated blob scan (on d["gmc_mv"]) under
+    blob_masks(d), and what the draw reaches: "multi" (frames with more than one blob), "flag_off" (frames whose centre
+    count alone would set the flag and whose largest blob is below min_blob_cells), "flag_kept" (frames flagged under a
+    min_blob_cells above 1), "masked", "behind" (frames behind the last stream of a masked call).  check_sources: the
+    memoised batch equals the model's own model_batch; masked, the blob scan's centres are the masked scan's expected
+    ones under the same streams and keeps, unmasked the oracle's; unmasked, the compensated form's centres and info are
+    the compensated scan's expected ones; every distinct plane labels as scipy labels it."""
+    p, off, sd = d["params"], d["off"], d["sd"]
+    soff, keeps = blob_masks(d)
+    if kernel == "blobs":
+        mv, gmc = d["mv"], None
+    else:
+        mv, gmc = d["gmc_mv"], (d["gmc_max_shift"], d["gmc_share_q8"])
+    e = blob_batch(p, mv, off, sd, soff, keeps, gmc, check_labels=check_sources)
+    if check_sources:
+        model = bm.model_batch(p, mv, off, sd, soff, keeps) if gmc is None else gbi.model_batch(p, mv, off, sd, gmc[0], gmc[1], soff, keeps)
+        for k in e:
+            assert e[k].tolist() == model[k].tolist(), (kernel, k, d["it"])
+        if gmc is None and keeps is not None:
+            assert e["centres"].tolist() == zi.model_batch(p, mv, off, sd, soff, keeps)[0].tolist(), ("blobs against zones", d["it"])
+        elif gmc is None:
+            assert e["centres"].tolist() == ob.scan_centres(p, mv, off, sd, nthreads=8)[1].tolist(), ("blobs against the oracle", d["it"])
+        elif keeps is None:
+            ce, rows = expected(d, "gmc")["centres"], expected(d, "gmc")["info"]
+            assert e["centres"].tolist() == ce.tolist() and e["info"].tolist() == rows.tolist(), ("gmc_blobs against gmc", d["it"])
+    mb, cn = d["min_blob_cells"], max(1, p.clusters_needed)
+    e["flags"] = bm.flags_np(p, e["centres"], e["largest"], mb)
+    by_count = e["centres"] >= cn
+    e.update(total=int(e["centres"].sum(dtype=np.uint64)), multi=int((e["blobs"] > 1).sum()),
+             flag_off=int((by_count & (e["flags"] == 0)).sum()), flag_kept=int((e["flags"] != 0).sum()) if mb > 1 else 0,
+             masked=keeps is not None, behind=int(len(sd) - int(soff[-1])) if keeps is not None else 0)
+    return e
+
+
 def expected(d, kernel, check_sources=False):
     """The expected outputs of `kernel` on draw d and "total", the sum of the centre counts they hold.  check_sources:
     assert that the second, independent source agrees — the sweep: the oracle and sweep_counts_np on every setting; the
@@ -234,7 +337,8 @@ def expected(d, kernel, check_sources=False):
     the oracle on the records as they are; the compensated scan (on d["gmc_mv"]): gmc_counts_np against tests/gmc_model.py
     with its candidate-by-candidate mode_of, and consequence C of include/mtgpu_gmc.h against the oracle on every frame
     whose src + (gx, gy) stays in int16.  The compensated scan adds "compensated" (frames with gx or gy != 0),
-    "compensated_with_centres" and "found_not_applied" (a mode != 0 on an axis whose g is 0)."""
+    "compensated_with_centres" and "found_not_applied" (a mode != 0 on an axis whose g is 0).  The two blob scans:
+    _expected_blobs."""
     p, mv, off, sd = d["params"], d["mv"], d["off"], d["sd"]
     if kernel == "gmc":
         mv, ms, q8 = d["gmc_mv"], d["gmc_max_shift"], d["gmc_share_q8"]
@@ -251,6 +355,8 @@ def expected(d, kernel, check_sources=False):
         lost = ((rows[:, 2] != 0) & (rows[:, 0] == 0)) | ((rows[:, 3] != 0) & (rows[:, 1] == 0))
         return dict(flags=(ce >= max(1, p.clusters_needed)).astype(np.uint8), centres=ce, info=rows, total=int(ce.sum(dtype=np.uint64)),
                     compensated=int(comp.sum()), compensated_with_centres=int((comp & (ce > 0)).sum()), found_not_applied=int(lost.sum()))
+    if kernel in ("blobs", "gmc_blobs"):
+        return _expected_blobs(d, kernel, check_sources)
     if kernel == "sweep":
         T, V, F = len(d["thr"]), len(d["vec"]), len(sd)
         want, memo = np.zeros((T, V, F), dtype=np.uint32), {}

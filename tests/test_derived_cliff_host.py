@@ -338,6 +338,79 @@ def test_soak_draws_reach_the_compensated_scan():
     assert shifts == set(dsoak.GMC_SHIFT_POOL) and shares == set(dsoak.GMC_SHARE_Q8_POOL) and outside >= 5
 
 
+# sha256 (first 16 hex digits) over mv, off, thr, vec, keeps and the compensated scan's max_shift, min_share_q8, pans, follow
+# share and records of the default seed's first eight draws, as draw() made them before the blob scans joined the soak
+DRAWS_BEFORE_BLOBS = ["c4072ee87b7db2d0", "1132c46077c7206c", "9ec73fe13afb5ee1", "4332b96d77677b17", "d65343551ffc13e1",
+                      "e6fb2e9100bf5bc2", "48c3bff0fbff536b", "1ad07dc68d9add95"]
+GMC_FIELDS = ("gmc_max_shift", "gmc_share_q8", "gmc_pans", "gmc_follow", "gmc_mv")
+
+
+def draw_digest_with_gmc(d):
+    import hashlib
+    h = hashlib.sha256(draw_digest(d).encode())
+    for k in GMC_FIELDS:
+        v = d.get(k)
+        if isinstance(v, np.ndarray) and v.dtype.names:              # field by field: a copy of padded records need not
+            for name in v.dtype.names:                               # carry the padding bytes over
+                h.update(np.ascontiguousarray(v[name]).tobytes())
+        else:
+            h.update(v.tobytes() if isinstance(v, np.ndarray) else repr(v).encode())
+    return h.hexdigest()[:16]
+
+
+def test_soak_draws_are_what_they_were_before_the_blob_scans_joined():
+    """min_blob_cells and the mask decision come from a RandomState of their own, seeded apart from draw_gmc's: `rng`, the
+    compensated scan's settings and its copy of the records are what they were."""
+    rng = np.random.RandomState(dsoak.DEFAULT_SEED)
+    for it, want in enumerate(DRAWS_BEFORE_BLOBS, start=1):
+        d = dsoak.draw(rng, it)
+        assert draw_digest_with_gmc(d) == want, it
+    a, b = dsoak.replay(dsoak.DEFAULT_SEED, 5), dsoak.replay(dsoak.DEFAULT_SEED, 5)
+    assert (a["min_blob_cells"], a["blob_masked"]) == (b["min_blob_cells"], b["blob_masked"])
+    picks = {(x["min_blob_cells"], x["blob_masked"]) for x in (dsoak.draw_blobs(s, 5, a["params"]) for s in range(12))}
+    assert len(picks) > 3                                            # other seeds draw other settings for the same iteration
+    # the third state is not draw_gmc's: the same (seed, it) gives another stream
+    g = np.random.RandomState([dsoak.DEFAULT_SEED, 5]).randint(0, 2 ** 31, size=4)
+    t = np.random.RandomState([dsoak.DEFAULT_SEED, 5, dsoak.BLOBS_SALT]).randint(0, 2 ** 31, size=4)
+    assert g.tolist() != t.tolist()
+
+
+BLOBS_REPLAYED = 60
+
+
+def test_soak_draws_reach_the_blob_scans():
+    """The default seed's first 60 iterations, from the models alone.  Measured: 60 creatable, each blob kernel supported
+    in 47 of them; see the figures printed below and docs/rounds/r15_blob_edges.md."""
+    rng = np.random.RandomState(dsoak.DEFAULT_SEED)
+    creatable = 0
+    n = {k: dict(supported=0, multi=0, flag_off=0, flag_kept=0, masked=0, behind=0, vn0=0) for k in ("blobs", "gmc_blobs")}
+    pool = set()
+    for it in range(1, BLOBS_REPLAYED + 1):
+        d = dsoak.draw(rng, it)
+        creatable += d["creatable"]
+        for k in n:
+            if not d["support"].get(k):
+                continue
+            e = dsoak.expected(d, k)
+            n[k]["supported"] += 1
+            pool.add(d["min_blob_cells"])
+            vn0 = (d["params"].vectors_needed & 0xFF) == 0
+            n[k]["vn0"] += vn0
+            if vn0 and k == "blobs" and not e["masked"]:              # one blob spanning the plane's inner columns
+                p = d["params"]
+                rows, has = max(0, p.grid_h - 2 * p.vertical_margin), zi.has_side_data(d["off"], d["sd"])
+                assert (e["blobs"][has] == (1 if rows and p.grid_w > 2 else 0)).all() and (e["largest"][has] == rows * max(0, p.grid_w - 2)).all()
+            for c in ("multi", "flag_off", "flag_kept", "behind"):
+                n[k][c] += e[c] > 0
+            n[k]["masked"] += e["masked"]
+    print("creatable", creatable, n, "min_blob_cells seen", sorted(pool))
+    for k, c in n.items():
+        assert 4 * c["supported"] >= 3 * creatable and c["supported"] < creatable, (k, c)
+        assert c["multi"] >= 1 and c["flag_off"] >= 1 and c["flag_kept"] >= 1, (k, c)
+        assert 1 <= c["masked"] < c["supported"] and c["behind"] >= 1 and c["vn0"] >= 1, (k, c)
+    assert {0, 1} <= pool and max(pool) >= 40
+
+
 def test_soak_preview_says_unsupported_as_the_library_does():
     p = m.ScanParams.from_config(3840, 2160, block_size=4, block_shift=2)
     assert dsoak.support_of(p, 3, 3) == {"sweep": False, "activity": False, "zones": False}

@@ -1,7 +1,8 @@
-"""Soak of the derived kernels: randomised parity of the sweep, the activity map, the masked scan and the compensated
-scan for MTGPU_SOAK_SECONDS (default 4 s; set it to minutes to hunt rare faults).  Every iteration draws a grid, a
-parameter set, a ragged batch with runs and blobs, streams with empty ones, keep masks, sweep settings, a pan per frame
-with max_shift and min_share_q8, a record layout and — every third time — a record base inside a larger buffer
+"""Soak of the derived kernels: randomised parity of the sweep, the activity map, the masked scan, the compensated scan,
+the blob scan and the compensated blob scan for MTGPU_SOAK_SECONDS (default 4 s; set it to minutes to hunt rare faults).
+Every iteration draws a grid, a parameter set, a ragged batch with runs and blobs, streams with empty ones, keep masks,
+sweep settings, a pan per frame with max_shift and min_share_q8, a minimum blob size, whether the blob scans are masked,
+a record layout and — every third time — a record base inside a larger buffer
 (tests/derived_soak.py, which also computes the expected values from the oracle and the numpy models and rebuilds any
 iteration on the CPU: derived_soak.replay(seed, it)).  Every comparison is exact; a kernel whose preview says
 unsupported must answer MT_ERR_UNSUPPORTED and touch nothing."""
@@ -15,6 +16,7 @@ import mvtrim_amd as m
 from mvtrim_amd import _abi
 
 import derived_soak as dsoak
+import test_gpu_gmc_blobs as gb
 from scan_checks import assert_counts_equal
 from test_gpu_activity import assert_maps_equal, junk_maps
 from test_gpu_derived_cliff import assert_lds_limit
@@ -117,9 +119,38 @@ def check_draw(s, d, where):
         what = f"gmc max_shift {d['gmc_max_shift']} min_share_q8 {d['gmc_share_q8']} follow {d['gmc_follow']}, {where}"
         assert_counts_equal(ce.cpu().numpy().view(np.uint32), e["centres"], what, got_f=fl.cpu().numpy(), want_f=e["flags"])
         assert_info_equal(inf.cpu().numpy().reshape(-1).view(_abi.GMC_INFO_DTYPE), e["info"], what)
-        return e
-    expect_unsupported(call, [fl, ce, inf], [JUNK_FLAG, JUNK, JUNK], "gmc, " + where)
-    return None
+        reached = {"gmc": e}
+    else:
+        expect_unsupported(call, [fl, ce, inf], [JUNK_FLAG, JUNK, JUNK], "gmc, " + where)
+        reached = {"gmc": None}
+    # the blob scan on the draw's records and the compensated blob scan on the compensated scan's copy: min_blob_cells and
+    # the mask decision of the draw, the draw's layout and base, all outputs requested
+    soff, keeps = dsoak.blob_masks(d)
+    b_soff, b_keep = (soff_tensor(soff), keep_tensor(keeps)) if keeps is not None else (None, None)
+    mb = d["min_blob_cells"]
+    masks = f"min_blob_cells {mb} masked {keeps is not None}" + (f" streams {soff.tolist()} densities {d['keep_density']}" if keeps is not None else "")
+    for kernel, rec in (("blobs", d_rec), ("gmc_blobs", g_rec)):
+        out = gb.junk_outputs(F, gb.OUTPUTS if kernel == "gmc_blobs" else gb.BLOB_OUTPUTS)
+        if kernel == "blobs":
+            call = lambda: s.scan_blobs_device(rec, d_off, d_sd, mb, b_soff, b_keep, compact=compact, out=out)   # noqa: E731
+        else:
+            call = lambda: s.scan_gmc_blobs_device(rec, d_off, d_sd, d["gmc_max_shift"], d["gmc_share_q8"], mb, b_soff, b_keep,   # noqa: E731
+                                                   compact=compact, out=out)
+        if d["support"][kernel]:
+            call()
+            torch.cuda.synchronize()
+            e = dsoak.expected(d, kernel)
+            what = f"{kernel} {masks}" + (f" max_shift {d['gmc_max_shift']} min_share_q8 {d['gmc_share_q8']}" if kernel == "gmc_blobs" else "") + ", " + where
+            got = gb.to_host(out)
+            gb.assert_blobs(got, e, what)
+            assert got["flags"].tolist() == e["flags"].tolist(), (what, "flags", got["flags"].tolist(), e["flags"].tolist())
+            if kernel == "gmc_blobs":
+                gb.assert_info(got, e["info"], what)
+            reached[kernel] = e
+        else:
+            expect_unsupported(call, list(out.values()), [{"flags": JUNK_FLAG, "box": gb.JUNK_BOX}.get(k, JUNK) for k in out], kernel + ", " + where)
+            reached[kernel] = None
+    return reached
 
 
 def test_soak_derived_kernels(gpu_scanner_factory):
@@ -131,6 +162,7 @@ def test_soak_derived_kernels(gpu_scanner_factory):
     it = done = 0
     ran = {k: 0 for k in dsoak.KERNELS}
     gmc = dict(compensated=0, compensated_with_centres=0, found_not_applied=0)
+    blobs = {k: dict(multi=0, flag_off=0, flag_kept=0, masked=0, behind=0) for k in ("blobs", "gmc_blobs")}
     while time.time() < t_end:
         it += 1
         d = dsoak.draw(rng, it, seed)
@@ -141,7 +173,7 @@ def test_soak_derived_kernels(gpu_scanner_factory):
                  f"window {d['window']}")
         s = gpu_scanner_factory(p)
         try:
-            g = check_draw(s, d, where)
+            reached = check_draw(s, d, where)
         except (AssertionError, m.MtgpuError, pytest.fail.Exception) as e:
             raise AssertionError(f"{where} (derived_soak.replay({seed}, {it}) rebuilds the inputs): {e}") from e
         finally:
@@ -150,12 +182,18 @@ def test_soak_derived_kernels(gpu_scanner_factory):
         for k in dsoak.KERNELS:
             ran[k] += d["support"][k]
         for k in gmc:
-            gmc[k] += g is not None and g[k] > 0
+            gmc[k] += reached["gmc"] is not None and reached["gmc"][k] > 0
+        for kernel, n in blobs.items():
+            for k in n:
+                n[k] += reached[kernel] is not None and reached[kernel][k] > 0
     # The budget is looked at between draws: a run overshoots it by at most one draw.  The costliest draw — the oracle on
     # 64 settings of 64 frames of 8000 records repeated 3.5 times, about 10^8 record visits on eight threads, and the numpy
     # models on 64 frames — takes about two seconds of CPU time, the average one a tenth of a second.  A second draw
     # starts whenever the first one ends inside the budget, so four seconds hold at least two; fewer means that the
-    # expected values, not the kernels, have become the cost.
+    # expected values, not the kernels, have become the cost.  The blob scans' expected values label every frame's centre
+    # plane by flood fill in plain Python; derived_soak.blob_batch labels each DISTINCT plane of a draw once, which keeps a
+    # vectors_needed 0 draw (64 frames, one blob of up to 37 000 cells per stream) at the cost of its streams.
     assert done >= (2 if budget >= 4 else 1), f"only {done} configurations in {budget:.0f} s"
     print(f"derived soak: {done} random configurations checked in {budget:.0f} s, kernels run {ran}, the compensated scan's "
-          f"draws with a frame compensated / one that keeps centres / a mode found and not applied: {gmc}")
+          f"draws with a frame compensated / one that keeps centres / a mode found and not applied: {gmc}, the blob scans' draws "
+          f"with several blobs in a frame / a flag min_blob_cells turns off / one it keeps / masks / a frame behind the last stream: {blobs}")
