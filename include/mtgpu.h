@@ -481,4 +481,8 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * the centres) — three more entry points, declared the same way. */
 #include "mtgpu_gmc_blobs.h"
 
+/* The compensated blob scan on the decode path: a pipe's third mode, motion blobs on compensated residuals for every
+ * batch, under the pipe's keep mask where it has one — two more entry points, declared the same way. */
+#include "mtgpu_pipe_gmc_blobs.h"
+
 #endif /* MTGPU_H */

@@ -52,8 +52,9 @@
  *  E. For a level L >= max(1, cn): `largest`, handed to the unchanged mtgpu_sweep_streams_device as its d_centres with
  *     levels = {L, ...}, gives the segments of `flags` at min_blob_cells = L, bit for bit.
  *
- * Out of scope: the decode path — mtgpu_pipe_set_gmc and mtgpu_pipe_set_blobs, the C++ host layer and mtgpu_scan_file
- * still refuse the pair; this is a call on a resident batch.  The row-banded grids (960x540, 32767-wide) are
+ * The decode path: mtgpu_pipe_gmc_blobs.h carries this scan through the pipe as a mode of its own
+ * (mtgpu_pipe_set_gmc_blobs), the C++ host layer and mtgpu_scan_file (--gmc-blobs); mtgpu_pipe_set_gmc and
+ * mtgpu_pipe_set_blobs, set one after the other, still refuse the pair.  Out of scope: the row-banded grids (960x540, 32767-wide) are
  * MT_ERR_UNSUPPORTED with the grid named, as for both parents.
  *
  * Kernel (csrc/gmc_blobs_kernels.hip): one workgroup per frame with side data; the keep rows are staged in LDS, a first

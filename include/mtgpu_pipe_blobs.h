@@ -58,6 +58,9 @@ extern "C" {
  * the unchanged mtgpu_sweep_streams_device at a level L >= max(1, clusters_needed), give the segments of
  * min_blob_cells = L, bit for bit.
  * With mtgpu_profile_enable on, a blob submit records one event triple, as a plain one.
+ * Compensation: this setter and mtgpu_pipe_set_gmc still refuse each other (MT_ERR_UNSUPPORTED, mtgpu_pipe_gmc.h); blobs
+ * on compensated residuals are a mode of their own, mtgpu_pipe_set_gmc_blobs (mtgpu_pipe_gmc_blobs.h), and while that
+ * mode is on, min_blob_cells > 0 here is MT_ERR_INVALID.
  */
 int mtgpu_pipe_set_blobs(mtgpu_pipe *pipe, int32_t min_blob_cells, int report);
 

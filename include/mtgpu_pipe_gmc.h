@@ -45,7 +45,8 @@
  * reports the flags and one 32-bit word per frame, chosen by `report`: the centre count or the applied vector.  There
  * is no mt_gmc_info through the pipe; it stays with mtgpu_scan_gmc_device.
  *
- * Out of scope: compensation together with blobs (each setter refuses the other, MT_ERR_UNSUPPORTED); a keep plane per
+ * Compensation together with blobs is a mode of its own, mtgpu_pipe_set_gmc_blobs (mtgpu_pipe_gmc_blobs.h); this setter
+ * and mtgpu_pipe_set_blobs still refuse each other (MT_ERR_UNSUPPORTED).  Out of scope: a keep plane per
  * stream, or a keep argument on the resident mtgpu_scan_gmc_device; the row-banded grids.
  *
  * Kernel (csrc/gmc_kernels.hip, the pipe form): the compensated scan without its clear kernel — the planning kernel

@@ -261,6 +261,12 @@ ABI_GMC_BLOBS = {
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_pipe_gmc_blobs.h declares (the compensated blob setting of a pipe; mtgpu.h includes it).
+ABI_PIPE_GMC_BLOBS = {
+    "mtgpu_pipe_set_gmc_blobs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int]),
+    "mtgpu_pipe_gmc_blobs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+}
+
 _lib = None
 
 
@@ -292,7 +298,8 @@ def load_library(path=None):
     lib = C.CDLL(p)
     for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
             list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
-            list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()) + list(ABI_GMC_BLOBS.items()):
+            list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()) + list(ABI_GMC_BLOBS.items()) + \
+            list(ABI_PIPE_GMC_BLOBS.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -15,6 +15,8 @@ namespace mtgpu {
 
 constexpr int kGmcBlobBlock = 1024;    // lanes per workgroup (a multiple of 64: a wave owns one 64-cell word of a row)
 constexpr int kGmcBlobUnroll = 4;      // independent record loads in flight per lane
+// What the pipe form's ONE count carries (MT_PIPE_REPORT_* of include/mtgpu.h).
+constexpr int kGmcBlobReportCentres = 0, kGmcBlobReportLargest = 1, kGmcBlobReportVector = 2;
 
 // LDS of one workgroup, in this order (R = analysed rows, at least 1; W = 64-bit words per mask row):
 //   tile     (R + 2) x gw u32, padded to 4 words   vote counters of the residual vote; the labels once the masks exist
@@ -52,7 +54,8 @@ struct GmcBlobOut {
 };
 
 // The ONE argument of gmc_blobs_frames_kernel: it starts the kernel-argument segment, where the kernel reads `out` a
-// second time, late (gmc_blobs_kernels.hip).
+// second time, late (gmc_blobs_kernels.hip).  The pipe form's fields stand behind `out`, so that the offsets of those
+// late loads are the same in both forms.
 struct GmcBlobArgs {
   const unsigned char *mv;
   const WorkItem *work;
@@ -62,6 +65,8 @@ struct GmcBlobArgs {
   unsigned int n_streams;
   const unsigned long long *keep;
   GmcBlobOut out;
+  int sys_flags, sys_count;               // pipe form: the array is pinned host memory, stored at system scope
+  int report;                             // pipe form: kGmcBlobReport*, what out.centres receives
 };
 
 struct GmcBlobLaunch {
@@ -79,6 +84,13 @@ struct GmcBlobLaunch {
   unsigned int *centres, *blobs, *largest;  // n_frames words each, or null
   BlobBox *box;                           // n_frames boxes, or null
   unsigned int *info;                     // n_frames x kGmcInfoWords words (mt_gmc_info), or null
+  // The pipe form (pipe.hip's staging batches; include/mtgpu_pipe_gmc_blobs.h): no clear kernel — launch_plan gets flags
+  // and `centres`, the batch's ONE count array, and answers the frames without side data; the results are stored at
+  // system scope where sys_flags / sys_count say that the array is not device memory; `keep` is ONE plane of gh x W
+  // words or null, stream_off / n_streams null / 0; `report` (kGmcBlobReport*) chooses what `centres` receives.  blobs,
+  // largest, box and info must be null.  0: the resident form — sys_* and report 0.
+  int pipe = 0;
+  int sys_flags = 0, sys_count = 0, report = 0;
   GmcBlobK k;
   int lds_bytes;
   int lds_max;                            // device limit of dynamic LDS per workgroup
@@ -89,7 +101,8 @@ struct GmcBlobLaunch {
 };
 
 // Fills the non-null outputs with the answer of a frame without a blob (0; an all-0xFFFF box; a zero info), builds the
-// work list (launch_plan), then one workgroup per entry.
+// work list (launch_plan), then one workgroup per entry.  Pipe form: no fill — the planner answers the frames without
+// side data.
 hipError_t launch_gmc_blob_scan(const GmcBlobLaunch &L);
 
 }  // namespace mtgpu

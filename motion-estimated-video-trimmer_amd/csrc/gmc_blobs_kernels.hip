@@ -1,8 +1,9 @@
 // gmc_blobs_kernels.hip — the compensated blob scan: motion blobs on the residuals of every frame's dominant vector
 // (include/mtgpu_gmc_blobs.h).  The estimate is that of gmc_kernels.hip (under a keep mask, the masked estimate of its
 // pipe form), the active plane that of zones_kernels.hip, the labelling that of blobs_kernels.hip; what is new is that
-// the residual vote, which lives only in a workgroup's LDS tile, is labelled before the workgroup ends.  Resident form
-// only: the decode path refuses compensation next to blobs.
+// the residual vote, which lives only in a workgroup's LDS tile, is labelled before the workgroup ends.  Two forms: the
+// resident one and the pipe form of include/mtgpu_pipe_gmc_blobs.h, the decode path's third mode (its two single
+// setters, mtgpu_pipe_set_gmc and mtgpu_pipe_set_blobs, still refuse each other).
 //
 //   gmc_blobs_clear_kernel    fills the non-null outputs ahead of the scan kernel with the answer of a frame without a
 //                             blob (0 everywhere, an all-0xFFFF box, a zero info): a frame without side data, and a
@@ -25,6 +26,13 @@
 //   Every loop with a barrier inside has a trip count computed from workgroup-uniform values; no barrier sits inside a
 //   non-uniform branch.  Every output element has one writer after the clear: lane 0 of the frame's workgroup, plain
 //   vector stores, no global atomics.  The planner answers nothing itself (the outputs hold the clear's values).
+//
+// The pipe form (PIPE, include/mtgpu_pipe_gmc_blobs.h) follows the cut of gmc_frames_kernel and blobs_frames_kernel: no
+// clear kernel — the planner answers the frames without side data at the outputs' scope; no stream lookup — `keep` is ONE
+// plane of gh x W words or null, staged into the same keep rows; BOTH exits store the flag and ONE count (centres, the
+// largest blob, or the applied vector, by `report`) through store_flag / store_centres, because a reused pinned block
+// holds the previous batch's values; no box pass, no blobs, no info.  The flag pointer, the count pointer, the scopes and
+// the report are re-taken from the kernel-argument segment where they are used, as `out` is in the resident form.
 //
 // record_stream.h is used as it is; walk_value and pick_mode are those of gmc_kernels.hip, restated here because that
 // file stays as it is and keeps them in its unnamed namespace; hist_add makes the same adds with one branch less.
@@ -100,6 +108,11 @@ __device__ __forceinline__ GmcBlobOut late_outputs(LateArgs late) {
   return o;
 }
 
+// The pipe form's count of a frame: its centres, its largest blob, or the applied vector of the estimate in `res`.
+__device__ __forceinline__ unsigned int pipe_count(int report, unsigned int ncentres, unsigned int big, const unsigned int *res) {
+  return report == kGmcBlobReportVector ? ((res[2] & 0xffffu) | (res[3] << 16)) : report == kGmcBlobReportLargest ? big : ncentres;
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(256) void gmc_blobs_clear_kernel(unsigned char *__restrict__ flags, unsigned int *__restrict__ centres,
@@ -121,7 +134,11 @@ __global__ __launch_bounds__(256) void gmc_blobs_clear_kernel(unsigned char *__r
 
 // Waves per SIMD as the parents: a 1080p workgroup takes 34 848 bytes of LDS, two workgroups of 16 waves share a CU, eight
 // waves per SIMD and so at most 64 VGPRs; the 4K workgroup sits alone on its CU.
-template <int BLOCK, int UNROLL, int REC>
+// PIPE: the form for a pipe's staging batch — stream_off / n_streams are not read (null / 0), `keep` is ONE plane (gh x W
+// words) or null, of `out` only flags and centres are read — centres is the batch's ONE count array, whatever it
+// carries — and the results leave through store_flag / store_centres with sys_flags / sys_count.  !PIPE: sys_* and
+// report are not read (0).
+template <int BLOCK, int UNROLL, int REC, bool PIPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void gmc_blobs_frames_kernel(const GmcBlobArgs a) {
   static_assert(BLOCK % 64 == 0, "a wave owns one word of the centre plane");
   static_assert(BLOCK >= 2 * kGmcHistBins + 16, "one lane per word of hist, res and total");
@@ -161,7 +178,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const unsigned int f = __builtin_amdgcn_readfirstlane(me.f);
   const bool masked = keep != nullptr;
   unsigned int s = 0u;
-  if (masked) {
+  if (!PIPE && masked) {                        // pipe form: plane 0 serves every frame of the batch
     unsigned int lo = 0u, hi = n_streams;
     while (lo < hi) {
       const unsigned int mid = lo + ((hi - lo) >> 1);
@@ -272,6 +289,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   __syncthreads();
   const unsigned int ncentres = total[0];
   if (ncentres == 0u) {                                       // workgroup-uniform: most frames of most streams
+    if constexpr (PIPE) {                                     // a reused pinned block holds the previous batch's values
+      if (tid == 0) {
+        unsigned char *const fl = late->out.flags;
+        unsigned int *const cnt = late->out.centres;
+        if (cnt) store_centres(cnt, f, pipe_count(late->report, 0u, 0u, res), late->sys_count);
+        if (fl) store_flag(fl, f, (unsigned char)0, late->sys_flags);
+      }
+      return;
+    }
     if (tid == 0) {
       const GmcBlobOut o = late_outputs(late);
       if (o.centres) o.centres[f] = 0u;
@@ -295,6 +321,16 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   blob_label::winner<BLOCK>(cpl, crows, W, gw, L, total, lane);
   __syncthreads();
   const unsigned long long key = *reinterpret_cast<const unsigned long long *>(total + 2);
+  if constexpr (PIPE) {                                       // the box serves no pipe output: no pass, no barrier
+    if (tid == 0) {
+      const unsigned int big = (unsigned int)(key >> 32);
+      unsigned char *const fl = late->out.flags;
+      unsigned int *const cnt = late->out.centres;
+      if (cnt) store_centres(cnt, f, pipe_count(late->report, ncentres, big, res), late->sys_count);
+      if (fl) store_flag(fl, f, (unsigned char)((ncentres >= k.clust_need && big >= k.blob_need) ? 1 : 0), late->sys_flags);
+    }
+    return;
+  }
   const unsigned int win = 0xffffffffu - (unsigned int)(key & 0xffffffffull);
   blob_label::box<BLOCK>(cpl, crows, W, gw, L, total, win, lane);
   __syncthreads();
@@ -313,9 +349,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 
 namespace {
 
-template <int REC>
+template <int REC, bool PIPE>
 hipError_t launch_frames(const GmcBlobLaunch &L) {
-  auto kern = gmc_blobs_frames_kernel<kGmcBlobBlock, kGmcBlobUnroll, REC>;
+  auto kern = gmc_blobs_frames_kernel<kGmcBlobBlock, kGmcBlobUnroll, REC, PIPE>;
   static std::atomic<unsigned long long> ready{0ull};
   hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
   if (e != hipSuccess) return e;
@@ -329,6 +365,9 @@ hipError_t launch_frames(const GmcBlobLaunch &L) {
   a.n_streams = L.n_streams;
   a.keep = L.keep;
   a.out = GmcBlobOut{L.flags, L.centres, L.blobs, L.largest, L.box, L.info};
+  a.sys_flags = L.sys_flags;
+  a.sys_count = L.sys_count;
+  a.report = L.report;
   return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
     a.item0 = (unsigned int)i0;
     hipLaunchKernelGGL(kern, dim3(n), dim3(kGmcBlobBlock), L.lds_bytes, L.stream, a);
@@ -341,7 +380,15 @@ hipError_t launch_gmc_blob_scan(const GmcBlobLaunch &L) {
   if (L.n_frames == 0) return hipSuccess;
   if (L.rec_bytes != 40 && L.rec_bytes != 8) return hipErrorInvalidValue;
   if (!L.flags && !L.centres && !L.blobs && !L.largest && !L.box && !L.info) return hipErrorInvalidValue;
-  if (L.keep ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0)) return hipErrorInvalidValue;
+  if (L.pipe) {
+    // one plane, no stream table; flags and ONE count (L.centres); a report other than the centres needs the count
+    if (L.stream_off || L.n_streams != 0 || L.blobs || L.largest || L.box || L.info) return hipErrorInvalidValue;
+    if (L.report != kGmcBlobReportCentres && L.report != kGmcBlobReportLargest && L.report != kGmcBlobReportVector) return hipErrorInvalidValue;
+    if (L.report != kGmcBlobReportCentres && !L.centres) return hipErrorInvalidValue;
+  } else {
+    if (L.sys_flags != 0 || L.sys_count != 0 || L.report != 0) return hipErrorInvalidValue;
+    if (L.keep ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0)) return hipErrorInvalidValue;
+  }
   if (!L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records) return hipErrorInvalidValue;
   if (L.k.max_shift < 0 || L.k.max_shift > kGmcMaxShift || L.k.min_share_q8 > 256u) return hipErrorInvalidValue;
   // The kernel indexes the staged keep rows and the planes by these fields: they must be the grid's.
@@ -349,6 +396,13 @@ hipError_t launch_gmc_blob_scan(const GmcBlobLaunch &L) {
       (size_t)L.lds_bytes < gmc_blobs_lds_bytes(L.k.gw, L.k.R) || (size_t)L.k.tile_words != blob_tile_words(L.k.gw, L.k.R) ||
       L.k.W != (L.k.gw + 63) / 64)
     return hipErrorInvalidValue;
+  if (L.pipe) {
+    // The planner is handed the outputs and answers every frame without side data itself (at the outputs' scope), as in
+    // launch_gmc_scan and launch_blob_scan: no clear kernel — planning + one kernel.
+    hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres, L.sys_count);
+    if (e != hipSuccess) return e;
+    return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
+  }
   {
     const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
     hipLaunchKernelGGL(gmc_blobs_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream,
@@ -359,7 +413,7 @@ hipError_t launch_gmc_blob_scan(const GmcBlobLaunch &L) {
   // flags / centres null: the planner answers nothing itself (the outputs hold the clear's values already)
   hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
   if (e != hipSuccess) return e;
-  return L.rec_bytes == 8 ? launch_frames<8>(L) : launch_frames<40>(L);
+  return L.rec_bytes == 8 ? launch_frames<8, false>(L) : launch_frames<40, false>(L);
 }
 
 }  // namespace mtgpu

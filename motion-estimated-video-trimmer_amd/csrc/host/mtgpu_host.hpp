@@ -725,6 +725,9 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   bool report_largest_ = false;                        // report_largest(): last_centres() holds the largest blob, not the centres
   int gmc_max_shift_ = -1, gmc_min_share_q8_ = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;   // set_gmc(): the pipe's compensation; max_shift < 0: off
   bool report_vector_ = false;                         // report_vector(): last_centres() holds the packed applied vector
+  int gmc_blob_cells_ = 0;                             // set_gmc_blobs(): the pipe's pair mode (compensated blob scan); 0: off
+  int gmc_blob_max_shift_ = MTGPU_GMC_DEFAULT_MAX_SHIFT, gmc_blob_min_share_q8_ = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
+  int gmc_blob_report_ = MT_PIPE_REPORT_CENTRES;       // report_gmc_blobs(): what last_centres() holds in pair mode
   bool ok(int rc) {
     if (rc == MT_OK) return true;
     err_ = mtgpu_last_error();
@@ -845,6 +848,18 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   // whatever a pooled pipe carries.
   void set_gmc(int max_shift, int min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8) { gmc_max_shift_ = max_shift; gmc_min_share_q8_ = min_share_q8; }
   void report_vector(bool on) { report_vector_ = on; }
+  // Call before initialize().  The compensated blob scan for this video (include/mtgpu_pipe_gmc_blobs.h), the pipe's
+  // third mode: every check_frame of scan_range (:375-383) asks that the largest 4-connected blob of the centres of the
+  // RESIDUAL vote has at least min_blob_cells cells; the estimate and the active plane honour set_keep.  0: off.
+  // report_gmc_blobs(MT_PIPE_REPORT_LARGEST / _VECTOR): last_centres() returns that count in place of the centre counts
+  // (needs keep_centres(true): the pipe has ONE count array); the pair is then on at max(1, min_blob_cells).  Not
+  // together with set_min_blob_cells(n > 0), report_largest, set_gmc(>= 0) or report_vector.  initialize() ALWAYS
+  // settles the pipe's pair setting — off first, on again at the end if asked: a pooled pipe never refuses the next
+  // video's setting because of the previous one's.
+  void set_gmc_blobs(int min_blob_cells, int max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT, int min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8) {
+    gmc_blob_cells_ = min_blob_cells; gmc_blob_max_shift_ = max_shift; gmc_blob_min_share_q8_ = min_share_q8;
+  }
+  void report_gmc_blobs(int report) { gmc_blob_report_ = report; }
 
   // batch_records == 0: sized from the source and the staging layout — MTGPU_BATCH_MB MiB of
   // pinned staging per batch, and never less than two frames of one record per 4x4 block (the
@@ -860,6 +875,8 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
     if (!be_->ensure(src_.width(), src_.height(), device_, batch_records, batch_frames, n_buffers, err_, keep_centres_)) return false;
     pipe_ = be_->pipe();
     // the pipe is idle here (a previous scanner on this backend left nothing in flight, or the backend was rebuilt)
+    // the pair off first: a pooled pipe that carries it would refuse both single settings below
+    if (mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
     // compensation off first: a pooled pipe that carries it would refuse the blob setting below
     if (mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
     {
@@ -901,6 +918,27 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
       }
       if (mtgpu_pipe_set_keep(pipe_, keep_.data()) != MT_OK) {
         err_ = mtgpu_last_error();
+        (void)mtgpu_pipe_set_keep(pipe_, nullptr);
+        pipe_ = nullptr;
+        return false;
+      }
+    }
+    if (gmc_blob_cells_ != 0 || gmc_blob_report_ != MT_PIPE_REPORT_CENTRES) {
+      const char *bad = nullptr;
+      if (gmc_blob_cells_ < 0) bad = "set_gmc_blobs: min_blob_cells is negative";
+      else if (min_blob_cells_ > 0) bad = "set_gmc_blobs together with set_min_blob_cells: the compensated blob scan has its own minimum blob size";
+      else if (report_largest_) bad = "set_gmc_blobs together with report_largest: ask report_gmc_blobs(MT_PIPE_REPORT_LARGEST)";
+      else if (gmc_max_shift_ >= 0) bad = "set_gmc_blobs together with set_gmc: the compensated blob scan has its own max_shift and min_share_q8";
+      else if (report_vector_) bad = "set_gmc_blobs together with report_vector: ask report_gmc_blobs(MT_PIPE_REPORT_VECTOR)";
+      else if (gmc_blob_report_ != MT_PIPE_REPORT_CENTRES && !keep_centres_)
+        bad = "report_gmc_blobs needs keep_centres: the largest blob and the applied vector travel in the pipe's count array";
+      // the existing sequence left both single modes off here unless `bad` names one of them
+      if (bad || mtgpu_pipe_set_gmc_blobs(pipe_, std::max(1, gmc_blob_cells_), gmc_blob_max_shift_, gmc_blob_min_share_q8_,
+                                          gmc_blob_report_) != MT_OK) {
+        err_ = bad ? bad : mtgpu_last_error();
+        (void)mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0);       // whatever fails here, no stale setting stays behind
+        (void)mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0);
+        (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);
         (void)mtgpu_pipe_set_keep(pipe_, nullptr);
         pipe_ = nullptr;
         return false;
@@ -1016,8 +1054,31 @@ struct PipelineResult {
   struct GmcVector { int gx, gy; uint64_t frames; };
   uint64_t gmc_moved_frames = 0;
   std::vector<GmcVector> gmc_top;
+  // The compensated blob scan (GpuMotionScanner::set_gmc_blobs / report_gmc_blobs; include/mtgpu_pipe_gmc_blobs.h).  In:
+  // gmc_blob_cells >= 1: on — `segments` are those of frames whose largest RESIDUAL blob has at least that many cells,
+  // under `keep` where there is one; -1: take gmc_blob_options(); 0: off whatever the options say.  gmc_blob_max_shift /
+  // gmc_blob_min_share_q8 (with gmc_blob_cells >= 1 or gmc_blob_sweep_levels).  gmc_blob_sweep_levels — every worker's
+  // pipe reports the largest residual blob in place of the centre count (the pipe has ONE count array: not together
+  // with keep_centres / sweep_levels), `centres` then holds {pts, largest} and `gmc_blob_sweep` = for every level L >=
+  // max(1, CLUSTERS_NEEDED) what this result's segments / merge would be with gmc_blob_cells = L, from the ONE decode
+  // pass.  Not together with min_blob_cells > 0, blob_sweep_levels, gmc_max_shift >= 0 or gmc_vectors.
+  int gmc_blob_cells = -1;
+  int gmc_blob_max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT;
+  int gmc_blob_min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
+  std::vector<int> gmc_blob_sweep_levels;
+  std::vector<SweepEntry> gmc_blob_sweep;              // SweepEntry::clusters_needed holds the level L
   std::string error;
 };
+
+// Process-wide defaults for PipelineResult::gmc_blob_cells / gmc_blob_max_shift / gmc_blob_min_share_q8 /
+// gmc_blob_sweep_levels (a front end's --gmc-blobs, --gmc-blobs-max-shift, --gmc-blobs-min-share-q8, --sweep-gmc-blobs):
+// set before the first pipeline starts, read by every run_scan_pipeline.  min_blob_cells 0 and no level: off.
+struct GmcBlobOptions {
+  int min_blob_cells = 0;
+  int max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT, min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
+  std::vector<int> sweep_levels;
+};
+inline GmcBlobOptions &gmc_blob_options() { static GmcBlobOptions o; return o; }
 
 // Process-wide defaults for PipelineResult::min_blob_cells / blob_sweep_levels (a front end's --min-blob-cells /
 // --sweep-blobs): set before the first pipeline starts, read by every run_scan_pipeline.
@@ -1101,7 +1162,44 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
     out.error = "gmc_vectors together with keep_centres / sweep_levels / blob_sweep_levels: the pipe has one count array";
     return 1;
   }
-  const bool keep_centres = out.keep_centres || centre_options().keep || !out.sweep_levels.empty() || report_largest || out.gmc_vectors;
+  // the compensated blob scan, the pipes' third mode: every conflict is answered here, before any decode
+  if (out.gmc_blob_cells == -1) {
+    out.gmc_blob_cells = gmc_blob_options().min_blob_cells;
+    out.gmc_blob_max_shift = gmc_blob_options().max_shift;
+    out.gmc_blob_min_share_q8 = gmc_blob_options().min_share_q8;
+    if (out.gmc_blob_sweep_levels.empty()) out.gmc_blob_sweep_levels = gmc_blob_options().sweep_levels;
+  }
+  const bool pair_largest = !out.gmc_blob_sweep_levels.empty();
+  const bool pair_on = out.gmc_blob_cells > 0 || pair_largest;
+  if (out.gmc_blob_cells < -1) { out.error = "gmc_blob_cells is " + std::to_string(out.gmc_blob_cells); return 1; }
+  if (pair_on) {
+    if (out.gmc_blob_max_shift < 0 || out.gmc_blob_max_shift > MTGPU_GMC_MAX_SHIFT || out.gmc_blob_min_share_q8 < 0 ||
+        out.gmc_blob_min_share_q8 > 256) {
+      out.error = "gmc_blob_max_shift must be in [0, 127] and gmc_blob_min_share_q8 in [0, 256]";
+      return 1;
+    }
+    if (out.min_blob_cells > 0 || report_largest) {
+      out.error = "gmc_blob_cells / gmc_blob_sweep_levels together with min_blob_cells / blob_sweep_levels: the compensated blob "
+                  "scan has its own minimum blob size";
+      return 1;
+    }
+    if (gmc_on || out.gmc_vectors) {
+      out.error = "gmc_blob_cells / gmc_blob_sweep_levels together with gmc_max_shift / gmc_vectors: the compensated blob scan "
+                  "has its own compensation";
+      return 1;
+    }
+    if (pair_largest && (out.keep_centres || centre_options().keep || !out.sweep_levels.empty())) {
+      out.error = "gmc_blob_sweep_levels together with keep_centres / sweep_levels: the pipe has one count array";
+      return 1;
+    }
+    for (int level : out.gmc_blob_sweep_levels)
+      if (level < std::max(1, (int)Config::clusters_needed())) {
+        out.error = "gmc blob sweep level " + std::to_string(level) + " is below max(1, CLUSTERS_NEEDED)";
+        return 1;
+      }
+  }
+  const bool keep_centres = out.keep_centres || centre_options().keep || !out.sweep_levels.empty() || report_largest || out.gmc_vectors ||
+                            pair_largest;
   std::mutex centres_mu;
   const auto wall0 = std::chrono::high_resolution_clock::now();
   std::mutex err_mu;
@@ -1143,6 +1241,8 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
         scanners[i]->report_largest(report_largest);
         scanners[i]->set_gmc(gmc_on ? out.gmc_max_shift : -1, out.gmc_min_share_q8);
         scanners[i]->report_vector(out.gmc_vectors);
+        scanners[i]->set_gmc_blobs(pair_on ? std::max(1, out.gmc_blob_cells) : 0, out.gmc_blob_max_shift, out.gmc_blob_min_share_q8);
+        scanners[i]->report_gmc_blobs(pair_largest ? MT_PIPE_REPORT_LARGEST : MT_PIPE_REPORT_CENTRES);
         if (!scanners[i]->initialize()) {                                // :198-199 (here: reported)
           fail_with(scanners[i]->error());
           return;
@@ -1220,9 +1320,9 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
     });
     if (out.gmc_top.size() > 8) out.gmc_top.resize(8);
   }
-  // the same merge on each level's timestamps: `centres` holds the centre counts (sweep_levels) or the largest blobs
-  // (blob_sweep_levels), never both
-  for (int level : report_largest ? out.blob_sweep_levels : out.sweep_levels) {
+  // the same merge on each level's timestamps: `centres` holds the centre counts (sweep_levels), the largest blobs
+  // (blob_sweep_levels) or the largest residual blobs (gmc_blob_sweep_levels), never two of them
+  for (int level : pair_largest ? out.gmc_blob_sweep_levels : report_largest ? out.blob_sweep_levels : out.sweep_levels) {
     PipelineResult::SweepEntry e;
     e.clusters_needed = level;
     const uint32_t need = level < 1 ? 1u : (uint32_t)level;              // motion_scanner.cpp:288
@@ -1232,7 +1332,7 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
     rc = mtgpu_merge_segments(merge_ctx, ts.data(), ts.size(), &mp, 1, e.segments.data(), e.segments.size(), &e.merge);
     if (rc != MT_OK) { out.error = mtgpu_last_error(); return 1; }
     e.segments.resize(e.merge.n_segments);
-    (report_largest ? out.blob_sweep : out.sweep).push_back(std::move(e));
+    (pair_largest ? out.gmc_blob_sweep : report_largest ? out.blob_sweep : out.sweep).push_back(std::move(e));
   }
   return 0;
 }

@@ -3,6 +3,7 @@
 //   mtgpu_scan_file stream.mtmv [more.mtmv ...] [--threads T] [--streams S] [--outdir DIR] [--timestamps] [--summary]
 //                   [--centres] [--sweep K1,K2,...] [--keep MASK.mtkeep] [--min-blob-cells N] [--sweep-blobs L1,L2,...]
 //                   [--gmc] [--gmc-max-shift N] [--gmc-min-share-q8 Q] [--gmc-vectors]
+//                   [--gmc-blobs N] [--gmc-blobs-max-shift S] [--gmc-blobs-min-share-q8 Q] [--sweep-gmc-blobs L1,L2,...]
 //   (--streams 0 / --threads 0: the reference's own sizing from PARALLEL_STREAMS / THREADS_PER_STREAM and the CPU limit)
 // One file: like `motion_trim in out` (single ProcessingPipeline).  Several files: like
 // `motion_trim in_dir out_dir` (BatchProcessor): S streams x T workers, jobs consumed by one
@@ -33,6 +34,15 @@
 // [[gx, gy, frames], ...] most frequent first}.  It combines with --keep, --centres and --sweep; --gmc-vectors does not
 // combine with --centres or --sweep (a pipe has one count array); none of it combines with --min-blob-cells N > 0 or
 // --sweep-blobs.  Without these options the output is unchanged.
+// --gmc-blobs N: the compensated blob scan (include/mtgpu_pipe_gmc_blobs.h), a shaking camera in the rain — a frame has
+// motion iff the centre count of its RESIDUAL vote reaches CLUSTERS_NEEDED AND the largest 4-connected blob of those
+// centres has at least N cells; --gmc-blobs-max-shift S (0 .. 127) and --gmc-blobs-min-share-q8 Q (0 .. 256) set its
+// compensation and are valid only next to --gmc-blobs or --sweep-gmc-blobs.  --sweep-gmc-blobs 3,8: the pipes report
+// every frame's largest residual blob; the job gains "largest" and "sweep_gmc_blobs", in the format of "sweep_blobs",
+// each level with the segments this tool prints when run with --gmc-blobs L.  It combines with --keep; --gmc-blobs
+// combines with --centres / --sweep, --sweep-gmc-blobs does not (a pipe has one count array); none of it combines with
+// --gmc, --gmc-max-shift, --gmc-min-share-q8, --gmc-vectors, --min-blob-cells N > 0 or --sweep-blobs.  Without these
+// options the output is unchanged.
 // --summary (several files): one more line {"batch_summary": ...} — frames scanned, wall time, worker-time
 // breakdown and what the S x T workers held (contexts, pipes, HIP streams, pinned / device bytes).
 #include <cmath>
@@ -92,6 +102,9 @@ static bool g_print_centres = false;   // --centres
 static std::string g_keep_path;        // --keep
 static bool g_print_largest = false;   // --sweep-blobs
 static bool g_print_gmc = false;       // --gmc-vectors
+static const char *g_pair_opt = nullptr;        // the first of --gmc-blobs N > 0 / --sweep-gmc-blobs given
+static const char *g_pair_param_opt = nullptr;  // the first of --gmc-blobs-max-shift / --gmc-blobs-min-share-q8 given
+static const char *g_gmc_opt = nullptr;         // the first option of the --gmc family given
 
 // The keep mask of g_keep_path for a width x height input; throws with load_keep's message (the line is named) when the
 // file is malformed or made for another grid.
@@ -143,7 +156,7 @@ static void print_job(const std::string &input, const PipelineResult &r, const s
     for (size_t i = 0; i < r.centres.size(); ++i) std::printf("%s[%.17g, %u]", i ? ", " : "", r.centres[i].first, r.centres[i].second);
     std::printf("]");
   }
-  if (g_print_largest) {
+  if (g_print_largest || !gmc_blob_options().sweep_levels.empty()) {
     std::printf(", \"largest\": [");
     for (size_t i = 0; i < r.centres.size(); ++i) std::printf("%s[%.17g, %u]", i ? ", " : "", r.centres[i].first, r.centres[i].second);
     std::printf("]");
@@ -169,6 +182,7 @@ static void print_job(const std::string &input, const PipelineResult &r, const s
   }
   if (!r.sweep.empty()) print_sweep("sweep", "clusters_needed", r.sweep);
   if (!r.blob_sweep.empty()) print_sweep("sweep_blobs", "min_blob_cells", r.blob_sweep);
+  if (!r.gmc_blob_sweep.empty()) print_sweep("sweep_gmc_blobs", "min_blob_cells", r.gmc_blob_sweep);
   std::printf("}\n");
   std::fflush(stdout);
 }
@@ -225,10 +239,51 @@ int main(int argc, char **argv) {
       }
       g_print_largest = true;
     }
+    else if (!std::strcmp(argv[i], "--gmc-blobs")) {
+      char *end = nullptr;
+      const long v = i + 1 < argc ? std::strtol(argv[i + 1], &end, 10) : -1;
+      if (i + 1 >= argc || end == argv[i + 1] || *end || v < 0 || v > 0x7fffffffL) {
+        std::fprintf(stderr, "error: --gmc-blobs takes a cell count >= 0\n");
+        return 2;
+      }
+      ++i;
+      gmc_blob_options().min_blob_cells = (int)v;
+      if (v > 0 && !g_pair_opt) g_pair_opt = "--gmc-blobs";
+    }
+    else if (!std::strcmp(argv[i], "--sweep-gmc-blobs")) {
+      const char *q = i + 1 < argc ? argv[++i] : "";
+      if (!*q) { std::fprintf(stderr, "error: --sweep-gmc-blobs takes a comma-separated list of integers\n"); return 2; }
+      while (*q) {
+        char *end = nullptr;
+        const long v = std::strtol(q, &end, 10);
+        if (end == q || (*end && (*end != ',' || !end[1])) || v > 0x7fffffffL || v < -0x7fffffffL) {
+          std::fprintf(stderr, "error: --sweep-gmc-blobs takes a comma-separated list of integers\n");
+          return 2;
+        }
+        gmc_blob_options().sweep_levels.push_back((int)v);
+        q = *end ? end + 1 : end;
+      }
+      if (!g_pair_opt) g_pair_opt = "--sweep-gmc-blobs";
+    }
+    else if (!std::strcmp(argv[i], "--gmc-blobs-max-shift") || !std::strcmp(argv[i], "--gmc-blobs-min-share-q8")) {
+      const bool shift = !std::strcmp(argv[i], "--gmc-blobs-max-shift");
+      const long hi = shift ? MTGPU_GMC_MAX_SHIFT : 256;
+      char *end = nullptr;
+      const long v = i + 1 < argc ? std::strtol(argv[i + 1], &end, 10) : -1;
+      if (i + 1 >= argc || end == argv[i + 1] || *end || v < 0 || v > hi) {
+        std::fprintf(stderr, "error: %s takes an integer in [0, %ld]\n", argv[i], hi);
+        return 2;
+      }
+      if (!g_pair_param_opt) g_pair_param_opt = argv[i];
+      ++i;
+      (shift ? gmc_blob_options().max_shift : gmc_blob_options().min_share_q8) = (int)v;
+    }
     else if (!std::strcmp(argv[i], "--gmc")) {
+      if (!g_gmc_opt) g_gmc_opt = argv[i];
       if (gmc_options().max_shift < 0) gmc_options().max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT;
     }
     else if (!std::strcmp(argv[i], "--gmc-vectors")) {
+      if (!g_gmc_opt) g_gmc_opt = argv[i];
       if (gmc_options().max_shift < 0) gmc_options().max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT;
       gmc_options().vectors = true;
       g_print_gmc = true;
@@ -242,6 +297,7 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "error: %s takes an integer in [0, %ld]\n", argv[i], hi);
         return 2;
       }
+      if (!g_gmc_opt) g_gmc_opt = argv[i];
       ++i;
       if (shift) gmc_options().max_shift = (int)v;
       else {
@@ -250,6 +306,37 @@ int main(int argc, char **argv) {
       }
     }
     else files.push_back(argv[i]);
+  }
+  // what the compensated blob scan cannot be combined with: answered here, before any device call
+  if (g_pair_param_opt && !g_pair_opt) {
+    std::fprintf(stderr, "error: %s is valid only next to --gmc-blobs or --sweep-gmc-blobs\n", g_pair_param_opt);
+    return 2;
+  }
+  if (g_pair_opt) {
+    if (g_gmc_opt) {
+      std::fprintf(stderr, "error: %s cannot be combined with %s: the compensated blob scan has its own compensation "
+                   "(--gmc-blobs-max-shift, --gmc-blobs-min-share-q8)\n", g_pair_opt, g_gmc_opt);
+      return 2;
+    }
+    if (blob_options().min_blob_cells > 0 || g_print_largest) {
+      std::fprintf(stderr, "error: %s cannot be combined with %s: the compensated blob scan has its own minimum blob size\n",
+                   g_pair_opt, g_print_largest ? "--sweep-blobs" : "--min-blob-cells");
+      return 2;
+    }
+    if (!gmc_blob_options().sweep_levels.empty()) {
+      if (g_print_centres || !centre_options().sweep_levels.empty()) {
+        std::fprintf(stderr, "error: --sweep-gmc-blobs cannot be combined with --centres or --sweep: a pipe has one count array\n");
+        return 2;
+      }
+      int need = 1;
+      try { need = std::max(1, Config::clusters_needed()); }
+      catch (const std::exception &e) { std::fprintf(stderr, "error: configuration: %s\n", e.what()); return 1; }
+      for (int level : gmc_blob_options().sweep_levels)
+        if (level < need) {
+          std::fprintf(stderr, "error: --sweep-gmc-blobs level %d is below max(1, CLUSTERS_NEEDED) = %d\n", level, need);
+          return 2;
+        }
+    }
   }
   // what compensation cannot be combined with: answered here, before any device call
   if (gmc_options().max_shift >= 0) {

@@ -2691,3 +2691,100 @@ int mtgpu_scan_frames_gmc_blobs(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *f
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- the compensated blob scan on the decode path
+// (include/mtgpu_pipe_gmc_blobs.h): the pipe form of the launch above, for pipe.hip
+
+namespace {
+
+static_assert(MT_PIPE_REPORT_CENTRES == mtgpu::kGmcBlobReportCentres && MT_PIPE_REPORT_LARGEST == mtgpu::kGmcBlobReportLargest &&
+              MT_PIPE_REPORT_VECTOR == mtgpu::kGmcBlobReportVector, "the kernel's report values are the ABI's");
+
+// The compensated blob scan of a pipe's staging batch on `st`.  The arguments have been validated; n_frames > 0.  The
+// work list lies in the caller's own block: nothing comes from the context's scratch ring.
+int gmc_blobs_pipe_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
+                      uint32_t n_frames, const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells,
+                      int report, uint8_t *d_flags, uint32_t *d_count, hipStream_t st, void *own_plan_ws, int outputs_in_host_memory) {
+  mtgpu_gmc_blobs_plan gp;
+  int rc = gmc_blobs_plan(c->params, c->lds_max, &gp);
+  if (rc != MT_OK) return rc;
+  mtgpu::GmcBlobLaunch L;
+  L.mv = static_cast<const unsigned char *>(d_rec);
+  L.n_records = n_records;
+  L.rebase = 0;
+  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
+  L.has_sd = d_sd;
+  L.n_frames = n_frames;
+  L.rec_bytes = rec_bytes;
+  L.stream_off = nullptr;
+  L.n_streams = 0;
+  L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
+  L.flags = d_flags; L.centres = d_count; L.blobs = nullptr; L.largest = nullptr;
+  L.box = nullptr;
+  L.info = nullptr;
+  L.pipe = 1;
+  L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
+  L.sys_count = (d_count && outputs_in_host_memory) ? 1 : 0;
+  L.report = report;
+  mtgpu::GmcBlobK &k = L.k;
+  std::memset(&k, 0, sizeof k);
+  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.clust_need = c->k.clust_need;
+  k.blob_need = min_blob_cells < 1 ? 1u : (unsigned int)min_blob_cells;
+  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
+  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
+  k.tile_words = (int)mtgpu::blob_tile_words(k.gw, k.R);
+  k.max_shift = (int)max_shift;
+  k.min_share_q8 = (unsigned int)min_share_q8;
+  L.lds_bytes = gp.lds_bytes;
+  L.lds_max = c->lds_max;
+  L.device = c->device;
+  L.stream = st;
+  L.ev_planned = nullptr;
+  L.plan_ws = own_plan_ws;
+  hipError_t e = hipSuccess;
+  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
+    mtgpu_ctx::Profile &pf = c->prof;
+    std::lock_guard<std::mutex> lock(pf.mu);
+    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
+    if (e == hipSuccess && pf.created) {
+      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
+      e = hipEventRecord(t[0], st);
+      L.ev_planned = t[1];
+      if (e == hipSuccess) e = mtgpu::launch_gmc_blob_scan(L);
+      if (e == hipSuccess) e = hipEventRecord(t[2], st);
+      if (e == hipSuccess) ++pf.count;
+    } else if (e == hipSuccess) {
+      e = mtgpu::launch_gmc_blob_scan(L);
+    }
+  } else {
+    e = mtgpu::launch_gmc_blob_scan(L);
+  }
+  if (e != hipSuccess) return hip_fail(e, "compensated blob pipe scan launch");
+  return MT_OK;
+}
+
+}  // namespace
+
+namespace mtgpu {
+int ctx_launch_gmc_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
+                         uint32_t n_frames, const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells,
+                         int report, uint8_t *d_flags, uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory,
+                         void *plan_ws, size_t plan_ws_bytes) {
+  if (n_frames == 0) return MT_OK;
+  const int rc = gmc_check_settings(max_shift, min_share_q8);
+  if (rc != MT_OK) return rc;
+  if (min_blob_cells < 1) return fail(MT_ERR_INVALID, "compensated blob pipe scan: min_blob_cells is %d, want >= 1", (int)min_blob_cells);
+  if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_LARGEST && report != MT_PIPE_REPORT_VECTOR)
+    return fail(MT_ERR_INVALID, "compensated blob pipe scan: report is %d", report);
+  if (report != MT_PIPE_REPORT_CENTRES && !d_count)
+    return fail(MT_ERR_INVALID, "compensated blob pipe scan: the largest and the vector report need the batch's count array");
+  if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
+    return fail(MT_ERR_INVALID, "compensated blob pipe scan: the batch's work-list block is missing, misaligned or too small");
+  return gmc_blobs_pipe_on(c, d_rec, rec_bytes, n_records, d_off, d_sd, n_frames, d_keep, max_shift, min_share_q8, min_blob_cells,
+                           report, d_flags, d_count, st, plan_ws, outputs_in_host_memory ? 1 : 0);
+}
+int ctx_gmc_blobs_supported(const mtgpu_ctx *c) {
+  mtgpu_gmc_blobs_plan gp;
+  return gmc_blobs_plan(c->params, c->lds_max, &gp);
+}
+}  // namespace mtgpu

@@ -118,6 +118,12 @@ struct mtgpu_pipe {
   int gmc = 0;
   int32_t gmc_max_shift = 0, gmc_min_share_q8 = 0;
   int gmc_report = 0;
+  // mtgpu_pipe_set_gmc_blobs (include/mtgpu_pipe_gmc_blobs.h): pair_blob > 0: every submit runs the compensated blob scan
+  // (ctx_launch_gmc_blobs), under the keep plane when `masked`; pair_report: MT_PIPE_REPORT_*.  A third mode: never
+  // together with min_blob > 0 or gmc.  They change only while no batch is being filled or in flight.
+  int32_t pair_blob = 0;
+  int32_t pair_max_shift = 0, pair_min_share_q8 = 0;
+  int pair_report = 0;
   std::vector<mtgpu_batch *> bufs;
   std::deque<mtgpu_batch *> inflight;
   std::mutex mu;
@@ -403,7 +409,11 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
       rc = fail(MT_ERR_DEVICE, "injected submit failure (MTGPU_INJECT_SUBMIT_FAIL)");
       goto bad;
     }
-    if (p->gmc)   // mtgpu_pipe_set_gmc: the compensated scan, estimate and vote under the pipe's keep plane when it has a mask
+    if (p->pair_blob > 0)   // mtgpu_pipe_set_gmc_blobs: the compensated blob scan, under the pipe's keep plane when it has a mask
+      rc = mtgpu::ctx_launch_gmc_blobs(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
+                                       p->pair_max_shift, p->pair_min_share_q8, p->pair_blob, p->pair_report, b->d_flags,
+                                       b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
+    else if (p->gmc)   // mtgpu_pipe_set_gmc: the compensated scan, estimate and vote under the pipe's keep plane when it has a mask
       rc = mtgpu::ctx_launch_gmc(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
                                  p->gmc_max_shift, p->gmc_min_share_q8, p->gmc_report == MT_PIPE_REPORT_VECTOR ? 1 : 0, b->d_flags,
                                  b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
@@ -563,6 +573,9 @@ int mtgpu_pipe_set_blobs(mtgpu_pipe *p, int32_t min_blob_cells, int report) {
       return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the blob setting",
                   b->state == 1 ? "being filled" : "in flight");
   if (min_blob_cells == 0) { p->min_blob = 0; p->report = 0; return MT_OK; }
+  if (p->pair_blob > 0)
+    return fail(MT_ERR_INVALID, "this pipe runs the compensated blob scan (mtgpu_pipe_set_gmc_blobs): turn it off first, or change "
+                "min_blob_cells through mtgpu_pipe_set_gmc_blobs");
   if (p->gmc)
     return fail(MT_ERR_UNSUPPORTED, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): blobs and compensation are "
                 "not together yet");
@@ -599,6 +612,9 @@ int mtgpu_pipe_set_gmc(mtgpu_pipe *p, int enable, int32_t max_shift, int32_t min
       return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the compensation setting",
                   b->state == 1 ? "being filled" : "in flight");
   if (!enable) { p->gmc = 0; p->gmc_max_shift = 0; p->gmc_min_share_q8 = 0; p->gmc_report = 0; return MT_OK; }
+  if (p->pair_blob > 0)
+    return fail(MT_ERR_INVALID, "this pipe runs the compensated blob scan (mtgpu_pipe_set_gmc_blobs): turn it off first, or change "
+                "the compensation through mtgpu_pipe_set_gmc_blobs");
   if (p->min_blob > 0)
     return fail(MT_ERR_UNSUPPORTED, "this pipe runs the blob scan (mtgpu_pipe_set_blobs): blobs and compensation are not "
                 "together yet");
@@ -618,6 +634,52 @@ int mtgpu_pipe_gmc(const mtgpu_pipe *p, int32_t *max_shift, int32_t *min_share_q
   if (max_shift) *max_shift = p->gmc_max_shift;
   if (min_share_q8) *min_share_q8 = p->gmc_min_share_q8;
   if (report) *report = p->gmc_report;
+  return 1;
+}
+
+int mtgpu_pipe_set_gmc_blobs(mtgpu_pipe *p, int32_t min_blob_cells, int32_t max_shift, int32_t min_share_q8, int report) {
+  if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
+  if (min_blob_cells < 0) return fail(MT_ERR_INVALID, "min_blob_cells is %d: want 0 (off) or a cell count >= 1", (int)min_blob_cells);
+  if (min_blob_cells > 0) {
+    if (max_shift < 0 || max_shift > MTGPU_GMC_MAX_SHIFT)
+      return fail(MT_ERR_INVALID, "max_shift must be in [0, %d], not %d", MTGPU_GMC_MAX_SHIFT, (int)max_shift);
+    if (min_share_q8 < 0 || min_share_q8 > 256) return fail(MT_ERR_INVALID, "min_share_q8 must be in [0, 256], not %d", (int)min_share_q8);
+    if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_LARGEST && report != MT_PIPE_REPORT_VECTOR)
+      return fail(MT_ERR_INVALID, "report is %d: want MT_PIPE_REPORT_CENTRES, MT_PIPE_REPORT_LARGEST or MT_PIPE_REPORT_VECTOR", report);
+    if (report != MT_PIPE_REPORT_CENTRES && !p->centres)
+      return fail(MT_ERR_INVALID, "%s needs a pipe with MT_LAYOUT_CENTRES: the %s travels in its count array",
+                  report == MT_PIPE_REPORT_LARGEST ? "MT_PIPE_REPORT_LARGEST" : "MT_PIPE_REPORT_VECTOR",
+                  report == MT_PIPE_REPORT_LARGEST ? "largest blob" : "applied vector");
+  }
+  std::lock_guard<std::mutex> lock(p->mu);
+  for (const mtgpu_batch *b : p->bufs)
+    if (b->state == 1 || b->state == 2)
+      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the compensated "
+                  "blob setting", b->state == 1 ? "being filled" : "in flight");
+  if (min_blob_cells == 0) { p->pair_blob = 0; p->pair_max_shift = 0; p->pair_min_share_q8 = 0; p->pair_report = 0; return MT_OK; }
+  if (p->min_blob > 0)
+    return fail(MT_ERR_INVALID, "this pipe runs the blob scan (mtgpu_pipe_set_blobs): turn it off first "
+                "(mtgpu_pipe_set_blobs(pipe, 0, 0)), then call mtgpu_pipe_set_gmc_blobs");
+  if (p->gmc)
+    return fail(MT_ERR_INVALID, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): turn it off first "
+                "(mtgpu_pipe_set_gmc(pipe, 0, 0, 0, 0)), then call mtgpu_pipe_set_gmc_blobs");
+  const int rc = mtgpu::ctx_gmc_blobs_supported(p->ctx);     // MT_ERR_UNSUPPORTED, the grid named: nothing changes
+  if (rc != MT_OK) return rc;
+  p->pair_blob = min_blob_cells;
+  p->pair_max_shift = max_shift;
+  p->pair_min_share_q8 = min_share_q8;
+  p->pair_report = report;
+  return MT_OK;
+}
+
+int mtgpu_pipe_gmc_blobs(const mtgpu_pipe *p, int32_t *min_blob_cells, int32_t *max_shift, int32_t *min_share_q8, int *report) {
+  if (!p) return -1;
+  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
+  if (p->pair_blob <= 0) return 0;
+  if (min_blob_cells) *min_blob_cells = p->pair_blob;
+  if (max_shift) *max_shift = p->pair_max_shift;
+  if (min_share_q8) *min_share_q8 = p->pair_min_share_q8;
+  if (report) *report = p->pair_report;
   return 1;
 }
 

@@ -1153,6 +1153,36 @@ class ScanPipe:
             return None
         return int(ms.value), int(q8.value), ("vector" if r.value == _abi.MT_PIPE_REPORT_VECTOR else "centres")
 
+    _PAIR_REPORTS = {"centres": _abi.MT_PIPE_REPORT_CENTRES, "largest": _abi.MT_PIPE_REPORT_LARGEST,
+                     "vector": _abi.MT_PIPE_REPORT_VECTOR}
+
+    def set_gmc_blobs(self, min_blob_cells: int, max_shift: int = _abi.GMC_DEFAULT_MAX_SHIFT,
+                      min_share_q8: int = _abi.GMC_DEFAULT_MIN_SHARE_Q8, report: str = "centres"):
+        """The compensated blob scan on the decode path (mtgpu_pipe_set_gmc_blobs), the pipe's third mode: from now on
+        every batch runs motion blobs on the residuals of each frame's dominant vector — flag = centres >=
+        max(1, clusters_needed) AND largest blob >= min_blob_cells — under the keep mask if the pipe has one.
+        min_blob_cells 0: off.  report: what drain_centres() returns per frame, "centres", "largest" or "vector"
+        (unpack_gmc_vector); the last two need centres=True.  Only while no batch is being filled or in flight:
+        otherwise MtgpuError(MT_ERR_BUSY) and nothing changes.  Not while set_blobs or set_gmc is on, nor they while
+        this is: MtgpuError(MT_ERR_INVALID)."""
+        if report not in self._PAIR_REPORTS:
+            raise ValueError(f"report is {report!r}, not 'centres', 'largest' or 'vector'")
+        check(self._lib.mtgpu_pipe_set_gmc_blobs(self._pipe, int(min_blob_cells), int(max_shift), int(min_share_q8),
+                                                 self._PAIR_REPORTS[report]))
+
+    def clear_gmc_blobs(self):
+        """The compensated blob scan off (mtgpu_pipe_set_gmc_blobs with min_blob_cells 0): the pipe as it was before."""
+        check(self._lib.mtgpu_pipe_set_gmc_blobs(self._pipe, 0, 0, 0, 0))
+
+    def gmc_blobs(self) -> Optional[Tuple[int, int, int, str]]:
+        """None, or (min_blob_cells, max_shift, min_share_q8, report) while the pipe's submits run the compensated blob
+        scan (mtgpu_pipe_gmc_blobs)."""
+        n, ms, q8, r = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int()
+        if self._lib.mtgpu_pipe_gmc_blobs(self._pipe, C.byref(n), C.byref(ms), C.byref(q8), C.byref(r)) != 1:
+            return None
+        names = {v: k for k, v in self._PAIR_REPORTS.items()}
+        return int(n.value), int(ms.value), int(q8.value), names[r.value]
+
     @staticmethod
     def unpack_gmc_vector(word: int) -> Tuple[int, int]:
         """(gx, gy) of a count reported under set_gmc(report="vector"): two signed 16-bit halves."""
