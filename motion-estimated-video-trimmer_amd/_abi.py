@@ -98,6 +98,10 @@ class GmcBlobsPlanC(C.Structure):
                 ("keep_words_per_stream", C.c_int32), ("hist_bins", C.c_int32), ("info_bytes", C.c_int32)]
 
 
+class PersistPlanC(C.Structure):
+    _fields_ = [("workgroup", C.c_int32), ("frames_per_tile", C.c_int32)]
+
+
 class CtxStatsC(C.Structure):
     _fields_ = [("staging_device_bytes", C.c_uint64), ("pool_reserved_bytes", C.c_uint64),
                 ("pool_reserved_high", C.c_uint64), ("hip_streams", C.c_uint32), ("private_pool", C.c_uint32)]
@@ -267,6 +271,17 @@ ABI_PIPE_GMC_BLOBS = {
     "mtgpu_pipe_gmc_blobs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_persist.h declares (temporal persistence; mtgpu.h includes it).
+ABI_PERSIST = {
+    "mtgpu_persist_preview": (C.c_int, [C.POINTER(PersistPlanC)]),
+    "mtgpu_persist_flags_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "mtgpu_persist_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+PERSIST_NO_DROPOUT_LIMIT = 0xFFFFFFFF
+
 _lib = None
 
 
@@ -299,7 +314,7 @@ def load_library(path=None):
     for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
             list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
             list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()) + list(ABI_GMC_BLOBS.items()) + \
-            list(ABI_PIPE_GMC_BLOBS.items()):
+            list(ABI_PIPE_GMC_BLOBS.items()) + list(ABI_PERSIST.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -28,6 +28,7 @@
 #include "blobs_kernels.h"
 #include "gmc_kernels.h"
 #include "gmc_blobs_kernels.h"
+#include "persist_kernels.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -2788,3 +2789,140 @@ int ctx_gmc_blobs_supported(const mtgpu_ctx *c) {
   return gmc_blobs_plan(c->params, c->lds_max, &gp);
 }
 }  // namespace mtgpu
+
+// ---------------------------------------------------------------- temporal persistence (include/mtgpu_persist.h)
+
+namespace {
+
+static_assert(sizeof(mtgpu::PersistBox) == sizeof(mt_blob_box), "the kernel's box is the ABI's");
+
+struct PersistRange { const char *name; const void *p; size_t bytes; };
+
+// What the arguments of a persistence call decide alone (`d`: "d_" for the device entry point, "" for the host one):
+// no context, no device.
+int persist_check_args(const char *d, const void *flags, const void *has_sd, const void *box, uint32_t n_frames,
+                       const void *stream_off, uint32_t n_streams, uint32_t reach, const void *work, bool need_work,
+                       const void *flags_out, const void *run, const void *pos) {
+  if (!flags_out && !run && !pos) return fail(MT_ERR_INVALID, "%sflags_out, %srun and %spos are all NULL", d, d, d);
+  if (reach > 65535u) return fail(MT_ERR_INVALID, "reach %u outside [0,65535]", reach);
+  if (n_frames > 0 && !flags) return fail(MT_ERR_INVALID, "%sflags is NULL", d);
+  if (n_frames > 0 && !stream_off) return fail(MT_ERR_INVALID, "%sstream_off is NULL", d);
+  if (n_frames > 0 && need_work && !work) return fail(MT_ERR_INVALID, "%swork is NULL", d);
+  if (n_frames > 0 && n_streams == 0) return fail(MT_ERR_INVALID, "n_streams is 0 with n_frames %u", n_frames);
+  if (((uintptr_t)stream_off & 7u) != 0) return fail(MT_ERR_INVALID, "%sstream_off must be 8-byte aligned", d);
+  if (((uintptr_t)box & 1u) != 0) return fail(MT_ERR_INVALID, "%sbox must be 2-byte aligned", d);
+  if (((uintptr_t)work & 3u) != 0) return fail(MT_ERR_INVALID, "%swork must be 4-byte aligned", d);
+  if (((uintptr_t)run & 3u) != 0) return fail(MT_ERR_INVALID, "%srun must be 4-byte aligned", d);
+  if (((uintptr_t)pos & 3u) != 0) return fail(MT_ERR_INVALID, "%spos must be 4-byte aligned", d);
+  // no in-place form: an output or the workspace shares no byte with an input or with another of them
+  const size_t n = n_frames;
+  const PersistRange r[8] = {{"flags", flags, n}, {"has_sd", has_sd, n}, {"box", box, n * sizeof(mt_blob_box)},
+                             {"stream_off", stream_off, ((size_t)n_streams + 1) * sizeof(uint64_t)},
+                             {"work", work, n * sizeof(uint32_t)}, {"flags_out", flags_out, n},
+                             {"run", run, n * sizeof(uint32_t)}, {"pos", pos, n * sizeof(uint32_t)}};
+  for (int i = 4; i < 8 && n > 0; ++i) {                      // r[4 ..]: the workspace and the outputs
+    if (!r[i].p) continue;
+    for (int j = 0; j < i; ++j) {
+      if (!r[j].p) continue;
+      const uintptr_t a0 = (uintptr_t)r[i].p, a1 = a0 + r[i].bytes, b0 = (uintptr_t)r[j].p, b1 = b0 + r[j].bytes;
+      if (a0 < b1 && b0 < a1) return fail(MT_ERR_INVALID, "%s%s overlaps %s%s: there is no in-place form", d, r[i].name, d, r[j].name);
+    }
+  }
+  return MT_OK;
+}
+
+int persist_on(const uint8_t *d_flags, const uint8_t *d_sd, const mt_blob_box *d_box, uint32_t n_frames, const uint64_t *d_stream_off,
+               uint32_t n_streams, uint32_t min_run, uint32_t max_dropout, uint32_t reach, uint32_t *d_work, uint8_t *d_flags_out,
+               uint32_t *d_run, uint32_t *d_pos, hipStream_t st) {
+  mtgpu::PersistLaunch L;
+  L.flags = d_flags;
+  L.has_sd = d_sd;
+  L.box = reinterpret_cast<const mtgpu::PersistBox *>(d_box);
+  L.n_frames = n_frames;
+  L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
+  L.n_streams = n_streams;
+  L.need = min_run < 1u ? 1u : min_run;
+  L.max_dropout = max_dropout;
+  L.reach = d_box ? reach : 0u;
+  L.work = d_work;
+  L.flags_out = d_flags_out;
+  L.run = d_run;
+  L.pos = d_pos;
+  L.stream = st;
+  const hipError_t e = mtgpu::launch_persist(L);
+  if (e != hipSuccess) return hip_fail(e, "persistence launch");
+  return MT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtgpu_persist_preview(mtgpu_persist_plan *out) {
+  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
+  out->workgroup = mtgpu::kPersistBlock;
+  out->frames_per_tile = mtgpu::kPersistTile;
+  return MT_OK;
+}
+
+int mtgpu_persist_flags_device(mtgpu_ctx *c, const uint8_t *d_flags, const uint8_t *d_has_sd, const mt_blob_box *d_box, uint32_t n_frames,
+                               const uint64_t *d_stream_off, uint32_t n_streams, uint32_t min_run, uint32_t max_dropout, uint32_t reach,
+                               uint32_t *d_work, uint8_t *d_flags_out, uint32_t *d_run, uint32_t *d_pos, void *stream) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  int rc = persist_check_args("d_", d_flags, d_has_sd, d_box, n_frames, d_stream_off, n_streams, reach, d_work, true, d_flags_out,
+                              d_run, d_pos);
+  if (rc != MT_OK) return rc;
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  if (n_frames == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!on_ctx_device(c, d_work)) return fail(MT_ERR_INVALID, "d_work is not memory of device %d", c->device);
+  if (d_flags_out && !on_ctx_device(c, d_flags_out)) return fail(MT_ERR_INVALID, "d_flags_out is not memory of device %d", c->device);
+  if (d_run && !on_ctx_device(c, d_run)) return fail(MT_ERR_INVALID, "d_run is not memory of device %d", c->device);
+  if (d_pos && !on_ctx_device(c, d_pos)) return fail(MT_ERR_INVALID, "d_pos is not memory of device %d", c->device);
+  return persist_on(d_flags, d_has_sd, d_box, n_frames, d_stream_off, n_streams, min_run, max_dropout, reach, d_work, d_flags_out,
+                    d_run, d_pos, static_cast<hipStream_t>(stream));
+}
+
+int mtgpu_persist_flags(mtgpu_ctx *c, const uint8_t *flags, const uint8_t *has_sd, const mt_blob_box *box, uint32_t n_frames,
+                        const uint64_t *stream_off, uint32_t n_streams, uint32_t min_run, uint32_t max_dropout, uint32_t reach,
+                        uint8_t *flags_out, uint32_t *run, uint32_t *pos) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  int rc = persist_check_args("", flags, has_sd, box, n_frames, stream_off, n_streams, reach, nullptr, false, flags_out, run, pos);
+  if (rc != MT_OK) return rc;
+  if (n_frames > 0) {
+    for (uint32_t s = 0; s < n_streams; ++s)
+      if (stream_off[s + 1] < stream_off[s]) return fail(MT_ERR_INVALID, "stream_off not monotonic at stream %u", s);
+    if (stream_off[n_streams] > (uint64_t)n_frames)
+      return fail(MT_ERR_INVALID, "stream_off[%u] is %llu, above n_frames %u", n_streams, (unsigned long long)stream_off[n_streams], n_frames);
+  }
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  if (n_frames == 0) return MT_OK;
+
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = n_frames, words = sizeof(uint32_t) * n, soff_bytes = sizeof(uint64_t) * ((size_t)n_streams + 1);
+  const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
+  const size_t o_soff = 0, o_fl = o_soff + up(soff_bytes), o_sd = o_fl + up(n), o_box = o_sd + (has_sd ? up(n) : 0),
+               o_work = o_box + (box ? up(sizeof(mt_blob_box) * n) : 0), o_out = o_work + up(words), o_run = o_out + (flags_out ? up(n) : 0),
+               o_pos = o_run + (run ? up(words) : 0), total = o_pos + (pos ? up(words) : 0);
+  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
+  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
+  hipStream_t st = c->stream;
+  DrainOnExit drain{st};
+  HIP_TRY(hipMemcpyAsync(d + o_soff, stream_off, soff_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d + o_fl, flags, n, hipMemcpyHostToDevice, st));
+  if (has_sd) HIP_TRY(hipMemcpyAsync(d + o_sd, has_sd, n, hipMemcpyHostToDevice, st));
+  if (box) HIP_TRY(hipMemcpyAsync(d + o_box, box, sizeof(mt_blob_box) * n, hipMemcpyHostToDevice, st));
+  rc = persist_on(d + o_fl, has_sd ? d + o_sd : nullptr, box ? reinterpret_cast<const mt_blob_box *>(d + o_box) : nullptr, n_frames,
+                  reinterpret_cast<const uint64_t *>(d + o_soff), n_streams, min_run, max_dropout, reach,
+                  reinterpret_cast<uint32_t *>(d + o_work), flags_out ? d + o_out : nullptr,
+                  run ? reinterpret_cast<uint32_t *>(d + o_run) : nullptr, pos ? reinterpret_cast<uint32_t *>(d + o_pos) : nullptr, st);
+  if (rc != MT_OK) return rc;
+  if (flags_out) HIP_TRY(hipMemcpyAsync(flags_out, d + o_out, n, hipMemcpyDeviceToHost, st));
+  if (run) HIP_TRY(hipMemcpyAsync(run, d + o_run, words, hipMemcpyDeviceToHost, st));
+  if (pos) HIP_TRY(hipMemcpyAsync(pos, d + o_pos, words, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MT_OK;
+}
+
+}  // extern "C"

@@ -22,7 +22,7 @@ import numpy as np
 from . import _abi, config
 from ._abi import (BLOB_BOX_DTYPE, BlobsPlanC, COMPACT_DTYPE, LAYOUT_AOS40, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
                    GMC_DEFAULT_MAX_SHIFT, GMC_DEFAULT_MIN_SHARE_Q8, GMC_INFO_DTYPE, GmcBlobsPlanC, GmcPlanC,
-                   MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PlanC, ScanParamsC, SweepPlanC, ZonesPlanC, check,
+                   MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PersistPlanC, PlanC, ScanParamsC, SweepPlanC, ZonesPlanC, check,
                    load_library)
 
 
@@ -246,7 +246,16 @@ def gmc_blobs_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     return {n: getattr(p, n) for n, _ in GmcBlobsPlanC._fields_}
 
 
+def persist_preview() -> dict:
+    """How the persistence pass runs (mtgpu_persist_preview): lanes per workgroup and the frames a workgroup takes per
+    step.  Host only: works without a GPU."""
+    p = PersistPlanC()
+    check(load_library().mtgpu_persist_preview(C.byref(p)))
+    return {n: getattr(p, n) for n, _ in PersistPlanC._fields_}
+
+
 ACTIVITY_OUTPUTS = ("active", "centre", "frames")
+PERSIST_OUTPUTS = ("flags", "run", "pos")
 BLOB_OUTPUTS = ("flags", "centres", "blobs", "largest", "box")
 GMC_BLOB_OUTPUTS = BLOB_OUTPUTS + ("info",)
 
@@ -860,6 +869,78 @@ class MotionScanner:
             self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
             None if d_sd is None else d_sd.data_ptr(), n_frames, ptr(d_stream_off), ns, ptr(d_keep), int(max_shift),
             int(min_share_q8), int(min_blob_cells), *(ptr(res[k]) for k in GMC_BLOB_OUTPUTS), st))
+        return res
+
+    # -------------------------------------------------------- temporal persistence
+    def persist(self, flags, stream_off, has_sd=None, box=None, min_run: int = 1, max_dropout: int = 0, reach: int = 1) -> dict:
+        """The runs of motion frames of a host batch (mtgpu_persist_flags, include/mtgpu_persist.h).  flags: uint8 [F]
+        from any scan (non-zero: a motion frame); stream_off: [S + 1] frame offsets; has_sd uint8 [F] or None: a quiet
+        frame without side data (a key frame) is transparent, it neither breaks a run nor counts as a dropout; box
+        BLOB_BOX_DTYPE [F] or None: consecutive motion frames stay in one run only while their largest blobs' boxes lie
+        within `reach` cells of each other; max_dropout: the quiet analysed frames a run bridges.  Returns a dict of
+        numpy arrays over the frames: flags uint8 (flags != 0 and run >= max(1, min_run)), run uint32 (motion frames in
+        the frame's run, 0 on a quiet frame), pos uint32 (1-based place in the run)."""
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
+        n, ns = len(fl), max(len(soff) - 1, 0)
+        sd = None if has_sd is None else np.ascontiguousarray(has_sd, dtype=np.uint8)
+        bx = None if box is None else np.ascontiguousarray(box, dtype=BLOB_BOX_DTYPE)
+        if (sd is not None and len(sd) != n) or (bx is not None and len(bx) != n):
+            raise ValueError("has_sd and box have one element per frame")
+        out = {"flags": np.zeros(n, dtype=np.uint8), "run": np.zeros(n, dtype=np.uint32), "pos": np.zeros(n, dtype=np.uint32)}
+        check(self._lib.mtgpu_persist_flags(self._ctx, _ptr(fl), _ptr(sd), _ptr(bx), n, _ptr(soff) if len(soff) else None, ns,
+                                            int(min_run), int(max_dropout), int(reach), *(_ptr(out[k]) for k in PERSIST_OUTPUTS)))
+        return out
+
+    def persist_device(self, d_flags, d_stream_off, d_has_sd=None, d_box=None, min_run: int = 1, max_dropout: int = 0,
+                       reach: int = 1, want=PERSIST_OUTPUTS, out=None, work=None, stream=None) -> dict:
+        """Device-resident batch (torch CUDA tensors) -> a dict of CUDA tensors over the frames: flags uint8, run / pos
+        int32 (the bits of the library's uint32 counts); None for an output not in `want`.  d_flags uint8 [F];
+        d_stream_off int64 [S + 1]; d_has_sd uint8 [F] or None; d_box int16 [F, 4] as scan_blobs_device returns it, or
+        None.  `run` is ready for sweep_streams_device: level L there is flags at min_run = L.  out: a dict of
+        preallocated tensors by name; work: int32 [F] workspace of the caller (else one is allocated and held until the
+        launch has passed).  No output may share memory with an input.  Asynchronous on `stream` (default: torch's
+        current stream)."""
+        import torch
+        want = tuple(want)
+        for w in want:
+            if w not in PERSIST_OUTPUTS:
+                raise ValueError(f"want: {w!r} is not one of {PERSIST_OUTPUTS}")
+        dev = d_flags.device
+        n_frames = d_flags.numel()
+        res = {}
+        for name in PERSIST_OUTPUTS:
+            if name not in want:
+                res[name] = None
+                continue
+            dtype = torch.uint8 if name == "flags" else torch.int32
+            t = (out or {}).get(name)
+            if t is None:
+                t = torch.empty(n_frames, dtype=dtype, device=dev)
+            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (n_frames,), name
+            res[name] = t
+        if n_frames == 0:              # nothing to write (an empty tensor has no address to hand over)
+            return res
+        assert d_flags.dtype == torch.uint8 and d_flags.is_contiguous()
+        assert d_stream_off.dtype == torch.int64 and d_stream_off.is_contiguous()
+        assert d_has_sd is None or (d_has_sd.dtype == torch.uint8 and d_has_sd.is_contiguous() and d_has_sd.numel() == n_frames)
+        assert d_box is None or (d_box.dtype == torch.int16 and d_box.is_contiguous() and tuple(d_box.shape) == (n_frames, 4))
+        held = work is None
+        if held:
+            work = torch.empty(n_frames, dtype=torch.int32, device=dev)
+        assert work.dtype == torch.int32 and work.is_contiguous() and work.numel() >= n_frames
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+        check(self._lib.mtgpu_persist_flags_device(
+            self._ctx, d_flags.data_ptr(), ptr(d_has_sd), ptr(d_box), n_frames, d_stream_off.data_ptr(),
+            max(d_stream_off.numel() - 1, 0), int(min_run), int(max_dropout), int(reach), work.data_ptr(),
+            *(ptr(res[k]) for k in PERSIST_OUTPUTS), st))
+        if held:
+            # (the workspace outlives the queued kernels: see merge_streams_device)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev))
+            self._held = [(e, w) for e, w in getattr(self, "_held", []) if not e.query()]
+            self._held.append((ev, work))
         return res
 
     # ------------------------------------------------------- motion scalar
