@@ -485,6 +485,11 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * batch, under the pipe's keep mask where it has one — two more entry points, declared the same way. */
 #include "mtgpu_pipe_gmc_blobs.h"
 
+/* The largest blob's box on the decode path: MT_LAYOUT_BOXES, a pipe whose blob and compensated blob submits also
+ * report every flagged frame's box, so that one persistence call per recording can use it — one more entry point,
+ * declared the same way. */
+#include "mtgpu_pipe_boxes.h"
+
 /* Temporal persistence: the runs of consecutive motion frames per stream — across the key frames that were never
  * analysed, with a bounded dropout and, given the blob boxes, only while the object stays in place — and every frame's
  * run length and place in its run (the frames src/motion_scanner.cpp:382-383 pools, before src/pipeline.cpp:328-344

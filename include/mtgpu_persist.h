@@ -51,9 +51,14 @@
  *  F. Raising max_dropout or reach never lowers any run[f].
  *  G. A stream's outputs equal those of a call on that stream alone.
  *
- * Out of scope: the pipe, the C++ host layer and mtgpu_scan_file — a run crosses batch and chunk boundaries, so that
- * needs carried state; run duration in seconds; filling the bridged Q frames (the merge's MAX_GAP_SEC covers them);
- * tracking more than the largest blob.
+ * On the decode path (mtgpu_pipe_boxes.h; the C++ host layer; mtgpu_scan_file --min-run): a run crosses batch and chunk
+ * boundaries, and the chunks of a recording are scanned in any order, so nothing is carried from one submit to the next —
+ * the flags, has_sd and (from a pipe with MT_LAYOUT_BOXES) the boxes of every batch are pooled, sorted by pts, and THIS
+ * call runs once per recording.
+ *
+ * Out of scope: the pipe's kernels carry no run state (see above: mtgpu_pipe_boxes.h is what the decode path adds); a
+ * level sweep of another setting under persistence; run duration in seconds; filling the bridged Q frames (the merge's
+ * MAX_GAP_SEC covers them); tracking more than the largest blob.
  *
  * Kernel (csrc/persist_kernels.hip): one workgroup per stream, as the merge launches; the workgroup walks the stream in
  * tiles of frames_per_tile frames, forwards for pos and backwards for run, with wave64 scans joined across the waves in

@@ -11,8 +11,9 @@
  * one recording).
  *
  * The staging block of a batch has the flag bytes and ONE count array (MT_LAYOUT_CENTRES).  So a blob pipe reports the
- * flags and one 32-bit count per frame, chosen by `report`; there is no `blobs` and no `box` through the pipe, and not
- * both counts at once.  Those stay with mtgpu_scan_blobs_device.
+ * flags and one 32-bit count per frame, chosen by `report`; there is no `blobs` and no `box` through the pipe as these
+ * two entry points make it, and not both counts at once.  Those stay with mtgpu_scan_blobs_device — except the box,
+ * which a pipe created with MT_LAYOUT_BOXES carries in an array of its own: mtgpu_pipe_boxes.h.
  *
  * Kernel (csrc/blobs_kernels.hip, the pipe form): the blob scan without its stream lookup and without its clear
  * kernel — the planning kernel answers the frames without side data — and with system-scope result stores, on both

@@ -26,7 +26,8 @@
  *  Q5. A frame without side data reads flag 0 and count 0 under every report: the planning kernel answers it.
  *
  * The staging block of a batch has the flag bytes and ONE count array (MT_LAYOUT_CENTRES), so `report` chooses what it
- * carries.  There is no blobs, box or mt_gmc_info through the pipe; they stay with mtgpu_scan_gmc_blobs_device.
+ * carries.  There is no blobs or mt_gmc_info through the pipe; they stay with mtgpu_scan_gmc_blobs_device.  The largest
+ * blob's box travels in an array of its own in a pipe created with MT_LAYOUT_BOXES: mtgpu_pipe_boxes.h.
  *
  * Kernel (csrc/gmc_blobs_kernels.hip, the pipe form): the compensated blob scan without its clear kernel — the planning
  * kernel answers the frames without side data — without the stream lookup and the box pass, and with system-scope result

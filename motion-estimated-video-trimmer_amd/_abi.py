@@ -14,6 +14,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libmtgpu.so")
 
 LAYOUT_COMPACT8, LAYOUT_AOS40, LAYOUT_ZERO_COPY, LAYOUT_CENTRES = 0, 1, 2, 4
+LAYOUT_BOXES = 8                                    # include/mtgpu_pipe_boxes.h
 SWEEP_MAX_LEVELS = 16
 SWEEP_MAX_THRESHOLDS, SWEEP_MAX_VECTORS = 8, 8      # include/mtgpu_sweep.h
 COMPACT_DTYPE = np.dtype([("src_x", "<i2"), ("src_y", "<i2"), ("dst_x", "<i2"), ("dst_y", "<i2")])
@@ -282,6 +283,11 @@ ABI_PERSIST = {
 }
 PERSIST_NO_DROPOUT_LIMIT = 0xFFFFFFFF
 
+# name -> (restype, argtypes): every symbol include/mtgpu_pipe_boxes.h declares (the boxes of a pipe's batch; mtgpu.h includes it).
+ABI_PIPE_BOXES = {
+    "mtgpu_batch_boxes": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+}
+
 _lib = None
 
 
@@ -314,7 +320,7 @@ def load_library(path=None):
     for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
             list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
             list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()) + list(ABI_GMC_BLOBS.items()) + \
-            list(ABI_PIPE_GMC_BLOBS.items()) + list(ABI_PERSIST.items()):
+            list(ABI_PIPE_GMC_BLOBS.items()) + list(ABI_PERSIST.items()) + list(ABI_PIPE_BOXES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -49,10 +49,13 @@ int ctx_zones_keep_words(const mtgpu_ctx *c, uint64_t *words);
 // are pinned host memory and are stored at system scope, the planner's answers for frames without side data too.  With
 // mtgpu_profile_enable on it records the same event triple as ctx_launch_scan.  MT_ERR_UNSUPPORTED as
 // mtgpu_blobs_preview.
+// d_box: nullptr, or the batch's box array (MT_LAYOUT_BOXES, include/mtgpu_pipe_boxes.h; 8-byte aligned, the same memory
+// kind as d_flags): the boxed kernel runs instead and stores the largest blob's box of every frame that reaches its
+// final exit — still planning + one kernel, nothing from the ring, one triple.
 int ctx_launch_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
                      uint32_t n_frames, const uint64_t *d_keep, int32_t min_blob_cells, int report_largest, uint8_t *d_flags,
                      uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
-                     size_t plan_ws_bytes);
+                     size_t plan_ws_bytes, mt_blob_box *d_box = nullptr);
 // MT_OK when the blob scan has a form for the context's grid; MT_ERR_UNSUPPORTED (the grid is named) as
 // mtgpu_blobs_preview otherwise.  No HIP call.
 int ctx_blobs_supported(const mtgpu_ctx *c);
@@ -76,11 +79,11 @@ int ctx_gmc_supported(const mtgpu_ctx *c);
 // receives; the last two require d_count.  plan_ws / plan_ws_bytes are REQUIRED (the batch's own block): nothing is taken
 // from the context's scratch ring.  outputs_in_host_memory: d_flags / d_count are pinned host memory and are stored at
 // system scope, the planner's answers for frames without side data too.  With mtgpu_profile_enable on it records the
-// same event triple as ctx_launch_scan.  MT_ERR_UNSUPPORTED as mtgpu_gmc_blobs_preview.
+// same event triple as ctx_launch_scan.  MT_ERR_UNSUPPORTED as mtgpu_gmc_blobs_preview.  d_box: as ctx_launch_blobs.
 int ctx_launch_gmc_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
                          uint32_t n_frames, const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells,
                          int report, uint8_t *d_flags, uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory,
-                         void *plan_ws, size_t plan_ws_bytes);
+                         void *plan_ws, size_t plan_ws_bytes, mt_blob_box *d_box = nullptr);
 // MT_OK when the compensated blob scan has a form for the context's grid; MT_ERR_UNSUPPORTED (the grid is named) as
 // mtgpu_gmc_blobs_preview otherwise.  No HIP call.
 int ctx_gmc_blobs_supported(const mtgpu_ctx *c);

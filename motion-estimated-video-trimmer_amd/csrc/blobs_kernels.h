@@ -33,6 +33,17 @@ inline size_t blob_lds_bytes(int gw, int R) {
 
 // mt_blob_box of include/mtgpu_blobs.h, as the kernel stores it (2-byte aligned, as the C struct: four 16-bit stores)
 struct BlobBox { unsigned short x0, y0, x1, y1; };
+// The boxed pipe form of blobs_frames_kernel and gmc_blobs_frames_kernel (MT_LAYOUT_BOXES, include/mtgpu_pipe_boxes.h) is
+// chosen by their REC template argument: the record size with kRecBoxed OR-ed in.  A fifth template parameter would
+// rename the four instantiations each kernel had before, and a body shared through an inlined function does not compile
+// to their device code (tried: the register allocation and the address arithmetic of the record loops change); this way
+// they keep both.
+constexpr int kRecBoxed = 0x100;
+// The same four values as the one little-endian 64-bit word the boxed pipe forms store (an 8-byte aligned array).
+__host__ __device__ inline unsigned long long pack_box(unsigned int x0, unsigned int y0, unsigned int x1, unsigned int y1) {
+  return (unsigned long long)(x0 & 0xffffu) | ((unsigned long long)(y0 & 0xffffu) << 16) | ((unsigned long long)(x1 & 0xffffu) << 32) |
+         ((unsigned long long)(y1 & 0xffffu) << 48);
+}
 
 // Kernel-side parameter block.
 struct BlobK {
@@ -59,12 +70,14 @@ struct BlobLaunch {
   const unsigned long long *keep;         // n_streams x gh x W, device memory (pipe form: one plane); null: no mask, no stream lookup
   unsigned char *flags;                   // n_frames bytes, device memory (pipe form: or pinned host memory), or null
   unsigned int *centres, *blobs, *largest;  // n_frames words each, as flags, or null (pipe form: blobs is null, and at most one of centres / largest is given)
-  BlobBox *box;                           // n_frames boxes, or null (pipe form: null)
+  BlobBox *box;                           // n_frames boxes, or null (pipe form: null, or the batch's 8-byte aligned box array —
+                                          // the boxed kernel, which stores the box of every frame that reaches its final exit,
+                                          // at the scope of sys_flags)
   // The pipe form (pipe.hip's staging batches): ONE plane serves every frame — no stream lookup; no clear kernel —
   // launch_plan gets flags and the one count array and answers the frames without side data; the results are stored at
   // system scope where sys_flags / sys_centres say that the array is not device memory (a zero-copy batch's pinned
   // block; sys_centres speaks of whichever of centres / largest is given).  The staging block has one count array: no
-  // blobs, no box, not both counts.  0: the form of mtgpu_scan_blobs_device — plain stores, sys_* must be 0.
+  // blobs, not both counts; a box only for a batch of a pipe with MT_LAYOUT_BOXES.  0: the form of mtgpu_scan_blobs_device — plain stores, sys_* must be 0.
   int pipe = 0;
   int sys_flags = 0, sys_centres = 0;
   BlobK k;

@@ -37,6 +37,9 @@
 //                 one count array).  Either may be a zero-copy batch's pinned block: lane 0 stores them at system scope
 //                 when the launch says so (store_flag / store_centres of record_stream.h) — on BOTH exits, the early
 //                 `no centre` one too: in a reused pinned block it overwrites the previous batch's values.
+//     box         the boxed pipe form (REC | kRecBoxed; MT_LAYOUT_BOXES, include/mtgpu_pipe_boxes.h) also stores the
+//                 winner's box, on the final exit only: one 8-byte store at the flags' scope.  The early exit and the
+//                 planner store none — a box is specified where the flag is set.
 //     no clear    launch_plan is handed the outputs and answers the frames without side data itself, as in launch_scan:
 //                 planning + one kernel.
 //
@@ -117,6 +120,9 @@ __global__ __launch_bounds__(256) void blobs_clear_kernel(unsigned char *__restr
 // plane 0 of `keep` serves every frame, at most one of centres / largest is given, and the results leave through
 // store_flag / store_centres with sys_flags / sys_centres (sys_centres: whichever count is given).  !PIPE: sys_* are not
 // read (0).
+// REC: 8 or 40, the bytes per record; | kRecBoxed (blobs_kernels.h): the boxed pipe form (MT_LAYOUT_BOXES,
+// include/mtgpu_pipe_boxes.h) — `box` is the batch's box array, 8-byte aligned, and the final exit stores the winner's box
+// there.  The early exit and the planner store no box: it is specified only where the flag is set.
 template <int BLOCK, int UNROLL, int REC, bool PIPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void blobs_frames_kernel(
     const unsigned char *__restrict__ mv, const WorkItem *__restrict__ work, unsigned int item0, unsigned int n_items, BlobK k,
@@ -124,6 +130,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     unsigned char *__restrict__ flags, unsigned int *__restrict__ centres, unsigned int *__restrict__ blobs,
     unsigned int *__restrict__ largest, BlobBox *__restrict__ box, int sys_flags, int sys_centres) {
   static_assert(BLOCK % 64 == 0, "a wave owns one word of the centre plane");
+  constexpr bool BOXED = (REC & kRecBoxed) != 0;     // the boxed pipe form: `box` is the batch's box array
+  constexpr int RB = REC & ~kRecBoxed;               // bytes per record
+  static_assert((RB == 8 || RB == 40) && (PIPE || !BOXED), "8 or 40 bytes per record; the boxed form is a pipe form");
   extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
   const unsigned int item = item0 + blockIdx.x;
   if (item >= n_items) return;
@@ -170,7 +179,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   // ---- the votes (an empty analysed range keeps nothing: nothing to read)
   if (crows > 0) {
     const auto one = [=, &k](const MvFields m) { vote(m, k, t0, tile); };
-    if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + me.r0 * 8ull, me.r1 - me.r0, one);
+    if constexpr (RB == 8) stream_compact<BLOCK, UNROLL>(mv + me.r0 * 8ull, me.r1 - me.r0, one);
     else stream_mv40<BLOCK, UNROLL>(mv + me.r0 * 40ull, me.r1 - me.r0, one);
   }
   __syncthreads();
@@ -280,8 +289,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const unsigned long long key = *best;
   const unsigned int win = 0xffffffffu - (unsigned int)(key & 0xffffffffull);
   // box: LDS min / max over the winner's cells (its root, and every cell whose label is the root).  In the PIPE form
-  // nothing reads the box or the blob count total[1]: both are computed all the same, on purpose — the five passes are
-  // those of the resident form, unchanged.
+  // without BOXED nothing reads the box, and in every PIPE form nothing reads the blob count total[1]: both are computed
+  // all the same, on purpose — the five passes are those of the resident form, unchanged.
   for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
     const unsigned int i = (unsigned int)(r * gw + w * 64 + lane);
     bool mine = false;
@@ -300,6 +309,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     if constexpr (PIPE) {
       if (centres) store_centres(centres, f, ncentres, sys_centres);
       if (largest) store_centres(largest, f, big, sys_centres);
+      if constexpr (BOXED)                                      // ONE 8-byte store, at the flags' scope: the same block
+        store_result(reinterpret_cast<unsigned long long *>(box) + f, pack_box(total[4], total[5] + (unsigned int)k.y_lo, total[6],
+                                                                               total[7] + (unsigned int)k.y_lo), sys_flags);
       if (flags) store_flag(flags, f, (unsigned char)((ncentres >= k.clust_need && big >= k.blob_need) ? 1 : 0), sys_flags);
     } else {
       if (centres) centres[f] = ncentres;
@@ -334,7 +346,7 @@ hipError_t launch_blob_scan(const BlobLaunch &L) {
   if (L.rec_bytes != 40 && L.rec_bytes != 8) return hipErrorInvalidValue;
   if (!L.flags && !L.centres && !L.blobs && !L.largest && !L.box) return hipErrorInvalidValue;
   if (L.pipe) {
-    if (L.blobs || L.box || (L.centres && L.largest)) return hipErrorInvalidValue;
+    if (L.blobs || (L.centres && L.largest) || ((uintptr_t)L.box & 7u) != 0u) return hipErrorInvalidValue;
   } else {
     if (L.sys_flags != 0 || L.sys_centres != 0) return hipErrorInvalidValue;
     if (L.keep ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0)) return hipErrorInvalidValue;
@@ -349,6 +361,7 @@ hipError_t launch_blob_scan(const BlobLaunch &L) {
     // launch_scan and launch_zone_scan: no clear kernel — planning + one kernel.  Its count array is whichever is given.
     hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres ? L.centres : L.largest, L.sys_centres);
     if (e != hipSuccess) return e;
+    if (L.box) return L.rec_bytes == 8 ? launch_frames<8 | kRecBoxed, true>(L) : launch_frames<40 | kRecBoxed, true>(L);
     return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
   }
   {

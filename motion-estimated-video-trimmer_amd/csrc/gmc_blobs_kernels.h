@@ -88,7 +88,8 @@ struct GmcBlobLaunch {
   // and `centres`, the batch's ONE count array, and answers the frames without side data; the results are stored at
   // system scope where sys_flags / sys_count say that the array is not device memory; `keep` is ONE plane of gh x W
   // words or null, stream_off / n_streams null / 0; `report` (kGmcBlobReport*) chooses what `centres` receives.  blobs,
-  // largest, box and info must be null.  0: the resident form — sys_* and report 0.
+  // largest and info must be null; box is null or the batch's 8-byte aligned box array (MT_LAYOUT_BOXES: the boxed
+  // kernel, which stores the box of every frame that reaches its final exit, at the scope of sys_flags).  0: the resident form — sys_* and report 0.
   int pipe = 0;
   int sys_flags = 0, sys_count = 0, report = 0;
   GmcBlobK k;

@@ -31,7 +31,9 @@
 // clear kernel — the planner answers the frames without side data at the outputs' scope; no stream lookup — `keep` is ONE
 // plane of gh x W words or null, staged into the same keep rows; BOTH exits store the flag and ONE count (centres, the
 // largest blob, or the applied vector, by `report`) through store_flag / store_centres, because a reused pinned block
-// holds the previous batch's values; no box pass, no blobs, no info.  The flag pointer, the count pointer, the scopes and
+// holds the previous batch's values; no box pass, no blobs, no info — except in the boxed pipe form (REC | kRecBoxed;
+// MT_LAYOUT_BOXES, include/mtgpu_pipe_boxes.h), which runs the box pass and its barrier on the final exit and stores the
+// winner's box with one 8-byte store at the flags' scope.  The flag pointer, the count pointer, the scopes and
 // the report are re-taken from the kernel-argument segment where they are used, as `out` is in the resident form.
 //
 // record_stream.h is used as it is; walk_value and pick_mode are those of gmc_kernels.hip, restated here because that
@@ -138,10 +140,17 @@ __global__ __launch_bounds__(256) void gmc_blobs_clear_kernel(unsigned char *__r
 // words) or null, of `out` only flags and centres are read — centres is the batch's ONE count array, whatever it
 // carries — and the results leave through store_flag / store_centres with sys_flags / sys_count.  !PIPE: sys_* and
 // report are not read (0).
+// REC: 8 or 40, the bytes per record; | kRecBoxed (blobs_kernels.h): the boxed pipe form (MT_LAYOUT_BOXES,
+// include/mtgpu_pipe_boxes.h) — out.box is the batch's box array, 8-byte aligned; the final exit runs the box pass and its
+// barrier and stores the winner's box.  The early exit and the planner store no box: it is specified only where the flag
+// is set.
 template <int BLOCK, int UNROLL, int REC, bool PIPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void gmc_blobs_frames_kernel(const GmcBlobArgs a) {
   static_assert(BLOCK % 64 == 0, "a wave owns one word of the centre plane");
   static_assert(BLOCK >= 2 * kGmcHistBins + 16, "one lane per word of hist, res and total");
+  constexpr bool BOXED = (REC & kRecBoxed) != 0;     // the boxed pipe form: out.box is the batch's box array
+  constexpr int RB = REC & ~kRecBoxed;               // bytes per record
+  static_assert((RB == 8 || RB == 40) && (PIPE || !BOXED), "8 or 40 bytes per record; the boxed form is a pipe form");
   extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
   const unsigned int item = a.item0 + blockIdx.x;
   if (item >= a.n_items) return;
@@ -170,7 +179,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const int crows = k.y_hi - k.y_lo;
   const int W = k.W, gw = k.gw;
   const int ms = k.max_shift;
-  const unsigned char *recs = mv + me.r0 * (unsigned long long)REC;
+  const unsigned char *recs = mv + me.r0 * (unsigned long long)RB;
   const unsigned long long nrec = me.r1 - me.r0;
 
   // The frame's stream, under a mask only: s = the number of streams that end at or before frame f (binary search on
@@ -218,7 +227,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
         hist_add(hx, dx + ms, in && (unsigned int)(dx + ms) <= (unsigned int)(2 * ms));
         hist_add(hy, dy + ms, in && (unsigned int)(dy + ms) <= (unsigned int)(2 * ms));
       };
-      if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(recs, nrec, onek);
+      if constexpr (RB == 8) stream_compact<BLOCK, UNROLL>(recs, nrec, onek);
       else stream_mv40<BLOCK, UNROLL>(recs, nrec, onek);
     } else {
       const auto one = [=, &k, &mine](const MvFields m) {
@@ -230,7 +239,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
         hist_add(hx, dx + ms, in && (unsigned int)(dx + ms) <= (unsigned int)(2 * ms));
         hist_add(hy, dy + ms, in && (unsigned int)(dy + ms) <= (unsigned int)(2 * ms));
       };
-      if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(recs, nrec, one);
+      if constexpr (RB == 8) stream_compact<BLOCK, UNROLL>(recs, nrec, one);
       else stream_mv40<BLOCK, UNROLL>(recs, nrec, one);
     }
 #pragma unroll
@@ -267,7 +276,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
       // gy in [y_lo, y_hi) and t0 <= y_lo: the index stays inside the tile
       if (in && mag >= k.thr) atomicAdd(&tile[(unsigned int)((gy - t0) * k.gw + gx)], 1u);
     };
-    if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(recs, nrec, one);
+    if constexpr (RB == 8) stream_compact<BLOCK, UNROLL>(recs, nrec, one);
     else stream_mv40<BLOCK, UNROLL>(recs, nrec, one);
   }
   __syncthreads();
@@ -321,7 +330,22 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   blob_label::winner<BLOCK>(cpl, crows, W, gw, L, total, lane);
   __syncthreads();
   const unsigned long long key = *reinterpret_cast<const unsigned long long *>(total + 2);
-  if constexpr (PIPE) {                                       // the box serves no pipe output: no pass, no barrier
+  if constexpr (PIPE && BOXED) {                              // the boxed pipe form: the box pass, then the three stores
+    blob_label::box<BLOCK>(cpl, crows, W, gw, L, total, 0xffffffffu - (unsigned int)(key & 0xffffffffull), lane);
+    __syncthreads();
+    if (tid == 0) {
+      const unsigned int big = (unsigned int)(key >> 32);
+      unsigned char *const fl = late->out.flags;
+      unsigned int *const cnt = late->out.centres;
+      BlobBox *const bx = late->out.box;
+      if (cnt) store_centres(cnt, f, pipe_count(late->report, ncentres, big, res), late->sys_count);
+      // ONE 8-byte store, at the flags' scope: the box array lives in the same block
+      store_result(reinterpret_cast<unsigned long long *>(bx) + f, pack_box(total[4], total[5] + (unsigned int)k.y_lo, total[6],
+                                                                              total[7] + (unsigned int)k.y_lo), late->sys_flags);
+      if (fl) store_flag(fl, f, (unsigned char)((ncentres >= k.clust_need && big >= k.blob_need) ? 1 : 0), late->sys_flags);
+    }
+    return;
+  } else if constexpr (PIPE) {                                // the box serves no output of this form: no pass, no barrier
     if (tid == 0) {
       const unsigned int big = (unsigned int)(key >> 32);
       unsigned char *const fl = late->out.flags;
@@ -382,7 +406,8 @@ hipError_t launch_gmc_blob_scan(const GmcBlobLaunch &L) {
   if (!L.flags && !L.centres && !L.blobs && !L.largest && !L.box && !L.info) return hipErrorInvalidValue;
   if (L.pipe) {
     // one plane, no stream table; flags and ONE count (L.centres); a report other than the centres needs the count
-    if (L.stream_off || L.n_streams != 0 || L.blobs || L.largest || L.box || L.info) return hipErrorInvalidValue;
+    // (L.box: the batch's box array of a pipe with MT_LAYOUT_BOXES, 8-byte aligned — the boxed kernel)
+    if (L.stream_off || L.n_streams != 0 || L.blobs || L.largest || ((uintptr_t)L.box & 7u) != 0u || L.info) return hipErrorInvalidValue;
     if (L.report != kGmcBlobReportCentres && L.report != kGmcBlobReportLargest && L.report != kGmcBlobReportVector) return hipErrorInvalidValue;
     if (L.report != kGmcBlobReportCentres && !L.centres) return hipErrorInvalidValue;
   } else {
@@ -401,6 +426,7 @@ hipError_t launch_gmc_blob_scan(const GmcBlobLaunch &L) {
     // launch_gmc_scan and launch_blob_scan: no clear kernel — planning + one kernel.
     hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres, L.sys_count);
     if (e != hipSuccess) return e;
+    if (L.box) return L.rec_bytes == 8 ? launch_frames<8 | kRecBoxed, true>(L) : launch_frames<40 | kRecBoxed, true>(L);
     return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
   }
   {

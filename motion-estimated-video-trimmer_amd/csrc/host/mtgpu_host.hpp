@@ -628,6 +628,7 @@ class GpuBackend {
   uint64_t pipe_us_ = 0, rebuilds_ = 0;
   bool dirty_ = false;
   bool centres_ = false;     // the pipe was created with MT_LAYOUT_CENTRES
+  bool boxes_ = false;       // the pipe was created with MT_LAYOUT_BOXES
  public:
   GpuBackend() = default;
   ~GpuBackend() { reset(); }
@@ -640,6 +641,7 @@ class GpuBackend {
     width_ = height_ = device_ = -1;
     dirty_ = false;
     centres_ = false;
+    boxes_ = false;
   }
   // A scanner that leaves this backend's pipe in an unknown state — a submit or collect failed, a batch may still
   // be in flight or retired (state 4) — marks it: the next video must not inherit that pipe (it would fail every
@@ -679,10 +681,14 @@ class GpuBackend {
   void trim() { if (shared_ && shared_.use_count() == 1) (void)mtgpu_trim(shared_->get()); }
   // cfg/grid derivation of MotionScanner::initialize (motion_scanner.cpp:184-199) + device setup;
   // a backend already set up for this frame size and device is reused as it is.
-  // `centres`: the pipe's batches also carry every frame's centre count (MT_LAYOUT_CENTRES).
+  // `centres`: the pipe's batches also carry every frame's centre count (MT_LAYOUT_CENTRES).  `boxes`: and the largest
+  // blob's box of every flagged frame of a blob submit (MT_LAYOUT_BOXES).  A pooled pipe whose layout is another one is
+  // rebuilt: the next video gets neither a count array nor a box array it did not ask for.
   bool ensure(int width, int height, int device, uint64_t batch_records, uint32_t batch_frames, int n_buffers,
-              std::string &err, bool centres = false) {
-    if (shared_ && pipe_ && !dirty_ && width == width_ && height == height_ && device == device_ && centres == centres_) return true;
+              std::string &err, bool centres = false, bool boxes = false) {
+    if (shared_ && pipe_ && !dirty_ && width == width_ && height == height_ && device == device_ && centres == centres_ &&
+        boxes == boxes_)
+      return true;
     if (dirty_) ++rebuilds_;
     reset();
     mt_scan_params p;
@@ -694,12 +700,21 @@ class GpuBackend {
     if (!shared_) return false;
     const auto t1 = std::chrono::steady_clock::now();
     rc = mtgpu_pipe_create_layout(shared_->get(), batch_records, batch_frames, n_buffers,
-                                  Config::staging_layout() | (centres ? MT_LAYOUT_CENTRES : 0), &pipe_);
+                                  Config::staging_layout() | (centres ? MT_LAYOUT_CENTRES : 0) | (boxes ? MT_LAYOUT_BOXES : 0), &pipe_);
     pipe_us_ += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t1).count();
     if (rc != MT_OK) { err = mtgpu_last_error(); reset(); return false; }
-    width_ = width; height_ = height; device_ = device; centres_ = centres;
+    width_ = width; height_ = height; device_ = device; centres_ = centres; boxes_ = boxes;
     return true;
   }
+};
+
+// What persistence (include/mtgpu_persist.h) needs of one fed frame: GpuMotionScanner::last_trace().  18 bytes before
+// padding, 24 in memory: a day at 30 fps is about 2.6 M frames, 62 MB — a trace needs no cap.
+struct TraceEntry {
+  double pts = 0;
+  uint8_t flag = 0;          // the scan's answer (check_frame)
+  uint8_t has_sd = 0;        // the frame carried MV side data (0: a key frame, transparent to a run)
+  mt_blob_box box{0xffffu, 0xffffu, 0xffffu, 0xffffu};   // the largest blob's box where flag != 0 and the pipe has boxes
 };
 
 class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:113-152)
@@ -728,6 +743,11 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   int gmc_blob_cells_ = 0;                             // set_gmc_blobs(): the pipe's pair mode (compensated blob scan); 0: off
   int gmc_blob_max_shift_ = MTGPU_GMC_DEFAULT_MAX_SHIFT, gmc_blob_min_share_q8_ = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
   int gmc_blob_report_ = MT_PIPE_REPORT_CENTRES;       // report_gmc_blobs(): what last_centres() holds in pair mode
+  bool trace_on_ = false;                              // set_persist(min_run >= 1): scan_range keeps a trace of every fed frame
+  int persist_reach_ = -1;                             // set_persist(): >= 0: the pipe carries boxes (MT_LAYOUT_BOXES)
+  std::vector<TraceEntry> last_trace_;
+  int persist_min_run_ = 0;
+  uint32_t persist_max_dropout_ = 0;
   bool ok(int rc) {
     if (rc == MT_OK) return true;
     err_ = mtgpu_last_error();
@@ -741,7 +761,8 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
     const double *pts = nullptr;
     uint32_t n = 0;
     const auto w0 = std::chrono::high_resolution_clock::now();
-    const bool got = ok(mtgpu_pipe_collect(pipe_, &b, &flags, &pts, nullptr, &n));
+    const uint64_t *tags = nullptr;                          // feed() passes has_side_data as the frame's tag
+    const bool got = ok(mtgpu_pipe_collect(pipe_, &b, &flags, &pts, &tags, &n));
     wait_us_ += since(w0);
     if (!got) {
       // a failed collect still hands the batch out (include/mtgpu.h): give it back, keep the first error
@@ -754,6 +775,18 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
       const uint32_t *centres = nullptr;
       if (!ok(mtgpu_batch_centres(b, &centres))) { const std::string first = err_; --inflight_; (void)mtgpu_pipe_release(pipe_, b); err_ = first; return false; }
       for (uint32_t i = 0; i < n; ++i) last_centres_.emplace_back(pts[i], centres[i]);
+    }
+    if (trace_on_) {                                         // what one persistence call per recording needs of every fed frame
+      const mt_blob_box *box = nullptr;
+      if (persist_reach_ >= 0 && !ok(mtgpu_batch_boxes(b, &box))) { const std::string first = err_; --inflight_; (void)mtgpu_pipe_release(pipe_, b); err_ = first; return false; }
+      for (uint32_t i = 0; i < n; ++i) {
+        TraceEntry e;
+        e.pts = pts[i];
+        e.flag = flags[i] ? 1 : 0;
+        e.has_sd = tags[i] ? 1 : 0;
+        if (box && flags[i]) e.box = box[i];                 // specified only there (include/mtgpu_pipe_boxes.h)
+        last_trace_.push_back(e);
+      }
     }
     --inflight_;
     return ok(mtgpu_pipe_release(pipe_, b));
@@ -783,7 +816,7 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
         take_token();
       }
       const auto c0 = std::chrono::high_resolution_clock::now();
-      int rc = mtgpu_batch_add_frame(cur_, f.mv, f.mv_bytes, f.has_side_data ? 1 : 0, pts, 0);
+      int rc = mtgpu_batch_add_frame(cur_, f.mv, f.mv_bytes, f.has_side_data ? 1 : 0, pts, f.has_side_data ? 1u : 0u);
       copy_us_ += since(c0);
       if (rc == MT_ERR_CAPACITY) { if (!submit()) return false; continue; }
       if (rc == MT_OK) ++frames_fed_;
@@ -860,6 +893,30 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
     gmc_blob_cells_ = min_blob_cells; gmc_blob_max_shift_ = max_shift; gmc_blob_min_share_q8_ = min_share_q8;
   }
   void report_gmc_blobs(int report) { gmc_blob_report_ = report; }
+  // Call before initialize().  Temporal persistence for this video (include/mtgpu_persist.h).  A run of motion frames
+  // crosses batch and chunk borders and the chunks of a recording are scanned by several workers in any order, so the
+  // scanner does NOT apply the rule: it keeps what ONE mtgpu_persist_flags call per recording needs (run_scan_pipeline
+  // makes it on the pooled, pts-sorted traces).  min_run <= 0: off — everything is as without this call and no trace is
+  // kept (a caller that only wants run lengths passes 1).  Otherwise scan_range also keeps a trace of every frame it fed,
+  // in feed order: last_trace().  reach < 0: persistence without boxes.  reach >= 0: the scanner's pipe is created with
+  // MT_LAYOUT_BOXES (include/mtgpu_pipe_boxes.h) and the trace carries the largest blob's box of every flagged frame —
+  // which needs set_min_blob_cells(n > 0) or set_gmc_blobs(n > 0): initialize() fails otherwise.  max_dropout travels
+  // with the two for the caller's one call.  Like the mask and the blob setting, initialize() ALWAYS settles this: a
+  // pooled GpuBackend never hands the next video a boxed pipe it did not ask for (a pipe of another layout is rebuilt,
+  // as for the centre counts), and the trace setting is this scanner's own.  scan_range's signature and its returned
+  // timestamps — the per-frame answer — stay as they are.  Frames dropped by the TARGET_FPS skip never reach the
+  // scanner: they are in no trace and in no run.
+  void set_persist(int min_run, uint32_t max_dropout = 0, int reach = -1) {
+    trace_on_ = min_run > 0;
+    persist_min_run_ = min_run; persist_max_dropout_ = max_dropout;
+    persist_reach_ = trace_on_ ? reach : -1;
+  }
+  int persist_min_run() const { return persist_min_run_; }
+  uint32_t persist_max_dropout() const { return persist_max_dropout_; }
+  int persist_reach() const { return persist_reach_; }
+  // {pts, flag, has_sd, box} of every frame the last scan_range fed, in feed order; box is the all-0xFFFF box where the
+  // pipe has no boxes or the flag is 0.  Empty without set_persist.
+  const std::vector<TraceEntry> &last_trace() const { return last_trace_; }
 
   // batch_records == 0: sized from the source and the staging layout — MTGPU_BATCH_MB MiB of
   // pinned staging per batch, and never less than two frames of one record per 4x4 block (the
@@ -872,7 +929,14 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
       const uint64_t rec_bytes = (Config::staging_layout() & MT_LAYOUT_AOS40) ? MT_MV_BYTES : MT_COMPACT_BYTES;
       batch_records = std::max<uint64_t>(2 * fine, ((uint64_t)Config::batch_mib() << 20) / rec_bytes);
     }
-    if (!be_->ensure(src_.width(), src_.height(), device_, batch_records, batch_frames, n_buffers, err_, keep_centres_)) return false;
+    if (persist_reach_ >= 0 && min_blob_cells_ <= 0 && gmc_blob_cells_ <= 0) {
+      err_ = "set_persist with reach >= 0 needs set_min_blob_cells(n > 0) or set_gmc_blobs(n > 0): only a blob scan reports the box "
+             "that reach compares";
+      return false;
+    }
+    if (persist_reach_ > 65535) { err_ = "set_persist: reach " + std::to_string(persist_reach_) + " outside [0,65535]"; return false; }
+    if (!be_->ensure(src_.width(), src_.height(), device_, batch_records, batch_frames, n_buffers, err_, keep_centres_, persist_reach_ >= 0))
+      return false;
     pipe_ = be_->pipe();
     // the pipe is idle here (a previous scanner on this backend left nothing in flight, or the backend was rebuilt)
     // the pair off first: a pooled pipe that carries it would refuse both single settings below
@@ -957,6 +1021,7 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
       return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
     std::vector<double> ts;
     last_centres_.clear();
+    last_trace_.clear();
     // however this call is left — also by an exception out of the FrameSource — the CPU token goes back: a worker
     // that died holding it would starve the others (with one token: for good)
     struct TokenGuard { GpuMotionScanner &s; ~TokenGuard() { s.drop_token(); } } token_guard{*this};
@@ -1067,8 +1132,44 @@ struct PipelineResult {
   int gmc_blob_min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
   std::vector<int> gmc_blob_sweep_levels;
   std::vector<SweepEntry> gmc_blob_sweep;              // SweepEntry::clusters_needed holds the level L
+  // Temporal persistence (GpuMotionScanner::set_persist; include/mtgpu_persist.h, include/mtgpu_pipe_boxes.h).  In:
+  // min_run > 1: on — a frame counts only as one of a run of at least min_run motion frames; -1: take persist_options();
+  // 0 or 1: off whatever the options say (with no run_sweep_levels everything is as without these fields).  max_dropout:
+  // quiet frames a run bridges (key frames without side data are never counted).  reach >= 0: a run also ends where the
+  // largest blob's box moves more than `reach` cells — needs min_blob_cells > 0 or gmc_blob_cells > 0; -1: no boxes.
+  // run_sweep_levels: `run_sweep` = for every level L what this result's segments / merge would be with min_run = L, from
+  // the ONE scan and the ONE persistence pass (mtgpu_persist.h, consequence E).
+  // How: the rule is applied ONCE per recording, after the scan — the workers' traces are pooled and sorted by pts, then
+  // one mtgpu_persist_flags call; no state is carried from batch to batch or chunk to chunk, so the result does not
+  // depend on CHUNK_DURATION_SEC or the number of workers.  Out: `timestamps` / `motion_frames` / `segments` / `merge`
+  // are those of the frames the rule keeps (timestamps sorted by pts); frames_before_persist = the motion frames the
+  // scan found; `runs` = {pts, run} of every fed frame, sorted by pts (run 0: no motion frame); `trace` = the call's
+  // input, {pts, flag, has_sd, box}, in the same order; persist_us = the wall time of the one call.  Frames dropped by the TARGET_FPS skip never reach a scanner: they are in no run.  A trace
+  // entry is 18 bytes before padding (TraceEntry) and a day at 30 fps about 2.6 M frames: no cap.
+  // Not together with sweep_levels / blob_sweep_levels / gmc_blob_sweep_levels: a level sweep under persistence needs one
+  // persistence pass per level, which is not built.  keep_centres, keep, gmc, min_blob_cells and gmc_blob_cells combine.
+  int min_run = -1;
+  uint32_t max_dropout = 0;
+  int reach = -1;
+  std::vector<int> run_sweep_levels;
+  std::vector<std::pair<double, uint32_t>> runs;
+  std::vector<TraceEntry> trace;                       // out: what the one call was given — every fed frame, sorted by pts
+  size_t frames_before_persist = 0;
+  long persist_us = 0;
+  std::vector<SweepEntry> run_sweep;                   // SweepEntry::clusters_needed holds the level L
   std::string error;
 };
+
+// Process-wide defaults for PipelineResult::min_run / max_dropout / reach / run_sweep_levels (a front end's --min-run,
+// --max-dropout, --reach, --sweep-min-run): set before the first pipeline starts, read by every run_scan_pipeline.
+// min_run <= 1 and no level: off.
+struct PersistOptions {
+  int min_run = 0;
+  uint32_t max_dropout = 0;
+  int reach = -1;
+  std::vector<int> sweep_levels;
+};
+inline PersistOptions &persist_options() { static PersistOptions o; return o; }
 
 // Process-wide defaults for PipelineResult::gmc_blob_cells / gmc_blob_max_shift / gmc_blob_min_share_q8 /
 // gmc_blob_sweep_levels (a front end's --gmc-blobs, --gmc-blobs-max-shift, --gmc-blobs-min-share-q8, --sweep-gmc-blobs):
@@ -1198,9 +1299,33 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
         return 1;
       }
   }
+  // temporal persistence: one pass per recording behind the scan; every conflict is answered here, before any decode
+  if (out.min_run == -1) {
+    out.min_run = persist_options().min_run;
+    out.max_dropout = persist_options().max_dropout;
+    out.reach = persist_options().reach;
+    if (out.run_sweep_levels.empty()) out.run_sweep_levels = persist_options().sweep_levels;
+  }
+  if (out.min_run < -1) { out.error = "min_run is " + std::to_string(out.min_run); return 1; }
+  const bool run_sweep = !out.run_sweep_levels.empty();
+  const bool persist_on = out.min_run > 1 || run_sweep;
+  if (persist_on) {
+    const char *lv = !out.sweep_levels.empty() ? "sweep_levels" : report_largest ? "blob_sweep_levels" : pair_largest ? "gmc_blob_sweep_levels" : nullptr;
+    if (lv) {
+      out.error = std::string(out.min_run > 1 ? "min_run" : "run_sweep_levels") + " together with " + lv +
+                  ": a level sweep under persistence needs one persistence pass per level, which is not built";
+      return 1;
+    }
+    if (out.reach >= 0 && out.min_blob_cells <= 0 && out.gmc_blob_cells <= 0) {
+      out.error = "reach without min_blob_cells / gmc_blob_cells: only a blob scan reports the box that reach compares";
+      return 1;
+    }
+    if (out.reach > 65535) { out.error = "reach " + std::to_string(out.reach) + " outside [0,65535]"; return 1; }
+  }
   const bool keep_centres = out.keep_centres || centre_options().keep || !out.sweep_levels.empty() || report_largest || out.gmc_vectors ||
                             pair_largest;
   std::mutex centres_mu;
+  std::vector<TraceEntry> trace;                                       // pooled under centres_mu, as `centres`
   const auto wall0 = std::chrono::high_resolution_clock::now();
   std::mutex err_mu;
   std::vector<std::thread> workers;
@@ -1243,6 +1368,7 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
         scanners[i]->report_vector(out.gmc_vectors);
         scanners[i]->set_gmc_blobs(pair_on ? std::max(1, out.gmc_blob_cells) : 0, out.gmc_blob_max_shift, out.gmc_blob_min_share_q8);
         scanners[i]->report_gmc_blobs(pair_largest ? MT_PIPE_REPORT_LARGEST : MT_PIPE_REPORT_CENTRES);
+        scanners[i]->set_persist(persist_on ? std::max(1, out.min_run) : 0, out.max_dropout, persist_on ? out.reach : -1);
         if (!scanners[i]->initialize()) {                                // :198-199 (here: reported)
           fail_with(scanners[i]->error());
           return;
@@ -1263,6 +1389,10 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
           if (keep_centres) {
             std::lock_guard<std::mutex> l(centres_mu);
             out.centres.insert(out.centres.end(), scanners[i]->last_centres().begin(), scanners[i]->last_centres().end());
+          }
+          if (persist_on) {
+            std::lock_guard<std::mutex> l(centres_mu);
+            trace.insert(trace.end(), scanners[i]->last_trace().begin(), scanners[i]->last_trace().end());
           }
           if (!r.empty()) results.add(std::move(r));
         }
@@ -1295,10 +1425,42 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
   }
   if (!out.error.empty()) return 1;
   out.timestamps = results.extract();
-  const std::vector<double> &timestamps = out.timestamps;
-  out.motion_frames = timestamps.size();
   for (auto &s : scanners) if (s && s->context()) { merge_ctx = s->context(); break; }
   if (!merge_ctx) { out.error = "no scanner context"; return 1; }
+  if (persist_on) {
+    // The workers' timestamps are the per-frame answer: under persistence they only count.  The rule runs ONCE, on the
+    // whole recording in pts order — a run crosses chunk borders, and neighbouring chunks were scanned by different
+    // workers in any order.
+    out.frames_before_persist = out.timestamps.size();
+    std::stable_sort(trace.begin(), trace.end(), [](const TraceEntry &a, const TraceEntry &b) { return a.pts < b.pts; });
+    if (trace.size() > 0xffffffffull) { out.error = "persistence: more than 2^32 - 1 frames in one recording"; return 1; }
+    const uint32_t n = (uint32_t)trace.size();
+    std::vector<uint8_t> flags(n), has_sd(n), flags_out(n, 0);
+    std::vector<mt_blob_box> box(out.reach >= 0 ? n : 0);
+    std::vector<uint32_t> run(n, 0);
+    for (uint32_t f = 0; f < n; ++f) {
+      flags[f] = trace[f].flag; has_sd[f] = trace[f].has_sd;
+      if (out.reach >= 0) box[f] = trace[f].box;
+    }
+    const uint64_t stream_off[2] = {0, n};
+    const auto p0 = std::chrono::high_resolution_clock::now();
+    if (n > 0) {
+      const int prc = mtgpu_persist_flags(merge_ctx, flags.data(), has_sd.data(), out.reach >= 0 ? box.data() : nullptr, n, stream_off, 1,
+                                          (uint32_t)std::max(1, out.min_run), out.max_dropout, out.reach >= 0 ? (uint32_t)out.reach : 0u,
+                                          flags_out.data(), run.data(), nullptr);
+      if (prc != MT_OK) { out.error = mtgpu_last_error(); return 1; }
+    }
+    out.persist_us = (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::high_resolution_clock::now() - p0).count();
+    out.timestamps.clear();
+    out.runs.clear();
+    for (uint32_t f = 0; f < n; ++f) {
+      if (flags_out[f]) out.timestamps.push_back(trace[f].pts);
+      out.runs.emplace_back(trace[f].pts, run[f]);
+    }
+    out.trace = std::move(trace);
+  }
+  const std::vector<double> &timestamps = out.timestamps;
+  out.motion_frames = timestamps.size();
   // sort + unique + merge + clamp + savings + cut decision on the device (pipeline.cpp:302-358, 387-388)
   mt_merge_params mp{Config::max_gap_sec(), Config::padding_sec(), duration, Config::min_savings_pct()};
   out.segments.assign(timestamps.size() + 1, mt_segment{0, 0});
@@ -1333,6 +1495,19 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
     if (rc != MT_OK) { out.error = mtgpu_last_error(); return 1; }
     e.segments.resize(e.merge.n_segments);
     (pair_largest ? out.gmc_blob_sweep : report_largest ? out.blob_sweep : out.sweep).push_back(std::move(e));
+  }
+  // consequence E of mtgpu_persist.h, done as the sweeps above: the same merge on the pts with run >= max(1, L)
+  for (int level : out.run_sweep_levels) {
+    PipelineResult::SweepEntry e;
+    e.clusters_needed = level;
+    const uint32_t need = level < 1 ? 1u : (uint32_t)level;
+    std::vector<double> ts;
+    for (const auto &r : out.runs) if (r.second >= need) ts.push_back(r.first);
+    e.segments.assign(ts.size() + 1, mt_segment{0, 0});
+    rc = mtgpu_merge_segments(merge_ctx, ts.data(), ts.size(), &mp, 1, e.segments.data(), e.segments.size(), &e.merge);
+    if (rc != MT_OK) { out.error = mtgpu_last_error(); return 1; }
+    e.segments.resize(e.merge.n_segments);
+    out.run_sweep.push_back(std::move(e));
   }
   return 0;
 }

@@ -4,6 +4,7 @@
 //                   [--centres] [--sweep K1,K2,...] [--keep MASK.mtkeep] [--min-blob-cells N] [--sweep-blobs L1,L2,...]
 //                   [--gmc] [--gmc-max-shift N] [--gmc-min-share-q8 Q] [--gmc-vectors]
 //                   [--gmc-blobs N] [--gmc-blobs-max-shift S] [--gmc-blobs-min-share-q8 Q] [--sweep-gmc-blobs L1,L2,...]
+//                   [--min-run N] [--max-dropout D] [--reach R] [--sweep-min-run L1,L2,...]
 //   (--streams 0 / --threads 0: the reference's own sizing from PARALLEL_STREAMS / THREADS_PER_STREAM and the CPU limit)
 // One file: like `motion_trim in out` (single ProcessingPipeline).  Several files: like
 // `motion_trim in_dir out_dir` (BatchProcessor): S streams x T workers, jobs consumed by one
@@ -43,6 +44,19 @@
 // combines with --centres / --sweep, --sweep-gmc-blobs does not (a pipe has one count array); none of it combines with
 // --gmc, --gmc-max-shift, --gmc-min-share-q8, --gmc-vectors, --min-blob-cells N > 0 or --sweep-blobs.  Without these
 // options the output is unchanged.
+// --min-run N: temporal persistence (include/mtgpu_persist.h) — a motion frame counts only as one of a run of at least N
+// motion frames; key frames (no side data) never break a run, --max-dropout D (default 0) quiet frames inside one are
+// bridged, and with --reach R (no default; without it no boxes) a run also ends where the largest blob's box moves more
+// than R cells — which needs --min-blob-cells N > 0 or --gmc-blobs N > 0 (include/mtgpu_pipe_boxes.h).  The rule is
+// applied once per recording, after the scan, on every scanned frame in pts order: the result does not depend on
+// CHUNK_DURATION_SEC or --threads.  Frames the TARGET_FPS skip drops are never scanned and are in no run.  The job gains
+// "min_run", "max_dropout", "reach" (when given), "frames_before_persist" (the motion frames of the scan) and
+// "persist_us"; "motion_frames", "segments" and the merge result are those of the kept frames.  --sweep-min-run 1,2,3:
+// the job gains "runs": [[pts, run], ...] for every scanned frame and "sweep_min_run", in the format of "sweep_blobs",
+// each level with the segments this tool prints when run with --min-run L — from the one scan and the one persistence
+// pass.  --min-run N > 1 and --sweep-min-run do not combine with --sweep, --sweep-blobs or --sweep-gmc-blobs (a level
+// sweep under persistence needs one persistence pass per level, which is not built); --max-dropout and --reach are valid
+// only next to them.  --min-run 0 or 1 with nothing else prints exactly what no option prints.
 // --summary (several files): one more line {"batch_summary": ...} — frames scanned, wall time, worker-time
 // breakdown and what the S x T workers held (contexts, pipes, HIP streams, pinned / device bytes).
 #include <cmath>
@@ -105,6 +119,8 @@ static bool g_print_gmc = false;       // --gmc-vectors
 static const char *g_pair_opt = nullptr;        // the first of --gmc-blobs N > 0 / --sweep-gmc-blobs given
 static const char *g_pair_param_opt = nullptr;  // the first of --gmc-blobs-max-shift / --gmc-blobs-min-share-q8 given
 static const char *g_gmc_opt = nullptr;         // the first option of the --gmc family given
+static const char *g_persist_param_opt = nullptr;   // the first of --max-dropout / --reach given
+static bool g_sweep_opt = false;                    // --sweep given
 
 // The keep mask of g_keep_path for a width x height input; throws with load_keep's message (the line is named) when the
 // file is malformed or made for another grid.
@@ -183,6 +199,17 @@ static void print_job(const std::string &input, const PipelineResult &r, const s
   if (!r.sweep.empty()) print_sweep("sweep", "clusters_needed", r.sweep);
   if (!r.blob_sweep.empty()) print_sweep("sweep_blobs", "min_blob_cells", r.blob_sweep);
   if (!r.gmc_blob_sweep.empty()) print_sweep("sweep_gmc_blobs", "min_blob_cells", r.gmc_blob_sweep);
+  if (r.min_run > 1 || !r.run_sweep_levels.empty()) {
+    std::printf(", \"min_run\": %d, \"max_dropout\": %u", std::max(1, r.min_run), (unsigned)r.max_dropout);
+    if (r.reach >= 0) std::printf(", \"reach\": %d", r.reach);
+    std::printf(", \"frames_before_persist\": %zu, \"persist_us\": %ld", r.frames_before_persist, r.persist_us);
+  }
+  if (!r.run_sweep_levels.empty()) {
+    std::printf(", \"runs\": [");
+    for (size_t i = 0; i < r.runs.size(); ++i) std::printf("%s[%.17g, %u]", i ? ", " : "", r.runs[i].first, r.runs[i].second);
+    std::printf("]");
+    print_sweep("sweep_min_run", "min_run", r.run_sweep);
+  }
   std::printf("}\n");
   std::fflush(stdout);
 }
@@ -200,6 +227,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--summary")) g_summary = true;
     else if (!std::strcmp(argv[i], "--centres")) { g_print_centres = true; centre_options().keep = true; }
     else if (!std::strcmp(argv[i], "--sweep") && i + 1 < argc) {
+      g_sweep_opt = true;
       for (const char *q = argv[++i]; *q;) {
         char *end = nullptr;
         const long v = std::strtol(q, &end, 10);
@@ -305,7 +333,59 @@ int main(int argc, char **argv) {
         if (gmc_options().max_shift < 0) gmc_options().max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT;
       }
     }
+    else if (!std::strcmp(argv[i], "--min-run") || !std::strcmp(argv[i], "--max-dropout") || !std::strcmp(argv[i], "--reach")) {
+      const bool run = !std::strcmp(argv[i], "--min-run"), drop = !std::strcmp(argv[i], "--max-dropout");
+      const long long hi = run ? 0x7fffffffLL : drop ? 0xffffffffLL : 65535LL;
+      char *end = nullptr;
+      const long long v = i + 1 < argc ? std::strtoll(argv[i + 1], &end, 10) : -1;
+      if (i + 1 >= argc || end == argv[i + 1] || *end || v < 0 || v > hi) {
+        std::fprintf(stderr, "error: %s takes an integer in [0, %lld]\n", argv[i], hi);
+        return 2;
+      }
+      if (!run && !g_persist_param_opt) g_persist_param_opt = argv[i];
+      ++i;
+      if (run) persist_options().min_run = (int)v;
+      else if (drop) persist_options().max_dropout = (uint32_t)v;
+      else persist_options().reach = (int)v;
+    }
+    else if (!std::strcmp(argv[i], "--sweep-min-run")) {
+      const char *q = i + 1 < argc ? argv[++i] : "";
+      if (!*q) { std::fprintf(stderr, "error: --sweep-min-run takes a comma-separated list of integers\n"); return 2; }
+      while (*q) {
+        char *end = nullptr;
+        const long v = std::strtol(q, &end, 10);
+        if (end == q || (*end && (*end != ',' || !end[1])) || v > 0x7fffffffL || v < 0) {
+          std::fprintf(stderr, "error: --sweep-min-run takes a comma-separated list of integers >= 0\n");
+          return 2;
+        }
+        persist_options().sweep_levels.push_back((int)v);
+        q = *end ? end + 1 : end;
+      }
+    }
     else files.push_back(argv[i]);
+  }
+  // what persistence cannot be combined with: answered here, before any device call
+  {
+    const PersistOptions &po = persist_options();
+    const bool persist_on = po.min_run > 1 || !po.sweep_levels.empty();
+    const char *mine = po.min_run > 1 ? "--min-run" : "--sweep-min-run";
+    if (g_persist_param_opt && !persist_on) {
+      std::fprintf(stderr, "error: %s is valid only next to --min-run N > 1 or --sweep-min-run\n", g_persist_param_opt);
+      return 2;
+    }
+    if (persist_on) {
+      const char *other = g_sweep_opt ? "--sweep" : g_print_largest ? "--sweep-blobs" : !gmc_blob_options().sweep_levels.empty() ? "--sweep-gmc-blobs" : nullptr;
+      if (other) {
+        std::fprintf(stderr, "error: %s cannot be combined with %s: a level sweep under persistence needs one persistence pass per "
+                     "level, which is not built\n", mine, other);
+        return 2;
+      }
+      if (po.reach >= 0 && blob_options().min_blob_cells <= 0 && gmc_blob_options().min_blob_cells <= 0) {
+        std::fprintf(stderr, "error: --reach needs --min-blob-cells N > 0 or --gmc-blobs N > 0: only a blob scan reports the box that "
+                     "--reach compares\n");
+        return 2;
+      }
+    }
   }
   // what the compensated blob scan cannot be combined with: answered here, before any device call
   if (g_pair_param_opt && !g_pair_opt) {

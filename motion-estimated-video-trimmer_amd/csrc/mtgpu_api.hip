@@ -2091,13 +2091,14 @@ int ctx_blobs_supported(const mtgpu_ctx *c) {
 int ctx_launch_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
                      uint32_t n_frames, const uint64_t *d_keep, int32_t min_blob_cells, int report_largest, uint8_t *d_flags,
                      uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
-                     size_t plan_ws_bytes) {
+                     size_t plan_ws_bytes, mt_blob_box *d_box) {
   if (n_frames == 0) return MT_OK;
   if (min_blob_cells < 1) return fail(MT_ERR_INVALID, "blob pipe scan with min_blob_cells %d", (int)min_blob_cells);
   if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
     return fail(MT_ERR_INVALID, "blob pipe scan: the batch's work-list block is missing, misaligned or too small");
+  if (((uintptr_t)d_box & 7u) != 0u) return fail(MT_ERR_INVALID, "blob pipe scan: the batch's box array must be 8-byte aligned");
   return blobs_on(c, d_rec, rec_bytes, n_records, 0, d_off, d_sd, n_frames, nullptr, 0, d_keep, min_blob_cells, d_flags,
-                  report_largest ? nullptr : d_count, nullptr, report_largest ? d_count : nullptr, nullptr, st, plan_ws,
+                  report_largest ? nullptr : d_count, nullptr, report_largest ? d_count : nullptr, d_box, st, plan_ws,
                   outputs_in_host_memory ? 1 : 0);
 }
 }  // namespace mtgpu
@@ -2705,7 +2706,8 @@ static_assert(MT_PIPE_REPORT_CENTRES == mtgpu::kGmcBlobReportCentres && MT_PIPE_
 // work list lies in the caller's own block: nothing comes from the context's scratch ring.
 int gmc_blobs_pipe_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
                       uint32_t n_frames, const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells,
-                      int report, uint8_t *d_flags, uint32_t *d_count, hipStream_t st, void *own_plan_ws, int outputs_in_host_memory) {
+                      int report, uint8_t *d_flags, uint32_t *d_count, mt_blob_box *d_box, hipStream_t st, void *own_plan_ws,
+                      int outputs_in_host_memory) {
   mtgpu_gmc_blobs_plan gp;
   int rc = gmc_blobs_plan(c->params, c->lds_max, &gp);
   if (rc != MT_OK) return rc;
@@ -2721,7 +2723,7 @@ int gmc_blobs_pipe_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n
   L.n_streams = 0;
   L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
   L.flags = d_flags; L.centres = d_count; L.blobs = nullptr; L.largest = nullptr;
-  L.box = nullptr;
+  L.box = reinterpret_cast<mtgpu::BlobBox *>(d_box);          // nullptr: the form without boxes
   L.info = nullptr;
   L.pipe = 1;
   L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
@@ -2770,8 +2772,10 @@ namespace mtgpu {
 int ctx_launch_gmc_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
                          uint32_t n_frames, const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells,
                          int report, uint8_t *d_flags, uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory,
-                         void *plan_ws, size_t plan_ws_bytes) {
+                         void *plan_ws, size_t plan_ws_bytes, mt_blob_box *d_box) {
   if (n_frames == 0) return MT_OK;
+  if (((uintptr_t)d_box & 7u) != 0u)
+    return fail(MT_ERR_INVALID, "compensated blob pipe scan: the batch's box array must be 8-byte aligned");
   const int rc = gmc_check_settings(max_shift, min_share_q8);
   if (rc != MT_OK) return rc;
   if (min_blob_cells < 1) return fail(MT_ERR_INVALID, "compensated blob pipe scan: min_blob_cells is %d, want >= 1", (int)min_blob_cells);
@@ -2782,7 +2786,7 @@ int ctx_launch_gmc_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, co
   if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
     return fail(MT_ERR_INVALID, "compensated blob pipe scan: the batch's work-list block is missing, misaligned or too small");
   return gmc_blobs_pipe_on(c, d_rec, rec_bytes, n_records, d_off, d_sd, n_frames, d_keep, max_shift, min_share_q8, min_blob_cells,
-                           report, d_flags, d_count, st, plan_ws, outputs_in_host_memory ? 1 : 0);
+                           report, d_flags, d_count, d_box, st, plan_ws, outputs_in_host_memory ? 1 : 0);
 }
 int ctx_gmc_blobs_supported(const mtgpu_ctx *c) {
   mtgpu_gmc_blobs_plan gp;

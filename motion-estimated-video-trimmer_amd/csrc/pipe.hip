@@ -41,7 +41,8 @@ struct mtgpu_batch {
   // pinned host staging: ONE block per batch,
   //   [off (cap_frames+1) x 8 | sd cap_frames | pad to 64 | records | pad to 128 | pts | tags | pad to 128 | flags | pad to 128]
   //   and, in a pipe with MT_LAYOUT_CENTRES, [centres (cap_frames+1) x 4 | pad to 128] behind that — device-written like the
-  //   flags, on lines of their own like them
+  //   flags, on lines of their own like them; in a pipe with MT_LAYOUT_BOXES (include/mtgpu_pipe_boxes.h),
+  //   [boxes (cap_frames+1) x 8 | pad to 128] behind whichever is last — device-written too, on lines of their own
   // The flag bytes — the only part of the block the DEVICE writes — own their 128-byte lines: no line holds both
   // bytes the host stored (pts, tags, records) and bytes the device stores.  x86 keeps such a shared line coherent
   // for snooped PCIe writes, so this is not a fix of a known fault; it removes the one place where the block's
@@ -61,6 +62,7 @@ struct mtgpu_batch {
   uint64_t *h_tag = nullptr;
   uint8_t *h_flags = nullptr;
   uint32_t *h_centres = nullptr;     // nullptr: the pipe keeps no centre counts
+  mt_blob_box *h_boxes = nullptr;    // nullptr: the pipe keeps no boxes
   // what the kernel dereferences: the device view of the pinned block (zero-copy) or a device mirror
   unsigned char *d_stage = nullptr;  // the mirror to free later (nullptr with zero-copy)
   void *d_plan = nullptr;            // device memory for this batch's work list (ctx_plan_ws_bytes(cap_frames)): its scans
@@ -70,6 +72,7 @@ struct mtgpu_batch {
   uint8_t *d_sd = nullptr;
   uint8_t *d_flags = nullptr;
   uint32_t *d_centres = nullptr;
+  mt_blob_box *d_boxes = nullptr;
   size_t hdr_bytes = 0;
   size_t stage_bytes = 0;             // [off | sd | records] part of the block
   size_t block_bytes = 0;             // the whole block: stage + pts / tag / flag arrays
@@ -79,6 +82,8 @@ struct mtgpu_batch {
   int rec_bytes = MT_COMPACT_BYTES;   // bytes per staged record: 8 (compact) or 40 (AoS)
   bool zero_copy = false;             // the scan reads the pinned staging (and writes the flags) over PCIe itself
   bool centres = false;               // MT_LAYOUT_CENTRES: the scan also reports every frame's centre count
+  bool boxes = false;                 // MT_LAYOUT_BOXES: a blob / compensated blob submit also reports the largest blob's box
+  bool wrote_boxes = false;           // set at submit: this batch's kernel was a boxed blob kernel (mtgpu_batch_boxes)
   hipStream_t stream = nullptr;       // from the context's pool (shared with other batches / pipes) or this batch's own
   bool own_stream = false;
   hipEvent_t done = nullptr;
@@ -91,6 +96,7 @@ struct mtgpu_pipe {
   int rec_bytes = MT_COMPACT_BYTES;
   bool zero_copy = false;
   bool centres = false;          // MT_LAYOUT_CENTRES
+  bool boxes = false;            // MT_LAYOUT_BOXES
   long inject_submit_fail = 0;   // MTGPU_INJECT_SUBMIT_FAIL=k (tests): the k-th submit fails after its copies were queued
   long inject_collect_fail = 0;  // MTGPU_INJECT_COLLECT_FAIL=k (tests): the k-th collect's event wait "fails";
                                  // negative: its stream drain "fails" as well (the batch is poisoned)
@@ -152,15 +158,19 @@ size_t stage_bytes_for(uint32_t cap_frames, uint64_t records, int rec_bytes, siz
   return (hdr + (size_t)records * (size_t)rec_bytes + 64 + 127u) & ~(size_t)127u;
 }
 
-// [pts (nf+1) x 8 | tags (nf+1) x 8 | pad to 128 | flags nf+1 | pad to 128 (| centres (nf+1) x 4 | pad to 128)];
-// *flags_off / *centres_off = offsets of the flags / the centre counts
-size_t aux_bytes_for(uint32_t cap_frames, bool centres, size_t *flags_off, size_t *centres_off) {
+// [pts (nf+1) x 8 | tags (nf+1) x 8 | pad to 128 | flags nf+1 | pad to 128 (| centres (nf+1) x 4 | pad to 128)
+//  (| boxes (nf+1) x 8 | pad to 128)];
+// *flags_off / *centres_off / *boxes_off = offsets of the flags / the centre counts / the boxes.  Without `boxes` the
+// size is what it was before the boxes existed, byte for byte.
+size_t aux_bytes_for(uint32_t cap_frames, bool centres, bool boxes, size_t *flags_off, size_t *centres_off, size_t *boxes_off) {
   const size_t nf = (size_t)cap_frames + 1;
   const size_t fo = (nf * (sizeof(double) + sizeof(uint64_t)) + 127u) & ~(size_t)127u;
   const size_t co = fo + ((nf + 127u) & ~(size_t)127u);
+  const size_t bo = centres ? co + ((nf * sizeof(uint32_t) + 127u) & ~(size_t)127u) : co;
   *flags_off = fo;
   *centres_off = co;
-  return centres ? co + ((nf * sizeof(uint32_t) + 127u) & ~(size_t)127u) : co;
+  *boxes_off = bo;
+  return boxes ? bo + ((nf * sizeof(mt_blob_box) + 127u) & ~(size_t)127u) : bo;
 }
 
 #define PIPE_TRY(expr)                                               \
@@ -178,8 +188,8 @@ int pin_block(mtgpu_batch *b, uint64_t records, bool inject_failure = false) {
   void *plan_new = nullptr;
   size_t hdr = 0;
   const size_t sbytes = stage_bytes_for(b->cap_frames, records, b->rec_bytes, &hdr);
-  size_t flags_off = 0, centres_off = 0;
-  const size_t bytes = sbytes + aux_bytes_for(b->cap_frames, b->centres, &flags_off, &centres_off);
+  size_t flags_off = 0, centres_off = 0, boxes_off = 0;
+  const size_t bytes = sbytes + aux_bytes_for(b->cap_frames, b->centres, b->boxes, &flags_off, &centres_off, &boxes_off);
   const size_t nf = (size_t)b->cap_frames + 1;
   // Driver-allocated pinned memory (hipHostMallocDefault: coherent, mapped into the device), on purpose — see
   // include/mtgpu.h "Memory the device entry points accept" and DESIGN.md §5a for why hipHostRegister'ed user
@@ -219,6 +229,9 @@ int pin_block(mtgpu_batch *b, uint64_t records, bool inject_failure = false) {
   b->d_flags = dev_view + sbytes + flags_off;
   b->h_centres = b->centres ? reinterpret_cast<uint32_t *>(h_new + sbytes + centres_off) : nullptr;
   b->d_centres = b->centres ? reinterpret_cast<uint32_t *>(dev_view + sbytes + centres_off) : nullptr;
+  // sbytes and boxes_off are multiples of 128 and the block is page-aligned: the boxes are 8-byte aligned
+  b->h_boxes = b->boxes ? reinterpret_cast<mt_blob_box *>(h_new + sbytes + boxes_off) : nullptr;
+  b->d_boxes = b->boxes ? reinterpret_cast<mt_blob_box *>(dev_view + sbytes + boxes_off) : nullptr;
   b->h_off[0] = 0;
   b->cap_records = records;
   return MT_OK;
@@ -245,6 +258,7 @@ int alloc_batch(mtgpu_batch **out, mtgpu_pipe *p, uint64_t max_records, uint32_t
   b->rec_bytes = p->rec_bytes;
   b->zero_copy = p->zero_copy;
   b->centres = p->centres;
+  b->boxes = p->boxes;
   b->owner = p;
   b->stream = mtgpu::ctx_pipe_stream(p->ctx);
   if (!b->stream) {
@@ -287,9 +301,9 @@ int mtgpu_pipe_create_layout(mtgpu_ctx *ctx, uint64_t max_records_per_batch, uin
                              int n_buffers, int layout, mtgpu_pipe **out) {
   if (!ctx || !out) return fail(MT_ERR_INVALID, "NULL argument");
   *out = nullptr;
-  if (layout < 0 || layout > (MT_LAYOUT_AOS40 | MT_LAYOUT_ZERO_COPY | MT_LAYOUT_CENTRES))
+  if (layout < 0 || layout > (MT_LAYOUT_AOS40 | MT_LAYOUT_ZERO_COPY | MT_LAYOUT_CENTRES | MT_LAYOUT_BOXES))
     return fail(MT_ERR_INVALID, "layout must be MT_LAYOUT_COMPACT8 or MT_LAYOUT_AOS40, optionally | MT_LAYOUT_ZERO_COPY "
-                "| MT_LAYOUT_CENTRES");
+                "| MT_LAYOUT_CENTRES | MT_LAYOUT_BOXES");
   if (max_records_per_batch == 0 || max_frames_per_batch == 0 || n_buffers < 1 || n_buffers > 64)
     return fail(MT_ERR_INVALID, "pipe needs max_records > 0, max_frames > 0, 1 <= n_buffers <= 64");
   hipError_t e = hipSetDevice(mtgpu::ctx_device(ctx));
@@ -300,6 +314,7 @@ int mtgpu_pipe_create_layout(mtgpu_ctx *ctx, uint64_t max_records_per_batch, uin
   p->rec_bytes = (layout & MT_LAYOUT_AOS40) ? MT_MV_BYTES : MT_COMPACT_BYTES;
   p->zero_copy = (layout & MT_LAYOUT_ZERO_COPY) != 0;
   p->centres = (layout & MT_LAYOUT_CENTRES) != 0;
+  p->boxes = (layout & MT_LAYOUT_BOXES) != 0;
   if (const char *v = std::getenv("MTGPU_INJECT_SUBMIT_FAIL")) p->inject_submit_fail = std::atol(v);
   if (const char *v = std::getenv("MTGPU_INJECT_GROW_FAIL")) p->inject_grow_fail = std::atol(v) != 0;
   if (const char *v = std::getenv("MTGPU_INJECT_COLLECT_FAIL")) p->inject_collect_fail = std::atol(v);
@@ -400,6 +415,12 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
   int rc = MT_OK;
   long nth;
   { std::lock_guard<std::mutex> lock(p->mu); nth = ++p->submits; }
+  // MT_LAYOUT_BOXES: the two blob modes are handed the batch's box array and run their boxed kernel; every other mode
+  // launches exactly what an unboxed pipe launches, and mtgpu_batch_boxes refuses the batch
+  // (the setters keep the two blob modes and the compensated mode apart: a minimum blob size means a blob kernel)
+  const bool blob_mode = (p->pair_blob >= 1 || p->min_blob >= 1) && !p->gmc;
+  mt_blob_box *const d_box = (b->boxes && blob_mode) ? b->d_boxes : nullptr;
+  b->wrote_boxes = d_box != nullptr;
   if (b->n_frames) {
     // one copy: offsets + has_sd header and the records that follow it (zero-copy: none at all)
     if (!b->zero_copy)
@@ -412,7 +433,7 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
     if (p->pair_blob > 0)   // mtgpu_pipe_set_gmc_blobs: the compensated blob scan, under the pipe's keep plane when it has a mask
       rc = mtgpu::ctx_launch_gmc_blobs(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
                                        p->pair_max_shift, p->pair_min_share_q8, p->pair_blob, p->pair_report, b->d_flags,
-                                       b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
+                                       b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes, d_box);
     else if (p->gmc)   // mtgpu_pipe_set_gmc: the compensated scan, estimate and vote under the pipe's keep plane when it has a mask
       rc = mtgpu::ctx_launch_gmc(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
                                  p->gmc_max_shift, p->gmc_min_share_q8, p->gmc_report == MT_PIPE_REPORT_VECTOR ? 1 : 0, b->d_flags,
@@ -420,7 +441,7 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
     else if (p->min_blob > 0)   // mtgpu_pipe_set_blobs: the blob scan, under the pipe's keep plane when it has a mask
       rc = mtgpu::ctx_launch_blobs(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
                                    p->min_blob, p->report == MT_PIPE_REPORT_LARGEST ? 1 : 0, b->d_flags, b->d_centres, st,
-                                   b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
+                                   b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes, d_box);
     else if (p->masked)   // mtgpu_pipe_set_keep: the masked scan, its work list in the batch's own block like the plain one's
       rc = mtgpu::ctx_launch_zones(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->d_keep, b->d_flags,
                                    b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
@@ -432,6 +453,8 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
       PIPE_TRY(hipMemcpyAsync(b->h_flags, b->d_flags, b->n_frames, hipMemcpyDeviceToHost, st));
       if (b->centres)
         PIPE_TRY(hipMemcpyAsync(b->h_centres, b->d_centres, sizeof(uint32_t) * (size_t)b->n_frames, hipMemcpyDeviceToHost, st));
+      if (d_box)
+        PIPE_TRY(hipMemcpyAsync(b->h_boxes, b->d_boxes, sizeof(mt_blob_box) * (size_t)b->n_frames, hipMemcpyDeviceToHost, st));
     }
   }
   PIPE_TRY(hipEventRecord(b->done, st));
@@ -504,6 +527,21 @@ int mtgpu_batch_centres(const mtgpu_batch *b, const uint32_t **centres) {
   return MT_OK;
 }
 
+int mtgpu_batch_boxes(const mtgpu_batch *b, const struct mt_blob_box **box) {
+  if (box) *box = nullptr;
+  if (!b || !box) return fail(MT_ERR_INVALID, "batch/box is NULL");
+  if (!b->boxes) return fail(MT_ERR_INVALID, "the batch's pipe was created without MT_LAYOUT_BOXES");
+  {
+    std::lock_guard<std::mutex> lock(b->owner->mu);
+    if (b->state != 3) return fail(MT_ERR_INVALID, "batch has not been collected");
+  }
+  if (!b->wrote_boxes)
+    return fail(MT_ERR_INVALID, "the batch was submitted while its pipe ran neither the blob scan (mtgpu_pipe_set_blobs) nor the "
+                "compensated blob scan (mtgpu_pipe_set_gmc_blobs): no kernel wrote boxes");
+  *box = b->h_boxes;
+  return MT_OK;
+}
+
 int mtgpu_pipe_get_stats(mtgpu_pipe *p, mtgpu_pipe_stats *out) {
   if (!p || !out) return fail(MT_ERR_INVALID, "NULL argument");
   std::lock_guard<std::mutex> lock(p->mu);
@@ -520,7 +558,7 @@ int mtgpu_pipe_get_stats(mtgpu_pipe *p, mtgpu_pipe_stats *out) {
   out->submits = (uint64_t)p->submits;
   out->n_buffers = (uint32_t)p->bufs.size();
   out->layout = (p->rec_bytes == MT_MV_BYTES ? MT_LAYOUT_AOS40 : MT_LAYOUT_COMPACT8) | (p->zero_copy ? MT_LAYOUT_ZERO_COPY : 0) |
-                (p->centres ? MT_LAYOUT_CENTRES : 0);
+                (p->centres ? MT_LAYOUT_CENTRES : 0) | (p->boxes ? MT_LAYOUT_BOXES : 0);
   return MT_OK;
 }
 

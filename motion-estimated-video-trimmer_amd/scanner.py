@@ -20,7 +20,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi, config
-from ._abi import (BLOB_BOX_DTYPE, BlobsPlanC, COMPACT_DTYPE, LAYOUT_AOS40, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
+from ._abi import (BLOB_BOX_DTYPE, BlobsPlanC, COMPACT_DTYPE, LAYOUT_AOS40, LAYOUT_BOXES, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
                    GMC_DEFAULT_MAX_SHIFT, GMC_DEFAULT_MIN_SHARE_Q8, GMC_INFO_DTYPE, GmcBlobsPlanC, GmcPlanC,
                    MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PersistPlanC, PlanC, ScanParamsC, SweepPlanC, ZonesPlanC, check,
                    load_library)
@@ -1131,18 +1131,23 @@ class ScanPipe:
     (pts, flag, tag) in submission order."""
 
     def __init__(self, scanner: MotionScanner, max_records: int, max_frames: int, n_buffers: int = 3,
-                 layout: int = LAYOUT_COMPACT8 | LAYOUT_ZERO_COPY, centres: bool = False):
+                 layout: int = LAYOUT_COMPACT8 | LAYOUT_ZERO_COPY, centres: bool = False, boxes: bool = False):
         """layout: LAYOUT_COMPACT8 (8 of every 40 record bytes are staged) or LAYOUT_AOS40 (records
         staged unchanged), optionally | LAYOUT_ZERO_COPY (the scan reads the pinned staging over
         PCIe itself: no copy commands).  Default: compact + zero-copy.  Results are identical.
         centres=True (or layout | LAYOUT_CENTRES): every batch also carries the frames' centre counts
-        (src/motion_scanner.cpp:272-294); read them with drain_centres()."""
+        (src/motion_scanner.cpp:272-294); read them with drain_centres().
+        boxes=True (or layout | LAYOUT_BOXES, include/mtgpu_pipe_boxes.h): every batch submitted under set_blobs or
+        set_gmc_blobs also carries the largest blob's box of every frame with a flag; read them with drain_boxes()."""
         self._lib = scanner._lib
         self._scanner = scanner            # keeps the context alive
         self._pipe = C.c_void_p()
         if centres:
             layout = int(layout) | LAYOUT_CENTRES
+        if boxes:
+            layout = int(layout) | LAYOUT_BOXES
         self._centres = (int(layout) & LAYOUT_CENTRES) != 0
+        self._boxes = (int(layout) & LAYOUT_BOXES) != 0
         check(self._lib.mtgpu_pipe_create_layout(scanner._ctx, int(max_records), int(max_frames),
                                                  int(n_buffers), int(layout), C.byref(self._pipe)))
         scanner._pipes.add(self)
@@ -1150,6 +1155,8 @@ class ScanPipe:
         self._inflight = 0
         self._done: List[Tuple[float, int, int]] = []
         self._done_centres: List[int] = []          # with LAYOUT_CENTRES: one count per entry of _done
+        self._done_boxes: List[Tuple[int, int, int, int]] = []   # with LAYOUT_BOXES: one box per entry of _done
+        self._box_error = None                      # the library's refusal of mtgpu_batch_boxes since the last drain
 
     def close(self):
         if getattr(self, "_pipe", None) and self._pipe.value:
@@ -1290,6 +1297,17 @@ class ScanPipe:
                 cp = C.c_void_p()
                 check(self._lib.mtgpu_batch_centres(b, C.byref(cp)))
                 self._done_centres += np.ctypeslib.as_array(C.cast(cp, C.POINTER(C.c_uint32)), (k,)).tolist()
+            if self._boxes:
+                bp = C.c_void_p()
+                rc = self._lib.mtgpu_batch_boxes(b, C.byref(bp))
+                if rc == _abi.MT_OK:
+                    # four uint16 per frame; specified where the flag is set, the no-blob box everywhere else
+                    bx = np.ctypeslib.as_array(C.cast(bp, C.POINTER(C.c_uint16)), (k, 4)).copy()
+                    bx[f == 0] = 0xFFFF
+                    self._done_boxes += [tuple(r) for r in bx.tolist()]
+                else:                           # not a blob submit: drain_boxes() raises this, drain() goes on
+                    self._box_error = (rc, self._lib.mtgpu_last_error().decode("utf-8", "replace"))
+                    self._done_boxes += [(0xFFFF,) * 4] * k
         check(self._lib.mtgpu_pipe_release(self._pipe, b))
         self._inflight -= 1
 
@@ -1339,6 +1357,8 @@ class ScanPipe:
             self._collect_one()
         out, self._done = self._done, []
         self._last_centres, self._done_centres = self._done_centres, []
+        self._last_boxes, self._done_boxes = self._done_boxes, []
+        self._last_box_error, self._box_error = self._box_error, None
         return out
 
     def drain_centres(self) -> List[Tuple[float, int, int, int]]:
@@ -1348,6 +1368,20 @@ class ScanPipe:
             raise _abi.MtgpuError(_abi.MT_ERR_INVALID, "the pipe was created without centres=True / LAYOUT_CENTRES")
         out = self.drain()
         return [(p, f, t, c) for (p, f, t), c in zip(out, self._last_centres)]
+
+    def drain_boxes(self) -> List[Tuple[float, int, int, Optional[int], Tuple[int, int, int, int]]]:
+        """drain() of a pipe created with boxes=True under set_blobs / set_gmc_blobs: (pts, flag, tag, count, (x0, y0, x1,
+        y1)) in submission order — count as drain_centres() reports it, None in a pipe without centres=True; the box is
+        the largest blob's inclusive cell bounds (mtgpu_scan_blobs_device's `box`) where the flag is set and the no-blob
+        box (0xFFFF,) * 4 everywhere else.  MtgpuError(MT_ERR_INVALID), the library's reason, when the pipe has no boxes
+        or a drained batch was submitted in a mode that writes none (the results of that drain are dropped)."""
+        if not self._boxes:
+            raise _abi.MtgpuError(_abi.MT_ERR_INVALID, "the pipe was created without boxes=True / LAYOUT_BOXES")
+        out = self.drain()
+        if self._last_box_error is not None:
+            raise _abi.MtgpuError(*self._last_box_error)
+        counts = self._last_centres if self._centres else [None] * len(out)
+        return [(p, f, t, c, b) for (p, f, t), c, b in zip(out, counts, self._last_boxes)]
 
 
 def results_from_bytes(res_bytes: np.ndarray) -> np.ndarray:
