@@ -490,6 +490,11 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * declared the same way. */
 #include "mtgpu_pipe_boxes.h"
 
+/* The direction filter: the centre scan in which a record votes only if the sector of dst - src is allowed, and the
+ * per-frame motion rose (src/motion_scanner.cpp:246-251 squares the displacement and loses its sign) — three more entry
+ * points, declared the same way. */
+#include "mtgpu_dir.h"
+
 /* Temporal persistence: the runs of consecutive motion frames per stream — across the key frames that were never
  * analysed, with a bounded dropout and, given the blob boxes, only while the object stays in place — and every frame's
  * run length and place in its run (the frames src/motion_scanner.cpp:382-383 pools, before src/pipeline.cpp:328-344

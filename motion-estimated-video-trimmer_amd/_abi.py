@@ -103,6 +103,10 @@ class PersistPlanC(C.Structure):
     _fields_ = [("workgroup", C.c_int32), ("frames_per_tile", C.c_int32)]
 
 
+class DirPlanC(C.Structure):
+    _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("sectors", C.c_int32), ("rose_bytes", C.c_int32)]
+
+
 class CtxStatsC(C.Structure):
     _fields_ = [("staging_device_bytes", C.c_uint64), ("pool_reserved_bytes", C.c_uint64),
                 ("pool_reserved_high", C.c_uint64), ("hip_streams", C.c_uint32), ("private_pool", C.c_uint32)]
@@ -288,6 +292,17 @@ ABI_PIPE_BOXES = {
     "mtgpu_batch_boxes": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_dir.h declares (the direction filter; mtgpu.h includes it).
+ABI_DIR = {
+    "mtgpu_dir_preview": (C.c_int, [C.POINTER(ScanParamsC), C.c_int, C.POINTER(DirPlanC)]),
+    "mtgpu_scan_dir_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "mtgpu_scan_frames_dir": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+DIR_ALL, DIR_SECTORS = 0xFF, 8
+
 _lib = None
 
 
@@ -320,7 +335,8 @@ def load_library(path=None):
     for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
             list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
             list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()) + list(ABI_GMC_BLOBS.items()) + \
-            list(ABI_PIPE_GMC_BLOBS.items()) + list(ABI_PERSIST.items()) + list(ABI_PIPE_BOXES.items()):
+            list(ABI_PIPE_GMC_BLOBS.items()) + list(ABI_PERSIST.items()) + list(ABI_PIPE_BOXES.items()) + \
+            list(ABI_DIR.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

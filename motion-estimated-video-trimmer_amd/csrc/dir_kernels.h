@@ -1,0 +1,72 @@
+// dir_kernels.h — launch interface between the C ABI (mtgpu_api.hip) and the gfx950 direction-filter kernel
+// (dir_kernels.hip): the centre counts of src/motion_scanner.cpp:272-294 from the votes of the records whose sector is
+// allowed (include/mtgpu_dir.h), and the per-frame rose of the counting records.  Internal; not part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "scan_kernels.h"
+
+namespace mtgpu {
+
+constexpr int kDirBlock = 1024;     // lanes per workgroup
+constexpr int kDirUnroll = 4;       // independent record loads in flight per lane
+// Records a workgroup streams between two flushes of the lanes' packed rose counters (eight 8-bit fields).  A lane
+// sees at most kDirChunk / kDirBlock records of the steps, one of the head peel and one odd last record: 130 < 256.
+constexpr unsigned long long kDirChunk = 128ull * kDirBlock;
+static_assert(kDirChunk / kDirBlock + 2 < 256, "a lane's 8-bit rose field must not wrap between two flushes");
+static_assert((kDirChunk / kDirBlock + 2) * 64 < 65536, "a wave's 16-bit partial sums must not wrap");
+
+// LDS of one workgroup, in this order (R = analysed rows, at least 1; W = 64-bit words per mask row):
+//   tile     (R + 2) x gw u32, padded to 4 words   vote counters: the analysed rows and one halo row each side
+//   amask    (R + 2) x W u64                       the frame's active cells; mask row j <-> grid row y_lo - 1 + j
+//   total    4 u32                                 [0]: the centre count
+//   rose     8 u32                                 the frame's counting records per sector
+inline size_t dir_tile_words(int gw, int R) {
+  const size_t w = (size_t)(R + 2) * (size_t)gw;
+  return (w + 3u) & ~(size_t)3u;
+}
+inline size_t dir_lds_bytes(int gw, int R) {
+  const size_t W = ((size_t)gw + 63u) / 64u;
+  return dir_tile_words(gw, R) * 4u + (size_t)(R + 2) * W * 8u + 16u + 32u;
+}
+
+// Kernel-side parameter block.
+struct DirK {
+  unsigned long long thr;        // a record counts iff |d|^2 >= thr (ScanK::thr, :251) and its cell is analysed (:262)
+  unsigned int vec_need;         // a cell is active iff votes >= vec_need (:282)
+  unsigned int clust_need;       // flags[f] = centres[f] >= clust_need = max(1, clusters_needed) (:288)
+  int shift, gw, gh, y_lo, y_hi; // as ScanK (y_hi >= y_lo)
+  int W;                         // 64-bit words per mask row
+  int R;                         // max(1, y_hi - y_lo): rows the LDS layout is sized for
+  int tile_words;                // dir_tile_words
+};
+
+struct DirLaunch {
+  const unsigned char *mv;
+  unsigned long long n_records;           // frame_off entries are clamped to this (before `rebase`)
+  unsigned long long rebase;
+  const unsigned long long *frame_off;    // n_frames + 1
+  const unsigned char *has_sd;            // n_frames or null
+  unsigned int n_frames;
+  int rec_bytes;                          // 40 or 8
+  const unsigned long long *stream_off;   // n_streams + 1, or null: `allow` serves every frame
+  unsigned int n_streams;
+  const unsigned char *allows;            // n_streams bytes, device memory, or null (then stream_off is null, n_streams 0)
+  unsigned int allow;                     // 0 .. 255; read only without `allows`
+  unsigned char *flags;                   // n_frames bytes, device memory, or null
+  unsigned int *centres;                  // n_frames words, or null
+  unsigned int *rose;                     // n_frames x 8 words (mt_dir_rose), or null
+  DirK k;
+  int lds_bytes;
+  int lds_max;                            // device limit of dynamic LDS per workgroup
+  int device;
+  void *plan_ws;                          // plan_scratch_bytes(n_frames), 32-byte aligned
+  hipStream_t stream;
+  hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the scan kernel; else nullptr
+};
+
+// Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.
+hipError_t launch_dir_scan(const DirLaunch &L);
+
+}  // namespace mtgpu

@@ -1,0 +1,252 @@
+// dir_kernels.hip — the direction filter: the centre scan of src/motion_scanner.cpp:242-292 (without the early return) in
+// which a record votes only if the sector of its displacement dst - src is allowed, and the per-frame rose: the counting
+// records of each of the eight sectors, whatever is allowed (include/mtgpu_dir.h).
+//
+//   dir_clear_kernel     zero-fills the non-null outputs ahead of the scan kernel: a frame without side data, and a frame
+//                        behind the last stream, reads 0 everywhere.
+//   dir_frames_kernel    one workgroup per entry of the scan's work list (plan_frames: the frames with side data, in
+//                        stream order).  Surplus workgroups find kNoFrame and leave.
+//     stream      with per-stream allow bytes: s = the number of streams that end at or before frame f, a binary search
+//                 on workgroup-uniform values; the stream's byte is one scalar load.  Without: the launch's byte.
+//     votes       zero the tile; stream the records as the zones kernel does (head peel to a 128-byte line, non-temporal
+//                 loads, kDirUnroll in flight per lane).  Per COUNTING record, behind the branch on the threshold and the
+//                 bounds that the vote needs anyway: two 24-bit multiplies and compares for the two axis tests, the
+//                 sector from the two predicates and the two sign bits, one shift of the allow byte — then the
+//                 fire-and-forget `ds_add_u32` of an allowed record.  A record that does not count costs what it costs
+//                 in the zones kernel.
+//     rose        NOT an LDS atomic per record.  A lane counts its records in eight 8-bit fields of one 64-bit register:
+//                 one shifted add per record.  The workgroup streams the frame in pieces of kDirChunk records — a
+//                 uniform loop; a frame of up to 131 072 records is one piece — and after each piece the lanes' fields
+//                 are summed across the wave (spread to 16-bit fields, DPP inside a row of 16 lanes, four lane reads
+//                 across the rows) and lane 0 of each wave adds the non-zero sums to eight LDS words.  A lane sees at
+//                 most 130 records of a piece, so no field wraps; the LDS words are 32 bits wide, as the output is.
+//     masks       the 64-bit masks of the active cells of every tracked row.
+//     centres     the shifted-mask neighbour test with carries across word boundaries.
+//   Every output element has one writer after the clear: lane 0 of the frame's workgroup, plain vector stores, no global
+//   atomics.
+//
+// The record loads, the streamers, the row masks, the centre test of a word are those of record_stream.h, instantiated
+// here with this kernel's functor; the launch helpers are those of scan_kernels.h.
+#if !defined(__HIP_DEVICE_COMPILE__) || defined(__gfx950__)
+#else
+#error "dir_kernels.hip is written for gfx950 only (wave64, 160 KB LDS)"
+#endif
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <atomic>
+
+#include "dir_kernels.h"
+#include "record_stream.h"
+
+namespace mtgpu {
+
+namespace {
+
+// ---- the centres (:277-293), one task per (analysed row, word): analysed row r <-> mask row r + 1; x in [1, gw-2]
+// (:280); neighbours across word and row boundaries; outside the grid: inactive.  As in zones_kernels.hip.
+template <int BLOCK>
+__device__ __forceinline__ void count_centres(const unsigned long long *amask, unsigned int *total, const DirK &k, int crows) {
+  const int W = k.W;
+  const int ntask = crows * W;
+  for (int tk = threadIdx.x; tk < ntask; tk += BLOCK) {
+    const int r = tk / W, w = tk - r * W;
+    const unsigned long long *mr = amask + (size_t)(r + 1) * W;
+    if (mr[w] == 0ull) continue;                               // no popcount, no add: most words of most frames
+    const unsigned int c = (unsigned int)__popcll(centre_word(mr, w, W, k.gw));
+    if (c) atomicAdd(total, c);
+  }
+}
+
+// ---- one record (src/motion_scanner.cpp:246-268 and the direction test of include/mtgpu_dir.h): threshold, cell,
+// bounds as record_stream.h's vote(); then the sector of (dx, dy); a counting record with a sector goes into the lane's
+// packed rose; a counting record without a sector, or with an allowed one, votes.
+//   axis tests   e: 12 |dy| <= 5 |dx| (E / W), s: 12 |dx| <= 5 |dy| (S / N); |d| <= 65535, so both products fit 24-bit
+//                multiplies.  Both hold only for dx == dy == 0.
+//   sector       e: 4 sx; s: 2 + 4 sy; neither: 1 + 4 sy + 2 (sx ^ sy)  (sx, sy: the sign bits: 1, 3, 5, 7 clockwise)
+__device__ __forceinline__ void dir_vote(const MvFields m, const DirK &k, int t0, unsigned int *tile, unsigned int allow,
+                                         unsigned long long &acc) {
+  const int sdx = m.dst_x - m.src_x, sdy = m.dst_y - m.src_y;  // |.| <= 65535
+  const unsigned int dx = (unsigned int)sdx, dy = (unsigned int)sdy;
+  // dx*dx < 2^32 exactly; the sum needs 34 bits
+  const unsigned long long mag = (unsigned long long)(dx * dx) + (unsigned long long)(dy * dy);
+  const int gx = m.dst_x >> k.shift, gy = m.dst_y >> k.shift;
+  // 0 <= gx < gw and y_lo <= gy < y_hi (:262) as two unsigned compares (y_hi >= y_lo by construction)
+  const bool in = ((unsigned int)gx < (unsigned int)k.gw) & ((unsigned int)(gy - k.y_lo) < (unsigned int)(k.y_hi - k.y_lo));
+  // The sector is worked out behind the branch the vote needs anyway: most records of most footage count nothing
+  // (they are still, or too slow), and a wave without a counting record skips all of it.  Behind the branch every value
+  // is computed for every lane and chosen with selects.
+  if (in & (mag >= k.thr)) {
+    const unsigned int ax = (unsigned int)(sdx < 0 ? -sdx : sdx), ay = (unsigned int)(sdy < 0 ? -sdy : sdy);
+    const bool e = __umul24(12u, ay) <= __umul24(5u, ax), s = __umul24(12u, ax) <= __umul24(5u, ay);
+    const unsigned int sx = dx >> 31, sy = dy >> 31;
+    const unsigned int diag = 1u | ((sx ^ sy) << 1);
+    const unsigned int mid = s ? 2u : diag;
+    const unsigned int south = mid | (sy << 2), west = sx << 2;
+    const unsigned int sec = e ? west : south;
+    const bool none = (dx | dy) == 0u;
+    const unsigned int eff = none ? 0xffu : allow;             // no direction to object to
+    acc += (unsigned long long)(none ? 0u : 1u) << (8u * sec);
+    if (((eff >> sec) & 1u) != 0u) atomicAdd(&tile[(unsigned int)((gy - t0) * k.gw + gx)], 1u);
+  }
+}
+
+// ---- sums over a wave, every lane active.  Inside a row of 16 lanes with DPP (quad_perm [1,0,3,2], quad_perm
+// [2,3,0,1], row_half_mirror, row_mirror: every lane of the row then holds the row's sum), across the four rows with
+// four lane reads: a scalar result.
+template <int CTRL>
+__device__ __forceinline__ unsigned int dpp_add(unsigned int v) {
+  return v + (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+}
+__device__ __forceinline__ unsigned int wave_sum(unsigned int v) {
+  v = dpp_add<0xB1>(v);
+  v = dpp_add<0x4E>(v);
+  v = dpp_add<0x141>(v);
+  v = dpp_add<0x140>(v);
+  return (unsigned int)__builtin_amdgcn_readlane((int)v, 0) + (unsigned int)__builtin_amdgcn_readlane((int)v, 16) +
+         (unsigned int)__builtin_amdgcn_readlane((int)v, 32) + (unsigned int)__builtin_amdgcn_readlane((int)v, 48);
+}
+
+// The lanes' packed counters (eight 8-bit fields, each at most 130) -> the eight LDS words, once per wave.  The even
+// and the odd fields are spread to four 16-bit fields each: a wave's sum is at most 64 x 130 and stays inside its field.
+__device__ __forceinline__ void flush_rose(unsigned long long acc, unsigned int *rose) {
+  constexpr unsigned long long kEven = 0x00ff00ff00ff00ffull;
+  const unsigned long long ev = acc & kEven, od = (acc >> 8) & kEven;
+  const unsigned int e0 = wave_sum((unsigned int)ev), e1 = wave_sum((unsigned int)(ev >> 32));
+  const unsigned int o0 = wave_sum((unsigned int)od), o1 = wave_sum((unsigned int)(od >> 32));
+  if ((threadIdx.x & 63u) == 0u) {
+    const unsigned int n[8] = {e0 & 0xffffu, o0 & 0xffffu, e0 >> 16, o0 >> 16, e1 & 0xffffu, o1 & 0xffffu, e1 >> 16, o1 >> 16};
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (n[j]) atomicAdd(&rose[j], n[j]);
+  }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void dir_clear_kernel(unsigned char *__restrict__ flags, unsigned int *__restrict__ centres,
+                                                        unsigned int *__restrict__ rose, unsigned int n) {
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256ull) {
+    if (flags) flags[i] = (unsigned char)0;
+    if (centres) centres[i] = 0u;
+    if (rose) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) rose[i * 8ull + j] = 0u;
+    }
+  }
+}
+
+// Waves per SIMD: as zones_frames_kernel — a workgroup is 16 waves, four per SIMD; a 1080p workgroup takes about 31 KB
+// of LDS, so the lane limit decides: two workgroups per CU, eight waves per SIMD and so at most 64 VGPRs.
+// allows == nullptr: stream_off / n_streams are not read and `allow` serves every frame.
+template <int BLOCK, int UNROLL, int REC>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void dir_frames_kernel(
+    const unsigned char *__restrict__ mv, const WorkItem *__restrict__ work, unsigned int item0, unsigned int n_items, DirK k,
+    const unsigned long long *__restrict__ stream_off, unsigned int n_streams, const unsigned char *__restrict__ allows,
+    unsigned int allow, unsigned char *__restrict__ flags, unsigned int *__restrict__ centres, unsigned int *__restrict__ rose) {
+  extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
+  const unsigned int item = item0 + blockIdx.x;
+  if (item >= n_items) return;
+  const WorkItem me = load_item(work, item);
+  if (me.f == kNoFrame) return;                 // the list has ended (every later entry is past its end too)
+  const int tid = threadIdx.x;
+  unsigned int *tile = lds;
+  unsigned long long *amask = reinterpret_cast<unsigned long long *>(lds + k.tile_words);
+  unsigned int *total = reinterpret_cast<unsigned int *>(amask + (size_t)(k.R + 2) * k.W);
+  unsigned int *lrose = total + 4;
+  const int t0 = max(k.y_lo - 1, 0), t1 = min(k.y_hi + 1, k.gh);
+  const int crows = k.y_hi - k.y_lo;
+
+  // The frame's stream: s = the number of streams that end at or before frame f (binary search, workgroup-uniform
+  // values: scalar code).  s == n_streams: the frame lies behind the last stream and keeps the zeros of the clear.
+  const unsigned int f = __builtin_amdgcn_readfirstlane(me.f);
+  if (allows != nullptr) {
+    unsigned int lo = 0u, hi = n_streams;
+    while (lo < hi) {
+      const unsigned int mid = lo + ((hi - lo) >> 1);
+      if (stream_off[mid + 1u] <= (unsigned long long)f) lo = mid + 1u; else hi = mid;
+    }
+    // in front of the first stream (stream_off[0] > f) the frame belongs to no stream either
+    if (lo >= n_streams || stream_off[lo] > (unsigned long long)f) return;
+    allow = (unsigned int)allows[lo];
+  }
+  // ---- zero the tile, the total and the rose
+  {
+    u32x4 *c4 = reinterpret_cast<u32x4 *>(tile);
+    const int n4 = k.tile_words >> 2;
+    for (int j = tid; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
+    if (tid < 12) total[tid] = 0u;              // total[0 .. 3] and the eight rose words behind them
+  }
+  __syncthreads();
+  // ---- the votes and the rose (an empty analysed range counts nothing: nothing to read)
+  if (crows > 0) {
+    for (unsigned long long r = me.r0; r < me.r1; r += kDirChunk) {      // uniform: one piece unless the frame is huge
+      const unsigned long long n = (me.r1 - r) < kDirChunk ? (me.r1 - r) : kDirChunk;
+      unsigned long long acc = 0ull;
+      const auto one = [=, &k, &acc](const MvFields m) { dir_vote(m, k, t0, tile, allow, acc); };
+      if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + r * 8ull, n, one);
+      else stream_mv40<BLOCK, UNROLL>(mv + r * 40ull, n, one);
+      flush_rose(acc, lrose);
+    }
+  }
+  __syncthreads();
+  // ---- the masks, then the centre count
+  row_masks<BLOCK>(tile, k, t0, t1, k.y_lo - 1, crows + 2, [=, &k](int j, int w, int g, unsigned long long m) {
+    amask[(size_t)j * k.W + w] = m;
+  });
+  __syncthreads();
+  count_centres<BLOCK>(amask, &total[0], k, crows);
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned int c = total[0];
+    if (centres) centres[f] = c;
+    if (flags) flags[f] = (unsigned char)(c >= k.clust_need ? 1 : 0);
+    if (rose) {
+      unsigned int *out = rose + (size_t)f * 8u;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) out[j] = lrose[j];
+    }
+  }
+}
+
+namespace {
+
+template <int REC>
+hipError_t launch_frames(const DirLaunch &L) {
+  auto kern = dir_frames_kernel<kDirBlock, kDirUnroll, REC>;
+  static std::atomic<unsigned long long> ready{0ull};
+  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
+  if (e != hipSuccess) return e;
+  const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
+  return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
+    hipLaunchKernelGGL(kern, dim3(n), dim3(kDirBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.k,
+                       L.stream_off, L.n_streams, L.allows, L.allow, L.flags, L.centres, L.rose);
+  });
+}
+
+}  // namespace
+
+hipError_t launch_dir_scan(const DirLaunch &L) {
+  if (L.n_frames == 0) return hipSuccess;
+  if (L.rec_bytes != 40 && L.rec_bytes != 8) return hipErrorInvalidValue;
+  if (!L.flags && !L.centres && !L.rose) return hipErrorInvalidValue;
+  if (L.allows ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0 || L.allow > 255u))
+    return hipErrorInvalidValue;
+  if (!L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records) return hipErrorInvalidValue;
+  if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.lds_bytes > L.lds_max ||
+      (size_t)L.lds_bytes < dir_lds_bytes(L.k.gw, L.k.R))
+    return hipErrorInvalidValue;
+  {
+    const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
+    hipLaunchKernelGGL(dir_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream, L.flags,
+                       L.centres, L.rose, L.n_frames);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  // flags / centres null: the planner answers nothing itself (the outputs are zero already)
+  hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
+  if (e != hipSuccess) return e;
+  return L.rec_bytes == 8 ? launch_frames<8>(L) : launch_frames<40>(L);
+}
+
+}  // namespace mtgpu

@@ -29,6 +29,7 @@
 #include "gmc_kernels.h"
 #include "gmc_blobs_kernels.h"
 #include "persist_kernels.h"
+#include "dir_kernels.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -2925,6 +2926,220 @@ int mtgpu_persist_flags(mtgpu_ctx *c, const uint8_t *flags, const uint8_t *has_s
   if (flags_out) HIP_TRY(hipMemcpyAsync(flags_out, d + o_out, n, hipMemcpyDeviceToHost, st));
   if (run) HIP_TRY(hipMemcpyAsync(run, d + o_run, words, hipMemcpyDeviceToHost, st));
   if (pos) HIP_TRY(hipMemcpyAsync(pos, d + o_pos, words, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the direction filter (src/motion_scanner.cpp:242-292 per
+// frame, the vote only for records of an allowed sector, and the per-frame rose; include/mtgpu_dir.h)
+
+namespace {
+
+static_assert(sizeof(mt_dir_rose) == 32 && alignof(mt_dir_rose) == 4, "mt_dir_rose is eight uint32");
+
+// One form: the tile, one mask plane, the total and the eight rose words.  It fits or the grid is unsupported.
+int dir_plan(const mt_scan_params &p, int lds_max, mtgpu_dir_plan *out) {
+  const int y_lo = p.vertical_margin;
+  int y_hi = p.grid_h - p.vertical_margin;
+  if (y_hi < y_lo) y_hi = y_lo;
+  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const long long need = (long long)mtgpu::dir_lds_bytes(p.grid_w, R);
+  if (need > (long long)lds_max)
+    return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows, one mask plane and the rose "
+                "(%lld bytes) do not fit %d bytes of LDS; the direction scan has no banded form", p.grid_w, p.grid_h, R + 2, need, lds_max);
+  out->lds_bytes = (int32_t)need;
+  out->workgroup = mtgpu::kDirBlock;
+  out->sectors = 8;
+  out->rose_bytes = (int32_t)sizeof(mt_dir_rose);
+  return MT_OK;
+}
+
+// What the arguments of a direction call decide alone (`d`: "d_" for the device entry point, "" for the host one): no
+// context, no device.
+int dir_check_args(const char *d, const char *allow_name, int rec_bytes, const void *rec, const void *frame_off, uint32_t n_frames,
+                   const void *stream_off, uint32_t n_streams, const void *allows, int32_t allow, const void *flags,
+                   const void *centres, const void *rose) {
+  if (allow < 0 || allow > 255) return fail(MT_ERR_INVALID, "allow %d outside [0,255]", (int)allow);
+  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
+    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
+  if (!flags && !centres && !rose) return fail(MT_ERR_INVALID, "%sflags, %scentres and %srose are all NULL", d, d, d);
+  if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "%sframe_off is NULL", d);
+  if (allows) {
+    if (!stream_off) return fail(MT_ERR_INVALID, "%s%s is given and %sstream_off is NULL", d, allow_name, d);
+    if (n_streams == 0) return fail(MT_ERR_INVALID, "%s%s is given and n_streams is 0", d, allow_name);
+  } else {
+    if (stream_off) return fail(MT_ERR_INVALID, "%sstream_off is given and %s%s is NULL", d, d, allow_name);
+    if (n_streams != 0) return fail(MT_ERR_INVALID, "n_streams is %u and %s%s is NULL", n_streams, d, allow_name);
+  }
+  if (((uintptr_t)frame_off & 7u) != 0) return fail(MT_ERR_INVALID, "%sframe_off must be 8-byte aligned", d);
+  if (((uintptr_t)stream_off & 7u) != 0) return fail(MT_ERR_INVALID, "%sstream_off must be 8-byte aligned", d);
+  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)rec & 7u) != 0)
+    return fail(MT_ERR_INVALID, "%srec: compact records must be 8-byte aligned", d);
+  if (((uintptr_t)rec & 3u) != 0) return fail(MT_ERR_INVALID, "%s must be 4-byte aligned", d[0] ? "d_rec" : "mv");
+  if (((uintptr_t)centres & 3u) != 0) return fail(MT_ERR_INVALID, "%scentres must be 4-byte aligned", d);
+  if (((uintptr_t)rose & 3u) != 0) return fail(MT_ERR_INVALID, "%srose must be 4-byte aligned", d);
+  return MT_OK;
+}
+
+// The direction scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
+int dir_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
+           const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, const uint8_t *d_allow,
+           int32_t allow, uint8_t *d_flags, uint32_t *d_centres, mt_dir_rose *d_rose, hipStream_t st) {
+  mtgpu_dir_plan dp;
+  int rc = dir_plan(c->params, c->lds_max, &dp);
+  if (rc != MT_OK) return rc;
+  mtgpu::DirLaunch L;
+  L.mv = static_cast<const unsigned char *>(d_rec);
+  L.n_records = n_records;
+  L.rebase = rebase;
+  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
+  L.has_sd = d_sd;
+  L.n_frames = n_frames;
+  L.rec_bytes = rec_bytes;
+  L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
+  L.n_streams = n_streams;
+  L.allows = d_allow;
+  L.allow = (unsigned int)allow;
+  L.flags = d_flags; L.centres = d_centres; L.rose = reinterpret_cast<unsigned int *>(d_rose);
+  mtgpu::DirK &k = L.k;
+  std::memset(&k, 0, sizeof k);
+  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.clust_need = c->k.clust_need;
+  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
+  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
+  k.tile_words = (int)mtgpu::dir_tile_words(k.gw, k.R);
+  L.lds_bytes = dp.lds_bytes;
+  L.lds_max = c->lds_max;
+  L.device = c->device;
+  L.stream = st;
+  L.ev_planned = nullptr;
+  void *scratch = nullptr;
+  int slot = -1;
+  rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
+  if (rc != MT_OK) return rc;
+  L.plan_ws = scratch;
+  hipError_t e = hipSuccess;
+  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
+    mtgpu_ctx::Profile &pf = c->prof;
+    std::lock_guard<std::mutex> lock(pf.mu);
+    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
+    if (e == hipSuccess && pf.created) {
+      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
+      e = hipEventRecord(t[0], st);
+      L.ev_planned = t[1];
+      if (e == hipSuccess) e = mtgpu::launch_dir_scan(L);
+      if (e == hipSuccess) e = hipEventRecord(t[2], st);
+      if (e == hipSuccess) ++pf.count;
+    } else if (e == hipSuccess) {
+      e = mtgpu::launch_dir_scan(L);
+    }
+  } else {
+    e = mtgpu::launch_dir_scan(L);
+  }
+  if (slot >= 0) scratch_release(c, slot, st);
+  if (e != hipSuccess) return hip_fail(e, "direction scan launch");
+  return MT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtgpu_dir_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_dir_plan *out) {
+  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
+  int rc = validate_params(p);
+  if (rc != MT_OK) return rc;
+  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
+  mtgpu_dir_plan dp;
+  if ((rc = dir_plan(*p, lds_bytes_per_workgroup, &dp)) != MT_OK) return rc;
+  *out = dp;
+  return MT_OK;
+}
+
+int mtgpu_scan_dir_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
+                          const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
+                          const uint8_t *d_allow, int32_t allow, uint8_t *d_flags, uint32_t *d_centres, mt_dir_rose *d_rose,
+                          void *stream) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  int rc = dir_check_args("d_", "allow", rec_bytes, d_rec, d_frame_off, n_frames, d_stream_off, n_streams, d_allow, allow, d_flags,
+                          d_centres, d_rose);
+  if (rc != MT_OK) return rc;
+  if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  {
+    mtgpu_dir_plan dp;                                       // a grid without a form: before any HIP call
+    if ((rc = dir_plan(c->params, c->lds_max, &dp)) != MT_OK) return rc;
+  }
+  if (n_frames == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  if (d_flags && !on_ctx_device(c, d_flags)) return fail(MT_ERR_INVALID, "d_flags is not memory of device %d", c->device);
+  if (d_centres && !on_ctx_device(c, d_centres)) return fail(MT_ERR_INVALID, "d_centres is not memory of device %d", c->device);
+  if (d_rose && !on_ctx_device(c, d_rose)) return fail(MT_ERR_INVALID, "d_rose is not memory of device %d", c->device);
+  if (c->check_offsets) {
+    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
+    if (rc2 != MT_OK) return rc2;
+  }
+  return dir_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_allow, allow, d_flags,
+                d_centres, d_rose, static_cast<hipStream_t>(stream));
+}
+
+int mtgpu_scan_frames_dir(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
+                          const uint64_t *stream_off, uint32_t n_streams, const uint8_t *allows, int32_t allow, uint8_t *flags,
+                          uint32_t *centres, mt_dir_rose *rose) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  int rc = dir_check_args("", "allows", MT_MV_BYTES, mv, frame_off, n_frames, stream_off, n_streams, allows, allow, flags, centres, rose);
+  if (rc != MT_OK) return rc;
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
+  if (allows) {
+    for (uint32_t s = 0; s < n_streams; ++s)
+      if (stream_off[s + 1] < stream_off[s]) return fail(MT_ERR_INVALID, "stream_off not monotonic at stream %u", s);
+    if (stream_off[n_streams] != (uint64_t)n_frames)
+      return fail(MT_ERR_INVALID, "stream_off[%u] is %llu, not n_frames %u", n_streams, (unsigned long long)stream_off[n_streams], n_frames);
+  }
+  const uint64_t r_begin = n_frames ? frame_off[0] : 0, r_end = n_frames ? frame_off[n_frames] : 0;
+  const uint64_t n_records = r_end - r_begin;
+  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  {
+    mtgpu_dir_plan dp;                                       // a grid without a form: before anything is staged
+    if ((rc = dir_plan(c->params, c->lds_max, &dp)) != MT_OK) return rc;
+  }
+  if (n_frames == 0) return MT_OK;
+
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t soff_bytes = allows ? sizeof(uint64_t) * ((size_t)n_streams + 1) : 0, allow_bytes = allows ? (size_t)n_streams : 0;
+  const size_t words = sizeof(uint32_t) * (size_t)n_frames, rose_bytes = sizeof(mt_dir_rose) * (size_t)n_frames;
+  const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
+  const size_t o_soff = 0, o_allow = o_soff + up(soff_bytes), o_fl = o_allow + up(allow_bytes), o_cen = o_fl + (flags ? up(n_frames) : 0),
+               o_rose = o_cen + (centres ? up(words) : 0), total = o_rose + (rose ? up(rose_bytes) : 0);
+  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
+  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
+  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
+  if (has_sd && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
+  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
+  hipStream_t st = c->stream;
+  DrainOnExit drain{st};
+  if (n_records)
+    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
+  if (has_sd) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
+  if (allows) {
+    HIP_TRY(hipMemcpyAsync(d + o_soff, stream_off, soff_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_allow, allows, allow_bytes, hipMemcpyHostToDevice, st));
+  }
+  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
+  rc = dir_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
+              has_sd ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames,
+              allows ? reinterpret_cast<const uint64_t *>(d + o_soff) : nullptr, n_streams, allows ? d + o_allow : nullptr, allow,
+              flags ? d + o_fl : nullptr, centres ? reinterpret_cast<uint32_t *>(d + o_cen) : nullptr,
+              rose ? reinterpret_cast<mt_dir_rose *>(d + o_rose) : nullptr, st);
+  if (rc != MT_OK) return rc;
+  if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_fl, n_frames, hipMemcpyDeviceToHost, st));
+  if (centres) HIP_TRY(hipMemcpyAsync(centres, d + o_cen, words, hipMemcpyDeviceToHost, st));
+  if (rose) HIP_TRY(hipMemcpyAsync(rose, d + o_rose, rose_bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return MT_OK;
 }

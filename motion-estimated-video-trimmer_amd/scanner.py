@@ -20,7 +20,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi, config
-from ._abi import (BLOB_BOX_DTYPE, BlobsPlanC, COMPACT_DTYPE, LAYOUT_AOS40, LAYOUT_BOXES, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
+from ._abi import (BLOB_BOX_DTYPE, BlobsPlanC, COMPACT_DTYPE, DIR_ALL, DirPlanC, LAYOUT_AOS40, LAYOUT_BOXES, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
                    GMC_DEFAULT_MAX_SHIFT, GMC_DEFAULT_MIN_SHARE_Q8, GMC_INFO_DTYPE, GmcBlobsPlanC, GmcPlanC,
                    MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PersistPlanC, PlanC, ScanParamsC, SweepPlanC, ZonesPlanC, check,
                    load_library)
@@ -246,6 +246,16 @@ def gmc_blobs_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     return {n: getattr(p, n) for n, _ in GmcBlobsPlanC._fields_}
 
 
+def dir_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
+    """How the direction scan runs on the grid of `params` with that much LDS per workgroup (mtgpu_dir_preview): LDS
+    bytes, lanes, sectors of a rose (8), bytes of one rose (32).  Host arithmetic only: works without a GPU.
+    MtgpuError(MT_ERR_UNSUPPORTED) for a grid the direction scan has no form for."""
+    p = DirPlanC()
+    c = params.to_c()
+    check(load_library().mtgpu_dir_preview(C.byref(c), int(lds_bytes), C.byref(p)))
+    return {n: getattr(p, n) for n, _ in DirPlanC._fields_}
+
+
 def persist_preview() -> dict:
     """How the persistence pass runs (mtgpu_persist_preview): lanes per workgroup and the frames a workgroup takes per
     step.  Host only: works without a GPU."""
@@ -258,6 +268,7 @@ ACTIVITY_OUTPUTS = ("active", "centre", "frames")
 PERSIST_OUTPUTS = ("flags", "run", "pos")
 BLOB_OUTPUTS = ("flags", "centres", "blobs", "largest", "box")
 GMC_BLOB_OUTPUTS = BLOB_OUTPUTS + ("info",)
+DIR_OUTPUTS = ("flags", "centres", "rose")
 
 
 def _activity_want(want):
@@ -667,6 +678,78 @@ class MotionScanner:
             None if d_sd is None else d_sd.data_ptr(), n_frames, d_stream_off.data_ptr(), ns, d_keep.data_ptr(),
             ptr(flags), ptr(centres), ptr(centres_all), st))
         return flags, centres, centres_all
+
+    # -------------------------------------------------------- the direction filter
+    def scan_dir(self, batch: FrameBatch, allow: int = DIR_ALL, stream_off=None, allows=None) -> dict:
+        """The centre scan of a host batch in which a record votes only if the sector of dst - src is allowed
+        (mtgpu_scan_frames_dir; the sectors: direction.SECTOR_NAMES, 0 = E, clockwise on the screen), and every frame's
+        rose.  allow: a byte, bit k lets sector k vote (direction.allow_from_names), for every frame; or stream_off
+        (S + 1 frame offsets) with allows (S bytes), one byte per stream.  Returns a dict of numpy arrays over the
+        frames: flags uint8, centres uint32, rose uint32 [F, 8]: the counting records per sector, whatever is allowed."""
+        if (stream_off is None) != (allows is None):
+            raise ValueError("stream_off and allows go together: give both or neither")
+        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
+        n = max(len(off) - 1, 0)
+        soff, ns = None, 0
+        if allows is not None:
+            soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
+            ns = max(len(soff) - 1, 0)
+            given = np.asarray(allows)
+            if given.shape != (ns,) or (ns and (int(given.min()) < 0 or int(given.max()) > 255)):
+                raise ValueError(f"allows: {ns} bytes in 0 .. 255 wanted, one per stream")
+            allows = np.ascontiguousarray(np.concatenate([given.astype(np.uint8), np.zeros(1, dtype=np.uint8)]))   # never empty
+        out = {"flags": np.zeros(n, dtype=np.uint8), "centres": np.zeros(n, dtype=np.uint32), "rose": np.zeros((n, 8), dtype=np.uint32)}
+        check(self._lib.mtgpu_scan_frames_dir(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, _ptr(soff), ns,
+                                              _ptr(allows), int(allow), *(_ptr(out[k]) for k in DIR_OUTPUTS)))
+        return out
+
+    def scan_dir_device(self, d_rec, d_off, d_sd, allow: int = DIR_ALL, d_stream_off=None, d_allow=None, compact=False,
+                        want=DIR_OUTPUTS, out=None, stream=None) -> dict:
+        """Device-resident batch (torch CUDA tensors) -> a dict of CUDA tensors over the frames: flags uint8, centres int32
+        and rose int32 [F, 8] (the bits of the library's uint32 counts); None for an output not in `want`.  d_rec: the
+        packed 40-byte records, or the 8-byte compact ones with compact=True; d_off int64 [F + 1]; d_sd uint8 [F] or
+        None; allow: the byte for every frame, or d_stream_off int64 [S + 1] and d_allow uint8 [S], both or neither.
+        out: a dict of preallocated tensors by name.  Asynchronous on `stream` (default: torch's current stream)."""
+        import torch
+        want = tuple(want)
+        for w in want:
+            if w not in DIR_OUTPUTS:
+                raise ValueError(f"want: {w!r} is not one of {DIR_OUTPUTS}")
+        if (d_stream_off is None) != (d_allow is None):
+            raise ValueError("d_stream_off and d_allow go together: give both or neither")
+        dev = d_off.device
+        n_frames = max(d_off.numel() - 1, 0)
+        res = {}
+        for name in DIR_OUTPUTS:
+            if name not in want:
+                res[name] = None
+                continue
+            dtype = torch.uint8 if name == "flags" else torch.int32
+            shape = (n_frames, 8) if name == "rose" else (n_frames,)
+            t = (out or {}).get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, name
+            res[name] = t
+        if n_frames == 0:              # nothing to write (an empty tensor has no address to hand over)
+            return res
+        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_off.dtype == torch.int64
+        ns = 0
+        if d_allow is not None:
+            ns = max(d_stream_off.numel() - 1, 0)
+            assert d_stream_off.is_contiguous() and d_stream_off.dtype == torch.int64
+            assert d_allow.is_contiguous() and d_allow.dtype == torch.uint8 and d_allow.numel() >= max(ns, 1)
+        rec_bytes = 8 if compact else 40
+        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+        check(self._lib.mtgpu_scan_dir_device(
+            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
+            None if d_sd is None else d_sd.data_ptr(), n_frames, ptr(d_stream_off), ns, ptr(d_allow), int(allow),
+            *(ptr(res[k]) for k in DIR_OUTPUTS), st))
+        return res
 
     # -------------------------------------------------------- global-motion compensation
     def scan_gmc(self, batch: FrameBatch, max_shift: int = GMC_DEFAULT_MAX_SHIFT, min_share_q8: int = GMC_DEFAULT_MIN_SHARE_Q8):

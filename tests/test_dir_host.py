@@ -1,0 +1,515 @@
+"""CPU tier: the direction filter (include/mtgpu_dir.h) exists at every layer — header, library, ctypes table, Python
+package, command, example — sizes its launch with host arithmetic alone, rejects bad arguments before any HIP call and
+has no fallback without a device; the sector rule of direction.py is the header's, with its four symmetries; and the
+model of tests/dir_model.py, which tests/test_gpu_dir.py holds the kernel to, equals the unchanged oracle on filtered
+records (consequence C) and every hand-derived number of tests/dir_inputs.py."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import mvtrim_amd as m
+from mvtrim_amd import _abi, config, direction
+
+import dir_inputs as di
+import dir_model as dm
+import oracle_binding as ob
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "motion-estimated-video-trimmer_amd", "csrc")
+MI355X_LDS = 163840
+
+NEW_SYMBOLS = ["mtgpu_dir_preview", "mtgpu_scan_dir_device", "mtgpu_scan_frames_dir"]
+
+
+def dir_header():
+    return open(os.path.join(ROOT, "include", "mtgpu_dir.h")).read()
+
+
+def vp(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# ------------------------------------------------------------------ symbols, headers, example
+
+def test_entry_points_are_declared_exported_and_prototyped():
+    lib = m.load_library()
+    hdr = dir_header()
+    declared = sorted(set(re.findall(r"\b(mtgpu_[a-z_]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))))
+    assert declared == NEW_SYMBOLS == sorted(_abi.ABI_DIR)
+    for n in NEW_SYMBOLS:
+        fn = getattr(lib, n)                      # AttributeError: not exported by libmtgpu.so
+        assert fn.restype is C.c_int and fn.argtypes == _abi.ABI_DIR[n][1], n
+        assert n not in _abi.ABI                  # mtgpu.h's own text does not declare it
+        # every declaration names the reference lines it stands for
+        at = hdr.index("int " + n + "(")
+        assert "src/motion_scanner.cpp:" in hdr[hdr.rindex("\n/*", 0, at):at], n
+    assert C.sizeof(_abi.DirPlanC) == 16
+    assert [f for f, _ in _abi.DirPlanC._fields_] == ["lds_bytes", "workgroup", "sectors", "rose_bytes"]
+    assert "#define MTGPU_DIR_ALL 0xFF" in hdr and _abi.DIR_ALL == 0xFF
+    # mtgpu.h hands the declarations to everyone who includes it, ahead of the persistence header
+    top = open(os.path.join(ROOT, "include", "mtgpu.h")).read()
+    assert 0 < top.index('#include "mtgpu_dir.h"') < top.index('#include "mtgpu_persist.h"')
+    assert not any(n in top for n in NEW_SYMBOLS)
+    # the header states the rule, the consequences the tests rest on and what is out of scope
+    flat = " ".join(hdr.replace("*", " ").split())
+    for text in ("12 ay <= 5 ax", "12 ax <= 5 ay", "5-12-13 triangle", "22.62 degrees", "22.5", "A tie on a boundary belongs to the axis sector",
+                 "A. allow == 0xFF gives the flags and centres of mtgpu_scan_centres_device bit for bit",
+                 "B. rose does not depend on allow", "C. Removal", "D. Rotation", "E. Monotone", "F. vn == 0 gives the plain centre scan",
+                 "Out of scope: keep masks, blobs and compensation", "the pipe, the C++ host layer and mtgpu_scan_file",
+                 "a per-cell allow plane", "the sign of mt_mv.source", "MT_ERR_UNSUPPORTED with the grid named"):
+        assert text in flat, text
+    src = open(os.path.join(CSRC, "dir_kernels.hip")).read()
+    assert "getenv" not in src and "__gfx950__" in src and "#error" in src
+    assert "amdgpu_waves_per_eu(8, 8)" in src and "__launch_bounds__(BLOCK)" in src
+    # record_stream.h serves the new kernel as it is: the functor lives in the new file
+    assert "stream_compact<BLOCK, UNROLL>" in src and "stream_mv40<BLOCK, UNROLL>" in src and "dir_vote" in src
+    # the kernels are in the library, and nothing of the checker is
+    blob = open(_abi.LIB_PATH, "rb").read()
+    assert b"dir_frames_kernel" in blob and b"dir_clear_kernel" in blob
+    syms = subprocess.check_output(["nm", "-D", "--defined-only", _abi.LIB_PATH]).decode()
+    assert "mto_" not in syms
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert "dir_kernels.hip" in mk and "dir_kernels.h " in mk and "mtgpu_dir.h" in mk
+
+
+def test_headers_compile_as_c_and_cpp_either_one_first(tmp_path):
+    body = ("int use(mtgpu_ctx *c) {\n"
+            "  mtgpu_dir_plan p;\n"
+            "  mt_dir_rose r = {{0, 0, 0, 0, 0, 0, 0, 0}};\n"
+            "  return mtgpu_dir_preview(0, 163840, &p)\n"
+            "       + mtgpu_scan_dir_device(c, 0, 40, 0, 0, 0, 0, 0, 0, 0, MTGPU_DIR_ALL, 0, 0, &r, 0)\n"
+            "       + mtgpu_scan_frames_dir(c, 0, 0, 0, 0, 0, 0, 0, MTGPU_DIR_ALL, 0, 0, &r)\n"
+            "       + p.lds_bytes + p.workgroup + p.sectors + p.rose_bytes + (int)sizeof(mt_dir_rose);\n}\n")
+    for first in ("mtgpu.h", "mtgpu_dir.h", "mtgpu_persist.h"):
+        src = tmp_path / ("use_" + first.replace(".", "_") + ".c")
+        src.write_text('#include "%s"\n#include "mtgpu_dir.h"\n%s' % (first, body))
+        for comp, flag, lang in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "c++")):
+            subprocess.check_call([comp, flag, "-Wall", "-Werror", "-fsyntax-only", "-x", lang,
+                                   "-I" + os.path.join(ROOT, "include"), str(src)])
+
+
+def test_plain_c_example_compiles():
+    """examples/dir_example.c against the headers as they are (it runs in the GPU tier)."""
+    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "dir_example.c")])
+
+
+def test_canary_program_builds(tmp_path):
+    """The plain-C contract program of the GPU tier compiles and links against the ABI (it cannot run without a device)."""
+    pkg = os.path.dirname(m.LIB_PATH)
+    exe = str(tmp_path / "abi_dir_canaries")
+    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c", "abi_dir_canaries.c"),
+                           "-o", exe, "-L" + pkg, "-lmtgpu", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + pkg,
+                           "-Wl,-rpath,/opt/rocm/lib"])
+    assert os.path.exists(exe)
+
+
+def test_package_exports_the_methods():
+    for name in ("scan_dir", "scan_dir_device"):
+        assert callable(getattr(m.MotionScanner, name)), name
+    assert callable(m.dir_preview) and "dir_preview" in m.__all__
+    for name in ("sector_of", "allow_from_names", "names_from_allow", "rotate_allow", "mirror_allow", "main", "measure", "parser"):
+        assert callable(getattr(direction, name)), name
+    assert direction.SECTOR_NAMES == ("E", "SE", "S", "SW", "W", "NW", "N", "NE")
+
+
+# ------------------------------------------------------------------ preview
+
+def preview(params, lds=MI355X_LDS):
+    p = _abi.DirPlanC()
+    c = params.to_c()
+    rc = m.load_library().mtgpu_dir_preview(C.byref(c), lds, C.byref(p))
+    return rc, p, m.load_library().mtgpu_last_error().decode()
+
+
+def lds_by_hand(gw, R):
+    """csrc/dir_kernels.h: the tile, one plane of R + 2 mask rows, 16 bytes of totals, the eight rose words."""
+    W = (gw + 63) // 64
+    return 4 * (((R + 2) * gw + 3) & ~3) + (R + 2) * W * 8 + 16 + 32
+
+
+def test_preview_sizes_the_launch():
+    # 1080p under the code defaults: 120 x 68 cells, margin 3, R = 62: 64 x 120 x 4 = 30 720 bytes of tile, 64 x 2 x 8 = 1 024
+    # of masks, 48: 31 792.  4K: 240 x 135, margin 6, R = 123: 125 x 240 x 4 = 120 000, 125 x 4 x 8 = 4 000, 48: 124 048.
+    assert lds_by_hand(120, 62) == 31792 and lds_by_hand(240, 123) == 124048
+    for (w, h, kw), (gw, gh, R) in [((1920, 1080, config.CODE_DEFAULTS), (120, 68, 62)), ((3840, 2160, config.CODE_DEFAULTS), (240, 135, 123)),
+                                     ((3840, 2160, dict(vertical_mask=0.0)), (240, 135, 135)), ((1280, 720, {}), (80, 45, 41)),
+                                     ((48, 48, dict(vertical_mask=0.0)), (3, 3, 3)), ((1920, 1080, dict(vertical_mask=0.5)), (120, 68, 1))]:
+        params = m.ScanParams.from_config(w, h, **kw)
+        assert (params.grid_w, params.grid_h) == (gw, gh)
+        assert max(1, gh - 2 * params.vertical_margin) == R
+        rc, p, msg = preview(params)
+        assert rc == _abi.MT_OK, msg
+        assert (p.workgroup, p.sectors, p.rose_bytes) == (1024, 8, 32)
+        assert p.lds_bytes == lds_by_hand(gw, R) <= MI355X_LDS
+        assert m.dir_preview(params) == {"lds_bytes": p.lds_bytes, "workgroup": 1024, "sectors": 8, "rose_bytes": 32}
+    assert preview(m.ScanParams.from_config(1920, 1080, **config.CODE_DEFAULTS))[1].lds_bytes == 31792
+    assert preview(m.ScanParams.from_config(3840, 2160, **config.CODE_DEFAULTS))[1].lds_bytes == 124048
+    # two 1080p workgroups of 1024 lanes per CU are limited by lanes, not LDS; 4K sits alone on its CU
+    assert 2 * 31792 <= MI355X_LDS < 2 * 124048
+    # the grids the plain scan cuts into row bands have no form; nor has 1080p on a device with 16 KB
+    rc, _, msg = preview(m.ScanParams.from_config(3840, 2160, block_size=4, block_shift=2))
+    assert rc == _abi.MT_ERR_UNSUPPORTED and "960x540" in msg
+    rc, _, msg = preview(m.ScanParams.from_config(32767, 3, block_size=1, block_shift=0, vertical_mask=0.0))
+    assert rc == _abi.MT_ERR_UNSUPPORTED and "32767x3" in msg
+    rc, _, msg = preview(m.ScanParams.from_config(1920, 1080), 16384)
+    assert rc == _abi.MT_ERR_UNSUPPORTED and "120x68" in msg
+    with pytest.raises(m.MtgpuError) as ei:
+        m.dir_preview(m.ScanParams.from_config(3840, 2160, block_size=4, block_shift=2))
+    assert ei.value.code == _abi.MT_ERR_UNSUPPORTED and "960x540" in str(ei.value)
+    # invalid
+    lib = m.load_library()
+    c = m.ScanParams.from_config(1920, 1080).to_c()
+    assert lib.mtgpu_dir_preview(None, MI355X_LDS, C.byref(_abi.DirPlanC())) == _abi.MT_ERR_INVALID
+    assert lib.mtgpu_dir_preview(C.byref(c), MI355X_LDS, None) == _abi.MT_ERR_INVALID
+    assert lib.mtgpu_dir_preview(C.byref(c), 100, C.byref(_abi.DirPlanC())) == _abi.MT_ERR_INVALID
+
+
+# ------------------------------------------------------------------ error paths that need no device
+
+def test_invalid_arguments_are_rejected_without_a_device():
+    """Everything the arguments alone decide is answered before the context is looked at: no HIP call, no byte written."""
+    lib = m.load_library()
+    inv = _abi.MT_ERR_INVALID
+    one = C.c_void_p(64)          # never dereferenced
+    odd = C.c_void_p(68)
+
+    def err():
+        return lib.mtgpu_last_error().decode()
+
+    def dev(rec=one, rb=40, nrec=1, off=one, n=1, soff=None, ns=0, al=None, allow=255, fl=one, ce=one, ro=one):
+        return lib.mtgpu_scan_dir_device(None, rec, rb, nrec, off, None, n, soff, ns, al, allow, fl, ce, ro, None)
+
+    for allow in (-1, 256, 1 << 20, -(1 << 31)):
+        assert dev(allow=allow) == inv and "allow" in err() and "[0,255]" in err()
+        assert dev(allow=allow, soff=one, ns=1, al=one) == inv and "allow" in err()      # in range even where it is not used
+    for rb in (0, 7, 16, 39, 41, -8):
+        assert dev(rb=rb) == inv and "rec_bytes" in err()
+    assert dev(fl=None, ce=None, ro=None) == inv and "all NULL" in err()
+    assert dev(off=None) == inv and "d_frame_off" in err()
+    assert dev(al=one) == inv and "d_allow is given" in err() and "d_stream_off" in err()
+    assert dev(al=one, soff=one) == inv and "d_allow is given" in err() and "n_streams" in err()
+    assert dev(soff=one) == inv and "d_stream_off is given" in err() and "d_allow is NULL" in err()
+    assert dev(ns=2) == inv and "n_streams is 2" in err() and "d_allow is NULL" in err()
+    assert dev(off=odd) == inv and "d_frame_off" in err() and "aligned" in err()
+    assert dev(soff=odd, ns=1, al=one) == inv and "d_stream_off" in err() and "aligned" in err()
+    assert dev(rec=None) == inv and "d_rec" in err()
+    assert dev(rec=odd, rb=8) == inv and "d_rec" in err() and "8-byte" in err()
+    assert dev(rec=C.c_void_p(66)) == inv and "d_rec" in err()
+    assert dev(ce=C.c_void_p(66)) == inv and "d_centres" in err()
+    assert dev(ro=C.c_void_p(66)) == inv and "d_rose" in err()
+    assert dev() == inv and "ctx" in err()
+    assert dev(soff=one, ns=1, al=one) == inv and "ctx" in err()
+
+    rose = np.full((2, 8), 7, dtype=np.uint32)
+    out = np.full(3, 7, dtype=np.uint32)
+    fl = np.full(3, 7, dtype=np.uint8)
+    mv = np.zeros(8, dtype=m.MV_DTYPE)
+    al = np.zeros(2, dtype=np.uint8)
+    good_off, good_soff = np.array([0, 4, 8], dtype=np.uint64), np.array([0, 2], dtype=np.uint64)
+
+    def host(off=good_off, soff=None, ns=0, a=None, allow=255, f=fl, c=out, r=rose, recs=mv):
+        return lib.mtgpu_scan_frames_dir(None, vp(recs), vp(off), None, 2, vp(soff), ns, vp(a), allow, vp(f), vp(c), vp(r))
+
+    assert host(allow=256) == inv and "allow" in err()
+    assert host(f=None, c=None, r=None) == inv and "all NULL" in err()
+    assert host(off=None) == inv and "frame_off" in err()
+    assert host(a=al) == inv and "allows is given" in err()
+    assert host(soff=good_soff) == inv and "allows is NULL" in err()
+    assert host(off=np.array([0, 9, 8], dtype=np.uint64)) == inv and "frame_off not monotonic" in err()
+    assert host(soff=np.array([0, 2, 1], dtype=np.uint64), ns=2, a=al) == inv and "stream_off not monotonic" in err()
+    assert host(soff=np.array([0, 1], dtype=np.uint64), ns=1, a=al) == inv and "stream_off[1]" in err() and "n_frames" in err()
+    assert host(recs=None) == inv and "mv is NULL" in err()
+    assert host() == inv and "ctx" in err()
+    assert host(soff=good_soff, ns=1, a=al) == inv and "ctx" in err()
+    assert out.tolist() == [7, 7, 7] and fl.tolist() == [7, 7, 7] and (rose == 7).all()
+
+
+def test_no_fallback_without_a_device(tmp_path):
+    """A context cannot be created without a device (MT_ERR_DEVICE, "no CPU fallback"), and the command, given a
+    readable file, prints its document with a device and fails with that message without one."""
+    mv = np.zeros(4, dtype=m.MV_DTYPE)
+    mv["dst_x"], mv["dst_y"], mv["src_x"], mv["src_y"] = [40, 41, 56, 57], 40, [30, 31, 66, 67], 40
+    path = str(tmp_path / "two.mtmv")
+    m.mvfile.write_mtmv(path, 160, 160, 1, 1000, 25.0, 1.0, [0, 40], [mv, None])
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    out = subprocess.run([sys.executable, "-m", "mvtrim_amd.direction", path, "--mv-threshold-sq", "4", "--vectors-needed", "2",
+                          "--clusters-needed", "1", "--vertical-mask", "0", "--ignore", "W", "--json"],
+                         capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
+    if m.load_library().mtgpu_device_count() > 0:
+        # cells (2, 2) and (3, 2) of a 10 x 10 grid hold two votes each, the first moving east, the second west: two
+        # centres; without W a single active cell is left
+        import json
+        assert out.returncode == 0, out.stderr
+        doc = json.loads(out.stdout)
+        assert doc["all"]["centres"] == 2 and doc["mask"]["centres"] == 0 and doc["mask"]["sectors"] == "E,SE,S,SW,NW,N,NE"
+        assert [t["records"] for t in doc["rose"]] == [2, 0, 0, 0, 2, 0, 0, 0]
+        return
+    assert out.returncode != 0 and out.stdout == ""
+    assert "no CPU fallback" in out.stderr
+    with pytest.raises(m.MtgpuError) as ei:
+        m.MotionScanner(m.ScanParams.from_config(160, 160))
+    assert ei.value.code == _abi.MT_ERR_DEVICE and "no CPU fallback" in str(ei.value)
+
+
+# ------------------------------------------------------------------ direction.py
+
+def test_sector_of_on_the_boundary_table():
+    for (dx, dy), k in di.BOUNDARY:
+        assert int(direction.sector_of(dx, dy)) == k, (dx, dy)
+    assert int(direction.sector_of(0, 0)) == -1
+    # the eight sectors by their names, clockwise on the screen from east, y downwards
+    assert [int(direction.sector_of(dx, dy)) for dx, dy in di.DISP] == list(range(8))
+    for (dx, dy), name in (((1, 0), "E"), ((1, 1), "SE"), ((0, 1), "S"), ((-1, 1), "SW"), ((-1, 0), "W"), ((-1, -1), "NW"),
+                           ((0, -1), "N"), ((1, -1), "NE")):
+        assert direction.SECTOR_NAMES[int(direction.sector_of(dx, dy))] == name
+    # the axis tests cannot both hold unless ax = ay = 0; all products fit 32 bits
+    assert 12 * 65535 < 2 ** 31
+
+
+def _symmetries(dx, dy):
+    k = direction.sector_of(dx, dy)
+    moving = k >= 0
+    assert ((k >= -1) & (k <= 7)).all()
+    assert np.array_equal(direction.sector_of(-dy, dx)[moving], (k[moving] + 2) & 7)
+    assert np.array_equal(direction.sector_of(-dx, dy)[moving], (4 - k[moving]) & 7)
+    assert np.array_equal(direction.sector_of(dx, -dy)[moving], (8 - k[moving]) & 7)
+    assert np.array_equal(direction.sector_of(dy, dx)[moving], (2 - k[moving]) & 7)
+    for other in (direction.sector_of(-dy, dx), direction.sector_of(-dx, dy), direction.sector_of(dx, -dy), direction.sector_of(dy, dx)):
+        assert (other[~moving] == -1).all()
+    return k
+
+
+def test_sector_of_has_its_four_symmetries():
+    dy, dx = np.mgrid[-60:61, -60:61]
+    k = _symmetries(dx.reshape(-1), dy.reshape(-1))
+    assert int((k < 0).sum()) == 1
+    # every sector is met, the four axis sectors equally often and the four diagonal ones equally often
+    n = np.bincount(k[k >= 0], minlength=8)
+    assert n.min() > 0 and len({int(n[0]), int(n[2]), int(n[4]), int(n[6])}) == 1 and len({int(n[1]), int(n[3]), int(n[5]), int(n[7])}) == 1
+    # at the ends of the range
+    big = np.array([65535, -65535, 27306, -27306, 27307, -27307, 0, 1, -1, 32767, -32768])
+    bx, by = np.meshgrid(big, big)
+    _symmetries(bx.reshape(-1), by.reshape(-1))
+    # the restatement against the header's rule written out in Python integers
+    rng = np.random.RandomState(5)
+    for dx, dy in rng.randint(-65535, 65536, size=(2000, 2)).tolist() + [[12, 5], [-12, 5], [5, -12], [-5, -12]]:
+        ax, ay = abs(dx), abs(dy)
+        if dx == 0 and dy == 0:
+            want = -1
+        elif 12 * ay <= 5 * ax:
+            want = 0 if dx > 0 else 4
+        elif 12 * ax <= 5 * ay:
+            want = 2 if dy > 0 else 6
+        else:
+            want = (1 if dy > 0 else 7) if dx > 0 else (3 if dy > 0 else 5)
+        assert int(direction.sector_of(dx, dy)) == want, (dx, dy)
+
+
+def test_helper_round_trips():
+    for allow in range(256):
+        assert direction.allow_from_names(direction.names_from_allow(allow)) == allow
+        assert direction.rotate_allow(direction.rotate_allow(allow, 2), 6) == allow
+        assert direction.rotate_allow(allow, 8) == allow and direction.rotate_allow(allow, 0) == allow
+        assert direction.mirror_allow(direction.mirror_allow(allow)) == allow
+        assert bin(direction.rotate_allow(allow, 3)).count("1") == bin(allow).count("1") == bin(direction.mirror_allow(allow)).count("1")
+    assert direction.allow_from_names("E,SE") == 0x03 and direction.allow_from_names(["w", " nw"]) == 0x30
+    assert direction.allow_from_names("all") == 0xFF and direction.allow_from_names("") == 0 and direction.allow_from_names("none") == 0
+    assert direction.names_from_allow(0x03) == "E,SE" and direction.names_from_allow(0xFF) == "all" and direction.names_from_allow(0) == "none"
+    # a quarter turn clockwise takes E to S; the mirror takes E to W, SE to SW, and leaves S and N
+    assert direction.rotate_allow(0x01) == 0x04 and direction.rotate_allow(0x80) == 0x02
+    assert direction.mirror_allow(0x01) == 0x10 and direction.mirror_allow(0x02) == 0x08 and direction.mirror_allow(0x44) == 0x44
+    # bit k of the turned / mirrored byte is bit (k - 2) / (4 - k) of the byte: what sector_of's symmetries ask for
+    for allow in (0x01, 0x5B, 0xA4):
+        for k in range(8):
+            assert (direction.rotate_allow(allow) >> ((k + 2) & 7)) & 1 == (allow >> k) & 1
+            assert (direction.mirror_allow(allow) >> ((4 - k) & 7)) & 1 == (allow >> k) & 1
+    assert direction.wedge(0) == 0x83 and direction.wedge(4) == 0x38
+    for bad in ("X", "E,,W", "EAST"):
+        with pytest.raises(ValueError):
+            direction.allow_from_names(bad)
+    for bad in (-1, 256):
+        with pytest.raises(ValueError):
+            direction.names_from_allow(bad)
+
+
+def test_direction_options_parse():
+    a = direction.parser().parse_args(["f.mtmv", "--ignore", "W,NW,SW", "--each", "--keep-level", "3", "--json", "--width", "1920",
+                                       "--height", "1080", "--duration", "12.5", "--vertical-mask", "0", "--vectors-needed", "3"])
+    assert a.ignore == 0x38 and a.allow is None and a.each and a.keep_level == 3 and a.json
+    assert (a.width, a.height, a.duration) == (1920, 1080, 12.5)
+    a = direction.parser().parse_args(["f", "--allow", "E,NE"])
+    assert a.allow == 0x81 and a.ignore is None and not a.each and a.keep_level is None
+
+
+@pytest.mark.parametrize("bad", [["--allow", "X"], ["--ignore", "E,Q"], ["--allow", "E", "--ignore", "W"], ["--keep-level", "0"],
+                                 ["--keep-level", "x"], ["--keep-level", "-2"]])
+def test_direction_bad_options_exit_2_before_any_device_is_touched(bad, monkeypatch):
+    """argparse's exit code 2, and neither the file nor a scanner has been looked at."""
+    def boom(*a, **k):
+        raise AssertionError("touched before the arguments were valid")
+    monkeypatch.setattr(direction, "MotionScanner", boom)
+    monkeypatch.setattr(direction.tune, "load", boom)
+    monkeypatch.setattr(direction.ScanParams, "from_config", boom)
+    with pytest.raises(SystemExit) as ei:
+        direction.main(["nothing_here.mtmv"] + bad)
+    assert ei.value.code == 2
+
+
+def test_direction_missing_geometry_exits_2_and_missing_file_1(tmp_path, monkeypatch):
+    def boom(*a, **k):
+        raise AssertionError("a scanner was created before the arguments were valid")
+    monkeypatch.setattr(direction, "MotionScanner", boom)
+    path = str(tmp_path / "one.json")
+    m.mvjson.write_json(path, [np.zeros(1, dtype=m.MV_DTYPE)], [0.0])           # a JSON carries no width / height / duration
+    with pytest.raises(SystemExit) as ei:
+        direction.main([path])
+    assert ei.value.code == 2
+    assert direction.main([str(tmp_path / "nothing_here.json")]) == 1
+
+
+# ------------------------------------------------------------------ the model, the oracle and the hand values
+
+def check_case(c, allows=None):
+    """The model equals the oracle on filtered records (consequence C) and the case's hand values; returns the model's
+    (flags, centres, rose)."""
+    p, mv, off, sd = c["params"], c["mv"], c["off"], c["sd"]
+    kw = dict(allow=c["allow"], soff=c["soff"], allows=c["allows"]) if allows is None else allows
+    fl, ce, rose = dm.model_batch(p, mv, off, sd, **kw)
+    ofl, oce = dm.oracle_batch(p, mv, off, sd, **kw)
+    assert ce.tolist() == oce.tolist() and fl.tolist() == ofl.tolist()
+    # consequence B: the rose's sum is the number of counting records that move, and allow = all gives the same rose
+    assert rose.sum(axis=1).tolist() == np.where(dm.frame_allows(len(off) - 1, **kw) >= 0, dm.counting_moving(p, mv, off, sd), 0).tolist()
+    return fl, ce, rose
+
+
+@pytest.mark.parametrize("name", sorted(di.HAND_CASES))
+def test_hand_frames(name):
+    c = di.HAND_CASES[name]()
+    fl, ce, rose = check_case(c)
+    assert ce.tolist() == c["hand_centres"].tolist() and rose.tolist() == c["hand_rose"].tolist()
+    # the scalar form gives each stream's values when it is handed that stream's byte
+    for s, allow in enumerate(c["allows"].tolist()):
+        a, b = int(c["soff"][s]), int(c["soff"][s + 1])
+        _, ce1, rose1 = dm.model_batch(c["params"], c["mv"], c["off"], c["sd"], allow=allow)
+        assert ce1[a:b].tolist() == ce[a:b].tolist() and rose1[a:b].tolist() == rose[a:b].tolist()
+
+
+def test_vn0_is_the_plain_scan_whatever_allow_is():
+    c = di.vn0_case()
+    plain = ob.scan_centres(c["params"], c["mv"], c["off"], c["sd"])[1]
+    for allow in (0x00, 0x01, 0xFF):
+        assert dm.model_batch(c["params"], c["mv"], c["off"], c["sd"], allow=allow)[1].tolist() == plain.tolist() == [20, 20, 20]
+
+
+def test_streamer_edge_input():
+    c = di.edge_case()
+    fl, ce, rose = check_case(c)
+    assert rose.tolist() == c["hand_rose"].tolist()
+    lengths = np.diff(c["off"].astype(np.int64))[c["test"]]
+    assert lengths.tolist() == di.EDGE_LENGTHS * 16
+    assert sorted(set((c["start"] % 16).tolist())) == list(range(16))
+    # the pad frames hold records and have no side data; the long frames hold centres under the mask and more without
+    pads = np.setdiff1d(np.arange(len(c["sd"])), c["test"])
+    assert not c["sd"][pads].any() and int(np.diff(c["off"].astype(np.int64))[pads].max()) == 15
+    allc = dm.model_batch(c["params"], c["mv"], c["off"], c["sd"], allow=0xFF)[1]
+    long_ones = c["test"][lengths >= 4095]
+    assert (ce[long_ones] > 0).all() and (allc[long_ones] > ce[long_ones]).all()
+    # neighbours differ in sector
+    sec = direction.sector_of(*dm.displacement(di.edge_frame(8207)))
+    assert (sec[1:] != sec[:-1]).all() and sec.min() == 0 and sec.max() == 7
+
+
+@pytest.mark.parametrize("gw", [65, 129])
+def test_word_seam_hand_values(gw):
+    c = di.seam_case(gw)
+    fl, ce, rose = check_case(c)
+    assert ce.tolist() == c["hand_centres"].tolist() == di.SEAM_HAND[gw] and rose.tolist() == c["hand_rose"].tolist()
+    assert (c["params"].grid_w + 63) // 64 == (2 if gw == 65 else 3)
+
+
+def test_counter_width_input():
+    c = di.width_case()
+    fl, ce, rose = check_case(c)
+    want = [1] * 8
+    want[di.WIDTH_SECTOR] = di.WIDTH_N
+    assert rose.tolist() == [want] == c["hand_rose"].tolist() and di.WIDTH_N > 256 * 1024
+    allc = dm.model_batch(c["params"], c["mv"], c["off"], c["sd"], allow=0xFF)[1]
+    assert ce.tolist() == [0] and allc[0] == 6 * 78                  # without sector 3 no cell holds three votes
+
+
+def test_extreme_input():
+    c = di.extreme_case()
+    fl, ce, rose = check_case(c)
+    assert rose.tolist() == c["hand_rose"].tolist() == [di.EXTREME_ROSE] * 2
+    dx, dy = dm.displacement(c["mv"][:len(di.EXTREME_RECORDS)])
+    assert {(65535, 0), (-65535, 0), (0, 65535), (0, -65535), (65535, 27306), (65535, 27307)} <= set(zip(dx.tolist(), dy.tolist()))
+
+
+def test_stream_input():
+    c = di.stream_case()
+    fl, ce, rose = check_case(c)
+    sizes = np.diff(c["soff"].astype(np.int64)).tolist()
+    F = len(c["sd"])
+    assert sizes == di.STREAM_SIZES and int(c["soff"][0]) == 3 and F - int(c["soff"][-1]) == 5
+    orphan = np.r_[0:3, F - 5:F]
+    assert not ce[orphan].any() and not rose[orphan].any() and (np.diff(c["off"].astype(np.int64))[orphan] > 0).all()
+    k = di.STREAM_KEY_FRAME
+    assert int(c["soff"][3]) <= k < int(c["soff"][4]) and c["sd"][k] == 0 and ce[k] == 0 and not rose[k].any()
+    assert int(c["off"][k + 1]) > int(c["off"][k])
+    # the streams differ: the counts under the streams' bytes are not those of one byte for all
+    check_case(c, dict(allow=c["scalar_allow"]))
+    one = dm.model_batch(c["params"], c["mv"], c["off"], c["sd"], allow=c["scalar_allow"])[1]
+    assert (one != ce).sum() > 20 and (ce > 0).sum() > 40 and 0 < fl.sum() < F
+
+
+@pytest.mark.parametrize("i", range(di.N_DRAWS))
+def test_random_draws_have_the_consequences(i):
+    """A (the plain oracle), B, C (inside check_case), D by rotation and by mirror, E, F on draw i — all on the model."""
+    c = di.draw(i)
+    p, mv, off, sd = c["params"], c["mv"], c["off"], c["sd"]
+    assert p.vectors_needed == i % 4 and p.vertical_margin in (0, (i // 4) % 4) and len(sd) <= 12
+    assert int(np.diff(off.astype(np.int64)).max()) <= 3000
+    plain_f, plain_c = ob.scan_centres(p, mv, off, sd, nthreads=4)
+    prev = None
+    roses = []
+    for allow in di.DRAW_ALLOWS:
+        fl, ce, rose = check_case(c, dict(allow=allow))
+        roses.append(rose)
+        if prev is not None:
+            assert (prev <= ce).all()                                                      # E
+        prev = ce
+        if p.vectors_needed == 0:
+            assert ce.tolist() == plain_c.tolist()                                         # F
+        for turn, perm, other in ((di.rotated, lambda k: (k + 2) & 7, direction.rotate_allow(allow, 2)),
+                                  (di.mirrored, lambda k: (4 - k) & 7, direction.mirror_allow(allow))):
+            _, ce2, rose2 = dm.model_batch(p, turn(mv), off, sd, allow=other)
+            assert ce2.tolist() == ce.tolist()                                             # D
+            assert rose2[:, [perm(k) for k in range(8)]].tolist() == rose.tolist()
+    assert prev.tolist() == plain_c.tolist() and fl.tolist() == plain_f.tolist()           # A
+    assert all(r.tolist() == roses[0].tolist() for r in roses)                             # B
+    assert all(a == b or (a & b) == a for a, b in zip(di.DRAW_ALLOWS, di.DRAW_ALLOWS[1:]))
+
+
+def test_random_draws_count_something():
+    """Over the forty draws: every vectors_needed and margin, most draws with centres, most lose some to a mask, every
+    sector in the roses."""
+    seen_vn, seen_margin, with_centres, losing, sectors = set(), set(), 0, 0, np.zeros(8, dtype=np.int64)
+    for i in range(di.N_DRAWS):
+        c = di.draw(i)
+        p = c["params"]
+        seen_vn.add(p.vectors_needed)
+        seen_margin.add(p.vertical_margin)
+        _, full, rose = dm.model_batch(p, c["mv"], c["off"], c["sd"], allow=0xFF)
+        _, part, _ = dm.model_batch(p, c["mv"], c["off"], c["sd"], allow=0x1B)
+        with_centres += int(full.sum() > 0)
+        losing += int((part < full).any())
+        sectors += rose.sum(axis=0).astype(np.int64)
+    assert seen_vn == {0, 1, 2, 3} and seen_margin == {0, 1, 2, 3}
+    assert with_centres >= 30 and losing >= 20 and (sectors > 0).all()
