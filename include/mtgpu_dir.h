@@ -67,7 +67,7 @@
  *  F. vn == 0 gives the plain centre scan, whatever allow is: no cell needs a vote.
  *
  * Out of scope: keep masks, blobs and compensation next to the direction test; the pipe, the C++ host layer and
- * mtgpu_scan_file; a per-cell allow plane; the sign of mt_mv.source — a compact record does not carry it, and the test
+ * mtgpu_scan_file (these, with the pipe's keep mask, are in mtgpu_pipe_dir.h); a per-cell allow plane; the sign of mt_mv.source — a compact record does not carry it, and the test
  * reads dst - src as the vote does; the row-banded grids (960x540 cells, 32767-wide grids: the class every sibling
  * rejects), which are MT_ERR_UNSUPPORTED with the grid named.
  *

@@ -303,6 +303,13 @@ ABI_DIR = {
 }
 DIR_ALL, DIR_SECTORS = 0xFF, 8
 
+# name -> (restype, argtypes): every symbol include/mtgpu_pipe_dir.h declares (the direction setting of a pipe; mtgpu.h includes it).
+ABI_PIPE_DIR = {
+    "mtgpu_pipe_set_dir": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int]),
+    "mtgpu_pipe_dir": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+}
+MT_PIPE_REPORT_SECTORS = 3
+
 _lib = None
 
 
@@ -336,7 +343,7 @@ def load_library(path=None):
             list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
             list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()) + list(ABI_GMC_BLOBS.items()) + \
             list(ABI_PIPE_GMC_BLOBS.items()) + list(ABI_PERSIST.items()) + list(ABI_PIPE_BOXES.items()) + \
-            list(ABI_DIR.items()):
+            list(ABI_DIR.items()) + list(ABI_PIPE_DIR.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -73,6 +73,21 @@ int ctx_launch_gmc(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const ui
 // MT_OK when the compensated scan has a form for the context's grid; MT_ERR_UNSUPPORTED (the grid is named) as
 // mtgpu_gmc_preview otherwise.  No HIP call.
 int ctx_gmc_supported(const mtgpu_ctx *c);
+// Launch the direction scan (dir_kernels.hip, the pipe form) for a pipe's staging batch on `st`: as ctx_launch_gmc, with
+// allow in [0, 255] serving every frame and d_count = the batch's ONE count array or nullptr, which receives the sector
+// word of include/mtgpu_pipe_dir.h when report_sectors (d_count is then required), else the frame's centre count.  d_keep
+// = ONE keep plane in device memory or nullptr (no mask): the rose counts only records of kept cells and the active plane
+// is the masked one.  plan_ws / plan_ws_bytes are REQUIRED (the batch's own block): nothing is taken from the context's
+// scratch ring.  outputs_in_host_memory: d_flags / d_count are pinned host memory and are stored at system scope, the
+// planner's answers for frames without side data too.  With mtgpu_profile_enable on it records the same event triple as
+// ctx_launch_scan.  MT_ERR_UNSUPPORTED as mtgpu_dir_preview.
+int ctx_launch_dir(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
+                   uint32_t n_frames, const uint64_t *d_keep, int32_t allow, int report_sectors, uint8_t *d_flags,
+                   uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
+                   size_t plan_ws_bytes);
+// MT_OK when the direction scan has a form for the context's grid; MT_ERR_UNSUPPORTED (the grid is named) as
+// mtgpu_dir_preview otherwise.  No HIP call.
+int ctx_dir_supported(const mtgpu_ctx *c);
 // Launch the compensated blob scan (gmc_blobs_kernels.hip, the pipe form) for a pipe's staging batch on `st`: as
 // ctx_launch_gmc, with min_blob_cells >= 1 (flags = centres >= max(1, clusters_needed) AND largest >= min_blob_cells) and
 // `report` (MT_PIPE_REPORT_CENTRES / _LARGEST / _VECTOR) choosing what d_count, the batch's ONE count array or nullptr,

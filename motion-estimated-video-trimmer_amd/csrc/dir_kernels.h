@@ -19,7 +19,9 @@ static_assert((kDirChunk / kDirBlock + 2) * 64 < 65536, "a wave's 16-bit partial
 
 // LDS of one workgroup, in this order (R = analysed rows, at least 1; W = 64-bit words per mask row):
 //   tile     (R + 2) x gw u32, padded to 4 words   vote counters: the analysed rows and one halo row each side
-//   amask    (R + 2) x W u64                       the frame's active cells; mask row j <-> grid row y_lo - 1 + j
+//   amask    (R + 2) x W u64                       the frame's active cells; mask row j <-> grid row y_lo - 1 + j.  Dead
+//                                                  until the masks are built: the pipe form keeps the keep words of the
+//                                                  analysed rows in rows 1 .. R until then (keep row r <-> mask row r + 1)
 //   total    4 u32                                 [0]: the centre count
 //   rose     8 u32                                 the frame's counting records per sector
 inline size_t dir_tile_words(int gw, int R) {
@@ -57,6 +59,16 @@ struct DirLaunch {
   unsigned char *flags;                   // n_frames bytes, device memory, or null
   unsigned int *centres;                  // n_frames words, or null
   unsigned int *rose;                     // n_frames x 8 words (mt_dir_rose), or null
+  // The pipe form (pipe.hip's staging batches; include/mtgpu_pipe_dir.h): no clear kernel — launch_plan gets flags and
+  // centres and answers the frames without side data; no stream lookup (`allow` serves every frame; allows / stream_off
+  // null); the results are stored at system scope where sys_flags / sys_centres say that the array is not device memory
+  // (a zero-copy batch's pinned block); `keep`: ONE plane of gh x W words in device memory, or null — counting records
+  // and active cells of the analysed rows need their keep bit; report_sectors: centres receives the sector word built
+  // from the frame's rose in place of the centre count.  No rose array.
+  // 0: the form of mtgpu_scan_dir_device — plain stores; keep must be null, sys_* and report_sectors 0.
+  int pipe = 0;
+  const unsigned long long *keep = nullptr;
+  int sys_flags = 0, sys_centres = 0, report_sectors = 0;
   DirK k;
   int lds_bytes;
   int lds_max;                            // device limit of dynamic LDS per workgroup
@@ -66,7 +78,8 @@ struct DirLaunch {
   hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the scan kernel; else nullptr
 };
 
-// Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.
+// Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.  Pipe form: no fill —
+// the planner answers the frames without side data.
 hipError_t launch_dir_scan(const DirLaunch &L);
 
 }  // namespace mtgpu

@@ -25,6 +25,12 @@
 //   Every output element has one writer after the clear: lane 0 of the frame's workgroup, plain vector stores, no global
 //   atomics.
 //
+// The pipe form (PIPE, include/mtgpu_pipe_dir.h): no clear kernel — the planner answers the frames without side data —
+// no stream search, no rose array: every listed frame's workgroup stores the flag and ONE count (the centre count or the
+// sector word) on the kernel's one exit, through store_flag / store_centres at the outputs' scope.  With a keep plane
+// the rose counts a record only where the keep bit of its destination cell is set, and the active plane is the masked
+// one of the zones kernel; the keep words wait in the amask rows they are ANDed into, so the LDS does not grow.
+//
 // The record loads, the streamers, the row masks, the centre test of a word are those of record_stream.h, instantiated
 // here with this kernel's functor; the launch helpers are those of scan_kernels.h.
 #if !defined(__HIP_DEVICE_COMPILE__) || defined(__gfx950__)
@@ -64,8 +70,12 @@ __device__ __forceinline__ void count_centres(const unsigned long long *amask, u
 //   axis tests   e: 12 |dy| <= 5 |dx| (E / W), s: 12 |dx| <= 5 |dy| (S / N); |d| <= 65535, so both products fit 24-bit
 //                multiplies.  Both hold only for dx == dy == 0.
 //   sector       e: 4 sx; s: 2 + 4 sy; neither: 1 + 4 sy + 2 (sx ^ sy)  (sx, sy: the sign bits: 1, 3, 5, 7 clockwise)
+// KEEP (the pipe form under a keep plane): `kl` = the staged keep words of the analysed rows (keep row r at kl + r * W).
+// The keep bit of the destination cell is read behind the same branch: a record that does not count reads nothing.  A
+// record of a keep-0 cell is in no sector of the rose and does not vote (its cell is inactive whatever its votes).
+template <bool KEEP = false>
 __device__ __forceinline__ void dir_vote(const MvFields m, const DirK &k, int t0, unsigned int *tile, unsigned int allow,
-                                         unsigned long long &acc) {
+                                         unsigned long long &acc, const unsigned long long *kl = nullptr) {
   const int sdx = m.dst_x - m.src_x, sdy = m.dst_y - m.src_y;  // |.| <= 65535
   const unsigned int dx = (unsigned int)sdx, dy = (unsigned int)sdy;
   // dx*dx < 2^32 exactly; the sum needs 34 bits
@@ -86,8 +96,14 @@ __device__ __forceinline__ void dir_vote(const MvFields m, const DirK &k, int t0
     const unsigned int sec = e ? west : south;
     const bool none = (dx | dy) == 0u;
     const unsigned int eff = none ? 0xffu : allow;             // no direction to object to
-    acc += (unsigned long long)(none ? 0u : 1u) << (8u * sec);
-    if (((eff >> sec) & 1u) != 0u) atomicAdd(&tile[(unsigned int)((gy - t0) * k.gw + gx)], 1u);
+    if constexpr (KEEP) {
+      const bool kept = ((kl[(gy - k.y_lo) * k.W + (gx >> 6)] >> (gx & 63)) & 1ull) != 0ull;
+      acc += (unsigned long long)((none | !kept) ? 0u : 1u) << (8u * sec);
+      if (kept & (((eff >> sec) & 1u) != 0u)) atomicAdd(&tile[(unsigned int)((gy - t0) * k.gw + gx)], 1u);
+    } else {
+      acc += (unsigned long long)(none ? 0u : 1u) << (8u * sec);
+      if (((eff >> sec) & 1u) != 0u) atomicAdd(&tile[(unsigned int)((gy - t0) * k.gw + gx)], 1u);
+    }
   }
 }
 
@@ -139,11 +155,20 @@ __global__ __launch_bounds__(256) void dir_clear_kernel(unsigned char *__restric
 // Waves per SIMD: as zones_frames_kernel — a workgroup is 16 waves, four per SIMD; a 1080p workgroup takes about 31 KB
 // of LDS, so the lane limit decides: two workgroups per CU, eight waves per SIMD and so at most 64 VGPRs.
 // allows == nullptr: stream_off / n_streams are not read and `allow` serves every frame.
-template <int BLOCK, int UNROLL, int REC>
+// PIPE: the form for a pipe's staging batch (include/mtgpu_pipe_dir.h) — no stream search: stream_off / n_streams /
+// allows are not read and `allow` serves every frame; `rose` is not read (null); `keep` is ONE plane (gh x W words) or
+// null; the flag and the ONE count leave through store_flag / store_centres with sys_flags / sys_centres on the kernel's
+// one exit, and with report_sectors the count is the sector word lane 0 builds from the eight LDS rose words.  The keep
+// words of the analysed rows take no LDS of their own: they are staged into the amask rows they will be ANDed into (keep
+// row r <-> mask row r + 1), which are dead until row_masks writes them; the lane that stores a word is the one that
+// reads the keep word under it.  keep == nullptr is a workgroup-uniform branch around the staging and around the
+// per-record lookup.  !PIPE: keep / sys_* / report_sectors are not read (null / 0).
+template <int BLOCK, int UNROLL, int REC, bool PIPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void dir_frames_kernel(
     const unsigned char *__restrict__ mv, const WorkItem *__restrict__ work, unsigned int item0, unsigned int n_items, DirK k,
     const unsigned long long *__restrict__ stream_off, unsigned int n_streams, const unsigned char *__restrict__ allows,
-    unsigned int allow, unsigned char *__restrict__ flags, unsigned int *__restrict__ centres, unsigned int *__restrict__ rose) {
+    unsigned int allow, unsigned char *__restrict__ flags, unsigned int *__restrict__ centres, unsigned int *__restrict__ rose,
+    const unsigned long long *__restrict__ keep, int sys_flags, int sys_centres, int report_sectors) {
   extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
   const unsigned int item = item0 + blockIdx.x;
   if (item >= n_items) return;
@@ -160,15 +185,18 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   // The frame's stream: s = the number of streams that end at or before frame f (binary search, workgroup-uniform
   // values: scalar code).  s == n_streams: the frame lies behind the last stream and keeps the zeros of the clear.
   const unsigned int f = __builtin_amdgcn_readfirstlane(me.f);
-  if (allows != nullptr) {
-    unsigned int lo = 0u, hi = n_streams;
-    while (lo < hi) {
-      const unsigned int mid = lo + ((hi - lo) >> 1);
-      if (stream_off[mid + 1u] <= (unsigned long long)f) lo = mid + 1u; else hi = mid;
+  [[maybe_unused]] unsigned int tw = (unsigned int)k.tile_words;   // the pipe form only
+  if constexpr (!PIPE) {
+    if (allows != nullptr) {
+      unsigned int lo = 0u, hi = n_streams;
+      while (lo < hi) {
+        const unsigned int mid = lo + ((hi - lo) >> 1);
+        if (stream_off[mid + 1u] <= (unsigned long long)f) lo = mid + 1u; else hi = mid;
+      }
+      // in front of the first stream (stream_off[0] > f) the frame belongs to no stream either
+      if (lo >= n_streams || stream_off[lo] > (unsigned long long)f) return;
+      allow = (unsigned int)allows[lo];
     }
-    // in front of the first stream (stream_off[0] > f) the frame belongs to no stream either
-    if (lo >= n_streams || stream_off[lo] > (unsigned long long)f) return;
-    allow = (unsigned int)allows[lo];
   }
   // ---- zero the tile, the total and the rose
   {
@@ -177,6 +205,21 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     for (int j = tid; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
     if (tid < 12) total[tid] = 0u;              // total[0 .. 3] and the eight rose words behind them
   }
+  if constexpr (PIPE) {
+    // the keep words of the analysed rows into mask rows 1 .. crows (crows <= R: inside the (R + 2) x W plane); keep row
+    // y_lo + r, r < crows, lies inside the gh x W plane
+    if (keep != nullptr) {
+      const unsigned long long *kp = keep + (size_t)k.y_lo * (size_t)k.W;
+      const int nkeep = crows * k.W;
+      for (int j = tid; j < nkeep; j += BLOCK) amask[(size_t)k.W + j] = kp[j];
+    }
+    // The mask plane's offset waits in a VGPR while the records stream (this form takes 52 / 51 VGPRs, 12 to spare under
+    // the 64 of eight waves per SIMD): held in an SGPR it is the one value too many there, and the compiler parks it in
+    // a VGPR lane itself — an SGPR spill.  Seen with hipcc 7.2.26015 (AMD clang 22.0.0git, roc-7.2.0), where the compact
+    // form then reports .sgpr_spill_count 1; the results do not depend on it, only the register use does.  With
+    // another compiler read the kernels' resource usage again (docs/rounds/r21_pipe_dir.md has the command line).
+    asm volatile("" : "+v"(tw));
+  }
   __syncthreads();
   // ---- the votes and the rose (an empty analysed range counts nothing: nothing to read)
   if (crows > 0) {
@@ -184,21 +227,67 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
       const unsigned long long n = (me.r1 - r) < kDirChunk ? (me.r1 - r) : kDirChunk;
       unsigned long long acc = 0ull;
       const auto one = [=, &k, &acc](const MvFields m) { dir_vote(m, k, t0, tile, allow, acc); };
-      if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + r * 8ull, n, one);
-      else stream_mv40<BLOCK, UNROLL>(mv + r * 40ull, n, one);
+      if constexpr (PIPE) {
+        if (keep != nullptr) {
+          const unsigned long long *kl = amask + k.W;
+          const auto onek = [=, &k, &acc](const MvFields m) { dir_vote<true>(m, k, t0, tile, allow, acc, kl); };
+          if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + r * 8ull, n, onek);
+          else stream_mv40<BLOCK, UNROLL>(mv + r * 40ull, n, onek);
+        } else {
+          if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + r * 8ull, n, one);
+          else stream_mv40<BLOCK, UNROLL>(mv + r * 40ull, n, one);
+        }
+      } else {
+        if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + r * 8ull, n, one);
+        else stream_mv40<BLOCK, UNROLL>(mv + r * 40ull, n, one);
+      }
       flush_rose(acc, lrose);
     }
   }
   __syncthreads();
   // ---- the masks, then the centre count
-  row_masks<BLOCK>(tile, k, t0, t1, k.y_lo - 1, crows + 2, [=, &k](int j, int w, int g, unsigned long long m) {
-    amask[(size_t)j * k.W + w] = m;
-  });
+  if constexpr (PIPE) {
+    // the plane, the total and the rose are found again from the offset parked in a VGPR above and from
+    // R = max(1, crows), which the launch checks
+    amask = reinterpret_cast<unsigned long long *>(lds + tw);
+    total = reinterpret_cast<unsigned int *>(amask + (size_t)(max(crows, 1) + 2) * k.W);
+    lrose = total + 4;
+    // an analysed row's word is ANDed with the keep word it overwrites (staged above); halo rows are stored as they come
+    const bool masked = keep != nullptr;
+    row_masks<BLOCK>(tile, k, t0, t1, k.y_lo - 1, crows + 2, [=, &k](int j, int w, int g, unsigned long long m) {
+      unsigned long long *slot = amask + (size_t)j * k.W + w;
+      const bool analysed = masked && g >= k.y_lo && g < k.y_hi;
+      *slot = analysed ? (m & *slot) : m;
+    });
+  } else {
+    row_masks<BLOCK>(tile, k, t0, t1, k.y_lo - 1, crows + 2, [=, &k](int j, int w, int g, unsigned long long m) {
+      amask[(size_t)j * k.W + w] = m;
+    });
+  }
   __syncthreads();
   count_centres<BLOCK>(amask, &total[0], k, crows);
   __syncthreads();
   if (tid == 0) {
     const unsigned int c = total[0];
+    if constexpr (PIPE) {                       // the one exit: a reused pinned block holds the previous batch's values
+      if (centres) {
+        unsigned int word = c;
+        if (report_sectors) {
+          // present byte | k* << 8 | min(n[k*], 2^21 - 1) << 11; k*: the smallest k whose count is maximal (0: none counts)
+          unsigned int present = 0u, best = 0u, kbest = 0u;
+#pragma unroll
+          for (unsigned int j = 0; j < 8u; ++j) {
+            const unsigned int n = lrose[j];
+            present |= (n ? 1u : 0u) << j;
+            if (n > best) { best = n; kbest = j; }
+          }
+          word = present | (kbest << 8) | ((best < 0x1fffffu ? best : 0x1fffffu) << 11);
+        }
+        store_centres(centres, f, word, sys_centres);
+      }
+      if (flags) store_flag(flags, f, (unsigned char)(c >= k.clust_need ? 1 : 0), sys_flags);
+      return;
+    }
     if (centres) centres[f] = c;
     if (flags) flags[f] = (unsigned char)(c >= k.clust_need ? 1 : 0);
     if (rose) {
@@ -211,16 +300,17 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 
 namespace {
 
-template <int REC>
+template <int REC, bool PIPE>
 hipError_t launch_frames(const DirLaunch &L) {
-  auto kern = dir_frames_kernel<kDirBlock, kDirUnroll, REC>;
+  auto kern = dir_frames_kernel<kDirBlock, kDirUnroll, REC, PIPE>;
   static std::atomic<unsigned long long> ready{0ull};
   hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
   if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
   return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
     hipLaunchKernelGGL(kern, dim3(n), dim3(kDirBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.k,
-                       L.stream_off, L.n_streams, L.allows, L.allow, L.flags, L.centres, L.rose);
+                       L.stream_off, L.n_streams, L.allows, L.allow, L.flags, L.centres, L.rose, L.keep, L.sys_flags,
+                       L.sys_centres, L.report_sectors);
   });
 }
 
@@ -230,12 +320,29 @@ hipError_t launch_dir_scan(const DirLaunch &L) {
   if (L.n_frames == 0) return hipSuccess;
   if (L.rec_bytes != 40 && L.rec_bytes != 8) return hipErrorInvalidValue;
   if (!L.flags && !L.centres && !L.rose) return hipErrorInvalidValue;
+  if (L.pipe) {
+    if (L.rose || L.allows || (L.report_sectors && !L.centres)) return hipErrorInvalidValue;
+  } else {
+    if (L.keep || L.sys_flags != 0 || L.sys_centres != 0 || L.report_sectors != 0) return hipErrorInvalidValue;
+  }
   if (L.allows ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0 || L.allow > 255u))
     return hipErrorInvalidValue;
   if (!L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records) return hipErrorInvalidValue;
   if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.lds_bytes > L.lds_max ||
       (size_t)L.lds_bytes < dir_lds_bytes(L.k.gw, L.k.R))
     return hipErrorInvalidValue;
+  if (L.pipe) {
+    // The keep rows are staged into the mask plane and indexed by the kernel: the block's layout fields must be the grid's.
+    // The kernel finds the plane again from R = max(1, y_hi - y_lo).
+    if ((size_t)L.k.tile_words != dir_tile_words(L.k.gw, L.k.R) || L.k.W != (L.k.gw + 63) / 64 || L.k.y_lo < 0 || L.k.y_hi > L.k.gh ||
+        L.k.R != (L.k.y_hi - L.k.y_lo < 1 ? 1 : L.k.y_hi - L.k.y_lo))
+      return hipErrorInvalidValue;
+    // The planner is handed the outputs and answers every frame without side data itself (at the outputs' scope), as in
+    // launch_scan, launch_zone_scan and launch_gmc_scan: no clear kernel — planning + one kernel.
+    hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres, L.sys_centres);
+    if (e != hipSuccess) return e;
+    return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
+  }
   {
     const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
     hipLaunchKernelGGL(dir_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream, L.flags,
@@ -246,7 +353,7 @@ hipError_t launch_dir_scan(const DirLaunch &L) {
   // flags / centres null: the planner answers nothing itself (the outputs are zero already)
   hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
   if (e != hipSuccess) return e;
-  return L.rec_bytes == 8 ? launch_frames<8>(L) : launch_frames<40>(L);
+  return L.rec_bytes == 8 ? launch_frames<8, false>(L) : launch_frames<40, false>(L);
 }
 
 }  // namespace mtgpu

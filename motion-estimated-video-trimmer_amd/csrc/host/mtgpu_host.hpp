@@ -743,6 +743,8 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   int gmc_blob_cells_ = 0;                             // set_gmc_blobs(): the pipe's pair mode (compensated blob scan); 0: off
   int gmc_blob_max_shift_ = MTGPU_GMC_DEFAULT_MAX_SHIFT, gmc_blob_min_share_q8_ = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
   int gmc_blob_report_ = MT_PIPE_REPORT_CENTRES;       // report_gmc_blobs(): what last_centres() holds in pair mode
+  int dir_allow_ = -1;                                 // set_dir(): the pipe's direction mode, the allow byte; -1: off
+  bool report_sectors_ = false;                        // report_sectors(): last_centres() holds the frames' sector words
   bool trace_on_ = false;                              // set_persist(min_run >= 1): scan_range keeps a trace of every fed frame
   int persist_reach_ = -1;                             // set_persist(): >= 0: the pipe carries boxes (MT_LAYOUT_BOXES)
   std::vector<TraceEntry> last_trace_;
@@ -893,6 +895,16 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
     gmc_blob_cells_ = min_blob_cells; gmc_blob_max_shift_ = max_shift; gmc_blob_min_share_q8_ = min_share_q8;
   }
   void report_gmc_blobs(int report) { gmc_blob_report_ = report; }
+  // Call before initialize().  The direction filter for this video (include/mtgpu_pipe_dir.h), the pipe's fourth mode:
+  // in every check_frame of scan_range (:375-383) a record votes only if bit k of `allow` is set, k the sector of
+  // dst - src (include/mtgpu_dir.h); the active plane honours set_keep.  allow 0 .. 255: on; -1: off.
+  // report_sectors(true): last_centres() returns {pts, sector word} in place of the centre counts (needs
+  // keep_centres(true): the pipe has ONE count array, and set_dir: without the mode there is no word).  Not together
+  // with set_min_blob_cells(n > 0), report_largest, set_gmc(>= 0), report_vector or set_gmc_blobs.  initialize() ALWAYS
+  // settles the pipe's direction setting — off first, on again at the end if asked: a pooled pipe never refuses the
+  // next video's setting because of the previous one's.
+  void set_dir(int allow) { dir_allow_ = allow; }
+  void report_sectors(bool on) { report_sectors_ = on; }
   // Call before initialize().  Temporal persistence for this video (include/mtgpu_persist.h).  A run of motion frames
   // crosses batch and chunk borders and the chunks of a recording are scanned by several workers in any order, so the
   // scanner does NOT apply the rule: it keeps what ONE mtgpu_persist_flags call per recording needs (run_scan_pipeline
@@ -939,6 +951,8 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
       return false;
     pipe_ = be_->pipe();
     // the pipe is idle here (a previous scanner on this backend left nothing in flight, or the backend was rebuilt)
+    // direction off first: a pooled pipe that carries it would refuse every other mode below
+    if (mtgpu_pipe_set_dir(pipe_, 0, 0, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
     // the pair off first: a pooled pipe that carries it would refuse both single settings below
     if (mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
     // compensation off first: a pooled pipe that carries it would refuse the blob setting below
@@ -1001,6 +1015,27 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
                                           gmc_blob_report_) != MT_OK) {
         err_ = bad ? bad : mtgpu_last_error();
         (void)mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0);       // whatever fails here, no stale setting stays behind
+        (void)mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0);
+        (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);
+        (void)mtgpu_pipe_set_keep(pipe_, nullptr);
+        pipe_ = nullptr;
+        return false;
+      }
+    }
+    if (dir_allow_ != -1 || report_sectors_) {
+      const char *bad = nullptr;
+      if (dir_allow_ == -1) bad = "report_sectors needs set_dir: there is no sector word without the direction mode";
+      else if (dir_allow_ < 0 || dir_allow_ > 255) bad = "set_dir: allow is outside [0,255]";
+      else if (min_blob_cells_ > 0 || report_largest_) bad = "set_dir together with set_min_blob_cells / report_largest: direction and blobs are not together yet";
+      else if (gmc_max_shift_ >= 0 || report_vector_) bad = "set_dir together with set_gmc / report_vector: direction and compensation are not together yet";
+      else if (gmc_blob_cells_ != 0 || gmc_blob_report_ != MT_PIPE_REPORT_CENTRES)
+        bad = "set_dir together with set_gmc_blobs: direction and the compensated blob scan are not together yet";
+      else if (report_sectors_ && !keep_centres_) bad = "report_sectors needs keep_centres: the sector word travels in the pipe's count array";
+      // the sequence above left the three other modes off here unless `bad` names one of them
+      if (bad || mtgpu_pipe_set_dir(pipe_, 1, dir_allow_, report_sectors_ ? MT_PIPE_REPORT_SECTORS : MT_PIPE_REPORT_CENTRES) != MT_OK) {
+        err_ = bad ? bad : mtgpu_last_error();
+        (void)mtgpu_pipe_set_dir(pipe_, 0, 0, 0);                // whatever fails here, no stale setting stays behind
+        (void)mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0);
         (void)mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0);
         (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);
         (void)mtgpu_pipe_set_keep(pipe_, nullptr);
@@ -1132,6 +1167,20 @@ struct PipelineResult {
   int gmc_blob_min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
   std::vector<int> gmc_blob_sweep_levels;
   std::vector<SweepEntry> gmc_blob_sweep;              // SweepEntry::clusters_needed holds the level L
+  // The direction filter (GpuMotionScanner::set_dir / report_sectors; include/mtgpu_pipe_dir.h).  In: dir_allow 0 .. 255:
+  // on — `segments` are those of the scan in which only records of an allowed sector vote, under `keep` where there is
+  // one; -1: take dir_options(); -2: off whatever dir_options() says.  dir_sectors: every worker's pipe reports the
+  // frame's sector word in place of the centre count (the pipe has ONE count array: not together with keep_centres /
+  // sweep_levels); `centres` then holds {pts, sector word}.  Out, with dir_sectors: dir_frames = scanned frames with a
+  // non-zero word, dir_present_frames[k] = those whose present byte has bit k, dir_dominant_frames[k] = those whose
+  // dominant sector is k.  Not together with min_blob_cells > 0 / blob_sweep_levels, gmc_max_shift >= 0 / gmc_vectors or
+  // gmc_blob_cells > 0 / gmc_blob_sweep_levels.  keep, keep_centres, sweep_levels, min_run, max_dropout and
+  // run_sweep_levels combine.
+  int dir_allow = -1;
+  bool dir_sectors = false;
+  uint64_t dir_frames = 0;
+  uint64_t dir_present_frames[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t dir_dominant_frames[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // Temporal persistence (GpuMotionScanner::set_persist; include/mtgpu_persist.h, include/mtgpu_pipe_boxes.h).  In:
   // min_run > 1: on — a frame counts only as one of a run of at least min_run motion frames; -1: take persist_options();
   // 0 or 1: off whatever the options say (with no run_sweep_levels everything is as without these fields).  max_dropout:
@@ -1191,6 +1240,11 @@ inline BlobOptions &blob_options() { static BlobOptions o; return o; }
 // run_scan_pipeline.  max_shift < 0: off.
 struct GmcOptions { int max_shift = -1; int min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8; bool vectors = false; };
 inline GmcOptions &gmc_options() { static GmcOptions o; return o; }
+
+// Process-wide defaults for PipelineResult::dir_allow / dir_sectors (a front end's --allow / --ignore / --dir-sectors):
+// set before the first pipeline starts, read by every run_scan_pipeline.  allow < 0: off.
+struct DirOptions { int allow = -1; bool sectors = false; };
+inline DirOptions &dir_options() { static DirOptions o; return o; }
 
 // Process-wide defaults for PipelineResult::keep_centres / sweep_levels (a front end's --centres / --sweep): set before
 // the first pipeline starts, read by every run_scan_pipeline.
@@ -1299,6 +1353,33 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
         return 1;
       }
   }
+  // the direction filter, the pipes' fourth mode: every conflict is answered here, before any decode
+  if (out.dir_allow == -1) {
+    out.dir_allow = dir_options().allow < 0 ? -2 : dir_options().allow;
+    out.dir_sectors = out.dir_sectors || dir_options().sectors;
+  }
+  const bool dir_on = out.dir_allow >= 0;
+  if (out.dir_allow < -2 || out.dir_allow > 255) { out.error = "dir_allow is " + std::to_string(out.dir_allow) + ": want 0 .. 255, -1 or -2"; return 1; }
+  if (out.dir_sectors && !dir_on) { out.error = "dir_sectors without the direction mode (dir_allow)"; return 1; }
+  if (dir_on) {
+    if (out.min_blob_cells > 0 || report_largest) {
+      out.error = "dir_allow together with min_blob_cells / blob_sweep_levels: direction and blobs are not together yet";
+      return 1;
+    }
+    if (gmc_on || out.gmc_vectors) {
+      out.error = "dir_allow together with gmc_max_shift / gmc_vectors: direction and compensation are not together yet";
+      return 1;
+    }
+    if (pair_on) {
+      out.error = "dir_allow together with gmc_blob_cells / gmc_blob_sweep_levels: direction and the compensated blob scan are "
+                  "not together yet";
+      return 1;
+    }
+    if (out.dir_sectors && (out.keep_centres || centre_options().keep || !out.sweep_levels.empty())) {
+      out.error = "dir_sectors together with keep_centres / sweep_levels: the pipe has one count array";
+      return 1;
+    }
+  }
   // temporal persistence: one pass per recording behind the scan; every conflict is answered here, before any decode
   if (out.min_run == -1) {
     out.min_run = persist_options().min_run;
@@ -1323,7 +1404,7 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
     if (out.reach > 65535) { out.error = "reach " + std::to_string(out.reach) + " outside [0,65535]"; return 1; }
   }
   const bool keep_centres = out.keep_centres || centre_options().keep || !out.sweep_levels.empty() || report_largest || out.gmc_vectors ||
-                            pair_largest;
+                            pair_largest || out.dir_sectors;
   std::mutex centres_mu;
   std::vector<TraceEntry> trace;                                       // pooled under centres_mu, as `centres`
   const auto wall0 = std::chrono::high_resolution_clock::now();
@@ -1368,6 +1449,8 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
         scanners[i]->report_vector(out.gmc_vectors);
         scanners[i]->set_gmc_blobs(pair_on ? std::max(1, out.gmc_blob_cells) : 0, out.gmc_blob_max_shift, out.gmc_blob_min_share_q8);
         scanners[i]->report_gmc_blobs(pair_largest ? MT_PIPE_REPORT_LARGEST : MT_PIPE_REPORT_CENTRES);
+        scanners[i]->set_dir(dir_on ? out.dir_allow : -1);
+        scanners[i]->report_sectors(out.dir_sectors);
         scanners[i]->set_persist(persist_on ? std::max(1, out.min_run) : 0, out.max_dropout, persist_on ? out.reach : -1);
         if (!scanners[i]->initialize()) {                                // :198-199 (here: reported)
           fail_with(scanners[i]->error());
@@ -1470,6 +1553,16 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
   out.segments.resize(out.merge.n_segments);
   std::stable_sort(out.centres.begin(), out.centres.end(),
                    [](const std::pair<double, uint32_t> &a, const std::pair<double, uint32_t> &b) { return a.first < b.first; });
+  if (out.dir_sectors) {                                                 // `centres` holds the frames' sector words
+    out.dir_frames = 0;
+    for (int k = 0; k < 8; ++k) out.dir_present_frames[k] = out.dir_dominant_frames[k] = 0;
+    for (const auto &c : out.centres) {
+      if (c.second == 0u) continue;
+      ++out.dir_frames;
+      for (int k = 0; k < 8; ++k) out.dir_present_frames[k] += (c.second >> k) & 1u;
+      ++out.dir_dominant_frames[(c.second >> 8) & 7u];
+    }
+  }
   if (out.gmc_vectors) {                                                 // `centres` holds the packed applied vectors
     std::map<uint32_t, uint64_t> seen;
     out.gmc_moved_frames = 0;

@@ -5,6 +5,7 @@
 //                   [--gmc] [--gmc-max-shift N] [--gmc-min-share-q8 Q] [--gmc-vectors]
 //                   [--gmc-blobs N] [--gmc-blobs-max-shift S] [--gmc-blobs-min-share-q8 Q] [--sweep-gmc-blobs L1,L2,...]
 //                   [--min-run N] [--max-dropout D] [--reach R] [--sweep-min-run L1,L2,...]
+//                   [--allow LIST | --ignore LIST] [--dir-sectors]
 //   (--streams 0 / --threads 0: the reference's own sizing from PARALLEL_STREAMS / THREADS_PER_STREAM and the CPU limit)
 // One file: like `motion_trim in out` (single ProcessingPipeline).  Several files: like
 // `motion_trim in_dir out_dir` (BatchProcessor): S streams x T workers, jobs consumed by one
@@ -57,6 +58,16 @@
 // pass.  --min-run N > 1 and --sweep-min-run do not combine with --sweep, --sweep-blobs or --sweep-gmc-blobs (a level
 // sweep under persistence needs one persistence pass per level, which is not built); --max-dropout and --reach are valid
 // only next to them.  --min-run 0 or 1 with nothing else prints exactly what no option prints.
+// --allow LIST / --ignore LIST: the direction filter (include/mtgpu_pipe_dir.h) — a record votes only if the sector of
+// dst - src is one of LIST (--allow) or none of LIST (--ignore); LIST holds sector names E,SE,S,SW,W,NW,N,NE or one
+// decimal number 0 .. 255 (the byte of the sectors named); the two are mutually exclusive.  Under --keep the ignored cells are not
+// active.  --dir-sectors (implies the mode, with every sector allowed when neither list is given): the pipes report every
+// frame's sector word; the job gains "dir": {"allow", "frames" (scanned frames with a counting moving record),
+// "present": [8] (frames in which sector k has a counting record), "dominant": [8] (frames whose strongest sector is
+// k)}, counted under --keep where it is given and whatever the lists say.  It combines with --keep, --centres, --sweep,
+// --min-run, --max-dropout and --sweep-min-run; --dir-sectors does not combine with --centres or --sweep (a pipe has one
+// count array); none of it combines with the --gmc family, --min-blob-cells N > 0, --sweep-blobs, the --gmc-blobs family
+// or --reach.  Without these options the output is unchanged.
 // --summary (several files): one more line {"batch_summary": ...} — frames scanned, wall time, worker-time
 // breakdown and what the S x T workers held (contexts, pipes, HIP streams, pinned / device bytes).
 #include <cmath>
@@ -65,6 +76,8 @@
 #include <map>
 #include <string>
 #include <vector>
+
+#include <strings.h>   // strncasecmp
 
 #include "mtgpu_host.hpp"
 
@@ -121,6 +134,36 @@ static const char *g_pair_param_opt = nullptr;  // the first of --gmc-blobs-max-
 static const char *g_gmc_opt = nullptr;         // the first option of the --gmc family given
 static const char *g_persist_param_opt = nullptr;   // the first of --max-dropout / --reach given
 static bool g_sweep_opt = false;                    // --sweep given
+static const char *g_dir_opt = nullptr;             // the first of --allow / --ignore / --dir-sectors given
+static const char *g_dir_list_opt = nullptr;        // --allow or --ignore, whichever was given
+static bool g_print_dir = false;                    // --dir-sectors
+
+// LIST of --allow / --ignore: sector names E,SE,S,SW,W,NW,N,NE (any case) or one decimal number 0 .. 255 -> the byte of
+// the sectors named.
+static bool parse_sector_list(const char *text, int *byte) {
+  static const char *const names[8] = {"E", "SE", "S", "SW", "W", "NW", "N", "NE"};
+  if (!text || !*text) return false;
+  if (*text >= '0' && *text <= '9') {
+    char *end = nullptr;
+    const long v = std::strtol(text, &end, 10);    // decimal only: "010" is ten, "0x11" is refused
+    if (*end || v < 0 || v > 255) return false;
+    *byte = (int)v;
+    return true;
+  }
+  int b = 0;
+  for (const char *q = text; *q;) {
+    const char *e = std::strchr(q, ',');
+    const size_t n = e ? (size_t)(e - q) : std::strlen(q);
+    int k = -1;
+    for (int j = 0; j < 8; ++j)
+      if (std::strlen(names[j]) == n && !strncasecmp(q, names[j], n)) k = j;
+    if (k < 0 || (e && !e[1])) return false;
+    b |= 1 << k;
+    q = e ? e + 1 : q + n;
+  }
+  *byte = b;
+  return true;
+}
 
 // The keep mask of g_keep_path for a width x height input; throws with load_keep's message (the line is named) when the
 // file is malformed or made for another grid.
@@ -194,6 +237,13 @@ static void print_job(const std::string &input, const PipelineResult &r, const s
                 (unsigned long long)r.gmc_moved_frames, r.centres.empty() ? 0.0 : (double)r.gmc_moved_frames / (double)r.centres.size());
     for (size_t i = 0; i < r.gmc_top.size(); ++i)
       std::printf("%s[%d, %d, %llu]", i ? ", " : "", r.gmc_top[i].gx, r.gmc_top[i].gy, (unsigned long long)r.gmc_top[i].frames);
+    std::printf("]}");
+  }
+  if (g_print_dir) {
+    std::printf(", \"dir\": {\"allow\": %d, \"frames\": %llu, \"present\": [", r.dir_allow, (unsigned long long)r.dir_frames);
+    for (int k = 0; k < 8; ++k) std::printf("%s%llu", k ? ", " : "", (unsigned long long)r.dir_present_frames[k]);
+    std::printf("], \"dominant\": [");
+    for (int k = 0; k < 8; ++k) std::printf("%s%llu", k ? ", " : "", (unsigned long long)r.dir_dominant_frames[k]);
     std::printf("]}");
   }
   if (!r.sweep.empty()) print_sweep("sweep", "clusters_needed", r.sweep);
@@ -348,6 +398,27 @@ int main(int argc, char **argv) {
       else if (drop) persist_options().max_dropout = (uint32_t)v;
       else persist_options().reach = (int)v;
     }
+    else if (!std::strcmp(argv[i], "--allow") || !std::strcmp(argv[i], "--ignore")) {
+      const bool allow_opt = !std::strcmp(argv[i], "--allow");
+      int byte = -1;
+      if (i + 1 >= argc || !parse_sector_list(argv[i + 1], &byte)) {
+        std::fprintf(stderr, "error: %s takes a comma-separated list of sector names (E,SE,S,SW,W,NW,N,NE) or one decimal number in [0, 255]\n", argv[i]);
+        return 2;
+      }
+      if (g_dir_list_opt && std::strcmp(g_dir_list_opt, argv[i])) {
+        std::fprintf(stderr, "error: --allow cannot be combined with --ignore: give the sectors that vote or the sectors that do not\n");
+        return 2;
+      }
+      g_dir_list_opt = argv[i];
+      if (!g_dir_opt) g_dir_opt = argv[i];
+      ++i;
+      dir_options().allow = allow_opt ? byte : (~byte & 0xff);
+    }
+    else if (!std::strcmp(argv[i], "--dir-sectors")) {
+      if (!g_dir_opt) g_dir_opt = argv[i];
+      g_print_dir = true;
+      dir_options().sectors = true;
+    }
     else if (!std::strcmp(argv[i], "--sweep-min-run")) {
       const char *q = i + 1 < argc ? argv[++i] : "";
       if (!*q) { std::fprintf(stderr, "error: --sweep-min-run takes a comma-separated list of integers\n"); return 2; }
@@ -363,6 +434,22 @@ int main(int argc, char **argv) {
       }
     }
     else files.push_back(argv[i]);
+  }
+  // --dir-sectors alone: the mode with every sector allowed
+  if (g_print_dir && dir_options().allow < 0) dir_options().allow = 0xff;
+  // what the direction filter cannot be combined with: answered here, before any device call
+  if (g_dir_opt) {
+    const char *other = g_gmc_opt ? g_gmc_opt : g_pair_opt ? g_pair_opt : g_pair_param_opt ? g_pair_param_opt :
+                        g_print_largest ? "--sweep-blobs" : blob_options().min_blob_cells > 0 ? "--min-blob-cells" :
+                        persist_options().reach >= 0 ? "--reach" : nullptr;
+    if (other) {
+      std::fprintf(stderr, "error: %s cannot be combined with %s: direction is not together with blobs or compensation yet\n", g_dir_opt, other);
+      return 2;
+    }
+    if (g_print_dir && (g_print_centres || !centre_options().sweep_levels.empty())) {
+      std::fprintf(stderr, "error: --dir-sectors cannot be combined with %s: a pipe has one count array\n", g_print_centres ? "--centres" : "--sweep");
+      return 2;
+    }
   }
   // what persistence cannot be combined with: answered here, before any device call
   {

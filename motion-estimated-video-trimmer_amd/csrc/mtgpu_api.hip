@@ -2984,9 +2984,14 @@ int dir_check_args(const char *d, const char *allow_name, int rec_bytes, const v
 }
 
 // The direction scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
+// own_plan_ws: the caller's own block for the work list (a pipe's batch; ctx_plan_ws_bytes(n_frames) bytes, 256-byte
+// aligned) — the launch then takes NOTHING from the context's scratch ring — and the pipe form of the launch: d_keep is
+// one plane or null, no clear kernel, no stream lookup, no rose, flags and one count (the sector word when
+// report_sectors) stored at system scope when `outputs_in_host_memory`.  nullptr: the ring, the stream form.
 int dir_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
            const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, const uint8_t *d_allow,
-           int32_t allow, uint8_t *d_flags, uint32_t *d_centres, mt_dir_rose *d_rose, hipStream_t st) {
+           int32_t allow, uint8_t *d_flags, uint32_t *d_centres, mt_dir_rose *d_rose, hipStream_t st, void *own_plan_ws = nullptr,
+           const uint64_t *d_keep = nullptr, int report_sectors = 0, int outputs_in_host_memory = 0) {
   mtgpu_dir_plan dp;
   int rc = dir_plan(c->params, c->lds_max, &dp);
   if (rc != MT_OK) return rc;
@@ -3016,9 +3021,18 @@ int dir_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, u
   L.ev_planned = nullptr;
   void *scratch = nullptr;
   int slot = -1;
-  rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-  if (rc != MT_OK) return rc;
-  L.plan_ws = scratch;
+  if (own_plan_ws) {
+    L.pipe = 1;
+    L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
+    L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
+    L.sys_centres = (d_centres && outputs_in_host_memory) ? 1 : 0;
+    L.report_sectors = report_sectors ? 1 : 0;
+    L.plan_ws = own_plan_ws;
+  } else {
+    rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
+    if (rc != MT_OK) return rc;
+    L.plan_ws = scratch;
+  }
   hipError_t e = hipSuccess;
   if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
     mtgpu_ctx::Profile &pf = c->prof;
@@ -3043,6 +3057,25 @@ int dir_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, u
 }
 
 }  // namespace
+
+namespace mtgpu {
+int ctx_dir_supported(const mtgpu_ctx *c) {
+  mtgpu_dir_plan dp;
+  return dir_plan(c->params, c->lds_max, &dp);
+}
+int ctx_launch_dir(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
+                   uint32_t n_frames, const uint64_t *d_keep, int32_t allow, int report_sectors, uint8_t *d_flags,
+                   uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
+                   size_t plan_ws_bytes) {
+  if (n_frames == 0) return MT_OK;
+  if (allow < 0 || allow > 255) return fail(MT_ERR_INVALID, "allow %d outside [0,255]", (int)allow);
+  if (report_sectors && !d_count) return fail(MT_ERR_INVALID, "direction pipe scan: the sector report needs the batch's count array");
+  if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
+    return fail(MT_ERR_INVALID, "direction pipe scan: the batch's work-list block is missing, misaligned or too small");
+  return dir_on(c, d_rec, rec_bytes, n_records, 0, d_off, d_sd, n_frames, nullptr, 0, nullptr, allow, d_flags, d_count, nullptr, st,
+                plan_ws, d_keep, report_sectors ? 1 : 0, outputs_in_host_memory ? 1 : 0);
+}
+}  // namespace mtgpu
 
 extern "C" {
 

@@ -130,6 +130,13 @@ struct mtgpu_pipe {
   int32_t pair_blob = 0;
   int32_t pair_max_shift = 0, pair_min_share_q8 = 0;
   int pair_report = 0;
+  // mtgpu_pipe_set_dir (include/mtgpu_pipe_dir.h): dir != 0: every submit runs the direction scan (ctx_launch_dir) with
+  // the allow byte dir_allow, rose and active plane under the keep plane when `masked`; dir_report: MT_PIPE_REPORT_CENTRES
+  // or MT_PIPE_REPORT_SECTORS.  A fourth mode: never together with min_blob > 0, gmc or pair_blob > 0.  They change only
+  // while no batch is being filled or in flight.
+  int dir = 0;
+  int32_t dir_allow = 0;
+  int dir_report = 0;
   std::vector<mtgpu_batch *> bufs;
   std::deque<mtgpu_batch *> inflight;
   std::mutex mu;
@@ -277,6 +284,12 @@ int alloc_batch(mtgpu_batch **out, mtgpu_pipe *p, uint64_t max_records, uint32_t
 bad:
   free_batch(b);
   return rc;
+}
+
+// The refusal between the direction mode and one of the three other modes, worded once for all six places: `runs`
+// (`setter`) is the mode the pipe already has, `other` what cannot stand next to direction.
+int refuse_next_to_dir(const char *runs, const char *setter, const char *other) {
+  return fail(MT_ERR_UNSUPPORTED, "this pipe runs the %s (%s): %s and direction are not together yet", runs, setter, other);
 }
 
 // hipSetDevice only when this thread's current device differs (a submit per few hundred
@@ -442,6 +455,10 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
       rc = mtgpu::ctx_launch_blobs(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
                                    p->min_blob, p->report == MT_PIPE_REPORT_LARGEST ? 1 : 0, b->d_flags, b->d_centres, st,
                                    b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes, d_box);
+    else if (p->dir)   // mtgpu_pipe_set_dir: the direction scan, rose and active plane under the pipe's keep plane when it has a mask
+      rc = mtgpu::ctx_launch_dir(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
+                                 p->dir_allow, p->dir_report == MT_PIPE_REPORT_SECTORS ? 1 : 0, b->d_flags, b->d_centres, st,
+                                 b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
     else if (p->masked)   // mtgpu_pipe_set_keep: the masked scan, its work list in the batch's own block like the plain one's
       rc = mtgpu::ctx_launch_zones(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->d_keep, b->d_flags,
                                    b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
@@ -617,6 +634,7 @@ int mtgpu_pipe_set_blobs(mtgpu_pipe *p, int32_t min_blob_cells, int report) {
   if (p->gmc)
     return fail(MT_ERR_UNSUPPORTED, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): blobs and compensation are "
                 "not together yet");
+  if (p->dir) return refuse_next_to_dir("direction scan", "mtgpu_pipe_set_dir", "blobs");
   const int rc = mtgpu::ctx_blobs_supported(p->ctx);         // MT_ERR_UNSUPPORTED, the grid named: nothing changes
   if (rc != MT_OK) return rc;
   p->min_blob = min_blob_cells;
@@ -656,6 +674,7 @@ int mtgpu_pipe_set_gmc(mtgpu_pipe *p, int enable, int32_t max_shift, int32_t min
   if (p->min_blob > 0)
     return fail(MT_ERR_UNSUPPORTED, "this pipe runs the blob scan (mtgpu_pipe_set_blobs): blobs and compensation are not "
                 "together yet");
+  if (p->dir) return refuse_next_to_dir("direction scan", "mtgpu_pipe_set_dir", "compensation");
   const int rc = mtgpu::ctx_gmc_supported(p->ctx);           // MT_ERR_UNSUPPORTED, the grid named: nothing changes
   if (rc != MT_OK) return rc;
   p->gmc = 1;
@@ -701,6 +720,7 @@ int mtgpu_pipe_set_gmc_blobs(mtgpu_pipe *p, int32_t min_blob_cells, int32_t max_
   if (p->gmc)
     return fail(MT_ERR_INVALID, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): turn it off first "
                 "(mtgpu_pipe_set_gmc(pipe, 0, 0, 0, 0)), then call mtgpu_pipe_set_gmc_blobs");
+  if (p->dir) return refuse_next_to_dir("direction scan", "mtgpu_pipe_set_dir", "the compensated blob scan");
   const int rc = mtgpu::ctx_gmc_blobs_supported(p->ctx);     // MT_ERR_UNSUPPORTED, the grid named: nothing changes
   if (rc != MT_OK) return rc;
   p->pair_blob = min_blob_cells;
@@ -718,6 +738,41 @@ int mtgpu_pipe_gmc_blobs(const mtgpu_pipe *p, int32_t *min_blob_cells, int32_t *
   if (max_shift) *max_shift = p->pair_max_shift;
   if (min_share_q8) *min_share_q8 = p->pair_min_share_q8;
   if (report) *report = p->pair_report;
+  return 1;
+}
+
+int mtgpu_pipe_set_dir(mtgpu_pipe *p, int enable, int32_t allow, int report) {
+  if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
+  if (enable) {
+    if (allow < 0 || allow > 255) return fail(MT_ERR_INVALID, "allow must be in [0, 255], not %d", (int)allow);
+    if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_SECTORS)
+      return fail(MT_ERR_INVALID, "report is %d: want MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_SECTORS", report);
+    if (report == MT_PIPE_REPORT_SECTORS && !p->centres)
+      return fail(MT_ERR_INVALID, "MT_PIPE_REPORT_SECTORS needs a pipe with MT_LAYOUT_CENTRES: the sector word travels in its count array");
+  }
+  std::lock_guard<std::mutex> lock(p->mu);
+  for (const mtgpu_batch *b : p->bufs)
+    if (b->state == 1 || b->state == 2)
+      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the direction setting",
+                  b->state == 1 ? "being filled" : "in flight");
+  if (!enable) { p->dir = 0; p->dir_allow = 0; p->dir_report = 0; return MT_OK; }
+  if (p->min_blob > 0) return refuse_next_to_dir("blob scan", "mtgpu_pipe_set_blobs", "blobs");
+  if (p->gmc) return refuse_next_to_dir("compensated scan", "mtgpu_pipe_set_gmc", "compensation");
+  if (p->pair_blob > 0) return refuse_next_to_dir("compensated blob scan", "mtgpu_pipe_set_gmc_blobs", "the compensated blob scan");
+  const int rc = mtgpu::ctx_dir_supported(p->ctx);           // MT_ERR_UNSUPPORTED, the grid named: nothing changes
+  if (rc != MT_OK) return rc;
+  p->dir = 1;
+  p->dir_allow = allow;
+  p->dir_report = report;
+  return MT_OK;
+}
+
+int mtgpu_pipe_dir(const mtgpu_pipe *p, int32_t *allow, int *report) {
+  if (!p) return -1;
+  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
+  if (!p->dir) return 0;
+  if (allow) *allow = p->dir_allow;
+  if (report) *report = p->dir_report;
   return 1;
 }
 

@@ -92,6 +92,32 @@ def wedge(k):
     return sum(1 << ((k + j) & 7) for j in (-1, 0, 1))
 
 
+SECTOR_WORD_MAX_COUNT = (1 << 21) - 1
+
+
+def sector_word(rose):
+    """A frame's rose (eight counts, sector 0 = E first) -> the sector word a pipe reports under
+    set_dir(report="sectors") (include/mtgpu_pipe_dir.h): bits 0 .. 7 the present byte (bit k iff n[k] >= 1), bits
+    8 .. 10 the smallest k whose count is maximal (0 when every count is 0), bits 11 .. 31 min(that count, 2^21 - 1)."""
+    n = [int(v) for v in rose]
+    if len(n) != 8 or min(n) < 0:
+        raise ValueError("a rose is eight counts >= 0")
+    present = sum(1 << k for k in range(8) if n[k] >= 1)
+    best = max(n)
+    k_star = n.index(best) if best > 0 else 0
+    return present | (k_star << 8) | (min(best, SECTOR_WORD_MAX_COUNT) << 11)
+
+
+def unpack_sector_word(word):
+    """The sector word -> (present byte, dominant sector or None, count); a frame without a counting moving record
+    (word 0) -> (0, None, 0).  The count saturates at 2^21 - 1."""
+    word = int(word)
+    if not 0 <= word <= 0xFFFFFFFF:
+        raise ValueError(f"sector word {word} outside 32 bits")
+    present, count = word & 0xFF, word >> 11
+    return present, (((word >> 8) & 7) if count else None), count
+
+
 # ------------------------------------------------------------------ the command
 
 def _names(flag):

@@ -1354,6 +1354,35 @@ class ScanPipe:
         names = {v: k for k, v in self._PAIR_REPORTS.items()}
         return int(n.value), int(ms.value), int(q8.value), names[r.value]
 
+    _DIR_REPORTS = {"centres": _abi.MT_PIPE_REPORT_CENTRES, "sectors": _abi.MT_PIPE_REPORT_SECTORS}
+
+    def set_dir(self, allow=_abi.DIR_ALL, report: str = "centres"):
+        """The direction filter on the decode path (mtgpu_pipe_set_dir), the pipe's fourth mode: from now on a record of
+        every batch votes only if the sector of dst - src is allowed (include/mtgpu_dir.h); under the keep mask, if the
+        pipe has one, the rose counts only records of kept cells and the active plane is the masked one.  allow: the
+        byte 0 .. 255, or sector names ("E,SE" / ["E", "SE"], direction.allow_from_names).  report: what
+        drain_centres() returns per frame, "centres" or "sectors" — the frame's sector word
+        (direction.unpack_sector_word); "sectors" needs centres=True.  Only while no batch is being filled or in flight
+        (call drain() first): otherwise MtgpuError(MT_ERR_BUSY) and nothing changes.  Not together with set_blobs,
+        set_gmc or set_gmc_blobs: MtgpuError(MT_ERR_UNSUPPORTED)."""
+        if report not in self._DIR_REPORTS:
+            raise ValueError(f"report is {report!r}, not 'centres' or 'sectors'")
+        if not isinstance(allow, (int, np.integer)):
+            from .direction import allow_from_names
+            allow = allow_from_names(allow)
+        check(self._lib.mtgpu_pipe_set_dir(self._pipe, 1, int(allow), self._DIR_REPORTS[report]))
+
+    def clear_dir(self):
+        """The direction filter off (mtgpu_pipe_set_dir with enable 0): the pipe is the plain or masked pipe it was before."""
+        check(self._lib.mtgpu_pipe_set_dir(self._pipe, 0, 0, 0))
+
+    def dir(self) -> Optional[Tuple[int, str]]:
+        """None, or (allow, report) while the pipe's submits run the direction scan (mtgpu_pipe_dir)."""
+        a, r = C.c_int32(), C.c_int()
+        if self._lib.mtgpu_pipe_dir(self._pipe, C.byref(a), C.byref(r)) != 1:
+            return None
+        return int(a.value), ("sectors" if r.value == _abi.MT_PIPE_REPORT_SECTORS else "centres")
+
     @staticmethod
     def unpack_gmc_vector(word: int) -> Tuple[int, int]:
         """(gx, gy) of a count reported under set_gmc(report="vector"): two signed 16-bit halves."""

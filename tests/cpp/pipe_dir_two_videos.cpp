@@ -1,0 +1,69 @@
+// pipe_dir_two_videos.cpp — one worker pool, several videos, a direction setting that must not leak
+// (tests/test_gpu_pipe_dir.py):
+//   pipe_dir_two_videos STREAM.mtmv THREADS
+// runs run_scan_pipeline (csrc/host/mtgpu_host.hpp) four times on the SAME pool of GpuBackends, as process_batch does
+// for the videos of one stream: the recording with W, NW and SW ignored (allow 0xC7), the recording without the mode, the
+// recording with E, NE and SE ignored (allow 0x7C) and the sector words reported, and — a conflict that must be refused
+// before any decode — direction together with min_blob_cells 3.  After each run it prints
+//   run <i> rc <rc> dir <d0,d1,...> motion_frames <n> frames_scanned <n> frames <n> present <p0:..:p7> dominant <d0:..:d7> timestamps <t0,t1,...>
+// (dir: mtgpu_pipe_dir's allow byte of every backend of the pool that holds a pipe, -1 where the mode is off, with an `S`
+// behind it where the pipe reports the sector word; timestamps sorted, %.17g).
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "mtgpu_host.hpp"
+
+using namespace mtgpu_host;
+
+int main(int argc, char **argv) {
+  if (argc != 3) { std::fprintf(stderr, "usage: %s STREAM.mtmv THREADS\n", argv[0]); return 2; }
+  const int threads = std::atoi(argv[2]);
+  try {
+    Config::load_all();
+    MtmvFile file(argv[1]);
+    std::vector<std::unique_ptr<GpuBackend>> pool;
+    for (int i = 0; i < threads; ++i) pool.emplace_back(new GpuBackend());
+    for (int run = 0; run < 4; ++run) {
+      PipelineResult r;
+      r.dir_allow = run == 0 ? 0xC7 : run == 1 ? -2 : run == 2 ? 0x7C : 0xFF;
+      r.dir_sectors = run == 2;
+      r.min_blob_cells = run == 3 ? 3 : 0;
+      const int rc = run_scan_pipeline([&]() -> std::unique_ptr<FrameSource> { return std::unique_ptr<FrameSource>(new MtmvSource(file)); },
+                                       threads, r, 0, &pool);
+      if (rc != 0 && run != 3) { std::fprintf(stderr, "error: run %d: %s\n", run, r.error.c_str()); return 1; }
+      if (run == 3) {
+        std::printf("run 3 rc %d frames_scanned %llu error %s\n", rc, (unsigned long long)r.frames_scanned, r.error.c_str());
+        continue;
+      }
+      std::printf("run %d rc %d dir ", run, rc);
+      bool first = true;
+      for (auto &b : pool)
+        if (b->pipe()) {
+          int32_t allow = 0;
+          int report = 0;
+          const int on = mtgpu_pipe_dir(b->pipe(), &allow, &report);
+          std::printf("%s%d%s", first ? "" : ",", on == 1 ? (int)allow : -1, on == 1 && report == MT_PIPE_REPORT_SECTORS ? "S" : "");
+          first = false;
+        }
+      std::vector<double> ts = r.timestamps;
+      std::sort(ts.begin(), ts.end());
+      std::printf(" motion_frames %zu frames_scanned %llu frames %llu present ", r.motion_frames, (unsigned long long)r.frames_scanned,
+                  (unsigned long long)r.dir_frames);
+      for (int k = 0; k < 8; ++k) std::printf("%s%llu", k ? ":" : "", (unsigned long long)r.dir_present_frames[k]);
+      std::printf(" dominant ");
+      for (int k = 0; k < 8; ++k) std::printf("%s%llu", k ? ":" : "", (unsigned long long)r.dir_dominant_frames[k]);
+      std::printf(" timestamps ");
+      for (size_t i = 0; i < ts.size(); ++i) std::printf("%s%.17g", i ? "," : "", ts[i]);
+      if (ts.empty()) std::printf("-");
+      std::printf("\n");
+    }
+  } catch (const std::exception &e) {
+    std::fprintf(stderr, "error: %s\n", e.what());
+    return 1;
+  }
+  return 0;
+}
