@@ -46,6 +46,8 @@
  *                  C++ host layer only: MTGPU_STAGING, MTGPU_BATCH_MB, MTGPU_CPU_TOKENS, MTGPU_CPU_WINDOW (mtgpu_host.hpp)
  *    tests only    MTGPU_FORCE_FB=32|1|2|4|8|108, MTGPU_FORCE_BLOCK=512|1024, MTGPU_FORCE_SLICES, MTGPU_GROUP,
  *                  MTGPU_ITEM_CHUNK, MTGPU_MERGE_LARGE_MIN (reach every kernel form on small inputs),
+ *                  MTGPU_WG_PER_CU=1|2|-1 (scan workgroups per CU: at most one / two on every launch, -1 = never
+ *                  fewer than the tile allows; default: one per CU for launches of large frames),
  *                  MTGPU_INJECT_SUBMIT_FAIL / _GROW_FAIL / _COLLECT_FAIL / MTGPU_INJECT_ONCE (pipe error paths)
  */
 #ifndef MTGPU_H

@@ -94,6 +94,8 @@ struct mtgpu_ctx {
   int item_chunk = 0;    // MTGPU_ITEM_CHUNK (tests): workgroups per kernel launch, 0 = 2^30
   int lds_max = 0;       // device limit of LDS per workgroup
   int group_request = 0; // MTGPU_GROUP: frames per workgroup, 0 = automatic
+  int per_cu_request = 0; // MTGPU_WG_PER_CU: 1 | 2 = at most that many scan workgroups per CU on every launch, -1 = never
+                          // fewer than the tile allows, 0 = automatic (choose_lds_floor)
   int check_offsets = 0; // MTGPU_CHECK_OFFSETS=1: the device entry points verify "frame_off non-decreasing" first (one sync per call)
   // Launch scratch (work lists of the device entry points, spill queues, slice tiles, merge workspaces): a ring of
   // device blocks, each with the event of its last user.  Whoever takes a block makes ITS stream wait for that event,
@@ -279,6 +281,11 @@ int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
   // Workgroup size: 512 threads x 4 loads in flight per lane keep a CU's memory queue full at
   // 4 workgroups/CU (measured +2.5 % over 256 on 1080p); tiles above 48 KB run 1-2
   // workgroups/CU and take 16 waves each.
+  // "4 workgroups/CU" is what LDS allows, not what runs: four 512-thread workgroups are 8 waves per SIMD, which a CU
+  // admits only up to 80 SGPRs and 64 VGPRs per wave — min(8, floor(800 / (ceil(sgpr / 16) * 16 + 16))) — and every
+  // scan kernel takes 106 SGPRs (the compact ones 67-85 VGPRs as well): 6 or 5 waves per SIMD, THREE such workgroups
+  // per CU.  Every figure quoted here was taken at three; four, tried in round 22, is slower (scan_kernels.hip), and
+  // launches of large frames ask for ONE per CU (choose_lds_floor).
   int block = lds <= 48u * 1024u ? 512 : 1024;
   // MTGPU_FORCE_BLOCK (tests): 512 | 1024.  The library instantiates what the planner can choose plus that switch:
   // 512- and 1024-thread workgroups for single tiles, 1024 for banded plans (their tiles always exceed 48 KB).
@@ -302,6 +309,7 @@ int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
   k.sys_flags = 0;                                            // per launch: launch_scan_on
   k.sys_centres = 0;
   c->group_request = env_int("MTGPU_GROUP", 0);
+  c->per_cu_request = env_int("MTGPU_WG_PER_CU", 0);
   c->check_offsets = env_int("MTGPU_CHECK_OFFSETS", 0) != 0;
   c->item_chunk = env_int("MTGPU_ITEM_CHUNK", 0);
   if (c->item_chunk < 0) c->item_chunk = 0;
@@ -335,7 +343,8 @@ int choose_slices(const mtgpu_ctx *c, uint64_t n_records, uint32_t n_frames) {
 // Frames per workgroup.  Very short workgroups are started more slowly than they finish (the
 // dispatcher starts ~19 per microsecond), so few are alive per CU and nothing overlaps their
 // zeroing / cluster test: frames below ~128 KB are scanned two or more per workgroup.  Measured
-// after the 32-bit kernels dropped to 58-61 VGPRs (four workgroups per CU): 65 KB frames (1080p,
+// after the 32-bit kernels dropped to 58-61 VGPRs (which allows four workgroups per CU; their 106 SGPRs admitted
+// three, see make_plan, so the figures here and below are three-per-CU figures): 65 KB frames (1080p,
 // one compact record per cell) +5 % with 2-4 per workgroup; 252 KB and 326 KB frames are 2-3 %
 // FASTER one per workgroup (the earlier 1 MB target dated from two workgroups per CU).
 // Only for batches that fill the chip several times over.
@@ -368,6 +377,9 @@ int choose_group(const mtgpu_ctx *c, uint64_t n_records, uint32_t n_frames, int 
     //   but -3 % on ragged ones (profiles/r06_group_ab.log, second part: 10 MB work units leave a long tail) — not taken;
     //   40-byte records on shared tiles (1080p 1.3 MB frames, 326 KB frames): nothing or a loss — they stay at one.
     // Only where every workgroup slot of the chip is still filled twice over afterwards.
+    // (per_cu is what LDS allows.  This rule is about compact records, whose kernels take 106 SGPRs and 67-85 VGPRs:
+    //  6 or 5 waves per SIMD, so a <= 40 KB tile really has THREE workgroups per CU, not four, and the bound below is
+    //  stricter than "twice over" by a third.  It is left where it was measured.)
     const uint64_t per_cu = c->plan.lds_bytes <= 40 * 1024 ? 4u : (c->plan.lds_bytes <= 80 * 1024 ? 2u : 1u);
     if (g == 1 && c->k.bands == 1 && rec_bytes == MT_COMPACT_BYTES && avg <= (2ull << 20) &&
         (uint64_t)n_frames >= cus * per_cu * 4ull)
@@ -375,6 +387,37 @@ int choose_group(const mtgpu_ctx *c, uint64_t n_records, uint32_t n_frames, int 
   }
   if (g > 64) g = 64;
   return g < 1 ? 1 : g;
+}
+
+// Workgroups per CU for this launch, set through the size of the dynamic LDS: a workgroup that asks for more than
+// half of a CU's 160 KB has the CU to itself, more than a third shares it with one other.  Returns the least LDS
+// size to ask for (0: whatever the tile needs).
+// Round 22, 40-byte records, scan-kernel time at 3 (what the tile and the kernels' 106 SGPRs allow) / 2 / 1 per CU
+// (profiles/r22_per_cu_legs.log): streaming LARGE frames, a CU is fastest with ONE workgroup — 256 record streams
+// into the memory system instead of 768 —
+//   1080p dense8x8 (1.26 MB frames)  16 384 frames 2941 / 2911 / 2874 us (-2.3 %), 8192: -2.1 %, 4096: -1.7 %, 2048: -1.6 %,
+//                                    1024: 189.5 / 187.8 / 189.7, 768: 151.2 / 166.2 / 148.2, 512: 96.7 / 96.9 / 98.8 (+2.2 %)
+//   720p dense8x8 (557 KB)           32 768 frames 2675 / 2659 / 2595 (-3.0 %)
+// while smaller frames need the neighbours that stream during a workgroup's zeroing and cluster test —
+//   1080p dense16 (316 KB)           65 536 frames 2923 / 2950 / 3116 (+6.6 %)
+//   480p dense8x8 (186 KB)           1791 / 1762 / 1949;   720p dense16 (139 KB) 2632 / 2619 / 3284;   480p dense16 (46 KB,
+//                                    8 per workgroup) 1765 / 1890 / 3204
+//   compact records                  1080p dense8x8 (252 KB) 629 / 617 / 783, dense16 (63 KB) 691 / 824 / 1385
+// (four per CU, which the kernels' SGPR count had never admitted, is slower than three: scan_kernels.hip).  So: one
+// per CU for frames of half a megabyte and more, in launches that give every CU at least eight of them; two per CU
+// gains 0.5-1.9 % on some of the shapes in between and loses 1-19 % on others: not taken.
+constexpr int kLdsPerCu = 160 * 1024;
+constexpr int kLdsOnePerCu = kLdsPerCu / 2 + 1024, kLdsTwoPerCu = kLdsPerCu / 3 + 1024;
+int choose_lds_floor(const mtgpu_ctx *c, uint64_t n_records, uint32_t n_frames, int rec_bytes, int slices, int group) {
+  int floor_bytes = 0;
+  if (c->per_cu_request == 1) floor_bytes = kLdsOnePerCu;
+  else if (c->per_cu_request == 2) floor_bytes = kLdsTwoPerCu;
+  else if (c->per_cu_request == 0 && rec_bytes == MT_MV_BYTES && c->k.bands == 1 && slices == 1 && group == 1 && n_frames != 0) {
+    const uint64_t avg = n_records * (uint64_t)rec_bytes / n_frames;
+    const uint64_t cus = (uint64_t)(c->plan.cu_count > 0 ? c->plan.cu_count : 256);
+    if (avg >= 512ull * 1024ull && (uint64_t)n_frames >= cus * 8ull) floor_bytes = kLdsOnePerCu;
+  }
+  return floor_bytes <= c->lds_max ? floor_bytes : 0;
 }
 
 // A scratch block of at least `bytes` for work queued on `st` (see mtgpu_ctx::Scratch).  The block is the caller's
@@ -525,6 +568,8 @@ int launch_scan_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uin
       L.k.group = 1;                                          // a tile that fills LDS to the last 2 KB: one frame per workgroup
     }
   }
+  // fewer workgroups per CU where that streams faster: the kernel never touches the LDS beyond its tile
+  L.lds_bytes = std::max(L.lds_bytes, choose_lds_floor(c, n_records - rebase, n_frames, rec_bytes, L.k.slices, L.k.group));
   L.stream = st;
   // launch scratch, one stream-ordered block: [work list + planning counts | spill queue or slice tiles + tickets]
   // the caller's own block for the work list (a pipe's batch), if it is large enough: the pool then serves only

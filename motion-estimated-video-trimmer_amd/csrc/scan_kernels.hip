@@ -1009,6 +1009,14 @@ __device__ __forceinline__ void scan_item(
 // The grid is sized for "every frame has side data"; the workgroups past the end of the list find a kNoFrame entry
 // and leave — all of them at the END of the grid, after the last workgroup with work, whatever the stream's key-frame
 // period is.
+//
+// Waves per SIMD.  A CU admits min(8, floor(800 / (ceil(sgpr / 16) * 16 + 16))) waves per SIMD by their scalar
+// registers: 8 up to 80 SGPRs, 6 at the 106 every instantiation below takes (nothing holds the allocator back) — THREE
+// 512-thread workgroups per CU, also where LDS (<= 40 KB) and VGPRs (<= 64) would allow four.  Left so on purpose:
+// held to 78 SGPRs by amdgpu_waves_per_eu(8, 8) (no scratch, no spilled scalar inside stream_mv40's loop) the 1080p
+// kernel ran four per CU and was 0.6 % SLOWER on 1.3 MB frames (docs/rounds/r22_scan_residency.md).  Streaming large
+// frames, a CU is better off with fewer workgroups, not more: launch_scan_on asks for ONE per CU there, through the
+// size of the dynamic LDS (choose_lds_floor, mtgpu_api.hip).
 template <int BLOCK, int UNROLL, int FB, int MODE, int REC, bool SPILL>
 __global__ __launch_bounds__(BLOCK) void scan_frames_kernel(
     const unsigned char *__restrict__ mv, const WorkItem *__restrict__ work,
