@@ -44,25 +44,12 @@ struct ActK {
   int max_run;                   // contributing frames the accumulators may hold (>= 1)
 };
 
-struct ActLaunch {
-  const unsigned char *mv;
-  unsigned long long n_records;           // frame_off entries are clamped to this (before `rebase`)
-  unsigned long long rebase;
-  const unsigned long long *frame_off;    // n_frames + 1
-  const unsigned char *has_sd;            // n_frames or null
-  unsigned int n_frames;
-  int rec_bytes;                          // 40 or 8
+struct ActLaunch : BatchLaunch {            // (plan_ws is unused when n_frames == 0)
   const unsigned long long *stream_off;   // n_streams + 1
   unsigned int n_streams;
   unsigned int *active, *centre, *frames; // device memory; any may be null
   ActK k;
   int acc_bits;                           // 32, 16 or 0
-  int lds_bytes;
-  int lds_max;                            // device limit of dynamic LDS per workgroup
-  int device;
-  void *plan_ws;                          // plan_scratch_bytes(n_frames), 32-byte aligned (unused when n_frames == 0)
-  hipStream_t stream;
-  hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the map kernel; else nullptr
 };
 
 // Clears the non-null outputs, builds the work list (launch_plan), then one workgroup per run of k.run entries.

@@ -44,14 +44,7 @@ struct DirK {
   int tile_words;                // dir_tile_words
 };
 
-struct DirLaunch {
-  const unsigned char *mv;
-  unsigned long long n_records;           // frame_off entries are clamped to this (before `rebase`)
-  unsigned long long rebase;
-  const unsigned long long *frame_off;    // n_frames + 1
-  const unsigned char *has_sd;            // n_frames or null
-  unsigned int n_frames;
-  int rec_bytes;                          // 40 or 8
+struct DirLaunch : BatchLaunch {
   const unsigned long long *stream_off;   // n_streams + 1, or null: `allow` serves every frame
   unsigned int n_streams;
   const unsigned char *allows;            // n_streams bytes, device memory, or null (then stream_off is null, n_streams 0)
@@ -70,12 +63,6 @@ struct DirLaunch {
   const unsigned long long *keep = nullptr;
   int sys_flags = 0, sys_centres = 0, report_sectors = 0;
   DirK k;
-  int lds_bytes;
-  int lds_max;                            // device limit of dynamic LDS per workgroup
-  int device;
-  void *plan_ws;                          // plan_scratch_bytes(n_frames), 32-byte aligned
-  hipStream_t stream;
-  hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the scan kernel; else nullptr
 };
 
 // Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.  Pipe form: no fill —

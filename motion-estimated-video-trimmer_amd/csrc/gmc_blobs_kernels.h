@@ -69,14 +69,7 @@ struct GmcBlobArgs {
   int report;                             // pipe form: kGmcBlobReport*, what out.centres receives
 };
 
-struct GmcBlobLaunch {
-  const unsigned char *mv;
-  unsigned long long n_records;           // frame_off entries are clamped to this (before `rebase`)
-  unsigned long long rebase;
-  const unsigned long long *frame_off;    // n_frames + 1
-  const unsigned char *has_sd;            // n_frames or null
-  unsigned int n_frames;
-  int rec_bytes;                          // 40 or 8
+struct GmcBlobLaunch : BatchLaunch {
   const unsigned long long *stream_off;   // n_streams + 1; null iff keep is null
   unsigned int n_streams;                 // 0 iff keep is null
   const unsigned long long *keep;         // n_streams x gh x W, device memory; null: no mask, no stream lookup
@@ -93,12 +86,6 @@ struct GmcBlobLaunch {
   int pipe = 0;
   int sys_flags = 0, sys_count = 0, report = 0;
   GmcBlobK k;
-  int lds_bytes;
-  int lds_max;                            // device limit of dynamic LDS per workgroup
-  int device;
-  void *plan_ws;                          // plan_scratch_bytes(n_frames), 32-byte aligned
-  hipStream_t stream;
-  hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the scan kernel; else nullptr
 };
 
 // Fills the non-null outputs with the answer of a frame without a blob (0; an all-0xFFFF box; a zero info), builds the

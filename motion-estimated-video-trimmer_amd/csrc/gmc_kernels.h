@@ -46,14 +46,7 @@ struct GmcK {
   unsigned int min_share_q8;     // [0, 256]: a mode is applied iff n * 256 >= min_share_q8 * n_in
 };
 
-struct GmcLaunch {
-  const unsigned char *mv;
-  unsigned long long n_records;           // frame_off entries are clamped to this (before `rebase`)
-  unsigned long long rebase;
-  const unsigned long long *frame_off;    // n_frames + 1
-  const unsigned char *has_sd;            // n_frames or null
-  unsigned int n_frames;
-  int rec_bytes;                          // 40 or 8
+struct GmcLaunch : BatchLaunch {
   unsigned char *flags;                   // n_frames bytes, device memory, or null
   unsigned int *centres;                  // n_frames words, or null
   unsigned int *info;                     // n_frames x kGmcInfoWords words (mt_gmc_info), or null
@@ -67,12 +60,6 @@ struct GmcLaunch {
   const unsigned long long *keep = nullptr;
   int sys_flags = 0, sys_centres = 0, report_vector = 0;
   GmcK k;
-  int lds_bytes;
-  int lds_max;                            // device limit of dynamic LDS per workgroup
-  int device;
-  void *plan_ws;                          // plan_scratch_bytes(n_frames), 32-byte aligned
-  hipStream_t stream;
-  hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the scan kernel; else nullptr
 };
 
 // Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.  Pipe form: no fill —

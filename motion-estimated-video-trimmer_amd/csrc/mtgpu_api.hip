@@ -505,6 +505,12 @@ void scratch_release(mtgpu_ctx *c, int slot, hipStream_t st) {
   sc.cv.notify_one();
 }
 
+}  // namespace
+
+#include "api_common.h"   // here: its helpers use mtgpu_ctx and the scratch ring above
+
+namespace {
+
 // Launches the scan on `st`; scratch (band centre counts, slice tiles + tickets) is allocated
 // and freed stream-ordered, so concurrent callers share nothing.
 // a caller's pointer (the *_device entry points): device memory takes plain stores; anything else the runtime
@@ -526,21 +532,12 @@ int launch_scan_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uin
   if (flags_sys < 0) flags_sys = d_flags ? result_memory_is_sys(d_flags) : 0;
   if (centres_sys < 0) centres_sys = d_centres ? result_memory_is_sys(d_centres) : 0;
   mtgpu::ScanLaunch L;
-  L.rec_bytes = rec_bytes;
-  L.lds_max = c->lds_max;
-  L.device = c->device;
-  L.mv = static_cast<const unsigned char *>(d_mv);
-  L.n_records = n_records;
-  L.rebase = rebase;
-  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
-  L.has_sd = d_sd;
-  L.n_frames = n_frames;
+  fill_batch(L, c, d_mv, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, c->plan.lds_bytes, st);
   L.flags = d_flags;
   L.centres = d_centres;
   L.spill_q = nullptr;
   L.slice_ws = nullptr;
   L.tickets = nullptr;
-  L.plan_ws = nullptr;
   L.k = c->k;
   L.k.sys_flags = flags_sys;
   L.k.sys_centres = centres_sys;
@@ -550,7 +547,6 @@ int launch_scan_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uin
     return fail(MT_ERR_INVALID, "%u frames x %d slices: work items must stay below 2^32 per call", n_frames, L.k.slices);
   L.block = c->plan.block_threads;
   L.item_chunk = (unsigned long long)c->item_chunk;
-  L.lds_bytes = c->plan.lds_bytes;
   if (c->wide_lds_bytes > c->plan.lds_bytes &&
       (uint64_t)n_frames * (uint64_t)L.k.bands * (uint64_t)L.k.slices <= (uint64_t)c->plan.cu_count) {
     L.k.chunk_rows = c->wide_chunk_rows;        // at most one workgroup per CU: bigger mask buffer, fewer chunks
@@ -570,7 +566,6 @@ int launch_scan_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uin
   }
   // fewer workgroups per CU where that streams faster: the kernel never touches the LDS beyond its tile
   L.lds_bytes = std::max(L.lds_bytes, choose_lds_floor(c, n_records - rebase, n_frames, rec_bytes, L.k.slices, L.k.group));
-  L.stream = st;
   // launch scratch, one stream-ordered block: [work list + planning counts | spill queue or slice tiles + tickets]
   // the caller's own block for the work list (a pipe's batch), if it is large enough: the pool then serves only
   // the spill queue / the slice tiles, i.e. nothing at all for single-tile plans
@@ -580,42 +575,16 @@ int launch_scan_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uin
   if (L.k.bands > 1) bytes += sizeof(unsigned int) * ((size_t)(n_records - rebase) + 4);   // spill queue: a slot per record
   if (L.k.slices > 1)
     bytes += sizeof(unsigned int) * ((size_t)n_frames * (size_t)L.k.slices * (size_t)L.k.cnt_words + (size_t)n_frames + 4);
-  void *scratch = nullptr;
-  int slot = -1;
-  hipError_t e = hipSuccess;
-  if (bytes) {
-    const int rc0 = scratch_acquire(c, bytes, st, &slot, &scratch);
-    if (rc0 != MT_OK) return rc0;
-  }
-  L.plan_ws = own_plan ? own_plan_ws : scratch;
-  unsigned int *rest = reinterpret_cast<unsigned int *>(static_cast<unsigned char *>(scratch) + plan_bytes);
+  PlanWs ws(c, st, nullptr, bytes);
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = own_plan ? own_plan_ws : ws.p;
+  unsigned int *rest = reinterpret_cast<unsigned int *>(static_cast<unsigned char *>(ws.p) + plan_bytes);
   if (L.k.bands > 1) L.spill_q = rest;
   if (L.k.slices > 1) {
     L.slice_ws = rest;
     L.tickets = L.slice_ws + (((size_t)n_frames * (size_t)L.k.slices * (size_t)L.k.cnt_words + 3) & ~(size_t)3);
   }
-  L.ev_planned = nullptr;
-  int rc = MT_OK;
-  if (c->prof.on.load(std::memory_order_relaxed)) {
-    mtgpu_ctx::Profile &pf = c->prof;
-    std::lock_guard<std::mutex> lock(pf.mu);
-    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
-    if (e == hipSuccess && pf.created) {
-      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
-      e = hipEventRecord(t[0], st);
-      L.ev_planned = t[1];
-      if (e == hipSuccess) e = mtgpu::launch_scan(L);
-      if (e == hipSuccess) e = hipEventRecord(t[2], st);
-      if (e == hipSuccess) ++pf.count;
-    } else if (e == hipSuccess) {
-      e = mtgpu::launch_scan(L);
-    }
-  } else {
-    e = mtgpu::launch_scan(L);
-  }
-  if (e != hipSuccess) rc = hip_fail(e, "scan launch");
-  if (slot >= 0) scratch_release(c, slot, st);
-  return rc;
+  return profiled_launch(c, st, L, mtgpu::launch_scan, "scan launch");
 }
 
 }  // namespace
@@ -847,19 +816,19 @@ int mtgpu_get_plan(const mtgpu_ctx *c, mtgpu_plan *out) {
 namespace {
 // MTGPU_CHECK_OFFSETS=1: verify the CSR precondition of the device entry points on the device, BEFORE the scan is
 // queued — costs one small kernel and one stream synchronisation per call, which is why it is opt-in.
-int check_offsets_on(mtgpu_ctx *c, const uint64_t *d_off, uint32_t n_frames, hipStream_t st) {
-  void *d_bad = nullptr;
-  int slot = -1;
-  const int rc0 = scratch_acquire(c, sizeof(unsigned int), st, &slot, &d_bad);
-  if (rc0 != MT_OK) return rc0;
+// Nothing unless the context asks for it and the batch has frames.
+int check_offsets_on(mtgpu_ctx *c, const uint64_t *d_off, uint32_t n_frames, void *stream) {
+  if (!c->check_offsets || n_frames == 0) return MT_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  PlanWs bad(c, st, nullptr, sizeof(unsigned int));
+  if (bad.rc != MT_OK) return bad.rc;
   unsigned int first_bad = 0xffffffffu;
-  hipError_t e = hipMemsetAsync(d_bad, 0xff, sizeof(unsigned int), st);
+  hipError_t e = hipMemsetAsync(bad.p, 0xff, sizeof(unsigned int), st);
   if (e == hipSuccess)
     e = mtgpu::launch_check_offsets(reinterpret_cast<const unsigned long long *>(d_off), n_frames,
-                                    static_cast<unsigned int *>(d_bad), st);
-  if (e == hipSuccess) e = hipMemcpyAsync(&first_bad, d_bad, sizeof first_bad, hipMemcpyDeviceToHost, st);
+                                    static_cast<unsigned int *>(bad.p), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&first_bad, bad.p, sizeof first_bad, hipMemcpyDeviceToHost, st);
   const hipError_t e2 = hipStreamSynchronize(st);
-  scratch_release(c, slot, st);
   if (e != hipSuccess) return hip_fail(e, "frame_off check");
   if (e2 != hipSuccess) return hip_fail(e2, "hipStreamSynchronize(frame_off check)");
   if (first_bad != 0xffffffffu)
@@ -879,10 +848,7 @@ int mtgpu_scan_frames_device(mtgpu_ctx *c, const void *d_mv, uint64_t n_records,
   if (n_records > 0 && !d_mv) return fail(MT_ERR_INVALID, "mv is NULL with n_records > 0");
   if (((uintptr_t)d_mv & 3u) != 0) return fail(MT_ERR_INVALID, "mv must be 4-byte aligned");
   HIP_TRY(hipSetDevice(c->device));
-  if (c->check_offsets) {
-    const int rc = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
-    if (rc != MT_OK) return rc;
-  }
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
   return launch_scan_on(c, d_mv, n_records, d_frame_off, d_has_sd, n_frames, d_flags,
                         static_cast<hipStream_t>(stream), MT_MV_BYTES, -1);
 }
@@ -896,10 +862,7 @@ int mtgpu_scan_frames_device_compact(mtgpu_ctx *c, const void *d_rec8, uint64_t 
   if (n_records > 0 && !d_rec8) return fail(MT_ERR_INVALID, "records is NULL with n_records > 0");
   if (((uintptr_t)d_rec8 & 7u) != 0) return fail(MT_ERR_INVALID, "compact records must be 8-byte aligned");
   HIP_TRY(hipSetDevice(c->device));
-  if (c->check_offsets) {
-    const int rc = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
-    if (rc != MT_OK) return rc;
-  }
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
   return launch_scan_on(c, d_rec8, n_records, d_frame_off, d_has_sd, n_frames, d_flags,
                         static_cast<hipStream_t>(stream), MT_COMPACT_BYTES, -1);
 }
@@ -908,21 +871,15 @@ int mtgpu_scan_centres_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, ui
                               const uint64_t *d_frame_off, const uint8_t *d_has_sd, uint32_t n_frames,
                               uint8_t *d_flags, uint32_t *d_centres, void *stream) {
   if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
-    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
+  MT_TRY(check_rec_bytes(rec_bytes));
   if (n_frames == 0) return MT_OK;
   if (!d_frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
-  if (!d_flags && !d_centres) return fail(MT_ERR_INVALID, "d_flags and d_centres are both NULL");
+  MT_TRY(check_any_output("d_", {{"flags", d_flags}, {"centres", d_centres}}));
   if (n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
-  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)d_rec & 7u) != 0)
-    return fail(MT_ERR_INVALID, "d_rec: compact records must be 8-byte aligned");
-  if (((uintptr_t)d_rec & 3u) != 0) return fail(MT_ERR_INVALID, "d_rec must be 4-byte aligned");
-  if (((uintptr_t)d_centres & 3u) != 0) return fail(MT_ERR_INVALID, "d_centres must be 4-byte aligned");
+  MT_TRY(check_rec("d_", rec_bytes, d_rec));
+  MT_TRY(check_aligned("d_", {{"centres", d_centres, 4}}));
   HIP_TRY(hipSetDevice(c->device));
-  if (c->check_offsets) {
-    const int rc = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
-    if (rc != MT_OK) return rc;
-  }
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
   return launch_scan_on(c, d_rec, n_records, d_frame_off, d_has_sd, n_frames, d_flags, static_cast<hipStream_t>(stream),
                         rec_bytes, -1, 0, nullptr, 0, d_centres, -1);
 }
@@ -1011,33 +968,13 @@ int scan_frames_host(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off,
   const uint64_t n_records = r_end - r_begin;
   if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
 
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
-  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
-  // [flags n_frames | pad to 256 | centres n_frames x 4]
-  const size_t centres_at = ((size_t)n_frames + 255u) & ~(size_t)255u;
-  if ((rc = c->d_flags.reserve(centres ? centres_at + sizeof(uint32_t) * (size_t)n_frames : (size_t)n_frames)) != MT_OK) return rc;
-  uint32_t *d_centres = centres ? reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(c->d_flags.p) + centres_at) : nullptr;
-  if (has_sd && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
-
-  hipStream_t st = c->stream;
-  DrainOnExit drain{st};
-  if (n_records)
-    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
-  if (has_sd) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
-  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
-  rc = launch_scan_on(c, c->d_mv.p, r_end, static_cast<const uint64_t *>(c->d_off.p),
-                      has_sd ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames,
-                      flags ? static_cast<uint8_t *>(c->d_flags.p) : nullptr, st, MT_MV_BYTES, 0, r_begin, nullptr, 0,
-                      d_centres, 0);
-  if (rc != MT_OK) return rc;
-  if (flags) HIP_TRY(hipMemcpyAsync(flags, c->d_flags.p, n_frames, hipMemcpyDeviceToHost, st));
-  if (centres) HIP_TRY(hipMemcpyAsync(centres, d_centres, sizeof(uint32_t) * (size_t)n_frames, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return MT_OK;
+  // d_flags: [flags n_frames | pad to 256 | centres n_frames x 4]; the flags' room stands with or without them
+  Staged sg(c, c->d_flags, true, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int o_fl = sg.out(flags, n_frames, true), o_cen = sg.out(centres, sizeof(uint32_t) * (size_t)n_frames);
+  MT_TRY(sg.upload());
+  MT_TRY(launch_scan_on(c, sg.d_mv(), r_end, sg.d_off(), sg.d_sd(), n_frames, sg.at<uint8_t>(o_fl), sg.st, MT_MV_BYTES, 0, r_begin,
+                        nullptr, 0, sg.at<uint32_t>(o_cen), 0));
+  return sg.download();
 }
 }  // namespace
 
@@ -1173,21 +1110,12 @@ int mtgpu_merge_timestamps_device(mtgpu_ctx *c, const double *d_ts, uint64_t n, 
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t wsb = merge_ts_ws_bytes(c, n) + 64;               // + the parameter block
-  void *scratch = nullptr;
-  int slot = -1;
-  {
-    const int rc0 = scratch_acquire(c, wsb, st, &slot, &scratch);
-    if (rc0 != MT_OK) return rc0;
-  }
-  unsigned char *w = static_cast<unsigned char *>(scratch);
-  int rc = MT_OK;
+  PlanWs ws(c, st, nullptr, wsb);
+  if (ws.rc != MT_OK) return ws.rc;
+  unsigned char *w = static_cast<unsigned char *>(ws.p);
   hipError_t e = mtgpu::launch_store_params(*mp, reinterpret_cast<mt_merge_params *>(w), st);   // by value: captured now
-  if (e != hipSuccess) rc = hip_fail(e, "merge params launch");
-  if (rc == MT_OK)
-    rc = merge_ts_on(c, d_ts, n, reinterpret_cast<const mt_merge_params *>(w), job_semantics, w + 64, d_seg, seg_cap,
-                     d_res, st);
-  scratch_release(c, slot, st);
-  return rc;
+  if (e != hipSuccess) return hip_fail(e, "merge params launch");
+  return merge_ts_on(c, d_ts, n, reinterpret_cast<const mt_merge_params *>(w), job_semantics, w + 64, d_seg, seg_cap, d_res, st);
 }
 
 int mtgpu_merge_segments(mtgpu_ctx *c, const double *ts, uint64_t n, const mt_merge_params *mp,
@@ -1252,13 +1180,10 @@ int motion_scores_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, uint64_
   L.sys_scores = sys_scores < 0 ? result_memory_is_sys(d_scores) : sys_scores;
   L.sys_terms = d_terms ? (sys_terms < 0 ? result_memory_is_sys(d_terms) : sys_terms) : 0;
   L.stream = st;
-  void *scratch = nullptr;
-  int slot = -1;
-  const int rc0 = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-  if (rc0 != MT_OK) return rc0;
-  L.plan_ws = scratch;
+  PlanWs ws(c, st, nullptr, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
   const hipError_t e = mtgpu::launch_motion_scores(L);
-  scratch_release(c, slot, st);
   if (e != hipSuccess) return hip_fail(e, "motion scores launch");
   return MT_OK;
 }
@@ -1378,10 +1303,7 @@ static_assert(MT_SWEEP_MAX_THRESHOLDS == mtgpu::kSweepMaxThr && MT_SWEEP_MAX_VEC
 // fit next to a mask buffer of min(R, 8) + 2 rows (next to three rows if not even one tile fits that way), the passes
 // balanced, and whatever room is left goes to the mask buffer.  *chunk_rows: centre rows per phase-2 chunk.
 int sweep_plan(const mt_scan_params &p, int lds_max, uint32_t n_thr, uint32_t n_vec, mtgpu_sweep_plan *out, int *chunk_rows) {
-  const int y_lo = p.vertical_margin;
-  int y_hi = p.grid_h - p.vertical_margin;
-  if (y_hi < y_lo) y_hi = y_lo;
-  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const int R = analysed_rows(p);
   const long long tile = (long long)mtgpu::sweep_tile_words(p.grid_w, R) * 4;
   const long long mask_row = (long long)((p.grid_w + 63) / 64) * 8 * (long long)n_vec;
   const long long fixed = (long long)mtgpu::kSweepMaxThr * mtgpu::kSweepMaxVec * 4;
@@ -1420,16 +1342,9 @@ int sweep_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records,
              uint32_t n_vec, uint32_t *d_centres, hipStream_t st, int centres_sys) {
   mtgpu_sweep_plan sp;
   int chunk_rows = 0;
-  int rc = sweep_plan(c->params, c->lds_max, n_thr, n_vec, &sp, &chunk_rows);
-  if (rc != MT_OK) return rc;
+  MT_TRY(sweep_plan(c->params, c->lds_max, n_thr, n_vec, &sp, &chunk_rows));
   mtgpu::SweepLaunch L;
-  L.mv = static_cast<const unsigned char *>(d_rec);
-  L.n_records = n_records;
-  L.rebase = rebase;
-  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
-  L.has_sd = d_sd;
-  L.n_frames = n_frames;
-  L.rec_bytes = rec_bytes;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, sp.lds_bytes, st);
   L.centres = d_centres;
   L.n_thr_all = (int)n_thr;
   L.thr_per_pass = sp.thresholds_per_pass;
@@ -1443,47 +1358,18 @@ int sweep_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records,
   }
   for (uint32_t i = n_thr; i < (uint32_t)mtgpu::kSweepMaxThr; ++i) { L.thr_sorted[i] = ~0ull; L.thr_index[i] = 0u; }
   mtgpu::SweepK &k = L.k;
-  std::memset(&k, 0, sizeof k);
+  fill_grid(k, c->k);
   for (uint32_t v = 0; v < (uint32_t)mtgpu::kSweepMaxVec; ++v)
     k.vec[v] = v < n_vec ? (unsigned int)(uint8_t)vectors[v] : 0xffffffffu;     // :186, config.hpp:75 — uint8
   k.n_vec = (int)n_vec;
-  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
-  const int R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
-  k.tile_words = (int)mtgpu::sweep_tile_words(k.gw, R);
+  k.tile_words = (int)mtgpu::sweep_tile_words(k.gw, analysed_rows(c->params));
   k.chunk_rows = chunk_rows;
   k.mask_rows = chunk_rows + 2;
   k.sys = centres_sys < 0 ? result_memory_is_sys(d_centres) : centres_sys;
-  L.lds_bytes = sp.lds_bytes;
-  L.lds_max = c->lds_max;
-  L.device = c->device;
-  L.stream = st;
-  L.ev_planned = nullptr;
-  void *scratch = nullptr;
-  int slot = -1;
-  rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-  if (rc != MT_OK) return rc;
-  L.plan_ws = scratch;
-  hipError_t e = hipSuccess;
-  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
-    mtgpu_ctx::Profile &pf = c->prof;
-    std::lock_guard<std::mutex> lock(pf.mu);
-    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
-    if (e == hipSuccess && pf.created) {
-      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
-      e = hipEventRecord(t[0], st);
-      L.ev_planned = t[1];
-      if (e == hipSuccess) e = mtgpu::launch_sweep_scan(L);
-      if (e == hipSuccess) e = hipEventRecord(t[2], st);
-      if (e == hipSuccess) ++pf.count;
-    } else if (e == hipSuccess) {
-      e = mtgpu::launch_sweep_scan(L);
-    }
-  } else {
-    e = mtgpu::launch_sweep_scan(L);
-  }
-  scratch_release(c, slot, st);
-  if (e != hipSuccess) return hip_fail(e, "sweep scan launch");
-  return MT_OK;
+  PlanWs ws(c, st, nullptr, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_sweep_scan, "sweep scan launch");
 }
 
 }  // namespace
@@ -1493,12 +1379,11 @@ extern "C" {
 int mtgpu_scan_sweep_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, uint32_t n_thresholds, uint32_t n_vectors,
                              mtgpu_sweep_plan *out) {
   if (!out) return fail(MT_ERR_INVALID, "out is NULL");
-  int rc = validate_params(p);
-  if (rc != MT_OK) return rc;
+  MT_TRY(validate_params(p));
   if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
-  if ((rc = sweep_counts_ok(n_thresholds, n_vectors)) != MT_OK) return rc;
+  MT_TRY(sweep_counts_ok(n_thresholds, n_vectors));
   mtgpu_sweep_plan sp;
-  if ((rc = sweep_plan(*p, lds_bytes_per_workgroup, n_thresholds, n_vectors, &sp, nullptr)) != MT_OK) return rc;
+  MT_TRY(sweep_plan(*p, lds_bytes_per_workgroup, n_thresholds, n_vectors, &sp, nullptr));
   *out = sp;
   return MT_OK;
 }
@@ -1506,26 +1391,19 @@ int mtgpu_scan_sweep_preview(const mt_scan_params *p, int lds_bytes_per_workgrou
 int mtgpu_scan_sweep_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
                             const uint8_t *d_has_sd, uint32_t n_frames, const double *thresholds, uint32_t n_thresholds,
                             const int32_t *vectors, uint32_t n_vectors, uint32_t *d_centres, void *stream) {
-  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
-    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
-  const int rc = sweep_counts_ok(n_thresholds, n_vectors);
-  if (rc != MT_OK) return rc;
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");      // the sweep, older than the rule below, asks for the context first
+  MT_TRY(check_rec_bytes(rec_bytes));
+  MT_TRY(sweep_counts_ok(n_thresholds, n_vectors));
   if (!thresholds) return fail(MT_ERR_INVALID, "thresholds is NULL");
   if (!vectors) return fail(MT_ERR_INVALID, "vectors is NULL");
   if (n_frames == 0) return MT_OK;
   if (!d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
   if (!d_centres) return fail(MT_ERR_INVALID, "d_centres is NULL");
   if (n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
-  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)d_rec & 7u) != 0)
-    return fail(MT_ERR_INVALID, "d_rec: compact records must be 8-byte aligned");
-  if (((uintptr_t)d_rec & 3u) != 0) return fail(MT_ERR_INVALID, "d_rec must be 4-byte aligned");
-  if (((uintptr_t)d_centres & 3u) != 0) return fail(MT_ERR_INVALID, "d_centres must be 4-byte aligned");
+  MT_TRY(check_rec("d_", rec_bytes, d_rec));
+  MT_TRY(check_aligned("d_", {{"centres", d_centres, 4}}));
   HIP_TRY(hipSetDevice(c->device));
-  if (c->check_offsets) {
-    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
-    if (rc2 != MT_OK) return rc2;
-  }
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
   return sweep_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, thresholds, n_thresholds, vectors,
                   n_vectors, d_centres, static_cast<hipStream_t>(stream), -1);
 }
@@ -1533,44 +1411,25 @@ int mtgpu_scan_sweep_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint
 int mtgpu_scan_frames_sweep(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
                             const double *thresholds, uint32_t n_thresholds, const int32_t *vectors, uint32_t n_vectors,
                             uint32_t *centres) {
-  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  int rc = sweep_counts_ok(n_thresholds, n_vectors);
-  if (rc != MT_OK) return rc;
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");      // context first, as the device form
+  MT_TRY(sweep_counts_ok(n_thresholds, n_vectors));
   if (!thresholds) return fail(MT_ERR_INVALID, "thresholds is NULL");
   if (!vectors) return fail(MT_ERR_INVALID, "vectors is NULL");
   if (n_frames == 0) return MT_OK;
   if (!frame_off || !centres) return fail(MT_ERR_INVALID, "frame_off/centres is NULL");
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
-  const uint64_t r_begin = frame_off[0], r_end = frame_off[n_frames];
-  const uint64_t n_records = r_end - r_begin;
-  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
   {
     mtgpu_sweep_plan sp;                                   // a grid without a sweep form: before anything is staged
-    if ((rc = sweep_plan(c->params, c->lds_max, n_thresholds, n_vectors, &sp, nullptr)) != MT_OK) return rc;
+    MT_TRY(sweep_plan(c->params, c->lds_max, n_thresholds, n_vectors, &sp, nullptr));
   }
-
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t out_bytes = sizeof(uint32_t) * (size_t)n_thresholds * (size_t)n_vectors * (size_t)n_frames;
-  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
-  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
-  if ((rc = c->d_flags.reserve(out_bytes)) != MT_OK) return rc;
-  if (has_sd && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
-  hipStream_t st = c->stream;
-  DrainOnExit drain{st};
-  if (n_records)
-    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
-  if (has_sd) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
-  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
-  rc = sweep_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
-                has_sd ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames, thresholds, n_thresholds, vectors,
-                n_vectors, static_cast<uint32_t *>(c->d_flags.p), st, 0);
-  if (rc != MT_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(centres, c->d_flags.p, out_bytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return MT_OK;
+  Staged sg(c, c->d_flags, true, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int o_cen = sg.out(centres, sizeof(uint32_t) * (size_t)n_thresholds * (size_t)n_vectors * (size_t)n_frames);
+  MT_TRY(sg.upload());
+  MT_TRY(sweep_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, thresholds, n_thresholds, vectors,
+                  n_vectors, sg.at<uint32_t>(o_cen), sg.st, 0));
+  return sg.download();
 }
 
 }  // extern "C"
@@ -1585,10 +1444,7 @@ namespace {
 // workgroups are preferred over wider ones that do not (1080p: 16-bit fields, 61 KB, two per CU; 32-bit fields
 // would take 90 KB and leave one).  Without room for 16-bit fields there are none and every frame flushes (4K).
 int activity_plan(const mt_scan_params &p, int lds_max, mtgpu_activity_plan *out) {
-  const int y_lo = p.vertical_margin;
-  int y_hi = p.grid_h - p.vertical_margin;
-  if (y_hi < y_lo) y_hi = y_lo;
-  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const int R = analysed_rows(p);
   const long long none = (long long)mtgpu::act_lds_bytes(p.grid_w, R, 0);
   const long long b16 = (long long)mtgpu::act_lds_bytes(p.grid_w, R, 16), b32 = (long long)mtgpu::act_lds_bytes(p.grid_w, R, 32);
   if (none > (long long)lds_max)
@@ -1606,39 +1462,20 @@ int activity_plan(const mt_scan_params &p, int lds_max, mtgpu_activity_plan *out
   return MT_OK;
 }
 
-// Is p memory of the context's device (the flush uses global atomics)?
-bool on_ctx_device(const mtgpu_ctx *c, const void *p) {
-  hipPointerAttribute_t at;
-  std::memset(&at, 0, sizeof at);
-  const hipError_t qe = hipPointerGetAttributes(&at, p);
-  if (qe != hipSuccess) { (void)hipGetLastError(); return false; }
-  return at.type == hipMemoryTypeDevice && at.device == c->device;
-}
-
 // The map of a device-resident batch on `st`.  The arguments have been validated.
 int activity_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
                 const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, uint32_t min_centres,
                 uint32_t run_frames, uint32_t *d_active, uint32_t *d_centre, uint32_t *d_frames, hipStream_t st) {
   mtgpu_activity_plan ap;
-  int rc = activity_plan(c->params, c->lds_max, &ap);
-  if (rc != MT_OK) return rc;
+  MT_TRY(activity_plan(c->params, c->lds_max, &ap));
   mtgpu::ActLaunch L;
-  L.mv = static_cast<const unsigned char *>(d_rec);
-  L.n_records = n_records;
-  L.rebase = rebase;
-  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
-  L.has_sd = d_sd;
-  L.n_frames = n_frames;
-  L.rec_bytes = rec_bytes;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, ap.lds_bytes, st);
   L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
   L.n_streams = n_streams;
   L.active = d_active; L.centre = d_centre; L.frames = d_frames;
   mtgpu::ActK &k = L.k;
-  std::memset(&k, 0, sizeof k);
-  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.min_centres = min_centres;
-  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
-  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
-  k.tile_words = (int)mtgpu::act_tile_words(k.gw, k.R);
+  fill_tile(k, c->k, mtgpu::act_tile_words);
+  k.min_centres = min_centres;
   k.gwp = mtgpu::act_gwp(k.gw);
   k.max_run = ap.max_run;
   {
@@ -1651,43 +1488,15 @@ int activity_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_recor
     k.run = (int)run;
   }
   L.acc_bits = ap.acc_bits;
-  L.lds_bytes = ap.lds_bytes;
-  L.lds_max = c->lds_max;
-  L.device = c->device;
-  L.stream = st;
-  L.ev_planned = nullptr;
-  L.plan_ws = nullptr;
-  hipError_t e = hipSuccess;
   if (n_frames == 0 || n_streams == 0) {                       // only the clear
-    e = mtgpu::launch_activity_map(L);
+    const hipError_t e = mtgpu::launch_activity_map(L);
     if (e != hipSuccess) return hip_fail(e, "activity map launch");
     return MT_OK;
   }
-  void *scratch = nullptr;
-  int slot = -1;
-  rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-  if (rc != MT_OK) return rc;
-  L.plan_ws = scratch;
-  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
-    mtgpu_ctx::Profile &pf = c->prof;
-    std::lock_guard<std::mutex> lock(pf.mu);
-    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
-    if (e == hipSuccess && pf.created) {
-      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
-      e = hipEventRecord(t[0], st);
-      L.ev_planned = t[1];
-      if (e == hipSuccess) e = mtgpu::launch_activity_map(L);
-      if (e == hipSuccess) e = hipEventRecord(t[2], st);
-      if (e == hipSuccess) ++pf.count;
-    } else if (e == hipSuccess) {
-      e = mtgpu::launch_activity_map(L);
-    }
-  } else {
-    e = mtgpu::launch_activity_map(L);
-  }
-  scratch_release(c, slot, st);
-  if (e != hipSuccess) return hip_fail(e, "activity map launch");
-  return MT_OK;
+  PlanWs ws(c, st, nullptr, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_activity_map, "activity map launch");
 }
 
 }  // namespace
@@ -1695,49 +1504,27 @@ int activity_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_recor
 extern "C" {
 
 int mtgpu_activity_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_activity_plan *out) {
-  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
-  int rc = validate_params(p);
-  if (rc != MT_OK) return rc;
-  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
-  mtgpu_activity_plan ap;
-  if ((rc = activity_plan(*p, lds_bytes_per_workgroup, &ap)) != MT_OK) return rc;
-  *out = ap;
-  return MT_OK;
+  return preview(p, lds_bytes_per_workgroup, out, activity_plan);
 }
 
 int mtgpu_activity_map_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
                               const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
                               uint32_t min_centres, uint32_t run_frames, uint32_t *d_active, uint32_t *d_centre,
                               uint32_t *d_frames, void *stream) {
-  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
-    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
-  if (!d_active && !d_centre && !d_frames) return fail(MT_ERR_INVALID, "d_active, d_centre and d_frames are all NULL");
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");      // context first, as the sweep
+  MT_TRY(check_rec_bytes(rec_bytes));
+  MT_TRY(check_any_output("d_", {{"active", d_active}, {"centre", d_centre}, {"frames", d_frames}}));
   if (n_frames > 0 && !d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
   if (n_frames > 0 && n_streams > 0 && !d_stream_off) return fail(MT_ERR_INVALID, "d_stream_off is NULL");
-  if (((uintptr_t)d_frame_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_frame_off must be 8-byte aligned");
-  if (((uintptr_t)d_stream_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_stream_off must be 8-byte aligned");
+  MT_TRY(check_aligned("d_", {{"frame_off", d_frame_off, 8}, {"stream_off", d_stream_off, 8}}));
   if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
-  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)d_rec & 7u) != 0)
-    return fail(MT_ERR_INVALID, "d_rec: compact records must be 8-byte aligned");
-  if (((uintptr_t)d_rec & 3u) != 0) return fail(MT_ERR_INVALID, "d_rec must be 4-byte aligned");
-  if (((uintptr_t)d_active & 3u) != 0) return fail(MT_ERR_INVALID, "d_active must be 4-byte aligned");
-  if (((uintptr_t)d_centre & 3u) != 0) return fail(MT_ERR_INVALID, "d_centre must be 4-byte aligned");
-  if (((uintptr_t)d_frames & 3u) != 0) return fail(MT_ERR_INVALID, "d_frames must be 4-byte aligned");
-  {
-    mtgpu_activity_plan ap;                                  // a grid without a form: before any HIP call
-    const int rc = activity_plan(c->params, c->lds_max, &ap);
-    if (rc != MT_OK) return rc;
-  }
+  MT_TRY(check_rec("d_", rec_bytes, d_rec));
+  MT_TRY(check_aligned("d_", {{"active", d_active, 4}, {"centre", d_centre, 4}, {"frames", d_frames, 4}}));
+  MT_TRY(plan_ok(c, activity_plan));                         // a grid without a form: before any HIP call
   if (n_streams == 0) return MT_OK;                          // no stream owns an output element
   HIP_TRY(hipSetDevice(c->device));
-  if (d_active && !on_ctx_device(c, d_active)) return fail(MT_ERR_INVALID, "d_active is not memory of device %d (global atomics)", c->device);
-  if (d_centre && !on_ctx_device(c, d_centre)) return fail(MT_ERR_INVALID, "d_centre is not memory of device %d (global atomics)", c->device);
-  if (d_frames && !on_ctx_device(c, d_frames)) return fail(MT_ERR_INVALID, "d_frames is not memory of device %d (global atomics)", c->device);
-  if (c->check_offsets && n_frames > 0) {
-    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
-    if (rc2 != MT_OK) return rc2;
-  }
+  MT_TRY(check_on_device(c, {{"d_active", d_active}, {"d_centre", d_centre}, {"d_frames", d_frames}}, " (global atomics)"));
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
   return activity_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, min_centres,
                      run_frames, d_active, d_centre, d_frames, static_cast<hipStream_t>(stream));
 }
@@ -1745,56 +1532,26 @@ int mtgpu_activity_map_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, ui
 int mtgpu_activity_map(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
                        const uint64_t *stream_off, uint32_t n_streams, uint32_t min_centres, uint32_t *active, uint32_t *centre,
                        uint32_t *frames) {
-  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  if (!active && !centre && !frames) return fail(MT_ERR_INVALID, "active, centre and frames are all NULL");
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");      // context first, as the sweep
+  MT_TRY(check_any_output("", {{"active", active}, {"centre", centre}, {"frames", frames}}));
   if (!stream_off) return fail(MT_ERR_INVALID, "stream_off is NULL");
   if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
-  for (uint32_t s = 0; s < n_streams; ++s)
-    if (stream_off[s + 1] < stream_off[s]) return fail(MT_ERR_INVALID, "stream_off not monotonic at stream %u", s);
-  if (stream_off[n_streams] != (uint64_t)n_frames)
-    return fail(MT_ERR_INVALID, "stream_off[%u] is %llu, not n_frames %u", n_streams, (unsigned long long)stream_off[n_streams], n_frames);
-  const uint64_t r_begin = n_frames ? frame_off[0] : 0, r_end = n_frames ? frame_off[n_frames] : 0;
-  const uint64_t n_records = r_end - r_begin;
-  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
-  int rc;
-  {
-    mtgpu_activity_plan ap;                                  // a grid without a form: before anything is staged
-    if ((rc = activity_plan(c->params, c->lds_max, &ap)) != MT_OK) return rc;
-  }
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  MT_TRY(check_stream_off(stream_off, n_streams, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
+  MT_TRY(plan_ok(c, activity_plan));                         // a grid without a form: before anything is staged
   if (n_streams == 0) return MT_OK;
 
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
+  // the room of `frames` stands whether it is asked for or not
   const size_t plane = sizeof(uint32_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.gw;
-  const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
-  const size_t o_soff = 0, o_act = o_soff + up(sizeof(uint64_t) * ((size_t)n_streams + 1)), o_cen = o_act + (active ? up(plane) : 0),
-               o_fr = o_cen + (centre ? up(plane) : 0), total = o_fr + up(sizeof(uint32_t) * (size_t)n_streams);
-  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
-  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
-  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
-  if (has_sd && n_frames && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
-  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
-  hipStream_t st = c->stream;
-  DrainOnExit drain{st};
-  if (n_records)
-    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
-  if (n_frames) HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
-  if (has_sd && n_frames) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d + o_soff, stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1), hipMemcpyHostToDevice, st));
-  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
-  rc = activity_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
-                   (has_sd && n_frames) ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames,
-                   reinterpret_cast<const uint64_t *>(d + o_soff), n_streams, min_centres, 0,
-                   active ? reinterpret_cast<uint32_t *>(d + o_act) : nullptr, centre ? reinterpret_cast<uint32_t *>(d + o_cen) : nullptr,
-                   frames ? reinterpret_cast<uint32_t *>(d + o_fr) : nullptr, st);
-  if (rc != MT_OK) return rc;
-  if (active) HIP_TRY(hipMemcpyAsync(active, d + o_act, plane, hipMemcpyDeviceToHost, st));
-  if (centre) HIP_TRY(hipMemcpyAsync(centre, d + o_cen, plane, hipMemcpyDeviceToHost, st));
-  if (frames) HIP_TRY(hipMemcpyAsync(frames, d + o_fr, sizeof(uint32_t) * (size_t)n_streams, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return MT_OK;
+  Staged sg(c, c->d_misc, false, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int i_soff = sg.in(stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1));
+  const int o_act = sg.out(active, plane), o_cen = sg.out(centre, plane), o_fr = sg.out(frames, sizeof(uint32_t) * (size_t)n_streams, true);
+  MT_TRY(sg.upload());
+  MT_TRY(activity_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff),
+                     n_streams, min_centres, 0, sg.at<uint32_t>(o_act), sg.at<uint32_t>(o_cen), sg.at<uint32_t>(o_fr), sg.st));
+  return sg.download();
 }
 
 }  // extern "C"
@@ -1806,10 +1563,7 @@ namespace {
 
 // One form: the tile, the staged keep rows and two mask planes.  It fits or the grid is unsupported.
 int zones_plan(const mt_scan_params &p, int lds_max, mtgpu_zones_plan *out) {
-  const int y_lo = p.vertical_margin;
-  int y_hi = p.grid_h - p.vertical_margin;
-  if (y_hi < y_lo) y_hi = y_lo;
-  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const int R = analysed_rows(p);
   const long long need = (long long)mtgpu::zone_lds_bytes(p.grid_w, R);
   if (need > (long long)lds_max)
     return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows, the keep rows and two mask planes "
@@ -1831,64 +1585,24 @@ int zones_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records,
              uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_centres_all, hipStream_t st, void *own_plan_ws = nullptr,
              int outputs_in_host_memory = 0) {
   mtgpu_zones_plan zp;
-  int rc = zones_plan(c->params, c->lds_max, &zp);
-  if (rc != MT_OK) return rc;
+  MT_TRY(zones_plan(c->params, c->lds_max, &zp));
   mtgpu::ZoneLaunch L;
-  L.mv = static_cast<const unsigned char *>(d_rec);
-  L.n_records = n_records;
-  L.rebase = rebase;
-  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
-  L.has_sd = d_sd;
-  L.n_frames = n_frames;
-  L.rec_bytes = rec_bytes;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, zp.lds_bytes, st);
   L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
   L.n_streams = n_streams;
   L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
   L.flags = d_flags; L.centres = d_centres; L.centres_all = d_centres_all;
-  mtgpu::ZoneK &k = L.k;
-  std::memset(&k, 0, sizeof k);
-  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.clust_need = c->k.clust_need;
-  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
-  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
-  k.tile_words = (int)mtgpu::zone_tile_words(k.gw, k.R);
-  L.lds_bytes = zp.lds_bytes;
-  L.lds_max = c->lds_max;
-  L.device = c->device;
-  L.stream = st;
-  L.ev_planned = nullptr;
-  void *scratch = nullptr;
-  int slot = -1;
+  fill_tile(L.k, c->k, mtgpu::zone_tile_words);
+  L.k.clust_need = c->k.clust_need;
   if (own_plan_ws) {
     L.pipe = 1;
     L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
     L.sys_centres = (d_centres && outputs_in_host_memory) ? 1 : 0;
-    L.plan_ws = own_plan_ws;
-  } else {
-    rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-    if (rc != MT_OK) return rc;
-    L.plan_ws = scratch;
   }
-  hipError_t e = hipSuccess;
-  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
-    mtgpu_ctx::Profile &pf = c->prof;
-    std::lock_guard<std::mutex> lock(pf.mu);
-    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
-    if (e == hipSuccess && pf.created) {
-      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
-      e = hipEventRecord(t[0], st);
-      L.ev_planned = t[1];
-      if (e == hipSuccess) e = mtgpu::launch_zone_scan(L);
-      if (e == hipSuccess) e = hipEventRecord(t[2], st);
-      if (e == hipSuccess) ++pf.count;
-    } else if (e == hipSuccess) {
-      e = mtgpu::launch_zone_scan(L);
-    }
-  } else {
-    e = mtgpu::launch_zone_scan(L);
-  }
-  if (slot >= 0) scratch_release(c, slot, st);
-  if (e != hipSuccess) return hip_fail(e, "zone scan launch");
-  return MT_OK;
+  PlanWs ws(c, st, own_plan_ws, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_zone_scan, "zone scan launch");
 }
 
 }  // namespace
@@ -1896,8 +1610,7 @@ int zones_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records,
 namespace mtgpu {
 int ctx_zones_keep_words(const mtgpu_ctx *c, uint64_t *words) {
   mtgpu_zones_plan zp;
-  const int rc = zones_plan(c->params, c->lds_max, &zp);
-  if (rc != MT_OK) return rc;
+  MT_TRY(zones_plan(c->params, c->lds_max, &zp));
   *words = (uint64_t)zp.keep_words_per_stream;
   return MT_OK;
 }
@@ -1906,8 +1619,7 @@ int ctx_launch_zones(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const 
                      int outputs_in_host_memory, void *plan_ws, size_t plan_ws_bytes) {
   if (n_frames == 0) return MT_OK;
   if (!d_keep) return fail(MT_ERR_INVALID, "masked pipe scan without a keep plane");
-  if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
-    return fail(MT_ERR_INVALID, "masked pipe scan: the batch's work-list block is missing, misaligned or too small");
+  MT_TRY(check_pipe_ws("masked", plan_ws, plan_ws_bytes, n_frames));
   return zones_on(c, d_rec, rec_bytes, n_records, 0, d_off, d_sd, n_frames, nullptr, 1, d_keep, d_flags, d_centres, nullptr, st,
                   plan_ws, outputs_in_host_memory ? 1 : 0);
 }
@@ -1916,53 +1628,30 @@ int ctx_launch_zones(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const 
 extern "C" {
 
 int mtgpu_zones_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_zones_plan *out) {
-  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
-  int rc = validate_params(p);
-  if (rc != MT_OK) return rc;
-  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
-  mtgpu_zones_plan zp;
-  if ((rc = zones_plan(*p, lds_bytes_per_workgroup, &zp)) != MT_OK) return rc;
-  *out = zp;
-  return MT_OK;
+  return preview(p, lds_bytes_per_workgroup, out, zones_plan);
 }
 
 int mtgpu_scan_zones_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
                             const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
                             const uint64_t *d_keep, uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_centres_all, void *stream) {
   // what the arguments alone decide comes first: these answers need neither a context nor a device
-  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
-    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
-  if (!d_flags && !d_centres && !d_centres_all) return fail(MT_ERR_INVALID, "d_flags, d_centres and d_centres_all are all NULL");
+  MT_TRY(check_rec_bytes(rec_bytes));
+  MT_TRY(check_any_output("d_", {{"flags", d_flags}, {"centres", d_centres}, {"centres_all", d_centres_all}}));
   if (n_frames > 0 && !d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
+  // the stream table and the keep planes are REQUIRED here, and only a batch with frames is asked for them
   if (n_frames > 0 && n_streams == 0) return fail(MT_ERR_INVALID, "n_streams is 0 with n_frames > 0");
   if (n_frames > 0 && !d_stream_off) return fail(MT_ERR_INVALID, "d_stream_off is NULL");
   if (n_frames > 0 && !d_keep) return fail(MT_ERR_INVALID, "d_keep is NULL");
-  if (((uintptr_t)d_frame_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_frame_off must be 8-byte aligned");
-  if (((uintptr_t)d_stream_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_stream_off must be 8-byte aligned");
-  if (((uintptr_t)d_keep & 7u) != 0) return fail(MT_ERR_INVALID, "d_keep must be 8-byte aligned");
+  MT_TRY(check_aligned("d_", {{"frame_off", d_frame_off, 8}, {"stream_off", d_stream_off, 8}, {"keep", d_keep, 8}}));
   if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
-  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)d_rec & 7u) != 0)
-    return fail(MT_ERR_INVALID, "d_rec: compact records must be 8-byte aligned");
-  if (((uintptr_t)d_rec & 3u) != 0) return fail(MT_ERR_INVALID, "d_rec must be 4-byte aligned");
-  if (((uintptr_t)d_centres & 3u) != 0) return fail(MT_ERR_INVALID, "d_centres must be 4-byte aligned");
-  if (((uintptr_t)d_centres_all & 3u) != 0) return fail(MT_ERR_INVALID, "d_centres_all must be 4-byte aligned");
+  MT_TRY(check_rec("d_", rec_bytes, d_rec));
+  MT_TRY(check_aligned("d_", {{"centres", d_centres, 4}, {"centres_all", d_centres_all, 4}}));
   if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  {
-    mtgpu_zones_plan zp;                                     // a grid without a form: before any HIP call
-    const int rc = zones_plan(c->params, c->lds_max, &zp);
-    if (rc != MT_OK) return rc;
-  }
+  MT_TRY(plan_ok(c, zones_plan));                            // a grid without a form: before any HIP call
   if (n_frames == 0) return MT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  if (!on_ctx_device(c, d_keep)) return fail(MT_ERR_INVALID, "d_keep is not memory of device %d", c->device);
-  if (d_flags && !on_ctx_device(c, d_flags)) return fail(MT_ERR_INVALID, "d_flags is not memory of device %d", c->device);
-  if (d_centres && !on_ctx_device(c, d_centres)) return fail(MT_ERR_INVALID, "d_centres is not memory of device %d", c->device);
-  if (d_centres_all && !on_ctx_device(c, d_centres_all))
-    return fail(MT_ERR_INVALID, "d_centres_all is not memory of device %d", c->device);
-  if (c->check_offsets) {
-    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
-    if (rc2 != MT_OK) return rc2;
-  }
+  MT_TRY(check_on_device(c, {{"d_keep", d_keep}, {"d_flags", d_flags}, {"d_centres", d_centres}, {"d_centres_all", d_centres_all}}));
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
   return zones_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_keep, d_flags,
                   d_centres, d_centres_all, static_cast<hipStream_t>(stream));
 }
@@ -1971,61 +1660,29 @@ int mtgpu_scan_frames_zones(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame
                             const uint64_t *stream_off, uint32_t n_streams, const uint64_t *keep, uint8_t *flags,
                             uint32_t *centres, uint32_t *centres_all) {
   // what the arguments alone decide comes first: these answers need neither a context nor a device
-  if (!flags && !centres && !centres_all) return fail(MT_ERR_INVALID, "flags, centres and centres_all are all NULL");
+  MT_TRY(check_any_output("", {{"flags", flags}, {"centres", centres}, {"centres_all", centres_all}}));
+  // the host form reads stream_off[n_streams] whatever n_frames is: it asks for the table ahead of frame_off
   if (!stream_off) return fail(MT_ERR_INVALID, "stream_off is NULL");
   if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
   if (n_frames > 0 && n_streams == 0) return fail(MT_ERR_INVALID, "n_streams is 0 with n_frames > 0");
   if (n_frames > 0 && !keep) return fail(MT_ERR_INVALID, "keep is NULL");
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
-  for (uint32_t s = 0; s < n_streams; ++s)
-    if (stream_off[s + 1] < stream_off[s]) return fail(MT_ERR_INVALID, "stream_off not monotonic at stream %u", s);
-  if (stream_off[n_streams] != (uint64_t)n_frames)
-    return fail(MT_ERR_INVALID, "stream_off[%u] is %llu, not n_frames %u", n_streams, (unsigned long long)stream_off[n_streams], n_frames);
-  const uint64_t r_begin = n_frames ? frame_off[0] : 0, r_end = n_frames ? frame_off[n_frames] : 0;
-  const uint64_t n_records = r_end - r_begin;
-  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  MT_TRY(check_stream_off(stream_off, n_streams, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
   if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  int rc;
-  {
-    mtgpu_zones_plan zp;                                     // a grid without a form: before anything is staged
-    if ((rc = zones_plan(c->params, c->lds_max, &zp)) != MT_OK) return rc;
-  }
+  MT_TRY(plan_ok(c, zones_plan));                            // a grid without a form: before anything is staged
   if (n_frames == 0) return MT_OK;
 
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t keep_bytes = sizeof(uint64_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.W;
-  const size_t soff_bytes = sizeof(uint64_t) * ((size_t)n_streams + 1);
-  const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
-  const size_t o_soff = 0, o_keep = o_soff + up(soff_bytes), o_fl = o_keep + up(keep_bytes), o_cen = o_fl + (flags ? up(n_frames) : 0),
-               o_all = o_cen + (centres ? up(sizeof(uint32_t) * (size_t)n_frames) : 0),
-               total = o_all + (centres_all ? up(sizeof(uint32_t) * (size_t)n_frames) : 0);
-  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
-  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
-  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
-  if (has_sd && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
-  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
-  hipStream_t st = c->stream;
-  DrainOnExit drain{st};
-  if (n_records)
-    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
-  if (has_sd) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d + o_soff, stream_off, soff_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d + o_keep, keep, keep_bytes, hipMemcpyHostToDevice, st));
-  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
-  rc = zones_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
-                has_sd ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames, reinterpret_cast<const uint64_t *>(d + o_soff),
-                n_streams, reinterpret_cast<const uint64_t *>(d + o_keep), flags ? d + o_fl : nullptr,
-                centres ? reinterpret_cast<uint32_t *>(d + o_cen) : nullptr,
-                centres_all ? reinterpret_cast<uint32_t *>(d + o_all) : nullptr, st);
-  if (rc != MT_OK) return rc;
-  if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_fl, n_frames, hipMemcpyDeviceToHost, st));
-  if (centres) HIP_TRY(hipMemcpyAsync(centres, d + o_cen, sizeof(uint32_t) * (size_t)n_frames, hipMemcpyDeviceToHost, st));
-  if (centres_all) HIP_TRY(hipMemcpyAsync(centres_all, d + o_all, sizeof(uint32_t) * (size_t)n_frames, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return MT_OK;
+  const size_t words = sizeof(uint32_t) * (size_t)n_frames;
+  Staged sg(c, c->d_misc, false, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int i_soff = sg.in(stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1));
+  const int i_keep = sg.in(keep, sizeof(uint64_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.W);
+  const int o_fl = sg.out(flags, n_frames), o_cen = sg.out(centres, words), o_all = sg.out(centres_all, words);
+  MT_TRY(sg.upload());
+  MT_TRY(zones_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff), n_streams,
+                  sg.at<const uint64_t>(i_keep), sg.at<uint8_t>(o_fl), sg.at<uint32_t>(o_cen), sg.at<uint32_t>(o_all), sg.st));
+  return sg.download();
 }
 
 }  // extern "C"
@@ -2039,10 +1696,7 @@ static_assert(sizeof(mt_blob_box) == sizeof(mtgpu::BlobBox) && sizeof(mt_blob_bo
 
 // One form: the tile (the labels later), the staged keep rows (the centre plane later) and one mask plane.
 int blobs_plan(const mt_scan_params &p, int lds_max, mtgpu_blobs_plan *out) {
-  const int y_lo = p.vertical_margin;
-  int y_hi = p.grid_h - p.vertical_margin;
-  if (y_hi < y_lo) y_hi = y_lo;
-  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const int R = analysed_rows(p);
   const long long need = (long long)mtgpu::blob_lds_bytes(p.grid_w, R);
   if (need > (long long)lds_max)
     return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows, the keep rows and one mask plane "
@@ -2065,83 +1719,40 @@ int blobs_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records,
              int32_t min_blob_cells, uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_blobs, uint32_t *d_largest,
              mt_blob_box *d_box, hipStream_t st, void *own_plan_ws = nullptr, int outputs_in_host_memory = 0) {
   mtgpu_blobs_plan bp;
-  int rc = blobs_plan(c->params, c->lds_max, &bp);
-  if (rc != MT_OK) return rc;
+  MT_TRY(blobs_plan(c->params, c->lds_max, &bp));
   mtgpu::BlobLaunch L;
-  L.mv = static_cast<const unsigned char *>(d_rec);
-  L.n_records = n_records;
-  L.rebase = rebase;
-  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
-  L.has_sd = d_sd;
-  L.n_frames = n_frames;
-  L.rec_bytes = rec_bytes;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, bp.lds_bytes, st);
   L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
   L.n_streams = n_streams;
   L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
   L.flags = d_flags; L.centres = d_centres; L.blobs = d_blobs; L.largest = d_largest;
   L.box = reinterpret_cast<mtgpu::BlobBox *>(d_box);
-  mtgpu::BlobK &k = L.k;
-  std::memset(&k, 0, sizeof k);
-  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.clust_need = c->k.clust_need;
-  k.blob_need = min_blob_cells < 1 ? 1u : (unsigned int)min_blob_cells;
-  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
-  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
-  k.tile_words = (int)mtgpu::blob_tile_words(k.gw, k.R);
-  L.lds_bytes = bp.lds_bytes;
-  L.lds_max = c->lds_max;
-  L.device = c->device;
-  L.stream = st;
-  L.ev_planned = nullptr;
-  void *scratch = nullptr;
-  int slot = -1;
+  fill_tile(L.k, c->k, mtgpu::blob_tile_words);
+  L.k.clust_need = c->k.clust_need;
+  L.k.blob_need = min_blob_cells < 1 ? 1u : (unsigned int)min_blob_cells;
   if (own_plan_ws) {
     L.pipe = 1;
     L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
     L.sys_centres = ((d_centres || d_largest) && outputs_in_host_memory) ? 1 : 0;
-    L.plan_ws = own_plan_ws;
-  } else {
-    rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-    if (rc != MT_OK) return rc;
-    L.plan_ws = scratch;
   }
-  hipError_t e = hipSuccess;
-  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
-    mtgpu_ctx::Profile &pf = c->prof;
-    std::lock_guard<std::mutex> lock(pf.mu);
-    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
-    if (e == hipSuccess && pf.created) {
-      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
-      e = hipEventRecord(t[0], st);
-      L.ev_planned = t[1];
-      if (e == hipSuccess) e = mtgpu::launch_blob_scan(L);
-      if (e == hipSuccess) e = hipEventRecord(t[2], st);
-      if (e == hipSuccess) ++pf.count;
-    } else if (e == hipSuccess) {
-      e = mtgpu::launch_blob_scan(L);
-    }
-  } else {
-    e = mtgpu::launch_blob_scan(L);
-  }
-  if (slot >= 0) scratch_release(c, slot, st);
-  if (e != hipSuccess) return hip_fail(e, "blob scan launch");
-  return MT_OK;
+  PlanWs ws(c, st, own_plan_ws, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_blob_scan, "blob scan launch");
 }
 
 }  // namespace
 
 namespace mtgpu {
-int ctx_blobs_supported(const mtgpu_ctx *c) {
-  mtgpu_blobs_plan bp;
-  return blobs_plan(c->params, c->lds_max, &bp);
-}
+int ctx_blobs_supported(const mtgpu_ctx *c) { return plan_ok(c, blobs_plan); }
 int ctx_launch_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
                      uint32_t n_frames, const uint64_t *d_keep, int32_t min_blob_cells, int report_largest, uint8_t *d_flags,
                      uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
                      size_t plan_ws_bytes, mt_blob_box *d_box) {
   if (n_frames == 0) return MT_OK;
   if (min_blob_cells < 1) return fail(MT_ERR_INVALID, "blob pipe scan with min_blob_cells %d", (int)min_blob_cells);
-  if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
-    return fail(MT_ERR_INVALID, "blob pipe scan: the batch's work-list block is missing, misaligned or too small");
+  MT_TRY(check_pipe_ws("blob", plan_ws, plan_ws_bytes, n_frames));
+  // the boxed kernel stores a box as ONE 64-bit word: 8-byte aligned here, against 2 in mtgpu_scan_blobs_device
   if (((uintptr_t)d_box & 7u) != 0u) return fail(MT_ERR_INVALID, "blob pipe scan: the batch's box array must be 8-byte aligned");
   return blobs_on(c, d_rec, rec_bytes, n_records, 0, d_off, d_sd, n_frames, nullptr, 0, d_keep, min_blob_cells, d_flags,
                   report_largest ? nullptr : d_count, nullptr, report_largest ? d_count : nullptr, d_box, st, plan_ws,
@@ -2152,14 +1763,7 @@ int ctx_launch_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const 
 extern "C" {
 
 int mtgpu_blobs_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_blobs_plan *out) {
-  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
-  int rc = validate_params(p);
-  if (rc != MT_OK) return rc;
-  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
-  mtgpu_blobs_plan bp;
-  if ((rc = blobs_plan(*p, lds_bytes_per_workgroup, &bp)) != MT_OK) return rc;
-  *out = bp;
-  return MT_OK;
+  return preview(p, lds_bytes_per_workgroup, out, blobs_plan);
 }
 
 int mtgpu_scan_blobs_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
@@ -2167,44 +1771,22 @@ int mtgpu_scan_blobs_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint
                             const uint64_t *d_keep, int32_t min_blob_cells, uint8_t *d_flags, uint32_t *d_centres,
                             uint32_t *d_blobs, uint32_t *d_largest, mt_blob_box *d_box, void *stream) {
   // what the arguments alone decide comes first: these answers need neither a context nor a device
-  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
-    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
-  if (!d_flags && !d_centres && !d_blobs && !d_largest && !d_box)
-    return fail(MT_ERR_INVALID, "d_flags, d_centres, d_blobs, d_largest and d_box are all NULL");
+  MT_TRY(check_rec_bytes(rec_bytes));
+  MT_TRY(check_any_output("d_", {{"flags", d_flags}, {"centres", d_centres}, {"blobs", d_blobs}, {"largest", d_largest}, {"box", d_box}}));
   if (n_frames > 0 && !d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
-  if (d_keep && !d_stream_off) return fail(MT_ERR_INVALID, "d_stream_off is NULL with d_keep given");
-  if (d_keep && n_streams == 0) return fail(MT_ERR_INVALID, "n_streams is 0 with d_keep given");
-  if (!d_keep && d_stream_off) return fail(MT_ERR_INVALID, "d_keep is NULL with d_stream_off given");
-  if (!d_keep && n_streams != 0) return fail(MT_ERR_INVALID, "d_keep is NULL with n_streams %u", n_streams);
-  if (((uintptr_t)d_frame_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_frame_off must be 8-byte aligned");
-  if (((uintptr_t)d_stream_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_stream_off must be 8-byte aligned");
-  if (((uintptr_t)d_keep & 7u) != 0) return fail(MT_ERR_INVALID, "d_keep must be 8-byte aligned");
+  MT_TRY(check_stream_table("d_", d_stream_off, n_streams, d_keep));
+  MT_TRY(check_aligned("d_", {{"frame_off", d_frame_off, 8}, {"stream_off", d_stream_off, 8}, {"keep", d_keep, 8}}));
   if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
-  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)d_rec & 7u) != 0)
-    return fail(MT_ERR_INVALID, "d_rec: compact records must be 8-byte aligned");
-  if (((uintptr_t)d_rec & 3u) != 0) return fail(MT_ERR_INVALID, "d_rec must be 4-byte aligned");
-  if (((uintptr_t)d_centres & 3u) != 0) return fail(MT_ERR_INVALID, "d_centres must be 4-byte aligned");
-  if (((uintptr_t)d_blobs & 3u) != 0) return fail(MT_ERR_INVALID, "d_blobs must be 4-byte aligned");
-  if (((uintptr_t)d_largest & 3u) != 0) return fail(MT_ERR_INVALID, "d_largest must be 4-byte aligned");
-  if (((uintptr_t)d_box & 1u) != 0) return fail(MT_ERR_INVALID, "d_box must be 2-byte aligned");
+  MT_TRY(check_rec("d_", rec_bytes, d_rec));
+  // (four 16-bit stores per box here: 2-byte aligned, against 8 in the pipe doorway)
+  MT_TRY(check_aligned("d_", {{"centres", d_centres, 4}, {"blobs", d_blobs, 4}, {"largest", d_largest, 4}, {"box", d_box, 2}}));
   if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  {
-    mtgpu_blobs_plan bp;                                     // a grid without a form: before any HIP call
-    const int rc = blobs_plan(c->params, c->lds_max, &bp);
-    if (rc != MT_OK) return rc;
-  }
+  MT_TRY(plan_ok(c, blobs_plan));                            // a grid without a form: before any HIP call
   if (n_frames == 0) return MT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  if (d_keep && !on_ctx_device(c, d_keep)) return fail(MT_ERR_INVALID, "d_keep is not memory of device %d", c->device);
-  if (d_flags && !on_ctx_device(c, d_flags)) return fail(MT_ERR_INVALID, "d_flags is not memory of device %d", c->device);
-  if (d_centres && !on_ctx_device(c, d_centres)) return fail(MT_ERR_INVALID, "d_centres is not memory of device %d", c->device);
-  if (d_blobs && !on_ctx_device(c, d_blobs)) return fail(MT_ERR_INVALID, "d_blobs is not memory of device %d", c->device);
-  if (d_largest && !on_ctx_device(c, d_largest)) return fail(MT_ERR_INVALID, "d_largest is not memory of device %d", c->device);
-  if (d_box && !on_ctx_device(c, d_box)) return fail(MT_ERR_INVALID, "d_box is not memory of device %d", c->device);
-  if (c->check_offsets) {
-    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
-    if (rc2 != MT_OK) return rc2;
-  }
+  MT_TRY(check_on_device(c, {{"d_keep", d_keep}, {"d_flags", d_flags}, {"d_centres", d_centres}, {"d_blobs", d_blobs},
+                             {"d_largest", d_largest}, {"d_box", d_box}}));
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
   return blobs_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_keep,
                   min_blob_cells, d_flags, d_centres, d_blobs, d_largest, d_box, static_cast<hipStream_t>(stream));
 }
@@ -2213,71 +1795,29 @@ int mtgpu_scan_frames_blobs(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame
                             const uint64_t *stream_off, uint32_t n_streams, const uint64_t *keep, int32_t min_blob_cells,
                             uint8_t *flags, uint32_t *centres, uint32_t *blobs, uint32_t *largest, mt_blob_box *box) {
   // what the arguments alone decide comes first: these answers need neither a context nor a device
-  if (!flags && !centres && !blobs && !largest && !box)
-    return fail(MT_ERR_INVALID, "flags, centres, blobs, largest and box are all NULL");
+  MT_TRY(check_any_output("", {{"flags", flags}, {"centres", centres}, {"blobs", blobs}, {"largest", largest}, {"box", box}}));
   if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
-  if (keep && !stream_off) return fail(MT_ERR_INVALID, "stream_off is NULL with keep given");
-  if (keep && n_streams == 0) return fail(MT_ERR_INVALID, "n_streams is 0 with keep given");
-  if (!keep && stream_off) return fail(MT_ERR_INVALID, "keep is NULL with stream_off given");
-  if (!keep && n_streams != 0) return fail(MT_ERR_INVALID, "keep is NULL with n_streams %u", n_streams);
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
-  if (keep) {
-    for (uint32_t s = 0; s < n_streams; ++s)
-      if (stream_off[s + 1] < stream_off[s]) return fail(MT_ERR_INVALID, "stream_off not monotonic at stream %u", s);
-    if (stream_off[n_streams] != (uint64_t)n_frames)
-      return fail(MT_ERR_INVALID, "stream_off[%u] is %llu, not n_frames %u", n_streams, (unsigned long long)stream_off[n_streams], n_frames);
-  }
-  const uint64_t r_begin = n_frames ? frame_off[0] : 0, r_end = n_frames ? frame_off[n_frames] : 0;
-  const uint64_t n_records = r_end - r_begin;
-  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
+  MT_TRY(check_stream_table("", stream_off, n_streams, keep));
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  if (keep) MT_TRY(check_stream_off(stream_off, n_streams, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
   if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  int rc;
-  {
-    mtgpu_blobs_plan bp;                                     // a grid without a form: before anything is staged
-    if ((rc = blobs_plan(c->params, c->lds_max, &bp)) != MT_OK) return rc;
-  }
+  MT_TRY(plan_ok(c, blobs_plan));                            // a grid without a form: before anything is staged
   if (n_frames == 0) return MT_OK;
 
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t keep_bytes = keep ? sizeof(uint64_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.W : 0;
-  const size_t soff_bytes = keep ? sizeof(uint64_t) * ((size_t)n_streams + 1) : 0;
+  // (without a mask stream_off and keep are null and n_streams is 0: no room, null device pointers)
   const size_t words = sizeof(uint32_t) * (size_t)n_frames;
-  const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
-  const size_t o_soff = 0, o_keep = o_soff + up(soff_bytes), o_fl = o_keep + up(keep_bytes), o_cen = o_fl + (flags ? up(n_frames) : 0),
-               o_bl = o_cen + (centres ? up(words) : 0), o_lg = o_bl + (blobs ? up(words) : 0), o_box = o_lg + (largest ? up(words) : 0),
-               total = o_box + (box ? up(sizeof(mt_blob_box) * (size_t)n_frames) : 0);
-  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
-  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
-  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
-  if (has_sd && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
-  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
-  hipStream_t st = c->stream;
-  DrainOnExit drain{st};
-  if (n_records)
-    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
-  if (has_sd) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
-  if (keep) {
-    HIP_TRY(hipMemcpyAsync(d + o_soff, stream_off, soff_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_keep, keep, keep_bytes, hipMemcpyHostToDevice, st));
-  }
-  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
-  rc = blobs_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
-                has_sd ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames,
-                keep ? reinterpret_cast<const uint64_t *>(d + o_soff) : nullptr, keep ? n_streams : 0u,
-                keep ? reinterpret_cast<const uint64_t *>(d + o_keep) : nullptr, min_blob_cells, flags ? d + o_fl : nullptr,
-                centres ? reinterpret_cast<uint32_t *>(d + o_cen) : nullptr, blobs ? reinterpret_cast<uint32_t *>(d + o_bl) : nullptr,
-                largest ? reinterpret_cast<uint32_t *>(d + o_lg) : nullptr, box ? reinterpret_cast<mt_blob_box *>(d + o_box) : nullptr, st);
-  if (rc != MT_OK) return rc;
-  if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_fl, n_frames, hipMemcpyDeviceToHost, st));
-  if (centres) HIP_TRY(hipMemcpyAsync(centres, d + o_cen, words, hipMemcpyDeviceToHost, st));
-  if (blobs) HIP_TRY(hipMemcpyAsync(blobs, d + o_bl, words, hipMemcpyDeviceToHost, st));
-  if (largest) HIP_TRY(hipMemcpyAsync(largest, d + o_lg, words, hipMemcpyDeviceToHost, st));
-  if (box) HIP_TRY(hipMemcpyAsync(box, d + o_box, sizeof(mt_blob_box) * (size_t)n_frames, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return MT_OK;
+  Staged sg(c, c->d_misc, false, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int i_soff = sg.in(stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1));
+  const int i_keep = sg.in(keep, sizeof(uint64_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.W);
+  const int o_fl = sg.out(flags, n_frames), o_cen = sg.out(centres, words), o_bl = sg.out(blobs, words), o_lg = sg.out(largest, words);
+  const int o_box = sg.out(box, sizeof(mt_blob_box) * (size_t)n_frames);
+  MT_TRY(sg.upload());
+  MT_TRY(blobs_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff), n_streams,
+                  sg.at<const uint64_t>(i_keep), min_blob_cells, sg.at<uint8_t>(o_fl), sg.at<uint32_t>(o_cen), sg.at<uint32_t>(o_bl),
+                  sg.at<uint32_t>(o_lg), sg.at<mt_blob_box>(o_box), sg.st));
+  return sg.download();
 }
 
 }  // extern "C"
@@ -2292,10 +1832,7 @@ static_assert(MTGPU_GMC_MAX_SHIFT == mtgpu::kGmcMaxShift && 2 * mtgpu::kGmcMaxSh
 
 // One form: the tile, one mask plane and the two histograms.  It fits or the grid is unsupported.
 int gmc_plan(const mt_scan_params &p, int lds_max, mtgpu_gmc_plan *out) {
-  const int y_lo = p.vertical_margin;
-  int y_hi = p.grid_h - p.vertical_margin;
-  if (y_hi < y_lo) y_hi = y_lo;
-  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const int R = analysed_rows(p);
   const long long need = (long long)mtgpu::gmc_lds_bytes(p.grid_w, R);
   if (need > (long long)lds_max)
     return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows, one mask plane and the histograms "
@@ -2325,84 +1862,39 @@ int gmc_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, u
            mt_gmc_info *d_info, hipStream_t st, void *own_plan_ws = nullptr, const uint64_t *d_keep = nullptr,
            int report_vector = 0, int outputs_in_host_memory = 0) {
   mtgpu_gmc_plan gp;
-  int rc = gmc_plan(c->params, c->lds_max, &gp);
-  if (rc != MT_OK) return rc;
+  MT_TRY(gmc_plan(c->params, c->lds_max, &gp));
   mtgpu::GmcLaunch L;
-  L.mv = static_cast<const unsigned char *>(d_rec);
-  L.n_records = n_records;
-  L.rebase = rebase;
-  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
-  L.has_sd = d_sd;
-  L.n_frames = n_frames;
-  L.rec_bytes = rec_bytes;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, gp.lds_bytes, st);
   L.flags = d_flags; L.centres = d_centres; L.info = reinterpret_cast<unsigned int *>(d_info);
-  mtgpu::GmcK &k = L.k;
-  std::memset(&k, 0, sizeof k);
-  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.clust_need = c->k.clust_need;
-  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
-  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
-  k.tile_words = (int)mtgpu::gmc_tile_words(k.gw, k.R);
-  k.max_shift = (int)max_shift;
-  k.min_share_q8 = (unsigned int)min_share_q8;
-  L.lds_bytes = gp.lds_bytes;
-  L.lds_max = c->lds_max;
-  L.device = c->device;
-  L.stream = st;
-  L.ev_planned = nullptr;
-  void *scratch = nullptr;
-  int slot = -1;
+  fill_tile(L.k, c->k, mtgpu::gmc_tile_words);
+  L.k.clust_need = c->k.clust_need;
+  L.k.max_shift = (int)max_shift;
+  L.k.min_share_q8 = (unsigned int)min_share_q8;
   if (own_plan_ws) {
     L.pipe = 1;
     L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
     L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
     L.sys_centres = (d_centres && outputs_in_host_memory) ? 1 : 0;
     L.report_vector = report_vector ? 1 : 0;
-    L.plan_ws = own_plan_ws;
-  } else {
-    rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-    if (rc != MT_OK) return rc;
-    L.plan_ws = scratch;
   }
-  hipError_t e = hipSuccess;
-  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
-    mtgpu_ctx::Profile &pf = c->prof;
-    std::lock_guard<std::mutex> lock(pf.mu);
-    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
-    if (e == hipSuccess && pf.created) {
-      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
-      e = hipEventRecord(t[0], st);
-      L.ev_planned = t[1];
-      if (e == hipSuccess) e = mtgpu::launch_gmc_scan(L);
-      if (e == hipSuccess) e = hipEventRecord(t[2], st);
-      if (e == hipSuccess) ++pf.count;
-    } else if (e == hipSuccess) {
-      e = mtgpu::launch_gmc_scan(L);
-    }
-  } else {
-    e = mtgpu::launch_gmc_scan(L);
-  }
-  if (slot >= 0) scratch_release(c, slot, st);
-  if (e != hipSuccess) return hip_fail(e, "compensated scan launch");
-  return MT_OK;
+  PlanWs ws(c, st, own_plan_ws, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_gmc_scan, "compensated scan launch");
 }
 
 }  // namespace
 
 namespace mtgpu {
-int ctx_gmc_supported(const mtgpu_ctx *c) {
-  mtgpu_gmc_plan gp;
-  return gmc_plan(c->params, c->lds_max, &gp);
-}
+int ctx_gmc_supported(const mtgpu_ctx *c) { return plan_ok(c, gmc_plan); }
 int ctx_launch_gmc(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
                    uint32_t n_frames, const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int report_vector,
                    uint8_t *d_flags, uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
                    size_t plan_ws_bytes) {
   if (n_frames == 0) return MT_OK;
-  const int rc = gmc_check_settings(max_shift, min_share_q8);
-  if (rc != MT_OK) return rc;
+  MT_TRY(gmc_check_settings(max_shift, min_share_q8));
   if (report_vector && !d_count) return fail(MT_ERR_INVALID, "compensated pipe scan: the vector report needs the batch's count array");
-  if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
-    return fail(MT_ERR_INVALID, "compensated pipe scan: the batch's work-list block is missing, misaligned or too small");
+  MT_TRY(check_pipe_ws("compensated", plan_ws, plan_ws_bytes, n_frames));
   return gmc_on(c, d_rec, rec_bytes, n_records, 0, d_off, d_sd, n_frames, max_shift, min_share_q8, d_flags, d_count, nullptr, st,
                 plan_ws, d_keep, report_vector ? 1 : 0, outputs_in_host_memory ? 1 : 0);
 }
@@ -2411,47 +1903,27 @@ int ctx_launch_gmc(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const ui
 extern "C" {
 
 int mtgpu_gmc_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_gmc_plan *out) {
-  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
-  int rc = validate_params(p);
-  if (rc != MT_OK) return rc;
-  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
-  mtgpu_gmc_plan gp;
-  if ((rc = gmc_plan(*p, lds_bytes_per_workgroup, &gp)) != MT_OK) return rc;
-  *out = gp;
-  return MT_OK;
+  return preview(p, lds_bytes_per_workgroup, out, gmc_plan);
 }
 
 int mtgpu_scan_gmc_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
                           const uint8_t *d_has_sd, uint32_t n_frames, int32_t max_shift, int32_t min_share_q8, uint8_t *d_flags,
                           uint32_t *d_centres, mt_gmc_info *d_info, void *stream) {
   // what the arguments alone decide comes first: these answers need neither a context nor a device
-  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
-    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
-  int rc = gmc_check_settings(max_shift, min_share_q8);
-  if (rc != MT_OK) return rc;
-  if (!d_flags && !d_centres && !d_info) return fail(MT_ERR_INVALID, "d_flags, d_centres and d_info are all NULL");
+  MT_TRY(check_rec_bytes(rec_bytes));
+  MT_TRY(gmc_check_settings(max_shift, min_share_q8));
+  MT_TRY(check_any_output("d_", {{"flags", d_flags}, {"centres", d_centres}, {"info", d_info}}));
   if (n_frames > 0 && !d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
-  if (((uintptr_t)d_frame_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_frame_off must be 8-byte aligned");
+  MT_TRY(check_aligned("d_", {{"frame_off", d_frame_off, 8}}));
   if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
-  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)d_rec & 7u) != 0)
-    return fail(MT_ERR_INVALID, "d_rec: compact records must be 8-byte aligned");
-  if (((uintptr_t)d_rec & 3u) != 0) return fail(MT_ERR_INVALID, "d_rec must be 4-byte aligned");
-  if (((uintptr_t)d_centres & 3u) != 0) return fail(MT_ERR_INVALID, "d_centres must be 4-byte aligned");
-  if (((uintptr_t)d_info & 3u) != 0) return fail(MT_ERR_INVALID, "d_info must be 4-byte aligned");
+  MT_TRY(check_rec("d_", rec_bytes, d_rec));
+  MT_TRY(check_aligned("d_", {{"centres", d_centres, 4}, {"info", d_info, 4}}));
   if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  {
-    mtgpu_gmc_plan gp;                                       // a grid without a form: before any HIP call
-    if ((rc = gmc_plan(c->params, c->lds_max, &gp)) != MT_OK) return rc;
-  }
+  MT_TRY(plan_ok(c, gmc_plan));                              // a grid without a form: before any HIP call
   if (n_frames == 0) return MT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  if (d_flags && !on_ctx_device(c, d_flags)) return fail(MT_ERR_INVALID, "d_flags is not memory of device %d", c->device);
-  if (d_centres && !on_ctx_device(c, d_centres)) return fail(MT_ERR_INVALID, "d_centres is not memory of device %d", c->device);
-  if (d_info && !on_ctx_device(c, d_info)) return fail(MT_ERR_INVALID, "d_info is not memory of device %d", c->device);
-  if (c->check_offsets) {
-    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
-    if (rc2 != MT_OK) return rc2;
-  }
+  MT_TRY(check_on_device(c, {{"d_flags", d_flags}, {"d_centres", d_centres}, {"d_info", d_info}}));
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
   return gmc_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, max_shift, min_share_q8, d_flags, d_centres,
                 d_info, static_cast<hipStream_t>(stream));
 }
@@ -2459,49 +1931,23 @@ int mtgpu_scan_gmc_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64
 int mtgpu_scan_frames_gmc(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
                           int32_t max_shift, int32_t min_share_q8, uint8_t *flags, uint32_t *centres, mt_gmc_info *info) {
   // what the arguments alone decide comes first: these answers need neither a context nor a device
-  int rc = gmc_check_settings(max_shift, min_share_q8);
-  if (rc != MT_OK) return rc;
-  if (!flags && !centres && !info) return fail(MT_ERR_INVALID, "flags, centres and info are all NULL");
+  MT_TRY(gmc_check_settings(max_shift, min_share_q8));
+  MT_TRY(check_any_output("", {{"flags", flags}, {"centres", centres}, {"info", info}}));
   if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
-  const uint64_t r_begin = n_frames ? frame_off[0] : 0, r_end = n_frames ? frame_off[n_frames] : 0;
-  const uint64_t n_records = r_end - r_begin;
-  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
   if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  {
-    mtgpu_gmc_plan gp;                                       // a grid without a form: before anything is staged
-    if ((rc = gmc_plan(c->params, c->lds_max, &gp)) != MT_OK) return rc;
-  }
+  MT_TRY(plan_ok(c, gmc_plan));                              // a grid without a form: before anything is staged
   if (n_frames == 0) return MT_OK;
 
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
-  const size_t words = sizeof(uint32_t) * (size_t)n_frames, info_bytes = sizeof(mt_gmc_info) * (size_t)n_frames;
-  const size_t o_fl = 0, o_cen = o_fl + (flags ? up(n_frames) : 0), o_info = o_cen + (centres ? up(words) : 0),
-               total = o_info + (info ? up(info_bytes) : 0);
-  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
-  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
-  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
-  if (has_sd && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
-  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
-  hipStream_t st = c->stream;
-  DrainOnExit drain{st};
-  if (n_records)
-    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
-  if (has_sd) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
-  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
-  rc = gmc_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
-              has_sd ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames, max_shift, min_share_q8, flags ? d + o_fl : nullptr,
-              centres ? reinterpret_cast<uint32_t *>(d + o_cen) : nullptr, info ? reinterpret_cast<mt_gmc_info *>(d + o_info) : nullptr, st);
-  if (rc != MT_OK) return rc;
-  if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_fl, n_frames, hipMemcpyDeviceToHost, st));
-  if (centres) HIP_TRY(hipMemcpyAsync(centres, d + o_cen, words, hipMemcpyDeviceToHost, st));
-  if (info) HIP_TRY(hipMemcpyAsync(info, d + o_info, info_bytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return MT_OK;
+  Staged sg(c, c->d_misc, false, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int o_fl = sg.out(flags, n_frames), o_cen = sg.out(centres, sizeof(uint32_t) * (size_t)n_frames);
+  const int o_info = sg.out(info, sizeof(mt_gmc_info) * (size_t)n_frames);
+  MT_TRY(sg.upload());
+  MT_TRY(gmc_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, max_shift, min_share_q8, sg.at<uint8_t>(o_fl),
+                sg.at<uint32_t>(o_cen), sg.at<mt_gmc_info>(o_info), sg.st));
+  return sg.download();
 }
 
 }  // extern "C"
@@ -2511,12 +1957,12 @@ int mtgpu_scan_frames_gmc(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_o
 
 namespace {
 
+static_assert(MT_PIPE_REPORT_CENTRES == mtgpu::kGmcBlobReportCentres && MT_PIPE_REPORT_LARGEST == mtgpu::kGmcBlobReportLargest &&
+              MT_PIPE_REPORT_VECTOR == mtgpu::kGmcBlobReportVector, "the kernel's report values are the ABI's");
+
 // One form: the blob scan's layout and the two histograms.  It fits or the grid is unsupported.
 int gmc_blobs_plan(const mt_scan_params &p, int lds_max, mtgpu_gmc_blobs_plan *out) {
-  const int y_lo = p.vertical_margin;
-  int y_hi = p.grid_h - p.vertical_margin;
-  if (y_hi < y_lo) y_hi = y_lo;
-  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const int R = analysed_rows(p);
   const long long need = (long long)mtgpu::gmc_blobs_lds_bytes(p.grid_w, R);
   if (need > (long long)lds_max)
     return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows, the keep rows, one mask plane and the "
@@ -2533,283 +1979,42 @@ int gmc_blobs_plan(const mt_scan_params &p, int lds_max, mtgpu_gmc_blobs_plan *o
 }
 
 // The compensated blob scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
+// own_plan_ws (include/mtgpu_pipe_gmc_blobs.h): the caller's own block for the work list (a pipe's batch) — nothing
+// comes from the context's scratch ring — and the pipe form of the launch: d_keep is one plane or null and there is no
+// stream table, d_centres is the batch's ONE count array and receives what `report` says, d_blobs, d_largest and d_info
+// are null, flags and the count are stored at system scope when `outputs_in_host_memory`.  nullptr: the ring, the
+// resident form.
 int gmc_blobs_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
                  const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, const uint64_t *d_keep,
                  int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells, uint8_t *d_flags, uint32_t *d_centres,
-                 uint32_t *d_blobs, uint32_t *d_largest, mt_blob_box *d_box, mt_gmc_info *d_info, hipStream_t st) {
+                 uint32_t *d_blobs, uint32_t *d_largest, mt_blob_box *d_box, mt_gmc_info *d_info, hipStream_t st,
+                 void *own_plan_ws = nullptr, int report = 0, int outputs_in_host_memory = 0) {
   mtgpu_gmc_blobs_plan gp;
-  int rc = gmc_blobs_plan(c->params, c->lds_max, &gp);
-  if (rc != MT_OK) return rc;
+  MT_TRY(gmc_blobs_plan(c->params, c->lds_max, &gp));
   mtgpu::GmcBlobLaunch L;
-  L.mv = static_cast<const unsigned char *>(d_rec);
-  L.n_records = n_records;
-  L.rebase = rebase;
-  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
-  L.has_sd = d_sd;
-  L.n_frames = n_frames;
-  L.rec_bytes = rec_bytes;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, gp.lds_bytes, st);
   L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
   L.n_streams = n_streams;
   L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
   L.flags = d_flags; L.centres = d_centres; L.blobs = d_blobs; L.largest = d_largest;
-  L.box = reinterpret_cast<mtgpu::BlobBox *>(d_box);
+  L.box = reinterpret_cast<mtgpu::BlobBox *>(d_box);          // (pipe form: nullptr is the form without boxes)
   L.info = reinterpret_cast<unsigned int *>(d_info);
-  mtgpu::GmcBlobK &k = L.k;
-  std::memset(&k, 0, sizeof k);
-  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.clust_need = c->k.clust_need;
-  k.blob_need = min_blob_cells < 1 ? 1u : (unsigned int)min_blob_cells;
-  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
-  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
-  k.tile_words = (int)mtgpu::blob_tile_words(k.gw, k.R);
-  k.max_shift = (int)max_shift;
-  k.min_share_q8 = (unsigned int)min_share_q8;
-  L.lds_bytes = gp.lds_bytes;
-  L.lds_max = c->lds_max;
-  L.device = c->device;
-  L.stream = st;
-  L.ev_planned = nullptr;
-  void *scratch = nullptr;
-  int slot = -1;
-  rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-  if (rc != MT_OK) return rc;
-  L.plan_ws = scratch;
-  hipError_t e = hipSuccess;
-  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
-    mtgpu_ctx::Profile &pf = c->prof;
-    std::lock_guard<std::mutex> lock(pf.mu);
-    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
-    if (e == hipSuccess && pf.created) {
-      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
-      e = hipEventRecord(t[0], st);
-      L.ev_planned = t[1];
-      if (e == hipSuccess) e = mtgpu::launch_gmc_blob_scan(L);
-      if (e == hipSuccess) e = hipEventRecord(t[2], st);
-      if (e == hipSuccess) ++pf.count;
-    } else if (e == hipSuccess) {
-      e = mtgpu::launch_gmc_blob_scan(L);
-    }
-  } else {
-    e = mtgpu::launch_gmc_blob_scan(L);
+  fill_tile(L.k, c->k, mtgpu::blob_tile_words);
+  L.k.clust_need = c->k.clust_need;
+  L.k.blob_need = min_blob_cells < 1 ? 1u : (unsigned int)min_blob_cells;
+  L.k.max_shift = (int)max_shift;
+  L.k.min_share_q8 = (unsigned int)min_share_q8;
+  if (own_plan_ws) {
+    L.pipe = 1;
+    L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
+    L.sys_count = (d_centres && outputs_in_host_memory) ? 1 : 0;
+    L.report = report;
   }
-  if (slot >= 0) scratch_release(c, slot, st);
-  if (e != hipSuccess) return hip_fail(e, "compensated blob scan launch");
-  return MT_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int mtgpu_gmc_blobs_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_gmc_blobs_plan *out) {
-  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
-  int rc = validate_params(p);
-  if (rc != MT_OK) return rc;
-  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
-  mtgpu_gmc_blobs_plan gp;
-  if ((rc = gmc_blobs_plan(*p, lds_bytes_per_workgroup, &gp)) != MT_OK) return rc;
-  *out = gp;
-  return MT_OK;
-}
-
-int mtgpu_scan_gmc_blobs_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
-                                const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
-                                const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells,
-                                uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_blobs, uint32_t *d_largest, mt_blob_box *d_box,
-                                mt_gmc_info *d_info, void *stream) {
-  // what the arguments alone decide comes first: these answers need neither a context nor a device
-  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
-    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
-  int rc = gmc_check_settings(max_shift, min_share_q8);
-  if (rc != MT_OK) return rc;
-  if (!d_flags && !d_centres && !d_blobs && !d_largest && !d_box && !d_info)
-    return fail(MT_ERR_INVALID, "d_flags, d_centres, d_blobs, d_largest, d_box and d_info are all NULL");
-  if (n_frames > 0 && !d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
-  if (d_keep && !d_stream_off) return fail(MT_ERR_INVALID, "d_stream_off is NULL with d_keep given");
-  if (d_keep && n_streams == 0) return fail(MT_ERR_INVALID, "n_streams is 0 with d_keep given");
-  if (!d_keep && d_stream_off) return fail(MT_ERR_INVALID, "d_keep is NULL with d_stream_off given");
-  if (!d_keep && n_streams != 0) return fail(MT_ERR_INVALID, "d_keep is NULL with n_streams %u", n_streams);
-  if (((uintptr_t)d_frame_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_frame_off must be 8-byte aligned");
-  if (((uintptr_t)d_stream_off & 7u) != 0) return fail(MT_ERR_INVALID, "d_stream_off must be 8-byte aligned");
-  if (((uintptr_t)d_keep & 7u) != 0) return fail(MT_ERR_INVALID, "d_keep must be 8-byte aligned");
-  if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
-  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)d_rec & 7u) != 0)
-    return fail(MT_ERR_INVALID, "d_rec: compact records must be 8-byte aligned");
-  if (((uintptr_t)d_rec & 3u) != 0) return fail(MT_ERR_INVALID, "d_rec must be 4-byte aligned");
-  if (((uintptr_t)d_centres & 3u) != 0) return fail(MT_ERR_INVALID, "d_centres must be 4-byte aligned");
-  if (((uintptr_t)d_blobs & 3u) != 0) return fail(MT_ERR_INVALID, "d_blobs must be 4-byte aligned");
-  if (((uintptr_t)d_largest & 3u) != 0) return fail(MT_ERR_INVALID, "d_largest must be 4-byte aligned");
-  if (((uintptr_t)d_box & 1u) != 0) return fail(MT_ERR_INVALID, "d_box must be 2-byte aligned");
-  if (((uintptr_t)d_info & 3u) != 0) return fail(MT_ERR_INVALID, "d_info must be 4-byte aligned");
-  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  {
-    mtgpu_gmc_blobs_plan gp;                                 // a grid without a form: before any HIP call
-    if ((rc = gmc_blobs_plan(c->params, c->lds_max, &gp)) != MT_OK) return rc;
-  }
-  if (n_frames == 0) return MT_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  if (d_keep && !on_ctx_device(c, d_keep)) return fail(MT_ERR_INVALID, "d_keep is not memory of device %d", c->device);
-  if (d_flags && !on_ctx_device(c, d_flags)) return fail(MT_ERR_INVALID, "d_flags is not memory of device %d", c->device);
-  if (d_centres && !on_ctx_device(c, d_centres)) return fail(MT_ERR_INVALID, "d_centres is not memory of device %d", c->device);
-  if (d_blobs && !on_ctx_device(c, d_blobs)) return fail(MT_ERR_INVALID, "d_blobs is not memory of device %d", c->device);
-  if (d_largest && !on_ctx_device(c, d_largest)) return fail(MT_ERR_INVALID, "d_largest is not memory of device %d", c->device);
-  if (d_box && !on_ctx_device(c, d_box)) return fail(MT_ERR_INVALID, "d_box is not memory of device %d", c->device);
-  if (d_info && !on_ctx_device(c, d_info)) return fail(MT_ERR_INVALID, "d_info is not memory of device %d", c->device);
-  if (c->check_offsets) {
-    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
-    if (rc2 != MT_OK) return rc2;
-  }
-  return gmc_blobs_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_keep,
-                      max_shift, min_share_q8, min_blob_cells, d_flags, d_centres, d_blobs, d_largest, d_box, d_info,
-                      static_cast<hipStream_t>(stream));
-}
-
-int mtgpu_scan_frames_gmc_blobs(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
-                                const uint64_t *stream_off, uint32_t n_streams, const uint64_t *keep, int32_t max_shift,
-                                int32_t min_share_q8, int32_t min_blob_cells, uint8_t *flags, uint32_t *centres, uint32_t *blobs,
-                                uint32_t *largest, mt_blob_box *box, mt_gmc_info *info) {
-  // what the arguments alone decide comes first: these answers need neither a context nor a device
-  int rc = gmc_check_settings(max_shift, min_share_q8);
-  if (rc != MT_OK) return rc;
-  if (!flags && !centres && !blobs && !largest && !box && !info)
-    return fail(MT_ERR_INVALID, "flags, centres, blobs, largest, box and info are all NULL");
-  if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
-  if (keep && !stream_off) return fail(MT_ERR_INVALID, "stream_off is NULL with keep given");
-  if (keep && n_streams == 0) return fail(MT_ERR_INVALID, "n_streams is 0 with keep given");
-  if (!keep && stream_off) return fail(MT_ERR_INVALID, "keep is NULL with stream_off given");
-  if (!keep && n_streams != 0) return fail(MT_ERR_INVALID, "keep is NULL with n_streams %u", n_streams);
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
-  if (keep) {
-    for (uint32_t s = 0; s < n_streams; ++s)
-      if (stream_off[s + 1] < stream_off[s]) return fail(MT_ERR_INVALID, "stream_off not monotonic at stream %u", s);
-    if (stream_off[n_streams] != (uint64_t)n_frames)
-      return fail(MT_ERR_INVALID, "stream_off[%u] is %llu, not n_frames %u", n_streams, (unsigned long long)stream_off[n_streams], n_frames);
-  }
-  const uint64_t r_begin = n_frames ? frame_off[0] : 0, r_end = n_frames ? frame_off[n_frames] : 0;
-  const uint64_t n_records = r_end - r_begin;
-  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
-  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  {
-    mtgpu_gmc_blobs_plan gp;                                 // a grid without a form: before anything is staged
-    if ((rc = gmc_blobs_plan(c->params, c->lds_max, &gp)) != MT_OK) return rc;
-  }
-  if (n_frames == 0) return MT_OK;
-
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t keep_bytes = keep ? sizeof(uint64_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.W : 0;
-  const size_t soff_bytes = keep ? sizeof(uint64_t) * ((size_t)n_streams + 1) : 0;
-  const size_t words = sizeof(uint32_t) * (size_t)n_frames, info_bytes = sizeof(mt_gmc_info) * (size_t)n_frames;
-  const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
-  const size_t o_soff = 0, o_keep = o_soff + up(soff_bytes), o_fl = o_keep + up(keep_bytes), o_cen = o_fl + (flags ? up(n_frames) : 0),
-               o_bl = o_cen + (centres ? up(words) : 0), o_lg = o_bl + (blobs ? up(words) : 0), o_box = o_lg + (largest ? up(words) : 0),
-               o_info = o_box + (box ? up(sizeof(mt_blob_box) * (size_t)n_frames) : 0), total = o_info + (info ? up(info_bytes) : 0);
-  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
-  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
-  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
-  if (has_sd && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
-  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
-  hipStream_t st = c->stream;
-  DrainOnExit drain{st};
-  if (n_records)
-    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
-  if (has_sd) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
-  if (keep) {
-    HIP_TRY(hipMemcpyAsync(d + o_soff, stream_off, soff_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_keep, keep, keep_bytes, hipMemcpyHostToDevice, st));
-  }
-  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
-  rc = gmc_blobs_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
-                    has_sd ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames,
-                    keep ? reinterpret_cast<const uint64_t *>(d + o_soff) : nullptr, keep ? n_streams : 0u,
-                    keep ? reinterpret_cast<const uint64_t *>(d + o_keep) : nullptr, max_shift, min_share_q8, min_blob_cells,
-                    flags ? d + o_fl : nullptr, centres ? reinterpret_cast<uint32_t *>(d + o_cen) : nullptr,
-                    blobs ? reinterpret_cast<uint32_t *>(d + o_bl) : nullptr, largest ? reinterpret_cast<uint32_t *>(d + o_lg) : nullptr,
-                    box ? reinterpret_cast<mt_blob_box *>(d + o_box) : nullptr, info ? reinterpret_cast<mt_gmc_info *>(d + o_info) : nullptr, st);
-  if (rc != MT_OK) return rc;
-  if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_fl, n_frames, hipMemcpyDeviceToHost, st));
-  if (centres) HIP_TRY(hipMemcpyAsync(centres, d + o_cen, words, hipMemcpyDeviceToHost, st));
-  if (blobs) HIP_TRY(hipMemcpyAsync(blobs, d + o_bl, words, hipMemcpyDeviceToHost, st));
-  if (largest) HIP_TRY(hipMemcpyAsync(largest, d + o_lg, words, hipMemcpyDeviceToHost, st));
-  if (box) HIP_TRY(hipMemcpyAsync(box, d + o_box, sizeof(mt_blob_box) * (size_t)n_frames, hipMemcpyDeviceToHost, st));
-  if (info) HIP_TRY(hipMemcpyAsync(info, d + o_info, info_bytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return MT_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- the compensated blob scan on the decode path
-// (include/mtgpu_pipe_gmc_blobs.h): the pipe form of the launch above, for pipe.hip
-
-namespace {
-
-static_assert(MT_PIPE_REPORT_CENTRES == mtgpu::kGmcBlobReportCentres && MT_PIPE_REPORT_LARGEST == mtgpu::kGmcBlobReportLargest &&
-              MT_PIPE_REPORT_VECTOR == mtgpu::kGmcBlobReportVector, "the kernel's report values are the ABI's");
-
-// The compensated blob scan of a pipe's staging batch on `st`.  The arguments have been validated; n_frames > 0.  The
-// work list lies in the caller's own block: nothing comes from the context's scratch ring.
-int gmc_blobs_pipe_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
-                      uint32_t n_frames, const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells,
-                      int report, uint8_t *d_flags, uint32_t *d_count, mt_blob_box *d_box, hipStream_t st, void *own_plan_ws,
-                      int outputs_in_host_memory) {
-  mtgpu_gmc_blobs_plan gp;
-  int rc = gmc_blobs_plan(c->params, c->lds_max, &gp);
-  if (rc != MT_OK) return rc;
-  mtgpu::GmcBlobLaunch L;
-  L.mv = static_cast<const unsigned char *>(d_rec);
-  L.n_records = n_records;
-  L.rebase = 0;
-  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
-  L.has_sd = d_sd;
-  L.n_frames = n_frames;
-  L.rec_bytes = rec_bytes;
-  L.stream_off = nullptr;
-  L.n_streams = 0;
-  L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
-  L.flags = d_flags; L.centres = d_count; L.blobs = nullptr; L.largest = nullptr;
-  L.box = reinterpret_cast<mtgpu::BlobBox *>(d_box);          // nullptr: the form without boxes
-  L.info = nullptr;
-  L.pipe = 1;
-  L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
-  L.sys_count = (d_count && outputs_in_host_memory) ? 1 : 0;
-  L.report = report;
-  mtgpu::GmcBlobK &k = L.k;
-  std::memset(&k, 0, sizeof k);
-  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.clust_need = c->k.clust_need;
-  k.blob_need = min_blob_cells < 1 ? 1u : (unsigned int)min_blob_cells;
-  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
-  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
-  k.tile_words = (int)mtgpu::blob_tile_words(k.gw, k.R);
-  k.max_shift = (int)max_shift;
-  k.min_share_q8 = (unsigned int)min_share_q8;
-  L.lds_bytes = gp.lds_bytes;
-  L.lds_max = c->lds_max;
-  L.device = c->device;
-  L.stream = st;
-  L.ev_planned = nullptr;
-  L.plan_ws = own_plan_ws;
-  hipError_t e = hipSuccess;
-  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
-    mtgpu_ctx::Profile &pf = c->prof;
-    std::lock_guard<std::mutex> lock(pf.mu);
-    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
-    if (e == hipSuccess && pf.created) {
-      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
-      e = hipEventRecord(t[0], st);
-      L.ev_planned = t[1];
-      if (e == hipSuccess) e = mtgpu::launch_gmc_blob_scan(L);
-      if (e == hipSuccess) e = hipEventRecord(t[2], st);
-      if (e == hipSuccess) ++pf.count;
-    } else if (e == hipSuccess) {
-      e = mtgpu::launch_gmc_blob_scan(L);
-    }
-  } else {
-    e = mtgpu::launch_gmc_blob_scan(L);
-  }
-  if (e != hipSuccess) return hip_fail(e, "compensated blob pipe scan launch");
-  return MT_OK;
+  PlanWs ws(c, st, own_plan_ws, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_gmc_blob_scan,
+                         own_plan_ws ? "compensated blob pipe scan launch" : "compensated blob scan launch");
 }
 
 }  // namespace
@@ -2820,25 +2025,92 @@ int ctx_launch_gmc_blobs(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, co
                          int report, uint8_t *d_flags, uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory,
                          void *plan_ws, size_t plan_ws_bytes, mt_blob_box *d_box) {
   if (n_frames == 0) return MT_OK;
+  // (8-byte aligned as in ctx_launch_blobs, but asked first here)
   if (((uintptr_t)d_box & 7u) != 0u)
     return fail(MT_ERR_INVALID, "compensated blob pipe scan: the batch's box array must be 8-byte aligned");
-  const int rc = gmc_check_settings(max_shift, min_share_q8);
-  if (rc != MT_OK) return rc;
+  MT_TRY(gmc_check_settings(max_shift, min_share_q8));
   if (min_blob_cells < 1) return fail(MT_ERR_INVALID, "compensated blob pipe scan: min_blob_cells is %d, want >= 1", (int)min_blob_cells);
   if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_LARGEST && report != MT_PIPE_REPORT_VECTOR)
     return fail(MT_ERR_INVALID, "compensated blob pipe scan: report is %d", report);
   if (report != MT_PIPE_REPORT_CENTRES && !d_count)
     return fail(MT_ERR_INVALID, "compensated blob pipe scan: the largest and the vector report need the batch's count array");
-  if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
-    return fail(MT_ERR_INVALID, "compensated blob pipe scan: the batch's work-list block is missing, misaligned or too small");
-  return gmc_blobs_pipe_on(c, d_rec, rec_bytes, n_records, d_off, d_sd, n_frames, d_keep, max_shift, min_share_q8, min_blob_cells,
-                           report, d_flags, d_count, d_box, st, plan_ws, outputs_in_host_memory ? 1 : 0);
+  MT_TRY(check_pipe_ws("compensated blob", plan_ws, plan_ws_bytes, n_frames));
+  return gmc_blobs_on(c, d_rec, rec_bytes, n_records, 0, d_off, d_sd, n_frames, nullptr, 0, d_keep, max_shift, min_share_q8,
+                      min_blob_cells, d_flags, d_count, nullptr, nullptr, d_box, nullptr, st, plan_ws, report,
+                      outputs_in_host_memory ? 1 : 0);
 }
-int ctx_gmc_blobs_supported(const mtgpu_ctx *c) {
-  mtgpu_gmc_blobs_plan gp;
-  return gmc_blobs_plan(c->params, c->lds_max, &gp);
-}
+int ctx_gmc_blobs_supported(const mtgpu_ctx *c) { return plan_ok(c, gmc_blobs_plan); }
 }  // namespace mtgpu
+
+extern "C" {
+
+int mtgpu_gmc_blobs_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_gmc_blobs_plan *out) {
+  return preview(p, lds_bytes_per_workgroup, out, gmc_blobs_plan);
+}
+
+int mtgpu_scan_gmc_blobs_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
+                                const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
+                                const uint64_t *d_keep, int32_t max_shift, int32_t min_share_q8, int32_t min_blob_cells,
+                                uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_blobs, uint32_t *d_largest, mt_blob_box *d_box,
+                                mt_gmc_info *d_info, void *stream) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  MT_TRY(check_rec_bytes(rec_bytes));
+  MT_TRY(gmc_check_settings(max_shift, min_share_q8));
+  MT_TRY(check_any_output("d_", {{"flags", d_flags}, {"centres", d_centres}, {"blobs", d_blobs}, {"largest", d_largest}, {"box", d_box},
+                                 {"info", d_info}}));
+  if (n_frames > 0 && !d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
+  MT_TRY(check_stream_table("d_", d_stream_off, n_streams, d_keep));
+  MT_TRY(check_aligned("d_", {{"frame_off", d_frame_off, 8}, {"stream_off", d_stream_off, 8}, {"keep", d_keep, 8}}));
+  if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
+  MT_TRY(check_rec("d_", rec_bytes, d_rec));
+  MT_TRY(check_aligned("d_", {{"centres", d_centres, 4}, {"blobs", d_blobs, 4}, {"largest", d_largest, 4}, {"box", d_box, 2},
+                              {"info", d_info, 4}}));
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  MT_TRY(plan_ok(c, gmc_blobs_plan));                        // a grid without a form: before any HIP call
+  if (n_frames == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  MT_TRY(check_on_device(c, {{"d_keep", d_keep}, {"d_flags", d_flags}, {"d_centres", d_centres}, {"d_blobs", d_blobs},
+                             {"d_largest", d_largest}, {"d_box", d_box}, {"d_info", d_info}}));
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
+  return gmc_blobs_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_keep,
+                      max_shift, min_share_q8, min_blob_cells, d_flags, d_centres, d_blobs, d_largest, d_box, d_info,
+                      static_cast<hipStream_t>(stream));
+}
+
+int mtgpu_scan_frames_gmc_blobs(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
+                                const uint64_t *stream_off, uint32_t n_streams, const uint64_t *keep, int32_t max_shift,
+                                int32_t min_share_q8, int32_t min_blob_cells, uint8_t *flags, uint32_t *centres, uint32_t *blobs,
+                                uint32_t *largest, mt_blob_box *box, mt_gmc_info *info) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  MT_TRY(gmc_check_settings(max_shift, min_share_q8));
+  MT_TRY(check_any_output("", {{"flags", flags}, {"centres", centres}, {"blobs", blobs}, {"largest", largest}, {"box", box}, {"info", info}}));
+  if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
+  MT_TRY(check_stream_table("", stream_off, n_streams, keep));
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  if (keep) MT_TRY(check_stream_off(stream_off, n_streams, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  MT_TRY(plan_ok(c, gmc_blobs_plan));                        // a grid without a form: before anything is staged
+  if (n_frames == 0) return MT_OK;
+
+  // (without a mask stream_off and keep are null and n_streams is 0: no room, null device pointers)
+  const size_t words = sizeof(uint32_t) * (size_t)n_frames;
+  Staged sg(c, c->d_misc, false, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int i_soff = sg.in(stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1));
+  const int i_keep = sg.in(keep, sizeof(uint64_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.W);
+  const int o_fl = sg.out(flags, n_frames), o_cen = sg.out(centres, words), o_bl = sg.out(blobs, words), o_lg = sg.out(largest, words);
+  const int o_box = sg.out(box, sizeof(mt_blob_box) * (size_t)n_frames), o_info = sg.out(info, sizeof(mt_gmc_info) * (size_t)n_frames);
+  MT_TRY(sg.upload());
+  MT_TRY(gmc_blobs_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff),
+                      n_streams, sg.at<const uint64_t>(i_keep), max_shift, min_share_q8, min_blob_cells, sg.at<uint8_t>(o_fl),
+                      sg.at<uint32_t>(o_cen), sg.at<uint32_t>(o_bl), sg.at<uint32_t>(o_lg), sg.at<mt_blob_box>(o_box),
+                      sg.at<mt_gmc_info>(o_info), sg.st));
+  return sg.download();
+}
+
+}  // extern "C"
+
 
 // ---------------------------------------------------------------- temporal persistence (include/mtgpu_persist.h)
 
@@ -2925,10 +2197,7 @@ int mtgpu_persist_flags_device(mtgpu_ctx *c, const uint8_t *d_flags, const uint8
   if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
   if (n_frames == 0) return MT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  if (!on_ctx_device(c, d_work)) return fail(MT_ERR_INVALID, "d_work is not memory of device %d", c->device);
-  if (d_flags_out && !on_ctx_device(c, d_flags_out)) return fail(MT_ERR_INVALID, "d_flags_out is not memory of device %d", c->device);
-  if (d_run && !on_ctx_device(c, d_run)) return fail(MT_ERR_INVALID, "d_run is not memory of device %d", c->device);
-  if (d_pos && !on_ctx_device(c, d_pos)) return fail(MT_ERR_INVALID, "d_pos is not memory of device %d", c->device);
+  MT_TRY(check_on_device(c, {{"d_work", d_work}, {"d_flags_out", d_flags_out}, {"d_run", d_run}, {"d_pos", d_pos}}));
   return persist_on(d_flags, d_has_sd, d_box, n_frames, d_stream_off, n_streams, min_run, max_dropout, reach, d_work, d_flags_out,
                     d_run, d_pos, static_cast<hipStream_t>(stream));
 }
@@ -2986,10 +2255,7 @@ static_assert(sizeof(mt_dir_rose) == 32 && alignof(mt_dir_rose) == 4, "mt_dir_ro
 
 // One form: the tile, one mask plane, the total and the eight rose words.  It fits or the grid is unsupported.
 int dir_plan(const mt_scan_params &p, int lds_max, mtgpu_dir_plan *out) {
-  const int y_lo = p.vertical_margin;
-  int y_hi = p.grid_h - p.vertical_margin;
-  if (y_hi < y_lo) y_hi = y_lo;
-  const int R = (y_hi - y_lo) < 1 ? 1 : (y_hi - y_lo);
+  const int R = analysed_rows(p);
   const long long need = (long long)mtgpu::dir_lds_bytes(p.grid_w, R);
   if (need > (long long)lds_max)
     return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows, one mask plane and the rose "
@@ -3007,10 +2273,10 @@ int dir_check_args(const char *d, const char *allow_name, int rec_bytes, const v
                    const void *stream_off, uint32_t n_streams, const void *allows, int32_t allow, const void *flags,
                    const void *centres, const void *rose) {
   if (allow < 0 || allow > 255) return fail(MT_ERR_INVALID, "allow %d outside [0,255]", (int)allow);
-  if (rec_bytes != MT_MV_BYTES && rec_bytes != MT_COMPACT_BYTES)
-    return fail(MT_ERR_INVALID, "rec_bytes must be %d (mt_mv) or %d (mt_mv_compact), not %d", MT_MV_BYTES, MT_COMPACT_BYTES, rec_bytes);
-  if (!flags && !centres && !rose) return fail(MT_ERR_INVALID, "%sflags, %scentres and %srose are all NULL", d, d, d);
+  MT_TRY(check_rec_bytes(rec_bytes));
+  MT_TRY(check_any_output(d, {{"flags", flags}, {"centres", centres}, {"rose", rose}}));
   if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "%sframe_off is NULL", d);
+  // check_stream_table's rule about the per-stream allow bytes, in this call's own words
   if (allows) {
     if (!stream_off) return fail(MT_ERR_INVALID, "%s%s is given and %sstream_off is NULL", d, allow_name, d);
     if (n_streams == 0) return fail(MT_ERR_INVALID, "%s%s is given and n_streams is 0", d, allow_name);
@@ -3018,14 +2284,9 @@ int dir_check_args(const char *d, const char *allow_name, int rec_bytes, const v
     if (stream_off) return fail(MT_ERR_INVALID, "%sstream_off is given and %s%s is NULL", d, d, allow_name);
     if (n_streams != 0) return fail(MT_ERR_INVALID, "n_streams is %u and %s%s is NULL", n_streams, d, allow_name);
   }
-  if (((uintptr_t)frame_off & 7u) != 0) return fail(MT_ERR_INVALID, "%sframe_off must be 8-byte aligned", d);
-  if (((uintptr_t)stream_off & 7u) != 0) return fail(MT_ERR_INVALID, "%sstream_off must be 8-byte aligned", d);
-  if (rec_bytes == MT_COMPACT_BYTES && ((uintptr_t)rec & 7u) != 0)
-    return fail(MT_ERR_INVALID, "%srec: compact records must be 8-byte aligned", d);
-  if (((uintptr_t)rec & 3u) != 0) return fail(MT_ERR_INVALID, "%s must be 4-byte aligned", d[0] ? "d_rec" : "mv");
-  if (((uintptr_t)centres & 3u) != 0) return fail(MT_ERR_INVALID, "%scentres must be 4-byte aligned", d);
-  if (((uintptr_t)rose & 3u) != 0) return fail(MT_ERR_INVALID, "%srose must be 4-byte aligned", d);
-  return MT_OK;
+  MT_TRY(check_aligned(d, {{"frame_off", frame_off, 8}, {"stream_off", stream_off, 8}}));
+  MT_TRY(check_rec(d, rec_bytes, rec));
+  return check_aligned(d, {{"centres", centres, 4}, {"rose", rose, 4}});
 }
 
 // The direction scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
@@ -3038,76 +2299,33 @@ int dir_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, u
            int32_t allow, uint8_t *d_flags, uint32_t *d_centres, mt_dir_rose *d_rose, hipStream_t st, void *own_plan_ws = nullptr,
            const uint64_t *d_keep = nullptr, int report_sectors = 0, int outputs_in_host_memory = 0) {
   mtgpu_dir_plan dp;
-  int rc = dir_plan(c->params, c->lds_max, &dp);
-  if (rc != MT_OK) return rc;
+  MT_TRY(dir_plan(c->params, c->lds_max, &dp));
   mtgpu::DirLaunch L;
-  L.mv = static_cast<const unsigned char *>(d_rec);
-  L.n_records = n_records;
-  L.rebase = rebase;
-  L.frame_off = reinterpret_cast<const unsigned long long *>(d_off);
-  L.has_sd = d_sd;
-  L.n_frames = n_frames;
-  L.rec_bytes = rec_bytes;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, dp.lds_bytes, st);
   L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
   L.n_streams = n_streams;
   L.allows = d_allow;
   L.allow = (unsigned int)allow;
   L.flags = d_flags; L.centres = d_centres; L.rose = reinterpret_cast<unsigned int *>(d_rose);
-  mtgpu::DirK &k = L.k;
-  std::memset(&k, 0, sizeof k);
-  k.thr = c->k.thr; k.vec_need = c->k.vec_need; k.clust_need = c->k.clust_need;
-  k.shift = c->k.shift; k.gw = c->k.gw; k.gh = c->k.gh; k.y_lo = c->k.y_lo; k.y_hi = c->k.y_hi; k.W = c->k.W;
-  k.R = (k.y_hi - k.y_lo) < 1 ? 1 : (k.y_hi - k.y_lo);
-  k.tile_words = (int)mtgpu::dir_tile_words(k.gw, k.R);
-  L.lds_bytes = dp.lds_bytes;
-  L.lds_max = c->lds_max;
-  L.device = c->device;
-  L.stream = st;
-  L.ev_planned = nullptr;
-  void *scratch = nullptr;
-  int slot = -1;
+  fill_tile(L.k, c->k, mtgpu::dir_tile_words);
+  L.k.clust_need = c->k.clust_need;
   if (own_plan_ws) {
     L.pipe = 1;
     L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
     L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
     L.sys_centres = (d_centres && outputs_in_host_memory) ? 1 : 0;
     L.report_sectors = report_sectors ? 1 : 0;
-    L.plan_ws = own_plan_ws;
-  } else {
-    rc = scratch_acquire(c, (mtgpu::plan_scratch_bytes(n_frames) + 255u) & ~(size_t)255u, st, &slot, &scratch);
-    if (rc != MT_OK) return rc;
-    L.plan_ws = scratch;
   }
-  hipError_t e = hipSuccess;
-  if (c->prof.on.load(std::memory_order_relaxed)) {            // the same event triple as a scan launch (launch_scan_on)
-    mtgpu_ctx::Profile &pf = c->prof;
-    std::lock_guard<std::mutex> lock(pf.mu);
-    if (pf.created && pf.count == mtgpu_ctx::Profile::kRing) e = pf.drain_one();
-    if (e == hipSuccess && pf.created) {
-      hipEvent_t *t = pf.ev[(pf.tail + pf.count) % mtgpu_ctx::Profile::kRing];
-      e = hipEventRecord(t[0], st);
-      L.ev_planned = t[1];
-      if (e == hipSuccess) e = mtgpu::launch_dir_scan(L);
-      if (e == hipSuccess) e = hipEventRecord(t[2], st);
-      if (e == hipSuccess) ++pf.count;
-    } else if (e == hipSuccess) {
-      e = mtgpu::launch_dir_scan(L);
-    }
-  } else {
-    e = mtgpu::launch_dir_scan(L);
-  }
-  if (slot >= 0) scratch_release(c, slot, st);
-  if (e != hipSuccess) return hip_fail(e, "direction scan launch");
-  return MT_OK;
+  PlanWs ws(c, st, own_plan_ws, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_dir_scan, "direction scan launch");
 }
 
 }  // namespace
 
 namespace mtgpu {
-int ctx_dir_supported(const mtgpu_ctx *c) {
-  mtgpu_dir_plan dp;
-  return dir_plan(c->params, c->lds_max, &dp);
-}
+int ctx_dir_supported(const mtgpu_ctx *c) { return plan_ok(c, dir_plan); }
 int ctx_launch_dir(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
                    uint32_t n_frames, const uint64_t *d_keep, int32_t allow, int report_sectors, uint8_t *d_flags,
                    uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
@@ -3115,8 +2333,7 @@ int ctx_launch_dir(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const ui
   if (n_frames == 0) return MT_OK;
   if (allow < 0 || allow > 255) return fail(MT_ERR_INVALID, "allow %d outside [0,255]", (int)allow);
   if (report_sectors && !d_count) return fail(MT_ERR_INVALID, "direction pipe scan: the sector report needs the batch's count array");
-  if (!plan_ws || ((uintptr_t)plan_ws & 255u) != 0u || plan_ws_bytes < plan_scratch_bytes(n_frames))
-    return fail(MT_ERR_INVALID, "direction pipe scan: the batch's work-list block is missing, misaligned or too small");
+  MT_TRY(check_pipe_ws("direction", plan_ws, plan_ws_bytes, n_frames));
   return dir_on(c, d_rec, rec_bytes, n_records, 0, d_off, d_sd, n_frames, nullptr, 0, nullptr, allow, d_flags, d_count, nullptr, st,
                 plan_ws, d_keep, report_sectors ? 1 : 0, outputs_in_host_memory ? 1 : 0);
 }
@@ -3125,14 +2342,7 @@ int ctx_launch_dir(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const ui
 extern "C" {
 
 int mtgpu_dir_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_dir_plan *out) {
-  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
-  int rc = validate_params(p);
-  if (rc != MT_OK) return rc;
-  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
-  mtgpu_dir_plan dp;
-  if ((rc = dir_plan(*p, lds_bytes_per_workgroup, &dp)) != MT_OK) return rc;
-  *out = dp;
-  return MT_OK;
+  return preview(p, lds_bytes_per_workgroup, out, dir_plan);
 }
 
 int mtgpu_scan_dir_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
@@ -3140,24 +2350,16 @@ int mtgpu_scan_dir_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64
                           const uint8_t *d_allow, int32_t allow, uint8_t *d_flags, uint32_t *d_centres, mt_dir_rose *d_rose,
                           void *stream) {
   // what the arguments alone decide comes first: these answers need neither a context nor a device
-  int rc = dir_check_args("d_", "allow", rec_bytes, d_rec, d_frame_off, n_frames, d_stream_off, n_streams, d_allow, allow, d_flags,
-                          d_centres, d_rose);
-  if (rc != MT_OK) return rc;
+  MT_TRY(dir_check_args("d_", "allow", rec_bytes, d_rec, d_frame_off, n_frames, d_stream_off, n_streams, d_allow, allow, d_flags,
+                        d_centres, d_rose));
+  // (behind the alignment rungs here; the other device forms ask before them)
   if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
   if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  {
-    mtgpu_dir_plan dp;                                       // a grid without a form: before any HIP call
-    if ((rc = dir_plan(c->params, c->lds_max, &dp)) != MT_OK) return rc;
-  }
+  MT_TRY(plan_ok(c, dir_plan));                              // a grid without a form: before any HIP call
   if (n_frames == 0) return MT_OK;
   HIP_TRY(hipSetDevice(c->device));
-  if (d_flags && !on_ctx_device(c, d_flags)) return fail(MT_ERR_INVALID, "d_flags is not memory of device %d", c->device);
-  if (d_centres && !on_ctx_device(c, d_centres)) return fail(MT_ERR_INVALID, "d_centres is not memory of device %d", c->device);
-  if (d_rose && !on_ctx_device(c, d_rose)) return fail(MT_ERR_INVALID, "d_rose is not memory of device %d", c->device);
-  if (c->check_offsets) {
-    const int rc2 = check_offsets_on(c, d_frame_off, n_frames, static_cast<hipStream_t>(stream));
-    if (rc2 != MT_OK) return rc2;
-  }
+  MT_TRY(check_on_device(c, {{"d_flags", d_flags}, {"d_centres", d_centres}, {"d_rose", d_rose}}));
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
   return dir_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_allow, allow, d_flags,
                 d_centres, d_rose, static_cast<hipStream_t>(stream));
 }
@@ -3166,60 +2368,25 @@ int mtgpu_scan_frames_dir(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_o
                           const uint64_t *stream_off, uint32_t n_streams, const uint8_t *allows, int32_t allow, uint8_t *flags,
                           uint32_t *centres, mt_dir_rose *rose) {
   // what the arguments alone decide comes first: these answers need neither a context nor a device
-  int rc = dir_check_args("", "allows", MT_MV_BYTES, mv, frame_off, n_frames, stream_off, n_streams, allows, allow, flags, centres, rose);
-  if (rc != MT_OK) return rc;
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (frame_off[f + 1] < frame_off[f]) return fail(MT_ERR_INVALID, "frame_off not monotonic at frame %u", f);
-  if (allows) {
-    for (uint32_t s = 0; s < n_streams; ++s)
-      if (stream_off[s + 1] < stream_off[s]) return fail(MT_ERR_INVALID, "stream_off not monotonic at stream %u", s);
-    if (stream_off[n_streams] != (uint64_t)n_frames)
-      return fail(MT_ERR_INVALID, "stream_off[%u] is %llu, not n_frames %u", n_streams, (unsigned long long)stream_off[n_streams], n_frames);
-  }
-  const uint64_t r_begin = n_frames ? frame_off[0] : 0, r_end = n_frames ? frame_off[n_frames] : 0;
-  const uint64_t n_records = r_end - r_begin;
-  if (n_records > 0 && !mv) return fail(MT_ERR_INVALID, "mv is NULL with records present");
+  // (the one host form with alignment rungs: it shares its checker with the device form)
+  MT_TRY(dir_check_args("", "allows", MT_MV_BYTES, mv, frame_off, n_frames, stream_off, n_streams, allows, allow, flags, centres, rose));
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  if (allows) MT_TRY(check_stream_off(stream_off, n_streams, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
   if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
-  {
-    mtgpu_dir_plan dp;                                       // a grid without a form: before anything is staged
-    if ((rc = dir_plan(c->params, c->lds_max, &dp)) != MT_OK) return rc;
-  }
+  MT_TRY(plan_ok(c, dir_plan));                              // a grid without a form: before anything is staged
   if (n_frames == 0) return MT_OK;
 
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t soff_bytes = allows ? sizeof(uint64_t) * ((size_t)n_streams + 1) : 0, allow_bytes = allows ? (size_t)n_streams : 0;
-  const size_t words = sizeof(uint32_t) * (size_t)n_frames, rose_bytes = sizeof(mt_dir_rose) * (size_t)n_frames;
-  const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
-  const size_t o_soff = 0, o_allow = o_soff + up(soff_bytes), o_fl = o_allow + up(allow_bytes), o_cen = o_fl + (flags ? up(n_frames) : 0),
-               o_rose = o_cen + (centres ? up(words) : 0), total = o_rose + (rose ? up(rose_bytes) : 0);
-  if ((rc = c->d_mv.reserve((size_t)n_records * MT_MV_BYTES + 16)) != MT_OK) return rc;
-  if ((rc = c->d_off.reserve(sizeof(uint64_t) * ((size_t)n_frames + 1))) != MT_OK) return rc;
-  if ((rc = c->d_misc.reserve(total)) != MT_OK) return rc;
-  if (has_sd && (rc = c->d_sd.reserve(n_frames)) != MT_OK) return rc;
-  unsigned char *d = static_cast<unsigned char *>(c->d_misc.p);
-  hipStream_t st = c->stream;
-  DrainOnExit drain{st};
-  if (n_records)
-    HIP_TRY(hipMemcpyAsync(c->d_mv.p, mv + r_begin, (size_t)n_records * MT_MV_BYTES, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(c->d_off.p, frame_off, sizeof(uint64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st));
-  if (has_sd) HIP_TRY(hipMemcpyAsync(c->d_sd.p, has_sd, n_frames, hipMemcpyHostToDevice, st));
-  if (allows) {
-    HIP_TRY(hipMemcpyAsync(d + o_soff, stream_off, soff_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d + o_allow, allows, allow_bytes, hipMemcpyHostToDevice, st));
-  }
-  // records of frame f live at d_mv + (frame_off[f] - r_begin) * 40: the work list is built with rebased offsets
-  rc = dir_on(c, c->d_mv.p, MT_MV_BYTES, r_end, r_begin, static_cast<const uint64_t *>(c->d_off.p),
-              has_sd ? static_cast<const uint8_t *>(c->d_sd.p) : nullptr, n_frames,
-              allows ? reinterpret_cast<const uint64_t *>(d + o_soff) : nullptr, n_streams, allows ? d + o_allow : nullptr, allow,
-              flags ? d + o_fl : nullptr, centres ? reinterpret_cast<uint32_t *>(d + o_cen) : nullptr,
-              rose ? reinterpret_cast<mt_dir_rose *>(d + o_rose) : nullptr, st);
-  if (rc != MT_OK) return rc;
-  if (flags) HIP_TRY(hipMemcpyAsync(flags, d + o_fl, n_frames, hipMemcpyDeviceToHost, st));
-  if (centres) HIP_TRY(hipMemcpyAsync(centres, d + o_cen, words, hipMemcpyDeviceToHost, st));
-  if (rose) HIP_TRY(hipMemcpyAsync(rose, d + o_rose, rose_bytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return MT_OK;
+  // (without per-stream bytes stream_off and allows are null: no room, null device pointers)
+  Staged sg(c, c->d_misc, false, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int i_soff = sg.in(stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1)), i_allow = sg.in(allows, n_streams);
+  const int o_fl = sg.out(flags, n_frames), o_cen = sg.out(centres, sizeof(uint32_t) * (size_t)n_frames);
+  const int o_rose = sg.out(rose, sizeof(mt_dir_rose) * (size_t)n_frames);
+  MT_TRY(sg.upload());
+  MT_TRY(dir_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff), n_streams,
+                sg.at<const uint8_t>(i_allow), allow, sg.at<uint8_t>(o_fl), sg.at<uint32_t>(o_cen), sg.at<mt_dir_rose>(o_rose), sg.st));
+  return sg.download();
 }
 
 }  // extern "C"

@@ -68,29 +68,37 @@ inline size_t plan_scratch_bytes(unsigned int n_frames) {
 
 constexpr int kStageBytes = 64 * 32;     // LDS behind the tile for the parked entries of a grouped workgroup (group <= 64)
 
-struct ScanLaunch {
+// What every launch over a record batch is given, whatever its kernel: the batch, the LDS it asks for, its scratch, its
+// stream.  The launch structs of the scan and of its derived kernels (SweepLaunch, ActLaunch, ZoneLaunch, BlobLaunch,
+// GmcLaunch, GmcBlobLaunch, DirLaunch) derive from it and add their own inputs, outputs and kernel parameter block.
+// Host side only: no kernel takes a launch struct as an argument.
+struct BatchLaunch {
   const unsigned char *mv;
-  unsigned long long n_records;    // frame_off entries are clamped to this (in the caller's units, before `rebase`)
-  const unsigned long long *frame_off;
-  const unsigned char *has_sd;
+  unsigned long long n_records;         // frame_off entries are clamped to this (in the caller's units, before `rebase`)
+  unsigned long long rebase;            // records [frame_off[f], frame_off[f + 1]) live at mv + (frame_off[f] - rebase) * rec_bytes
+                                        // (a host-pointer call copies only the window its offsets span); <= n_records
+  const unsigned long long *frame_off;  // n_frames + 1
+  const unsigned char *has_sd;          // n_frames or null
   unsigned int n_frames;
+  int rec_bytes;                        // 40 = AVMotionVector records, 8 = compact {src_x,src_y,dst_x,dst_y}
+  int lds_bytes;
+  int lds_max;                          // device limit of dynamic LDS per workgroup (set once per kernel instantiation)
+  int device;
+  void *plan_ws;                        // plan_scratch_bytes(n_frames), 32-byte aligned: work list + planning counts
+  hipStream_t stream;
+  hipEvent_t ev_planned;                // profiling (mtgpu_profile_enable): recorded between the planning kernels and the
+                                        // kernel that walks the list (a sweep: its first pass); else nullptr
+};
+
+struct ScanLaunch : BatchLaunch {
   unsigned char *flags;         // n_frames bytes; may be null when `centres` is not
   unsigned int *centres;        // n_frames words or null: every frame's centre count (0 without side data)
   unsigned int *spill_q;        // n_records words (one slot per record), only when k.bands > 1
   unsigned int *slice_ws;       // n_frames * slices * cnt_words words, only when k.slices > 1
   unsigned int *tickets;        // n_frames words (zeroed by launch_scan), only when k.slices > 1
-  void *plan_ws;                // plan_scratch_bytes(n_frames), 32-byte aligned: work list + planning counts
-  unsigned long long rebase;    // records [frame_off[f], frame_off[f + 1]) live at mv + (frame_off[f] - rebase) * rec_bytes
-                                // (a host-pointer call copies only the window its offsets span); <= n_records
   ScanK k;
   int block;
   unsigned long long item_chunk;  // WORKGROUPS per launch (0 = 2^30; MTGPU_ITEM_CHUNK shrinks it for tests); a workgroup scans k.group items
-  int lds_bytes;
-  int lds_max;             // device limit of dynamic LDS per workgroup (set once per kernel instantiation)
-  int device;
-  int rec_bytes;           // 40 = AVMotionVector records, 8 = compact {src_x,src_y,dst_x,dst_y}
-  hipStream_t stream;
-  hipEvent_t ev_planned;   // profiling (mtgpu_profile_enable): recorded between the planning kernels and the scan kernel; else nullptr
 };
 
 hipError_t launch_scan(const ScanLaunch &L);

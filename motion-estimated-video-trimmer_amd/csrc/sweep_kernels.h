@@ -41,26 +41,13 @@ struct SweepK {
   int sys;                                // the output is not device memory: system-scope stores
 };
 
-struct SweepLaunch {
-  const unsigned char *mv;
-  unsigned long long n_records;           // frame_off entries are clamped to this (before `rebase`)
-  unsigned long long rebase;
-  const unsigned long long *frame_off;    // n_frames + 1
-  const unsigned char *has_sd;            // n_frames or null
-  unsigned int n_frames;
-  int rec_bytes;                          // 40 or 8
+struct SweepLaunch : BatchLaunch {
   unsigned int *centres;                  // n_thr_all * n_vec * n_frames words, setting-major
   int n_thr_all;                          // thresholds of the call
   int thr_per_pass;                       // tiles per launch; passes = ceil(n_thr_all / thr_per_pass)
   unsigned long long thr_sorted[kSweepMaxThr];   // ascending
   unsigned int thr_index[kSweepMaxThr];          // thr_sorted[i] is the caller's threshold thr_index[i]
   SweepK k;                               // everything but thr, out_t, n_thr (set per pass)
-  int lds_bytes;
-  int lds_max;                            // device limit of dynamic LDS per workgroup
-  int device;
-  void *plan_ws;                          // plan_scratch_bytes(n_frames), 32-byte aligned
-  hipStream_t stream;
-  hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the first pass; else nullptr
 };
 
 // Zero-fills the whole output block, builds the work list (launch_plan), then one launch per pass.

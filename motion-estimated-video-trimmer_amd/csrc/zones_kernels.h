@@ -38,14 +38,7 @@ struct ZoneK {
   int tile_words;                // zone_tile_words
 };
 
-struct ZoneLaunch {
-  const unsigned char *mv;
-  unsigned long long n_records;           // frame_off entries are clamped to this (before `rebase`)
-  unsigned long long rebase;
-  const unsigned long long *frame_off;    // n_frames + 1
-  const unsigned char *has_sd;            // n_frames or null
-  unsigned int n_frames;
-  int rec_bytes;                          // 40 or 8
+struct ZoneLaunch : BatchLaunch {
   const unsigned long long *stream_off;   // n_streams + 1 (pipe form: not read)
   unsigned int n_streams;
   const unsigned long long *keep;         // n_streams x gh x W, device memory (pipe form: one plane)
@@ -60,12 +53,6 @@ struct ZoneLaunch {
   int pipe = 0;
   int sys_flags = 0, sys_centres = 0;
   ZoneK k;
-  int lds_bytes;
-  int lds_max;                            // device limit of dynamic LDS per workgroup
-  int device;
-  void *plan_ws;                          // plan_scratch_bytes(n_frames), 32-byte aligned
-  hipStream_t stream;
-  hipEvent_t ev_planned;                  // profiling: recorded between the planning kernels and the zone kernel; else nullptr
 };
 
 // Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.  Pipe form: no

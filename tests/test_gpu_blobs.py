@@ -200,6 +200,23 @@ def test_tie_and_box(gpu_scanner_factory):
             assert got["flags"].tolist() == want, label
 
 
+def test_profiled_call_records_one_triple(gpu_scanner_factory):
+    """With mtgpu_profile_enable on, one resident blob scan is one event triple, and its answers are the hand values."""
+    c = bi.tie_case()
+    s = gpu_scanner_factory(c.p)
+    d_rec, d_off, d_sd = to_device(c.mv, c.off, c.sd, False)
+    s.profile(True)
+    try:
+        s.profile_read()
+        got = device_blobs(s, d_rec, d_off, d_sd, False)
+        r = s.profile_read()
+    finally:
+        s.profile(False)
+    assert r["launches"] == 1 and r["scan_ms"] > 0.0 and r["plan_ms"] > 0.0
+    assert got["centres"].tolist() == c.hand["centres"]
+    assert_outputs(got, c.hand, "profiled call", c.p)
+
+
 # ------------------------------------------------------------------ 8. batch plumbing
 
 def test_batch_plumbing(gpu_scanner_factory):
