@@ -162,8 +162,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ACC != 0 
     for (int i = tid; i < n8; i += BLOCK) a8[i] = 0ull;
   }
 
-  // The run's first stream: s = the number of streams that end at or before frame f (binary search, workgroup-uniform
-  // values: scalar code).  s == n_streams: the frame lies behind the last stream and is counted nowhere.
+  // The run's first stream, where the forward walk below starts: s = the number of streams that end at or before frame f.
+  // s == n_streams: the frame lies behind the last stream and is counted nowhere.  record_stream.h's stream_of written
+  // out: with the call the 4K form measured 1 % slower (docs/rounds/r24_kernel_fold.md).
   unsigned int s = 0u;
   {
     unsigned int lo = 0u, hi = n_streams;
@@ -197,11 +198,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(ACC != 0 
     }
     if (s >= n_streams) break;
 
-    // ---- zero the tile
+    // ---- zero the tile (record_stream.h's zero_tile written out: the call moves the register counts of the ACC 0 forms).
+    // The compact forms with accumulators make the zeros per frame: held across the run loop they take the four VGPRs
+    // those forms lack under 64, and two lane offsets of the streamer went to scratch (docs/rounds/r24_kernel_fold.md).
     {
       u32x4 *c4 = reinterpret_cast<u32x4 *>(tile);
       const int n4 = k.tile_words >> 2;
-      for (int j = tid; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
+      u32x4 zero = (u32x4){0u, 0u, 0u, 0u};
+      if constexpr (ACC != 0 && REC == 8) asm volatile("" : "+v"(zero));
+      for (int j = tid; j < n4; j += BLOCK) c4[j] = zero;
     }
     __syncthreads();
     // ---- the votes (an empty analysed range keeps nothing: nothing to read)
@@ -239,11 +244,9 @@ template <int REC, int ACC>
 hipError_t launch_map(const ActLaunch &L) {
   auto kern = activity_frames_kernel<kActBlock, kActUnroll, REC, ACC>;
   static std::atomic<unsigned long long> ready{0ull};
-  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
-  if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
   const unsigned long long groups = ((unsigned long long)L.n_frames + (unsigned long long)L.k.run - 1ull) / (unsigned long long)L.k.run;
-  return launch_chunked(groups, kGridChunk, [&](unsigned long long g0, unsigned int n) {
+  return launch_over_list(kern, ready, L, groups, [&](unsigned long long g0, unsigned int n) {
     hipLaunchKernelGGL(kern, dim3(n), dim3(kActBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)g0, L.n_frames, L.k,
                        L.stream_off, L.n_streams, L.active, L.centre, L.frames);
   });
@@ -258,8 +261,7 @@ hipError_t launch_map_acc(const ActLaunch &L) {
 
 hipError_t clear(unsigned int *out, unsigned long long n, hipStream_t stream) {
   if (!out || n == 0ull) return hipSuccess;
-  const unsigned long long blocks = (n + 255ull) / 256ull;
-  hipLaunchKernelGGL(activity_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, stream, out, n);
+  hipLaunchKernelGGL(activity_clear_kernel, dim3(clear_grid(n)), dim3(256), 0, stream, out, n);
   return hipGetLastError();
 }
 
@@ -278,10 +280,8 @@ hipError_t launch_activity_map(const ActLaunch &L) {
   if (e == hipSuccess) e = clear(L.frames, L.n_streams, L.stream);
   if (e != hipSuccess) return e;
   if (L.n_frames == 0 || L.n_streams == 0) return hipSuccess;
-  if (!L.frame_off || !L.stream_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records)
-    return hipErrorInvalidValue;
-  // flags / centres null: the planner answers nothing itself
-  e = plan_work_list(L, nullptr, 0, nullptr, 0);
+  if (!L.stream_off || !check_batch_launch(L)) return hipErrorInvalidValue;
+  e = plan_work_list(L, nullptr, 0, nullptr, 0);   // flags / centres null: the planner answers nothing itself
   if (e != hipSuccess) return e;
   return L.rec_bytes == 8 ? launch_map_acc<8>(L) : launch_map_acc<40>(L);
 }

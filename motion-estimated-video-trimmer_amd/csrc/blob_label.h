@@ -1,8 +1,9 @@
-// blob_label.h — the labelling of a centre plane in LDS: union-find over a dead vote tile, the five passes of
-// blobs_kernels.hip (init, unite, flatten, winner, box) as `__device__ __forceinline__` functions for the kernels that
-// label the residual centres (gmc_blobs_kernels.hip).  blobs_kernels.hip keeps its own text of the same passes (see
-// docs/rounds/r13_gmc_blobs.md); an edit to one is an edit to the other.  tests/test_gpu_blob_planes.py is where both
-// texts meet random connectivity (percolation, mazes, combs) and are compared output for output.
+// blob_label.h — the labelling of a centre plane in LDS: union-find over a dead vote tile, five passes (init, unite,
+// flatten, winner, box) as `__device__ __forceinline__` functions.  The ONE text of them: blobs_frames_kernel
+// (blobs_kernels.hip) and gmc_blobs_frames_kernel (gmc_blobs_kernels.hip, on the residual centres) both call it, in
+// every form.  find_root and unite have no iteration cap, so an edit here is made once and is then held, for all three
+// labelling kernels (resident, pipe, compensated), by tests/test_gpu_blob_planes.py: random connectivity (percolation,
+// mazes, combs), every kernel against the model and the kernels against each other, the smallest grid first.
 //
 //   cpl     crows x W u64   the centre plane: bit x & 63 of word x >> 6 of row r is the centre (x, y_lo + r)
 //   L       crows x gw u32  the labels, word r * gw + x.  A root holds kRoot | (cells - 1), every other cell the index

@@ -43,8 +43,9 @@
 //     no clear    launch_plan is handed the outputs and answers the frames without side data itself, as in launch_scan:
 //                 planning + one kernel.
 //
-// The record loads, the streamers, the vote, the row masks and the centre test of a word are those of record_stream.h,
-// unchanged; the launch helpers are those of scan_kernels.h.
+// The record loads, the stream search, the streamers, the vote, the row masks and the centre plane are those of
+// record_stream.h, the five labelling passes those of blob_label.h (one text, shared with gmc_blobs_kernels.hip); the
+// launch helpers are those of scan_kernels.h.
 #if !defined(__HIP_DEVICE_COMPILE__) || defined(__gfx950__)
 #else
 #error "blobs_kernels.hip is written for gfx950 only (wave64, 160 KB LDS)"
@@ -56,51 +57,9 @@
 
 #include "blobs_kernels.h"
 #include "record_stream.h"
+#include "blob_label.h"
 
 namespace mtgpu {
-
-namespace {
-
-constexpr unsigned int kRoot = 0x80000000u;    // label word of a root: kRoot | (cells of the tree - 1)
-
-// The root of cell x: labels below kRoot are cell indices smaller than the cell that holds them.
-__device__ __forceinline__ unsigned int find_root(unsigned int *L, unsigned int x) {
-  for (;;) {
-    const unsigned int v = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (v & kRoot) return x;
-    x = v;
-  }
-}
-
-// Joins the trees of cells a and b.  Runs concurrently in every lane; only roots are linked, always towards the smaller
-// index.  When the atomic finds that `a` has been linked by another lane in the meantime, label[a] is min(old, b) now,
-// and old and b are what remains to be joined.
-__device__ __forceinline__ void unite(unsigned int *L, unsigned int a, unsigned int b) {
-  for (;;) {
-    a = find_root(L, a);
-    b = find_root(L, b);
-    if (a == b) return;
-    if (a < b) { const unsigned int t = a; a = b; b = t; }
-    const unsigned int old = atomicMin(&L[a], b);
-    if (old & kRoot) return;
-    a = old;
-  }
-}
-
-// f(r, w, cw, tw) for every non-empty word cw = cpl[tw] of the centre plane, tw = r * W + w; a wave per word, lane =
-// bit.  The trip count depends on the wave alone.
-template <int BLOCK, class F>
-__device__ __forceinline__ void for_centre_words(const unsigned long long *cpl, int crows, int W, F f) {
-  const int nw = crows * W;
-  for (int tw = (int)(threadIdx.x >> 6); tw < nw; tw += BLOCK / 64) {
-    const unsigned long long cw = cpl[tw];
-    if (cw == 0ull) continue;
-    const int r = tw / W;
-    f(r, tw - r * W, cw, tw);
-  }
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void blobs_clear_kernel(unsigned char *__restrict__ flags, unsigned int *__restrict__ centres,
                                                           unsigned int *__restrict__ blobs, unsigned int *__restrict__ largest,
@@ -154,25 +113,16 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const bool masked = keep != nullptr;
   unsigned int s = 0u;
   if (!PIPE && masked) {
-    unsigned int lo = 0u, hi = n_streams;
-    while (lo < hi) {
-      const unsigned int mid = lo + ((hi - lo) >> 1);
-      if (stream_off[mid + 1u] <= (unsigned long long)f) lo = mid + 1u; else hi = mid;
-    }
-    s = lo;
-    if (s >= n_streams) return;
+    s = stream_of(stream_off, n_streams, f);
+    if (s >= n_streams) return;                 // a frame in front of the first stream is not told apart: it takes plane 0
   }
 
   // ---- the keep words of the analysed rows (no mask: ones), the first word of a lane on its way while the tile is zeroed
   const int nkeep = crows * W;
   const unsigned long long *kp = masked ? keep + ((size_t)s * (size_t)k.gh + (size_t)k.y_lo) * (size_t)W : nullptr;
   const unsigned long long k0 = (masked && tid < nkeep) ? kp[tid] : ~0ull;
-  {
-    u32x4 *c4 = reinterpret_cast<u32x4 *>(tile);
-    const int n4 = k.tile_words >> 2;
-    for (int j = tid; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
-    if (tid < 8) total[tid] = (tid == 4 || tid == 5) ? 0xffffffffu : 0u;   // [4], [5]: minima
-  }
+  zero_tile<BLOCK>(tile, k.tile_words);
+  if (tid < 8) total[tid] = (tid == 4 || tid == 5) ? 0xffffffffu : 0u;   // [4], [5]: minima
   if (tid < nkeep) klds[tid] = k0;
   for (int j = tid + BLOCK; j < nkeep; j += BLOCK) klds[j] = masked ? kp[j] : ~0ull;
   __syncthreads();
@@ -192,12 +142,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   __syncthreads();
   // ---- the centre plane (over the keep words, dead now) and the count.  Every word is written, the empty ones too.
   unsigned long long *cpl = klds;
-  for (int tk = tid; tk < nkeep; tk += BLOCK) {
-    const int r = tk / W, w = tk - r * W;
-    const unsigned long long c = centre_word(amask + (size_t)(r + 1) * W, w, W, gw);
-    cpl[tk] = c;
-    if (c) atomicAdd(&total[0], (unsigned int)__popcll(c));
-  }
+  centre_plane<BLOCK>(amask, cpl, &total[0], W, gw, nkeep);
   __syncthreads();
   const unsigned int ncentres = total[0];
   if (ncentres == 0u) {                                       // workgroup-uniform: most frames of most streams
@@ -219,90 +164,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 
   // ---- labels.  L[r * gw + x], r < crows <= R: inside the tile's (R + 2) * gw words.
   unsigned int *L = tile;
-  // init: the first cell of a horizontal run is a root, the others point at it.  Column 0 is never a centre, so the
-  // scan to the left ends at a clear bit; `ww >= 0` bounds it all the same.
-  for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
-    if (((cw >> lane) & 1ull) == 0ull) return;
-    const unsigned long long below = ~cw & ((1ull << lane) - 1ull);        // clear bits to the left of this cell, in its word
-    int xs;
-    if (below != 0ull) {
-      xs = w * 64 + 64 - __clzll((long long)below);
-    } else {
-      xs = w * 64;
-      for (int ww = w - 1; ww >= 0; --ww) {
-        const unsigned long long nz = ~cpl[tw - w + ww];
-        if (nz != 0ull) { xs = ww * 64 + 64 - __clzll((long long)nz); break; }
-        xs = ww * 64;
-      }
-    }
-    const int x = w * 64 + lane;
-    L[r * gw + x] = (x == xs) ? kRoot : (unsigned int)(r * gw + xs);
-  });
+  // The five passes of blob_label.h, a barrier behind each.
+  blob_label::init<BLOCK>(cpl, crows, W, gw, L, lane);
   __syncthreads();
-  // unite: the first cell of every segment in which this row's centres lie under the row above's (per word: a segment
-  // that crosses a word seam is joined twice)
-  for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
-    if (r == 0) return;
-    const unsigned long long both = cw & cpl[tw - W];
-    const unsigned long long first = both & ~(both << 1);
-    if ((first >> lane) & 1ull) {
-      const unsigned int i = (unsigned int)(r * gw + w * 64 + lane);
-      unite(L, i, i - (unsigned int)gw);
-    }
-  });
+  blob_label::unite_rows<BLOCK>(cpl, crows, W, gw, L, lane);
   __syncthreads();
-  // flatten and count: a cell that is no root stores its root and adds 1 to it — one add per (wave, distinct root)
-  for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
-    const unsigned int i = (unsigned int)(r * gw + w * 64 + lane);
-    unsigned int p = 0u;
-    bool todo = false;
-    if ((cw >> lane) & 1ull) {
-      p = find_root(L, i);
-      todo = p != i;
-      if (todo) __hip_atomic_store(&L[i], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    unsigned long long b;
-    while ((b = __ballot(todo)) != 0ull) {
-      const int leader = __ffsll((long long)b) - 1;
-      const unsigned int p0 = (unsigned int)__shfl((int)p, leader);
-      const bool same = todo && p == p0;
-      const unsigned long long sb = __ballot(same);
-      if (lane == leader) atomicAdd(&L[p0], (unsigned int)__popcll(sb));
-      todo = todo && !same;
-    }
-  });
+  blob_label::flatten<BLOCK>(cpl, crows, W, gw, L, lane);
   __syncthreads();
-  // winner: the number of roots, and the largest (cells, smallest root index first)
-  unsigned long long *best = reinterpret_cast<unsigned long long *>(total + 2);
-  for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
-    const unsigned int i = (unsigned int)(r * gw + w * 64 + lane);
-    unsigned int v = 0u;
-    if ((cw >> lane) & 1ull) v = L[i];
-    const bool root = (v & kRoot) != 0u;
-    const unsigned long long rb = __ballot(root);
-    if (root) {
-      if (lane == __ffsll((long long)rb) - 1) atomicAdd(&total[1], (unsigned int)__popcll(rb));
-      atomicMax(best, ((unsigned long long)((v & ~kRoot) + 1u) << 32) | (unsigned long long)(0xffffffffu - i));
-    }
-  });
+  blob_label::winner<BLOCK>(cpl, crows, W, gw, L, total, lane);
   __syncthreads();
-  const unsigned long long key = *best;
-  const unsigned int win = 0xffffffffu - (unsigned int)(key & 0xffffffffull);
-  // box: LDS min / max over the winner's cells (its root, and every cell whose label is the root).  In the PIPE form
-  // without BOXED nothing reads the box, and in every PIPE form nothing reads the blob count total[1]: both are computed
-  // all the same, on purpose — the five passes are those of the resident form, unchanged.
-  for_centre_words<BLOCK>(cpl, crows, W, [&](int r, int w, unsigned long long cw, int tw) {
-    const unsigned int i = (unsigned int)(r * gw + w * 64 + lane);
-    bool mine = false;
-    if ((cw >> lane) & 1ull) mine = i == win || L[i] == win;
-    const unsigned long long mb = __ballot(mine);
-    if (mine && lane == __ffsll((long long)mb) - 1) {
-      atomicMin(&total[4], (unsigned int)(w * 64 + lane));
-      atomicMax(&total[6], (unsigned int)(w * 64 + 63 - __clzll((long long)mb)));
-      atomicMin(&total[5], (unsigned int)r);
-      atomicMax(&total[7], (unsigned int)r);
-    }
-  });
+  const unsigned long long key = *reinterpret_cast<const unsigned long long *>(total + 2);
+  // In the PIPE form without BOXED nothing reads the box, and in every PIPE form nothing reads the blob count total[1]:
+  // both are computed all the same, on purpose — the five passes are those of the resident form, unchanged.
+  blob_label::box<BLOCK>(cpl, crows, W, gw, L, total, 0xffffffffu - (unsigned int)(key & 0xffffffffull), lane);
   __syncthreads();
   if (tid == 0) {
     const unsigned int big = (unsigned int)(key >> 32);
@@ -330,10 +204,8 @@ template <int REC, bool PIPE>
 hipError_t launch_frames(const BlobLaunch &L) {
   auto kern = blobs_frames_kernel<kBlobBlock, kBlobUnroll, REC, PIPE>;
   static std::atomic<unsigned long long> ready{0ull};
-  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
-  if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
-  return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
+  return launch_over_list(kern, ready, L, L.n_frames, [&](unsigned long long i0, unsigned int n) {
     hipLaunchKernelGGL(kern, dim3(n), dim3(kBlobBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.k,
                        L.stream_off, L.n_streams, L.keep, L.flags, L.centres, L.blobs, L.largest, L.box, L.sys_flags, L.sys_centres);
   });
@@ -351,30 +223,22 @@ hipError_t launch_blob_scan(const BlobLaunch &L) {
     if (L.sys_flags != 0 || L.sys_centres != 0) return hipErrorInvalidValue;
     if (L.keep ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0)) return hipErrorInvalidValue;
   }
-  if (!L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records) return hipErrorInvalidValue;
-  if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.lds_bytes > L.lds_max ||
-      (size_t)L.lds_bytes < blob_lds_bytes(L.k.gw, L.k.R) || (size_t)L.k.tile_words != blob_tile_words(L.k.gw, L.k.R) ||
-      L.k.W != (L.k.gw + 63) / 64)
+  if (!check_batch_launch(L) || !check_rows(L.k, L.lds_bytes, L.lds_max, blob_lds_bytes(L.k.gw, L.k.R)) ||
+      (size_t)L.k.tile_words != blob_tile_words(L.k.gw, L.k.R) || L.k.W != (L.k.gw + 63) / 64)
     return hipErrorInvalidValue;
-  if (L.pipe) {
-    // The planner is handed the outputs and answers every frame without side data itself (at the outputs' scope), as in
-    // launch_scan and launch_zone_scan: no clear kernel — planning + one kernel.  Its count array is whichever is given.
-    hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres ? L.centres : L.largest, L.sys_centres);
-    if (e != hipSuccess) return e;
-    if (L.box) return L.rec_bytes == 8 ? launch_frames<8 | kRecBoxed, true>(L) : launch_frames<40 | kRecBoxed, true>(L);
-    return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
-  }
-  {
-    const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
-    hipLaunchKernelGGL(blobs_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream,
-                       L.flags, L.centres, L.blobs, L.largest, L.box, L.n_frames);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  // flags / centres null: the planner answers nothing itself (the outputs hold the clear's values already)
-  hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
-  if (e != hipSuccess) return e;
-  return L.rec_bytes == 8 ? launch_frames<8, false>(L) : launch_frames<40, false>(L);
+  // pipe form: the planner's count array is whichever is given; the boxed kernel where the batch has a box array
+  return plan_and_launch(
+      L, L.pipe, L.flags, L.sys_flags, L.centres ? L.centres : L.largest, L.sys_centres,
+      [&](unsigned int grid) {
+        hipLaunchKernelGGL(blobs_clear_kernel, dim3(grid), dim3(256), 0, L.stream, L.flags, L.centres, L.blobs, L.largest, L.box,
+                           L.n_frames);
+      },
+      [&](auto rec, auto pipe) {
+        if constexpr (pipe()) {
+          if (L.box) return launch_frames<rec() | kRecBoxed, true>(L);
+        }
+        return launch_frames<rec(), pipe()>(L);
+      });
 }
 
 }  // namespace mtgpu

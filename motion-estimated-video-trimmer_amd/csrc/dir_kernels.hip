@@ -49,8 +49,9 @@ namespace mtgpu {
 
 namespace {
 
-// ---- the centres (:277-293), one task per (analysed row, word): analysed row r <-> mask row r + 1; x in [1, gw-2]
-// (:280); neighbours across word and row boundaries; outside the grid: inactive.  As in zones_kernels.hip.
+// ---- the centres: record_stream.h's count_centres, kept as this file's own text.  Called with W and gw as scalars the
+// 40-byte pipe form takes 77 SGPRs instead of 76 and the four forms come out in another register order
+// (docs/rounds/r24_kernel_fold.md): no fold without identical resource figures.
 template <int BLOCK>
 __device__ __forceinline__ void count_centres(const unsigned long long *amask, unsigned int *total, const DirK &k, int crows) {
   const int W = k.W;
@@ -188,23 +189,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   [[maybe_unused]] unsigned int tw = (unsigned int)k.tile_words;   // the pipe form only
   if constexpr (!PIPE) {
     if (allows != nullptr) {
-      unsigned int lo = 0u, hi = n_streams;
-      while (lo < hi) {
-        const unsigned int mid = lo + ((hi - lo) >> 1);
-        if (stream_off[mid + 1u] <= (unsigned long long)f) lo = mid + 1u; else hi = mid;
-      }
+      const unsigned int lo = stream_of(stream_off, n_streams, f);
       // in front of the first stream (stream_off[0] > f) the frame belongs to no stream either
       if (lo >= n_streams || stream_off[lo] > (unsigned long long)f) return;
       allow = (unsigned int)allows[lo];
     }
   }
   // ---- zero the tile, the total and the rose
-  {
-    u32x4 *c4 = reinterpret_cast<u32x4 *>(tile);
-    const int n4 = k.tile_words >> 2;
-    for (int j = tid; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
-    if (tid < 12) total[tid] = 0u;              // total[0 .. 3] and the eight rose words behind them
-  }
+  zero_tile<BLOCK>(tile, k.tile_words);
+  if (tid < 12) total[tid] = 0u;                // total[0 .. 3] and the eight rose words behind them
   if constexpr (PIPE) {
     // the keep words of the analysed rows into mask rows 1 .. crows (crows <= R: inside the (R + 2) x W plane); keep row
     // y_lo + r, r < crows, lies inside the gh x W plane
@@ -304,10 +297,8 @@ template <int REC, bool PIPE>
 hipError_t launch_frames(const DirLaunch &L) {
   auto kern = dir_frames_kernel<kDirBlock, kDirUnroll, REC, PIPE>;
   static std::atomic<unsigned long long> ready{0ull};
-  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
-  if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
-  return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
+  return launch_over_list(kern, ready, L, L.n_frames, [&](unsigned long long i0, unsigned int n) {
     hipLaunchKernelGGL(kern, dim3(n), dim3(kDirBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.k,
                        L.stream_off, L.n_streams, L.allows, L.allow, L.flags, L.centres, L.rose, L.keep, L.sys_flags,
                        L.sys_centres, L.report_sectors);
@@ -327,33 +318,18 @@ hipError_t launch_dir_scan(const DirLaunch &L) {
   }
   if (L.allows ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0 || L.allow > 255u))
     return hipErrorInvalidValue;
-  if (!L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records) return hipErrorInvalidValue;
-  if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.lds_bytes > L.lds_max ||
-      (size_t)L.lds_bytes < dir_lds_bytes(L.k.gw, L.k.R))
+  if (!check_batch_launch(L) || !check_rows(L.k, L.lds_bytes, L.lds_max, dir_lds_bytes(L.k.gw, L.k.R))) return hipErrorInvalidValue;
+  // The pipe form stages the keep rows into the mask plane and indexes them: the block's layout fields must be the grid's.
+  // The kernel finds the plane again from R = max(1, y_hi - y_lo).
+  if (L.pipe && ((size_t)L.k.tile_words != dir_tile_words(L.k.gw, L.k.R) || L.k.W != (L.k.gw + 63) / 64 || L.k.y_lo < 0 ||
+                 L.k.y_hi > L.k.gh || L.k.R != (L.k.y_hi - L.k.y_lo < 1 ? 1 : L.k.y_hi - L.k.y_lo)))
     return hipErrorInvalidValue;
-  if (L.pipe) {
-    // The keep rows are staged into the mask plane and indexed by the kernel: the block's layout fields must be the grid's.
-    // The kernel finds the plane again from R = max(1, y_hi - y_lo).
-    if ((size_t)L.k.tile_words != dir_tile_words(L.k.gw, L.k.R) || L.k.W != (L.k.gw + 63) / 64 || L.k.y_lo < 0 || L.k.y_hi > L.k.gh ||
-        L.k.R != (L.k.y_hi - L.k.y_lo < 1 ? 1 : L.k.y_hi - L.k.y_lo))
-      return hipErrorInvalidValue;
-    // The planner is handed the outputs and answers every frame without side data itself (at the outputs' scope), as in
-    // launch_scan, launch_zone_scan and launch_gmc_scan: no clear kernel — planning + one kernel.
-    hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres, L.sys_centres);
-    if (e != hipSuccess) return e;
-    return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
-  }
-  {
-    const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
-    hipLaunchKernelGGL(dir_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream, L.flags,
-                       L.centres, L.rose, L.n_frames);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  // flags / centres null: the planner answers nothing itself (the outputs are zero already)
-  hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
-  if (e != hipSuccess) return e;
-  return L.rec_bytes == 8 ? launch_frames<8, false>(L) : launch_frames<40, false>(L);
+  return plan_and_launch(
+      L, L.pipe, L.flags, L.sys_flags, L.centres, L.sys_centres,
+      [&](unsigned int grid) {
+        hipLaunchKernelGGL(dir_clear_kernel, dim3(grid), dim3(256), 0, L.stream, L.flags, L.centres, L.rose, L.n_frames);
+      },
+      [&](auto rec, auto pipe) { return launch_frames<rec(), pipe()>(L); });
 }
 
 }  // namespace mtgpu

@@ -188,13 +188,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const bool masked = keep != nullptr;
   unsigned int s = 0u;
   if (!PIPE && masked) {                        // pipe form: plane 0 serves every frame of the batch
-    unsigned int lo = 0u, hi = n_streams;
-    while (lo < hi) {
-      const unsigned int mid = lo + ((hi - lo) >> 1);
-      if (stream_off[mid + 1u] <= (unsigned long long)f) lo = mid + 1u; else hi = mid;
-    }
-    s = lo;
-    if (s >= n_streams) return;
+    s = stream_of(stream_off, n_streams, f);
+    if (s >= n_streams) return;                 // a frame in front of the first stream is not told apart: it takes plane 0
   }
 
   // ---- the keep words of the analysed rows (no mask: ones; keep row y_lo + r, r < crows, lies inside the stream's
@@ -202,13 +197,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const int nkeep = crows * W;
   const unsigned long long *kp = masked ? keep + ((size_t)s * (size_t)k.gh + (size_t)k.y_lo) * (size_t)W : nullptr;
   const unsigned long long k0 = (masked && tid < nkeep) ? kp[tid] : ~0ull;
-  {
-    u32x4 *c4 = reinterpret_cast<u32x4 *>(tile);
-    const int n4 = k.tile_words >> 2;
-    for (int j = tid; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
-    // hx, hy, res and total are contiguous; total[4], total[5]: minima
-    if (tid < 2 * kGmcHistBins + 16) hx[tid] = (tid == 2 * kGmcHistBins + 12 || tid == 2 * kGmcHistBins + 13) ? 0xffffffffu : 0u;
-  }
+  zero_tile<BLOCK>(tile, k.tile_words);
+  // hx, hy, res and total are contiguous; total[4], total[5]: minima
+  if (tid < 2 * kGmcHistBins + 16) hx[tid] = (tid == 2 * kGmcHistBins + 12 || tid == 2 * kGmcHistBins + 13) ? 0xffffffffu : 0u;
   if (tid < nkeep) klds[tid] = k0;
   for (int j = tid + BLOCK; j < nkeep; j += BLOCK) klds[j] = masked ? kp[j] : ~0ull;
   __syncthreads();
@@ -289,12 +280,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   __syncthreads();
   // ---- the centre plane (over the keep words, dead now) and the count.  Every word is written, the empty ones too.
   unsigned long long *cpl = klds;
-  for (int tk = tid; tk < nkeep; tk += BLOCK) {
-    const int r = tk / W, w = tk - r * W;
-    const unsigned long long c = centre_word(amask + (size_t)(r + 1) * W, w, W, gw);
-    cpl[tk] = c;
-    if (c) atomicAdd(&total[0], (unsigned int)__popcll(c));
-  }
+  centre_plane<BLOCK>(amask, cpl, &total[0], W, gw, nkeep);
   __syncthreads();
   const unsigned int ncentres = total[0];
   if (ncentres == 0u) {                                       // workgroup-uniform: most frames of most streams
@@ -377,8 +363,6 @@ template <int REC, bool PIPE>
 hipError_t launch_frames(const GmcBlobLaunch &L) {
   auto kern = gmc_blobs_frames_kernel<kGmcBlobBlock, kGmcBlobUnroll, REC, PIPE>;
   static std::atomic<unsigned long long> ready{0ull};
-  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
-  if (e != hipSuccess) return e;
   GmcBlobArgs a;
   a.mv = L.mv;
   a.work = static_cast<const WorkItem *>(L.plan_ws);
@@ -392,7 +376,7 @@ hipError_t launch_frames(const GmcBlobLaunch &L) {
   a.sys_flags = L.sys_flags;
   a.sys_count = L.sys_count;
   a.report = L.report;
-  return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
+  return launch_over_list(kern, ready, L, L.n_frames, [&](unsigned long long i0, unsigned int n) {
     a.item0 = (unsigned int)i0;
     hipLaunchKernelGGL(kern, dim3(n), dim3(kGmcBlobBlock), L.lds_bytes, L.stream, a);
   });
@@ -414,32 +398,25 @@ hipError_t launch_gmc_blob_scan(const GmcBlobLaunch &L) {
     if (L.sys_flags != 0 || L.sys_count != 0 || L.report != 0) return hipErrorInvalidValue;
     if (L.keep ? (!L.stream_off || L.n_streams == 0) : (L.stream_off != nullptr || L.n_streams != 0)) return hipErrorInvalidValue;
   }
-  if (!L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records) return hipErrorInvalidValue;
+  if (!check_batch_launch(L)) return hipErrorInvalidValue;
   if (L.k.max_shift < 0 || L.k.max_shift > kGmcMaxShift || L.k.min_share_q8 > 256u) return hipErrorInvalidValue;
   // The kernel indexes the staged keep rows and the planes by these fields: they must be the grid's.
-  if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.k.y_lo < 0 || L.k.y_hi > L.k.gh || L.lds_bytes > L.lds_max ||
-      (size_t)L.lds_bytes < gmc_blobs_lds_bytes(L.k.gw, L.k.R) || (size_t)L.k.tile_words != blob_tile_words(L.k.gw, L.k.R) ||
-      L.k.W != (L.k.gw + 63) / 64)
+  if (!check_rows(L.k, L.lds_bytes, L.lds_max, gmc_blobs_lds_bytes(L.k.gw, L.k.R)) || L.k.y_lo < 0 || L.k.y_hi > L.k.gh ||
+      (size_t)L.k.tile_words != blob_tile_words(L.k.gw, L.k.R) || L.k.W != (L.k.gw + 63) / 64)
     return hipErrorInvalidValue;
-  if (L.pipe) {
-    // The planner is handed the outputs and answers every frame without side data itself (at the outputs' scope), as in
-    // launch_gmc_scan and launch_blob_scan: no clear kernel — planning + one kernel.
-    hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres, L.sys_count);
-    if (e != hipSuccess) return e;
-    if (L.box) return L.rec_bytes == 8 ? launch_frames<8 | kRecBoxed, true>(L) : launch_frames<40 | kRecBoxed, true>(L);
-    return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
-  }
-  {
-    const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
-    hipLaunchKernelGGL(gmc_blobs_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream,
-                       L.flags, L.centres, L.blobs, L.largest, L.box, L.info, L.n_frames);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  // flags / centres null: the planner answers nothing itself (the outputs hold the clear's values already)
-  hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
-  if (e != hipSuccess) return e;
-  return L.rec_bytes == 8 ? launch_frames<8, false>(L) : launch_frames<40, false>(L);
+  // pipe form: the boxed kernel where the batch has a box array
+  return plan_and_launch(
+      L, L.pipe, L.flags, L.sys_flags, L.centres, L.sys_count,
+      [&](unsigned int grid) {
+        hipLaunchKernelGGL(gmc_blobs_clear_kernel, dim3(grid), dim3(256), 0, L.stream, L.flags, L.centres, L.blobs, L.largest, L.box,
+                           L.info, L.n_frames);
+      },
+      [&](auto rec, auto pipe) {
+        if constexpr (pipe()) {
+          if (L.box) return launch_frames<rec() | kRecBoxed, true>(L);
+        }
+        return launch_frames<rec(), pipe()>(L);
+      });
 }
 
 }  // namespace mtgpu

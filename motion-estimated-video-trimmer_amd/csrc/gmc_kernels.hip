@@ -136,12 +136,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const unsigned long long nrec = me.r1 - me.r0;
 
   // ---- zero the tile, the histograms and the result words
-  {
-    u32x4 *c4 = reinterpret_cast<u32x4 *>(tile);
-    const int n4 = k.tile_words >> 2;
-    for (int j = tid; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
-    if (tid < 2 * kGmcHistBins + 8) hx[tid] = 0u;              // hx, hy and res are contiguous
-  }
+  zero_tile<BLOCK>(tile, k.tile_words);
+  if (tid < 2 * kGmcHistBins + 8) hx[tid] = 0u;                // hx, hy and res are contiguous
   if constexpr (PIPE) {
     // the keep words of the analysed rows into mask rows 1 .. crows (crows <= R: inside the (R + 2) x W plane); keep row
     // y_lo + r, r < crows, lies inside the gh x W plane
@@ -241,17 +237,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
                      [=, &k](int j, int w, int g, unsigned long long m) { amask[(size_t)j * k.W + w] = m; });
   }
   __syncthreads();
-  {
-    const int W = k.W;
-    const int ntask = crows * W;
-    for (int tk = tid; tk < ntask; tk += BLOCK) {
-      const int r = tk / W, w = tk - r * W;
-      const unsigned long long *mr = amask + (size_t)(r + 1) * W;
-      if (mr[w] == 0ull) continue;
-      const unsigned int c = (unsigned int)__popcll(centre_word(mr, w, W, k.gw));
-      if (c) atomicAdd(&res[0], c);
-    }
-  }
+  count_centres<BLOCK>(amask, &res[0], k.W, k.gw, crows);
   __syncthreads();
   if (tid == 0) {
     const unsigned int c = res[0];
@@ -279,10 +265,8 @@ template <int REC, bool PIPE>
 hipError_t launch_frames(const GmcLaunch &L) {
   auto kern = gmc_frames_kernel<kGmcBlock, kGmcUnroll, REC, PIPE>;
   static std::atomic<unsigned long long> ready{0ull};
-  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
-  if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
-  return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
+  return launch_over_list(kern, ready, L, L.n_frames, [&](unsigned long long i0, unsigned int n) {
     hipLaunchKernelGGL(kern, dim3(n), dim3(kGmcBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.k,
                        L.flags, L.centres, L.info, L.keep, L.sys_flags, L.sys_centres, L.report_vector);
   });
@@ -299,32 +283,17 @@ hipError_t launch_gmc_scan(const GmcLaunch &L) {
   } else {
     if (L.keep || L.sys_flags != 0 || L.sys_centres != 0 || L.report_vector != 0) return hipErrorInvalidValue;
   }
-  if (!L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records) return hipErrorInvalidValue;
+  if (!check_batch_launch(L) || !check_rows(L.k, L.lds_bytes, L.lds_max, gmc_lds_bytes(L.k.gw, L.k.R))) return hipErrorInvalidValue;
   if (L.k.max_shift < 0 || L.k.max_shift > kGmcMaxShift || L.k.min_share_q8 > 256u) return hipErrorInvalidValue;
-  if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.lds_bytes > L.lds_max ||
-      (size_t)L.lds_bytes < gmc_lds_bytes(L.k.gw, L.k.R))
+  // The pipe form stages the keep rows into the mask plane and indexes them: the block's layout fields must be the grid's.
+  if (L.pipe && ((size_t)L.k.tile_words != gmc_tile_words(L.k.gw, L.k.R) || L.k.W != (L.k.gw + 63) / 64 || L.k.y_lo < 0 || L.k.y_hi > L.k.gh))
     return hipErrorInvalidValue;
-  if (L.pipe) {
-    // The keep rows are staged into the mask plane and indexed by the kernel: the block's layout fields must be the grid's.
-    if ((size_t)L.k.tile_words != gmc_tile_words(L.k.gw, L.k.R) || L.k.W != (L.k.gw + 63) / 64 || L.k.y_lo < 0 || L.k.y_hi > L.k.gh)
-      return hipErrorInvalidValue;
-    // The planner is handed the outputs and answers every frame without side data itself (at the outputs' scope), as in
-    // launch_scan, launch_zone_scan and launch_blob_scan: no clear kernel — planning + one kernel.
-    hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres, L.sys_centres);
-    if (e != hipSuccess) return e;
-    return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
-  }
-  {
-    const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
-    hipLaunchKernelGGL(gmc_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream,
-                       L.flags, L.centres, L.info, L.n_frames);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  // flags / centres null: the planner answers nothing itself (the outputs are zero already)
-  hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
-  if (e != hipSuccess) return e;
-  return L.rec_bytes == 8 ? launch_frames<8, false>(L) : launch_frames<40, false>(L);
+  return plan_and_launch(
+      L, L.pipe, L.flags, L.sys_flags, L.centres, L.sys_centres,
+      [&](unsigned int grid) {
+        hipLaunchKernelGGL(gmc_clear_kernel, dim3(grid), dim3(256), 0, L.stream, L.flags, L.centres, L.info, L.n_frames);
+      },
+      [&](auto rec, auto pipe) { return launch_frames<rec(), pipe()>(L); });
 }
 
 }  // namespace mtgpu

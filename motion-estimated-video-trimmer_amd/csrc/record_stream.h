@@ -1,7 +1,8 @@
 // record_stream.h — the device helpers every kernel that walks the scan's work list shares: the record loads and
 // decodes, the work-list entry load, the scope-aware result store, and — for the kernels derived from the scan (sweep,
-// activity, zones) — the plain record streamers, the single-threshold vote, the single-level row masks and the centre
-// test of one mask word.  All `__device__ __forceinline__`: every kernel still compiles its own instantiation, so a
+// activity, zones, blobs, gmc, gmc_blobs, dir) — the stream search, the tile zero-fill, the plain record streamers, the
+// single-threshold vote, the single-level row masks, the centre test of one mask word, and the two passes over a mask
+// plane built on it: the centre count and the centre plane.  All `__device__ __forceinline__`: every kernel still compiles its own instantiation, so a
 // change here is a change to each of them.  The rule that keeps sharing safe: an edit to this header must leave the
 // device assembly of every including translation unit as it was, or be measured for each of them.
 // Internal; included after scan_kernels.h; not part of the C ABI.
@@ -76,6 +77,28 @@ __device__ __forceinline__ void store_flag(unsigned char *flags, unsigned int f,
 }
 __device__ __forceinline__ void store_centres(unsigned int *centres, unsigned int f, unsigned int v, int sys) {
   store_result(&centres[f], v, sys);
+}
+
+// ---- a frame's stream: the number of streams that end at or before frame f, i.e. the stream of f where it has one
+// (stream s holds frames [stream_off[s], stream_off[s + 1])).  n_streams: f lies behind the last stream.  A frame in
+// front of the first stream gets 0, like a frame of stream 0: the caller that minds tests stream_off[0] itself.  Binary
+// search on workgroup-uniform values: scalar code.
+__device__ __forceinline__ unsigned int stream_of(const unsigned long long *stream_off, unsigned int n_streams, unsigned int f) {
+  unsigned int lo = 0u, hi = n_streams;
+  while (lo < hi) {
+    const unsigned int mid = lo + ((hi - lo) >> 1);
+    if (stream_off[mid + 1u] <= (unsigned long long)f) lo = mid + 1u; else hi = mid;
+  }
+  return lo;
+}
+
+// ---- the vote tile (tile_words words, a multiple of 4, 16-byte aligned) zeroed with 16-byte stores.  What a kernel
+// zeroes behind it (totals, histograms, result words) differs per kernel and stays there.
+template <int BLOCK>
+__device__ __forceinline__ void zero_tile(unsigned int *tile, int tile_words) {
+  u32x4 *c4 = reinterpret_cast<u32x4 *>(tile);
+  const int n4 = tile_words >> 2;
+  for (int j = threadIdx.x; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
 }
 
 // ---- the derived kernels' record streamers.  (The scan's own stream_mv40 / stream_compact / stream_tail, with the
@@ -235,6 +258,33 @@ __device__ __forceinline__ unsigned long long centre_word(const unsigned long lo
     valid &= ~((1ull << lo) - 1ull);
   }
   return m & nb & valid;
+}
+
+// ---- the centres (:277-293) of one mask plane, one task per (analysed row, word): analysed row r <-> mask row r + 1 of
+// amask (crows + 2 rows of W words).  On a masked plane an ignored cell next to a word boundary carries nothing over.
+// (The sweep counts per vector level and the activity map keeps every centre word: their passes are their own.)
+// The count alone, added to *total:
+template <int BLOCK>
+__device__ __forceinline__ void count_centres(const unsigned long long *amask, unsigned int *total, int W, int gw, int crows) {
+  const int ntask = crows * W;
+  for (int tk = threadIdx.x; tk < ntask; tk += BLOCK) {
+    const int r = tk / W, w = tk - r * W;
+    const unsigned long long *mr = amask + (size_t)(r + 1) * W;
+    if (mr[w] == 0ull) continue;                               // no popcount, no add: most words of most frames
+    const unsigned int c = (unsigned int)__popcll(centre_word(mr, w, W, gw));
+    if (c) atomicAdd(total, c);
+  }
+}
+// The centre words into cpl[0 .. nkeep), nkeep = crows * W, and the count.  Every word is written, the empty ones too.
+template <int BLOCK>
+__device__ __forceinline__ void centre_plane(const unsigned long long *amask, unsigned long long *cpl, unsigned int *total, int W,
+                                             int gw, int nkeep) {
+  for (int tk = threadIdx.x; tk < nkeep; tk += BLOCK) {
+    const int r = tk / W, w = tk - r * W;
+    const unsigned long long c = centre_word(amask + (size_t)(r + 1) * W, w, W, gw);
+    cpl[tk] = c;
+    if (c) atomicAdd(total, (unsigned int)__popcll(c));
+  }
 }
 
 }  // namespace mtgpu

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 namespace mtgpu {
 
@@ -129,9 +130,11 @@ inline hipError_t plan_work_list(const unsigned long long *frame_off, const unsi
   if (e != hipSuccess) return e;
   return ev_planned ? hipEventRecord(ev_planned, stream) : hipSuccess;
 }
-// The same from a launch block with the usual fields (ScanLaunch, SweepLaunch, ActLaunch, ZoneLaunch).
+// The same from a launch block.  Kept out of line, one copy per launch type whoever calls it: the library's symbol list
+// then does not depend on what the optimiser inlines into plan_and_launch below.
 template <class Launch>
-hipError_t plan_work_list(const Launch &L, unsigned char *flags, int sys_flags, unsigned int *centres, int sys_centres) {
+__attribute__((noinline)) hipError_t plan_work_list(const Launch &L, unsigned char *flags, int sys_flags, unsigned int *centres,
+                                                    int sys_centres) {
   return plan_work_list(L.frame_off, L.has_sd, L.n_records, L.rebase, L.n_frames, L.plan_ws, L.stream, L.ev_planned, flags,
                         sys_flags, centres, sys_centres);
 }
@@ -162,6 +165,56 @@ hipError_t launch_chunked(unsigned long long total, unsigned long long chunk, F 
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// The launch tail of a kernel over the work list: the LDS ceiling of `kern` raised once (`ready`: the static word of the
+// caller's instantiation, one per kernel instantiation), then `total` workgroups in chunks, launch(first, n) each.  The
+// functor owns the argument list: it may pass arguments one by one or patch one argument block per chunk.
+template <class Kern, class F>
+hipError_t launch_over_list(Kern kern, std::atomic<unsigned long long> &ready, const BatchLaunch &L, unsigned long long total,
+                            F launch) {
+  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
+  return e != hipSuccess ? e : launch_chunked(total, kGridChunk, launch);
+}
+
+// Blocks of 256 threads of a clear kernel over n elements (the kernels stride over what 1024 blocks leave).
+inline unsigned int clear_grid(unsigned long long n) {
+  const unsigned long long blocks = (n + 255ull) / 256ull;
+  return (unsigned int)(blocks < 1024ull ? blocks : 1024ull);
+}
+
+// ---- the rungs every launcher over a record batch has (false: hipErrorInvalidValue)
+inline bool check_batch_launch(const BatchLaunch &L) {
+  return L.frame_off && L.plan_ws && ((uintptr_t)L.plan_ws & 31u) == 0u && L.rebase <= L.n_records;
+}
+// k: a one-tile kernel's parameter block (R tracked rows serve the analysed rows [y_lo, y_hi)); lds_need: what its
+// layout takes for the block's grid.
+template <class K>
+bool check_rows(const K &k, int lds_bytes, int lds_max, size_t lds_need) {
+  return k.R >= 1 && k.y_hi >= k.y_lo && k.R >= k.y_hi - k.y_lo && lds_bytes <= lds_max && (size_t)lds_bytes >= lds_need;
+}
+
+// The tail of a derived scan's launcher, behind its rungs.  Pipe form: the planner is handed the outputs (flags, ONE
+// count array) and answers every frame without side data itself, at the outputs' scope, as in launch_scan: no clear
+// kernel — planning + one kernel.  Resident form: clear(grid blocks) launches the feature's clear kernel over the frames,
+// then the planner answers nothing (null outputs: they hold the clear's values already).  Then frames(rec, pipe)
+// launches the instantiation for them: rec the record's bytes, 8 or 40, and pipe the form, both as constants
+// (std::integral_constant), so the functor can hand them on as template arguments.
+template <class Launch, class Clear, class Frames>
+hipError_t plan_and_launch(const Launch &L, bool pipe, unsigned char *flags, int sys_flags, unsigned int *count, int sys_count,
+                           Clear clear, Frames frames) {
+  const std::integral_constant<int, 8> rec8{};
+  const std::integral_constant<int, 40> rec40{};
+  if (pipe) {
+    hipError_t e = plan_work_list(L, flags, sys_flags, count, sys_count);
+    if (e != hipSuccess) return e;
+    return L.rec_bytes == 8 ? frames(rec8, std::true_type{}) : frames(rec40, std::true_type{});
+  }
+  clear(clear_grid(L.n_frames));
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = plan_work_list(L, nullptr, 0, nullptr, 0);
+  if (e != hipSuccess) return e;
+  return L.rec_bytes == 8 ? frames(rec8, std::false_type{}) : frames(rec40, std::false_type{});
 }
 
 }  // namespace mtgpu

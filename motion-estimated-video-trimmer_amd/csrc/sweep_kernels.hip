@@ -168,12 +168,8 @@ __global__ __launch_bounds__(BLOCK) void sweep_frames_kernel(
   const Rows b = {max(k.y_lo - 1, 0), min(k.y_hi + 1, k.gh)};
 
   // ---- phase 0
-  {
-    u32x4 *c4 = reinterpret_cast<u32x4 *>(tiles);
-    const int n4 = (k.n_thr * k.tile_words) >> 2;
-    for (int i = tid; i < n4; i += BLOCK) c4[i] = (u32x4){0u, 0u, 0u, 0u};
-    if (tid < kSweepMaxThr * kSweepMaxVec) totals[tid] = 0u;
-  }
+  zero_tile<BLOCK>(tiles, k.n_thr * k.tile_words);
+  if (tid < kSweepMaxThr * kSweepMaxVec) totals[tid] = 0u;
   __syncthreads();
 
   // ---- phase 1 (an empty analysed range keeps nothing: nothing to read)
@@ -214,10 +210,8 @@ template <int REC, int NT>
 hipError_t launch_pass(const SweepLaunch &L, const SweepK &k) {
   auto kern = sweep_frames_kernel<kSweepBlock, kSweepUnroll, REC, NT>;
   static std::atomic<unsigned long long> ready{0ull};
-  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
-  if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
-  return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
+  return launch_over_list(kern, ready, L, L.n_frames, [&](unsigned long long i0, unsigned int n) {
     hipLaunchKernelGGL(kern, dim3(n), dim3(kSweepBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, k,
                        L.centres, L.n_frames);
   });
@@ -237,16 +231,13 @@ hipError_t launch_pass_nt(const SweepLaunch &L, const SweepK &k) {
 hipError_t launch_sweep_scan(const SweepLaunch &L) {
   if (L.n_frames == 0) return hipSuccess;
   if (L.rec_bytes != 40 && L.rec_bytes != 8) return hipErrorInvalidValue;
-  if (!L.centres || !L.frame_off || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u || L.rebase > L.n_records)
-    return hipErrorInvalidValue;
+  if (!L.centres || !check_batch_launch(L)) return hipErrorInvalidValue;
   if (L.n_thr_all < 1 || L.n_thr_all > kSweepMaxThr || L.k.n_vec < 1 || L.k.n_vec > kSweepMaxVec || L.thr_per_pass < 1 ||
       L.lds_bytes > L.lds_max)
     return hipErrorInvalidValue;
   {
     const unsigned long long n = (unsigned long long)L.n_thr_all * (unsigned long long)L.k.n_vec * L.n_frames;
-    const unsigned long long blocks = (n + 255ull) / 256ull;
-    hipLaunchKernelGGL(sweep_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream,
-                       L.centres, n, L.k.sys);
+    hipLaunchKernelGGL(sweep_clear_kernel, dim3(clear_grid(n)), dim3(256), 0, L.stream, L.centres, n, L.k.sys);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -45,27 +45,6 @@
 
 namespace mtgpu {
 
-namespace {
-
-// ---- the centres (:277-293), one task per (analysed row, word): analysed row r <-> mask row r + 1; x in [1, gw-2]
-// (:280); neighbours across word and row boundaries; outside the grid: inactive.  The sweep's count_centres with one
-// level.  Every neighbour, the carries included, comes from the plane handed in: on the masked plane an ignored cell
-// next to a word boundary carries nothing over.
-template <int BLOCK>
-__device__ __forceinline__ void count_centres(const unsigned long long *amask, unsigned int *total, const ZoneK &k, int crows) {
-  const int W = k.W;
-  const int ntask = crows * W;
-  for (int tk = threadIdx.x; tk < ntask; tk += BLOCK) {
-    const int r = tk / W, w = tk - r * W;
-    const unsigned long long *mr = amask + (size_t)(r + 1) * W;
-    if (mr[w] == 0ull) continue;                               // no popcount, no add: most words of most frames
-    const unsigned int c = (unsigned int)__popcll(centre_word(mr, w, W, k.gw));
-    if (c) atomicAdd(total, c);
-  }
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(256) void zones_clear_kernel(unsigned char *__restrict__ flags, unsigned int *__restrict__ centres,
                                                           unsigned int *__restrict__ centres_all, unsigned int n) {
   for (unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256ull) {
@@ -106,13 +85,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const unsigned int f = __builtin_amdgcn_readfirstlane(me.f);
   unsigned int s = 0u;
   if constexpr (!PIPE) {
-    unsigned int lo = 0u, hi = n_streams;
-    while (lo < hi) {
-      const unsigned int mid = lo + ((hi - lo) >> 1);
-      if (stream_off[mid + 1u] <= (unsigned long long)f) lo = mid + 1u; else hi = mid;
-    }
-    s = lo;
-    if (s >= n_streams) return;
+    s = stream_of(stream_off, n_streams, f);
+    if (s >= n_streams) return;                 // a frame in front of the first stream is not told apart: it takes plane 0
   }
 
   // ---- the keep words of the analysed rows, one contiguous block of the stream's plane.  The first word of every
@@ -120,13 +94,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   const unsigned long long *kp = keep + ((size_t)s * (size_t)k.gh + (size_t)k.y_lo) * (size_t)k.W;
   const int nkeep = crows * k.W;
   const unsigned long long k0 = tid < nkeep ? kp[tid] : 0ull;
-  // ---- zero the tile
-  {
-    u32x4 *c4 = reinterpret_cast<u32x4 *>(tile);
-    const int n4 = k.tile_words >> 2;
-    for (int j = tid; j < n4; j += BLOCK) c4[j] = (u32x4){0u, 0u, 0u, 0u};
-    if (tid < 4) total[tid] = 0u;
-  }
+  zero_tile<BLOCK>(tile, k.tile_words);
+  if (tid < 4) total[tid] = 0u;
   if (tid < nkeep) klds[tid] = k0;
   for (int j = tid + BLOCK; j < nkeep; j += BLOCK) klds[j] = kp[j];
   __syncthreads();
@@ -149,8 +118,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     if (uplane) uplane[(size_t)j * k.W + w] = m;
   });
   __syncthreads();
-  count_centres<BLOCK>(kmask, &total[0], k, crows);
-  if (want_all) count_centres<BLOCK>(umask, &total[1], k, crows);
+  count_centres<BLOCK>(kmask, &total[0], k.W, k.gw, crows);
+  if (want_all) count_centres<BLOCK>(umask, &total[1], k.W, k.gw, crows);
   __syncthreads();
   if (tid == 0) {
     const unsigned int c = total[0];
@@ -171,10 +140,8 @@ template <int REC, bool PIPE>
 hipError_t launch_frames(const ZoneLaunch &L) {
   auto kern = zones_frames_kernel<kZoneBlock, kZoneUnroll, REC, PIPE>;
   static std::atomic<unsigned long long> ready{0ull};
-  hipError_t e = raise_lds_limit_once(kern, ready, L.device, L.lds_max);
-  if (e != hipSuccess) return e;
   const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
-  return launch_chunked(L.n_frames, kGridChunk, [&](unsigned long long i0, unsigned int n) {
+  return launch_over_list(kern, ready, L, L.n_frames, [&](unsigned long long i0, unsigned int n) {
     hipLaunchKernelGGL(kern, dim3(n), dim3(kZoneBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.k,
                        L.stream_off, L.n_streams, L.keep, L.flags, L.centres, L.centres_all, L.sys_flags, L.sys_centres);
   });
@@ -188,30 +155,14 @@ hipError_t launch_zone_scan(const ZoneLaunch &L) {
   if (!L.flags && !L.centres && !L.centres_all) return hipErrorInvalidValue;
   if (L.pipe ? (L.centres_all != nullptr) : (L.sys_flags != 0 || L.sys_centres != 0 || !L.stream_off || L.n_streams == 0))
     return hipErrorInvalidValue;
-  if (!L.frame_off || !L.keep || !L.plan_ws || ((uintptr_t)L.plan_ws & 31u) != 0u ||
-      L.rebase > L.n_records)
+  if (!L.keep || !check_batch_launch(L) || !check_rows(L.k, L.lds_bytes, L.lds_max, zone_lds_bytes(L.k.gw, L.k.R)))
     return hipErrorInvalidValue;
-  if (L.k.R < 1 || L.k.y_hi < L.k.y_lo || L.k.R < L.k.y_hi - L.k.y_lo || L.lds_bytes > L.lds_max ||
-      (size_t)L.lds_bytes < zone_lds_bytes(L.k.gw, L.k.R))
-    return hipErrorInvalidValue;
-  if (L.pipe) {
-    // The planner is handed the outputs and answers every frame without side data itself (plan_scatter_kernel, at the
-    // outputs' scope), as in launch_scan: no clear kernel — planning + one kernel.
-    hipError_t e = plan_work_list(L, L.flags, L.sys_flags, L.centres, L.sys_centres);
-    if (e != hipSuccess) return e;
-    return L.rec_bytes == 8 ? launch_frames<8, true>(L) : launch_frames<40, true>(L);
-  }
-  {
-    const unsigned long long blocks = ((unsigned long long)L.n_frames + 255ull) / 256ull;
-    hipLaunchKernelGGL(zones_clear_kernel, dim3((unsigned int)(blocks < 1024ull ? blocks : 1024ull)), dim3(256), 0, L.stream,
-                       L.flags, L.centres, L.centres_all, L.n_frames);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  // flags / centres null: the planner answers nothing itself (the outputs are zero already)
-  hipError_t e = plan_work_list(L, nullptr, 0, nullptr, 0);
-  if (e != hipSuccess) return e;
-  return L.rec_bytes == 8 ? launch_frames<8, false>(L) : launch_frames<40, false>(L);
+  return plan_and_launch(
+      L, L.pipe, L.flags, L.sys_flags, L.centres, L.sys_centres,
+      [&](unsigned int grid) {
+        hipLaunchKernelGGL(zones_clear_kernel, dim3(grid), dim3(256), 0, L.stream, L.flags, L.centres, L.centres_all, L.n_frames);
+      },
+      [&](auto rec, auto pipe) { return launch_frames<rec(), pipe()>(L); });
 }
 
 }  // namespace mtgpu

@@ -1,6 +1,6 @@
 """Inputs of tests/test_gpu_blob_planes.py and tests/test_blob_planes_host.py: random and adversarial CENTRE PLANES for the
-three labelling kernels (csrc/blobs_kernels.hip in its resident and its pipe form, csrc/blob_label.h behind
-gmc_blobs_frames_kernel), built once per process and handed out read-only.
+three labelling kernels (csrc/blobs_kernels.hip in its resident and its pipe form, csrc/gmc_blobs_kernels.hip; the five
+passes of all three are the one text of csrc/blob_label.h), built once per process and handed out read-only.
 
 A plane is a bool [rows, gw] array of ACTIVE cells, a pure function of (gw, rows, seed).  `rows` is the number of
 analysed rows of the grid it is made for (grid_h - 2 * margin): batch() puts it on the rows margin .. grid_h - margin - 1,

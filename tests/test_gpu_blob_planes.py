@@ -1,6 +1,6 @@
 """GPU tier (`-m gpu`): the three labelling kernels on random and adversarial centre planes (tests/blob_planes.py) — the
-resident blob scan and its pipe form (both csrc/blobs_kernels.hip) and the compensated blob scan (csrc/blob_label.h behind
-gmc_blobs_frames_kernel) — against the flood-fill model (tests/blobs_model.py; tests/test_blob_planes_host.py holds it to
+resident blob scan and its pipe form (both csrc/blobs_kernels.hip) and the compensated blob scan
+(csrc/gmc_blobs_kernels.hip), all three on the ONE text of the five passes in csrc/blob_label.h — against the flood-fill model (tests/blobs_model.py; tests/test_blob_planes_host.py holds it to
 scipy on every plane).  This is where `unite`, the one place whose result depends on how the waves of a workgroup
 interleave, meets percolation clusters, mazes, combs, bars and ties.
 
@@ -102,7 +102,7 @@ def test_pipe_form(gpu_scanner_factory, name):
             assert run(pipe, frames) == (flags, centres.tolist()), (name, layout, "centres")
 
 
-# ------------------------------------------------------------------ 3. consequence A, and the two texts side by side
+# ------------------------------------------------------------------ 3. consequence A, and the two kernels side by side
 
 @pytest.mark.parametrize("name", bp.GPU_ORDER)
 def test_compensated_blob_scan_at_max_shift_0(gpu_scanner_factory, name):
@@ -118,7 +118,7 @@ def test_compensated_blob_scan_at_max_shift_0(gpu_scanner_factory, name):
         got = gmc_blob_scan(s, d_rec, d_off, d_sd, compact, d_soff, d_keep, 0)
         tb.assert_outputs(tb.to_host(ref), want, f"{name}, blob scan (blobs_kernels.hip), {layout_name(compact)}", b.p, 1)
         host = tg.to_host(got)
-        tg.assert_blobs(host, want, f"{name}, compensated blob scan at max_shift 0 (blob_label.h), {layout_name(compact)}", b.p, 1)
+        tg.assert_blobs(host, want, f"{name}, compensated blob scan at max_shift 0 (gmc_blobs_kernels.hip), {layout_name(compact)}", b.p, 1)
         assert not host["info"][:, :4].any(), name
         for k in tg.BLOB_OUTPUTS:
             assert ref[k].dtype == got[k].dtype and torch.equal(ref[k], got[k]), (name, layout_name(compact), k)
@@ -129,7 +129,7 @@ def test_compensated_blob_scan_at_max_shift_0(gpu_scanner_factory, name):
 @pytest.mark.parametrize("name", bp.GPU_ORDER)
 def test_compensated_blob_scan_under_a_pan(gpu_scanner_factory, name):
     """The batch under gmc_blobs_inputs.embed with the pan (9, -3), max_shift 16, min_share_q8 128: all six outputs are
-    gmc_blobs_inputs.model_batch's and info reports the pan on every frame with side data — blob_label.h's text on the
+    gmc_blobs_inputs.model_batch's and info reports the pan on every frame with side data — blob_label.h's passes on the
     residual plane, the same connectivity reached through the other kernel."""
     b, e, want = bp.batch(name), bp.embedded(name), bp.expected_embedded(name)
     assert e is not None
