@@ -497,6 +497,11 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * points, declared the same way. */
 #include "mtgpu_dir.h"
 
+/* Direction planes: the direction scan with one allow byte per grid cell, and the flow map — the counting records per
+ * stream, sector and cell — that such a plane is learned from (src/motion_scanner.cpp:262 gives every record a cell;
+ * the sector's test is decided there) — five more entry points, declared the same way. */
+#include "mtgpu_lanes.h"
+
 /* The direction filter on the decode path: a pipe whose submits run the direction scan, under its keep mask where it
  * has one, and report the centre count or the frame's sector word — two more entry points, declared the same way. */
 #include "mtgpu_pipe_dir.h"

@@ -7,11 +7,11 @@ from . import config, mvfile, mvjson
 from ._abi import (COMPACT_DTYPE, GMC_INFO_DTYPE, LAYOUT_AOS40, LAYOUT_BOXES, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, LIB_PATH, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE, MV_DTYPE, SEGMENT_DTYPE,
                    MtgpuError, load_library)
 from .scanner import (FrameBatch, activity_preview, blobs_preview, dir_preview, MergeParams, MotionScanner, ScanParams, ScanPipe, concat_list, filter_frames,
-                      frame_skip, gmc_blobs_preview, gmc_preview, make_chunks, pack_records, persist_preview, plan_preview, results_from_bytes, sweep_preview, zones_preview)
+                      frame_skip, gmc_blobs_preview, gmc_preview, lanes_preview, make_chunks, pack_records, persist_preview, plan_preview, results_from_bytes, sweep_preview, zones_preview)
 
 __all__ = ["config", "mvfile", "mvjson", "LIB_PATH", "COMPACT_DTYPE", "LAYOUT_AOS40", "LAYOUT_BOXES", "LAYOUT_CENTRES", "LAYOUT_COMPACT8", "LAYOUT_ZERO_COPY",
            "pack_records", "plan_preview", "MV_DTYPE", "SEGMENT_DTYPE", "MERGE_PARAMS_DTYPE",
            "MERGE_RESULT_DTYPE", "MtgpuError", "load_library", "FrameBatch", "MergeParams",
            "MotionScanner", "ScanParams", "ScanPipe", "concat_list", "filter_frames", "frame_skip", "make_chunks",
            "results_from_bytes", "sweep_preview", "activity_preview", "zones_preview", "blobs_preview", "gmc_preview", "GMC_INFO_DTYPE",
-           "gmc_blobs_preview", "persist_preview", "dir_preview"]
+           "gmc_blobs_preview", "persist_preview", "dir_preview", "lanes_preview"]

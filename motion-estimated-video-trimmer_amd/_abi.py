@@ -107,6 +107,10 @@ class DirPlanC(C.Structure):
     _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("sectors", C.c_int32), ("rose_bytes", C.c_int32)]
 
 
+class LanesPlanC(C.Structure):
+    _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("staged", C.c_int32), ("plane_bytes", C.c_int32)]
+
+
 class CtxStatsC(C.Structure):
     _fields_ = [("staging_device_bytes", C.c_uint64), ("pool_reserved_bytes", C.c_uint64),
                 ("pool_reserved_high", C.c_uint64), ("hip_streams", C.c_uint32), ("private_pool", C.c_uint32)]
@@ -310,6 +314,18 @@ ABI_PIPE_DIR = {
 }
 MT_PIPE_REPORT_SECTORS = 3
 
+# name -> (restype, argtypes): every symbol include/mtgpu_lanes.h declares (direction planes and flow maps; mtgpu.h includes it).
+ABI_LANES = {
+    "mtgpu_lanes_preview": (C.c_int, [C.POINTER(ScanParamsC), C.c_int, C.POINTER(LanesPlanC)]),
+    "mtgpu_scan_lanes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtgpu_scan_frames_lanes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtgpu_flow_map_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mtgpu_flow_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -343,7 +359,7 @@ def load_library(path=None):
             list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
             list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()) + list(ABI_GMC_BLOBS.items()) + \
             list(ABI_PIPE_GMC_BLOBS.items()) + list(ABI_PERSIST.items()) + list(ABI_PIPE_BOXES.items()) + \
-            list(ABI_DIR.items()) + list(ABI_PIPE_DIR.items()):
+            list(ABI_DIR.items()) + list(ABI_PIPE_DIR.items()) + list(ABI_LANES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -30,6 +30,7 @@
 #include "gmc_blobs_kernels.h"
 #include "persist_kernels.h"
 #include "dir_kernels.h"
+#include "lanes_kernels.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -2386,6 +2387,185 @@ int mtgpu_scan_frames_dir(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_o
   MT_TRY(sg.upload());
   MT_TRY(dir_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff), n_streams,
                 sg.at<const uint8_t>(i_allow), allow, sg.at<uint8_t>(o_fl), sg.at<uint32_t>(o_cen), sg.at<mt_dir_rose>(o_rose), sg.st));
+  return sg.download();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- direction planes (src/motion_scanner.cpp:242-292 per
+// frame, the vote only for records whose sector the destination cell's byte allows; the flow map: the counting records
+// per stream, sector and cell; include/mtgpu_lanes.h)
+
+namespace {
+
+// Two forms: the direction scan's LDS with the plane's analysed rows behind it, or without them.  The direction scan's
+// part fits or the grid is unsupported.
+int lanes_plan(const mt_scan_params &p, int lds_max, mtgpu_lanes_plan *out) {
+  const int R = analysed_rows(p);
+  const long long base = (long long)mtgpu::lanes_lds_bytes(p.grid_w, R, false);
+  const long long with_rows = (long long)mtgpu::lanes_lds_bytes(p.grid_w, R, true);
+  if (base > (long long)lds_max)
+    return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows, one mask plane and the rose "
+                "(%lld bytes) do not fit %d bytes of LDS; the plane scan has no banded form", p.grid_w, p.grid_h, R + 2, base, lds_max);
+  out->staged = with_rows <= (long long)lds_max ? 1 : 0;
+  out->lds_bytes = (int32_t)(out->staged ? with_rows : base);
+  out->workgroup = mtgpu::kLanesBlock;
+  out->plane_bytes = (int32_t)((long long)p.grid_w * (long long)p.grid_h);
+  return MT_OK;
+}
+
+// What the arguments of a plane scan decide alone (`d`: "d_" for the device entry point, "" for the host one): no
+// context, no device.  mtgpu_dir.h's ladder with the planes in the place of the allow bytes.
+int lanes_check_args(const char *d, int rec_bytes, const void *rec, const void *frame_off, uint32_t n_frames, const void *stream_off,
+                     uint32_t n_streams, const void *planes, const void *flags, const void *centres, const void *rose) {
+  if (!planes) return fail(MT_ERR_INVALID, "%splanes is NULL", d);
+  MT_TRY(check_rec_bytes(rec_bytes));
+  MT_TRY(check_any_output(d, {{"flags", flags}, {"centres", centres}, {"rose", rose}}));
+  if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "%sframe_off is NULL", d);
+  // per-stream planes come with the stream table, one plane for every frame without it
+  if (stream_off && n_streams == 0) return fail(MT_ERR_INVALID, "%sstream_off is given and n_streams is 0", d);
+  if (!stream_off && n_streams != 0) return fail(MT_ERR_INVALID, "n_streams is %u and %sstream_off is NULL", n_streams, d);
+  MT_TRY(check_aligned(d, {{"frame_off", frame_off, 8}, {"stream_off", stream_off, 8}}));
+  MT_TRY(check_rec(d, rec_bytes, rec));
+  return check_aligned(d, {{"centres", centres, 4}, {"rose", rose, 4}});
+}
+
+// ... and of a flow-map call.
+int flow_check_args(const char *d, int rec_bytes, const void *rec, const void *frame_off, uint32_t n_frames, const void *stream_off,
+                    const void *flow) {
+  if (!flow) return fail(MT_ERR_INVALID, "%sflow is NULL", d);
+  MT_TRY(check_rec_bytes(rec_bytes));
+  if (!stream_off) return fail(MT_ERR_INVALID, "%sstream_off is NULL", d);
+  if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "%sframe_off is NULL", d);
+  MT_TRY(check_aligned(d, {{"frame_off", frame_off, 8}, {"stream_off", stream_off, 8}}));
+  MT_TRY(check_rec(d, rec_bytes, rec));
+  return check_aligned(d, {{"flow", flow, 4}});
+}
+
+// The plane scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
+int lanes_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
+             const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, const uint8_t *d_planes,
+             uint8_t *d_flags, uint32_t *d_centres, mt_dir_rose *d_rose, hipStream_t st) {
+  mtgpu_lanes_plan lp;
+  MT_TRY(lanes_plan(c->params, c->lds_max, &lp));
+  mtgpu::LanesLaunch L;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, lp.lds_bytes, st);
+  L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
+  L.n_streams = n_streams;
+  L.planes = d_planes;
+  L.flags = d_flags; L.centres = d_centres; L.rose = reinterpret_cast<unsigned int *>(d_rose);
+  L.staged = lp.staged;
+  fill_tile(L.k, c->k, mtgpu::dir_tile_words);
+  L.k.clust_need = c->k.clust_need;
+  PlanWs ws(c, st, nullptr, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_lanes_scan, "plane scan launch");
+}
+
+// The flow map of a device-resident batch on `st`.  The arguments have been validated; n_streams > 0.
+int flow_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
+            const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, uint32_t *d_flow,
+            hipStream_t st) {
+  mtgpu::FlowLaunch L;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, 0, st);
+  L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
+  L.n_streams = n_streams;
+  L.flow = d_flow;
+  fill_tile(L.k, c->k, mtgpu::dir_tile_words);
+  if (n_frames == 0) {                                         // only the clear
+    const hipError_t e = mtgpu::launch_flow_map(L);
+    return e == hipSuccess ? MT_OK : hip_fail(e, "flow map launch");
+  }
+  PlanWs ws(c, st, nullptr, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_flow_map, "flow map launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtgpu_lanes_preview(const mt_scan_params *p, int lds_bytes_per_workgroup, mtgpu_lanes_plan *out) {
+  return preview(p, lds_bytes_per_workgroup, out, lanes_plan);
+}
+
+int mtgpu_scan_lanes_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
+                            const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
+                            const uint8_t *d_planes, uint8_t *d_flags, uint32_t *d_centres, mt_dir_rose *d_rose, void *stream) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  MT_TRY(lanes_check_args("d_", rec_bytes, d_rec, d_frame_off, n_frames, d_stream_off, n_streams, d_planes, d_flags, d_centres, d_rose));
+  if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  MT_TRY(plan_ok(c, lanes_plan));                            // a grid without a form: before any HIP call
+  if (n_frames == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  MT_TRY(check_on_device(c, {{"d_flags", d_flags}, {"d_centres", d_centres}, {"d_rose", d_rose}}));
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
+  return lanes_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_planes, d_flags,
+                  d_centres, d_rose, static_cast<hipStream_t>(stream));
+}
+
+int mtgpu_scan_frames_lanes(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
+                            const uint64_t *stream_off, uint32_t n_streams, const uint8_t *planes, uint8_t *flags, uint32_t *centres,
+                            mt_dir_rose *rose) {
+  MT_TRY(lanes_check_args("", MT_MV_BYTES, mv, frame_off, n_frames, stream_off, n_streams, planes, flags, centres, rose));
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  if (stream_off) MT_TRY(check_stream_off(stream_off, n_streams, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  MT_TRY(plan_ok(c, lanes_plan));                            // a grid without a form: before anything is staged
+  if (n_frames == 0) return MT_OK;
+
+  // (with one plane for every frame stream_off is null: no room, a null device pointer)
+  const size_t plane = (size_t)c->k.gh * (size_t)c->k.gw;
+  Staged sg(c, c->d_misc, false, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int i_soff = sg.in(stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1));
+  const int i_pl = sg.in(planes, plane * (stream_off ? (size_t)n_streams : 1u));
+  const int o_fl = sg.out(flags, n_frames), o_cen = sg.out(centres, sizeof(uint32_t) * (size_t)n_frames);
+  const int o_rose = sg.out(rose, sizeof(mt_dir_rose) * (size_t)n_frames);
+  MT_TRY(sg.upload());
+  MT_TRY(lanes_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff), n_streams,
+                  sg.at<const uint8_t>(i_pl), sg.at<uint8_t>(o_fl), sg.at<uint32_t>(o_cen), sg.at<mt_dir_rose>(o_rose), sg.st));
+  return sg.download();
+}
+
+int mtgpu_flow_map_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
+                          const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
+                          uint32_t *d_flow, void *stream) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  MT_TRY(flow_check_args("d_", rec_bytes, d_rec, d_frame_off, n_frames, d_stream_off, d_flow));
+  if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  MT_TRY(plan_ok(c, lanes_plan));                            // a grid without a form: before any HIP call
+  if (n_streams == 0) return MT_OK;                          // no stream owns an output element
+  HIP_TRY(hipSetDevice(c->device));
+  MT_TRY(check_on_device(c, {{"d_flow", d_flow}}, " (global atomics)"));
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
+  return flow_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_flow,
+                 static_cast<hipStream_t>(stream));
+}
+
+int mtgpu_flow_map(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
+                   const uint64_t *stream_off, uint32_t n_streams, uint32_t *flow) {
+  MT_TRY(flow_check_args("", MT_MV_BYTES, mv, frame_off, n_frames, stream_off, flow));
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  MT_TRY(check_stream_off(stream_off, n_streams, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  MT_TRY(plan_ok(c, lanes_plan));                            // a grid without a form: before anything is staged
+  if (n_streams == 0) return MT_OK;
+
+  const size_t words = (size_t)n_streams * 8u * (size_t)c->k.gh * (size_t)c->k.gw;
+  Staged sg(c, c->d_misc, false, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int i_soff = sg.in(stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1));
+  const int o_flow = sg.out(flow, sizeof(uint32_t) * words);
+  MT_TRY(sg.upload());
+  MT_TRY(flow_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff), n_streams,
+                 sg.at<uint32_t>(o_flow), sg.st));
   return sg.download();
 }
 

@@ -20,7 +20,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi, config
-from ._abi import (BLOB_BOX_DTYPE, BlobsPlanC, COMPACT_DTYPE, DIR_ALL, DirPlanC, LAYOUT_AOS40, LAYOUT_BOXES, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
+from ._abi import (BLOB_BOX_DTYPE, BlobsPlanC, COMPACT_DTYPE, DIR_ALL, DirPlanC, LanesPlanC, LAYOUT_AOS40, LAYOUT_BOXES, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
                    GMC_DEFAULT_MAX_SHIFT, GMC_DEFAULT_MIN_SHARE_Q8, GMC_INFO_DTYPE, GmcBlobsPlanC, GmcPlanC,
                    MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PersistPlanC, PlanC, ScanParamsC, SweepPlanC, ZonesPlanC, check,
                    load_library)
@@ -254,6 +254,17 @@ def dir_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     c = params.to_c()
     check(load_library().mtgpu_dir_preview(C.byref(c), int(lds_bytes), C.byref(p)))
     return {n: getattr(p, n) for n, _ in DirPlanC._fields_}
+
+
+def lanes_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
+    """How the plane scan runs on the grid of `params` with that much LDS per workgroup (mtgpu_lanes_preview): LDS bytes,
+    lanes, staged (1: the plane's analysed rows are held in LDS, 0: read from memory), bytes of one plane (gw * gh).
+    Host arithmetic only: works without a GPU.  MtgpuError(MT_ERR_UNSUPPORTED) for a grid the plane scan has no form
+    for."""
+    p = LanesPlanC()
+    c = params.to_c()
+    check(load_library().mtgpu_lanes_preview(C.byref(c), int(lds_bytes), C.byref(p)))
+    return {n: getattr(p, n) for n, _ in LanesPlanC._fields_}
 
 
 def persist_preview() -> dict:
@@ -750,6 +761,124 @@ class MotionScanner:
             None if d_sd is None else d_sd.data_ptr(), n_frames, ptr(d_stream_off), ns, ptr(d_allow), int(allow),
             *(ptr(res[k]) for k in DIR_OUTPUTS), st))
         return res
+
+    # -------------------------------------------------------- direction planes and flow maps
+    def _planes(self, planes, n_streams):
+        """uint8 [S, gh, gw] (n_streams given) or [gh, gw] (n_streams None: one plane for every frame), contiguous."""
+        gh, gw = self.params.grid_h, self.params.grid_w
+        planes = np.ascontiguousarray(planes, dtype=np.uint8)
+        want = (gh, gw) if n_streams is None else (n_streams, gh, gw)
+        if planes.shape != want:
+            raise ValueError(f"planes has shape {planes.shape}, not {want}")
+        return planes
+
+    def scan_lanes(self, batch: FrameBatch, planes, stream_off=None) -> dict:
+        """The centre scan of a host batch in which a record votes only if the allow byte of its destination cell lets
+        its sector vote (mtgpu_scan_frames_lanes), and every frame's rose.  planes: uint8 [gh, gw], one plane for every
+        frame; or, with stream_off (S + 1 frame offsets), uint8 [S, gh, gw], one plane per stream (lanes.plane_from_rects,
+        lanes.plane_from_flow).  Returns a dict of numpy arrays over the frames: flags uint8, centres uint32, rose uint32
+        [F, 8]: the counting records per sector, whatever the planes say."""
+        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
+        n = max(len(off) - 1, 0)
+        soff, ns = None, 0
+        if stream_off is not None:
+            soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
+            ns = max(len(soff) - 1, 0)
+            if ns == 0:
+                raise ValueError("stream_off: at least one stream wanted (or None: one plane for every frame)")
+        planes = self._planes(planes, None if soff is None else ns)
+        out = {"flags": np.zeros(n, dtype=np.uint8), "centres": np.zeros(n, dtype=np.uint32), "rose": np.zeros((n, 8), dtype=np.uint32)}
+        check(self._lib.mtgpu_scan_frames_lanes(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, _ptr(soff), ns,
+                                                _ptr(planes), *(_ptr(out[k]) for k in DIR_OUTPUTS)))
+        return out
+
+    def scan_lanes_device(self, d_rec, d_off, d_sd, d_planes, d_stream_off=None, compact=False, want=DIR_OUTPUTS, out=None,
+                          stream=None) -> dict:
+        """Device-resident batch (torch CUDA tensors) -> a dict of CUDA tensors over the frames: flags uint8, centres int32
+        and rose int32 [F, 8] (the bits of the library's uint32 counts); None for an output not in `want`.  d_rec: the
+        packed 40-byte records, or the 8-byte compact ones with compact=True; d_off int64 [F + 1]; d_sd uint8 [F] or
+        None; d_planes uint8: gh x gw bytes, or S x gh x gw with d_stream_off int64 [S + 1] — a contiguous tensor at any
+        byte address.  out: a dict of preallocated tensors by name.  Asynchronous on `stream` (default: torch's current
+        stream)."""
+        import torch
+        want = tuple(want)
+        for w in want:
+            if w not in DIR_OUTPUTS:
+                raise ValueError(f"want: {w!r} is not one of {DIR_OUTPUTS}")
+        dev = d_off.device
+        n_frames = max(d_off.numel() - 1, 0)
+        res = {}
+        for name in DIR_OUTPUTS:
+            if name not in want:
+                res[name] = None
+                continue
+            dtype = torch.uint8 if name == "flags" else torch.int32
+            shape = (n_frames, 8) if name == "rose" else (n_frames,)
+            t = (out or {}).get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, name
+            res[name] = t
+        if n_frames == 0:              # nothing to write (an empty tensor has no address to hand over)
+            return res
+        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_off.dtype == torch.int64
+        ns = 0
+        if d_stream_off is not None:
+            ns = max(d_stream_off.numel() - 1, 0)
+            assert d_stream_off.is_contiguous() and d_stream_off.dtype == torch.int64 and ns > 0
+        assert d_planes.is_contiguous() and d_planes.dtype == torch.uint8
+        assert d_planes.numel() == max(ns, 1) * self.params.grid_h * self.params.grid_w
+        rec_bytes = 8 if compact else 40
+        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
+        check(self._lib.mtgpu_scan_lanes_device(
+            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
+            None if d_sd is None else d_sd.data_ptr(), n_frames, ptr(d_stream_off), ns, d_planes.data_ptr(),
+            *(ptr(res[k]) for k in DIR_OUTPUTS), st))
+        return res
+
+    def flow_map(self, batch: FrameBatch, stream_off) -> np.ndarray:
+        """The flow map of a host batch (mtgpu_flow_map): uint32 [S, 8, gh, gw] — per stream, sector (0 = E, clockwise on
+        the screen) and grid cell, the counting records with that sector and destination cell over the stream's frames
+        with side data.  stream_off: S + 1 frame offsets.  Maps of successive batches add."""
+        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
+        soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
+        n, ns = max(len(off) - 1, 0), max(len(soff) - 1, 0)
+        flow = np.zeros((ns, 8, self.params.grid_h, self.params.grid_w), dtype=np.uint32)
+        if ns == 0:
+            return flow
+        check(self._lib.mtgpu_flow_map(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, _ptr(soff), ns, _ptr(flow)))
+        return flow
+
+    def flow_map_device(self, d_rec, d_off, d_sd, d_stream_off, compact=False, out=None, stream=None):
+        """Device-resident batch (torch CUDA tensors) -> the flow map, an int32 [S, 8, gh, gw] CUDA tensor (the bits of the
+        library's uint32 counts).  d_rec / d_off / d_sd as scan_lanes_device; d_stream_off int64 [S + 1].  out: a
+        preallocated tensor; it is cleared, then counted into.  Asynchronous on `stream` (default: torch's current
+        stream)."""
+        import torch
+        dev = d_off.device
+        n_frames = max(d_off.numel() - 1, 0)
+        ns = max(d_stream_off.numel() - 1, 0)
+        shape = (ns, 8, self.params.grid_h, self.params.grid_w)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=dev)
+        assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == shape
+        if ns == 0:
+            return out
+        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_stream_off.is_contiguous()
+        assert d_off.dtype == torch.int64 and d_stream_off.dtype == torch.int64
+        rec_bytes = 8 if compact else 40
+        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        check(self._lib.mtgpu_flow_map_device(
+            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
+            None if d_sd is None else d_sd.data_ptr(), n_frames, d_stream_off.data_ptr(), ns, out.data_ptr(), st))
+        return out
 
     # -------------------------------------------------------- global-motion compensation
     def scan_gmc(self, batch: FrameBatch, max_shift: int = GMC_DEFAULT_MAX_SHIFT, min_share_q8: int = GMC_DEFAULT_MIN_SHARE_Q8):
