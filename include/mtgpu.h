@@ -506,6 +506,11 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * has one, and report the centre count or the frame's sector word — two more entry points, declared the same way. */
 #include "mtgpu_pipe_dir.h"
 
+/* Direction planes on the decode path: a pipe whose submits run the plane scan — one allow byte per grid cell — under
+ * its keep mask where it has one, and report the centre count or the frame's sector word — two more entry points,
+ * declared the same way. */
+#include "mtgpu_pipe_lanes.h"
+
 /* Temporal persistence: the runs of consecutive motion frames per stream — across the key frames that were never
  * analysed, with a bounded dropout and, given the blob boxes, only while the object stays in place — and every frame's
  * run length and place in its run (the frames src/motion_scanner.cpp:382-383 pools, before src/pipeline.cpp:328-344

@@ -46,7 +46,8 @@
  *  G. For every stream and every k, the sum of flow[s][k] over its cells equals the sum of rose[f].n[k] over its frames.
  *     The flow map depends on neither the launch grid nor the order in which workgroups arrive.
  *
- * Out of scope: the pipe, the C++ host layer and mtgpu_scan_file; planes next to keep masks, blobs or compensation; a
+ * Out of scope: the pipe, the C++ host layer and mtgpu_scan_file (these, with the pipe's keep mask, are in
+ * mtgpu_pipe_lanes.h); planes next to keep masks on a resident batch, blobs or compensation; a
  * min_centres filter on the flow map; the row-banded grids (960x540 cells, 32767-wide grids: the class every sibling
  * rejects), which are MT_ERR_UNSUPPORTED with the grid named.
  *

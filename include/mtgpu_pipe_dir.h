@@ -52,7 +52,7 @@
  * stays with mtgpu_scan_dir_device.
  *
  * Out of scope: a full mt_dir_rose array through the pipe (a layout bit of its own, as MT_LAYOUT_BOXES was); per-stream
- * allow bytes on a pipe and a per-cell allow plane; direction together with blobs, compensation or the compensated blob
+ * allow bytes on a pipe; a per-cell allow plane (that one is in mtgpu_pipe_lanes.h); direction together with blobs, compensation or the compensated blob
  * scan — the setters refuse each other (MT_ERR_UNSUPPORTED, "not together yet"); a keep argument on the resident
  * mtgpu_scan_dir_device; the row-banded grids.
  *

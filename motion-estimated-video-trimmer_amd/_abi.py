@@ -326,6 +326,12 @@ ABI_LANES = {
     "mtgpu_flow_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_pipe_lanes.h declares (the direction plane of a pipe; mtgpu.h includes it).
+ABI_PIPE_LANES = {
+    "mtgpu_pipe_set_plane": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "mtgpu_pipe_plane": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+}
+
 _lib = None
 
 
@@ -359,7 +365,8 @@ def load_library(path=None):
             list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
             list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()) + list(ABI_GMC_BLOBS.items()) + \
             list(ABI_PIPE_GMC_BLOBS.items()) + list(ABI_PERSIST.items()) + list(ABI_PIPE_BOXES.items()) + \
-            list(ABI_DIR.items()) + list(ABI_PIPE_DIR.items()) + list(ABI_LANES.items()):
+            list(ABI_DIR.items()) + list(ABI_PIPE_DIR.items()) + list(ABI_LANES.items()) + \
+            list(ABI_PIPE_LANES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

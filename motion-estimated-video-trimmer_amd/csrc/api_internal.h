@@ -88,6 +88,22 @@ int ctx_launch_dir(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const ui
 // MT_OK when the direction scan has a form for the context's grid; MT_ERR_UNSUPPORTED (the grid is named) as
 // mtgpu_dir_preview otherwise.  No HIP call.
 int ctx_dir_supported(const mtgpu_ctx *c);
+// Launch the plane scan (lanes_kernels.hip, the pipe form) for a pipe's staging batch on `st`: as ctx_launch_dir, with
+// d_plane = ONE direction plane (gh * gw bytes, include/mtgpu_lanes.h) in device memory in the place of the allow byte: a
+// record's byte is the one of its destination cell.  d_count receives the sector word of include/mtgpu_pipe_lanes.h when
+// report_sectors (d_count is then required), else the frame's centre count.  d_keep = ONE keep plane in device memory or
+// nullptr.  plan_ws / plan_ws_bytes are REQUIRED (the batch's own block): nothing is taken from the context's scratch
+// ring.  outputs_in_host_memory: as ctx_launch_dir.  With mtgpu_profile_enable on it records the same event triple as
+// ctx_launch_scan.  MT_ERR_UNSUPPORTED as mtgpu_lanes_preview.
+int ctx_launch_lanes(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
+                     uint32_t n_frames, const uint64_t *d_keep, const uint8_t *d_plane, int report_sectors, uint8_t *d_flags,
+                     uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
+                     size_t plan_ws_bytes);
+// MT_OK when the plane scan has a form for the context's grid; MT_ERR_UNSUPPORTED (the grid is named) as
+// mtgpu_lanes_preview otherwise.  No HIP call.
+int ctx_lanes_supported(const mtgpu_ctx *c);
+// *bytes = bytes of one direction plane (gh * gw) of the context's grid; MT_ERR_UNSUPPORTED as ctx_lanes_supported.
+int ctx_lanes_plane_bytes(const mtgpu_ctx *c, uint64_t *bytes);
 // Launch the compensated blob scan (gmc_blobs_kernels.hip, the pipe form) for a pipe's staging batch on `st`: as
 // ctx_launch_gmc, with min_blob_cells >= 1 (flags = centres >= max(1, clusters_needed) AND largest >= min_blob_cells) and
 // `report` (MT_PIPE_REPORT_CENTRES / _LARGEST / _VECTOR) choosing what d_count, the batch's ONE count array or nullptr,

@@ -561,6 +561,66 @@ inline bool load_keep(const std::string &path, int gw, int gh, std::vector<uint6
   return true;
 }
 
+// ---------------------------------------------------------------- direction planes
+// A `.mtdir` file: the direction plane of include/mtgpu_lanes.h as text a user can edit (python -m mvtrim_amd.lanes
+// --learn --save-plane x.mtdir writes it).  Line 1 `mtdir 1`; line 2 `<grid_w> <grid_h>`; then grid_h lines of grid_w
+// two-digit hex bytes without separators, bit k of a byte = sector k may vote in that cell (0 = E, clockwise on the
+// screen).  load_plane parses `path` for a gw x gh grid into gh * gw bytes, row-major — what GpuMotionScanner::set_plane
+// and mtgpu_pipe_set_plane take — with exactly the strictness of lanes.load_plane.  CRLF line ends are accepted.  false,
+// with the line named in `err`: another first line, a grid that is not gw x gh, a short file, a row of another length, a
+// character that is no hex digit, text behind the last row.  `bytes` is left empty then.
+inline bool load_plane(const std::string &path, int gw, int gh, std::vector<uint8_t> &bytes, std::string &err) {
+  bytes.clear();
+  std::ifstream in(path, std::ios::binary);
+  if (!in) { err = path + ": cannot open"; return false; }
+  std::string text((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+  std::vector<std::string> lines;
+  for (size_t at = 0; at < text.size();) {
+    size_t nl = text.find('\n', at);
+    if (nl == std::string::npos) nl = text.size();
+    std::string ln = text.substr(at, nl - at);
+    if (!ln.empty() && ln.back() == '\r') ln.pop_back();
+    lines.push_back(std::move(ln));
+    at = nl + 1;
+  }
+  auto bad = [&](size_t line, const std::string &what) { err = path + ": line " + std::to_string(line) + ": " + what; bytes.clear(); return false; };
+  if (lines.empty() || lines[0] != "mtdir 1") return bad(1, "want 'mtdir 1'");
+  long fw = -1, fh = -1;
+  if (lines.size() > 1) {
+    const std::string &d = lines[1];
+    const size_t sp = d.find(' ');
+    auto number = [](const std::string &t) -> long {
+      if (t.empty() || t.size() > 6) return -1;
+      long v = 0;
+      for (char ch : t) { if (ch < '0' || ch > '9') return -1; v = v * 10 + (ch - '0'); }
+      return v;
+    };
+    if (sp != std::string::npos) { fw = number(d.substr(0, sp)); fh = number(d.substr(sp + 1)); }
+  }
+  if (fw < 1 || fh < 1) return bad(2, "want '<grid_w> <grid_h>'");
+  if (gw < 1 || gh < 1 || fw != gw || fh != gh)
+    return bad(2, "the plane is for a " + std::to_string(fw) + "x" + std::to_string(fh) + " grid, this one is " + std::to_string(gw) + "x" + std::to_string(gh));
+  auto hex = [](char ch) -> int {
+    if (ch >= '0' && ch <= '9') return ch - '0';
+    if (ch >= 'a' && ch <= 'f') return ch - 'a' + 10;
+    if (ch >= 'A' && ch <= 'F') return ch - 'A' + 10;
+    return -1;
+  };
+  bytes.assign((size_t)gh * (size_t)gw, 0);
+  for (size_t y = 0; y < (size_t)gh; ++y) {
+    const size_t n = 3 + y;
+    if (n > lines.size()) return bad(n, "the file ends after " + std::to_string(y) + " of " + std::to_string(gh) + " rows");
+    const std::string &row = lines[n - 1];
+    if (row.size() != 2 * (size_t)gw)
+      return bad(n, std::to_string(row.size()) + " characters, want " + std::to_string(2 * gw) + " (" + std::to_string(gw) + " two-digit hex bytes)");
+    for (size_t x = 0; x < row.size(); ++x)
+      if (hex(row[x]) < 0) return bad(n, "character " + std::to_string(x + 1) + " is no hex digit");
+    for (size_t x = 0; x < (size_t)gw; ++x) bytes[y * (size_t)gw + x] = (uint8_t)(hex(row[2 * x]) * 16 + hex(row[2 * x + 1]));
+  }
+  if (lines.size() > 2 + (size_t)gh) return bad(3 + (size_t)gh, "text behind the last of " + std::to_string(gh) + " rows");
+  return true;
+}
+
 // ---------------------------------------------------------------- scanner
 // The GPU side of one worker: a scan context (cfg + launch plan) and its pinned pipe.  Kept
 // separate from the decoder-facing scanner so that a batch worker can reuse it for the next
@@ -745,6 +805,7 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   int gmc_blob_report_ = MT_PIPE_REPORT_CENTRES;       // report_gmc_blobs(): what last_centres() holds in pair mode
   int dir_allow_ = -1;                                 // set_dir(): the pipe's direction mode, the allow byte; -1: off
   bool report_sectors_ = false;                        // report_sectors(): last_centres() holds the frames' sector words
+  std::vector<uint8_t> plane_;                         // set_plane(): the direction plane initialize() hands to the pipe; empty: none
   bool trace_on_ = false;                              // set_persist(min_run >= 1): scan_range keeps a trace of every fed frame
   int persist_reach_ = -1;                             // set_persist(): >= 0: the pipe carries boxes (MT_LAYOUT_BOXES)
   std::vector<TraceEntry> last_trace_;
@@ -905,6 +966,13 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   // next video's setting because of the previous one's.
   void set_dir(int allow) { dir_allow_ = allow; }
   void report_sectors(bool on) { report_sectors_ = on; }
+  // Call before initialize().  The direction plane of this video (include/mtgpu_pipe_lanes.h: gh * gw bytes, load_plane's
+  // result): in every check_frame of scan_range (:375-383) a record votes only if its DESTINATION CELL's byte has the bit
+  // of its sector; the active plane honours set_keep.  Empty: off.  report_sectors(true) works with a plane as with
+  // set_dir's byte.  Not together with set_dir (one rule at two granularities), set_min_blob_cells(n > 0),
+  // report_largest, set_gmc(>= 0), report_vector or set_gmc_blobs.  initialize() ALWAYS settles the pipe's plane — off
+  // first, on again last if asked: the next video never inherits the previous one's lanes.
+  void set_plane(const std::vector<uint8_t> &plane) { plane_ = plane; }
   // Call before initialize().  Temporal persistence for this video (include/mtgpu_persist.h).  A run of motion frames
   // crosses batch and chunk borders and the chunks of a recording are scanned by several workers in any order, so the
   // scanner does NOT apply the rule: it keeps what ONE mtgpu_persist_flags call per recording needs (run_scan_pipeline
@@ -951,7 +1019,8 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
       return false;
     pipe_ = be_->pipe();
     // the pipe is idle here (a previous scanner on this backend left nothing in flight, or the backend was rebuilt)
-    // direction off first: a pooled pipe that carries it would refuse every other mode below
+    // the plane off first, then direction: a pooled pipe that carries either would refuse every other mode below
+    if (mtgpu_pipe_set_plane(pipe_, nullptr, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
     if (mtgpu_pipe_set_dir(pipe_, 0, 0, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
     // the pair off first: a pooled pipe that carries it would refuse both single settings below
     if (mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
@@ -1022,7 +1091,7 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
         return false;
       }
     }
-    if (dir_allow_ != -1 || report_sectors_) {
+    if (dir_allow_ != -1 || (report_sectors_ && plane_.empty())) {
       const char *bad = nullptr;
       if (dir_allow_ == -1) bad = "report_sectors needs set_dir: there is no sector word without the direction mode";
       else if (dir_allow_ < 0 || dir_allow_ > 255) bad = "set_dir: allow is outside [0,255]";
@@ -1035,6 +1104,36 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
       if (bad || mtgpu_pipe_set_dir(pipe_, 1, dir_allow_, report_sectors_ ? MT_PIPE_REPORT_SECTORS : MT_PIPE_REPORT_CENTRES) != MT_OK) {
         err_ = bad ? bad : mtgpu_last_error();
         (void)mtgpu_pipe_set_dir(pipe_, 0, 0, 0);                // whatever fails here, no stale setting stays behind
+        (void)mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0);
+        (void)mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0);
+        (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);
+        (void)mtgpu_pipe_set_keep(pipe_, nullptr);
+        pipe_ = nullptr;
+        return false;
+      }
+    }
+    if (!plane_.empty()) {
+      mt_scan_params p;
+      if (mtgpu_get_params(be_->ctx(), &p) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
+      const size_t want = (size_t)p.grid_h * (size_t)p.grid_w;
+      std::string size_bad;
+      const char *bad = nullptr;
+      if (dir_allow_ != -1) bad = "set_plane together with set_dir: a plane and the allow byte are one rule at two granularities";
+      else if (min_blob_cells_ > 0 || report_largest_) bad = "set_plane together with set_min_blob_cells / report_largest: planes and blobs are not together yet";
+      else if (gmc_max_shift_ >= 0 || report_vector_) bad = "set_plane together with set_gmc / report_vector: planes and compensation are not together yet";
+      else if (gmc_blob_cells_ != 0 || gmc_blob_report_ != MT_PIPE_REPORT_CENTRES)
+        bad = "set_plane together with set_gmc_blobs: planes and the compensated blob scan are not together yet";
+      else if (report_sectors_ && !keep_centres_) bad = "report_sectors needs keep_centres: the sector word travels in the pipe's count array";
+      else if (plane_.size() != want) {
+        size_bad = "direction plane: " + std::to_string(plane_.size()) + " bytes, the " + std::to_string(p.grid_w) + "x" +
+                   std::to_string(p.grid_h) + " grid takes " + std::to_string(want);
+        bad = size_bad.c_str();
+      }
+      // the sequence above left every other mode off here unless `bad` names one of them
+      if (bad || mtgpu_pipe_set_plane(pipe_, plane_.data(), report_sectors_ ? MT_PIPE_REPORT_SECTORS : MT_PIPE_REPORT_CENTRES) != MT_OK) {
+        err_ = bad ? bad : mtgpu_last_error();
+        (void)mtgpu_pipe_set_plane(pipe_, nullptr, 0);           // whatever fails here, no stale setting stays behind
+        (void)mtgpu_pipe_set_dir(pipe_, 0, 0, 0);
         (void)mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0);
         (void)mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0);
         (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);
@@ -1181,6 +1280,14 @@ struct PipelineResult {
   uint64_t dir_frames = 0;
   uint64_t dir_present_frames[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t dir_dominant_frames[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // A direction plane (GpuMotionScanner::set_plane; include/mtgpu_pipe_lanes.h).  In: dir_plane = the bytes of this
+  // video's plane (load_plane's result, gh * gw): `segments` are those of the scan in which a record votes only if its
+  // destination cell's byte allows its sector, under `keep` where there is one; empty: take plane_options(), and none
+  // where that is empty too.  dir_sectors works with a plane as with dir_allow and fills dir_frames /
+  // dir_present_frames / dir_dominant_frames.  Not together with dir_allow >= 0 (one rule at two granularities), nor
+  // with min_blob_cells > 0 / blob_sweep_levels, gmc_max_shift >= 0 / gmc_vectors or gmc_blob_cells > 0 /
+  // gmc_blob_sweep_levels.  keep, keep_centres, sweep_levels, min_run, max_dropout and run_sweep_levels combine.
+  std::vector<uint8_t> dir_plane;
   // Temporal persistence (GpuMotionScanner::set_persist; include/mtgpu_persist.h, include/mtgpu_pipe_boxes.h).  In:
   // min_run > 1: on — a frame counts only as one of a run of at least min_run motion frames; -1: take persist_options();
   // 0 or 1: off whatever the options say (with no run_sweep_levels everything is as without these fields).  max_dropout:
@@ -1245,6 +1352,12 @@ inline GmcOptions &gmc_options() { static GmcOptions o; return o; }
 // set before the first pipeline starts, read by every run_scan_pipeline.  allow < 0: off.
 struct DirOptions { int allow = -1; bool sectors = false; };
 inline DirOptions &dir_options() { static DirOptions o; return o; }
+
+// Process-wide default for PipelineResult::dir_plane (a front end with ONE plane for every input): set before the first
+// pipeline starts, read by every run_scan_pipeline whose dir_plane is empty.  Empty: none.  A front end whose inputs have
+// grids of their own hands process_batch a plane_for hook instead.
+struct PlaneOptions { std::vector<uint8_t> plane; };
+inline PlaneOptions &plane_options() { static PlaneOptions o; return o; }
 
 // Process-wide defaults for PipelineResult::keep_centres / sweep_levels (a front end's --centres / --sweep): set before
 // the first pipeline starts, read by every run_scan_pipeline.
@@ -1360,7 +1473,32 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
   }
   const bool dir_on = out.dir_allow >= 0;
   if (out.dir_allow < -2 || out.dir_allow > 255) { out.error = "dir_allow is " + std::to_string(out.dir_allow) + ": want 0 .. 255, -1 or -2"; return 1; }
-  if (out.dir_sectors && !dir_on) { out.error = "dir_sectors without the direction mode (dir_allow)"; return 1; }
+  if (out.dir_plane.empty()) out.dir_plane = plane_options().plane;
+  const bool plane_on = !out.dir_plane.empty();
+  if (out.dir_sectors && !dir_on && !plane_on) { out.error = "dir_sectors without the direction mode (dir_allow)"; return 1; }
+  if (plane_on) {
+    if (dir_on) {
+      out.error = "dir_plane together with dir_allow: a plane and the allow byte are one rule at two granularities";
+      return 1;
+    }
+    if (out.min_blob_cells > 0 || report_largest) {
+      out.error = "dir_plane together with min_blob_cells / blob_sweep_levels: planes and blobs are not together yet";
+      return 1;
+    }
+    if (gmc_on || out.gmc_vectors) {
+      out.error = "dir_plane together with gmc_max_shift / gmc_vectors: planes and compensation are not together yet";
+      return 1;
+    }
+    if (pair_on) {
+      out.error = "dir_plane together with gmc_blob_cells / gmc_blob_sweep_levels: planes and the compensated blob scan are "
+                  "not together yet";
+      return 1;
+    }
+    if (out.dir_sectors && (out.keep_centres || centre_options().keep || !out.sweep_levels.empty())) {
+      out.error = "dir_sectors together with keep_centres / sweep_levels: the pipe has one count array";
+      return 1;
+    }
+  }
   if (dir_on) {
     if (out.min_blob_cells > 0 || report_largest) {
       out.error = "dir_allow together with min_blob_cells / blob_sweep_levels: direction and blobs are not together yet";
@@ -1451,6 +1589,7 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
         scanners[i]->report_gmc_blobs(pair_largest ? MT_PIPE_REPORT_LARGEST : MT_PIPE_REPORT_CENTRES);
         scanners[i]->set_dir(dir_on ? out.dir_allow : -1);
         scanners[i]->report_sectors(out.dir_sectors);
+        scanners[i]->set_plane(out.dir_plane);
         scanners[i]->set_persist(persist_on ? std::max(1, out.min_run) : 0, out.max_dropout, persist_on ? out.reach : -1);
         if (!scanners[i]->initialize()) {                                // :198-199 (here: reported)
           fail_with(scanners[i]->error());
@@ -1687,11 +1826,14 @@ struct BatchSummary {   // what a whole process_batch run did and what it held (
 // before the scan; it may throw: the video then fails with that message and the others go on.  One mask per video,
 // applied by every worker of its pipeline.
 struct NoKeep { std::vector<uint64_t> operator()(const std::string &) const { return {}; } };
+// plane_for(path) -> the direction plane of that video (load_plane's bytes; empty: none — plane_options() then decides),
+// called next to keep_for, under the same rules.
+struct NoPlane { std::vector<uint8_t> operator()(const std::string &) const { return {}; } };
 
-template <class OpenSource, class KeepFor = NoKeep>
+template <class OpenSource, class KeepFor = NoKeep, class PlaneFor = NoPlane>
 int process_batch(const std::vector<std::string> &files, const std::string &output_dir, int parallel_streams,
                   int threads_per_stream, OpenSource open_source, JobQueue &jobs, std::vector<std::string> *errors,
-                  BatchSummary *summary = nullptr, KeepFor keep_for = KeepFor()) {
+                  BatchSummary *summary = nullptr, KeepFor keep_for = KeepFor(), PlaneFor plane_for = PlaneFor()) {
   parallel_streams = std::max(1, std::min<int>(parallel_streams, (int)files.size()));
   threads_per_stream = std::max(1, threads_per_stream);
   std::mutex q_mu, e_mu, s_mu;
@@ -1755,6 +1897,7 @@ int process_batch(const std::vector<std::string> &files, const std::string &outp
           auto factory = open_source(in);
           job.result.keep = keep_for(in);
           job.keep = job.result.keep;
+          job.result.dir_plane = plane_for(in);
           rc = run_scan_pipeline(factory, threads_per_stream, job.result, s * threads_per_stream, &pool);
         } catch (const std::exception &e) {
           job.result.error = e.what();

@@ -5,7 +5,7 @@
 //                   [--gmc] [--gmc-max-shift N] [--gmc-min-share-q8 Q] [--gmc-vectors]
 //                   [--gmc-blobs N] [--gmc-blobs-max-shift S] [--gmc-blobs-min-share-q8 Q] [--sweep-gmc-blobs L1,L2,...]
 //                   [--min-run N] [--max-dropout D] [--reach R] [--sweep-min-run L1,L2,...]
-//                   [--allow LIST | --ignore LIST] [--dir-sectors]
+//                   [--allow LIST | --ignore LIST] [--dir-sectors] [--plane FILE.mtdir]
 //   (--streams 0 / --threads 0: the reference's own sizing from PARALLEL_STREAMS / THREADS_PER_STREAM and the CPU limit)
 // One file: like `motion_trim in out` (single ProcessingPipeline).  Several files: like
 // `motion_trim in_dir out_dir` (BatchProcessor): S streams x T workers, jobs consumed by one
@@ -68,6 +68,13 @@
 // --min-run, --max-dropout and --sweep-min-run; --dir-sectors does not combine with --centres or --sweep (a pipe has one
 // count array); none of it combines with the --gmc family, --min-blob-cells N > 0, --sweep-blobs, the --gmc-blobs family
 // or --reach.  Without these options the output is unchanged.
+// --plane FILE.mtdir: a direction plane (include/mtgpu_pipe_lanes.h) — one allow byte per grid cell where --allow has one
+// for the whole picture: a record votes only if its destination cell's byte has the bit of its sector
+// (mtgpu_host::load_plane; `python -m mvtrim_amd.lanes --learn --save-plane` writes such a file).  Loaded per input
+// against that input's grid, as --keep is; a mismatch is the loader's message with the line named.  It combines with
+// --keep, --centres, --sweep, --min-run and --dir-sectors (the "dir" object then carries "plane": "<path>" in place of
+// "allow"); it does not combine with --allow / --ignore (one rule at two granularities), the --gmc family, the blob
+// options or --reach.
 // --summary (several files): one more line {"batch_summary": ...} — frames scanned, wall time, worker-time
 // breakdown and what the S x T workers held (contexts, pipes, HIP streams, pinned / device bytes).
 #include <cmath>
@@ -137,6 +144,7 @@ static bool g_sweep_opt = false;                    // --sweep given
 static const char *g_dir_opt = nullptr;             // the first of --allow / --ignore / --dir-sectors given
 static const char *g_dir_list_opt = nullptr;        // --allow or --ignore, whichever was given
 static bool g_print_dir = false;                    // --dir-sectors
+static std::string g_plane_path;                    // --plane
 
 // LIST of --allow / --ignore: sector names E,SE,S,SW,W,NW,N,NE (any case) or one decimal number 0 .. 255 -> the byte of
 // the sectors named.
@@ -177,6 +185,20 @@ static std::vector<uint64_t> keep_for_size(int width, int height) {
   std::string err;
   if (!load_keep(g_keep_path, p.grid_w, p.grid_h, words, err)) throw std::runtime_error("--keep: " + err);
   return words;
+}
+
+// The direction plane of g_plane_path for a width x height input; throws with load_plane's message (the line is named)
+// when the file is malformed or made for another grid.
+static std::vector<uint8_t> plane_for_size(int width, int height) {
+  Config::load_all();
+  mt_scan_params p;
+  if (mtgpu_params_from_config(&p, width, height, Config::mv_threshold_sq(), Config::block_size(), Config::block_shift(),
+                               Config::vectors_needed(), Config::clusters_needed(), Config::vertical_mask()) != MT_OK)
+    throw std::runtime_error(mtgpu_last_error());
+  std::vector<uint8_t> bytes;
+  std::string err;
+  if (!load_plane(g_plane_path, p.grid_w, p.grid_h, bytes, err)) throw std::runtime_error("--plane: " + err);
+  return bytes;
 }
 
 static unsigned long long ignored_cells(const std::vector<uint64_t> &keep, int width, int height) {
@@ -240,7 +262,10 @@ static void print_job(const std::string &input, const PipelineResult &r, const s
     std::printf("]}");
   }
   if (g_print_dir) {
-    std::printf(", \"dir\": {\"allow\": %d, \"frames\": %llu, \"present\": [", r.dir_allow, (unsigned long long)r.dir_frames);
+    if (!g_plane_path.empty())
+      std::printf(", \"dir\": {\"plane\": \"%s\", \"frames\": %llu, \"present\": [", g_plane_path.c_str(), (unsigned long long)r.dir_frames);
+    else
+      std::printf(", \"dir\": {\"allow\": %d, \"frames\": %llu, \"present\": [", r.dir_allow, (unsigned long long)r.dir_frames);
     for (int k = 0; k < 8; ++k) std::printf("%s%llu", k ? ", " : "", (unsigned long long)r.dir_present_frames[k]);
     std::printf("], \"dominant\": [");
     for (int k = 0; k < 8; ++k) std::printf("%s%llu", k ? ", " : "", (unsigned long long)r.dir_dominant_frames[k]);
@@ -291,6 +316,10 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--keep")) {
       if (i + 1 >= argc) { std::fprintf(stderr, "error: --keep takes the path of a .mtkeep file\n"); return 2; }
       g_keep_path = argv[++i];
+    }
+    else if (!std::strcmp(argv[i], "--plane")) {
+      if (i + 1 >= argc) { std::fprintf(stderr, "error: --plane takes the path of a .mtdir file\n"); return 2; }
+      g_plane_path = argv[++i];
     }
     else if (!std::strcmp(argv[i], "--min-blob-cells")) {
       char *end = nullptr;
@@ -436,7 +465,21 @@ int main(int argc, char **argv) {
     else files.push_back(argv[i]);
   }
   // --dir-sectors alone: the mode with every sector allowed
-  if (g_print_dir && dir_options().allow < 0) dir_options().allow = 0xff;
+  if (g_print_dir && dir_options().allow < 0 && g_plane_path.empty()) dir_options().allow = 0xff;
+  // what a direction plane cannot be combined with: answered here, before any device call and before the plane is read
+  if (!g_plane_path.empty()) {
+    if (g_dir_list_opt) {
+      std::fprintf(stderr, "error: --plane cannot be combined with %s: a plane and the allow byte are one rule at two granularities\n", g_dir_list_opt);
+      return 2;
+    }
+    const char *other = g_gmc_opt ? g_gmc_opt : g_pair_opt ? g_pair_opt : g_pair_param_opt ? g_pair_param_opt :
+                        g_print_largest ? "--sweep-blobs" : blob_options().min_blob_cells > 0 ? "--min-blob-cells" :
+                        persist_options().reach >= 0 ? "--reach" : nullptr;
+    if (other) {
+      std::fprintf(stderr, "error: --plane cannot be combined with %s: planes are not together with blobs or compensation yet\n", other);
+      return 2;
+    }
+  }
   // what the direction filter cannot be combined with: answered here, before any device call
   if (g_dir_opt) {
     const char *other = g_gmc_opt ? g_gmc_opt : g_pair_opt ? g_pair_opt : g_pair_param_opt ? g_pair_param_opt :
@@ -555,6 +598,7 @@ int main(int argc, char **argv) {
       MtmvFile file(files[0]);
       PipelineResult r;
       if (!g_keep_path.empty()) r.keep = keep_for_size((int)file.hdr->width, (int)file.hdr->height);
+      if (!g_plane_path.empty()) r.dir_plane = plane_for_size((int)file.hdr->width, (int)file.hdr->height);
       int rc = run_scan_pipeline([&]() -> std::unique_ptr<FrameSource> {
         if (repeat > 1) return std::unique_ptr<FrameSource>(new RepeatSource(file, (uint64_t)repeat));
         return std::unique_ptr<FrameSource>(new MtmvSource(file));
@@ -586,11 +630,17 @@ int main(int argc, char **argv) {
       size_of(path, w, h);
       return keep_for_size(w, h);
     };
+    auto plane_for = [&](const std::string &path) -> std::vector<uint8_t> {
+      if (g_plane_path.empty()) return {};
+      int w = 0, h = 0;
+      size_of(path, w, h);
+      return plane_for_size(w, h);
+    };
     JobQueue jobs;
     std::vector<std::string> errors;
     int failed = 0;
     BatchSummary sum;
-    std::thread producer([&] { failed = process_batch(files, outdir, streams, threads, open_source, jobs, &errors, &sum, keep_for); });
+    std::thread producer([&] { failed = process_batch(files, outdir, streams, threads, open_source, jobs, &errors, &sum, keep_for, plane_for); });
     ScanJob job;                                   // the single consumer (batch_processor.cpp:138-150)
     while (jobs.pop(job)) {
       int w = 0, h = 0;

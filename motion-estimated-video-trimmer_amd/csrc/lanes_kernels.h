@@ -47,6 +47,15 @@ struct LanesLaunch : BatchLaunch {
   unsigned int *centres;                  // n_frames words, or null
   unsigned int *rose;                     // n_frames x 8 words (mt_dir_rose), or null
   int staged;                             // 1: the plane's analysed rows are held in LDS (lds_bytes counts them)
+  // The pipe form (pipe.hip's staging batches; include/mtgpu_pipe_lanes.h), launch_lanes_pipe: no clear kernel — the
+  // planner gets flags and centres and answers the frames without side data; no stream lookup (`planes` is ONE plane;
+  // stream_off null, n_streams 0); no rose array; the results are stored at system scope where sys_flags / sys_centres
+  // say that the array is not device memory (a zero-copy batch's pinned block); `keep`: ONE plane of gh x W words in
+  // device memory, or null — counting records and active cells of the analysed rows need their keep bit;
+  // report_sectors: centres receives the sector word built from the frame's rose in place of the centre count.
+  // launch_lanes_scan reads none of them.
+  const unsigned long long *keep = nullptr;
+  int sys_flags = 0, sys_centres = 0, report_sectors = 0;
   LanesK k;
 };
 
@@ -59,6 +68,9 @@ struct FlowLaunch : BatchLaunch {
 
 // Zero-fills the non-null outputs, builds the work list (launch_plan), then one workgroup per entry.
 hipError_t launch_lanes_scan(const LanesLaunch &L);
+// The pipe form: no fill — the planner answers the frames without side data — then one workgroup per entry of the list,
+// each of which stores its frame's flag and ONE count.  Planning + one kernel.
+hipError_t launch_lanes_pipe(const LanesLaunch &L);
 // Zero-fills the map; then, with frames and streams, builds the work list and runs one workgroup per entry.
 hipError_t launch_flow_map(const FlowLaunch &L);
 

@@ -23,6 +23,13 @@
 //   Every output element has one writer after the clear: lane 0 of the frame's workgroup, plain vector stores, no global
 //   atomics.
 //
+//   lanes_pipe_kernel    the form for a pipe's staging batch (include/mtgpu_pipe_lanes.h): no clear kernel — the planner
+//                        answers the frames without side data — no stream search (ONE plane), no rose array; every
+//                        listed frame's workgroup stores the flag and ONE count (the centre count or the sector word) on
+//                        the kernel's one exit, through store_flag / store_centres at the outputs' scope.  With a keep
+//                        plane the rose counts a record only where the keep bit of its destination cell is set, and the
+//                        active plane is the masked one; the keep words wait in the amask rows they are ANDed into.
+//
 //   flow_clear_kernel    zero-fills the map: the call clears, then counts.
 //   flow_frames_kernel   the same work list, stream search and streamers; no tile, no LDS.  Per counting record with a
 //                        sector one no-return agent-scope relaxed atomic add of 1 on the word of (stream, sector, cell):
@@ -264,6 +271,170 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 
 namespace {
 
+// ---- one record of the pipe form (include/mtgpu_pipe_lanes.h).  As lanes_vote; KEEP (under a keep plane): `kl` = the
+// staged keep words of the analysed rows (keep row r at kl + r * W).  The keep bit and the plane byte of the destination
+// cell are both read behind the branch: a record that does not count reads neither.  A record of a keep-0 cell is in no
+// sector of the rose and does not vote (its cell is inactive whatever its votes).
+template <bool KEEP>
+__device__ __forceinline__ void lanes_pipe_vote(const MvFields m, const LanesK &k, int t0, unsigned int *tile, const unsigned char *plane,
+                                                unsigned long long &acc, const unsigned long long *kl) {
+  const Counted c = counted(m, k);
+  if (c.counts) {
+    const unsigned int sec = sector_of(c.dx, c.dy);
+    const bool none = (c.dx | c.dy) == 0u;
+    const unsigned int allow = (unsigned int)plane[(unsigned int)((c.gy - k.y_lo) * k.gw + c.gx)];
+    const unsigned int eff = none ? 0xffu : allow;             // no direction to object to
+    if constexpr (KEEP) {
+      const bool kept = ((kl[(c.gy - k.y_lo) * k.W + (c.gx >> 6)] >> (c.gx & 63)) & 1ull) != 0ull;
+      acc += (unsigned long long)((none | !kept) ? 0u : 1u) << (8u * sec);
+      if (kept & (((eff >> sec) & 1u) != 0u)) atomicAdd(&tile[(unsigned int)((c.gy - t0) * k.gw + c.gx)], 1u);
+    } else {
+      acc += (unsigned long long)(none ? 0u : 1u) << (8u * sec);
+      if (((eff >> sec) & 1u) != 0u) atomicAdd(&tile[(unsigned int)((c.gy - t0) * k.gw + c.gx)], 1u);
+    }
+  }
+}
+
+}  // namespace
+
+// The pipe form of lanes_frames_kernel (include/mtgpu_pipe_lanes.h): what dir_frames_kernel<.., PIPE = true> is to the
+// direction scan.  No stream search — `plane` is ONE plane (gh x gw bytes) and serves every frame; no rose array; `keep`
+// is ONE keep plane (gh x W words) or null.  The flag and the ONE count leave through store_flag / store_centres with
+// sys_flags / sys_centres on the kernel's one exit, which an empty analysed range reaches too: a reused pinned block
+// holds the previous batch's values, so every listed frame stores.  With report_sectors the count is the sector word lane
+// 0 builds from the eight LDS rose words.
+//   plane   STAGED: rows y_lo .. y_hi - 1 behind `total`, the copy of lanes_frames_kernel.  The plane starts at an
+//           allocation boundary, but y_lo gw is odd for odd gw and odd y_lo: the head and tail byte paths stay live.
+//           !STAGED: one cached global byte load per counting record.
+//   keep    no LDS of its own: the keep words of the analysed rows wait in the amask rows they will be ANDed into (keep
+//           row r <-> mask row r + 1), which are dead until row_masks writes them; the lane that stores a word is the one
+//           that reads the keep word under it.  They are alive at the same time as the staged plane bytes, which lie
+//           behind `total` and so behind every mask row.  keep == nullptr is a workgroup-uniform branch around the
+//           staging and around the masked streamer.
+// Waves per SIMD: as lanes_frames_kernel.
+template <int BLOCK, int UNROLL, int REC, bool STAGED>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void lanes_pipe_kernel(
+    const unsigned char *__restrict__ mv, const WorkItem *__restrict__ work, unsigned int item0, unsigned int n_items, LanesK k,
+    const unsigned char *__restrict__ plane1, unsigned char *__restrict__ flags, unsigned int *__restrict__ centres,
+    const unsigned long long *__restrict__ keep, int sys_flags, int sys_centres, int report_sectors) {
+  extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
+  const unsigned int item = item0 + blockIdx.x;
+  if (item >= n_items) return;
+  const WorkItem me = load_item(work, item);
+  if (me.f == kNoFrame) return;                 // the list has ended (every later entry is past its end too)
+  const int tid = threadIdx.x;
+  unsigned int *tile = lds;
+  unsigned long long *amask = reinterpret_cast<unsigned long long *>(lds + k.tile_words);
+  unsigned int *lrose = reinterpret_cast<unsigned int *>(amask + (size_t)(k.R + 2) * k.W);
+  unsigned int *total = lrose + 8;
+  const int t0 = max(k.y_lo - 1, 0), t1 = min(k.y_hi + 1, k.gh);
+  const int crows = k.y_hi - k.y_lo;
+  const unsigned int f = __builtin_amdgcn_readfirstlane(me.f);
+  // rows y_lo .. y_hi - 1 of the plane: crows x gw bytes at any byte address
+  const unsigned char *src = plane1 + (size_t)k.y_lo * (size_t)k.gw;
+  const unsigned char *plane = src;
+  // ---- zero the tile, the rose and the total; stage the plane and the keep rows
+  zero_tile<BLOCK>(tile, k.tile_words);
+  if (tid < 9) lrose[tid] = 0u;                 // the eight rose words and total[0] behind them
+  if constexpr (STAGED) {
+    const unsigned int nbytes = (unsigned int)(max(crows, 0) * k.gw);
+    unsigned int head = (0u - (unsigned int)(uintptr_t)src) & 3u;            // bytes in front of the first aligned word
+    head = head < nbytes ? head : nbytes;
+    unsigned int *area = total + 4;                                          // 16-byte aligned
+    unsigned char *copy = reinterpret_cast<unsigned char *>(area) - head;    // inside total[3], which nobody else touches
+    const unsigned int nwords = (nbytes - head) >> 2, tail = (nbytes - head) & 3u;
+    if ((unsigned int)tid < head) copy[tid] = src[tid];
+    const unsigned int *src4 = reinterpret_cast<const unsigned int *>(src + head);   // 4-byte aligned wherever nwords > 0
+    for (unsigned int j = tid; j < nwords; j += BLOCK) area[j] = src4[j];
+    const unsigned int done = head + 4u * nwords;
+    if ((unsigned int)tid < tail) copy[done + tid] = src[done + tid];
+    plane = copy;
+  }
+  // the keep words of the analysed rows into mask rows 1 .. crows (crows <= R: inside the (R + 2) x W plane); keep row
+  // y_lo + r, r < crows, lies inside the gh x W plane
+  if (keep != nullptr) {
+    const unsigned long long *kp = keep + (size_t)k.y_lo * (size_t)k.W;
+    const int nkeep = crows * k.W;
+    for (int j = tid; j < nkeep; j += BLOCK) amask[(size_t)k.W + j] = kp[j];
+  }
+  // The mask plane's offset and the frame's number wait in VGPRs while the records stream (this form has VGPRs to spare
+  // under the 64 of eight waves per SIMD): held in SGPRs they are the values too many there, and the compiler parks
+  // them in VGPR lanes itself — SGPR spills, as dir_kernels.hip's pipe form met.  Seen with hipcc 7.2.26015 (AMD clang
+  // 22.0.0git, roc-7.2.0): one to three spilled SGPRs per form without this; the results do not depend on it, only the
+  // register use does.  With another compiler read the kernels' resource usage again
+  // (docs/rounds/r26_pipe_lanes.md has the command line).
+  unsigned int tw = (unsigned int)k.tile_words, fv = f;
+  asm volatile("" : "+v"(tw));
+  asm volatile("" : "+v"(fv));
+  __syncthreads();
+  // ---- the votes and the rose (an empty analysed range counts nothing: nothing to read)
+  if (crows > 0) {
+    for (unsigned long long r = me.r0; r < me.r1; r += kLanesChunk) {    // uniform: one piece unless the frame is huge
+      const unsigned long long n = (me.r1 - r) < kLanesChunk ? (me.r1 - r) : kLanesChunk;
+      unsigned long long acc = 0ull;
+      if (keep != nullptr) {
+        const unsigned long long *kl = amask + k.W;
+        const auto onek = [=, &k, &acc](const MvFields m) { lanes_pipe_vote<true>(m, k, t0, tile, plane, acc, kl); };
+        if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + r * 8ull, n, onek);
+        else stream_mv40<BLOCK, UNROLL>(mv + r * 40ull, n, onek);
+      } else {
+        const auto one = [=, &k, &acc](const MvFields m) { lanes_pipe_vote<false>(m, k, t0, tile, plane, acc, nullptr); };
+        if constexpr (REC == 8) stream_compact<BLOCK, UNROLL>(mv + r * 8ull, n, one);
+        else stream_mv40<BLOCK, UNROLL>(mv + r * 40ull, n, one);
+      }
+      flush_rose(acc, lrose);
+    }
+  }
+  __syncthreads();
+  // ---- the masks, then the centre count: an analysed row's word is ANDed with the keep word it overwrites (staged
+  // above); halo rows are stored as they come.  The plane, the rose and the total are found again from the offset parked
+  // in a VGPR above and from R = max(1, crows), which the launch checks.
+  amask = reinterpret_cast<unsigned long long *>(lds + tw);
+  lrose = reinterpret_cast<unsigned int *>(amask + (size_t)(max(crows, 1) + 2) * k.W);
+  total = lrose + 8;
+  const bool masked = keep != nullptr;
+  row_masks<BLOCK>(tile, k, t0, t1, k.y_lo - 1, crows + 2, [=, &k](int j, int w, int g, unsigned long long m) {
+    unsigned long long *slot = amask + (size_t)j * k.W + w;
+    const bool analysed = masked && g >= k.y_lo && g < k.y_hi;
+    *slot = analysed ? (m & *slot) : m;
+  });
+  __syncthreads();
+  count_centres<BLOCK>(amask, &total[0], k.W, k.gw, crows);
+  __syncthreads();
+  if (tid == 0) {                               // the one exit
+    const unsigned int c = total[0];
+    if (centres) {
+      unsigned int word = c;
+      if (report_sectors) {
+        // present byte | k* << 8 | min(n[k*], 2^21 - 1) << 11; k*: the smallest k whose count is maximal (0: none counts)
+        unsigned int present = 0u, best = 0u, kbest = 0u;
+#pragma unroll
+        for (unsigned int j = 0; j < 8u; ++j) {
+          const unsigned int n = lrose[j];
+          present |= (n ? 1u : 0u) << j;
+          if (n > best) { best = n; kbest = j; }
+        }
+        word = present | (kbest << 8) | ((best < 0x1fffffu ? best : 0x1fffffu) << 11);
+      }
+      store_centres(centres, fv, word, sys_centres);
+    }
+    if (flags) store_flag(flags, fv, (unsigned char)(c >= k.clust_need ? 1 : 0), sys_flags);
+  }
+}
+
+namespace {
+
+template <int REC, bool STAGED>
+hipError_t launch_pipe(const LanesLaunch &L) {
+  auto kern = lanes_pipe_kernel<kLanesBlock, kLanesUnroll, REC, STAGED>;
+  static std::atomic<unsigned long long> ready{0ull};
+  const WorkItem *work = static_cast<const WorkItem *>(L.plan_ws);
+  return launch_over_list(kern, ready, L, L.n_frames, [&](unsigned long long i0, unsigned int n) {
+    hipLaunchKernelGGL(kern, dim3(n), dim3(kLanesBlock), L.lds_bytes, L.stream, L.mv, work, (unsigned int)i0, L.n_frames, L.k,
+                       L.planes, L.flags, L.centres, L.keep, L.sys_flags, L.sys_centres, L.report_sectors);
+  });
+}
+
 template <int REC, bool STAGED>
 hipError_t launch_frames(const LanesLaunch &L) {
   auto kern = lanes_frames_kernel<kLanesBlock, kLanesUnroll, REC, STAGED>;
@@ -303,6 +474,21 @@ hipError_t launch_lanes_scan(const LanesLaunch &L) {
         hipLaunchKernelGGL(lanes_clear_kernel, dim3(grid), dim3(256), 0, L.stream, L.flags, L.centres, L.rose, L.n_frames);
       },
       [&](auto rec, auto) { return L.staged ? launch_frames<rec(), true>(L) : launch_frames<rec(), false>(L); });
+}
+
+hipError_t launch_lanes_pipe(const LanesLaunch &L) {
+  if (L.n_frames == 0) return hipSuccess;
+  if (L.rec_bytes != 40 && L.rec_bytes != 8) return hipErrorInvalidValue;
+  if ((!L.flags && !L.centres) || !L.planes || L.rose || L.stream_off || L.n_streams != 0) return hipErrorInvalidValue;
+  if (L.report_sectors && !L.centres) return hipErrorInvalidValue;
+  // the kernel finds its LDS areas, the plane's rows and the keep rows from the block's layout fields: they must be the grid's
+  if (!check_batch_launch(L) || !check_rows(L.k, L.lds_bytes, L.lds_max, lanes_lds_bytes(L.k.gw, L.k.R, L.staged != 0)) ||
+      (size_t)L.k.tile_words != dir_tile_words(L.k.gw, L.k.R) || L.k.W != (L.k.gw + 63) / 64 || L.k.y_lo < 0 || L.k.y_hi > L.k.gh ||
+      L.k.R != (L.k.y_hi - L.k.y_lo < 1 ? 1 : L.k.y_hi - L.k.y_lo))
+    return hipErrorInvalidValue;
+  return plan_and_launch(
+      L, true, L.flags, L.sys_flags, L.centres, L.sys_centres, [](unsigned int) {},
+      [&](auto rec, auto) { return L.staged ? launch_pipe<rec(), true>(L) : launch_pipe<rec(), false>(L); });
 }
 
 hipError_t launch_flow_map(const FlowLaunch &L) {

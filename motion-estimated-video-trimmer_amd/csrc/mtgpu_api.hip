@@ -2443,9 +2443,14 @@ int flow_check_args(const char *d, int rec_bytes, const void *rec, const void *f
 }
 
 // The plane scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
+// own_plan_ws: the caller's own block for the work list (a pipe's batch; ctx_plan_ws_bytes(n_frames) bytes, 256-byte
+// aligned) — the launch then takes NOTHING from the context's scratch ring — and the pipe form of the launch: d_planes is
+// ONE plane, d_keep one keep plane or null, no clear kernel, no stream lookup, no rose, flags and one count (the sector
+// word when report_sectors) stored at system scope when `outputs_in_host_memory`.  nullptr: the ring, the resident form.
 int lanes_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
              const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, const uint8_t *d_planes,
-             uint8_t *d_flags, uint32_t *d_centres, mt_dir_rose *d_rose, hipStream_t st) {
+             uint8_t *d_flags, uint32_t *d_centres, mt_dir_rose *d_rose, hipStream_t st, void *own_plan_ws = nullptr,
+             const uint64_t *d_keep = nullptr, int report_sectors = 0, int outputs_in_host_memory = 0) {
   mtgpu_lanes_plan lp;
   MT_TRY(lanes_plan(c->params, c->lds_max, &lp));
   mtgpu::LanesLaunch L;
@@ -2457,9 +2462,16 @@ int lanes_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records,
   L.staged = lp.staged;
   fill_tile(L.k, c->k, mtgpu::dir_tile_words);
   L.k.clust_need = c->k.clust_need;
-  PlanWs ws(c, st, nullptr, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (own_plan_ws) {
+    L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
+    L.sys_flags = (d_flags && outputs_in_host_memory) ? 1 : 0;
+    L.sys_centres = (d_centres && outputs_in_host_memory) ? 1 : 0;
+    L.report_sectors = report_sectors ? 1 : 0;
+  }
+  PlanWs ws(c, st, own_plan_ws, mtgpu::ctx_plan_ws_bytes(n_frames));
   if (ws.rc != MT_OK) return ws.rc;
   L.plan_ws = ws.p;
+  if (own_plan_ws) return profiled_launch(c, st, L, mtgpu::launch_lanes_pipe, "plane pipe scan launch");
   return profiled_launch(c, st, L, mtgpu::launch_lanes_scan, "plane scan launch");
 }
 
@@ -2484,6 +2496,27 @@ int flow_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, 
 }
 
 }  // namespace
+
+namespace mtgpu {
+int ctx_lanes_supported(const mtgpu_ctx *c) { return plan_ok(c, lanes_plan); }
+int ctx_lanes_plane_bytes(const mtgpu_ctx *c, uint64_t *bytes) {
+  mtgpu_lanes_plan lp;
+  MT_TRY(lanes_plan(c->params, c->lds_max, &lp));
+  *bytes = (uint64_t)lp.plane_bytes;
+  return MT_OK;
+}
+int ctx_launch_lanes(mtgpu_ctx *c, const void *d_rec, uint64_t n_records, const uint64_t *d_off, const uint8_t *d_sd,
+                     uint32_t n_frames, const uint64_t *d_keep, const uint8_t *d_plane, int report_sectors, uint8_t *d_flags,
+                     uint32_t *d_count, hipStream_t st, int rec_bytes, int outputs_in_host_memory, void *plan_ws,
+                     size_t plan_ws_bytes) {
+  if (n_frames == 0) return MT_OK;
+  if (!d_plane) return fail(MT_ERR_INVALID, "plane pipe scan without a plane");
+  if (report_sectors && !d_count) return fail(MT_ERR_INVALID, "plane pipe scan: the sector report needs the batch's count array");
+  MT_TRY(check_pipe_ws("plane", plan_ws, plan_ws_bytes, n_frames));
+  return lanes_on(c, d_rec, rec_bytes, n_records, 0, d_off, d_sd, n_frames, nullptr, 0, d_plane, d_flags, d_count, nullptr, st, plan_ws,
+                  d_keep, report_sectors ? 1 : 0, outputs_in_host_memory ? 1 : 0);
+}
+}  // namespace mtgpu
 
 extern "C" {
 

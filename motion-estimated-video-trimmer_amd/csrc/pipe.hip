@@ -137,6 +137,17 @@ struct mtgpu_pipe {
   int dir = 0;
   int32_t dir_allow = 0;
   int dir_report = 0;
+  // mtgpu_pipe_set_plane (include/mtgpu_pipe_lanes.h): lanes != 0: every submit runs the plane scan (ctx_launch_lanes)
+  // with the ONE plane d_plane (gh x gw bytes in device memory, owned by the pipe as d_keep is: allocated on first use,
+  // kept across off / on, freed with the pipe), rose and active plane under the keep plane when `masked`; lanes_report:
+  // MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_SECTORS.  h_plane: the bytes as they were given, for mtgpu_pipe_plane.  The
+  // direction rule at a cell's granularity: never together with dir, nor with min_blob > 0, gmc or pair_blob > 0.  They
+  // change only while no batch is being filled or in flight.
+  uint8_t *d_plane = nullptr;
+  uint64_t plane_bytes = 0;
+  std::vector<uint8_t> h_plane;
+  int lanes = 0;
+  int lanes_report = 0;
   std::vector<mtgpu_batch *> bufs;
   std::deque<mtgpu_batch *> inflight;
   std::mutex mu;
@@ -353,6 +364,7 @@ void mtgpu_pipe_destroy(mtgpu_pipe *p) {
   (void)hipSetDevice(mtgpu::ctx_device(p->ctx));
   for (mtgpu_batch *b : p->bufs) free_batch(b);      // drains every batch's stream first
   if (p->d_keep) (void)hipFree(p->d_keep);
+  if (p->d_plane) (void)hipFree(p->d_plane);
   delete p;
 }
 
@@ -459,6 +471,10 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
       rc = mtgpu::ctx_launch_dir(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
                                  p->dir_allow, p->dir_report == MT_PIPE_REPORT_SECTORS ? 1 : 0, b->d_flags, b->d_centres, st,
                                  b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
+    else if (p->lanes)   // mtgpu_pipe_set_plane: the plane scan, rose and active plane under the pipe's keep plane when it has a mask
+      rc = mtgpu::ctx_launch_lanes(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
+                                   p->d_plane, p->lanes_report == MT_PIPE_REPORT_SECTORS ? 1 : 0, b->d_flags, b->d_centres, st,
+                                   b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
     else if (p->masked)   // mtgpu_pipe_set_keep: the masked scan, its work list in the batch's own block like the plain one's
       rc = mtgpu::ctx_launch_zones(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->d_keep, b->d_flags,
                                    b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
@@ -635,6 +651,7 @@ int mtgpu_pipe_set_blobs(mtgpu_pipe *p, int32_t min_blob_cells, int report) {
     return fail(MT_ERR_UNSUPPORTED, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): blobs and compensation are "
                 "not together yet");
   if (p->dir) return refuse_next_to_dir("direction scan", "mtgpu_pipe_set_dir", "blobs");
+  if (p->lanes) return refuse_next_to_dir("plane scan", "mtgpu_pipe_set_plane", "blobs");
   const int rc = mtgpu::ctx_blobs_supported(p->ctx);         // MT_ERR_UNSUPPORTED, the grid named: nothing changes
   if (rc != MT_OK) return rc;
   p->min_blob = min_blob_cells;
@@ -675,6 +692,7 @@ int mtgpu_pipe_set_gmc(mtgpu_pipe *p, int enable, int32_t max_shift, int32_t min
     return fail(MT_ERR_UNSUPPORTED, "this pipe runs the blob scan (mtgpu_pipe_set_blobs): blobs and compensation are not "
                 "together yet");
   if (p->dir) return refuse_next_to_dir("direction scan", "mtgpu_pipe_set_dir", "compensation");
+  if (p->lanes) return refuse_next_to_dir("plane scan", "mtgpu_pipe_set_plane", "compensation");
   const int rc = mtgpu::ctx_gmc_supported(p->ctx);           // MT_ERR_UNSUPPORTED, the grid named: nothing changes
   if (rc != MT_OK) return rc;
   p->gmc = 1;
@@ -721,6 +739,7 @@ int mtgpu_pipe_set_gmc_blobs(mtgpu_pipe *p, int32_t min_blob_cells, int32_t max_
     return fail(MT_ERR_INVALID, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): turn it off first "
                 "(mtgpu_pipe_set_gmc(pipe, 0, 0, 0, 0)), then call mtgpu_pipe_set_gmc_blobs");
   if (p->dir) return refuse_next_to_dir("direction scan", "mtgpu_pipe_set_dir", "the compensated blob scan");
+  if (p->lanes) return refuse_next_to_dir("plane scan", "mtgpu_pipe_set_plane", "the compensated blob scan");
   const int rc = mtgpu::ctx_gmc_blobs_supported(p->ctx);     // MT_ERR_UNSUPPORTED, the grid named: nothing changes
   if (rc != MT_OK) return rc;
   p->pair_blob = min_blob_cells;
@@ -756,6 +775,9 @@ int mtgpu_pipe_set_dir(mtgpu_pipe *p, int enable, int32_t allow, int report) {
       return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the direction setting",
                   b->state == 1 ? "being filled" : "in flight");
   if (!enable) { p->dir = 0; p->dir_allow = 0; p->dir_report = 0; return MT_OK; }
+  if (p->lanes)
+    return fail(MT_ERR_INVALID, "this pipe runs the plane scan (mtgpu_pipe_set_plane): a plane and the allow byte are one rule at two "
+                "granularities; turn the plane off first (mtgpu_pipe_set_plane(pipe, NULL, 0))");
   if (p->min_blob > 0) return refuse_next_to_dir("blob scan", "mtgpu_pipe_set_blobs", "blobs");
   if (p->gmc) return refuse_next_to_dir("compensated scan", "mtgpu_pipe_set_gmc", "compensation");
   if (p->pair_blob > 0) return refuse_next_to_dir("compensated blob scan", "mtgpu_pipe_set_gmc_blobs", "the compensated blob scan");
@@ -773,6 +795,60 @@ int mtgpu_pipe_dir(const mtgpu_pipe *p, int32_t *allow, int *report) {
   if (!p->dir) return 0;
   if (allow) *allow = p->dir_allow;
   if (report) *report = p->dir_report;
+  return 1;
+}
+
+int mtgpu_pipe_set_plane(mtgpu_pipe *p, const uint8_t *plane, int report) {
+  if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
+  if (plane) {
+    if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_SECTORS)
+      return fail(MT_ERR_INVALID, "report is %d: want MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_SECTORS", report);
+    if (report == MT_PIPE_REPORT_SECTORS && !p->centres)
+      return fail(MT_ERR_INVALID, "MT_PIPE_REPORT_SECTORS needs a pipe with MT_LAYOUT_CENTRES: the sector word travels in its count array");
+  }
+  std::lock_guard<std::mutex> lock(p->mu);
+  for (const mtgpu_batch *b : p->bufs)
+    if (b->state == 1 || b->state == 2)
+      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the direction plane",
+                  b->state == 1 ? "being filled" : "in flight");
+  if (!plane) { p->lanes = 0; p->lanes_report = 0; return MT_OK; }   // the plane stays allocated, as the keep plane does
+  if (p->dir)
+    return fail(MT_ERR_INVALID, "this pipe runs the direction scan (mtgpu_pipe_set_dir): a plane and the allow byte are one rule at "
+                "two granularities; turn the byte off first (mtgpu_pipe_set_dir(pipe, 0, 0, 0))");
+  if (p->min_blob > 0) return refuse_next_to_dir("blob scan", "mtgpu_pipe_set_blobs", "blobs");
+  if (p->gmc) return refuse_next_to_dir("compensated scan", "mtgpu_pipe_set_gmc", "compensation");
+  if (p->pair_blob > 0) return refuse_next_to_dir("compensated blob scan", "mtgpu_pipe_set_gmc_blobs", "the compensated blob scan");
+  uint64_t bytes = 0;
+  int rc = mtgpu::ctx_lanes_plane_bytes(p->ctx, &bytes);     // MT_ERR_UNSUPPORTED, the grid named: nothing changes
+  if (rc != MT_OK) return rc;
+  hipError_t e = use_device(mtgpu::ctx_device(p->ctx));
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  std::vector<uint8_t> host;
+  try { host.assign(plane, plane + (size_t)bytes); } catch (const std::bad_alloc &) { return fail(MT_ERR_NOMEM, "out of host memory"); }
+  if (!p->d_plane) {
+    void *d = nullptr;
+    if ((e = hipMalloc(&d, (size_t)bytes)) != hipSuccess) return hip_fail(e, "hipMalloc (direction plane)");
+    p->d_plane = static_cast<uint8_t *>(d);
+    p->plane_bytes = bytes;
+  }
+  // synchronous: no kernel of this pipe is queued or running (no batch in state 2), the next submit finds the plane complete
+  if ((e = hipMemcpy(p->d_plane, plane, (size_t)bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+    p->lanes = 0;                                            // the plane's contents are unknown: never scan with it
+    p->lanes_report = 0;
+    return hip_fail(e, "hipMemcpy (direction plane)");
+  }
+  p->h_plane.swap(host);
+  p->lanes = 1;
+  p->lanes_report = report;
+  return MT_OK;
+}
+
+int mtgpu_pipe_plane(const mtgpu_pipe *p, uint8_t *plane, int *report) {
+  if (!p) return -1;
+  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
+  if (!p->lanes) return 0;
+  if (plane) std::memcpy(plane, p->h_plane.data(), p->h_plane.size());
+  if (report) *report = p->lanes_report;
   return 1;
 }
 

@@ -1512,6 +1512,39 @@ class ScanPipe:
             return None
         return int(a.value), ("sectors" if r.value == _abi.MT_PIPE_REPORT_SECTORS else "centres")
 
+    def set_plane(self, plane, report: str = "centres"):
+        """A direction plane on the decode path (mtgpu_pipe_set_plane): from now on a record of every batch votes only if
+        the allow byte of its DESTINATION CELL has the bit of its sector (include/mtgpu_lanes.h); under the keep mask, if
+        the pipe has one, the rose counts only records of kept cells and the active plane is the masked one.  plane:
+        uint8 [grid_h, grid_w] (lanes.load_plane / lanes.learn_plane).  report: what drain_centres() returns per frame,
+        "centres" or "sectors" — the frame's sector word (direction.unpack_sector_word); "sectors" needs centres=True.
+        Only while no batch is being filled or in flight (call drain() first): otherwise MtgpuError(MT_ERR_BUSY) and
+        nothing changes.  Not together with set_dir (MtgpuError(MT_ERR_INVALID): one rule at two granularities), nor
+        with set_blobs, set_gmc or set_gmc_blobs (MtgpuError(MT_ERR_UNSUPPORTED))."""
+        if report not in self._DIR_REPORTS:
+            raise ValueError(f"report is {report!r}, not 'centres' or 'sectors'")
+        p = self._scanner.params
+        a = np.asarray(plane)
+        if a.dtype != np.uint8:
+            raise ValueError(f"plane has dtype {a.dtype}, not uint8")
+        if a.shape != (p.grid_h, p.grid_w):
+            raise ValueError(f"plane has shape {a.shape}, not {(p.grid_h, p.grid_w)}")
+        a = np.ascontiguousarray(a)
+        check(self._lib.mtgpu_pipe_set_plane(self._pipe, _ptr(a), self._DIR_REPORTS[report]))
+
+    def clear_plane(self):
+        """The direction plane off (mtgpu_pipe_set_plane with NULL): the pipe is the plain or masked pipe it was before."""
+        check(self._lib.mtgpu_pipe_set_plane(self._pipe, None, 0))
+
+    @property
+    def plane(self) -> Optional[Tuple[np.ndarray, str]]:
+        """None, or (plane uint8 [grid_h, grid_w], report) while the pipe's submits run the plane scan (mtgpu_pipe_plane)."""
+        p = self._scanner.params
+        a, r = np.zeros((p.grid_h, p.grid_w), np.uint8), C.c_int()
+        if self._lib.mtgpu_pipe_plane(self._pipe, _ptr(a), C.byref(r)) != 1:
+            return None
+        return a, ("sectors" if r.value == _abi.MT_PIPE_REPORT_SECTORS else "centres")
+
     @staticmethod
     def unpack_gmc_vector(word: int) -> Tuple[int, int]:
         """(gx, gy) of a count reported under set_gmc(report="vector"): two signed 16-bit halves."""
