@@ -1,5 +1,5 @@
-"""Inputs of tests/test_gpu_derived_cliff.py: the grids on which the sweep, the activity map, the masked scan and the
-compensated scan fill their LDS to the last row or column, found with the previews (host arithmetic, no GPU), and a
+"""Inputs of tests/test_gpu_derived_cliff.py: the grids on which the sweep, the activity map, the masked scan, the
+compensated scan, the direction scan and the plane scan fill their LDS to the last row or column, found with the previews (host arithmetic, no GPU), and a
 small batch for each with the values derived BY HAND from its construction.  tests/test_derived_cliff_host.py proves
 without a GPU that every shape sits on the limit, that the batches carry centres and that two independent expected-value sources agree on them.
 
@@ -14,6 +14,9 @@ pixel coordinate is the cell index itself.  Nothing below is a literal size; bis
     sweep 1 x 1   20442  13627  626    209     | 13217   8028
     sweep 8 x 8   20422  13614  625    208     | 10896   7104
     gmc           10108  8086   584    199     | 13069   7841
+    dir           10234  8187   591    201     | 13234   7939
+    lanes staged  9096   7119   478    162     | 12244   6931    (one more is supported and reads the plane from memory)
+    lanes         10234  8187   591    201     | 13234   7939    (the unstaged form needs what the direction scan needs)
 
     activity at gw = 120 (every plan outcome is reachable there; the rows are the largest gh of the outcome and, as the
     row after it, the smallest gh that no longer has it — both are shapes):
@@ -41,7 +44,11 @@ a cell of another pair of that frame — plant() refuses a pair that would.  Bot
     with one cell ignored by a keep mask the other cell has no active neighbour left: the pair adds 0;
     at level 0 every cell of the grid is active, whatever the records: gh * (gw - 2) centres from gw = 3 on
     (gh = 1: the horizontal neighbours suffice), in the frame without records too.
-hand_count() is that rule and nothing else."""
+hand_count() is that rule and nothing else.
+
+The direction scan and the plane scan get the same pairs with a sector each (the directed planting); their hand values
+are stated in front of that section, at the end of this module."""
+import dataclasses
 import functools
 
 import numpy as np
@@ -49,12 +56,14 @@ import numpy as np
 import mvtrim_amd as m
 from mvtrim_amd import _abi
 
+import dir_model as dm
+import lanes_model as lm
 import oracle_binding as ob
 import zones_inputs as zi
 from derived_edge_inputs import MI355X_LDS, frozen, sweep_chunk_rows, voters
 from scan_checks import junk_padding
 
-KERNELS = ("zones", "activity", "sweep1", "sweep8", "gmc")
+KERNELS = ("zones", "activity", "sweep1", "sweep8", "gmc", "dir", "lanes")
 TALL_GW = (2, 3, 65, 193)
 WIDE_GH = (1, 3)
 ACT_GW = 120
@@ -85,6 +94,10 @@ def kernel_preview(kernel, p, lds=MI355X_LDS):
             return m.activity_preview(p, lds)
         if kernel == "gmc":
             return m.gmc_preview(p, lds)
+        if kernel == "dir":
+            return m.dir_preview(p, lds)
+        if kernel == "lanes":
+            return m.lanes_preview(p, lds)
         n = 1 if kernel == "sweep1" else 8
         return m.sweep_preview(p, n, n, lds)
     except m.MtgpuError as e:
@@ -128,6 +141,21 @@ def widest(kernel, gh):
     return largest(ok, 16383)
 
 
+def lanes_staged(p):
+    pv = kernel_preview("lanes", p)
+    return pv is not None and pv["staged"] == 1
+
+
+@functools.lru_cache(maxsize=None)
+def tallest_staged(gw):
+    return largest(lambda gh: lanes_staged(grid_params(gw, gh)))
+
+
+@functools.lru_cache(maxsize=None)
+def widest_staged(gh):
+    return largest(lambda gw: creatable(grid_params(gw, gh)) and lanes_staged(grid_params(gw, gh)), 16383)
+
+
 def act_outcome(gh, gw=ACT_GW):
     """Index into ACT_OUTCOMES of the plan of a gw x gh grid; len(ACT_OUTCOMES) where the map is unsupported."""
     pv = kernel_preview("activity", grid_params(gw, gh))
@@ -142,11 +170,20 @@ def act_last(outcome):
 @functools.lru_cache(maxsize=None)
 def shapes(kernel):
     """{name: (gw, gh, kind)}; kind "tall": one more is gh + 1, "wide": gw + 1, "plan": a plan outcome of the activity
-    map that is not the last one — one more row is supported and has the next outcome."""
+    map that is not the last one — one more row is supported and has the next outcome — or a grid of the plane scan
+    around the end of its staged form: "tall-staged" / "wide-staged", the last grid whose plane rows fit next to the
+    tile, and "tall-unstaged" / "wide-unstaged", one row or column further, the first one that reads the plane from
+    memory.  (The plane scan's "tall" and "wide" shapes are the last unstaged grids: the direction scan's.)"""
     out = {}
     for gw in TALL_GW:
+        if kernel == "lanes":
+            out[f"tall-staged-{gw}x{tallest_staged(gw)}"] = (gw, tallest_staged(gw), "plan")
+            out[f"tall-unstaged-{gw}x{tallest_staged(gw) + 1}"] = (gw, tallest_staged(gw) + 1, "plan")
         out[f"tall-{gw}x{tallest(kernel, gw)}"] = (gw, tallest(kernel, gw), "tall")
     for gh in WIDE_GH:
+        if kernel == "lanes":
+            out[f"wide-staged-{widest_staged(gh)}x{gh}"] = (widest_staged(gh), gh, "plan")
+            out[f"wide-unstaged-{widest_staged(gh) + 1}x{gh}"] = (widest_staged(gh) + 1, gh, "plan")
         out[f"wide-{widest(kernel, gh)}x{gh}"] = (widest(kernel, gh), gh, "wide")
     if kernel == "activity":
         for i, (bits, two) in enumerate(ACT_OUTCOMES):
@@ -161,9 +198,16 @@ def one_more(gw, gh, kind):
     return (gw + 1, gh) if kind == "wide" else (gw, gh + 1)
 
 
-# The four LDS formulas, restated from the layout comments of csrc/zones_kernels.h, csrc/activity_kernels.h,
-# csrc/sweep_kernels.h and csrc/gmc_kernels.h (tile: (R + 2) x gw 32-bit counters padded to 16 bytes; W 64-bit words per
-# mask row; the compensated scan: the tile, one plane of R + 2 mask rows, two histograms of 256 bins, eight result words).  A grid past
+def grows(name):
+    """"wide" or "tall": the way a shape of that name grows, whatever its kind."""
+    return name.split("-")[0]
+
+
+# The LDS formulas, restated from the layout comments of csrc/zones_kernels.h, csrc/activity_kernels.h,
+# csrc/sweep_kernels.h, csrc/gmc_kernels.h, csrc/dir_kernels.h and csrc/lanes_kernels.h (tile: (R + 2) x gw 32-bit counters
+# padded to 16 bytes; W 64-bit words per mask row; the compensated scan: the tile, one plane of R + 2 mask rows, two
+# histograms of 256 bins, eight result words; the direction scan: the tile, one plane of R + 2 mask rows, four words of
+# totals and the eight of the rose; the plane scan: the same and, staged, R x gw plane bytes padded to 16).  A grid past
 # the limit has no preview to ask, so "what one more row or column would add" comes from these; the host test holds
 # them to the previews' lds_bytes on every shape.
 def _tile(gw, R):
@@ -173,7 +217,7 @@ def _tile(gw, R):
 def lds_need(kernel, gw, gh):
     """The LEAST the kernel needs on a gw x gh grid (vertical_mask 0): zones and the compensated scan have one form; the
     activity map's smallest is the one without accumulators; the sweep's is one tile and the three-row mask buffer per
-    level."""
+    level; the plane scan's is the unstaged form, which is the direction scan's."""
     W = (gw + 63) // 64
     if kernel == "zones":
         return _tile(gw, gh) + (3 * gh + 4) * W * 8 + 16
@@ -181,11 +225,18 @@ def lds_need(kernel, gw, gh):
         return _tile(gw, gh) + (2 * gh + 2) * W * 8 + 16
     if kernel == "gmc":
         return _tile(gw, gh) + (gh + 2) * W * 8 + 2 * 256 * 4 + 32
+    if kernel in ("dir", "lanes"):
+        return _tile(gw, gh) + (gh + 2) * W * 8 + 16 + 32
     return _tile(gw, gh) + (1 if kernel == "sweep1" else 8) * 3 * W * 8 + 256
 
 
 def act_lds(gw, gh, bits):
     return lds_need("activity", gw, gh) + 2 * gh * ((gw + 3) & ~3) * bits // 8
+
+
+def lanes_lds(gw, gh, staged):
+    """csrc/lanes_kernels.h: the direction scan's LDS and, staged, the gh x gw bytes of the plane's rows padded to 16."""
+    return lds_need("lanes", gw, gh) + (((gh * gw + 15) & ~15) if staged else 0)
 
 
 # ------------------------------------------------------------------ planted pairs
@@ -269,14 +320,19 @@ ACT_RUN = 4                          # runs [0, 4) [4, 8) ...: the stream bounda
 @functools.lru_cache(maxsize=None)
 def batch(gw, gh):
     """(mv, off, sd, planted): the 12 frames of ORDER (E and H appear twice, for the masked scan's streams)."""
+    return _batch(gw, gh, planted_frames(gw, gh), pairs_records)
+
+
+def _batch(gw, gh, planted, records):
+    """The batch of a shape with `planted` pairs turned into records by `records`.  The random stream sees the pairs'
+    record counts alone: two plantings with the same counts share their blob frames, permutations and padding."""
     sh = shift_of(gw, gh)
     p = grid_params(gw, gh)
     rng = np.random.RandomState(gw * 40009 + gh)
-    planted = planted_frames(gw, gh)
     frames, sd = [], []
     for name in ORDER:
         if name in planted:
-            f = pairs_records(planted[name], sh)
+            f = records(planted[name], sh)
         elif name == "Z":
             f = np.zeros(0, dtype=m.MV_DTYPE)
         else:
@@ -468,3 +524,181 @@ def gmc_pan_case(name):
     junk_padding(mv, rng)
     return (p,) + frozen(mv, np.ascontiguousarray(b.frame_off, dtype=np.uint64), np.ones(2, dtype=np.uint8),
                          np.array(centres, dtype=np.uint32), np.array(info, dtype=np.int64))
+
+
+# ------------------------------------------------------------------ the direction scan and the plane scan
+#
+# The directed planting: the pairs of planted_frames() on the ANALYSED rows (all of them, but for a phase variant with a
+# margin), both cells of pair i with pair_votes(i) records of displacement dir_inputs.DISP[i % 8] — sector i % 8,
+# |d|^2 = 25 or 32 — in the batch of _batch(): blob frames (every record moves east), N, Z, junk padding.  Under CTX_KW
+# every pair passes the threshold and the level.  Hand values:
+#   the rose of a planted frame   bin s = the sum over the pairs with i % 8 == s of 2 pair_votes(i), whatever is allowed
+#   the direction scan, byte A    pair i adds one centre per cell with its column in [1, gw - 2] iff bit i % 8 of A is
+#                                 set (a pair whose sector is forbidden casts no vote: both cells are inactive and, being
+#                                 isolated, take no other pair's centre with them); A = 0xFF: hand_count
+#   the plane scan                P_all: 0xFF everywhere: hand_count.  P_own: both cells of pair i hold 1 << (i % 8), every
+#                                 other cell 0x00: every pair votes: hand_count.  P_half: the first cell of pair i holds
+#                                 0xFF ^ (1 << (i % 8)), the second 1 << (i % 8), every other cell 0xFF: the first cell
+#                                 casts no vote, the second has no active neighbour left: 0.
+#   the flow map of a frame       cell (x, y) of pair i holds pair_votes(i) in sector i % 8, every other word 0
+# P_own and P_half take their bytes from the pairs of E and then from the pairs of H that share no cell with them (on
+# three and four columns H holds the right corners): the first and the last cell of the first and the last analysed row
+# hold a byte of their own wherever the grid has room for the corner pairs.  The hand values of P_own and P_half are
+# stated for E, and for H where all of its pairs got their bytes; the other frames' expected values are the model's.
+# hand_dir_count(), hand_rose(), hand_flow() and lanes_hand() are those rules and nothing else.
+
+DIR_CHAIN = (0x00, 0x55, 0xAA, 0xFF)           # nothing; E, S, W, N; SE, SW, NW, NE; everything
+DIR_STREAM_ALLOWS = (0x0F, 0xA5, 0xD2)         # one byte per stream of ZONE_SOFF
+LANES_ROTATIONS = (("all", "own", "half"), ("half", "all", "own"), ("own", "half", "all"))   # plane of stream 0, 1, 2
+
+
+def directed_records(pairs, shift):
+    from dir_inputs import DISP          # not at the top: dir_inputs imports the soak, whose blob inputs import this module
+    return voters([(x, y, pair_votes(i)) + tuple(DISP[i % 8]) for i, pr in enumerate(pairs) for x, y in pr], shift)
+
+
+def with_margin(p, margin):
+    return dataclasses.replace(p, vertical_margin=margin) if margin else p
+
+
+@functools.lru_cache(maxsize=None)
+def dir_batch(gw, gh, margin=0):
+    """(mv, off, sd, planted) with the directed planting on rows margin .. gh - margin - 1."""
+    planted = {n: [tuple((x, y + margin) for x, y in pr) for pr in prs] for n, prs in planted_frames(gw, gh - 2 * margin).items()}
+    return _batch(gw, gh, planted, directed_records)
+
+
+def hand_rose(pairs):
+    rose = np.zeros(8, dtype=np.uint32)
+    for i in range(len(pairs)):
+        rose[i % 8] += 2 * pair_votes(i)
+    return rose
+
+
+def hand_dir_count(pairs, gw, allow):
+    return sum(sum(1 for x, _ in pr if 1 <= x <= gw - 2) for i, pr in enumerate(pairs) if (allow >> (i % 8)) & 1)
+
+
+def hand_flow(pairs, gw, gh):
+    flow = np.zeros((8, gh, gw), dtype=np.uint32)
+    for i, pr in enumerate(pairs):
+        for x, y in pr:
+            flow[i % 8, y, x] = pair_votes(i)
+    return flow
+
+
+@functools.lru_cache(maxsize=None)
+def dir_case(name):
+    """dict: params, mv, off, sd, planted, soff (ZONE_SOFF), allows (DIR_STREAM_ALLOWS)."""
+    gw, gh, _ = shapes("dir")[name]
+    mv, off, sd, planted = dir_batch(gw, gh)
+    return dict(params=grid_params(gw, gh, **CTX_KW), mv=mv, off=off, sd=sd, planted=planted,
+                soff=frozen(np.array(ZONE_SOFF, dtype=np.uint64))[0], allows=frozen(np.array(DIR_STREAM_ALLOWS, dtype=np.uint8))[0])
+
+
+@functools.lru_cache(maxsize=None)
+def dir_expected(name, allow=None):
+    """The model's (flags, centres, rose) of the shape's batch under one byte, or (None) under the case's streams."""
+    c = dir_case(name)
+    kw = dict(soff=c["soff"], allows=c["allows"]) if allow is None else dict(allow=allow)
+    return frozen(*dm.model_batch(c["params"], c["mv"], c["off"], c["sd"], **kw))
+
+
+def dir_hand(c, allow=None):
+    """{frame: (centres, rose)} of the planted frames under one byte, or under the case's streams."""
+    st = zi.stream_of_frames(c["soff"], len(ORDER))
+    gw = c["params"].grid_w
+    return {f: (hand_dir_count(c["planted"][n], gw, int(c["allows"][st[f]]) if allow is None else allow), hand_rose(c["planted"][n]))
+            for f, n in enumerate(ORDER) if n in c["planted"]}
+
+
+def pair_planes(gw, gh, planted):
+    """({"all", "own", "half": uint8 [gh, gw]}, the planted frames whose every pair got its bytes)."""
+    own, half = np.zeros((gh, gw), dtype=np.uint8), np.full((gh, gw), 0xFF, dtype=np.uint8)
+    taken, whole = set(), []
+    for n in ("E", "H"):
+        placed = 0
+        for i, (a, b) in enumerate(planted[n]):
+            if {a, b} & taken:
+                continue
+            taken |= {a, b}
+            placed += 1
+            bit = 1 << (i % 8)
+            own[a[1], a[0]] = own[b[1], b[0]] = bit
+            half[a[1], a[0]], half[b[1], b[0]] = 0xFF ^ bit, bit
+        if placed == len(planted[n]):
+            whole.append(n)
+    return dict(zip(("all", "own", "half"), frozen(np.full((gh, gw), 0xFF, dtype=np.uint8), own, half))), tuple(whole)
+
+
+@functools.lru_cache(maxsize=None)
+def lanes_case(name, margin=0):
+    """dict: params, mv, off, sd, planted, soff (ZONE_SOFF), planes {"all", "own", "half"}, whole, R (analysed rows)."""
+    gw, gh, _ = shapes("lanes")[name]
+    mv, off, sd, planted = dir_batch(gw, gh, margin)
+    planes, whole = pair_planes(gw, gh, planted)
+    return dict(params=with_margin(grid_params(gw, gh, **CTX_KW), margin), mv=mv, off=off, sd=sd, planted=planted,
+                soff=frozen(np.array(ZONE_SOFF, dtype=np.uint64))[0], planes=planes, whole=whole, R=gh - 2 * margin)
+
+
+def lanes_stack(c, rotation):
+    return np.stack([c["planes"][k] for k in rotation])
+
+
+@functools.lru_cache(maxsize=None)
+def lanes_expected(name, rotation, margin=0):
+    c = lanes_case(name, margin)
+    return frozen(*lm.model_batch(c["params"], c["mv"], c["off"], c["sd"], lanes_stack(c, rotation), c["soff"]))
+
+
+def lanes_hand(c, rotation):
+    """{frame: (centres or None where the rule above states none, rose)} of the planted frames."""
+    st = zi.stream_of_frames(c["soff"], len(ORDER))
+    gw = c["params"].grid_w
+    out = {}
+    for f, n in enumerate(ORDER):
+        if n in c["planted"]:
+            kind, full = rotation[st[f]], hand_count(c["planted"][n], gw, c["R"], 4.0, 2)
+            count = full if kind == "all" else None if n not in c["whole"] else full if kind == "own" else 0
+            out[f] = (count, hand_rose(c["planted"][n]))
+    return out
+
+
+FLOW_EACH = tuple(range(len(ORDER) + 1))       # one stream per frame: the planted frames' maps stand alone
+
+
+@functools.lru_cache(maxsize=None)
+def flow_expected(name, soff):
+    c = lanes_case(name)
+    return frozen(lm.flow_map(c["params"], c["mv"], c["off"], c["sd"], np.array(soff, dtype=np.uint64)))[0]
+
+
+# Plane base phases.  The staged copy moves up to three head bytes, aligned words and up to three tail bytes; what it
+# meets is decided by the source's phase inside a 32-bit word, ((s gh + y_lo) gw + shift) % 4 for stream s of a plane
+# tensor that starts `shift` bytes behind an allocation's start, and by the copied bytes, R gw.  The runs: the six
+# last-staged shapes and tall-65 of the unstaged limit (which copies nothing and reads bytes from memory), each at shifts
+# 0 .. 3; the shifts give every shape every phase, and the six staged shapes end on 0, 1 and 2 bytes behind the last
+# word.  phase_runs() adds the first staged shape of more than four columns and margin (1 .. 3 rows) with R gw % 4 == 3 —
+# found when this was written: wide-staged-6931x3 with a margin of one row, which leaves ONE analysed row between two halo
+# rows; no code reads that.  More than four columns: there the last cell of the last analysed row belongs to a corner
+# pair of E whose other cell can be a centre, so one wrong byte at the very end of the copy changes a count (on two
+# columns nothing is a centre; on three and four the last column's pair is vertical and neither cell can be one).
+PHASE_SHIFTS = (0, 1, 2, 3)
+PHASE_ROTATION = LANES_ROTATIONS[0]
+
+
+def phase_pairs(gw, gh, margin=0):
+    """{(source phase % 4, copied bytes % 4)} over the three streams and the four shifts."""
+    return {(((s * gh + margin) * gw + shift) % 4, ((gh - 2 * margin) * gw) % 4) for s in range(3) for shift in PHASE_SHIFTS}
+
+
+@functools.lru_cache(maxsize=None)
+def phase_runs():
+    """[(shape name, margin)]"""
+    names = [n for n in shapes("lanes") if "-staged-" in n] + [n for n, (gw, _, kind) in shapes("lanes").items() if kind == "tall" and gw == 65]
+    runs = [(n, 0) for n in names]
+    tails = {(shapes("lanes")[n][0] * shapes("lanes")[n][1]) % 4 for n in names if "-staged-" in n}
+    for want in sorted(set(range(4)) - tails):
+        runs.append(next((n, mg) for n in names if "-staged-" in n and shapes("lanes")[n][0] > 4 for mg in (1, 2, 3)
+                         if shapes("lanes")[n][1] > 2 * mg and (shapes("lanes")[n][0] * (shapes("lanes")[n][1] - 2 * mg)) % 4 == want))
+    return runs

@@ -1,5 +1,6 @@
 """The random stream of tests/test_gpu_derived_soak.py — the soak of the sweep, the activity map, the masked scan, the
-compensated scan, the blob scan and the compensated blob scan — and its expected values, usable without a GPU
+compensated scan, the blob scan, the compensated blob scan, the direction scan, the plane scan and the flow map — and
+its expected values, usable without a GPU
 (tests/test_derived_cliff_host.py replays the first iterations).  The two labelling kernels meet any grid width and
 height here, with the LDS layout that follows from it; random connectivity is the business of tests/test_gpu_blob_planes.py.
 
@@ -12,7 +13,11 @@ a share of every frame's records follows the pan) comes from a RandomState of it
 stream `rng` and everything drawn from it are what they were before that kernel joined.  What the two blob scans alone
 need (min_blob_cells, whether the call is masked) comes from a third RandomState, seeded from (seed, it) and BLOBS_SALT:
 `rng` and draw_gmc's state are what they were before the blob scans joined.  The blob scan runs on d["mv"], the
-compensated one on d["gmc_mv"] with draw_gmc's settings; masked, both use d["zsoff"] and d["keeps"].
+compensated one on d["gmc_mv"] with draw_gmc's settings; masked, both use d["zsoff"] and d["keeps"].  What the direction
+scan, the plane scan and the flow map alone need (an allow byte, bytes per stream, planes, the forms of the two calls)
+comes from a fourth RandomState, seeded from (seed, it) and DIR_SALT: the three states before it are what they were.
+All three run on d["mv"]; the per-stream forms use d["zsoff"] (frames may lie behind the last stream), the flow map
+d["soff"].
 
 The grid comes from w, h in [64, 3900] x [64, 2200] and block_shift 1 .. 5 as in tests/soak_replay.py, but the shifts are
 not equally likely: a derived kernel holds a whole frame's counters in LDS and supports about 37 000 cells, which a
@@ -24,8 +29,10 @@ import mvtrim_amd as m
 from mvtrim_amd import _abi, synth
 
 import blobs_model as bm
+import dir_model as dm
 import gmc_blobs_inputs as gbi
 import gmc_model as gm
+import lanes_model as lm
 import oracle_binding as ob
 import pipe_gmc_inputs as pgi
 import zones_inputs as zi
@@ -33,7 +40,7 @@ from activity_model import assert_oracle_identities, model_maps
 from derived_edge_inputs import MI355X_LDS, UNALIGNED_SHIFTS
 from scan_checks import junk_padding
 
-KERNELS = ("sweep", "activity", "zones", "gmc", "blobs", "gmc_blobs")
+KERNELS = ("sweep", "activity", "zones", "gmc", "blobs", "gmc_blobs", "dir", "lanes", "flow")
 DEFAULT_SEED = 24680
 SHIFT_P = [0.04, 0.08, 0.18, 0.35, 0.35]                 # block_shift 1 .. 5
 THR_POOL = [0.0, 4.0, 9.5, 16.0, 25.0, 37.0, 4294967296.0, float("inf")]
@@ -46,6 +53,13 @@ GMC_SHARE_Q8_P = [0.25, 0.3, 0.3, 0.15]
 GMC_FOLLOW_P = [0.1, 0.25, 0.3, 0.35]
 BLOBS_SALT = 0xB10B                                      # the third state's seed is (seed, it, BLOBS_SALT); draw_gmc's is (seed, it)
 MIN_BLOB_POOL = [0, 1, 2, 3, 5, 12, 40, 3000]            # 0 and 1 change no flag; 40 and 3000 lie above most blobs' sizes
+DIR_SALT = 0xD12                                         # the fourth state's seed is (seed, it, DIR_SALT)
+# nothing, everything, single sectors, halves and mixed bytes.  The blobs of zones_inputs.clustered_frame all move east
+# (bit 0): most of the pool forbids that, which is what turns flags off.
+ALLOW_POOL = [0x00, 0xFF, 0x01, 0x02, 0x10, 0x80, 0x55, 0xAA, 0x0F, 0xF0, 0xA4, 0x3C, 0xDA, 0xFE]
+PLANE_KINDS = ("bytes", "density", "all")                # random bytes; 0x00 / 0xFF at a drawn density; all 0xFF
+PLANE_KIND_P = [0.5, 0.35, 0.15]
+PLANE_DENSITY_POOL = [0.0, 0.3, 0.9]                     # the share of 0xFF cells of a "density" plane
 
 
 def _preview(fn, *a):
@@ -87,6 +101,39 @@ def draw_blobs(seed, it, p):
     rng = np.random.RandomState([int(seed) & 0xFFFFFFFF, int(it), BLOBS_SALT])
     return dict(min_blob_cells=int(rng.choice(MIN_BLOB_POOL)), blob_masked=bool(rng.rand() < 0.5),
                 support_blobs=_preview(m.blobs_preview, p, MI355X_LDS), support_gmc_blobs=_preview(m.gmc_blobs_preview, p, MI355X_LDS))
+
+
+def draw_dir(seed, it, p, n_streams):
+    """The inputs of the direction scan, the plane scan and the flow map of iteration `it`: a scalar allow byte; whether
+    the direction call is per-stream and its bytes (one per stream of d["zsoff"]); the planes uint8 [S, gh, gw] of those
+    streams — each random bytes, 0x00 / 0xFF at a drawn density, or all 0xFF — where the plane scan supports the grid
+    (None elsewhere: a refused call reads no plane); whether the plane call uses the one-plane form (planes[0] for every
+    frame)."""
+    rng = np.random.RandomState([int(seed) & 0xFFFFFFFF, int(it), DIR_SALT])
+    out = dict(allow=int(rng.choice(ALLOW_POOL)), dir_per_stream=bool(rng.rand() < 0.5),
+               allows=rng.choice(ALLOW_POOL, size=n_streams).astype(np.uint8), lanes_one_plane=bool(rng.rand() < 0.35),
+               support_dir=_preview(m.dir_preview, p, MI355X_LDS), support_lanes=_preview(m.lanes_preview, p, MI355X_LDS),
+               planes=None, plane_kinds=None)
+    if out["support_lanes"]:
+        kinds = [str(k) for k in rng.choice(PLANE_KINDS, size=n_streams, p=PLANE_KIND_P)]
+        planes = np.full((n_streams, p.grid_h, p.grid_w), 0xFF, dtype=np.uint8)
+        for i, kind in enumerate(kinds):
+            if kind == "bytes":
+                planes[i] = rng.randint(0, 256, size=(p.grid_h, p.grid_w))
+            elif kind == "density":
+                planes[i] = np.where(rng.rand(p.grid_h, p.grid_w) < float(rng.choice(PLANE_DENSITY_POOL)), 0xFF, 0x00)
+        out.update(planes=planes, plane_kinds=kinds, lanes_staged=m.lanes_preview(p, MI355X_LDS)["staged"])
+    return out
+
+
+def dir_args(d):
+    """The keyword arguments of dir_model.model_batch for the draw's direction call."""
+    return dict(soff=d["zsoff"], allows=d["allows"]) if d["dir_per_stream"] else dict(allow=d["allow"])
+
+
+def lanes_args(d):
+    """(planes, stream_off) of the draw's plane call."""
+    return (d["planes"][0], None) if d["lanes_one_plane"] else (d["planes"], d["zsoff"])
 
 
 def blob_masks(d):
@@ -152,6 +199,10 @@ def draw(rng, it, seed=DEFAULT_SEED):
     b = draw_blobs(seed, it, p)                              # nor from draw_gmc's state
     support["blobs"], support["gmc_blobs"] = b.pop("support_blobs"), b.pop("support_gmc_blobs")
     d.update(b)
+    g = draw_dir(seed, it, p, S)                             # nor from draw_blobs' state
+    support["dir"], support["lanes"] = g.pop("support_dir"), g.pop("support_lanes")
+    support["flow"] = support["lanes"]                       # the flow map answers with the plane scan's plan
+    d.update(g)
     return d
 
 
@@ -329,6 +380,42 @@ def _expected_blobs(d, kernel, check_sources):
     return e
 
 
+def plain_scan(d):
+    """(flags, centres) of the oracle on the draw's records as they are: what allow 0xFF and a plane of 0xFF must give.
+    Computed once per draw."""
+    if "_plain" not in d:
+        d["_plain"] = ob.scan_centres(d["params"], d["mv"], d["off"], d["sd"], nthreads=8)
+    return d["_plain"]
+
+
+def _expected_dir(d, kernel, check_sources):
+    """The expected outputs of the direction scan or the plane scan on d["mv"], "plain" (plain_scan) and what the draw
+    reaches: "flag_off" (frames inside a stream whose plain flag is set and which the byte or plane turns off),
+    "per_stream" (the form with one byte or plane per stream of d["zsoff"]), "behind" (frames behind its last stream).
+    check_sources: the oracle on filtered records (consequence C), or under vectors_needed 0, where that oracle has no
+    level 0, consequence F against the plain scan; the roses' sums against dir_model.counting_moving (B)."""
+    p, mv, off, sd = d["params"], d["mv"], d["off"], d["sd"]
+    F = len(sd)
+    if kernel == "dir":
+        kw, per_stream = dir_args(d), d["dir_per_stream"]
+        fl, ce, rose = dm.model_batch(p, mv, off, sd, **kw)
+        owned = dm.frame_allows(F, d["allow"], kw.get("soff"), kw.get("allows")) >= 0
+    else:
+        (planes, soff), per_stream = lanes_args(d), not d["lanes_one_plane"]
+        fl, ce, rose = lm.model_batch(p, mv, off, sd, planes, soff)
+        owned = lm.frame_planes(F, planes, soff) >= 0
+    pf, pc = plain_scan(d)
+    if check_sources:
+        if (p.vectors_needed & 0xFF) == 0:
+            assert ce[owned].tolist() == pc[owned].tolist() and not ce[~owned].any(), (kernel, "consequence F", d["it"])
+        else:
+            ofl, oce = dm.oracle_batch(p, mv, off, sd, **kw) if kernel == "dir" else lm.oracle_batch(p, mv, off, sd, planes, soff)
+            assert oce.tolist() == ce.tolist() and ofl.tolist() == fl.tolist(), (kernel, "consequence C", d["it"])
+        assert rose.sum(axis=1).tolist() == np.where(owned, dm.counting_moving(p, mv, off, sd), 0).tolist(), (kernel, "B", d["it"])
+    return dict(flags=fl, centres=ce, rose=rose, plain=(pf, pc), total=int(ce.sum(dtype=np.uint64)) + int(pc.sum(dtype=np.uint64)),
+                flag_off=int((owned & (pf != 0) & (fl == 0)).sum()), per_stream=per_stream, behind=int((~owned).sum()) if per_stream else 0)
+
+
 def expected(d, kernel, check_sources=False):
     """The expected outputs of `kernel` on draw d and "total", the sum of the centre counts they hold.  check_sources:
     assert that the second, independent source agrees — the sweep: the oracle and sweep_counts_np on every setting; the
@@ -338,7 +425,9 @@ def expected(d, kernel, check_sources=False):
     with its candidate-by-candidate mode_of, and consequence C of include/mtgpu_gmc.h against the oracle on every frame
     whose src + (gx, gy) stays in int16.  The compensated scan adds "compensated" (frames with gx or gy != 0),
     "compensated_with_centres" and "found_not_applied" (a mode != 0 on an axis whose g is 0).  The two blob scans:
-    _expected_blobs."""
+    _expected_blobs.  The direction scan and the plane scan: _expected_dir; their "total" adds the plain scan's counts,
+    which the GPU run also holds allow 0xFF and a plane of 0xFF to.  The flow map (on d["soff"]): lanes_model.flow_map,
+    "total" its sum; check_sources: per stream its sums are the sums of the roses of the stream's frames (G)."""
     p, mv, off, sd = d["params"], d["mv"], d["off"], d["sd"]
     if kernel == "gmc":
         mv, ms, q8 = d["gmc_mv"], d["gmc_max_shift"], d["gmc_share_q8"]
@@ -357,6 +446,16 @@ def expected(d, kernel, check_sources=False):
                     compensated=int(comp.sum()), compensated_with_centres=int((comp & (ce > 0)).sum()), found_not_applied=int(lost.sum()))
     if kernel in ("blobs", "gmc_blobs"):
         return _expected_blobs(d, kernel, check_sources)
+    if kernel in ("dir", "lanes"):
+        return _expected_dir(d, kernel, check_sources)
+    if kernel == "flow":
+        flow = lm.flow_map(p, mv, off, sd, d["soff"])
+        if check_sources:
+            rose = dm.model_batch(p, mv, off, sd)[2]
+            for st in range(len(d["soff"]) - 1):
+                a, b = int(d["soff"][st]), int(d["soff"][st + 1])
+                assert flow[st].sum(axis=(1, 2)).tolist() == rose[a:b].sum(axis=0, dtype=np.uint64).tolist(), ("flow G", d["it"], st)
+        return dict(flow=flow, total=int(flow.sum(dtype=np.uint64)))
     if kernel == "sweep":
         T, V, F = len(d["thr"]), len(d["vec"]), len(sd)
         want, memo = np.zeros((T, V, F), dtype=np.uint32), {}

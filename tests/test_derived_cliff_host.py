@@ -29,17 +29,35 @@ def test_pixel_coordinates_of_every_shape_stay_inside_int16():
 def test_shape_is_the_last_one_that_fits(kernel, name):
     """The kernel's preview and plan_preview succeed; one more row (tall) or column (wide) is MT_ERR_UNSUPPORTED, and
     the LDS left over is less than what that row or column would add.  The sweep's lds_bytes includes a mask buffer that
-    takes whatever room is left, so its need is stated with the three-row minimum the plan falls back to."""
+    takes whatever room is left, so its need is stated with the three-row minimum the plan falls back to.  The plane scan's
+    "staged" shapes are the last ones whose plane rows fit as well — one more is supported, unstaged, and a shape of its
+    own — and its last shapes are the direction scan's; `staged` is asserted on each."""
     gw, gh, kind = dci.shapes(kernel)[name]
     p = dci.grid_params(gw, gh)
     pv = dci.kernel_preview(kernel, p)
     assert pv is not None and dci.creatable(p) and pv["lds_bytes"] <= LDS
-    more = dci.one_more(gw, gh, kind)
+    more = dci.one_more(gw, gh, dci.grows(name) if kernel == "lanes" else kind)
     p_more = dci.grid_params(*more)
     assert dci.creatable(p_more)                                     # the GPU test creates a context for it
     if kernel == "activity":
         assert pv["lds_bytes"] == dci.act_lds(gw, gh, pv["acc_bits"])
         i = dci.ACT_OUTCOMES.index((pv["acc_bits"], 2 * pv["lds_bytes"] <= LDS))
+    if kernel == "lanes":
+        # staged up to the "staged" shape, read from memory from the "unstaged" one on, up to the direction scan's limit
+        staged = "-staged-" in name
+        assert pv["staged"] == (1 if staged else 0) and pv["lds_bytes"] == dci.lanes_lds(gw, gh, staged)
+        assert pv["plane_bytes"] == gw * gh
+        if "-unstaged-" in name:
+            before = (gw - 1, gh) if dci.grows(name) == "wide" else (gw, gh - 1)
+            assert dci.kernel_preview(kernel, dci.grid_params(*before))["staged"] == 1
+            return
+        if staged:
+            pm = dci.kernel_preview(kernel, p_more)
+            assert pm is not None and pm["staged"] == 0 and more + ("plan",) in dci.shapes(kernel).values()
+            used = dci.lanes_lds(gw, gh, True)
+            assert 0 <= LDS - used < dci.lanes_lds(*more, True) - used
+            return
+        assert (gw, gh, kind) in dci.shapes("dir").values()          # the last unstaged grid is the direction scan's limit
     if kind == "plan":
         # not the last shape of the map, but the last (or, "past": the first) of its plan outcome
         bits, two = dci.ACT_OUTCOMES[i]
@@ -59,7 +77,7 @@ def test_shape_is_the_last_one_that_fits(kernel, name):
         W = (gw + 63) // 64
         assert spv["thresholds_per_pass"] == 1 and need == spv["lds_bytes"] - n * (ch - 1) * W * 8
         assert LDS - spv["lds_bytes"] < n * W * 8 or ch == R          # the buffer took all the room a whole row fits in
-    elif kernel in ("zones", "gmc"):
+    elif kernel in ("zones", "gmc", "dir", "lanes"):
         assert need == pv["lds_bytes"]
     else:
         assert pv["acc_bits"] == 0 and need == pv["lds_bytes"]
@@ -247,6 +265,157 @@ def test_gmc_expected_values(name):
     assert gm.gmc_batch(pp, pmv, poff, psd, 0, 128)[1].tolist() == plain.tolist()
 
 
+# ------------------------------------------------------------------ the direction scan and the plane scan
+
+def test_directed_batches_share_everything_but_the_pairs_displacements():
+    """The directed planting changes src of the planted pairs' records and nothing else: the blob frames, N, Z, the
+    permutations and the padding bytes are those of batch()."""
+    for gw, gh, _ in dci.shapes("dir").values():
+        a, b = dci.batch(gw, gh), dci.dir_batch(gw, gh)
+        assert a[3] == b[3] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+        for k in ("dst_x", "dst_y"):
+            assert np.array_equal(a[0][k], b[0][k])
+        fr = np.repeat(np.arange(len(dci.ORDER)), np.diff(a[1].astype(np.int64)))
+        blob = ~np.isin(fr, [f for f, n in enumerate(dci.ORDER) if n in a[3]])
+        assert np.array_equal(a[0].view(np.uint8).reshape(-1, 40)[blob], b[0].view(np.uint8).reshape(-1, 40)[blob])
+        assert np.array_equal(a[0].view(np.uint8).reshape(-1, 40)[:, 34:], b[0].view(np.uint8).reshape(-1, 40)[:, 34:])
+    sectors = {i % 8 for i in range(len(dci.dir_batch(65, dci.tallest("dir", 65))[3]["E"]))}
+    assert sectors == set(range(8))                                   # E alone meets every sector
+
+
+@pytest.mark.parametrize("name", list(dci.shapes("dir")))
+def test_dir_expected_values(name):
+    """The model under every byte of the chain and under the per-stream bytes equals the oracle on filtered records
+    (consequence C); 0xFF the oracle on the records as they are; the planted frames have their hand values, and under
+    0xFF those are hand_count's."""
+    import dir_model as dm
+    import oracle_binding as ob
+    c = dci.dir_case(name)
+    p, mv, off, sd, planted = c["params"], c["mv"], c["off"], c["sd"], c["planted"]
+    gw, gh = p.grid_w, p.grid_h
+    planted_is_planted(gw, gh, planted)
+    assert {0x00, 0xFF} < set(dci.DIR_CHAIN) and len(set(dci.DIR_STREAM_ALLOWS)) == 3
+    prev = None
+    for allow in dci.DIR_CHAIN + (None,):
+        fl, ce, rose = dci.dir_expected(name, allow)
+        kw = dict(soff=c["soff"], allows=c["allows"]) if allow is None else dict(allow=allow)
+        ofl, oce = dm.oracle_batch(p, mv, off, sd, **kw)
+        assert np.array_equal(ce, oce) and np.array_equal(fl, ofl), (name, allow)
+        for f, (hc, hr) in dci.dir_hand(c, allow).items():
+            assert int(ce[f]) == hc and rose[f].tolist() == hr.tolist(), (name, allow, f)
+        assert prev is None or np.array_equal(rose, prev)             # one rose whatever is allowed
+        prev = rose
+        assert rose.sum(axis=1).tolist() == dm.counting_moving(p, mv, off, sd).tolist()
+    fl, ce, _ = dci.dir_expected(name, 0xFF)
+    assert np.array_equal(ce, ob.scan_centres(p, mv, off, sd, nthreads=4)[1])
+    for f, n in enumerate(dci.ORDER):
+        if n in planted:
+            assert dci.dir_hand(c, 0xFF)[f][0] == dci.hand_count(planted[n], gw, gh, 4.0, 2) == int(ce[f])
+    if gw == 2:
+        assert not ce.any()
+        return
+    e = dci.frames_named("E")[0]
+    even, odd = (int(dci.dir_expected(name, a)[1][e]) for a in (0x55, 0xAA))
+    assert even > 0 and odd > 0 and even + odd == int(ce[e]) and int(dci.dir_expected(name, 0x00)[1][e]) == 0
+
+
+def corner_cells(gw, gh, margin=0):
+    """The first and the last cell of the first and the last analysed row."""
+    return [(0, margin), (gw - 1, margin), (0, gh - 1 - margin), (gw - 1, gh - 1 - margin)]
+
+
+@pytest.mark.parametrize("name", list(dci.shapes("lanes")))
+def test_lanes_expected_values(name):
+    """Every rotation of the three planes over the three streams: the model equals the oracle on filtered records
+    (consequence C), P_all alone the oracle on the records as they are, the planted frames have their hand values.  The
+    flow maps: per stream and per frame against the hand maps, and their sums are the roses' (G).  The corners of the
+    analysed rows hold bytes of their own, and a plane that loses its last one, two or three bytes, or arrives one byte
+    late, changes a planted frame's count — what a short or shifted staged copy would do."""
+    import lanes_model as lm
+    import oracle_binding as ob
+    c = dci.lanes_case(name)
+    p, mv, off, sd, planted = c["params"], c["mv"], c["off"], c["sd"], c["planted"]
+    gw, gh = p.grid_w, p.grid_h
+    assert "E" in c["whole"] and m.lanes_preview(p)["staged"] == (1 if "-staged-" in name else 0)
+    plain = ob.scan_centres(p, mv, off, sd, nthreads=4)[1]
+    assert np.array_equal(lm.model_batch(p, mv, off, sd, c["planes"]["all"])[1], plain)
+    st = zi.stream_of_frames(c["soff"], len(sd))
+    for rot in dci.LANES_ROTATIONS:
+        fl, ce, rose = dci.lanes_expected(name, rot)
+        ofl, oce = lm.oracle_batch(p, mv, off, sd, dci.lanes_stack(c, rot), c["soff"])
+        assert np.array_equal(ce, oce) and np.array_equal(fl, ofl), (name, rot)
+        under_all = np.array([rot[s] == "all" for s in st])
+        assert np.array_equal(ce[under_all], plain[under_all])
+        for f, (hc, hr) in dci.lanes_hand(c, rot).items():
+            assert (hc is None or int(ce[f]) == hc) and rose[f].tolist() == hr.tolist(), (name, rot, f)
+    hands = [h[0] for rot in dci.LANES_ROTATIONS for h in dci.lanes_hand(c, rot).values()]
+    assert hands.count(None) < len(hands) // 2 and (gw == 2 or (0 in hands and max(x or 0 for x in hands) > 0))
+    # the flow maps
+    each = dci.flow_expected(name, dci.FLOW_EACH)
+    for f, n in enumerate(dci.ORDER):
+        if n in planted:
+            assert np.array_equal(each[f], dci.hand_flow(planted[n], gw, gh)), (name, f)
+    assert not each[dci.frames_named("N")[0]].any() and not each[dci.frames_named("Z")[0]].any()
+    per_stream = dci.flow_expected(name, dci.ZONE_SOFF)
+    rose = dci.lanes_expected(name, dci.LANES_ROTATIONS[0])[2]
+    for s in range(3):
+        a, b = dci.ZONE_SOFF[s], dci.ZONE_SOFF[s + 1]
+        assert np.array_equal(per_stream[s], each[a:b].sum(axis=0))
+        assert per_stream[s].sum(axis=(1, 2)).tolist() == rose[a:b].sum(axis=0, dtype=np.uint64).tolist()
+    if gw == 2:
+        return                                                        # no column can hold a centre: the planes decide no count
+    own = c["planes"]["own"]
+    corners = [int(own[y, x]) for x, y in corner_cells(gw, gh)]
+    # (on three columns the right corners are pairs 0 and 1 of H: the bytes of pairs 0 and 1 of E)
+    assert all(corners) and (gh == 1 or len(set(corners)) >= (3 if gw > 4 else 2)), (name, corners)
+    # the control: what a staged copy that drops tail bytes, or starts one byte late, would hand the vote
+    frames = dci.frames_named("E") + dci.frames_named("H")
+    for kind, want_rot in (("own", dci.LANES_ROTATIONS[2]), ("all", dci.LANES_ROTATIONS[1])):
+        s = want_rot.index(kind)
+        mine = [f for f in frames if st[f] == s]
+        want = dci.lanes_expected(name, want_rot)[1]
+        for cut in (1, 2, 3) if gw > 4 else (3,):                     # (three columns: the last column's pair holds no centre)
+            short = c["planes"][kind].copy().reshape(-1)
+            short[-cut:] = 0
+            got = lm.model_batch(p, mv, off, sd, np.stack([short.reshape(gh, gw)] * 3), c["soff"])[1]
+            assert any(got[f] != want[f] for f in mine), (name, kind, cut)
+    late = np.roll(own.reshape(-1), 1).reshape(gh, gw)
+    s = dci.LANES_ROTATIONS[2].index("own")
+    got = lm.model_batch(p, mv, off, sd, np.stack([late] * 3), c["soff"])[1]
+    want = dci.lanes_expected(name, dci.LANES_ROTATIONS[2])[1]
+    assert any(got[f] != want[f] for f in frames if st[f] == s), name
+
+
+def test_plane_base_phases_cover_every_combination():
+    """Over the runs of test_lanes_plane_base_phases the source's phase inside a 32-bit word and the number of copied
+    bytes modulo 4 take all sixteen combinations; every run but tall-65 of the unstaged limit is staged; the variant with
+    a margin keeps the planted pairs on its analysed rows, where a plane whose rows are taken from gy - (y_lo - 1) in
+    place of gy - y_lo — one row late — changes a planted frame's count."""
+    import lanes_model as lm
+    seen = set()
+    for name, margin in dci.phase_runs():
+        gw, gh, kind = dci.shapes("lanes")[name]
+        c = dci.lanes_case(name, margin)
+        assert m.lanes_preview(c["params"])["staged"] == (0 if kind == "tall" else 1) and c["params"].vertical_margin == margin
+        if kind != "tall":
+            seen |= dci.phase_pairs(gw, gh, margin)
+    assert seen == {(a, b) for a in range(4) for b in range(4)}
+    assert sum(1 for _, mg in dci.phase_runs() if mg) == 1 and len(dci.phase_runs()) == 8
+    name, margin = [r for r in dci.phase_runs() if r[1]][0]
+    c = dci.lanes_case(name, margin)
+    p, gw, gh = c["params"], c["params"].grid_w, c["params"].grid_h
+    own = c["planes"]["own"]
+    assert all(int(own[y, x]) for x, y in corner_cells(gw, gh, margin)) and not own[:margin].any() and not own[gh - margin:].any()
+    rot = dci.LANES_ROTATIONS[2]
+    want = dci.lanes_expected(name, rot, margin)
+    for f, (hc, hr) in dci.lanes_hand(c, rot).items():
+        assert (hc is None or int(want[1][f]) == hc) and want[2][f].tolist() == hr.tolist()
+    row_late = np.roll(own, -1, axis=0)                               # the byte of row gy + 1 where row gy's is wanted
+    got = lm.model_batch(p, c["mv"], c["off"], c["sd"], np.stack([row_late] * 3), c["soff"])[1]
+    e = dci.frames_named("E")[0]
+    assert int(want[1][e]) > 0 and got[e] != want[1][e]
+
+
 # ------------------------------------------------------------------ the soak's draws
 
 SOAK_REPLAYED = 40
@@ -409,6 +578,84 @@ def test_soak_draws_reach_the_blob_scans():
         assert c["multi"] >= 1 and c["flag_off"] >= 1 and c["flag_kept"] >= 1, (k, c)
         assert 1 <= c["masked"] < c["supported"] and c["behind"] >= 1 and c["vn0"] >= 1, (k, c)
     assert {0, 1} <= pool and max(pool) >= 40
+
+
+# sha256 (first 16 hex digits) over draw_digest_with_gmc and the blob scans' min_blob_cells and mask decision of the default
+# seed's first eight draws, as draw() made them before the direction scan, the plane scan and the flow map joined the soak
+DRAWS_BEFORE_DIR = ["86b018d452f6ec74", "c4252deebcbf5bf6", "17f93285a47ae65e", "73b424478bc157f9", "ea20f336fcf7fdb5",
+                    "1c67ddf09c4c5e04", "f1b10d3462f80db8", "6c42a8f906a8a7b3"]
+
+
+def draw_digest_with_blobs(d):
+    import hashlib
+    h = hashlib.sha256(draw_digest_with_gmc(d).encode())
+    for k in ("min_blob_cells", "blob_masked"):
+        h.update(repr(d.get(k)).encode())
+    return h.hexdigest()[:16]
+
+
+def test_soak_draws_are_what_they_were_before_the_direction_scans_joined():
+    """The allow bytes, the planes and the forms of the calls come from a RandomState of their own, seeded apart from
+    draw_gmc's and draw_blobs': `rng`, the compensated scan's inputs and the blob scans' settings are what they were."""
+    rng = np.random.RandomState(dsoak.DEFAULT_SEED)
+    for it, want in enumerate(DRAWS_BEFORE_DIR, start=1):
+        d = dsoak.draw(rng, it)
+        assert draw_digest_with_blobs(d) == want, it
+    a, b = dsoak.replay(dsoak.DEFAULT_SEED, 5), dsoak.replay(dsoak.DEFAULT_SEED, 5)
+    assert (a["allow"], a["dir_per_stream"], a["lanes_one_plane"], a["plane_kinds"]) == (b["allow"], b["dir_per_stream"], b["lanes_one_plane"], b["plane_kinds"])
+    assert np.array_equal(a["allows"], b["allows"]) and np.array_equal(a["planes"], b["planes"])
+    S = len(a["zsoff"]) - 1
+    assert a["allows"].shape == (S,) and a["planes"].shape == (S, a["params"].grid_h, a["params"].grid_w) and a["planes"].dtype == np.uint8
+    picks = {(x["allow"], x["dir_per_stream"], x["lanes_one_plane"]) for x in (dsoak.draw_dir(s, 5, a["params"], S) for s in range(12))}
+    assert len(picks) > 3                                            # other seeds draw other settings for the same iteration
+    # the fourth state is neither draw_gmc's nor draw_blobs'
+    streams = [np.random.RandomState([dsoak.DEFAULT_SEED, 5] + salt).randint(0, 2 ** 31, size=4).tolist()
+               for salt in ([], [dsoak.BLOBS_SALT], [dsoak.DIR_SALT])]
+    assert len({tuple(x) for x in streams}) == 3
+
+
+DIR_REPLAYED = 60
+
+
+def test_soak_draws_reach_the_direction_scans():
+    """The default seed's first 60 iterations, from the models alone.  Each of the direction scan, the plane scan and the
+    flow map is supported in at least three quarters of the creatable draws; in at least a third of the supported draws
+    the drawn byte or plane turns off a flag the plain scan sets; the scalar and the per-stream form of the direction
+    call, and the one-plane and the per-stream form of the plane call, all occur.  Measured: 60 creatable, 47 supported,
+    a flag turned off in 22 (bytes) and 16 (planes), 23 and 33 per-stream calls, one unstaged plane call — which is
+    reported and not asserted: tests/test_gpu_derived_cliff.py carries that form."""
+    rng = np.random.RandomState(dsoak.DEFAULT_SEED)
+    creatable = 0
+    n = {k: dict(supported=0, flag_off=0, per_stream=0, behind=0, vn0=0) for k in ("dir", "lanes")}
+    flow = dict(supported=0, nonzero=0)
+    unstaged, bytes_seen, kinds_seen = 0, set(), set()
+    for it in range(1, DIR_REPLAYED + 1):
+        d = dsoak.draw(rng, it)
+        creatable += d["creatable"]
+        for k in n:
+            if not d["support"].get(k):
+                continue
+            e = dsoak.expected(d, k)
+            n[k]["supported"] += 1
+            n[k]["vn0"] += (d["params"].vectors_needed & 0xFF) == 0
+            for c in ("flag_off", "behind"):
+                n[k][c] += e[c] > 0
+            n[k]["per_stream"] += e["per_stream"]
+        if d["support"].get("dir"):
+            bytes_seen |= {d["allow"]} | set(d["allows"].tolist())
+        if d["support"].get("lanes"):
+            unstaged += d["lanes_staged"] == 0
+            kinds_seen |= set(d["plane_kinds"])
+        if d["support"].get("flow"):
+            flow["supported"] += 1
+            flow["nonzero"] += dsoak.expected(d, "flow")["total"] > 0
+    print("creatable", creatable, n, "flow", flow, "unstaged plane calls", unstaged, "bytes seen", sorted(bytes_seen))
+    for k, c in n.items():
+        assert 4 * c["supported"] >= 3 * creatable and c["supported"] < creatable, (k, c)
+        assert 3 * c["flag_off"] >= c["supported"], (k, c)
+        assert 1 <= c["per_stream"] < c["supported"] and c["behind"] >= 1 and c["vn0"] >= 1, (k, c)
+    assert 4 * flow["supported"] >= 3 * creatable and 2 * flow["nonzero"] >= flow["supported"]
+    assert {0x00, 0xFF} <= bytes_seen and kinds_seen == set(dsoak.PLANE_KINDS)
 
 
 def test_soak_preview_says_unsupported_as_the_library_does():

@@ -513,3 +513,23 @@ def test_random_draws_count_something():
         sectors += rose.sum(axis=0).astype(np.int64)
     assert seen_vn == {0, 1, 2, 3} and seen_margin == {0, 1, 2, 3}
     assert with_centres >= 30 and losing >= 20 and (sectors > 0).all()
+
+
+def test_a_skipped_first_record_moves_a_bin_of_every_edge_frame():
+    """What test_unaligned_40_byte_base (tests/test_gpu_dir.py, tests/test_gpu_lanes.py) would see of a streamer whose
+    branch for a base off the 8-byte grid starts at record 1: every test frame with records loses one count in the bin of
+    its record 0, which is sector 0 — and of a streamer that reads record 0 twice: one count more.  Neighbouring records
+    lie in different sectors, so no other record's bin hides either."""
+    c = di.edge_case()
+    p, mv, off, sd = c["params"], c["mv"], c["off"], c["sd"]
+    rose = dm.model_batch(p, mv, off, sd, allow=c["allow"])[2].astype(np.int64)
+    lens = np.diff(off.astype(np.int64))
+    keep = np.ones(len(mv), dtype=bool)
+    keep[off[:-1][lens > 0].astype(np.int64)] = False
+    cut_off = np.concatenate([[0], np.cumsum(lens - (lens > 0))]).astype(np.uint64)
+    cut = dm.model_batch(p, mv[keep], cut_off, sd, allow=c["allow"])[2].astype(np.int64)
+    test = c["test"][lens[c["test"]] > 0]
+    assert len(test) == 16 * (len(di.EDGE_LENGTHS) - 1)
+    assert ((rose - cut)[test] == np.eye(8, dtype=np.int64)[0]).all()
+    i = np.arange(max(di.EDGE_LENGTHS) - 1)
+    assert (((i + i // 8) % 8) != ((i + 1 + (i + 1) // 8) % 8)).all()

@@ -1,7 +1,8 @@
-"""GPU tier (`-m gpu`): the sweep, the activity map, the masked scan and the compensated scan on the last grids their LDS
-layouts hold — two, three, 65 and 193 columns at the largest height, one and three rows at the largest width, and for
-the activity map the last and the first grid of every plan outcome — through the C ABI's device entry points on both
-record layouts.
+"""GPU tier (`-m gpu`): the sweep, the activity map, the masked scan, the compensated scan, the direction scan and the
+plane scan (with the flow map) on the last grids their LDS layouts hold — two, three, 65 and 193 columns at the largest
+height, one and three rows at the largest width, for the activity map the last and the first grid of every plan
+outcome, and for the plane scan the last grid of its staged form and the first one behind it — through the C ABI's
+device entry points on both record layouts.
 
 The shapes, the batches and the values derived by hand come from tests/derived_cliff_inputs.py, which finds the shapes
 with the previews at 163 840 bytes of LDS; tests/test_derived_cliff_host.py proves without a GPU that they sit on the
@@ -179,3 +180,122 @@ def test_gmc_at_the_lds_limit(gpu_scanner_factory, name):
     inf = torch.full((F, 5), JUNK, dtype=torch.int32, device="cuda")
     refused(lambda: more.scan_gmc_device(d_rec, d_off, d_sd, 16, 128, compact=True, flags=fl, centres=ce, info=inf))
     assert untouched(fl, JUNK_FLAG) and untouched(ce, JUNK) and untouched(inf, JUNK)
+
+
+# ------------------------------------------------------------------ the direction scan
+
+@pytest.mark.parametrize("name", list(dci.shapes("dir")))
+def test_dir_at_the_lds_limit(gpu_scanner_factory, name):
+    """The rose words are the last things in the LDS, behind the tile, the mask plane and the totals: on the last grid
+    that fits, the directed batch under nothing, the even sectors, the odd sectors and everything, then under one byte
+    per stream — flags, centres and roses against the numpy model (== the oracle on filtered records, on the CPU), the
+    planted frames against their hand values — then the grid one row or column further."""
+    from test_gpu_dir import assert_equals_model, device_dir, junk_outputs
+    assert_lds_limit(gpu_scanner_factory)
+    gw, gh, kind = dci.shapes("dir")[name]
+    c = dci.dir_case(name)
+    s = gpu_scanner_factory(c["params"])
+    for compact in (False, True):
+        d_rec, d_off, d_sd = to_device(c["mv"], c["off"], c["sd"], compact)
+        for allow in dci.DIR_CHAIN + (None,):
+            kw = dict(soff=c["soff"], allows=c["allows"]) if allow is None else dict(allow=allow)
+            label = f"{name} allow {'per stream' if allow is None else hex(allow)} compact {compact}"
+            got = device_dir(s, d_rec, d_off, d_sd, compact, **kw)
+            assert_equals_model(got, dci.dir_expected(name, allow), label)
+            for f, (hc, hr) in dci.dir_hand(c, allow).items():
+                assert int(got[1][f]) == hc and got[2][f].tolist() == hr.tolist(), (label, "planted frame", f)
+    more = gpu_scanner_factory(dci.grid_params(*dci.one_more(gw, gh, kind), **dci.CTX_KW))
+    out = junk_outputs(len(c["sd"]))
+    refused(lambda: more.scan_dir_device(d_rec, d_off, d_sd, allow=0xFF, compact=True, out=out))
+    assert untouched(out["flags"], JUNK_FLAG) and untouched(out["centres"], JUNK) and untouched(out["rose"], JUNK)
+
+
+# ------------------------------------------------------------------ the plane scan and the flow map
+
+def planes_at(planes, shift):
+    """The planes in device memory `shift` bytes behind an allocation's start, as a contiguous uint8 tensor (what
+    test_gpu_derived_edges.shifted does for records, whose shifts are 4 modulo 8; a plane takes any byte)."""
+    import torch
+    flat = np.ascontiguousarray(planes, dtype=np.uint8).reshape(-1)
+    room = torch.zeros(flat.size + 8, dtype=torch.uint8, device="cuda")
+    assert room.data_ptr() % 16 == 0
+    view = room[shift:shift + flat.size]
+    view.copy_(torch.from_numpy(flat.copy()))
+    assert view.data_ptr() % 4 == shift % 4 and view.is_contiguous()
+    return view
+
+
+def device_lanes_at(s, d_rec, d_off, d_sd, compact, planes, soff, shift):
+    """Through mtgpu_scan_lanes_device with the plane tensor at `shift`, into junk-filled outputs."""
+    import torch
+    from test_gpu_dir import junk_outputs
+    n = d_off.numel() - 1
+    out = junk_outputs(n)
+    d_planes = planes_at(planes, shift)
+    torch.cuda.synchronize()
+    s.scan_lanes_device(d_rec, d_off, d_sd, d_planes, d_stream_off=soff_tensor(soff), compact=compact, out=out)
+    torch.cuda.synchronize()
+    return out["flags"].cpu().numpy(), out["centres"].cpu().numpy().view(np.uint32), out["rose"].cpu().numpy().view(np.uint32).reshape(n, 8)
+
+
+def assert_lanes_case(s, c, name, rotation, want, d_rec, d_off, d_sd, compact, shift):
+    from test_gpu_dir import assert_equals_model
+    label = f"{name} planes {rotation} at byte {shift} compact {compact}"
+    got = device_lanes_at(s, d_rec, d_off, d_sd, compact, dci.lanes_stack(c, rotation), c["soff"], shift)
+    assert_equals_model(got, want, label)
+    for f, (hc, hr) in dci.lanes_hand(c, rotation).items():
+        assert (hc is None or int(got[1][f]) == hc) and got[2][f].tolist() == hr.tolist(), (label, "planted frame", f)
+
+
+@pytest.mark.parametrize("name", list(dci.shapes("lanes")))
+def test_lanes_at_the_lds_limit(gpu_scanner_factory, name):
+    """The staged plane rows are the last bytes of the LDS: on the last staged grid, the first unstaged one and the last
+    one that fits at all, three streams under P_all, P_own and P_half in every rotation (stream s reads plane s, whose
+    rows start (s gh) gw bytes into the tensor; the tensor starts 1, 2 and 3 bytes behind an allocation) — flags,
+    centres and roses against the numpy model (== the oracle on filtered records, on the CPU), the planted frames against
+    their hand values: the corner pairs hold the first and the last bytes of the copy.  Then the flow map of the same
+    batch per stream and per frame, the planted frames' maps by hand; then, on the last grid, one row or column further."""
+    from test_gpu_dir import junk_outputs
+    from test_gpu_lanes import assert_flow_equal, device_flow
+    import torch
+    assert_lds_limit(gpu_scanner_factory)
+    gw, gh, kind = dci.shapes("lanes")[name]
+    c = dci.lanes_case(name)
+    assert m.lanes_preview(c["params"])["staged"] == (1 if "-staged-" in name else 0)
+    s = gpu_scanner_factory(c["params"])
+    for compact in (False, True):
+        d_rec, d_off, d_sd = to_device(c["mv"], c["off"], c["sd"], compact)
+        for i, rot in enumerate(dci.LANES_ROTATIONS):
+            assert_lanes_case(s, c, name, rot, dci.lanes_expected(name, rot), d_rec, d_off, d_sd, compact, i + 1)
+        for soff in (dci.ZONE_SOFF, dci.FLOW_EACH):
+            got = device_flow(s, d_rec, d_off, d_sd, compact, list(soff))
+            assert_flow_equal(got, dci.flow_expected(name, soff), f"{name} flow map, {len(soff) - 1} streams, compact {compact}")
+        for f, n in enumerate(dci.ORDER):                            # got: one stream per frame
+            if n in c["planted"]:
+                assert np.array_equal(got[f], dci.hand_flow(c["planted"][n], gw, gh)), (name, "planted frame's flow map", f)
+    if kind == "plan":
+        return
+    mw, mh = dci.one_more(gw, gh, kind)
+    more = gpu_scanner_factory(dci.grid_params(mw, mh, **dci.CTX_KW))
+    out = junk_outputs(len(c["sd"]))
+    d_planes = planes_at(np.full((3, mh, mw), 0xFF, dtype=np.uint8), 0)
+    refused(lambda: more.scan_lanes_device(d_rec, d_off, d_sd, d_planes, d_stream_off=soff_tensor(c["soff"]), compact=True, out=out))
+    assert untouched(out["flags"], JUNK_FLAG) and untouched(out["centres"], JUNK) and untouched(out["rose"], JUNK)
+    flow = torch.full((3, 8, mh, mw), JUNK, dtype=torch.int32, device="cuda")
+    refused(lambda: more.flow_map_device(d_rec, d_off, d_sd, soff_tensor(c["soff"]), compact=True, out=flow))
+    assert untouched(flow, JUNK)
+
+
+@pytest.mark.parametrize("name,margin", dci.phase_runs(), ids=[f"{n}-margin{mg}" for n, mg in dci.phase_runs()])
+def test_lanes_plane_base_phases(gpu_scanner_factory, name, margin):
+    """The three-stream call with the plane tensor 0, 1, 2 and 3 bytes behind an allocation's start: over the runs the
+    staged copy meets every source phase with 0, 1, 2 and 3 tail bytes (tests/test_derived_cliff_host.py).  The run with a
+    margin copies rows y_lo .. y_hi - 1 only, and its planted pairs sit on those rows."""
+    assert_lds_limit(gpu_scanner_factory)
+    c = dci.lanes_case(name, margin)
+    s = gpu_scanner_factory(c["params"])
+    want = dci.lanes_expected(name, dci.PHASE_ROTATION, margin)
+    for shift in dci.PHASE_SHIFTS:
+        compact = bool(shift % 2)
+        d_rec, d_off, d_sd = to_device(c["mv"], c["off"], c["sd"], compact)
+        assert_lanes_case(s, c, f"{name} margin {margin}", dci.PHASE_ROTATION, want, d_rec, d_off, d_sd, compact, shift)

@@ -270,6 +270,25 @@ def test_hand_cases_through_sweep_and_activity_map(gpu_scanner_factory, name, kw
     assert_maps_parity(s, mv, off, sd, [0, 1], maps[:3], name, host=False)
 
 
+@pytest.mark.parametrize("name,kw,case", load_hand_cases()[1], ids=id_of)
+def test_hand_cases_through_direction_and_plane_scans(gpu_scanner_factory, name, kw, case):
+    """The same hand-derived answers through the direction scan with every sector allowed and through the plane scan
+    with a plane of 0xFF, in a context created with the case's own parameters: centre count and flag by hand, on both
+    record layouts."""
+    from test_gpu_dir import device_dir
+    from test_gpu_lanes import device_lanes
+    p = m.ScanParams.from_config(**kw)
+    mv, off, sd, hand = dei.hand_case_batch(case)
+    flag = int(case["expect"]) if sd[0] else 0
+    s = gpu_scanner_factory(p)
+    for compact in (False, True):
+        d_rec, d_off, d_sd = to_device(mv, off, sd, compact)
+        fl, ce, _ = device_dir(s, d_rec, d_off, d_sd, compact, allow=0xFF)
+        assert (ce.tolist(), fl.tolist()) == ([hand], [flag]), (name, "direction scan", compact)
+        fl, ce, _ = device_lanes(s, d_rec, d_off, d_sd, compact, np.full((p.grid_h, p.grid_w), 0xFF, dtype=np.uint8))
+        assert (ce.tolist(), fl.tolist()) == ([hand], [flag]), (name, "plane scan", compact)
+
+
 def test_hand_cases_one_batch_through_sweep_and_activity_map(gpu_scanner_factory):
     """The cases that share the base parameters as ONE batch, one stream per frame: the centre plane of stream i sums
     to case i's hand value."""

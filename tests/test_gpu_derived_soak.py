@@ -1,8 +1,9 @@
 """Soak of the derived kernels: randomised parity of the sweep, the activity map, the masked scan, the compensated scan,
-the blob scan and the compensated blob scan for MTGPU_SOAK_SECONDS (default 4 s; set it to minutes to hunt rare faults).
+the blob scan, the compensated blob scan, the direction scan, the plane scan and the flow map for MTGPU_SOAK_SECONDS
+(default 4 s; set it to minutes to hunt rare faults).
 Every iteration draws a grid, a parameter set, a ragged batch with runs and blobs, streams with empty ones, keep masks,
 sweep settings, a pan per frame with max_shift and min_share_q8, a minimum blob size, whether the blob scans are masked,
-a record layout and — every third time — a record base inside a larger buffer
+an allow byte, bytes and planes per stream with the forms of their calls, a record layout and — every third time — a record base inside a larger buffer
 (tests/derived_soak.py, which also computes the expected values from the oracle and the numpy models and rebuilds any
 iteration on the CPU: derived_soak.replay(seed, it)).  Every comparison is exact; a kernel whose preview says
 unsupported must answer MT_ERR_UNSUPPORTED and touch nothing."""
@@ -21,7 +22,10 @@ from scan_checks import assert_counts_equal
 from test_gpu_activity import assert_maps_equal, junk_maps
 from test_gpu_derived_cliff import assert_lds_limit
 from test_gpu_derived_edges import shifted
+from test_gpu_dir import assert_equals_model
+from test_gpu_dir import junk_outputs as dir_junk_outputs
 from test_gpu_gmc import assert_info_equal
+from test_gpu_lanes import assert_flow_equal, odd_planes
 from test_gpu_zones import keep_tensor, soff_tensor
 
 pytestmark = pytest.mark.gpu
@@ -150,6 +154,69 @@ def check_draw(s, d, where):
         else:
             expect_unsupported(call, list(out.values()), [{"flags": JUNK_FLAG, "box": gb.JUNK_BOX}.get(k, JUNK) for k in out], kernel + ", " + where)
             reached[kernel] = None
+    # the direction scan and the plane scan on the draw's records, layout and base: the drawn byte(s) or plane(s) in the
+    # drawn form, then allow 0xFF and a plane of 0xFF, which must give the oracle's plain counts
+    def rose_outputs(out):
+        return out["flags"].cpu().numpy(), out["centres"].cpu().numpy().view(np.uint32), out["rose"].cpu().numpy().view(np.uint32).reshape(F, 8)
+
+    junks = [JUNK_FLAG, JUNK, JUNK]
+    z_soff = soff_tensor(d["zsoff"])
+    out = dir_junk_outputs(F)
+    if d["dir_per_stream"]:
+        d_allow = torch.from_numpy(np.concatenate([d["allows"], np.zeros(1, dtype=np.uint8)])).cuda()
+        call = lambda: s.scan_dir_device(d_rec, d_off, d_sd, d_stream_off=z_soff, d_allow=d_allow, compact=compact, out=out)   # noqa: E731
+        what = f"dir streams {d['zsoff'].tolist()} bytes {d['allows'].tolist()}, {where}"
+    else:
+        call = lambda: s.scan_dir_device(d_rec, d_off, d_sd, allow=d["allow"], compact=compact, out=out)   # noqa: E731
+        what = f"dir byte {d['allow']:#x}, {where}"
+    if d["support"]["dir"]:
+        call()
+        torch.cuda.synchronize()
+        e = dsoak.expected(d, "dir")
+        assert_equals_model(rose_outputs(out), (e["flags"], e["centres"], e["rose"]), what)
+        out = dir_junk_outputs(F)
+        s.scan_dir_device(d_rec, d_off, d_sd, allow=0xFF, compact=compact, out=out)
+        torch.cuda.synchronize()
+        fl, ce, _ = rose_outputs(out)
+        assert_counts_equal(ce, e["plain"][1], "dir byte 0xff against the oracle, " + where, got_f=fl, want_f=e["plain"][0])
+        reached["dir"] = e
+    else:
+        expect_unsupported(call, list(out.values()), junks, "dir, " + where)
+        reached["dir"] = None
+    out = dir_junk_outputs(F)
+    S = len(d["zsoff"]) - 1
+    planes = d["planes"] if d["planes"] is not None else np.full((S, gh, gw), 0xFF, dtype=np.uint8)
+    if d["lanes_one_plane"]:
+        d_planes = odd_planes(planes[0])
+        call = lambda: s.scan_lanes_device(d_rec, d_off, d_sd, d_planes, compact=compact, out=out)   # noqa: E731
+        what = f"lanes one plane ({(d['plane_kinds'] or ['-'])[0]}), {where}"
+    else:
+        d_planes = odd_planes(planes)
+        call = lambda: s.scan_lanes_device(d_rec, d_off, d_sd, d_planes, d_stream_off=z_soff, compact=compact, out=out)   # noqa: E731
+        what = f"lanes streams {d['zsoff'].tolist()} planes {d['plane_kinds']}, {where}"
+    if d["support"]["lanes"]:
+        call()
+        torch.cuda.synchronize()
+        e = dsoak.expected(d, "lanes")
+        assert_equals_model(rose_outputs(out), (e["flags"], e["centres"], e["rose"]), what)
+        out = dir_junk_outputs(F)
+        s.scan_lanes_device(d_rec, d_off, d_sd, odd_planes(np.full((gh, gw), 0xFF, dtype=np.uint8)), compact=compact, out=out)
+        torch.cuda.synchronize()
+        fl, ce, _ = rose_outputs(out)
+        assert_counts_equal(ce, e["plain"][1], "lanes plane 0xff against the oracle, " + where, got_f=fl, want_f=e["plain"][0])
+        reached["lanes"] = dict(e, unstaged=int(d["lanes_staged"] == 0))
+    else:
+        expect_unsupported(call, list(out.values()), junks, "lanes, " + where)
+        reached["lanes"] = None
+    # the flow map over the activity map's streams
+    flow = torch.full((len(d["soff"]) - 1, 8, gh, gw), JUNK, dtype=torch.int32, device="cuda")
+    call = lambda: s.flow_map_device(d_rec, d_off, d_sd, soff_tensor(d["soff"]), compact=compact, out=flow)   # noqa: E731
+    if d["support"]["flow"]:
+        call()
+        torch.cuda.synchronize()
+        assert_flow_equal(flow.cpu().numpy().view(np.uint32), dsoak.expected(d, "flow")["flow"], f"flow map streams {d['soff'].tolist()}, {where}")
+    else:
+        expect_unsupported(call, [flow], [JUNK], "flow, " + where)
     return reached
 
 
@@ -163,6 +230,7 @@ def test_soak_derived_kernels(gpu_scanner_factory):
     ran = {k: 0 for k in dsoak.KERNELS}
     gmc = dict(compensated=0, compensated_with_centres=0, found_not_applied=0)
     blobs = {k: dict(multi=0, flag_off=0, flag_kept=0, masked=0, behind=0) for k in ("blobs", "gmc_blobs")}
+    dirs = {"dir": dict(flag_off=0, per_stream=0), "lanes": dict(flag_off=0, per_stream=0, unstaged=0)}
     while time.time() < t_end:
         it += 1
         d = dsoak.draw(rng, it, seed)
@@ -186,14 +254,20 @@ def test_soak_derived_kernels(gpu_scanner_factory):
         for kernel, n in blobs.items():
             for k in n:
                 n[k] += reached[kernel] is not None and reached[kernel][k] > 0
+        for kernel, n in dirs.items():
+            for k in n:
+                n[k] += reached[kernel] is not None and reached[kernel][k] > 0
     # The budget is looked at between draws: a run overshoots it by at most one draw.  The costliest draw — the oracle on
     # 64 settings of 64 frames of 8000 records repeated 3.5 times, about 10^8 record visits on eight threads, and the numpy
     # models on 64 frames — takes about two seconds of CPU time, the average one a tenth of a second.  A second draw
     # starts whenever the first one ends inside the budget, so four seconds hold at least two; fewer means that the
     # expected values, not the kernels, have become the cost.  The blob scans' expected values label every frame's centre
     # plane by flood fill in plain Python; derived_soak.blob_batch labels each DISTINCT plane of a draw once, which keeps a
-    # vectors_needed 0 draw (64 frames, one blob of up to 37 000 cells per stream) at the cost of its streams.
+    # vectors_needed 0 draw (64 frames, one blob of up to 37 000 cells per stream) at the cost of its streams.  The direction
+    # scan, the plane scan and the flow map add two numpy models and one oracle pass on the records as they are: a fifth
+    # of a second on the costliest draw (docs/rounds/r27_direction_limits.md).
     assert done >= (2 if budget >= 4 else 1), f"only {done} configurations in {budget:.0f} s"
     print(f"derived soak: {done} random configurations checked in {budget:.0f} s, kernels run {ran}, the compensated scan's "
           f"draws with a frame compensated / one that keeps centres / a mode found and not applied: {gmc}, the blob scans' draws "
-          f"with several blobs in a frame / a flag min_blob_cells turns off / one it keeps / masks / a frame behind the last stream: {blobs}")
+          f"with several blobs in a frame / a flag min_blob_cells turns off / one it keeps / masks / a frame behind the last stream: {blobs}, "
+          f"the direction and plane scans' draws with a flag the byte or plane turns off / in the per-stream form / unstaged: {dirs}")

@@ -119,6 +119,47 @@ def test_streamer_edges(gpu_scanner_factory):
         assert_equals_model(got, want, label)
 
 
+EDGE_STREAM_ALLOWS = [0xA5, 0x0F, 0xFF]
+
+
+def edge_streams(n_frames):
+    """Three streams over the edge batch; its last five frames lie behind the last one."""
+    return np.array([0, n_frames // 3, n_frames // 2, n_frames - 5], dtype=np.uint64)
+
+
+def test_unaligned_40_byte_base(gpu_scanner_factory):
+    """(base & 7) != 0 takes stream_mv40's branch without a head peel, here with dir_vote at 1024 lanes and four loads in
+    flight: the edge batch (frames of 0 .. 8207 records, neighbouring records in different sectors, so a record skipped
+    or read twice moves a bin) as 40-byte records at byte shifts 4, 12 and 20, under one byte and under one byte per
+    stream — roses, centres and flags against the model.  An odd base is MT_ERR_INVALID and writes nothing: asserted here
+    with a live context and junk-filled outputs (tests/api_arg_rungs.py holds the rung's place in the ladder, with a NULL
+    context and made-up addresses)."""
+    import torch
+    from test_gpu_derived_edges import shifted
+    from derived_edge_inputs import UNALIGNED_SHIFTS
+    c = CASES["edge"]()
+    p, mv, off, sd = c["params"], c["mv"], c["off"], c["sd"]
+    F = len(sd)
+    s = gpu_scanner_factory(p)
+    soff = edge_streams(F)
+    wants = {"one byte": (dict(allow=c["allow"]), model_of("edge")),
+             "per stream": (dict(soff=soff, allows=EDGE_STREAM_ALLOWS), dm.model_batch(p, mv, off, sd, soff=soff, allows=EDGE_STREAM_ALLOWS))}
+    assert wants["one byte"][1][2].tolist() == c["hand_rose"].tolist() and not wants["per stream"][1][2][F - 5:].any()
+    raw = torch.from_numpy(mv.view(np.uint8).reshape(-1).copy())
+    _, d_off, d_sd = to_device(mv[:0], off, sd, False)
+    for shift in UNALIGNED_SHIFTS:
+        d_rec = shifted(raw, shift)
+        for form, (kw, want) in wants.items():
+            assert_equals_model(device_dir(s, d_rec, d_off, d_sd, False, **kw), want, f"base shifted by {shift} bytes, {form}")
+    out = junk_outputs(F)
+    odd = torch.zeros(raw.numel() + 8, dtype=torch.uint8, device="cuda")[1:1 + raw.numel()]
+    rc = s._lib.mtgpu_scan_dir_device(s._ctx, odd.data_ptr(), 40, len(mv), d_off.data_ptr(), d_sd.data_ptr(), F, None, 0, None, 0xFF,
+                                      out["flags"].data_ptr(), out["centres"].data_ptr(), out["rose"].data_ptr(), None)
+    torch.cuda.synchronize()
+    assert rc == _abi.MT_ERR_INVALID and "4-byte" in s._lib.mtgpu_last_error().decode()
+    assert all(int((t != (JUNK_FLAG if n == "flags" else JUNK)).sum()) == 0 for n, t in out.items())
+
+
 # ------------------------------------------------------------------ 3. word seams
 
 @pytest.mark.parametrize("gw", [65, 129])

@@ -175,6 +175,50 @@ def test_uniform_planes_on_the_streamer_edges(gpu_scanner_factory):
     assert want[1].tolist() == di.BOUNDARY_HAND
 
 
+def test_unaligned_40_byte_base(gpu_scanner_factory):
+    """(base & 7) != 0 takes stream_mv40's branch without a head peel, here with lanes_vote and flow_count at 1024 lanes
+    and four loads in flight: the batch of test_uniform_planes_on_the_streamer_edges as 40-byte records at byte shifts 4,
+    12 and 20.  The plane scan under a plane whose bytes differ cell by cell, one plane for every frame and one per
+    stream (five frames lie behind the last stream), and the flow map over the same streams, against the models.  An odd
+    base is MT_ERR_INVALID and writes nothing: asserted here for both entry points — tests/api_arg_rungs.py holds neither
+    mtgpu_scan_lanes_device nor mtgpu_flow_map_device."""
+    import torch
+    from test_gpu_derived_edges import shifted
+    from derived_edge_inputs import UNALIGNED_SHIFTS
+    c = di.edge_case()
+    p, mv, off, sd = c["params"], c["mv"], c["off"], c["sd"]
+    F = len(sd)
+    s = gpu_scanner_factory(p)
+    soff = np.array([0, F // 3, F // 2, F - 5], dtype=np.uint64)
+    one = li.cellwise_plane(p)
+    planes = np.stack([one, np.full_like(one, di.EDGE_ALLOW), one ^ 0xFF])
+    want_one, want_streams = lm.model_batch(p, mv, off, sd, one), lm.model_batch(p, mv, off, sd, planes, soff)
+    want_flow = lm.flow_map(p, mv, off, sd, soff)
+    assert want_one[2].tolist() == c["hand_rose"].tolist() and (want_one[1] > 0).any() and not want_streams[2][F - 5:].any()
+    assert want_flow.sum(axis=(0, 2, 3)).tolist() == want_one[2][:F - 5].sum(axis=0, dtype=np.uint64).tolist()      # G
+    raw = torch.from_numpy(mv.view(np.uint8).reshape(-1).copy())
+    _, d_off, d_sd = to_device(mv[:0], off, sd, False)
+    for shift in UNALIGNED_SHIFTS:
+        d_rec = shifted(raw, shift)
+        assert_equals_model(device_lanes(s, d_rec, d_off, d_sd, False, one), want_one, f"base shifted by {shift} bytes, one plane")
+        assert_equals_model(device_lanes(s, d_rec, d_off, d_sd, False, planes, soff), want_streams, f"base shifted by {shift} bytes, per stream")
+        assert_flow_equal(device_flow(s, d_rec, d_off, d_sd, False, soff), want_flow, f"base shifted by {shift} bytes, flow map")
+    out = junk_outputs(F)
+    flow = torch.full((3, 8, p.grid_h, p.grid_w), JUNK, dtype=torch.int32, device="cuda")
+    odd = torch.zeros(raw.numel() + 8, dtype=torch.uint8, device="cuda")[1:1 + raw.numel()]
+    d_planes, d_soff = odd_planes(planes), torch.from_numpy(soff.astype(np.int64)).cuda()
+    lib = s._lib
+    rc = lib.mtgpu_scan_lanes_device(s._ctx, odd.data_ptr(), 40, len(mv), d_off.data_ptr(), d_sd.data_ptr(), F, d_soff.data_ptr(), 3,
+                                     d_planes.data_ptr(), out["flags"].data_ptr(), out["centres"].data_ptr(), out["rose"].data_ptr(), None)
+    torch.cuda.synchronize()
+    assert rc == _abi.MT_ERR_INVALID and "4-byte" in lib.mtgpu_last_error().decode()
+    rc = lib.mtgpu_flow_map_device(s._ctx, odd.data_ptr(), 40, len(mv), d_off.data_ptr(), d_sd.data_ptr(), F, d_soff.data_ptr(), 3,
+                                   flow.data_ptr(), None)
+    torch.cuda.synchronize()
+    assert rc == _abi.MT_ERR_INVALID and "4-byte" in lib.mtgpu_last_error().decode()
+    assert all(int((t != (JUNK_FLAG if n == "flags" else JUNK)).sum()) == 0 for n, t in out.items()) and int((flow != JUNK).sum()) == 0
+
+
 # ------------------------------------------------------------------ 3. word seams
 
 @pytest.mark.parametrize("gw", [65, 129])
