@@ -48,6 +48,7 @@
 #include <unistd.h>
 
 #include "mtgpu.h"
+#include "scan_request.hpp"
 
 namespace mtgpu_host {
 
@@ -793,21 +794,11 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   }
 
   bool device_error_ = false;                         // a submit / collect / release failed: the pipe's state is unknown
-  bool keep_centres_ = false;                          // keep_centres(): the pipe carries centre counts, scan_range keeps them
-  std::vector<std::pair<double, uint32_t>> last_centres_;
+  ScannerAsk ask_;                                     // what the setters below were told (scan_request.hpp), but for the two planes:
   std::vector<uint64_t> keep_;                         // set_keep(): the keep mask initialize() hands to the pipe; empty: none
-  int min_blob_cells_ = 0;                             // set_min_blob_cells(): the pipe's blob setting; 0: off
-  bool report_largest_ = false;                        // report_largest(): last_centres() holds the largest blob, not the centres
-  int gmc_max_shift_ = -1, gmc_min_share_q8_ = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;   // set_gmc(): the pipe's compensation; max_shift < 0: off
-  bool report_vector_ = false;                         // report_vector(): last_centres() holds the packed applied vector
-  int gmc_blob_cells_ = 0;                             // set_gmc_blobs(): the pipe's pair mode (compensated blob scan); 0: off
-  int gmc_blob_max_shift_ = MTGPU_GMC_DEFAULT_MAX_SHIFT, gmc_blob_min_share_q8_ = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
-  int gmc_blob_report_ = MT_PIPE_REPORT_CENTRES;       // report_gmc_blobs(): what last_centres() holds in pair mode
-  int dir_allow_ = -1;                                 // set_dir(): the pipe's direction mode, the allow byte; -1: off
-  bool report_sectors_ = false;                        // report_sectors(): last_centres() holds the frames' sector words
   std::vector<uint8_t> plane_;                         // set_plane(): the direction plane initialize() hands to the pipe; empty: none
+  std::vector<std::pair<double, uint32_t>> last_centres_;
   bool trace_on_ = false;                              // set_persist(min_run >= 1): scan_range keeps a trace of every fed frame
-  int persist_reach_ = -1;                             // set_persist(): >= 0: the pipe carries boxes (MT_LAYOUT_BOXES)
   std::vector<TraceEntry> last_trace_;
   int persist_min_run_ = 0;
   uint32_t persist_max_dropout_ = 0;
@@ -834,14 +825,14 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
     }
     for (uint32_t i = 0; i < n; ++i)
       if (flags[i]) ts.push_back(pts[i]);                    // :382-383
-    if (keep_centres_) {                                     // the `clusters` counter of every analysed frame (:272-294)
+    if (ask_.keep_centres) {                                     // the `clusters` counter of every analysed frame (:272-294)
       const uint32_t *centres = nullptr;
       if (!ok(mtgpu_batch_centres(b, &centres))) { const std::string first = err_; --inflight_; (void)mtgpu_pipe_release(pipe_, b); err_ = first; return false; }
       for (uint32_t i = 0; i < n; ++i) last_centres_.emplace_back(pts[i], centres[i]);
     }
     if (trace_on_) {                                         // what one persistence call per recording needs of every fed frame
       const mt_blob_box *box = nullptr;
-      if (persist_reach_ >= 0 && !ok(mtgpu_batch_boxes(b, &box))) { const std::string first = err_; --inflight_; (void)mtgpu_pipe_release(pipe_, b); err_ = first; return false; }
+      if (ask_.persist_reach >= 0 && !ok(mtgpu_batch_boxes(b, &box))) { const std::string first = err_; --inflight_; (void)mtgpu_pipe_release(pipe_, b); err_ = first; return false; }
       for (uint32_t i = 0; i < n; ++i) {
         TraceEntry e;
         e.pts = pts[i];
@@ -887,6 +878,37 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
     }
   }
 
+  // The five off forms, in one fixed order; the keep mask is not a mode and is not touched.
+  static bool all_off(mtgpu_pipe *pipe) {
+    return mtgpu_pipe_set_plane(pipe, nullptr, 0) == MT_OK && mtgpu_pipe_set_dir(pipe, 0, 0, 0) == MT_OK &&
+           mtgpu_pipe_set_gmc_blobs(pipe, 0, 0, 0, 0) == MT_OK && mtgpu_pipe_set_gmc(pipe, 0, 0, 0, 0) == MT_OK &&
+           mtgpu_pipe_set_blobs(pipe, 0, 0) == MT_OK;
+  }
+  // The on form of the one mode a request resolved to (the pipe runs the plain scan before the call).
+  int apply(mtgpu_pipe *pipe, const ScanRequest &r) const {
+    switch (r.mode) {
+      case ScanMode::blobs: return mtgpu_pipe_set_blobs(pipe, r.min_blob, r.report);
+      case ScanMode::gmc: return mtgpu_pipe_set_gmc(pipe, 1, r.max_shift, r.min_share_q8, r.report);
+      case ScanMode::gmc_blobs: return mtgpu_pipe_set_gmc_blobs(pipe, r.min_blob, r.max_shift, r.min_share_q8, r.report);
+      case ScanMode::dir: return mtgpu_pipe_set_dir(pipe, 1, r.allow, r.report);
+      case ScanMode::plane: return mtgpu_pipe_set_plane(pipe, plane_.data(), r.report);
+      default: return MT_OK;   // plain
+    }
+  }
+  // initialize() behind the pipe: false with err_ set at the first thing that fails.
+  bool settle(ScannerAsk &ask) {
+    mt_scan_params p;
+    if (mtgpu_get_params(be_->ctx(), &p) != MT_OK || !all_off(pipe_)) { err_ = mtgpu_last_error(); return false; }
+    ask.grid_w = p.grid_w; ask.grid_h = p.grid_h;
+    const ScanRequest req = resolve_scanner(ask);
+    if (!req.error.empty()) { err_ = req.error; return false; }
+    if (mtgpu_pipe_set_keep(pipe_, keep_.empty() ? nullptr : keep_.data()) != MT_OK || apply(pipe_, req) != MT_OK) {
+      err_ = mtgpu_last_error();
+      return false;
+    }
+    return true;
+  }
+
  public:
   GpuMotionScanner(FrameSource &src, int device, GpuBackend *shared = nullptr)
       : src_(src), device_(device), be_(shared ? shared : &own_) {}
@@ -916,64 +938,56 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   // host-pointer scan entry points on it from a worker: they take the context's lock and its single stream and
   // would serialise or re-plan all S x T workers.  (run_scan_pipeline's own merge call is one short call per video.)
   mtgpu_ctx *context() { return be_->ctx(); }
-  // Call before initialize().  On: the scanner's pipe is created with MT_LAYOUT_CENTRES and last_centres() returns
+  // The setters below are called before initialize(), which ALWAYS settles the pipe for this video — every mode off, this
+  // video's mask set or the previous one's cleared, then the ONE mode asked for: a GpuBackend lives on from one video to
+  // the next, and the next video never inherits or is refused because of the previous one's settings.  Blobs, compensation,
+  // the compensated blob scan, the direction byte and the direction plane are modes of the pipe and exclude each other;
+  // resolve_scanner (scan_request.hpp) has every sentence initialize() fails with when two are asked for.
+  // On: the scanner's pipe is created with MT_LAYOUT_CENTRES and last_centres() returns
   // {pts, centres} of every frame the last scan_range analysed, in order — the reference's `clusters` counter
   // (motion_scanner.cpp:272-294) without its early return: what a motion graph or a CLUSTERS_NEEDED sweep needs.
   // scan_range's signature and result stay the reference's.
-  void keep_centres(bool on) { keep_centres_ = on; }
+  void keep_centres(bool on) { ask_.keep_centres = on; }
   const std::vector<std::pair<double, uint32_t>> &last_centres() const { return last_centres_; }
-  // Call before initialize().  The keep mask of this video (include/mtgpu_zones.h: gh * W words, load_keep's result):
-  // every check_frame of scan_range (:375-383) then runs under it — :282 ANDed with the keep bit.  Empty: no mask.
-  // initialize() ALWAYS settles the pipe's mask — it sets this one or clears whatever the pipe carries: a GpuBackend
-  // lives on from one video to the next, and the next video must never inherit the previous one's zones.
+  // The keep mask of this video (include/mtgpu_zones.h: gh * W words, load_keep's result): every check_frame of
+  // scan_range (:375-383) then runs under it — :282 ANDed with the keep bit.  Empty: no mask.
   void set_keep(std::vector<uint64_t> words) { keep_ = std::move(words); }
-  // Call before initialize().  A minimum blob size for this video (include/mtgpu_pipe_blobs.h): every check_frame of
+  // A minimum blob size for this video (include/mtgpu_pipe_blobs.h): every check_frame of
   // scan_range (:375-383) then also asks that the largest 4-connected blob of the frame's centres (:272-294) has at
   // least n cells.  0: off.  report_largest(true): last_centres() returns {pts, largest blob} in place of the centre
   // counts (needs keep_centres(true): the pipe has ONE count array); the blob scan is then on at n = max(1, n), and
-  // n <= 1 leaves the flags those of the plain scan (mtgpu_blobs.h, Consequences).  Like the mask, initialize() ALWAYS
-  // settles the pipe's blob setting — it sets this one or turns off whatever a pooled pipe carries.
-  void set_min_blob_cells(int n) { min_blob_cells_ = n; }
-  void report_largest(bool on) { report_largest_ = on; }
-  // Call before initialize().  Global-motion compensation for this video (include/mtgpu_pipe_gmc.h): every check_frame
+  // n <= 1 leaves the flags those of the plain scan (mtgpu_blobs.h, Consequences).
+  void set_min_blob_cells(int n) { ask_.min_blob_cells = n; }
+  void report_largest(bool on) { ask_.report_largest = on; }
+  // Global-motion compensation for this video (include/mtgpu_pipe_gmc.h): every check_frame
   // of scan_range (:375-383) thresholds the residuals of the frame's dominant vector, estimated within +-max_shift from
   // the records of kept cells (set_keep) and applied where min_share_q8 / 256 of them agree.  max_shift < 0: off.
   // report_vector(true): last_centres() returns {pts, (uint16)gx | (uint16)gy << 16} in place of the centre counts
-  // (needs keep_centres(true): the pipe has ONE count array).  Not together with set_min_blob_cells(n > 0) or
-  // report_largest.  Like the mask, initialize() ALWAYS settles the pipe's setting — it sets this one or turns off
-  // whatever a pooled pipe carries.
-  void set_gmc(int max_shift, int min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8) { gmc_max_shift_ = max_shift; gmc_min_share_q8_ = min_share_q8; }
-  void report_vector(bool on) { report_vector_ = on; }
-  // Call before initialize().  The compensated blob scan for this video (include/mtgpu_pipe_gmc_blobs.h), the pipe's
+  // (needs keep_centres(true): the pipe has ONE count array).
+  void set_gmc(int max_shift, int min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8) { ask_.gmc_max_shift = max_shift; ask_.gmc_min_share_q8 = min_share_q8; }
+  void report_vector(bool on) { ask_.report_vector = on; }
+  // The compensated blob scan for this video (include/mtgpu_pipe_gmc_blobs.h), the pipe's
   // third mode: every check_frame of scan_range (:375-383) asks that the largest 4-connected blob of the centres of the
   // RESIDUAL vote has at least min_blob_cells cells; the estimate and the active plane honour set_keep.  0: off.
   // report_gmc_blobs(MT_PIPE_REPORT_LARGEST / _VECTOR): last_centres() returns that count in place of the centre counts
-  // (needs keep_centres(true): the pipe has ONE count array); the pair is then on at max(1, min_blob_cells).  Not
-  // together with set_min_blob_cells(n > 0), report_largest, set_gmc(>= 0) or report_vector.  initialize() ALWAYS
-  // settles the pipe's pair setting — off first, on again at the end if asked: a pooled pipe never refuses the next
-  // video's setting because of the previous one's.
+  // (needs keep_centres(true): the pipe has ONE count array); the pair is then on at max(1, min_blob_cells).
   void set_gmc_blobs(int min_blob_cells, int max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT, int min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8) {
-    gmc_blob_cells_ = min_blob_cells; gmc_blob_max_shift_ = max_shift; gmc_blob_min_share_q8_ = min_share_q8;
+    ask_.gmc_blob_cells = min_blob_cells; ask_.gmc_blob_max_shift = max_shift; ask_.gmc_blob_min_share_q8 = min_share_q8;
   }
-  void report_gmc_blobs(int report) { gmc_blob_report_ = report; }
-  // Call before initialize().  The direction filter for this video (include/mtgpu_pipe_dir.h), the pipe's fourth mode:
+  void report_gmc_blobs(int report) { ask_.gmc_blob_report = report; }
+  // The direction filter for this video (include/mtgpu_pipe_dir.h), the pipe's fourth mode:
   // in every check_frame of scan_range (:375-383) a record votes only if bit k of `allow` is set, k the sector of
   // dst - src (include/mtgpu_dir.h); the active plane honours set_keep.  allow 0 .. 255: on; -1: off.
   // report_sectors(true): last_centres() returns {pts, sector word} in place of the centre counts (needs
-  // keep_centres(true): the pipe has ONE count array, and set_dir: without the mode there is no word).  Not together
-  // with set_min_blob_cells(n > 0), report_largest, set_gmc(>= 0), report_vector or set_gmc_blobs.  initialize() ALWAYS
-  // settles the pipe's direction setting — off first, on again at the end if asked: a pooled pipe never refuses the
-  // next video's setting because of the previous one's.
-  void set_dir(int allow) { dir_allow_ = allow; }
-  void report_sectors(bool on) { report_sectors_ = on; }
-  // Call before initialize().  The direction plane of this video (include/mtgpu_pipe_lanes.h: gh * gw bytes, load_plane's
+  // keep_centres(true): the pipe has ONE count array, and set_dir: without the mode there is no word).
+  void set_dir(int allow) { ask_.dir_allow = allow; }
+  void report_sectors(bool on) { ask_.report_sectors = on; }
+  // The direction plane of this video (include/mtgpu_pipe_lanes.h: gh * gw bytes, load_plane's
   // result): in every check_frame of scan_range (:375-383) a record votes only if its DESTINATION CELL's byte has the bit
   // of its sector; the active plane honours set_keep.  Empty: off.  report_sectors(true) works with a plane as with
-  // set_dir's byte.  Not together with set_dir (one rule at two granularities), set_min_blob_cells(n > 0),
-  // report_largest, set_gmc(>= 0), report_vector or set_gmc_blobs.  initialize() ALWAYS settles the pipe's plane — off
-  // first, on again last if asked: the next video never inherits the previous one's lanes.
+  // set_dir's byte (the two are one rule at two granularities).
   void set_plane(const std::vector<uint8_t> &plane) { plane_ = plane; }
-  // Call before initialize().  Temporal persistence for this video (include/mtgpu_persist.h).  A run of motion frames
+  // Temporal persistence for this video (include/mtgpu_persist.h).  A run of motion frames
   // crosses batch and chunk borders and the chunks of a recording are scanned by several workers in any order, so the
   // scanner does NOT apply the rule: it keeps what ONE mtgpu_persist_flags call per recording needs (run_scan_pipeline
   // makes it on the pooled, pts-sorted traces).  min_run <= 0: off — everything is as without this call and no trace is
@@ -989,11 +1003,11 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
   void set_persist(int min_run, uint32_t max_dropout = 0, int reach = -1) {
     trace_on_ = min_run > 0;
     persist_min_run_ = min_run; persist_max_dropout_ = max_dropout;
-    persist_reach_ = trace_on_ ? reach : -1;
+    ask_.persist_reach = trace_on_ ? reach : -1;
   }
   int persist_min_run() const { return persist_min_run_; }
   uint32_t persist_max_dropout() const { return persist_max_dropout_; }
-  int persist_reach() const { return persist_reach_; }
+  int persist_reach() const { return ask_.persist_reach; }
   // {pts, flag, has_sd, box} of every frame the last scan_range fed, in feed order; box is the all-0xFFFF box where the
   // pipe has no boxes or the flag is 0.  Empty without set_persist.
   const std::vector<TraceEntry> &last_trace() const { return last_trace_; }
@@ -1009,140 +1023,24 @@ class GpuMotionScanner {   // public shape of MotionScanner (motion_scanner.hpp:
       const uint64_t rec_bytes = (Config::staging_layout() & MT_LAYOUT_AOS40) ? MT_MV_BYTES : MT_COMPACT_BYTES;
       batch_records = std::max<uint64_t>(2 * fine, ((uint64_t)Config::batch_mib() << 20) / rec_bytes);
     }
-    if (persist_reach_ >= 0 && min_blob_cells_ <= 0 && gmc_blob_cells_ <= 0) {
-      err_ = "set_persist with reach >= 0 needs set_min_blob_cells(n > 0) or set_gmc_blobs(n > 0): only a blob scan reports the box "
-             "that reach compares";
+    ScannerAsk ask = ask_;
+    ask.plane_bytes = plane_.size(); ask.keep_words = keep_.size();
+    // Whatever fails from here on, the backend's pipe — this video's or the one a previous video left in the pool — is
+    // left without a mode and without a mask.
+    auto give_up = [this] {
+      if (mtgpu_pipe *p = be_->pipe()) { (void)all_off(p); (void)mtgpu_pipe_set_keep(p, nullptr); }
+      pipe_ = nullptr;
       return false;
-    }
-    if (persist_reach_ > 65535) { err_ = "set_persist: reach " + std::to_string(persist_reach_) + " outside [0,65535]"; return false; }
-    if (!be_->ensure(src_.width(), src_.height(), device_, batch_records, batch_frames, n_buffers, err_, keep_centres_, persist_reach_ >= 0))
+    };
+    err_ = persist_error(ask);                       // the rungs that need no grid: ahead of any pipe
+    if (!err_.empty()) return give_up();
+    if (!be_->ensure(src_.width(), src_.height(), device_, batch_records, batch_frames, n_buffers, err_, ask_.keep_centres, ask_.persist_reach >= 0))
       return false;
     pipe_ = be_->pipe();
-    // the pipe is idle here (a previous scanner on this backend left nothing in flight, or the backend was rebuilt)
-    // the plane off first, then direction: a pooled pipe that carries either would refuse every other mode below
-    if (mtgpu_pipe_set_plane(pipe_, nullptr, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
-    if (mtgpu_pipe_set_dir(pipe_, 0, 0, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
-    // the pair off first: a pooled pipe that carries it would refuse both single settings below
-    if (mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
-    // compensation off first: a pooled pipe that carries it would refuse the blob setting below
-    if (mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
-    {
-      if (min_blob_cells_ < 0) { err_ = "min_blob_cells is " + std::to_string(min_blob_cells_); (void)mtgpu_pipe_set_blobs(pipe_, 0, 0); pipe_ = nullptr; return false; }
-      if (report_largest_ && !keep_centres_) { err_ = "report_largest needs keep_centres: the largest blob travels in the pipe's count array"; (void)mtgpu_pipe_set_blobs(pipe_, 0, 0); pipe_ = nullptr; return false; }
-      const int n = report_largest_ ? std::max(1, min_blob_cells_) : min_blob_cells_;
-      if (mtgpu_pipe_set_blobs(pipe_, n, n > 0 && report_largest_ ? MT_PIPE_REPORT_LARGEST : MT_PIPE_REPORT_CENTRES) != MT_OK) {
-        err_ = mtgpu_last_error();
-        (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);               // whatever fails here, no stale setting stays behind
-        pipe_ = nullptr;
-        return false;
-      }
-    }
-    if (gmc_max_shift_ >= 0 || report_vector_) {
-      const char *bad = nullptr;
-      if (gmc_max_shift_ < 0) bad = "report_vector needs set_gmc: there is no applied vector without compensation";
-      else if (min_blob_cells_ > 0 || report_largest_) bad = "compensation and blobs are not together yet";
-      else if (report_vector_ && !keep_centres_) bad = "report_vector needs keep_centres: the applied vector travels in the pipe's count array";
-      if (bad || mtgpu_pipe_set_gmc(pipe_, 1, gmc_max_shift_, gmc_min_share_q8_,
-                                    report_vector_ ? MT_PIPE_REPORT_VECTOR : MT_PIPE_REPORT_CENTRES) != MT_OK) {
-        err_ = bad ? bad : mtgpu_last_error();
-        (void)mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0);             // whatever fails here, no stale setting stays behind
-        pipe_ = nullptr;
-        return false;
-      }
-    }
-    if (keep_.empty()) {
-      if (mtgpu_pipe_set_keep(pipe_, nullptr) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
-    } else {
-      mt_scan_params p;
-      if (mtgpu_get_params(be_->ctx(), &p) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
-      const size_t want = (size_t)p.grid_h * (((size_t)p.grid_w + 63u) / 64u);
-      if (keep_.size() != want) {
-        err_ = "keep mask: " + std::to_string(keep_.size()) + " words, the " + std::to_string(p.grid_w) + "x" +
-               std::to_string(p.grid_h) + " grid takes " + std::to_string(want);
-        (void)mtgpu_pipe_set_keep(pipe_, nullptr);             // whatever fails here, no stale mask stays behind
-        pipe_ = nullptr;
-        return false;
-      }
-      if (mtgpu_pipe_set_keep(pipe_, keep_.data()) != MT_OK) {
-        err_ = mtgpu_last_error();
-        (void)mtgpu_pipe_set_keep(pipe_, nullptr);
-        pipe_ = nullptr;
-        return false;
-      }
-    }
-    if (gmc_blob_cells_ != 0 || gmc_blob_report_ != MT_PIPE_REPORT_CENTRES) {
-      const char *bad = nullptr;
-      if (gmc_blob_cells_ < 0) bad = "set_gmc_blobs: min_blob_cells is negative";
-      else if (min_blob_cells_ > 0) bad = "set_gmc_blobs together with set_min_blob_cells: the compensated blob scan has its own minimum blob size";
-      else if (report_largest_) bad = "set_gmc_blobs together with report_largest: ask report_gmc_blobs(MT_PIPE_REPORT_LARGEST)";
-      else if (gmc_max_shift_ >= 0) bad = "set_gmc_blobs together with set_gmc: the compensated blob scan has its own max_shift and min_share_q8";
-      else if (report_vector_) bad = "set_gmc_blobs together with report_vector: ask report_gmc_blobs(MT_PIPE_REPORT_VECTOR)";
-      else if (gmc_blob_report_ != MT_PIPE_REPORT_CENTRES && !keep_centres_)
-        bad = "report_gmc_blobs needs keep_centres: the largest blob and the applied vector travel in the pipe's count array";
-      // the existing sequence left both single modes off here unless `bad` names one of them
-      if (bad || mtgpu_pipe_set_gmc_blobs(pipe_, std::max(1, gmc_blob_cells_), gmc_blob_max_shift_, gmc_blob_min_share_q8_,
-                                          gmc_blob_report_) != MT_OK) {
-        err_ = bad ? bad : mtgpu_last_error();
-        (void)mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0);       // whatever fails here, no stale setting stays behind
-        (void)mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0);
-        (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);
-        (void)mtgpu_pipe_set_keep(pipe_, nullptr);
-        pipe_ = nullptr;
-        return false;
-      }
-    }
-    if (dir_allow_ != -1 || (report_sectors_ && plane_.empty())) {
-      const char *bad = nullptr;
-      if (dir_allow_ == -1) bad = "report_sectors needs set_dir: there is no sector word without the direction mode";
-      else if (dir_allow_ < 0 || dir_allow_ > 255) bad = "set_dir: allow is outside [0,255]";
-      else if (min_blob_cells_ > 0 || report_largest_) bad = "set_dir together with set_min_blob_cells / report_largest: direction and blobs are not together yet";
-      else if (gmc_max_shift_ >= 0 || report_vector_) bad = "set_dir together with set_gmc / report_vector: direction and compensation are not together yet";
-      else if (gmc_blob_cells_ != 0 || gmc_blob_report_ != MT_PIPE_REPORT_CENTRES)
-        bad = "set_dir together with set_gmc_blobs: direction and the compensated blob scan are not together yet";
-      else if (report_sectors_ && !keep_centres_) bad = "report_sectors needs keep_centres: the sector word travels in the pipe's count array";
-      // the sequence above left the three other modes off here unless `bad` names one of them
-      if (bad || mtgpu_pipe_set_dir(pipe_, 1, dir_allow_, report_sectors_ ? MT_PIPE_REPORT_SECTORS : MT_PIPE_REPORT_CENTRES) != MT_OK) {
-        err_ = bad ? bad : mtgpu_last_error();
-        (void)mtgpu_pipe_set_dir(pipe_, 0, 0, 0);                // whatever fails here, no stale setting stays behind
-        (void)mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0);
-        (void)mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0);
-        (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);
-        (void)mtgpu_pipe_set_keep(pipe_, nullptr);
-        pipe_ = nullptr;
-        return false;
-      }
-    }
-    if (!plane_.empty()) {
-      mt_scan_params p;
-      if (mtgpu_get_params(be_->ctx(), &p) != MT_OK) { err_ = mtgpu_last_error(); pipe_ = nullptr; return false; }
-      const size_t want = (size_t)p.grid_h * (size_t)p.grid_w;
-      std::string size_bad;
-      const char *bad = nullptr;
-      if (dir_allow_ != -1) bad = "set_plane together with set_dir: a plane and the allow byte are one rule at two granularities";
-      else if (min_blob_cells_ > 0 || report_largest_) bad = "set_plane together with set_min_blob_cells / report_largest: planes and blobs are not together yet";
-      else if (gmc_max_shift_ >= 0 || report_vector_) bad = "set_plane together with set_gmc / report_vector: planes and compensation are not together yet";
-      else if (gmc_blob_cells_ != 0 || gmc_blob_report_ != MT_PIPE_REPORT_CENTRES)
-        bad = "set_plane together with set_gmc_blobs: planes and the compensated blob scan are not together yet";
-      else if (report_sectors_ && !keep_centres_) bad = "report_sectors needs keep_centres: the sector word travels in the pipe's count array";
-      else if (plane_.size() != want) {
-        size_bad = "direction plane: " + std::to_string(plane_.size()) + " bytes, the " + std::to_string(p.grid_w) + "x" +
-                   std::to_string(p.grid_h) + " grid takes " + std::to_string(want);
-        bad = size_bad.c_str();
-      }
-      // the sequence above left every other mode off here unless `bad` names one of them
-      if (bad || mtgpu_pipe_set_plane(pipe_, plane_.data(), report_sectors_ ? MT_PIPE_REPORT_SECTORS : MT_PIPE_REPORT_CENTRES) != MT_OK) {
-        err_ = bad ? bad : mtgpu_last_error();
-        (void)mtgpu_pipe_set_plane(pipe_, nullptr, 0);           // whatever fails here, no stale setting stays behind
-        (void)mtgpu_pipe_set_dir(pipe_, 0, 0, 0);
-        (void)mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0);
-        (void)mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0);
-        (void)mtgpu_pipe_set_blobs(pipe_, 0, 0);
-        (void)mtgpu_pipe_set_keep(pipe_, nullptr);
-        pipe_ = nullptr;
-        return false;
-      }
-    }
-    return true;
+    // The pipe is idle here (a previous scanner on this backend left nothing in flight, or the backend was rebuilt).
+    // Everything off first — a pooled pipe that carries the previous video's mode would refuse this one's — then this
+    // video's mask, then its ONE mode.
+    return settle(ask) || give_up();
   }
   double get_duration() { return src_.duration(); }
   double get_fps() { return src_.fps(); }
@@ -1231,10 +1129,13 @@ struct PipelineResult {
   // In: the keep mask of this video (GpuMotionScanner::set_keep; load_keep's words), handed to every worker's scanner.
   // Empty: none — and a pooled backend that carried another video's mask is cleared.
   std::vector<uint64_t> keep;
+  // The five groups of fields below are the pipe's modes and exclude each other, and the pipe has ONE count array: at most
+  // one of keep_centres / sweep_levels, blob_sweep_levels, gmc_vectors, gmc_blob_sweep_levels and dir_sectors reports into
+  // it.  resolve_pipeline (scan_request.hpp) holds every such rule and its sentence; keep combines with everything.
   // Blobs (GpuMotionScanner::set_min_blob_cells / report_largest; include/mtgpu_pipe_blobs.h).  In: min_blob_cells (0:
   // off) — `segments` are then those of frames whose largest blob has at least that many cells; blob_sweep_levels —
-  // every worker's pipe reports the largest blob in place of the centre count (the pipe has ONE count array: not
-  // together with keep_centres / sweep_levels), `centres` then holds {pts, largest} and `blob_sweep` = for every level
+  // every worker's pipe reports the largest blob in place of the centre count, `centres` then holds {pts, largest} and
+  // `blob_sweep` = for every level
   // L >= max(1, CLUSTERS_NEEDED) what this result's segments / merge would be with min_blob_cells = L, from the ONE scan
   // (mtgpu_blobs.h: largest >= L implies centres >= L).  -1 / empty: blob_options().
   int min_blob_cells = -1;
@@ -1243,10 +1144,9 @@ struct PipelineResult {
   // Global-motion compensation (GpuMotionScanner::set_gmc / report_vector; include/mtgpu_pipe_gmc.h).  In:
   // gmc_max_shift >= 0: on — `segments` are those of the residual scan, under `keep` where there is one; -1: take
   // gmc_options(); -2: off whatever gmc_options() says.  gmc_min_share_q8 (with gmc_max_shift >= 0).  gmc_vectors: every
-  // worker's pipe reports the applied vector in place of the centre count (the pipe has ONE count array: not together
-  // with keep_centres / sweep_levels / blob_sweep_levels); `centres` then holds {pts, (uint16)gx | (uint16)gy << 16}.
-  // Out, with gmc_vectors: gmc_moved_frames = scanned frames whose applied vector is not (0, 0), gmc_top = the applied
-  // vectors by falling frame count (then by gx, gy), at most 8.  Not together with min_blob_cells > 0 / blob_sweep_levels.
+  // worker's pipe reports the applied vector in place of the centre count; `centres` then holds {pts, (uint16)gx |
+  // (uint16)gy << 16}.  Out, with gmc_vectors: gmc_moved_frames = scanned frames whose applied vector is not (0, 0),
+  // gmc_top = the applied vectors by falling frame count (then by gx, gy), at most 8.
   int gmc_max_shift = -1;
   int gmc_min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
   bool gmc_vectors = false;
@@ -1257,10 +1157,9 @@ struct PipelineResult {
   // gmc_blob_cells >= 1: on — `segments` are those of frames whose largest RESIDUAL blob has at least that many cells,
   // under `keep` where there is one; -1: take gmc_blob_options(); 0: off whatever the options say.  gmc_blob_max_shift /
   // gmc_blob_min_share_q8 (with gmc_blob_cells >= 1 or gmc_blob_sweep_levels).  gmc_blob_sweep_levels — every worker's
-  // pipe reports the largest residual blob in place of the centre count (the pipe has ONE count array: not together
-  // with keep_centres / sweep_levels), `centres` then holds {pts, largest} and `gmc_blob_sweep` = for every level L >=
-  // max(1, CLUSTERS_NEEDED) what this result's segments / merge would be with gmc_blob_cells = L, from the ONE decode
-  // pass.  Not together with min_blob_cells > 0, blob_sweep_levels, gmc_max_shift >= 0 or gmc_vectors.
+  // pipe reports the largest residual blob in place of the centre count, `centres` then holds {pts, largest} and
+  // `gmc_blob_sweep` = for every level L >= max(1, CLUSTERS_NEEDED) what this result's segments / merge would be with
+  // gmc_blob_cells = L, from the ONE decode pass.
   int gmc_blob_cells = -1;
   int gmc_blob_max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT;
   int gmc_blob_min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
@@ -1269,11 +1168,9 @@ struct PipelineResult {
   // The direction filter (GpuMotionScanner::set_dir / report_sectors; include/mtgpu_pipe_dir.h).  In: dir_allow 0 .. 255:
   // on — `segments` are those of the scan in which only records of an allowed sector vote, under `keep` where there is
   // one; -1: take dir_options(); -2: off whatever dir_options() says.  dir_sectors: every worker's pipe reports the
-  // frame's sector word in place of the centre count (the pipe has ONE count array: not together with keep_centres /
-  // sweep_levels); `centres` then holds {pts, sector word}.  Out, with dir_sectors: dir_frames = scanned frames with a
-  // non-zero word, dir_present_frames[k] = those whose present byte has bit k, dir_dominant_frames[k] = those whose
-  // dominant sector is k.  Not together with min_blob_cells > 0 / blob_sweep_levels, gmc_max_shift >= 0 / gmc_vectors or
-  // gmc_blob_cells > 0 / gmc_blob_sweep_levels.  keep, keep_centres, sweep_levels, min_run, max_dropout and
+  // frame's sector word in place of the centre count; `centres` then holds {pts, sector word}.  Out, with dir_sectors:
+  // dir_frames = scanned frames with a non-zero word, dir_present_frames[k] = those whose present byte has bit k,
+  // dir_dominant_frames[k] = those whose dominant sector is k.  keep_centres, sweep_levels, min_run, max_dropout and
   // run_sweep_levels combine.
   int dir_allow = -1;
   bool dir_sectors = false;
@@ -1284,9 +1181,8 @@ struct PipelineResult {
   // video's plane (load_plane's result, gh * gw): `segments` are those of the scan in which a record votes only if its
   // destination cell's byte allows its sector, under `keep` where there is one; empty: take plane_options(), and none
   // where that is empty too.  dir_sectors works with a plane as with dir_allow and fills dir_frames /
-  // dir_present_frames / dir_dominant_frames.  Not together with dir_allow >= 0 (one rule at two granularities), nor
-  // with min_blob_cells > 0 / blob_sweep_levels, gmc_max_shift >= 0 / gmc_vectors or gmc_blob_cells > 0 /
-  // gmc_blob_sweep_levels.  keep, keep_centres, sweep_levels, min_run, max_dropout and run_sweep_levels combine.
+  // dir_present_frames / dir_dominant_frames.  A plane and dir_allow >= 0 are one rule at two granularities.
+  // keep_centres, sweep_levels, min_run, max_dropout and run_sweep_levels combine.
   std::vector<uint8_t> dir_plane;
   // Temporal persistence (GpuMotionScanner::set_persist; include/mtgpu_persist.h, include/mtgpu_pipe_boxes.h).  In:
   // min_run > 1: on — a frame counts only as one of a run of at least min_run motion frames; -1: take persist_options();
@@ -1316,52 +1212,14 @@ struct PipelineResult {
   std::string error;
 };
 
-// Process-wide defaults for PipelineResult::min_run / max_dropout / reach / run_sweep_levels (a front end's --min-run,
-// --max-dropout, --reach, --sweep-min-run): set before the first pipeline starts, read by every run_scan_pipeline.
-// min_run <= 1 and no level: off.
-struct PersistOptions {
-  int min_run = 0;
-  uint32_t max_dropout = 0;
-  int reach = -1;
-  std::vector<int> sweep_levels;
-};
+// Process-wide defaults for a PipelineResult's fields (scan_request.hpp has the structs, each with the fields and the
+// front-end options it stands for): set before the first pipeline starts, read by every run_scan_pipeline.
 inline PersistOptions &persist_options() { static PersistOptions o; return o; }
-
-// Process-wide defaults for PipelineResult::gmc_blob_cells / gmc_blob_max_shift / gmc_blob_min_share_q8 /
-// gmc_blob_sweep_levels (a front end's --gmc-blobs, --gmc-blobs-max-shift, --gmc-blobs-min-share-q8, --sweep-gmc-blobs):
-// set before the first pipeline starts, read by every run_scan_pipeline.  min_blob_cells 0 and no level: off.
-struct GmcBlobOptions {
-  int min_blob_cells = 0;
-  int max_shift = MTGPU_GMC_DEFAULT_MAX_SHIFT, min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8;
-  std::vector<int> sweep_levels;
-};
 inline GmcBlobOptions &gmc_blob_options() { static GmcBlobOptions o; return o; }
-
-// Process-wide defaults for PipelineResult::min_blob_cells / blob_sweep_levels (a front end's --min-blob-cells /
-// --sweep-blobs): set before the first pipeline starts, read by every run_scan_pipeline.
-struct BlobOptions { int min_blob_cells = 0; std::vector<int> sweep_levels; };
 inline BlobOptions &blob_options() { static BlobOptions o; return o; }
-
-// Process-wide defaults for PipelineResult::gmc_max_shift / gmc_min_share_q8 / gmc_vectors (a front end's --gmc,
-// --gmc-max-shift, --gmc-min-share-q8, --gmc-vectors): set before the first pipeline starts, read by every
-// run_scan_pipeline.  max_shift < 0: off.
-struct GmcOptions { int max_shift = -1; int min_share_q8 = MTGPU_GMC_DEFAULT_MIN_SHARE_Q8; bool vectors = false; };
 inline GmcOptions &gmc_options() { static GmcOptions o; return o; }
-
-// Process-wide defaults for PipelineResult::dir_allow / dir_sectors (a front end's --allow / --ignore / --dir-sectors):
-// set before the first pipeline starts, read by every run_scan_pipeline.  allow < 0: off.
-struct DirOptions { int allow = -1; bool sectors = false; };
 inline DirOptions &dir_options() { static DirOptions o; return o; }
-
-// Process-wide default for PipelineResult::dir_plane (a front end with ONE plane for every input): set before the first
-// pipeline starts, read by every run_scan_pipeline whose dir_plane is empty.  Empty: none.  A front end whose inputs have
-// grids of their own hands process_batch a plane_for hook instead.
-struct PlaneOptions { std::vector<uint8_t> plane; };
 inline PlaneOptions &plane_options() { static PlaneOptions o; return o; }
-
-// Process-wide defaults for PipelineResult::keep_centres / sweep_levels (a front end's --centres / --sweep): set before
-// the first pipeline starts, read by every run_scan_pipeline.
-struct CentreOptions { bool keep = false; std::vector<int> sweep_levels; };
 inline CentreOptions &centre_options() { static CentreOptions o; return o; }
 
 // The scan + merge part of ProcessingPipeline::run: chunk the timeline, N workers (each with its
@@ -1398,151 +1256,13 @@ int run_scan_pipeline(MakeSource make_source, int num_threads, PipelineResult &o
   std::atomic<long> seek_us{0}, decode_us{0}, analyze_us{0}, init_us{0}, copy_us{0}, submit_us{0}, wait_us{0};
   std::atomic<uint64_t> frames_scanned{0};
   std::atomic<long> worker_cpu_us{0};
-  if (out.sweep_levels.empty()) out.sweep_levels = centre_options().sweep_levels;
-  if (out.min_blob_cells < 0) out.min_blob_cells = blob_options().min_blob_cells;
-  if (out.blob_sweep_levels.empty()) out.blob_sweep_levels = blob_options().sweep_levels;
-  const bool report_largest = !out.blob_sweep_levels.empty();
-  if (report_largest && (out.keep_centres || centre_options().keep || !out.sweep_levels.empty())) {
-    out.error = "blob_sweep_levels together with keep_centres / sweep_levels: the pipe has one count array";
-    return 1;
-  }
-  for (int level : out.blob_sweep_levels)
-    if (level < std::max(1, (int)Config::clusters_needed())) {
-      out.error = "blob sweep level " + std::to_string(level) + " is below max(1, CLUSTERS_NEEDED)";
-      return 1;
-    }
-  if (out.gmc_max_shift == -1) {
-    out.gmc_max_shift = gmc_options().max_shift < 0 ? -2 : gmc_options().max_shift;
-    out.gmc_min_share_q8 = gmc_options().min_share_q8;
-    out.gmc_vectors = out.gmc_vectors || gmc_options().vectors;
-  }
-  const bool gmc_on = out.gmc_max_shift >= 0;
-  if (out.gmc_vectors && !gmc_on) { out.error = "gmc_vectors without compensation (gmc_max_shift)"; return 1; }
-  if (gmc_on && (out.gmc_max_shift > MTGPU_GMC_MAX_SHIFT || out.gmc_min_share_q8 < 0 || out.gmc_min_share_q8 > 256)) {
-    out.error = "gmc_max_shift must be in [0, 127] and gmc_min_share_q8 in [0, 256]";
-    return 1;
-  }
-  if (gmc_on && (out.min_blob_cells > 0 || report_largest)) {
-    out.error = "compensation together with min_blob_cells / blob_sweep_levels: not together yet";
-    return 1;
-  }
-  if (out.gmc_vectors && (out.keep_centres || centre_options().keep || !out.sweep_levels.empty() || report_largest)) {
-    out.error = "gmc_vectors together with keep_centres / sweep_levels / blob_sweep_levels: the pipe has one count array";
-    return 1;
-  }
-  // the compensated blob scan, the pipes' third mode: every conflict is answered here, before any decode
-  if (out.gmc_blob_cells == -1) {
-    out.gmc_blob_cells = gmc_blob_options().min_blob_cells;
-    out.gmc_blob_max_shift = gmc_blob_options().max_shift;
-    out.gmc_blob_min_share_q8 = gmc_blob_options().min_share_q8;
-    if (out.gmc_blob_sweep_levels.empty()) out.gmc_blob_sweep_levels = gmc_blob_options().sweep_levels;
-  }
-  const bool pair_largest = !out.gmc_blob_sweep_levels.empty();
-  const bool pair_on = out.gmc_blob_cells > 0 || pair_largest;
-  if (out.gmc_blob_cells < -1) { out.error = "gmc_blob_cells is " + std::to_string(out.gmc_blob_cells); return 1; }
-  if (pair_on) {
-    if (out.gmc_blob_max_shift < 0 || out.gmc_blob_max_shift > MTGPU_GMC_MAX_SHIFT || out.gmc_blob_min_share_q8 < 0 ||
-        out.gmc_blob_min_share_q8 > 256) {
-      out.error = "gmc_blob_max_shift must be in [0, 127] and gmc_blob_min_share_q8 in [0, 256]";
-      return 1;
-    }
-    if (out.min_blob_cells > 0 || report_largest) {
-      out.error = "gmc_blob_cells / gmc_blob_sweep_levels together with min_blob_cells / blob_sweep_levels: the compensated blob "
-                  "scan has its own minimum blob size";
-      return 1;
-    }
-    if (gmc_on || out.gmc_vectors) {
-      out.error = "gmc_blob_cells / gmc_blob_sweep_levels together with gmc_max_shift / gmc_vectors: the compensated blob scan "
-                  "has its own compensation";
-      return 1;
-    }
-    if (pair_largest && (out.keep_centres || centre_options().keep || !out.sweep_levels.empty())) {
-      out.error = "gmc_blob_sweep_levels together with keep_centres / sweep_levels: the pipe has one count array";
-      return 1;
-    }
-    for (int level : out.gmc_blob_sweep_levels)
-      if (level < std::max(1, (int)Config::clusters_needed())) {
-        out.error = "gmc blob sweep level " + std::to_string(level) + " is below max(1, CLUSTERS_NEEDED)";
-        return 1;
-      }
-  }
-  // the direction filter, the pipes' fourth mode: every conflict is answered here, before any decode
-  if (out.dir_allow == -1) {
-    out.dir_allow = dir_options().allow < 0 ? -2 : dir_options().allow;
-    out.dir_sectors = out.dir_sectors || dir_options().sectors;
-  }
-  const bool dir_on = out.dir_allow >= 0;
-  if (out.dir_allow < -2 || out.dir_allow > 255) { out.error = "dir_allow is " + std::to_string(out.dir_allow) + ": want 0 .. 255, -1 or -2"; return 1; }
-  if (out.dir_plane.empty()) out.dir_plane = plane_options().plane;
-  const bool plane_on = !out.dir_plane.empty();
-  if (out.dir_sectors && !dir_on && !plane_on) { out.error = "dir_sectors without the direction mode (dir_allow)"; return 1; }
-  if (plane_on) {
-    if (dir_on) {
-      out.error = "dir_plane together with dir_allow: a plane and the allow byte are one rule at two granularities";
-      return 1;
-    }
-    if (out.min_blob_cells > 0 || report_largest) {
-      out.error = "dir_plane together with min_blob_cells / blob_sweep_levels: planes and blobs are not together yet";
-      return 1;
-    }
-    if (gmc_on || out.gmc_vectors) {
-      out.error = "dir_plane together with gmc_max_shift / gmc_vectors: planes and compensation are not together yet";
-      return 1;
-    }
-    if (pair_on) {
-      out.error = "dir_plane together with gmc_blob_cells / gmc_blob_sweep_levels: planes and the compensated blob scan are "
-                  "not together yet";
-      return 1;
-    }
-    if (out.dir_sectors && (out.keep_centres || centre_options().keep || !out.sweep_levels.empty())) {
-      out.error = "dir_sectors together with keep_centres / sweep_levels: the pipe has one count array";
-      return 1;
-    }
-  }
-  if (dir_on) {
-    if (out.min_blob_cells > 0 || report_largest) {
-      out.error = "dir_allow together with min_blob_cells / blob_sweep_levels: direction and blobs are not together yet";
-      return 1;
-    }
-    if (gmc_on || out.gmc_vectors) {
-      out.error = "dir_allow together with gmc_max_shift / gmc_vectors: direction and compensation are not together yet";
-      return 1;
-    }
-    if (pair_on) {
-      out.error = "dir_allow together with gmc_blob_cells / gmc_blob_sweep_levels: direction and the compensated blob scan are "
-                  "not together yet";
-      return 1;
-    }
-    if (out.dir_sectors && (out.keep_centres || centre_options().keep || !out.sweep_levels.empty())) {
-      out.error = "dir_sectors together with keep_centres / sweep_levels: the pipe has one count array";
-      return 1;
-    }
-  }
-  // temporal persistence: one pass per recording behind the scan; every conflict is answered here, before any decode
-  if (out.min_run == -1) {
-    out.min_run = persist_options().min_run;
-    out.max_dropout = persist_options().max_dropout;
-    out.reach = persist_options().reach;
-    if (out.run_sweep_levels.empty()) out.run_sweep_levels = persist_options().sweep_levels;
-  }
-  if (out.min_run < -1) { out.error = "min_run is " + std::to_string(out.min_run); return 1; }
-  const bool run_sweep = !out.run_sweep_levels.empty();
-  const bool persist_on = out.min_run > 1 || run_sweep;
-  if (persist_on) {
-    const char *lv = !out.sweep_levels.empty() ? "sweep_levels" : report_largest ? "blob_sweep_levels" : pair_largest ? "gmc_blob_sweep_levels" : nullptr;
-    if (lv) {
-      out.error = std::string(out.min_run > 1 ? "min_run" : "run_sweep_levels") + " together with " + lv +
-                  ": a level sweep under persistence needs one persistence pass per level, which is not built";
-      return 1;
-    }
-    if (out.reach >= 0 && out.min_blob_cells <= 0 && out.gmc_blob_cells <= 0) {
-      out.error = "reach without min_blob_cells / gmc_blob_cells: only a blob scan reports the box that reach compares";
-      return 1;
-    }
-    if (out.reach > 65535) { out.error = "reach " + std::to_string(out.reach) + " outside [0,65535]"; return 1; }
-  }
-  const bool keep_centres = out.keep_centres || centre_options().keep || !out.sweep_levels.empty() || report_largest || out.gmc_vectors ||
-                            pair_largest || out.dir_sectors;
+  // the options' defaults go into `out` and every conflict between the modes is answered here, before any decode
+  const PipelineModes modes = resolve_pipeline(out, PipelineDefaults{centre_options(), blob_options(), gmc_options(), gmc_blob_options(),
+                                                                     dir_options(), plane_options(), persist_options()},
+                                               (int)Config::clusters_needed());
+  if (!modes.error.empty()) { out.error = modes.error; return 1; }
+  const bool gmc_on = modes.gmc_on, pair_on = modes.pair_on, pair_largest = modes.pair_largest, report_largest = modes.report_largest,
+             dir_on = modes.dir_on, persist_on = modes.persist_on, keep_centres = modes.keep_centres;
   std::mutex centres_mu;
   std::vector<TraceEntry> trace;                                       // pooled under centres_mu, as `centres`
   const auto wall0 = std::chrono::high_resolution_clock::now();

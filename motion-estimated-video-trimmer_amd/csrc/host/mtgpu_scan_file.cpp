@@ -466,15 +466,16 @@ int main(int argc, char **argv) {
   }
   // --dir-sectors alone: the mode with every sector allowed
   if (g_print_dir && dir_options().allow < 0 && g_plane_path.empty()) dir_options().allow = 0xff;
+  // the first option that stands for blobs or compensation: what neither a direction plane nor the direction filter goes with
+  const char *const other = g_gmc_opt ? g_gmc_opt : g_pair_opt ? g_pair_opt : g_pair_param_opt ? g_pair_param_opt :
+                            g_print_largest ? "--sweep-blobs" : blob_options().min_blob_cells > 0 ? "--min-blob-cells" :
+                            persist_options().reach >= 0 ? "--reach" : nullptr;
   // what a direction plane cannot be combined with: answered here, before any device call and before the plane is read
   if (!g_plane_path.empty()) {
     if (g_dir_list_opt) {
       std::fprintf(stderr, "error: --plane cannot be combined with %s: a plane and the allow byte are one rule at two granularities\n", g_dir_list_opt);
       return 2;
     }
-    const char *other = g_gmc_opt ? g_gmc_opt : g_pair_opt ? g_pair_opt : g_pair_param_opt ? g_pair_param_opt :
-                        g_print_largest ? "--sweep-blobs" : blob_options().min_blob_cells > 0 ? "--min-blob-cells" :
-                        persist_options().reach >= 0 ? "--reach" : nullptr;
     if (other) {
       std::fprintf(stderr, "error: --plane cannot be combined with %s: planes are not together with blobs or compensation yet\n", other);
       return 2;
@@ -482,9 +483,6 @@ int main(int argc, char **argv) {
   }
   // what the direction filter cannot be combined with: answered here, before any device call
   if (g_dir_opt) {
-    const char *other = g_gmc_opt ? g_gmc_opt : g_pair_opt ? g_pair_opt : g_pair_param_opt ? g_pair_param_opt :
-                        g_print_largest ? "--sweep-blobs" : blob_options().min_blob_cells > 0 ? "--min-blob-cells" :
-                        persist_options().reach >= 0 ? "--reach" : nullptr;
     if (other) {
       std::fprintf(stderr, "error: %s cannot be combined with %s: direction is not together with blobs or compensation yet\n", g_dir_opt, other);
       return 2;

@@ -36,6 +36,7 @@
 
 #include "api_internal.h"
 #include "pack_simd.h"
+#include "pipe_mode.h"
 
 struct mtgpu_batch {
   // pinned host staging: ONE block per batch,
@@ -113,41 +114,17 @@ struct mtgpu_pipe {
   uint64_t *d_keep = nullptr;
   uint64_t keep_words = 0;
   bool masked = false;
-  // mtgpu_pipe_set_blobs (include/mtgpu_pipe_blobs.h): min_blob > 0: every submit runs the blob scan (ctx_launch_blobs),
-  // under the keep plane when `masked`; `report`: which count the batch's one count array receives
-  // (MT_PIPE_REPORT_*).  Both change only while no batch is being filled or in flight.
-  int32_t min_blob = 0;
-  int report = 0;
-  // mtgpu_pipe_set_gmc (include/mtgpu_pipe_gmc.h): gmc != 0: every submit runs the compensated scan (ctx_launch_gmc),
-  // estimate and vote under the keep plane when `masked`; gmc_report: MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_VECTOR.
-  // Never together with min_blob > 0.  They change only while no batch is being filled or in flight.
-  int gmc = 0;
-  int32_t gmc_max_shift = 0, gmc_min_share_q8 = 0;
-  int gmc_report = 0;
-  // mtgpu_pipe_set_gmc_blobs (include/mtgpu_pipe_gmc_blobs.h): pair_blob > 0: every submit runs the compensated blob scan
-  // (ctx_launch_gmc_blobs), under the keep plane when `masked`; pair_report: MT_PIPE_REPORT_*.  A third mode: never
-  // together with min_blob > 0 or gmc.  They change only while no batch is being filled or in flight.
-  int32_t pair_blob = 0;
-  int32_t pair_max_shift = 0, pair_min_share_q8 = 0;
-  int pair_report = 0;
-  // mtgpu_pipe_set_dir (include/mtgpu_pipe_dir.h): dir != 0: every submit runs the direction scan (ctx_launch_dir) with
-  // the allow byte dir_allow, rose and active plane under the keep plane when `masked`; dir_report: MT_PIPE_REPORT_CENTRES
-  // or MT_PIPE_REPORT_SECTORS.  A fourth mode: never together with min_blob > 0, gmc or pair_blob > 0.  They change only
-  // while no batch is being filled or in flight.
-  int dir = 0;
-  int32_t dir_allow = 0;
-  int dir_report = 0;
-  // mtgpu_pipe_set_plane (include/mtgpu_pipe_lanes.h): lanes != 0: every submit runs the plane scan (ctx_launch_lanes)
-  // with the ONE plane d_plane (gh x gw bytes in device memory, owned by the pipe as d_keep is: allocated on first use,
-  // kept across off / on, freed with the pipe), rose and active plane under the keep plane when `masked`; lanes_report:
-  // MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_SECTORS.  h_plane: the bytes as they were given, for mtgpu_pipe_plane.  The
-  // direction rule at a cell's granularity: never together with dir, nor with min_blob > 0, gmc or pair_blob > 0.  They
+  // The ONE scan every submit runs (pipe_mode.h) and its settings: PIPE_PLAIN, or what the last accepted on form of
+  // mtgpu_pipe_set_blobs / _gmc / _gmc_blobs / _dir / _plane asked for — each under the keep plane when `masked`.  Both
   // change only while no batch is being filled or in flight.
+  pipe_mode mode = PIPE_PLAIN;
+  pipe_settings set{};
+  // mtgpu_pipe_set_plane (include/mtgpu_pipe_lanes.h): the ONE direction plane, gh x gw bytes in device memory, owned by
+  // the pipe as d_keep is: allocated on first use, kept across off / on, freed with the pipe.  h_plane: the bytes as they
+  // were given, for mtgpu_pipe_plane.
   uint8_t *d_plane = nullptr;
   uint64_t plane_bytes = 0;
   std::vector<uint8_t> h_plane;
-  int lanes = 0;
-  int lanes_report = 0;
   std::vector<mtgpu_batch *> bufs;
   std::deque<mtgpu_batch *> inflight;
   std::mutex mu;
@@ -297,10 +274,60 @@ bad:
   return rc;
 }
 
-// The refusal between the direction mode and one of the three other modes, worded once for all six places: `runs`
-// (`setter`) is the mode the pipe already has, `other` what cannot stand next to direction.
-int refuse_next_to_dir(const char *runs, const char *setter, const char *other) {
-  return fail(MT_ERR_UNSUPPORTED, "this pipe runs the %s (%s): %s and direction are not together yet", runs, setter, other);
+// Rung 4 of every setter (under the pipe's lock): a setting changes only while no batch is being filled or in flight.
+// `x`: the mode whose setter asks; PIPE_PLAIN: the keep mask's.
+int refuse_busy(const mtgpu_pipe *p, pipe_mode x) {
+  for (const mtgpu_batch *b : p->bufs)
+    if (b->state == 1 || b->state == 2) return fail(MT_ERR_BUSY, PIPE_BUSY_FMT, b->state == 1 ? "being filled" : "in flight", PIPE_BUSY_WORDS[x]);
+  return MT_OK;
+}
+
+// Range rungs that more than one setter has.
+int bad_min_blob(int32_t min_blob_cells) {
+  return fail(MT_ERR_INVALID, "min_blob_cells is %d: want 0 (off) or a cell count >= 1", (int)min_blob_cells);
+}
+int bad_gmc_range(int32_t max_shift, int32_t min_share_q8) {
+  if (max_shift < 0 || max_shift > MTGPU_GMC_MAX_SHIFT)
+    return fail(MT_ERR_INVALID, "max_shift must be in [0, %d], not %d", MTGPU_GMC_MAX_SHIFT, (int)max_shift);
+  if (min_share_q8 < 0 || min_share_q8 > 256) return fail(MT_ERR_INVALID, "min_share_q8 must be in [0, 256], not %d", (int)min_share_q8);
+  return MT_OK;
+}
+
+// What the five mode setters share, behind their own NULL and range rungs: the report code (on form only), the lock, the
+// busy rung, the off form, the refusal, `ready` — ctx_*_supported, or the plane's size and upload — and the store.
+// The off form of x clears the mode only if the pipe runs x: turning x off while y runs is accepted and leaves y alone.
+template <class Ready>
+int set_mode(mtgpu_pipe *p, pipe_mode x, bool on, const pipe_settings &want, Ready ready) {
+  if (on) {
+    const pipe_report_code *r = pipe_report_accepted(x, want.report);
+    if (!r) return fail(MT_ERR_INVALID, PIPE_REPORT_FMT, want.report, PIPE_REPORT_RUNGS[x].want);
+    if (r->travels && !p->centres) return fail(MT_ERR_INVALID, PIPE_REPORT_CENTRES_FMT, r->name, r->travels);
+  }
+  std::lock_guard<std::mutex> lock(p->mu);
+  if (const int busy = refuse_busy(p, x)) return busy;
+  if (!on) {
+    if (p->mode == x) { p->mode = PIPE_PLAIN; p->set = {}; }
+    return MT_OK;
+  }
+  if (p->mode != PIPE_PLAIN && p->mode != x) return fail(PIPE_REFUSALS[p->mode][x].code, "%s", PIPE_REFUSALS[p->mode][x].text);
+  const int rc = ready(p);                                   // MT_ERR_UNSUPPORTED, the grid named: nothing changes
+  if (rc != MT_OK) return rc;
+  p->mode = x;
+  p->set = want;
+  return MT_OK;
+}
+
+// 1 and the settings (each through its pointer, where given) while the pipe runs x, 0 while it does not, -1: p is NULL.
+int get_mode(const mtgpu_pipe *p, pipe_mode x, int32_t *min_blob, int32_t *max_shift, int32_t *min_share_q8, int32_t *allow, int *report) {
+  if (!p) return -1;
+  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
+  if (p->mode != x) return 0;
+  if (min_blob) *min_blob = p->set.min_blob;
+  if (max_shift) *max_shift = p->set.max_shift;
+  if (min_share_q8) *min_share_q8 = p->set.min_share_q8;
+  if (allow) *allow = p->set.allow;
+  if (report) *report = p->set.report;
+  return 1;
 }
 
 // hipSetDevice only when this thread's current device differs (a submit per few hundred
@@ -309,6 +336,32 @@ hipError_t use_device(int dev) {
   int cur = -1;
   if (hipGetDevice(&cur) == hipSuccess && cur == dev) return hipSuccess;
   return hipSetDevice(dev);
+}
+
+// What makes a pipe ready for the plane scan: the plane's size for this grid (MT_ERR_UNSUPPORTED, the grid named: nothing
+// changes), then its bytes go up.  Under the pipe's lock, behind set_mode's refusal: the pipe runs the plain or the plane scan.
+int upload_plane(mtgpu_pipe *q, const uint8_t *plane) {
+  uint64_t bytes = 0;
+  int rc = mtgpu::ctx_lanes_plane_bytes(q->ctx, &bytes);
+  if (rc != MT_OK) return rc;
+  hipError_t e = use_device(mtgpu::ctx_device(q->ctx));
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  std::vector<uint8_t> host;
+  try { host.assign(plane, plane + (size_t)bytes); } catch (const std::bad_alloc &) { return fail(MT_ERR_NOMEM, "out of host memory"); }
+  if (!q->d_plane) {
+    void *d = nullptr;
+    if ((e = hipMalloc(&d, (size_t)bytes)) != hipSuccess) return hip_fail(e, "hipMalloc (direction plane)");
+    q->d_plane = static_cast<uint8_t *>(d);
+    q->plane_bytes = bytes;
+  }
+  // synchronous: no kernel of this pipe is queued or running (no batch in state 2), the next submit finds the plane complete
+  if ((e = hipMemcpy(q->d_plane, plane, (size_t)bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+    q->mode = PIPE_PLAIN;                                  // the plane's contents are unknown: never scan with it
+    q->set = {};                              // (the pipe ran the plain scan or the plane scan here)
+    return hip_fail(e, "hipMemcpy (direction plane)");
+  }
+  q->h_plane.swap(host);
+  return MT_OK;
 }
 
 }  // namespace
@@ -442,8 +495,7 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
   { std::lock_guard<std::mutex> lock(p->mu); nth = ++p->submits; }
   // MT_LAYOUT_BOXES: the two blob modes are handed the batch's box array and run their boxed kernel; every other mode
   // launches exactly what an unboxed pipe launches, and mtgpu_batch_boxes refuses the batch
-  // (the setters keep the two blob modes and the compensated mode apart: a minimum blob size means a blob kernel)
-  const bool blob_mode = (p->pair_blob >= 1 || p->min_blob >= 1) && !p->gmc;
+  const bool blob_mode = p->mode == PIPE_BLOBS || p->mode == PIPE_GMC_BLOBS;
   mt_blob_box *const d_box = (b->boxes && blob_mode) ? b->d_boxes : nullptr;
   b->wrote_boxes = d_box != nullptr;
   if (b->n_frames) {
@@ -455,32 +507,36 @@ int mtgpu_pipe_submit(mtgpu_pipe *p, mtgpu_batch *b) {
       rc = fail(MT_ERR_DEVICE, "injected submit failure (MTGPU_INJECT_SUBMIT_FAIL)");
       goto bad;
     }
-    if (p->pair_blob > 0)   // mtgpu_pipe_set_gmc_blobs: the compensated blob scan, under the pipe's keep plane when it has a mask
-      rc = mtgpu::ctx_launch_gmc_blobs(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
-                                       p->pair_max_shift, p->pair_min_share_q8, p->pair_blob, p->pair_report, b->d_flags,
-                                       b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes, d_box);
-    else if (p->gmc)   // mtgpu_pipe_set_gmc: the compensated scan, estimate and vote under the pipe's keep plane when it has a mask
-      rc = mtgpu::ctx_launch_gmc(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
-                                 p->gmc_max_shift, p->gmc_min_share_q8, p->gmc_report == MT_PIPE_REPORT_VECTOR ? 1 : 0, b->d_flags,
-                                 b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
-    else if (p->min_blob > 0)   // mtgpu_pipe_set_blobs: the blob scan, under the pipe's keep plane when it has a mask
-      rc = mtgpu::ctx_launch_blobs(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
-                                   p->min_blob, p->report == MT_PIPE_REPORT_LARGEST ? 1 : 0, b->d_flags, b->d_centres, st,
-                                   b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes, d_box);
-    else if (p->dir)   // mtgpu_pipe_set_dir: the direction scan, rose and active plane under the pipe's keep plane when it has a mask
-      rc = mtgpu::ctx_launch_dir(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
-                                 p->dir_allow, p->dir_report == MT_PIPE_REPORT_SECTORS ? 1 : 0, b->d_flags, b->d_centres, st,
-                                 b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
-    else if (p->lanes)   // mtgpu_pipe_set_plane: the plane scan, rose and active plane under the pipe's keep plane when it has a mask
-      rc = mtgpu::ctx_launch_lanes(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->masked ? p->d_keep : nullptr,
-                                   p->d_plane, p->lanes_report == MT_PIPE_REPORT_SECTORS ? 1 : 0, b->d_flags, b->d_centres, st,
-                                   b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
-    else if (p->masked)   // mtgpu_pipe_set_keep: the masked scan, its work list in the batch's own block like the plain one's
-      rc = mtgpu::ctx_launch_zones(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, p->d_keep, b->d_flags,
-                                   b->d_centres, st, b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes);
-    else
-      rc = mtgpu::ctx_launch_scan(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, b->d_flags, st,
-                                  b->rec_bytes, b->zero_copy ? 1 : 0, b->d_plan, b->plan_bytes, b->d_centres);
+    const uint64_t *const keep = p->masked ? p->d_keep : nullptr;   // every mode runs under the pipe's keep plane when it has a mask
+    const pipe_settings &v = p->set;
+    const int zc = b->zero_copy ? 1 : 0;
+    switch (p->mode) {
+      case PIPE_GMC_BLOBS:
+        rc = mtgpu::ctx_launch_gmc_blobs(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, keep, v.max_shift, v.min_share_q8, v.min_blob,
+                                         v.report, b->d_flags, b->d_centres, st, b->rec_bytes, zc, b->d_plan, b->plan_bytes, d_box);
+        break;
+      case PIPE_GMC:
+        rc = mtgpu::ctx_launch_gmc(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, keep, v.max_shift, v.min_share_q8,
+                                   v.report == MT_PIPE_REPORT_VECTOR ? 1 : 0, b->d_flags, b->d_centres, st, b->rec_bytes, zc, b->d_plan, b->plan_bytes);
+        break;
+      case PIPE_BLOBS:
+        rc = mtgpu::ctx_launch_blobs(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, keep, v.min_blob, v.report == MT_PIPE_REPORT_LARGEST ? 1 : 0,
+                                     b->d_flags, b->d_centres, st, b->rec_bytes, zc, b->d_plan, b->plan_bytes, d_box);
+        break;
+      case PIPE_DIR:
+        rc = mtgpu::ctx_launch_dir(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, keep, v.allow, v.report == MT_PIPE_REPORT_SECTORS ? 1 : 0,
+                                   b->d_flags, b->d_centres, st, b->rec_bytes, zc, b->d_plan, b->plan_bytes);
+        break;
+      case PIPE_PLANE:
+        rc = mtgpu::ctx_launch_lanes(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, keep, p->d_plane, v.report == MT_PIPE_REPORT_SECTORS ? 1 : 0,
+                                     b->d_flags, b->d_centres, st, b->rec_bytes, zc, b->d_plan, b->plan_bytes);
+        break;
+      default:   // PIPE_PLAIN: the masked scan under a keep mask (its work list in the batch's own block like the plain one's)
+        rc = keep ? mtgpu::ctx_launch_zones(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, keep, b->d_flags, b->d_centres, st, b->rec_bytes, zc,
+                                            b->d_plan, b->plan_bytes)
+                  : mtgpu::ctx_launch_scan(p->ctx, b->d_mv, b->n_records, b->d_off, b->d_sd, b->n_frames, b->d_flags, st, b->rec_bytes, zc, b->d_plan,
+                                           b->plan_bytes, b->d_centres);
+    }
     if (rc != MT_OK) goto bad;
     if (!b->zero_copy) {
       PIPE_TRY(hipMemcpyAsync(b->h_flags, b->d_flags, b->n_frames, hipMemcpyDeviceToHost, st));
@@ -598,10 +654,7 @@ int mtgpu_pipe_get_stats(mtgpu_pipe *p, mtgpu_pipe_stats *out) {
 int mtgpu_pipe_set_keep(mtgpu_pipe *p, const uint64_t *keep) {
   if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
   std::lock_guard<std::mutex> lock(p->mu);
-  for (const mtgpu_batch *b : p->bufs)
-    if (b->state == 1 || b->state == 2)
-      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the keep mask",
-                  b->state == 1 ? "being filled" : "in flight");
+  if (const int busy = refuse_busy(p, PIPE_PLAIN)) return busy;
   if (!keep) { p->masked = false; return MT_OK; }           // the plain scan again; the plane stays allocated (see mtgpu_pipe)
   uint64_t words = 0;
   int rc = mtgpu::ctx_zones_keep_words(p->ctx, &words);      // MT_ERR_UNSUPPORTED, the grid named: nothing changes
@@ -629,226 +682,65 @@ int mtgpu_pipe_has_keep(const mtgpu_pipe *p) {
   return p->masked ? 1 : 0;
 }
 
+// The five mode setters.  Each body holds what is its own — which argument means "on", its range rungs, its settings
+// {min_blob, max_shift, min_share_q8, allow, report}, what makes the context ready — and set_mode (above) does the rest
+// in one order for all.  The getters return 1 and the settings while their mode is the pipe's, 0 otherwise.
+
 int mtgpu_pipe_set_blobs(mtgpu_pipe *p, int32_t min_blob_cells, int report) {
   if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
-  if (min_blob_cells < 0) return fail(MT_ERR_INVALID, "min_blob_cells is %d: want 0 (off) or a cell count >= 1", (int)min_blob_cells);
-  if (min_blob_cells > 0) {
-    if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_LARGEST)
-      return fail(MT_ERR_INVALID, "report is %d: want MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_LARGEST", report);
-    if (report == MT_PIPE_REPORT_LARGEST && !p->centres)
-      return fail(MT_ERR_INVALID, "MT_PIPE_REPORT_LARGEST needs a pipe with MT_LAYOUT_CENTRES: the largest blob travels in its count array");
-  }
-  std::lock_guard<std::mutex> lock(p->mu);
-  for (const mtgpu_batch *b : p->bufs)
-    if (b->state == 1 || b->state == 2)
-      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the blob setting",
-                  b->state == 1 ? "being filled" : "in flight");
-  if (min_blob_cells == 0) { p->min_blob = 0; p->report = 0; return MT_OK; }
-  if (p->pair_blob > 0)
-    return fail(MT_ERR_INVALID, "this pipe runs the compensated blob scan (mtgpu_pipe_set_gmc_blobs): turn it off first, or change "
-                "min_blob_cells through mtgpu_pipe_set_gmc_blobs");
-  if (p->gmc)
-    return fail(MT_ERR_UNSUPPORTED, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): blobs and compensation are "
-                "not together yet");
-  if (p->dir) return refuse_next_to_dir("direction scan", "mtgpu_pipe_set_dir", "blobs");
-  if (p->lanes) return refuse_next_to_dir("plane scan", "mtgpu_pipe_set_plane", "blobs");
-  const int rc = mtgpu::ctx_blobs_supported(p->ctx);         // MT_ERR_UNSUPPORTED, the grid named: nothing changes
-  if (rc != MT_OK) return rc;
-  p->min_blob = min_blob_cells;
-  p->report = report;
-  return MT_OK;
+  if (min_blob_cells < 0) return bad_min_blob(min_blob_cells);
+  return set_mode(p, PIPE_BLOBS, min_blob_cells > 0, {min_blob_cells, 0, 0, 0, report}, [](mtgpu_pipe *q) { return mtgpu::ctx_blobs_supported(q->ctx); });
 }
 
 int mtgpu_pipe_blobs(const mtgpu_pipe *p, int32_t *min_blob_cells, int *report) {
-  if (!p) return -1;
-  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
-  if (p->min_blob <= 0) return 0;
-  if (min_blob_cells) *min_blob_cells = p->min_blob;
-  if (report) *report = p->report;
-  return 1;
+  return get_mode(p, PIPE_BLOBS, min_blob_cells, nullptr, nullptr, nullptr, report);
 }
 
 int mtgpu_pipe_set_gmc(mtgpu_pipe *p, int enable, int32_t max_shift, int32_t min_share_q8, int report) {
   if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
-  if (enable) {
-    if (max_shift < 0 || max_shift > MTGPU_GMC_MAX_SHIFT)
-      return fail(MT_ERR_INVALID, "max_shift must be in [0, %d], not %d", MTGPU_GMC_MAX_SHIFT, (int)max_shift);
-    if (min_share_q8 < 0 || min_share_q8 > 256) return fail(MT_ERR_INVALID, "min_share_q8 must be in [0, 256], not %d", (int)min_share_q8);
-    if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_VECTOR)
-      return fail(MT_ERR_INVALID, "report is %d: want MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_VECTOR", report);
-    if (report == MT_PIPE_REPORT_VECTOR && !p->centres)
-      return fail(MT_ERR_INVALID, "MT_PIPE_REPORT_VECTOR needs a pipe with MT_LAYOUT_CENTRES: the applied vector travels in its count array");
-  }
-  std::lock_guard<std::mutex> lock(p->mu);
-  for (const mtgpu_batch *b : p->bufs)
-    if (b->state == 1 || b->state == 2)
-      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the compensation setting",
-                  b->state == 1 ? "being filled" : "in flight");
-  if (!enable) { p->gmc = 0; p->gmc_max_shift = 0; p->gmc_min_share_q8 = 0; p->gmc_report = 0; return MT_OK; }
-  if (p->pair_blob > 0)
-    return fail(MT_ERR_INVALID, "this pipe runs the compensated blob scan (mtgpu_pipe_set_gmc_blobs): turn it off first, or change "
-                "the compensation through mtgpu_pipe_set_gmc_blobs");
-  if (p->min_blob > 0)
-    return fail(MT_ERR_UNSUPPORTED, "this pipe runs the blob scan (mtgpu_pipe_set_blobs): blobs and compensation are not "
-                "together yet");
-  if (p->dir) return refuse_next_to_dir("direction scan", "mtgpu_pipe_set_dir", "compensation");
-  if (p->lanes) return refuse_next_to_dir("plane scan", "mtgpu_pipe_set_plane", "compensation");
-  const int rc = mtgpu::ctx_gmc_supported(p->ctx);           // MT_ERR_UNSUPPORTED, the grid named: nothing changes
-  if (rc != MT_OK) return rc;
-  p->gmc = 1;
-  p->gmc_max_shift = max_shift;
-  p->gmc_min_share_q8 = min_share_q8;
-  p->gmc_report = report;
-  return MT_OK;
+  if (enable)
+    if (const int bad = bad_gmc_range(max_shift, min_share_q8)) return bad;
+  return set_mode(p, PIPE_GMC, enable != 0, {0, max_shift, min_share_q8, 0, report}, [](mtgpu_pipe *q) { return mtgpu::ctx_gmc_supported(q->ctx); });
 }
 
 int mtgpu_pipe_gmc(const mtgpu_pipe *p, int32_t *max_shift, int32_t *min_share_q8, int *report) {
-  if (!p) return -1;
-  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
-  if (!p->gmc) return 0;
-  if (max_shift) *max_shift = p->gmc_max_shift;
-  if (min_share_q8) *min_share_q8 = p->gmc_min_share_q8;
-  if (report) *report = p->gmc_report;
-  return 1;
+  return get_mode(p, PIPE_GMC, nullptr, max_shift, min_share_q8, nullptr, report);
 }
 
 int mtgpu_pipe_set_gmc_blobs(mtgpu_pipe *p, int32_t min_blob_cells, int32_t max_shift, int32_t min_share_q8, int report) {
   if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
-  if (min_blob_cells < 0) return fail(MT_ERR_INVALID, "min_blob_cells is %d: want 0 (off) or a cell count >= 1", (int)min_blob_cells);
-  if (min_blob_cells > 0) {
-    if (max_shift < 0 || max_shift > MTGPU_GMC_MAX_SHIFT)
-      return fail(MT_ERR_INVALID, "max_shift must be in [0, %d], not %d", MTGPU_GMC_MAX_SHIFT, (int)max_shift);
-    if (min_share_q8 < 0 || min_share_q8 > 256) return fail(MT_ERR_INVALID, "min_share_q8 must be in [0, 256], not %d", (int)min_share_q8);
-    if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_LARGEST && report != MT_PIPE_REPORT_VECTOR)
-      return fail(MT_ERR_INVALID, "report is %d: want MT_PIPE_REPORT_CENTRES, MT_PIPE_REPORT_LARGEST or MT_PIPE_REPORT_VECTOR", report);
-    if (report != MT_PIPE_REPORT_CENTRES && !p->centres)
-      return fail(MT_ERR_INVALID, "%s needs a pipe with MT_LAYOUT_CENTRES: the %s travels in its count array",
-                  report == MT_PIPE_REPORT_LARGEST ? "MT_PIPE_REPORT_LARGEST" : "MT_PIPE_REPORT_VECTOR",
-                  report == MT_PIPE_REPORT_LARGEST ? "largest blob" : "applied vector");
-  }
-  std::lock_guard<std::mutex> lock(p->mu);
-  for (const mtgpu_batch *b : p->bufs)
-    if (b->state == 1 || b->state == 2)
-      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the compensated "
-                  "blob setting", b->state == 1 ? "being filled" : "in flight");
-  if (min_blob_cells == 0) { p->pair_blob = 0; p->pair_max_shift = 0; p->pair_min_share_q8 = 0; p->pair_report = 0; return MT_OK; }
-  if (p->min_blob > 0)
-    return fail(MT_ERR_INVALID, "this pipe runs the blob scan (mtgpu_pipe_set_blobs): turn it off first "
-                "(mtgpu_pipe_set_blobs(pipe, 0, 0)), then call mtgpu_pipe_set_gmc_blobs");
-  if (p->gmc)
-    return fail(MT_ERR_INVALID, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): turn it off first "
-                "(mtgpu_pipe_set_gmc(pipe, 0, 0, 0, 0)), then call mtgpu_pipe_set_gmc_blobs");
-  if (p->dir) return refuse_next_to_dir("direction scan", "mtgpu_pipe_set_dir", "the compensated blob scan");
-  if (p->lanes) return refuse_next_to_dir("plane scan", "mtgpu_pipe_set_plane", "the compensated blob scan");
-  const int rc = mtgpu::ctx_gmc_blobs_supported(p->ctx);     // MT_ERR_UNSUPPORTED, the grid named: nothing changes
-  if (rc != MT_OK) return rc;
-  p->pair_blob = min_blob_cells;
-  p->pair_max_shift = max_shift;
-  p->pair_min_share_q8 = min_share_q8;
-  p->pair_report = report;
-  return MT_OK;
+  if (min_blob_cells < 0) return bad_min_blob(min_blob_cells);
+  if (min_blob_cells > 0)
+    if (const int bad = bad_gmc_range(max_shift, min_share_q8)) return bad;
+  return set_mode(p, PIPE_GMC_BLOBS, min_blob_cells > 0, {min_blob_cells, max_shift, min_share_q8, 0, report},
+                  [](mtgpu_pipe *q) { return mtgpu::ctx_gmc_blobs_supported(q->ctx); });
 }
 
 int mtgpu_pipe_gmc_blobs(const mtgpu_pipe *p, int32_t *min_blob_cells, int32_t *max_shift, int32_t *min_share_q8, int *report) {
-  if (!p) return -1;
-  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
-  if (p->pair_blob <= 0) return 0;
-  if (min_blob_cells) *min_blob_cells = p->pair_blob;
-  if (max_shift) *max_shift = p->pair_max_shift;
-  if (min_share_q8) *min_share_q8 = p->pair_min_share_q8;
-  if (report) *report = p->pair_report;
-  return 1;
+  return get_mode(p, PIPE_GMC_BLOBS, min_blob_cells, max_shift, min_share_q8, nullptr, report);
 }
 
 int mtgpu_pipe_set_dir(mtgpu_pipe *p, int enable, int32_t allow, int report) {
   if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
-  if (enable) {
-    if (allow < 0 || allow > 255) return fail(MT_ERR_INVALID, "allow must be in [0, 255], not %d", (int)allow);
-    if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_SECTORS)
-      return fail(MT_ERR_INVALID, "report is %d: want MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_SECTORS", report);
-    if (report == MT_PIPE_REPORT_SECTORS && !p->centres)
-      return fail(MT_ERR_INVALID, "MT_PIPE_REPORT_SECTORS needs a pipe with MT_LAYOUT_CENTRES: the sector word travels in its count array");
-  }
-  std::lock_guard<std::mutex> lock(p->mu);
-  for (const mtgpu_batch *b : p->bufs)
-    if (b->state == 1 || b->state == 2)
-      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the direction setting",
-                  b->state == 1 ? "being filled" : "in flight");
-  if (!enable) { p->dir = 0; p->dir_allow = 0; p->dir_report = 0; return MT_OK; }
-  if (p->lanes)
-    return fail(MT_ERR_INVALID, "this pipe runs the plane scan (mtgpu_pipe_set_plane): a plane and the allow byte are one rule at two "
-                "granularities; turn the plane off first (mtgpu_pipe_set_plane(pipe, NULL, 0))");
-  if (p->min_blob > 0) return refuse_next_to_dir("blob scan", "mtgpu_pipe_set_blobs", "blobs");
-  if (p->gmc) return refuse_next_to_dir("compensated scan", "mtgpu_pipe_set_gmc", "compensation");
-  if (p->pair_blob > 0) return refuse_next_to_dir("compensated blob scan", "mtgpu_pipe_set_gmc_blobs", "the compensated blob scan");
-  const int rc = mtgpu::ctx_dir_supported(p->ctx);           // MT_ERR_UNSUPPORTED, the grid named: nothing changes
-  if (rc != MT_OK) return rc;
-  p->dir = 1;
-  p->dir_allow = allow;
-  p->dir_report = report;
-  return MT_OK;
+  if (enable && (allow < 0 || allow > 255)) return fail(MT_ERR_INVALID, "allow must be in [0, 255], not %d", (int)allow);
+  return set_mode(p, PIPE_DIR, enable != 0, {0, 0, 0, allow, report}, [](mtgpu_pipe *q) { return mtgpu::ctx_dir_supported(q->ctx); });
 }
 
 int mtgpu_pipe_dir(const mtgpu_pipe *p, int32_t *allow, int *report) {
-  if (!p) return -1;
-  std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
-  if (!p->dir) return 0;
-  if (allow) *allow = p->dir_allow;
-  if (report) *report = p->dir_report;
-  return 1;
+  return get_mode(p, PIPE_DIR, nullptr, nullptr, nullptr, allow, report);
 }
 
 int mtgpu_pipe_set_plane(mtgpu_pipe *p, const uint8_t *plane, int report) {
   if (!p) return fail(MT_ERR_INVALID, "pipe is NULL");
-  if (plane) {
-    if (report != MT_PIPE_REPORT_CENTRES && report != MT_PIPE_REPORT_SECTORS)
-      return fail(MT_ERR_INVALID, "report is %d: want MT_PIPE_REPORT_CENTRES or MT_PIPE_REPORT_SECTORS", report);
-    if (report == MT_PIPE_REPORT_SECTORS && !p->centres)
-      return fail(MT_ERR_INVALID, "MT_PIPE_REPORT_SECTORS needs a pipe with MT_LAYOUT_CENTRES: the sector word travels in its count array");
-  }
-  std::lock_guard<std::mutex> lock(p->mu);
-  for (const mtgpu_batch *b : p->bufs)
-    if (b->state == 1 || b->state == 2)
-      return fail(MT_ERR_BUSY, "a batch of this pipe is %s: submit / collect it (or release it) before changing the direction plane",
-                  b->state == 1 ? "being filled" : "in flight");
-  if (!plane) { p->lanes = 0; p->lanes_report = 0; return MT_OK; }   // the plane stays allocated, as the keep plane does
-  if (p->dir)
-    return fail(MT_ERR_INVALID, "this pipe runs the direction scan (mtgpu_pipe_set_dir): a plane and the allow byte are one rule at "
-                "two granularities; turn the byte off first (mtgpu_pipe_set_dir(pipe, 0, 0, 0))");
-  if (p->min_blob > 0) return refuse_next_to_dir("blob scan", "mtgpu_pipe_set_blobs", "blobs");
-  if (p->gmc) return refuse_next_to_dir("compensated scan", "mtgpu_pipe_set_gmc", "compensation");
-  if (p->pair_blob > 0) return refuse_next_to_dir("compensated blob scan", "mtgpu_pipe_set_gmc_blobs", "the compensated blob scan");
-  uint64_t bytes = 0;
-  int rc = mtgpu::ctx_lanes_plane_bytes(p->ctx, &bytes);     // MT_ERR_UNSUPPORTED, the grid named: nothing changes
-  if (rc != MT_OK) return rc;
-  hipError_t e = use_device(mtgpu::ctx_device(p->ctx));
-  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-  std::vector<uint8_t> host;
-  try { host.assign(plane, plane + (size_t)bytes); } catch (const std::bad_alloc &) { return fail(MT_ERR_NOMEM, "out of host memory"); }
-  if (!p->d_plane) {
-    void *d = nullptr;
-    if ((e = hipMalloc(&d, (size_t)bytes)) != hipSuccess) return hip_fail(e, "hipMalloc (direction plane)");
-    p->d_plane = static_cast<uint8_t *>(d);
-    p->plane_bytes = bytes;
-  }
-  // synchronous: no kernel of this pipe is queued or running (no batch in state 2), the next submit finds the plane complete
-  if ((e = hipMemcpy(p->d_plane, plane, (size_t)bytes, hipMemcpyHostToDevice)) != hipSuccess) {
-    p->lanes = 0;                                            // the plane's contents are unknown: never scan with it
-    p->lanes_report = 0;
-    return hip_fail(e, "hipMemcpy (direction plane)");
-  }
-  p->h_plane.swap(host);
-  p->lanes = 1;
-  p->lanes_report = report;
-  return MT_OK;
+  return set_mode(p, PIPE_PLANE, plane != nullptr, {0, 0, 0, 0, report}, [plane](mtgpu_pipe *q) { return upload_plane(q, plane); });
 }
 
 int mtgpu_pipe_plane(const mtgpu_pipe *p, uint8_t *plane, int *report) {
   if (!p) return -1;
   std::lock_guard<std::mutex> lock(const_cast<mtgpu_pipe *>(p)->mu);
-  if (!p->lanes) return 0;
+  if (p->mode != PIPE_PLANE) return 0;
   if (plane) std::memcpy(plane, p->h_plane.data(), p->h_plane.size());
-  if (report) *report = p->lanes_report;
+  if (report) *report = p->set.report;
   return 1;
 }
 

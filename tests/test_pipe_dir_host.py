@@ -53,8 +53,11 @@ def test_both_forms_of_the_kernel_are_in_the_library_and_the_pipe_reads_no_new_e
     pipe_src = open(os.path.join(PKG, "csrc", "pipe.hip")).read()
     assert pipe_src.count("getenv") == 4
     assert "getenv" not in open(os.path.join(PKG, "csrc", "dir_kernels.hip")).read()
-    sub = pipe_src[pipe_src.index("int mtgpu_pipe_submit("):]
-    assert sub.index("p->min_blob > 0") < sub.index("else if (p->dir)") < sub.index("else if (p->masked)")
+    # which scan a submit runs is the pipe's ONE mode (csrc/pipe_mode.h), so there is no order of tests left to hold: that no
+    # second mode can be on next to this one is held by cases (a) and (b) of tests/golden/pipe_mode_matrix.json, recorded from
+    # the commit before the modes became one value, together with this mode's result tests (tests/test_gpu_pipe_dir.py)
+    import pipe_mode_matrix as pm
+    assert pm.excludes_every_other("dir")
 
 
 def test_header_compiles_alone_as_c11_and_as_cpp17(tmp_path):
@@ -76,9 +79,8 @@ def test_python_and_host_layer_expose_it():
                  "uint64_t dir_present_frames[8]", "uint64_t dir_dominant_frames[8]", "inline DirOptions &dir_options()",
                  "scanners[i]->report_sectors(out.dir_sectors)"):
         assert text in host, text
-    # initialize() turns direction off before it settles any other mode
-    init = host[host.index("bool initialize("):]
-    assert init.index("mtgpu_pipe_set_dir(pipe_, 0, 0, 0)") < init.index("mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0)")
+    # initialize() turns every mode off before it settles this video's one (all_off): held on a GPU by the 36 "the previous
+    # video ran X, this video asks Y" pairs of tests/test_gpu_host_mode_matrix.py
     tool = open(os.path.join(PKG, "csrc", "host", "mtgpu_scan_file.cpp")).read()
     for opt in ('"--allow"', '"--ignore"', '"--dir-sectors"'):
         assert opt in tool

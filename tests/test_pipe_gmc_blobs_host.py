@@ -54,8 +54,11 @@ def test_all_four_forms_of_the_kernel_are_in_the_library_and_the_submit_tests_th
     pipe_src = open(os.path.join(PKG, "csrc", "pipe.hip")).read()
     assert pipe_src.count("getenv") == 4
     assert "getenv" not in open(os.path.join(PKG, "csrc", "gmc_blobs_kernels.hip")).read()
-    sub = pipe_src[pipe_src.index("int mtgpu_pipe_submit("):]
-    assert sub.index("if (p->pair_blob > 0)") < sub.index("if (p->gmc)") < sub.index("p->min_blob > 0") < sub.index("else if (p->masked)")
+    # which scan a submit runs is the pipe's ONE mode (csrc/pipe_mode.h), so there is no order of tests left to hold: that no
+    # second mode can be on next to this one is held by cases (a) and (b) of tests/golden/pipe_mode_matrix.json, recorded from
+    # the commit before the modes became one value, together with this mode's result tests (tests/test_gpu_pipe_gmc_blobs.py)
+    import pipe_mode_matrix as pm
+    assert pm.excludes_every_other("gmc_blobs")
 
 
 def test_headers_compile_as_c_and_cpp_either_one_first(tmp_path):
@@ -79,10 +82,8 @@ def test_python_and_host_layer_expose_it():
                  "std::vector<int> gmc_blob_sweep_levels;", "std::vector<SweepEntry> gmc_blob_sweep;",
                  "inline GmcBlobOptions &gmc_blob_options()"):
         assert text in host, text
-    # initialize(): the pair off first, the existing sequence, the pair on last
-    init = host[host.index("bool initialize("):host.index("double get_duration()")]
-    assert init.index("mtgpu_pipe_set_gmc_blobs(pipe_, 0, 0, 0, 0)") < init.index("mtgpu_pipe_set_gmc(pipe_, 0, 0, 0, 0)") < \
-        init.index("mtgpu_pipe_set_keep(pipe_, keep_.data())") < init.index("mtgpu_pipe_set_gmc_blobs(pipe_, std::max(1, gmc_blob_cells_)")
+    # initialize() turns every mode off before it settles this video's one (all_off): held on a GPU by the 36 "the previous
+    # video ran X, this video asks Y" pairs of tests/test_gpu_host_mode_matrix.py
     tool = open(os.path.join(PKG, "csrc", "host", "mtgpu_scan_file.cpp")).read()
     for opt in ('"--gmc-blobs"', '"--gmc-blobs-max-shift"', '"--gmc-blobs-min-share-q8"', '"--sweep-gmc-blobs"'):
         assert opt in tool
@@ -153,14 +154,19 @@ def test_what_combines_is_no_usage_error(args):
 
 
 def test_the_single_modes_still_refuse_each_other_in_the_same_words():
-    pipe_src = open(os.path.join(PKG, "csrc", "pipe.hip")).read()
-    assert pipe_src.count('"not together yet");') == 1 and pipe_src.count('"together yet");') == 1
-    for text in ('fail(MT_ERR_UNSUPPORTED, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): blobs and compensation are "',
-                 'fail(MT_ERR_UNSUPPORTED, "this pipe runs the blob scan (mtgpu_pipe_set_blobs): blobs and compensation are not "'):
-        assert text in pipe_src, text
-    host = open(os.path.join(PKG, "csrc", "host", "mtgpu_host.hpp")).read()
-    assert '"compensation and blobs are not together yet"' in host
-    assert '"compensation together with min_blob_cells / blob_sweep_levels: not together yet"' in host
+    """The whole sentences, as a GPU answered them at the commit before the refusals became tables (tests/golden/
+    pipe_mode_matrix.json, host_mode_matrix.json); tests/test_pipe_mode_host.py and tests/test_scan_request_host.py hold the
+    tables to every one of them."""
+    import host_mode_matrix as hm
+    import pipe_mode_matrix as pm
+    ans = pm.recorded()
+    assert (ans["a/gmc/blobs"][1]["rc"], ans["a/gmc/blobs"][1]["error"]) == \
+        (_abi.MT_ERR_UNSUPPORTED, "this pipe runs the compensated scan (mtgpu_pipe_set_gmc): blobs and compensation are not together yet")
+    assert (ans["a/blobs/gmc"][1]["rc"], ans["a/blobs/gmc"][1]["error"]) == \
+        (_abi.MT_ERR_UNSUPPORTED, "this pipe runs the blob scan (mtgpu_pipe_set_blobs): blobs and compensation are not together yet")
+    _, scanner, pipeline = hm.load()
+    assert "compensation and blobs are not together yet" in {v[0] for v in scanner.values()}
+    assert "compensation together with min_blob_cells / blob_sweep_levels: not together yet" in {v[2] for v in pipeline.values()}
     for name in ("mtgpu_gmc_blobs.h", "mtgpu_pipe_gmc.h", "mtgpu_pipe_blobs.h"):
         assert "mtgpu_pipe_gmc_blobs.h" in open(os.path.join(ROOT, "include", name)).read(), name
     assert "mtgpu_pipe_gmc_blobs.h" in open(os.path.join(PKG, "csrc", "gmc_blobs_kernels.hip")).read()

@@ -52,9 +52,11 @@ def test_both_forms_of_the_kernel_are_in_the_library_and_the_pipe_reads_no_new_e
     pipe_src = open(os.path.join(PKG, "csrc", "pipe.hip")).read()
     assert pipe_src.count("getenv") == 4
     assert "getenv" not in open(os.path.join(PKG, "csrc", "gmc_kernels.hip")).read()
-    # the submit tests the new setting first
-    sub = pipe_src[pipe_src.index("int mtgpu_pipe_submit("):]
-    assert sub.index("if (p->gmc)") < sub.index("p->min_blob > 0") < sub.index("else if (p->masked)")
+    # which scan a submit runs is the pipe's ONE mode (csrc/pipe_mode.h), so there is no order of tests left to hold: that no
+    # second mode can be on next to this one is held by cases (a) and (b) of tests/golden/pipe_mode_matrix.json, recorded from
+    # the commit before the modes became one value, together with this mode's result tests (tests/test_gpu_pipe_gmc.py)
+    import pipe_mode_matrix as pm
+    assert pm.excludes_every_other("gmc")
 
 
 def test_headers_compile_as_c_and_cpp_either_one_first(tmp_path):

@@ -161,11 +161,19 @@ def test_what_combines_is_no_usage_error(args):
 
 
 def test_the_pipeline_refuses_the_same_combinations_and_names_both_sides():
-    host = open(os.path.join(PKG, "csrc", "host", "mtgpu_host.hpp")).read()
-    for text in ('" together with " + lv +', '": a level sweep under persistence needs one persistence pass per level, which is not built"',
-                 '"reach without min_blob_cells / gmc_blob_cells: only a blob scan reports the box that reach compares"',
-                 '"set_persist with reach >= 0 needs set_min_blob_cells(n > 0) or set_gmc_blobs(n > 0): only a blob scan reports the box "'):
-        assert text in host, text
+    """The whole sentences, as run_scan_pipeline and initialize() gave them on a GPU at the commit before the refusals became
+    tables (tests/golden/host_mode_matrix.json); tests/test_scan_request_host.py holds csrc/host/scan_request.hpp to every
+    recorded case."""
+    import host_mode_matrix as hm
+    _, scanner, pipeline = hm.load()
+    said = {v[2] for v in pipeline.values()}
+    for mine in ("min_run", "run_sweep_levels"):
+        for other in ("sweep_levels", "blob_sweep_levels", "gmc_blob_sweep_levels"):
+            assert mine + " together with " + other + ": a level sweep under persistence needs one persistence pass per level, which is " \
+                "not built" in said, (mine, other)
+    assert "reach without min_blob_cells / gmc_blob_cells: only a blob scan reports the box that reach compares" in said
+    assert "set_persist with reach >= 0 needs set_min_blob_cells(n > 0) or set_gmc_blobs(n > 0): only a blob scan reports the box " \
+        "that reach compares" in {v[0] for v in scanner.values()}
 
 
 # ------------------------------------------------------------------ the worked numbers, by the models alone
