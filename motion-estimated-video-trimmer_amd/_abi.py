@@ -332,6 +332,11 @@ ABI_PIPE_LANES = {
     "mtgpu_pipe_plane": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
 }
 
+# every table above, in header order: what load_library() binds
+ABI_TABLES = (ABI, ABI_MOTION, ABI_SWEEP, ABI_ACTIVITY, ABI_ZONES, ABI_PIPE_ZONES, ABI_BLOBS, ABI_PIPE_BLOBS, ABI_GMC,
+              ABI_PIPE_GMC, ABI_GMC_BLOBS, ABI_PIPE_GMC_BLOBS, ABI_PERSIST, ABI_PIPE_BOXES, ABI_DIR, ABI_PIPE_DIR, ABI_LANES,
+              ABI_PIPE_LANES)
+
 _lib = None
 
 
@@ -361,15 +366,11 @@ def load_library(path=None):
             f"{p} not found: build it with `make -C {os.path.join(PKG_DIR, 'csrc')}` "
             "(or __graft_entry__.build()).  There is no fallback path.")
     lib = C.CDLL(p)
-    for name, (res, args) in list(ABI.items()) + list(ABI_MOTION.items()) + list(ABI_SWEEP.items()) + \
-            list(ABI_ACTIVITY.items()) + list(ABI_ZONES.items()) + list(ABI_PIPE_ZONES.items()) + list(ABI_BLOBS.items()) + \
-            list(ABI_PIPE_BLOBS.items()) + list(ABI_GMC.items()) + list(ABI_PIPE_GMC.items()) + list(ABI_GMC_BLOBS.items()) + \
-            list(ABI_PIPE_GMC_BLOBS.items()) + list(ABI_PERSIST.items()) + list(ABI_PIPE_BOXES.items()) + \
-            list(ABI_DIR.items()) + list(ABI_PIPE_DIR.items()) + list(ABI_LANES.items()) + \
-            list(ABI_PIPE_LANES.items()):
-        fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
+    for table in ABI_TABLES:
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
+            fn.restype = res
+            fn.argtypes = args
     if path is None:
         _lib = lib
     return lib

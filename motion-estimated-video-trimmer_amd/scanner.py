@@ -175,23 +175,42 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _dptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _stream_handle(dev, stream):
+    """The hipStream_t of a device call: the caller's handle, or torch's current stream on `dev`."""
+    if stream is not None:
+        return stream
+    import torch
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _fields(p) -> dict:
+    """A ctypes struct as a dict of its fields (padding, named _..., left out)."""
+    return {n: getattr(p, n) for n, *_ in p._fields_ if not n.startswith("_")}
+
+
+def _preview(symbol, plan_c, params, *ints) -> dict:
+    """One mtgpu_*_preview call: (params, ints..., plan out) -> the plan as a dict; params None: the call takes none."""
+    p = plan_c()
+    head = () if params is None else (C.byref(params.to_c()),)
+    check(getattr(load_library(), symbol)(*head, *(int(i) for i in ints), C.byref(p)))
+    return _fields(p)
+
+
 def plan_preview(params: "ScanParams", lds_bytes: int = 163840, cu_count: int = 256) -> dict:
     """The launch plan the library would pick for `params` on a device with that much LDS per
     workgroup and that many CUs (defaults: MI355X).  Host arithmetic only: works without a GPU."""
-    p = PlanC()
-    c = params.to_c()
-    check(load_library().mtgpu_plan_preview(C.byref(c), int(lds_bytes), int(cu_count), C.byref(p)))
-    return {n: getattr(p, n) for n, _ in PlanC._fields_ if not n.startswith("_")}
+    return _preview("mtgpu_plan_preview", PlanC, params, lds_bytes, cu_count)
 
 
 def sweep_preview(params: "ScanParams", n_thresholds: int, n_vectors: int, lds_bytes: int = 163840) -> dict:
     """How a sweep of n_thresholds x n_vectors settings would run on the grid of `params` with that much LDS per
     workgroup (mtgpu_scan_sweep_preview): tiles per launch, launches (= reads of the records), LDS bytes.  Host
     arithmetic only: works without a GPU.  MtgpuError(MT_ERR_UNSUPPORTED) for a grid the sweep has no form for."""
-    p = SweepPlanC()
-    c = params.to_c()
-    check(load_library().mtgpu_scan_sweep_preview(C.byref(c), int(lds_bytes), int(n_thresholds), int(n_vectors), C.byref(p)))
-    return {n: getattr(p, n) for n, _ in SweepPlanC._fields_}
+    return _preview("mtgpu_scan_sweep_preview", SweepPlanC, params, lds_bytes, n_thresholds, n_vectors)
 
 
 def activity_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
@@ -199,40 +218,28 @@ def activity_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     (mtgpu_activity_preview): LDS bytes, width of the LDS accumulators (32, 16, or 0 = every frame flushes), the most
     frames a workgroup accumulates before it flushes, lanes.  Host arithmetic only: works without a GPU.
     MtgpuError(MT_ERR_UNSUPPORTED) for a grid the map has no form for."""
-    p = ActivityPlanC()
-    c = params.to_c()
-    check(load_library().mtgpu_activity_preview(C.byref(c), int(lds_bytes), C.byref(p)))
-    return {n: getattr(p, n) for n, _ in ActivityPlanC._fields_}
+    return _preview("mtgpu_activity_preview", ActivityPlanC, params, lds_bytes)
 
 
 def zones_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     """How the masked scan runs on the grid of `params` with that much LDS per workgroup (mtgpu_zones_preview): LDS
     bytes, lanes, and the sizes of a keep mask: uint64 words per grid row and per stream.  Host arithmetic only: works
     without a GPU.  MtgpuError(MT_ERR_UNSUPPORTED) for a grid the masked scan has no form for."""
-    p = ZonesPlanC()
-    c = params.to_c()
-    check(load_library().mtgpu_zones_preview(C.byref(c), int(lds_bytes), C.byref(p)))
-    return {n: getattr(p, n) for n, _ in ZonesPlanC._fields_}
+    return _preview("mtgpu_zones_preview", ZonesPlanC, params, lds_bytes)
 
 
 def blobs_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     """How the blob scan runs on the grid of `params` with that much LDS per workgroup (mtgpu_blobs_preview): LDS
     bytes, lanes, and the sizes of a keep mask: uint64 words per grid row and per stream.  Host arithmetic only: works
     without a GPU.  MtgpuError(MT_ERR_UNSUPPORTED) for a grid the blob scan has no form for."""
-    p = BlobsPlanC()
-    c = params.to_c()
-    check(load_library().mtgpu_blobs_preview(C.byref(c), int(lds_bytes), C.byref(p)))
-    return {n: getattr(p, n) for n, _ in BlobsPlanC._fields_}
+    return _preview("mtgpu_blobs_preview", BlobsPlanC, params, lds_bytes)
 
 
 def gmc_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     """How the compensated scan runs on the grid of `params` with that much LDS per workgroup (mtgpu_gmc_preview): LDS
     bytes, lanes, histogram bins per axis, bytes of one GMC_INFO_DTYPE element.  Host arithmetic only: works without a
     GPU.  MtgpuError(MT_ERR_UNSUPPORTED) for a grid the compensated scan has no form for."""
-    p = GmcPlanC()
-    c = params.to_c()
-    check(load_library().mtgpu_gmc_preview(C.byref(c), int(lds_bytes), C.byref(p)))
-    return {n: getattr(p, n) for n, _ in GmcPlanC._fields_}
+    return _preview("mtgpu_gmc_preview", GmcPlanC, params, lds_bytes)
 
 
 def gmc_blobs_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
@@ -240,20 +247,14 @@ def gmc_blobs_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     (mtgpu_gmc_blobs_preview): LDS bytes, lanes, the sizes of a keep mask (uint64 words per grid row and per stream),
     histogram bins per axis, bytes of one GMC_INFO_DTYPE element.  Host arithmetic only: works without a GPU.
     MtgpuError(MT_ERR_UNSUPPORTED) for a grid the scan has no form for."""
-    p = GmcBlobsPlanC()
-    c = params.to_c()
-    check(load_library().mtgpu_gmc_blobs_preview(C.byref(c), int(lds_bytes), C.byref(p)))
-    return {n: getattr(p, n) for n, _ in GmcBlobsPlanC._fields_}
+    return _preview("mtgpu_gmc_blobs_preview", GmcBlobsPlanC, params, lds_bytes)
 
 
 def dir_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     """How the direction scan runs on the grid of `params` with that much LDS per workgroup (mtgpu_dir_preview): LDS
     bytes, lanes, sectors of a rose (8), bytes of one rose (32).  Host arithmetic only: works without a GPU.
     MtgpuError(MT_ERR_UNSUPPORTED) for a grid the direction scan has no form for."""
-    p = DirPlanC()
-    c = params.to_c()
-    check(load_library().mtgpu_dir_preview(C.byref(c), int(lds_bytes), C.byref(p)))
-    return {n: getattr(p, n) for n, _ in DirPlanC._fields_}
+    return _preview("mtgpu_dir_preview", DirPlanC, params, lds_bytes)
 
 
 def lanes_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
@@ -261,18 +262,13 @@ def lanes_preview(params: "ScanParams", lds_bytes: int = 163840) -> dict:
     lanes, staged (1: the plane's analysed rows are held in LDS, 0: read from memory), bytes of one plane (gw * gh).
     Host arithmetic only: works without a GPU.  MtgpuError(MT_ERR_UNSUPPORTED) for a grid the plane scan has no form
     for."""
-    p = LanesPlanC()
-    c = params.to_c()
-    check(load_library().mtgpu_lanes_preview(C.byref(c), int(lds_bytes), C.byref(p)))
-    return {n: getattr(p, n) for n, _ in LanesPlanC._fields_}
+    return _preview("mtgpu_lanes_preview", LanesPlanC, params, lds_bytes)
 
 
 def persist_preview() -> dict:
     """How the persistence pass runs (mtgpu_persist_preview): lanes per workgroup and the frames a workgroup takes per
     step.  Host only: works without a GPU."""
-    p = PersistPlanC()
-    check(load_library().mtgpu_persist_preview(C.byref(p)))
-    return {n: getattr(p, n) for n, _ in PersistPlanC._fields_}
+    return _preview("mtgpu_persist_preview", PersistPlanC, None)
 
 
 ACTIVITY_OUTPUTS = ("active", "centre", "frames")
@@ -282,12 +278,88 @@ GMC_BLOB_OUTPUTS = BLOB_OUTPUTS + ("info",)
 DIR_OUTPUTS = ("flags", "centres", "rose")
 
 
-def _activity_want(want):
+# Every named output of the scans: name -> (torch element type, trailing shape on the device, numpy dtype on the host,
+# the byte a host array is filled with).  A structured numpy dtype takes the trailing shape into its element; a trailing
+# shape of None is the caller's (the grid of an activity map).  The *_OUTPUTS tuples above are the public lists of names
+# and the order of the library's arguments.
+_COUNT = ("int32", (), np.uint32, 0)
+_OUTPUTS = {
+    "flags": ("uint8", (), np.uint8, 0),
+    "centres": _COUNT, "blobs": _COUNT, "largest": _COUNT, "run": _COUNT, "pos": _COUNT, "frames": _COUNT,
+    "rose": ("int32", (8,), np.uint32, 0),
+    "box": ("int16", (4,), BLOB_BOX_DTYPE, 0xFF),
+    "info": ("int32", (5,), GMC_INFO_DTYPE, 0),
+    "active": ("int32", None, np.uint32, 0), "centre": ("int32", None, np.uint32, 0),
+}
+
+
+def _wanted(want, names) -> tuple:
     want = tuple(want)
     for w in want:
-        if w not in ACTIVITY_OUTPUTS:
-            raise ValueError(f"want: {w!r} is not one of {ACTIVITY_OUTPUTS}")
+        if w not in names:
+            raise ValueError(f"want: {w!r} is not one of {names}")
     return want
+
+
+def _host_outputs(names, n, want=None, grid=()) -> dict:
+    """name -> the numpy array of `n` elements the library fills (None for a name left out of `want`)."""
+    out = {}
+    for name in names:
+        _, trail, dtype, fill = _OUTPUTS[name]
+        out[name] = None
+        if want is None or name in want:
+            out[name] = np.empty((n,) + (() if np.dtype(dtype).names else grid if trail is None else trail), dtype=dtype)
+            out[name].view(np.uint8)[...] = fill
+    return out
+
+
+def _device_outputs(names, want, out, n, dev, grid=()) -> dict:
+    """name -> the torch tensor of `n` elements the library fills: the caller's out[name], checked, or a new one; None
+    for a name left out of `want`."""
+    import torch
+    want = _wanted(want, names)
+    res = {}
+    for name in names:
+        if name not in want:
+            res[name] = None
+            continue
+        elem, trail = _OUTPUTS[name][:2]
+        dtype, shape = getattr(torch, elem), (n,) + (grid if trail is None else trail)
+        t = (out or {}).get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, name
+        res[name] = t
+    return res
+
+
+def _optional(t, n, spec, dev, none_allocates=True, checked=True):
+    """One optional output of a tuple-returning device scan: None = allocated, False = not computed (None comes back),
+    or a tensor of at least `n` elements to fill.  spec: a name of _OUTPUTS, or (element type, trailing shape).
+    none_allocates=False: None is "not computed" too and True allocates.  checked=False: a tensor passes unlooked at."""
+    import torch
+    elem, trail = (_OUTPUTS[spec] if isinstance(spec, str) else spec)[:2]
+    dtype, shape = getattr(torch, elem), (n,) + trail
+    if t is False or (t is None and not none_allocates):
+        return None
+    if t is None or (t is True and not none_allocates):
+        return torch.empty(shape, dtype=dtype, device=dev)
+    assert not checked or (t.dtype == dtype and t.is_contiguous() and t.numel() >= int(np.prod(shape)))
+    return t
+
+
+def _host_batch(batch, stream_off=None, null_if_empty=False):
+    """The arrays of a host batch as the library takes them: ((mv or NULL, frame_off, has_sd or NULL, n frames),
+    (stream_off or NULL, n streams), the contiguous arrays themselves).  The pointers keep their arrays alive."""
+    mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
+    off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+    sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
+    soff, ns = None, 0
+    if stream_off is not None:
+        soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
+        ns = max(len(soff) - 1, 0)
+    soff_ptr = None if null_if_empty and not len(soff) else _ptr(soff)
+    return (_ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), max(len(off) - 1, 0)), (soff_ptr, ns), (mv, off, sd, soff)
 
 
 def _sweep_settings(thresholds, vectors):
@@ -353,7 +425,7 @@ class MotionScanner:
     def plan(self) -> dict:
         p = PlanC()
         check(self._lib.mtgpu_get_plan(self._ctx, C.byref(p)))
-        return {n: getattr(p, n) for n, _ in PlanC._fields_ if not n.startswith("_")}
+        return _fields(p)
 
     def set_slices(self, slices: int):
         """Workgroups per frame: 0 = automatic (default), or 1 / 2 / 4 / 8.  Never changes results."""
@@ -376,30 +448,48 @@ class MotionScanner:
         from ._abi import CtxStatsC
         st = CtxStatsC()
         check(self._lib.mtgpu_get_stats(self._ctx, C.byref(st)))
-        return {n: getattr(st, n) for n, _ in CtxStatsC._fields_}
+        return _fields(st)
 
     def trim(self):
         """Hand the scratch pool's unused blocks back to the device (mtgpu_trim)."""
         check(self._lib.mtgpu_trim(self._ctx))
 
+    def _device_batch(self, d_rec, d_off, d_sd, compact, stream):
+        """The head of every device scan's argument list — (context, records or NULL, bytes per record, n records,
+        frame offsets, has_sd or NULL, n frames) — and the stream handle, from a device-resident batch."""
+        import torch
+        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_off.dtype == torch.int64
+        rec_bytes = 8 if compact else 40
+        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
+        return (self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(), _dptr(d_sd),
+                max(d_off.numel() - 1, 0)), _stream_handle(d_off.device, stream)
+
+    def _hold(self, ws, dev, stream):
+        """Keeps a workspace of this call alive: it must outlive the kernel that was just queued, so it is held until an
+        event recorded behind the launch on ITS stream has passed (torch's caching allocator knows nothing of a raw
+        hipStream_t handed in by the caller, and several launches may be queued back to back)."""
+        import torch
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev))
+        self._held = [(e, w) for e, w in getattr(self, "_held", []) if not e.query()]
+        self._held.append((ev, ws))
+
     # ---------------------------------------------------------------- scan
     def check_frames(self, batch: FrameBatch) -> np.ndarray:
         """check_frame() for every frame of a host batch -> uint8 flags [F]."""
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        n = len(off) - 1
-        flags = np.zeros(max(n, 0), dtype=np.uint8)
+        (mv, off, sd, n), _, _ = _host_batch(batch)
+        flags = _host_outputs(("flags",), n)["flags"]
         if n <= 0:
             return flags
-        check(self._lib.mtgpu_scan_frames(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off),
-                                          _ptr(sd), n, _ptr(flags)))
+        check(self._lib.mtgpu_scan_frames(self._ctx, mv, off, sd, n, _ptr(flags)))
         return flags
 
     def check_frames_device(self, mv, frame_off, has_sd=None, flags=None, stream=None):
         """Device-resident batch (torch CUDA tensors).  mv: uint8 [n_records*40] (or any
         dtype viewing the packed records), frame_off: int64 [F+1].  Asynchronous on
         `stream` (default: torch's current stream).  Returns the uint8 flags tensor."""
+        # (this form and the compact one below run inside bench.py's timed loops: they keep their direct bodies, the
+        # shared _device_batch costs them about a microsecond per call — docs/rounds/r29_python_fold.md)
         import torch
         n_frames = frame_off.numel() - 1
         if flags is None:
@@ -438,17 +528,11 @@ class MotionScanner:
         """check_frame() for every frame of a host batch, with the frame's centre count: the `clusters` counter of
         src/motion_scanner.cpp:272-294 without its early return (0 for a frame without side data).
         Returns (flags uint8 [F], centres uint32 [F]); flags == centres >= max(1, clusters_needed)."""
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        n = len(off) - 1
-        flags = np.zeros(max(n, 0), dtype=np.uint8)
-        centres = np.zeros(max(n, 0), dtype=np.uint32)
-        if n <= 0:
-            return flags, centres
-        check(self._lib.mtgpu_scan_frames_centres(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off),
-                                                  _ptr(sd), n, _ptr(flags), _ptr(centres)))
-        return flags, centres
+        head, _, _ = _host_batch(batch)
+        out = _host_outputs(("flags", "centres"), head[3])
+        if head[3] > 0:
+            check(self._lib.mtgpu_scan_frames_centres(self._ctx, *head, _ptr(out["flags"]), _ptr(out["centres"])))
+        return out["flags"], out["centres"]
 
     def count_centres_device(self, records, frame_off, has_sd=None, compact=False, flags=None, centres=None,
                              stream=None):
@@ -458,25 +542,15 @@ class MotionScanner:
         `stream` (default: torch's current stream)."""
         import torch
         n_frames = frame_off.numel() - 1
-        dev = frame_off.device
-        if flags is None:
-            flags = torch.empty(max(n_frames, 0), dtype=torch.uint8, device=dev)
-        elif flags is False:
-            flags = None
+        dev, n = frame_off.device, max(n_frames, 0)
+        flags = _optional(flags, n, "flags", dev, checked=n_frames > 0)
         if centres is None:
-            centres = torch.empty(max(n_frames, 0), dtype=torch.int32, device=dev)
+            centres = torch.empty(n, dtype=torch.int32, device=dev)
         if n_frames <= 0:
             return flags, centres
-        assert records.is_contiguous() and frame_off.is_contiguous() and centres.is_contiguous()
-        assert frame_off.dtype == torch.int64 and centres.dtype == torch.int32 and centres.numel() >= n_frames
-        assert flags is None or (flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() >= n_frames)
-        rec_bytes = 8 if compact else 40
-        n_records = (records.numel() * records.element_size()) // rec_bytes
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        check(self._lib.mtgpu_scan_centres_device(
-            self._ctx, records.data_ptr() if n_records else None, rec_bytes, n_records, frame_off.data_ptr(),
-            None if has_sd is None else has_sd.data_ptr(), n_frames, None if flags is None else flags.data_ptr(),
-            centres.data_ptr(), st))
+        assert centres.is_contiguous() and centres.dtype == torch.int32 and centres.numel() >= n_frames
+        head, st = self._device_batch(records, frame_off, has_sd, compact, stream)
+        check(self._lib.mtgpu_scan_centres_device(*head, _dptr(flags), centres.data_ptr(), st))
         return flags, centres
 
     def flags_from_centres(self, centres, clusters_needed: int, flags=None, stream=None):
@@ -487,7 +561,7 @@ class MotionScanner:
         n = centres.numel()
         if flags is None:
             flags = torch.empty(n, dtype=torch.uint8, device=centres.device)
-        st = torch.cuda.current_stream(centres.device).cuda_stream if stream is None else stream
+        st = _stream_handle(centres.device, stream)
         if n:
             check(self._lib.mtgpu_flags_from_centres_device(self._ctx, centres.data_ptr(), n, int(clusters_needed),
                                                             flags.data_ptr(), st))
@@ -509,17 +583,12 @@ class MotionScanner:
         ws = torch.empty(2 * max(n_frames, 1) * max(n_levels, 1), dtype=torch.float64, device=dev)
         seg = torch.zeros((n_levels, max(n_streams, 0), seg_cap, 2), dtype=torch.float64, device=dev)
         res = torch.zeros((n_levels, max(n_streams, 0), MERGE_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
         c_levels = (C.c_int32 * max(n_levels, 1))(*levels)
         check(self._lib.mtgpu_sweep_streams_device(
             self._ctx, centres.data_ptr(), pts.data_ptr(), stream_off.data_ptr(), max(n_streams, 0), n_frames,
             merge_params.data_ptr(), c_levels, n_levels, 1 if job_semantics else 0, ws.data_ptr(), seg.data_ptr(),
-            seg_cap, res.data_ptr(), st))
-        # (the workspace outlives the queued kernel: see merge_streams_device)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev))
-        self._held = [(e, w) for e, w in getattr(self, "_held", []) if not e.query()]
-        self._held.append((ev, ws))
+            seg_cap, res.data_ptr(), _stream_handle(dev, stream)))
+        self._hold(ws, dev, stream)
         return seg, res
 
     # ------------------------------------------------------- setting sweep
@@ -529,13 +598,9 @@ class MotionScanner:
         out[t, v] is what count_centres returns through a scanner created with thresholds[t] and vectors[v];
         the scanner's own threshold, vectors and clusters play no part."""
         c_th, n_th, c_ve, n_ve = _sweep_settings(thresholds, vectors)
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        n = max(len(off) - 1, 0)
-        out = np.zeros((n_th, n_ve, n), dtype=np.uint32)
-        check(self._lib.mtgpu_scan_frames_sweep(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, c_th, n_th,
-                                                c_ve, n_ve, _ptr(out) if out.size else None))
+        head, _, _ = _host_batch(batch)
+        out = np.zeros((n_th, n_ve, head[3]), dtype=np.uint32)
+        check(self._lib.mtgpu_scan_frames_sweep(self._ctx, *head, c_th, n_th, c_ve, n_ve, _ptr(out) if out.size else None))
         return out
 
     def sweep_centres_device(self, records, frame_off, has_sd, thresholds, vectors, compact=False, out=None, stream=None):
@@ -547,17 +612,11 @@ class MotionScanner:
         import torch
         c_th, n_th, c_ve, n_ve = _sweep_settings(thresholds, vectors)
         n_frames = max(frame_off.numel() - 1, 0)
-        dev = frame_off.device
         if out is None:
-            out = torch.empty((n_th, n_ve, n_frames), dtype=torch.int32, device=dev)
-        assert records.is_contiguous() and frame_off.is_contiguous() and out.is_contiguous()
-        assert frame_off.dtype == torch.int64 and out.dtype == torch.int32 and out.numel() >= n_th * n_ve * n_frames
-        rec_bytes = 8 if compact else 40
-        n_records = (records.numel() * records.element_size()) // rec_bytes
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        check(self._lib.mtgpu_scan_sweep_device(
-            self._ctx, records.data_ptr() if n_records else None, rec_bytes, n_records, frame_off.data_ptr(),
-            None if has_sd is None else has_sd.data_ptr(), n_frames, c_th, n_th, c_ve, n_ve, out.data_ptr(), st))
+            out = torch.empty((n_th, n_ve, n_frames), dtype=torch.int32, device=frame_off.device)
+        assert out.is_contiguous() and out.dtype == torch.int32 and out.numel() >= n_th * n_ve * n_frames
+        head, st = self._device_batch(records, frame_off, has_sd, compact, stream)
+        check(self._lib.mtgpu_scan_sweep_device(*head, c_th, n_th, c_ve, n_ve, out.data_ptr(), st))
         return out
 
     # ------------------------------------------------------- activity maps
@@ -567,20 +626,11 @@ class MotionScanner:
         active / one of the centres src/motion_scanner.cpp:277-292 counts; frames[s]: the contributing frames.  A
         frame contributes iff it has side data and its centre count is >= min_centres.  stream_off: S + 1 frame
         offsets.  An output left out of `want` is not computed and comes back as None."""
-        want = _activity_want(want)
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
-        n, ns = max(len(off) - 1, 0), max(len(soff) - 1, 0)
-        gh, gw = self.params.grid_h, self.params.grid_w
-        active = np.zeros((ns, gh, gw), dtype=np.uint32) if "active" in want else None
-        centre = np.zeros((ns, gh, gw), dtype=np.uint32) if "centre" in want else None
-        frames = np.zeros(ns, dtype=np.uint32) if "frames" in want else None
-        check(self._lib.mtgpu_activity_map(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n,
-                                           _ptr(soff) if len(soff) else None, ns, int(min_centres), _ptr(active),
-                                           _ptr(centre), _ptr(frames)))
-        return active, centre, frames
+        want = _wanted(want, ACTIVITY_OUTPUTS)
+        head, (soff, ns), _ = _host_batch(batch, stream_off, null_if_empty=True)
+        out = _host_outputs(ACTIVITY_OUTPUTS, ns, want, (self.params.grid_h, self.params.grid_w))
+        check(self._lib.mtgpu_activity_map(self._ctx, *head, soff, ns, int(min_centres), *(_ptr(out[k]) for k in ACTIVITY_OUTPUTS)))
+        return tuple(out[k] for k in ACTIVITY_OUTPUTS)
 
     def activity_map_device(self, d_rec, d_off, d_sd, d_stream_off, min_centres: int = 0, run_frames: int = 0,
                             want=ACTIVITY_OUTPUTS, compact=False, out=None, stream=None):
@@ -591,33 +641,13 @@ class MotionScanner:
         the maps do not depend on it.  out: a dict of preallocated tensors by name.  Asynchronous on `stream`
         (default: torch's current stream)."""
         import torch
-        want = _activity_want(want)
-        dev = d_off.device
-        n_frames = max(d_off.numel() - 1, 0)
         ns = max(d_stream_off.numel() - 1, 0)
-        gh, gw = self.params.grid_h, self.params.grid_w
-        res = {}
-        for name in ACTIVITY_OUTPUTS:
-            if name not in want:
-                res[name] = None
-                continue
-            shape = (ns,) if name == "frames" else (ns, gh, gw)
-            t = (out or {}).get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=torch.int32, device=dev)
-            assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape, name
-            res[name] = t
-        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_stream_off.is_contiguous()
-        assert d_off.dtype == torch.int64 and d_stream_off.dtype == torch.int64
-        rec_bytes = 8 if compact else 40
-        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-        check(self._lib.mtgpu_activity_map_device(
-            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
-            None if d_sd is None else d_sd.data_ptr(), n_frames, d_stream_off.data_ptr(), ns, int(min_centres),
-            int(run_frames), ptr(res["active"]), ptr(res["centre"]), ptr(res["frames"]), st))
-        return res["active"], res["centre"], res["frames"]
+        res = _device_outputs(ACTIVITY_OUTPUTS, want, out, ns, d_off.device, (self.params.grid_h, self.params.grid_w))
+        assert d_stream_off.is_contiguous() and d_stream_off.dtype == torch.int64
+        head, st = self._device_batch(d_rec, d_off, d_sd, compact, stream)
+        check(self._lib.mtgpu_activity_map_device(*head, d_stream_off.data_ptr(), ns, int(min_centres), int(run_frames),
+                                                  *(_dptr(res[k]) for k in ACTIVITY_OUTPUTS), st))
+        return tuple(res[k] for k in ACTIVITY_OUTPUTS)
 
     # -------------------------------------------------------- ignore zones
     def _keep_words(self, keep, n_streams):
@@ -630,25 +660,30 @@ class MotionScanner:
             raise ValueError(f"keep has shape {keep.shape}, not {(n_streams, gh, W)} (or {(gh, W)} for every stream)")
         return keep
 
+    def _device_keep(self, d_stream_off, d_keep) -> int:
+        """The streams of a device keep mask, checked against its stream offsets; 0 without a mask."""
+        if d_keep is None:
+            return 0
+        import torch
+        ns = max(d_stream_off.numel() - 1, 0)
+        assert d_stream_off.is_contiguous() and d_keep.is_contiguous()
+        assert d_stream_off.dtype == torch.int64 and d_keep.dtype == torch.int64
+        assert d_keep.numel() == ns * self.params.grid_h * ((self.params.grid_w + 63) // 64)
+        return ns
+
     def scan_zones(self, batch: FrameBatch, stream_off, keep, want_all: bool = False):
         """The centre scan of a host batch under per-stream keep masks (mtgpu_scan_frames_zones): on the analysed rows
         a cell is active iff votes >= vectors_needed (src/motion_scanner.cpp:282) AND its keep bit is set.  stream_off:
         S + 1 frame offsets; keep: uint64 [S, gh, W] from zones.pack_keep (or [gh, W]: the same mask for every stream).
         Returns (flags uint8 [F], centres uint32 [F], centres_all): centres_all is the count without the mask from the
         same votes (uint32 [F]) with want_all=True, else None."""
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
-        n, ns = max(len(off) - 1, 0), max(len(soff) - 1, 0)
+        head, (soff, ns), _ = _host_batch(batch, stream_off, null_if_empty=True)
         keep = self._keep_words(keep, ns)
-        flags = np.zeros(n, dtype=np.uint8)
-        centres = np.zeros(n, dtype=np.uint32)
-        call = np.zeros(n, dtype=np.uint32) if want_all else None
-        check(self._lib.mtgpu_scan_frames_zones(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n,
-                                                _ptr(soff) if len(soff) else None, ns, _ptr(keep) if keep.size else None,
-                                                _ptr(flags), _ptr(centres), _ptr(call)))
-        return flags, centres, call
+        out = _host_outputs(("flags", "centres"), head[3])
+        call = _host_outputs(("centres",), head[3])["centres"] if want_all else None
+        check(self._lib.mtgpu_scan_frames_zones(self._ctx, *head, soff, ns, _ptr(keep) if keep.size else None,
+                                                _ptr(out["flags"]), _ptr(out["centres"]), _ptr(call)))
+        return out["flags"], out["centres"], call
 
     def scan_zones_device(self, d_rec, d_off, d_sd, d_stream_off, d_keep, compact=False, flags=None, centres=None,
                           centres_all=None, stream=None):
@@ -662,32 +697,15 @@ class MotionScanner:
         dev = d_off.device
         n_frames = max(d_off.numel() - 1, 0)
         ns = max(d_stream_off.numel() - 1, 0)
-        if flags is None:
-            flags = torch.empty(n_frames, dtype=torch.uint8, device=dev)
-        elif flags is False:
-            flags = None
-        if centres is None:
-            centres = torch.empty(n_frames, dtype=torch.int32, device=dev)
-        elif centres is False:
-            centres = None
-        if centres_all is True:
-            centres_all = torch.empty(n_frames, dtype=torch.int32, device=dev)
-        elif centres_all is False:
-            centres_all = None
-        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_stream_off.is_contiguous() and d_keep.is_contiguous()
-        assert d_off.dtype == torch.int64 and d_stream_off.dtype == torch.int64 and d_keep.dtype == torch.int64
+        flags = _optional(flags, n_frames, "flags", dev)
+        centres = _optional(centres, n_frames, "centres", dev)
+        centres_all = _optional(centres_all, n_frames, "centres", dev, none_allocates=False)
+        assert d_stream_off.is_contiguous() and d_keep.is_contiguous()
+        assert d_stream_off.dtype == torch.int64 and d_keep.dtype == torch.int64
         assert d_keep.numel() == ns * self.params.grid_h * ((self.params.grid_w + 63) // 64)
-        assert flags is None or (flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() >= n_frames)
-        for t in (centres, centres_all):
-            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n_frames)
-        rec_bytes = 8 if compact else 40
-        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-        check(self._lib.mtgpu_scan_zones_device(
-            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
-            None if d_sd is None else d_sd.data_ptr(), n_frames, d_stream_off.data_ptr(), ns, d_keep.data_ptr(),
-            ptr(flags), ptr(centres), ptr(centres_all), st))
+        head, st = self._device_batch(d_rec, d_off, d_sd, compact, stream)
+        check(self._lib.mtgpu_scan_zones_device(*head, d_stream_off.data_ptr(), ns, d_keep.data_ptr(), _dptr(flags),
+                                                _dptr(centres), _dptr(centres_all), st))
         return flags, centres, centres_all
 
     # -------------------------------------------------------- the direction filter
@@ -699,21 +717,15 @@ class MotionScanner:
         frames: flags uint8, centres uint32, rose uint32 [F, 8]: the counting records per sector, whatever is allowed."""
         if (stream_off is None) != (allows is None):
             raise ValueError("stream_off and allows go together: give both or neither")
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        n = max(len(off) - 1, 0)
-        soff, ns = None, 0
+        head, (soff, ns), _ = _host_batch(batch, stream_off)
         if allows is not None:
-            soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
-            ns = max(len(soff) - 1, 0)
             given = np.asarray(allows)
             if given.shape != (ns,) or (ns and (int(given.min()) < 0 or int(given.max()) > 255)):
                 raise ValueError(f"allows: {ns} bytes in 0 .. 255 wanted, one per stream")
             allows = np.ascontiguousarray(np.concatenate([given.astype(np.uint8), np.zeros(1, dtype=np.uint8)]))   # never empty
-        out = {"flags": np.zeros(n, dtype=np.uint8), "centres": np.zeros(n, dtype=np.uint32), "rose": np.zeros((n, 8), dtype=np.uint32)}
-        check(self._lib.mtgpu_scan_frames_dir(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, _ptr(soff), ns,
-                                              _ptr(allows), int(allow), *(_ptr(out[k]) for k in DIR_OUTPUTS)))
+        out = _host_outputs(DIR_OUTPUTS, head[3])
+        check(self._lib.mtgpu_scan_frames_dir(self._ctx, *head, soff, ns, _ptr(allows), int(allow),
+                                              *(_ptr(out[k]) for k in DIR_OUTPUTS)))
         return out
 
     def scan_dir_device(self, d_rec, d_off, d_sd, allow: int = DIR_ALL, d_stream_off=None, d_allow=None, compact=False,
@@ -724,42 +736,21 @@ class MotionScanner:
         None; allow: the byte for every frame, or d_stream_off int64 [S + 1] and d_allow uint8 [S], both or neither.
         out: a dict of preallocated tensors by name.  Asynchronous on `stream` (default: torch's current stream)."""
         import torch
-        want = tuple(want)
-        for w in want:
-            if w not in DIR_OUTPUTS:
-                raise ValueError(f"want: {w!r} is not one of {DIR_OUTPUTS}")
+        want = _wanted(want, DIR_OUTPUTS)
         if (d_stream_off is None) != (d_allow is None):
             raise ValueError("d_stream_off and d_allow go together: give both or neither")
-        dev = d_off.device
         n_frames = max(d_off.numel() - 1, 0)
-        res = {}
-        for name in DIR_OUTPUTS:
-            if name not in want:
-                res[name] = None
-                continue
-            dtype = torch.uint8 if name == "flags" else torch.int32
-            shape = (n_frames, 8) if name == "rose" else (n_frames,)
-            t = (out or {}).get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=dev)
-            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, name
-            res[name] = t
+        res = _device_outputs(DIR_OUTPUTS, want, out, n_frames, d_off.device)
         if n_frames == 0:              # nothing to write (an empty tensor has no address to hand over)
             return res
-        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_off.dtype == torch.int64
         ns = 0
         if d_allow is not None:
             ns = max(d_stream_off.numel() - 1, 0)
             assert d_stream_off.is_contiguous() and d_stream_off.dtype == torch.int64
             assert d_allow.is_contiguous() and d_allow.dtype == torch.uint8 and d_allow.numel() >= max(ns, 1)
-        rec_bytes = 8 if compact else 40
-        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-        check(self._lib.mtgpu_scan_dir_device(
-            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
-            None if d_sd is None else d_sd.data_ptr(), n_frames, ptr(d_stream_off), ns, ptr(d_allow), int(allow),
-            *(ptr(res[k]) for k in DIR_OUTPUTS), st))
+        head, st = self._device_batch(d_rec, d_off, d_sd, compact, stream)
+        check(self._lib.mtgpu_scan_dir_device(*head, _dptr(d_stream_off), ns, _dptr(d_allow), int(allow),
+                                              *(_dptr(res[k]) for k in DIR_OUTPUTS), st))
         return res
 
     # -------------------------------------------------------- direction planes and flow maps
@@ -778,20 +769,12 @@ class MotionScanner:
         frame; or, with stream_off (S + 1 frame offsets), uint8 [S, gh, gw], one plane per stream (lanes.plane_from_rects,
         lanes.plane_from_flow).  Returns a dict of numpy arrays over the frames: flags uint8, centres uint32, rose uint32
         [F, 8]: the counting records per sector, whatever the planes say."""
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        n = max(len(off) - 1, 0)
-        soff, ns = None, 0
-        if stream_off is not None:
-            soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
-            ns = max(len(soff) - 1, 0)
-            if ns == 0:
-                raise ValueError("stream_off: at least one stream wanted (or None: one plane for every frame)")
-        planes = self._planes(planes, None if soff is None else ns)
-        out = {"flags": np.zeros(n, dtype=np.uint8), "centres": np.zeros(n, dtype=np.uint32), "rose": np.zeros((n, 8), dtype=np.uint32)}
-        check(self._lib.mtgpu_scan_frames_lanes(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, _ptr(soff), ns,
-                                                _ptr(planes), *(_ptr(out[k]) for k in DIR_OUTPUTS)))
+        head, (soff, ns), _ = _host_batch(batch, stream_off)
+        if stream_off is not None and ns == 0:
+            raise ValueError("stream_off: at least one stream wanted (or None: one plane for every frame)")
+        planes = self._planes(planes, None if stream_off is None else ns)
+        out = _host_outputs(DIR_OUTPUTS, head[3])
+        check(self._lib.mtgpu_scan_frames_lanes(self._ctx, *head, soff, ns, _ptr(planes), *(_ptr(out[k]) for k in DIR_OUTPUTS)))
         return out
 
     def scan_lanes_device(self, d_rec, d_off, d_sd, d_planes, d_stream_off=None, compact=False, want=DIR_OUTPUTS, out=None,
@@ -803,56 +786,30 @@ class MotionScanner:
         byte address.  out: a dict of preallocated tensors by name.  Asynchronous on `stream` (default: torch's current
         stream)."""
         import torch
-        want = tuple(want)
-        for w in want:
-            if w not in DIR_OUTPUTS:
-                raise ValueError(f"want: {w!r} is not one of {DIR_OUTPUTS}")
-        dev = d_off.device
         n_frames = max(d_off.numel() - 1, 0)
-        res = {}
-        for name in DIR_OUTPUTS:
-            if name not in want:
-                res[name] = None
-                continue
-            dtype = torch.uint8 if name == "flags" else torch.int32
-            shape = (n_frames, 8) if name == "rose" else (n_frames,)
-            t = (out or {}).get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=dev)
-            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, name
-            res[name] = t
+        res = _device_outputs(DIR_OUTPUTS, want, out, n_frames, d_off.device)
         if n_frames == 0:              # nothing to write (an empty tensor has no address to hand over)
             return res
-        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_off.dtype == torch.int64
         ns = 0
         if d_stream_off is not None:
             ns = max(d_stream_off.numel() - 1, 0)
             assert d_stream_off.is_contiguous() and d_stream_off.dtype == torch.int64 and ns > 0
         assert d_planes.is_contiguous() and d_planes.dtype == torch.uint8
         assert d_planes.numel() == max(ns, 1) * self.params.grid_h * self.params.grid_w
-        rec_bytes = 8 if compact else 40
-        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-        check(self._lib.mtgpu_scan_lanes_device(
-            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
-            None if d_sd is None else d_sd.data_ptr(), n_frames, ptr(d_stream_off), ns, d_planes.data_ptr(),
-            *(ptr(res[k]) for k in DIR_OUTPUTS), st))
+        head, st = self._device_batch(d_rec, d_off, d_sd, compact, stream)
+        check(self._lib.mtgpu_scan_lanes_device(*head, _dptr(d_stream_off), ns, d_planes.data_ptr(),
+                                                *(_dptr(res[k]) for k in DIR_OUTPUTS), st))
         return res
 
     def flow_map(self, batch: FrameBatch, stream_off) -> np.ndarray:
         """The flow map of a host batch (mtgpu_flow_map): uint32 [S, 8, gh, gw] — per stream, sector (0 = E, clockwise on
         the screen) and grid cell, the counting records with that sector and destination cell over the stream's frames
         with side data.  stream_off: S + 1 frame offsets.  Maps of successive batches add."""
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
-        n, ns = max(len(off) - 1, 0), max(len(soff) - 1, 0)
+        head, (soff, ns), _ = _host_batch(batch, stream_off)
         flow = np.zeros((ns, 8, self.params.grid_h, self.params.grid_w), dtype=np.uint32)
         if ns == 0:
             return flow
-        check(self._lib.mtgpu_flow_map(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, _ptr(soff), ns, _ptr(flow)))
+        check(self._lib.mtgpu_flow_map(self._ctx, *head, soff, ns, _ptr(flow)))
         return flow
 
     def flow_map_device(self, d_rec, d_off, d_sd, d_stream_off, compact=False, out=None, stream=None):
@@ -861,23 +818,16 @@ class MotionScanner:
         preallocated tensor; it is cleared, then counted into.  Asynchronous on `stream` (default: torch's current
         stream)."""
         import torch
-        dev = d_off.device
-        n_frames = max(d_off.numel() - 1, 0)
         ns = max(d_stream_off.numel() - 1, 0)
         shape = (ns, 8, self.params.grid_h, self.params.grid_w)
         if out is None:
-            out = torch.empty(shape, dtype=torch.int32, device=dev)
+            out = torch.empty(shape, dtype=torch.int32, device=d_off.device)
         assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == shape
         if ns == 0:
             return out
-        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_stream_off.is_contiguous()
-        assert d_off.dtype == torch.int64 and d_stream_off.dtype == torch.int64
-        rec_bytes = 8 if compact else 40
-        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        check(self._lib.mtgpu_flow_map_device(
-            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
-            None if d_sd is None else d_sd.data_ptr(), n_frames, d_stream_off.data_ptr(), ns, out.data_ptr(), st))
+        assert d_stream_off.is_contiguous() and d_stream_off.dtype == torch.int64
+        head, st = self._device_batch(d_rec, d_off, d_sd, compact, stream)
+        check(self._lib.mtgpu_flow_map_device(*head, d_stream_off.data_ptr(), ns, out.data_ptr(), st))
         return out
 
     # -------------------------------------------------------- global-motion compensation
@@ -886,16 +836,10 @@ class MotionScanner:
         per-axis mode of the displacements of the records inside the analysed rows, within +-max_shift, is subtracted
         where at least min_share_q8 / 256 of those records agree on it; then src/motion_scanner.cpp:246-292 as
         count_centres runs it.  Returns (flags uint8 [F], centres uint32 [F], info GMC_INFO_DTYPE [F])."""
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        n = max(len(off) - 1, 0)
-        flags = np.zeros(n, dtype=np.uint8)
-        centres = np.zeros(n, dtype=np.uint32)
-        info = np.zeros(n, dtype=GMC_INFO_DTYPE)
-        check(self._lib.mtgpu_scan_frames_gmc(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, int(max_shift),
-                                              int(min_share_q8), _ptr(flags), _ptr(centres), _ptr(info)))
-        return flags, centres, info
+        head, _, _ = _host_batch(batch)
+        out = _host_outputs(("flags", "centres", "info"), head[3])
+        check(self._lib.mtgpu_scan_frames_gmc(self._ctx, *head, int(max_shift), int(min_share_q8), *(_ptr(a) for a in out.values())))
+        return tuple(out.values())
 
     def scan_gmc_device(self, d_rec, d_off, d_sd, max_shift: int = GMC_DEFAULT_MAX_SHIFT,
                         min_share_q8: int = GMC_DEFAULT_MIN_SHARE_Q8, compact=False, flags=None, centres=None, info=None,
@@ -905,33 +849,14 @@ class MotionScanner:
         d_rec: the packed 40-byte records, or the 8-byte compact ones with compact=True; d_off int64 [F + 1]; d_sd uint8
         [F] or None.  flags / centres / info: None = allocated, False = not computed, or a tensor to fill.
         Asynchronous on `stream` (default: torch's current stream)."""
-        import torch
         dev = d_off.device
         n_frames = max(d_off.numel() - 1, 0)
-        if flags is None:
-            flags = torch.empty(n_frames, dtype=torch.uint8, device=dev)
-        elif flags is False:
-            flags = None
-        if centres is None:
-            centres = torch.empty(n_frames, dtype=torch.int32, device=dev)
-        elif centres is False:
-            centres = None
-        if info is None:
-            info = torch.empty((n_frames, 5), dtype=torch.int32, device=dev)
-        elif info is False:
-            info = None
-        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_off.dtype == torch.int64
-        assert flags is None or (flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() >= n_frames)
-        assert centres is None or (centres.dtype == torch.int32 and centres.is_contiguous() and centres.numel() >= n_frames)
-        assert info is None or (info.dtype == torch.int32 and info.is_contiguous() and info.numel() >= 5 * n_frames)
-        rec_bytes = 8 if compact else 40
-        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-        check(self._lib.mtgpu_scan_gmc_device(
-            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
-            None if d_sd is None else d_sd.data_ptr(), n_frames, int(max_shift), int(min_share_q8), ptr(flags), ptr(centres),
-            ptr(info), st))
+        flags = _optional(flags, n_frames, "flags", dev)
+        centres = _optional(centres, n_frames, "centres", dev)
+        info = _optional(info, n_frames, "info", dev)
+        head, st = self._device_batch(d_rec, d_off, d_sd, compact, stream)
+        check(self._lib.mtgpu_scan_gmc_device(*head, int(max_shift), int(min_share_q8), _dptr(flags), _dptr(centres),
+                                              _dptr(info), st))
         return flags, centres, info
 
     # -------------------------------------------------------- motion blobs
@@ -943,19 +868,12 @@ class MotionScanner:
         all 0xFFFF without a blob).  stream_off / keep: per-stream keep masks as for scan_zones, both or neither."""
         if (stream_off is None) != (keep is None):
             raise ValueError("stream_off and keep go together: give both or neither")
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        n = max(len(off) - 1, 0)
-        soff, ns = None, 0
+        head, (soff, ns), _ = _host_batch(batch, stream_off)
         if keep is not None:
-            soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
-            ns = max(len(soff) - 1, 0)
             keep = self._keep_words(keep, ns)
-        out = {"flags": np.zeros(n, dtype=np.uint8), "centres": np.zeros(n, dtype=np.uint32), "blobs": np.zeros(n, dtype=np.uint32),
-               "largest": np.zeros(n, dtype=np.uint32), "box": np.full(n, 0xFFFF, dtype=np.uint16).repeat(4).view(BLOB_BOX_DTYPE)}
-        check(self._lib.mtgpu_scan_frames_blobs(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, _ptr(soff), ns,
-                                                _ptr(keep), int(min_blob_cells), *(_ptr(out[k]) for k in BLOB_OUTPUTS)))
+        out = _host_outputs(BLOB_OUTPUTS, head[3])
+        check(self._lib.mtgpu_scan_frames_blobs(self._ctx, *head, soff, ns, _ptr(keep), int(min_blob_cells),
+                                                *(_ptr(out[k]) for k in BLOB_OUTPUTS)))
         return out
 
     def scan_blobs_device(self, d_rec, d_off, d_sd, min_blob_cells: int = 1, d_stream_off=None, d_keep=None, compact=False,
@@ -967,44 +885,17 @@ class MotionScanner:
         d_keep int64 [S, gh, W] (the bits of zones.pack_keep's words), both or neither.  `largest` is ready for
         sweep_streams_device: level L there is flags at min_blob_cells = L.  out: a dict of preallocated tensors by
         name.  Asynchronous on `stream` (default: torch's current stream)."""
-        import torch
-        want = tuple(want)
-        for w in want:
-            if w not in BLOB_OUTPUTS:
-                raise ValueError(f"want: {w!r} is not one of {BLOB_OUTPUTS}")
+        want = _wanted(want, BLOB_OUTPUTS)
         if (d_stream_off is None) != (d_keep is None):
             raise ValueError("d_stream_off and d_keep go together: give both or neither")
-        dev = d_off.device
         n_frames = max(d_off.numel() - 1, 0)
-        res = {}
-        for name in BLOB_OUTPUTS:
-            if name not in want:
-                res[name] = None
-                continue
-            dtype = torch.uint8 if name == "flags" else torch.int16 if name == "box" else torch.int32
-            shape = (n_frames, 4) if name == "box" else (n_frames,)
-            t = (out or {}).get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=dev)
-            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, name
-            res[name] = t
+        res = _device_outputs(BLOB_OUTPUTS, want, out, n_frames, d_off.device)
         if n_frames == 0:              # nothing to write (an empty tensor has no address to hand over)
             return res
-        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_off.dtype == torch.int64
-        ns = 0
-        if d_keep is not None:
-            ns = max(d_stream_off.numel() - 1, 0)
-            assert d_stream_off.is_contiguous() and d_keep.is_contiguous()
-            assert d_stream_off.dtype == torch.int64 and d_keep.dtype == torch.int64
-            assert d_keep.numel() == ns * self.params.grid_h * ((self.params.grid_w + 63) // 64)
-        rec_bytes = 8 if compact else 40
-        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-        check(self._lib.mtgpu_scan_blobs_device(
-            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
-            None if d_sd is None else d_sd.data_ptr(), n_frames, ptr(d_stream_off), ns, ptr(d_keep), int(min_blob_cells),
-            *(ptr(res[k]) for k in BLOB_OUTPUTS), st))
+        head, st = self._device_batch(d_rec, d_off, d_sd, compact, stream)
+        ns = self._device_keep(d_stream_off, d_keep)
+        check(self._lib.mtgpu_scan_blobs_device(*head, _dptr(d_stream_off), ns, _dptr(d_keep), int(min_blob_cells),
+                                                *(_dptr(res[k]) for k in BLOB_OUTPUTS), st))
         return res
 
     # -------------------------------------------------------- motion blobs on compensated residuals
@@ -1017,21 +908,12 @@ class MotionScanner:
         modes' counts).  stream_off / keep: per-stream keep masks as for scan_zones, both or neither."""
         if (stream_off is None) != (keep is None):
             raise ValueError("stream_off and keep go together: give both or neither")
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        sd = None if batch.has_sd is None else np.ascontiguousarray(batch.has_sd, dtype=np.uint8)
-        n = max(len(off) - 1, 0)
-        soff, ns = None, 0
+        head, (soff, ns), _ = _host_batch(batch, stream_off)
         if keep is not None:
-            soff = np.ascontiguousarray(stream_off, dtype=np.uint64)
-            ns = max(len(soff) - 1, 0)
             keep = self._keep_words(keep, ns)
-        out = {"flags": np.zeros(n, dtype=np.uint8), "centres": np.zeros(n, dtype=np.uint32), "blobs": np.zeros(n, dtype=np.uint32),
-               "largest": np.zeros(n, dtype=np.uint32), "box": np.full(n, 0xFFFF, dtype=np.uint16).repeat(4).view(BLOB_BOX_DTYPE),
-               "info": np.zeros(n, dtype=GMC_INFO_DTYPE)}
-        check(self._lib.mtgpu_scan_frames_gmc_blobs(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(sd), n, _ptr(soff), ns,
-                                                    _ptr(keep), int(max_shift), int(min_share_q8), int(min_blob_cells),
-                                                    *(_ptr(out[k]) for k in GMC_BLOB_OUTPUTS)))
+        out = _host_outputs(GMC_BLOB_OUTPUTS, head[3])
+        check(self._lib.mtgpu_scan_frames_gmc_blobs(self._ctx, *head, soff, ns, _ptr(keep), int(max_shift), int(min_share_q8),
+                                                    int(min_blob_cells), *(_ptr(out[k]) for k in GMC_BLOB_OUTPUTS)))
         return out
 
     def scan_gmc_blobs_device(self, d_rec, d_off, d_sd, max_shift: int = GMC_DEFAULT_MAX_SHIFT,
@@ -1043,44 +925,18 @@ class MotionScanner:
         d_rec / d_off / d_sd / d_stream_off / d_keep / compact as for scan_blobs_device.  `largest` is ready for
         sweep_streams_device: level L there is flags at min_blob_cells = L.  out: a dict of preallocated tensors by
         name.  Asynchronous on `stream` (default: torch's current stream)."""
-        import torch
-        want = tuple(want)
-        for w in want:
-            if w not in GMC_BLOB_OUTPUTS:
-                raise ValueError(f"want: {w!r} is not one of {GMC_BLOB_OUTPUTS}")
+        want = _wanted(want, GMC_BLOB_OUTPUTS)
         if (d_stream_off is None) != (d_keep is None):
             raise ValueError("d_stream_off and d_keep go together: give both or neither")
-        dev = d_off.device
         n_frames = max(d_off.numel() - 1, 0)
-        res = {}
-        for name in GMC_BLOB_OUTPUTS:
-            if name not in want:
-                res[name] = None
-                continue
-            dtype = torch.uint8 if name == "flags" else torch.int16 if name == "box" else torch.int32
-            shape = (n_frames, 4) if name == "box" else (n_frames, 5) if name == "info" else (n_frames,)
-            t = (out or {}).get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=dev)
-            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, name
-            res[name] = t
+        res = _device_outputs(GMC_BLOB_OUTPUTS, want, out, n_frames, d_off.device)
         if n_frames == 0:              # nothing to write (an empty tensor has no address to hand over)
             return res
-        assert d_rec.is_contiguous() and d_off.is_contiguous() and d_off.dtype == torch.int64
-        ns = 0
-        if d_keep is not None:
-            ns = max(d_stream_off.numel() - 1, 0)
-            assert d_stream_off.is_contiguous() and d_keep.is_contiguous()
-            assert d_stream_off.dtype == torch.int64 and d_keep.dtype == torch.int64
-            assert d_keep.numel() == ns * self.params.grid_h * ((self.params.grid_w + 63) // 64)
-        rec_bytes = 8 if compact else 40
-        n_records = (d_rec.numel() * d_rec.element_size()) // rec_bytes
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-        check(self._lib.mtgpu_scan_gmc_blobs_device(
-            self._ctx, d_rec.data_ptr() if n_records else None, rec_bytes, n_records, d_off.data_ptr(),
-            None if d_sd is None else d_sd.data_ptr(), n_frames, ptr(d_stream_off), ns, ptr(d_keep), int(max_shift),
-            int(min_share_q8), int(min_blob_cells), *(ptr(res[k]) for k in GMC_BLOB_OUTPUTS), st))
+        head, st = self._device_batch(d_rec, d_off, d_sd, compact, stream)
+        ns = self._device_keep(d_stream_off, d_keep)
+        check(self._lib.mtgpu_scan_gmc_blobs_device(*head, _dptr(d_stream_off), ns, _dptr(d_keep), int(max_shift),
+                                                    int(min_share_q8), int(min_blob_cells),
+                                                    *(_dptr(res[k]) for k in GMC_BLOB_OUTPUTS), st))
         return res
 
     # -------------------------------------------------------- temporal persistence
@@ -1099,7 +955,7 @@ class MotionScanner:
         bx = None if box is None else np.ascontiguousarray(box, dtype=BLOB_BOX_DTYPE)
         if (sd is not None and len(sd) != n) or (bx is not None and len(bx) != n):
             raise ValueError("has_sd and box have one element per frame")
-        out = {"flags": np.zeros(n, dtype=np.uint8), "run": np.zeros(n, dtype=np.uint32), "pos": np.zeros(n, dtype=np.uint32)}
+        out = _host_outputs(PERSIST_OUTPUTS, n)
         check(self._lib.mtgpu_persist_flags(self._ctx, _ptr(fl), _ptr(sd), _ptr(bx), n, _ptr(soff) if len(soff) else None, ns,
                                             int(min_run), int(max_dropout), int(reach), *(_ptr(out[k]) for k in PERSIST_OUTPUTS)))
         return out
@@ -1114,23 +970,9 @@ class MotionScanner:
         launch has passed).  No output may share memory with an input.  Asynchronous on `stream` (default: torch's
         current stream)."""
         import torch
-        want = tuple(want)
-        for w in want:
-            if w not in PERSIST_OUTPUTS:
-                raise ValueError(f"want: {w!r} is not one of {PERSIST_OUTPUTS}")
         dev = d_flags.device
         n_frames = d_flags.numel()
-        res = {}
-        for name in PERSIST_OUTPUTS:
-            if name not in want:
-                res[name] = None
-                continue
-            dtype = torch.uint8 if name == "flags" else torch.int32
-            t = (out or {}).get(name)
-            if t is None:
-                t = torch.empty(n_frames, dtype=dtype, device=dev)
-            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (n_frames,), name
-            res[name] = t
+        res = _device_outputs(PERSIST_OUTPUTS, want, out, n_frames, dev)
         if n_frames == 0:              # nothing to write (an empty tensor has no address to hand over)
             return res
         assert d_flags.dtype == torch.uint8 and d_flags.is_contiguous()
@@ -1141,18 +983,12 @@ class MotionScanner:
         if held:
             work = torch.empty(n_frames, dtype=torch.int32, device=dev)
         assert work.dtype == torch.int32 and work.is_contiguous() and work.numel() >= n_frames
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        ptr = lambda t: None if t is None else t.data_ptr()        # noqa: E731
         check(self._lib.mtgpu_persist_flags_device(
-            self._ctx, d_flags.data_ptr(), ptr(d_has_sd), ptr(d_box), n_frames, d_stream_off.data_ptr(),
+            self._ctx, d_flags.data_ptr(), _dptr(d_has_sd), _dptr(d_box), n_frames, d_stream_off.data_ptr(),
             max(d_stream_off.numel() - 1, 0), int(min_run), int(max_dropout), int(reach), work.data_ptr(),
-            *(ptr(res[k]) for k in PERSIST_OUTPUTS), st))
+            *(_dptr(res[k]) for k in PERSIST_OUTPUTS), _stream_handle(dev, stream)))
         if held:
-            # (the workspace outlives the queued kernels: see merge_streams_device)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev))
-            self._held = [(e, w) for e, w in getattr(self, "_held", []) if not e.query()]
-            self._held.append((ev, work))
+            self._hold(work, dev, stream)
         return res
 
     # ------------------------------------------------------- motion scalar
@@ -1165,8 +1001,7 @@ class MotionScanner:
             return np.zeros(0, dtype=np.float64), np.zeros(0, dtype=np.uint32)
         import torch
         dev = torch.device("cuda", self.device)
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
+        _, _, (mv, off, _, _) = _host_batch(batch)
         d_mv = torch.from_numpy(mv.view(np.uint8).reshape(-1).copy()).to(dev)
         d_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
         scores, terms = self.motion_scores_device(d_mv, d_off)
@@ -1182,20 +1017,15 @@ class MotionScanner:
         dev = frame_off.device
         if scores is None:
             scores = torch.empty(max(n_frames, 0), dtype=torch.float64, device=dev)
-        if terms is None:
-            terms = torch.empty(max(n_frames, 0), dtype=torch.int32, device=dev)
-        elif terms is False:
-            terms = None
+        terms = _optional(terms, max(n_frames, 0), _COUNT, dev, checked=n_frames > 0)
         if n_frames <= 0:
             return scores, terms
         assert records.is_contiguous() and frame_off.is_contiguous() and scores.is_contiguous()
         assert frame_off.dtype == torch.int64 and scores.dtype == torch.float64 and scores.numel() >= n_frames
-        assert terms is None or (terms.dtype == torch.int32 and terms.is_contiguous() and terms.numel() >= n_frames)
         n_records = (records.numel() * records.element_size()) // 40
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
         check(self._lib.mtgpu_motion_scores_device(
             self._ctx, records.data_ptr() if n_records else None, n_records, frame_off.data_ptr(), n_frames,
-            scores.data_ptr(), None if terms is None else terms.data_ptr(), st))
+            scores.data_ptr(), _dptr(terms), _stream_handle(dev, stream)))
         return scores, terms
 
     def motion_bins_device(self, scores, terms, pts, stream_off, n_sec: int, acc=None, bin_terms=None, stream=None):
@@ -1209,21 +1039,16 @@ class MotionScanner:
         n_sec = int(n_sec)
         if acc is None:
             acc = torch.empty((max(n_streams, 0), n_sec), dtype=torch.float64, device=dev)
-        if bin_terms is None and terms is not None:
-            bin_terms = torch.empty((max(n_streams, 0), n_sec), dtype=torch.int64, device=dev)
-        elif bin_terms is False:
-            bin_terms = None
         assert scores.dtype == torch.float64 and pts.dtype == torch.float64 and stream_off.dtype == torch.int64
         assert scores.is_contiguous() and pts.is_contiguous() and stream_off.is_contiguous() and acc.is_contiguous()
         assert acc.dtype == torch.float64 and acc.numel() >= max(n_streams, 0) * n_sec
         assert terms is None or (terms.dtype == torch.int32 and terms.is_contiguous())
-        assert bin_terms is None or (bin_terms.dtype == torch.int64 and bin_terms.is_contiguous()
-                                     and bin_terms.numel() >= max(n_streams, 0) * n_sec)
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        if bin_terms is None and terms is None:          # no counts in, none out
+            bin_terms = False
+        bin_terms = _optional(bin_terms, max(n_streams, 0), ("int64", (n_sec,)), dev)
         check(self._lib.mtgpu_motion_bins_device(
-            self._ctx, scores.data_ptr(), None if terms is None else terms.data_ptr(), pts.data_ptr(),
-            stream_off.data_ptr(), max(n_streams, 0), n_sec, acc.data_ptr(),
-            None if bin_terms is None else bin_terms.data_ptr(), st))
+            self._ctx, scores.data_ptr(), _dptr(terms), pts.data_ptr(), stream_off.data_ptr(), max(n_streams, 0), n_sec,
+            acc.data_ptr(), _dptr(bin_terms), _stream_handle(dev, stream)))
         return acc, bin_terms
 
     def motion_scalar(self, batch: FrameBatch, pts_seconds, n_sec: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
@@ -1241,10 +1066,9 @@ class MotionScanner:
         n_sec = int(n_sec)
         acc = np.zeros(max(n_sec, 0), dtype=np.float64)
         bin_terms = np.zeros(max(n_sec, 0), dtype=np.uint64)
-        mv = np.ascontiguousarray(batch.mv, dtype=MV_DTYPE)
-        off = np.ascontiguousarray(batch.frame_off, dtype=np.uint64)
-        check(self._lib.mtgpu_motion_scalar(self._ctx, _ptr(mv) if len(mv) else None, _ptr(off), _ptr(pts), max(n, 0),
-                                            n_sec, _ptr(acc) if n_sec > 0 else None, _ptr(bin_terms) if n_sec > 0 else None))
+        (mv, off, _, n), _, _ = _host_batch(batch)
+        check(self._lib.mtgpu_motion_scalar(self._ctx, mv, off, _ptr(pts), n, n_sec, _ptr(acc) if n_sec > 0 else None,
+                                            _ptr(bin_terms) if n_sec > 0 else None))
         return acc, bin_terms
 
     def scan_range(self, frame_pts: Sequence[int], frames: Sequence[Optional[np.ndarray]],
@@ -1276,8 +1100,7 @@ class MotionScanner:
         check(self._lib.mtgpu_merge_segments(self._ctx, _ptr(ts) if len(ts) else None, len(ts),
                                              C.byref(c_mp), 1 if job_semantics else 0,
                                              _ptr(seg) if cap else None, cap, C.byref(res)))
-        out = {n: getattr(res, n) for n, _ in MergeResultC._fields_}
-        return seg[:res.n_segments].copy(), out
+        return seg[:res.n_segments].copy(), _fields(res)
 
     def merge_timestamps_device(self, ts, mp: MergeParams, job_semantics: bool = False, seg_cap: int = 64,
                                 stream=None):
@@ -1290,11 +1113,10 @@ class MotionScanner:
         dev = ts.device
         seg = torch.zeros((seg_cap, 2), dtype=torch.float64, device=dev)
         res = torch.zeros(MERGE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
         c_mp = mp.to_c()
         check(self._lib.mtgpu_merge_timestamps_device(
             self._ctx, ts.data_ptr() if ts.numel() else None, ts.numel(), C.byref(c_mp),
-            1 if job_semantics else 0, seg.data_ptr(), seg_cap, res.data_ptr(), st))
+            1 if job_semantics else 0, seg.data_ptr(), seg_cap, res.data_ptr(), _stream_handle(dev, stream)))
         return seg, res
 
     def merge_streams_device(self, flags, pts, stream_off, merge_params, job_semantics=False,
@@ -1319,20 +1141,39 @@ class MotionScanner:
             res = torch.zeros((max(n_streams, 0), MERGE_RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
         if n_streams <= 0:
             return seg, res
-        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream      # (direct: a timed loop of bench.py)
         check(self._lib.mtgpu_merge_streams_device(
             self._ctx, None if flags is None else flags.data_ptr(), pts.data_ptr(),
             stream_off.data_ptr(), n_streams, merge_params.data_ptr(), 1 if job_semantics else 0,
             ws.data_ptr(), seg.data_ptr(), seg_cap, res.data_ptr(), st))
         if out is None:
-            # the workspace must outlive the kernel that was just queued: it is held until an event recorded
-            # behind the launch on ITS stream has passed (torch's caching allocator knows nothing of a raw
-            # hipStream_t handed in by the caller, and several merges may be queued back to back)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev))
-            self._held = [(e, w) for e, w in getattr(self, "_held", []) if not e.query()]
-            self._held.append((ev, ws))
+            self._hold(ws, dev, stream)
         return seg, res
+
+
+# what a pipe's drain_centres() can carry per frame (mt_pipe_report), and which of them each scan mode of a pipe takes
+_REPORTS = {"centres": _abi.MT_PIPE_REPORT_CENTRES, "largest": _abi.MT_PIPE_REPORT_LARGEST,
+            "vector": _abi.MT_PIPE_REPORT_VECTOR, "sectors": _abi.MT_PIPE_REPORT_SECTORS}
+_REPORT_NAMES = {code: name for name, code in _REPORTS.items()}
+_MODE_REPORTS = {"blobs": ("centres", "largest"), "gmc": ("centres", "vector"), "gmc_blobs": ("centres", "largest", "vector"),
+                 "dir": ("centres", "sectors"), "plane": ("centres", "sectors")}
+
+
+def _report_code(mode, report) -> int:
+    names = _MODE_REPORTS[mode]
+    if report not in names:
+        quoted = [repr(n) for n in names]
+        raise ValueError(f"report is {report!r}, not {', '.join(quoted[:-1])} or {quoted[-1]}")
+    return _REPORTS[report]
+
+
+def _report_name(mode, code) -> str:
+    """The report a getter of `mode` hands back for the library's code.  A code the mode does not take reads as
+    "centres"; under gmc_blobs it is a KeyError (the library answers neither)."""
+    name = _REPORT_NAMES.get(code)
+    if mode == "gmc_blobs" and name not in _MODE_REPORTS[mode]:
+        raise KeyError(code)
+    return name if name in _MODE_REPORTS[mode] else "centres"
 
 
 class ScanPipe:
@@ -1415,10 +1256,7 @@ class ScanPipe:
         was.  report: which count drain_centres() returns, "centres" or "largest" (the staging block has one count
         array; "largest" needs centres=True).  Only while no batch is being filled or in flight (call drain() first):
         otherwise MtgpuError(MT_ERR_BUSY) and nothing changes."""
-        codes = {"centres": _abi.MT_PIPE_REPORT_CENTRES, "largest": _abi.MT_PIPE_REPORT_LARGEST}
-        if report not in codes:
-            raise ValueError(f"report is {report!r}, not 'centres' or 'largest'")
-        check(self._lib.mtgpu_pipe_set_blobs(self._pipe, int(min_blob_cells), codes[report]))
+        check(self._lib.mtgpu_pipe_set_blobs(self._pipe, int(min_blob_cells), _report_code("blobs", report)))
 
     @property
     def blobs(self) -> Optional[Tuple[int, str]]:
@@ -1426,7 +1264,7 @@ class ScanPipe:
         n, r = C.c_int32(), C.c_int()
         if self._lib.mtgpu_pipe_blobs(self._pipe, C.byref(n), C.byref(r)) != 1:
             return None
-        return int(n.value), ("largest" if r.value == _abi.MT_PIPE_REPORT_LARGEST else "centres")
+        return int(n.value), _report_name("blobs", r.value)
 
     def set_gmc(self, max_shift: int = _abi.GMC_DEFAULT_MAX_SHIFT, min_share_q8: int = _abi.GMC_DEFAULT_MIN_SHARE_Q8,
                 report: str = "centres"):
@@ -1437,10 +1275,7 @@ class ScanPipe:
         (uint16)gx | (uint16)gy << 16 (unpack_gmc_vector); "vector" needs centres=True.  Only while no batch is being
         filled or in flight (call drain() first): otherwise MtgpuError(MT_ERR_BUSY) and nothing changes.  Not together
         with set_blobs: MtgpuError(MT_ERR_UNSUPPORTED)."""
-        codes = {"centres": _abi.MT_PIPE_REPORT_CENTRES, "vector": _abi.MT_PIPE_REPORT_VECTOR}
-        if report not in codes:
-            raise ValueError(f"report is {report!r}, not 'centres' or 'vector'")
-        check(self._lib.mtgpu_pipe_set_gmc(self._pipe, 1, int(max_shift), int(min_share_q8), codes[report]))
+        check(self._lib.mtgpu_pipe_set_gmc(self._pipe, 1, int(max_shift), int(min_share_q8), _report_code("gmc", report)))
 
     def clear_gmc(self):
         """Compensation off (mtgpu_pipe_set_gmc with enable 0): the pipe is the plain or masked pipe it was before."""
@@ -1451,10 +1286,7 @@ class ScanPipe:
         ms, q8, r = C.c_int32(), C.c_int32(), C.c_int()
         if self._lib.mtgpu_pipe_gmc(self._pipe, C.byref(ms), C.byref(q8), C.byref(r)) != 1:
             return None
-        return int(ms.value), int(q8.value), ("vector" if r.value == _abi.MT_PIPE_REPORT_VECTOR else "centres")
-
-    _PAIR_REPORTS = {"centres": _abi.MT_PIPE_REPORT_CENTRES, "largest": _abi.MT_PIPE_REPORT_LARGEST,
-                     "vector": _abi.MT_PIPE_REPORT_VECTOR}
+        return int(ms.value), int(q8.value), _report_name("gmc", r.value)
 
     def set_gmc_blobs(self, min_blob_cells: int, max_shift: int = _abi.GMC_DEFAULT_MAX_SHIFT,
                       min_share_q8: int = _abi.GMC_DEFAULT_MIN_SHARE_Q8, report: str = "centres"):
@@ -1465,10 +1297,8 @@ class ScanPipe:
         (unpack_gmc_vector); the last two need centres=True.  Only while no batch is being filled or in flight:
         otherwise MtgpuError(MT_ERR_BUSY) and nothing changes.  Not while set_blobs or set_gmc is on, nor they while
         this is: MtgpuError(MT_ERR_INVALID)."""
-        if report not in self._PAIR_REPORTS:
-            raise ValueError(f"report is {report!r}, not 'centres', 'largest' or 'vector'")
         check(self._lib.mtgpu_pipe_set_gmc_blobs(self._pipe, int(min_blob_cells), int(max_shift), int(min_share_q8),
-                                                 self._PAIR_REPORTS[report]))
+                                                 _report_code("gmc_blobs", report)))
 
     def clear_gmc_blobs(self):
         """The compensated blob scan off (mtgpu_pipe_set_gmc_blobs with min_blob_cells 0): the pipe as it was before."""
@@ -1480,10 +1310,7 @@ class ScanPipe:
         n, ms, q8, r = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int()
         if self._lib.mtgpu_pipe_gmc_blobs(self._pipe, C.byref(n), C.byref(ms), C.byref(q8), C.byref(r)) != 1:
             return None
-        names = {v: k for k, v in self._PAIR_REPORTS.items()}
-        return int(n.value), int(ms.value), int(q8.value), names[r.value]
-
-    _DIR_REPORTS = {"centres": _abi.MT_PIPE_REPORT_CENTRES, "sectors": _abi.MT_PIPE_REPORT_SECTORS}
+        return int(n.value), int(ms.value), int(q8.value), _report_name("gmc_blobs", r.value)
 
     def set_dir(self, allow=_abi.DIR_ALL, report: str = "centres"):
         """The direction filter on the decode path (mtgpu_pipe_set_dir), the pipe's fourth mode: from now on a record of
@@ -1494,12 +1321,11 @@ class ScanPipe:
         (direction.unpack_sector_word); "sectors" needs centres=True.  Only while no batch is being filled or in flight
         (call drain() first): otherwise MtgpuError(MT_ERR_BUSY) and nothing changes.  Not together with set_blobs,
         set_gmc or set_gmc_blobs: MtgpuError(MT_ERR_UNSUPPORTED)."""
-        if report not in self._DIR_REPORTS:
-            raise ValueError(f"report is {report!r}, not 'centres' or 'sectors'")
+        code = _report_code("dir", report)
         if not isinstance(allow, (int, np.integer)):
             from .direction import allow_from_names
             allow = allow_from_names(allow)
-        check(self._lib.mtgpu_pipe_set_dir(self._pipe, 1, int(allow), self._DIR_REPORTS[report]))
+        check(self._lib.mtgpu_pipe_set_dir(self._pipe, 1, int(allow), code))
 
     def clear_dir(self):
         """The direction filter off (mtgpu_pipe_set_dir with enable 0): the pipe is the plain or masked pipe it was before."""
@@ -1510,7 +1336,7 @@ class ScanPipe:
         a, r = C.c_int32(), C.c_int()
         if self._lib.mtgpu_pipe_dir(self._pipe, C.byref(a), C.byref(r)) != 1:
             return None
-        return int(a.value), ("sectors" if r.value == _abi.MT_PIPE_REPORT_SECTORS else "centres")
+        return int(a.value), _report_name("dir", r.value)
 
     def set_plane(self, plane, report: str = "centres"):
         """A direction plane on the decode path (mtgpu_pipe_set_plane): from now on a record of every batch votes only if
@@ -1521,8 +1347,7 @@ class ScanPipe:
         Only while no batch is being filled or in flight (call drain() first): otherwise MtgpuError(MT_ERR_BUSY) and
         nothing changes.  Not together with set_dir (MtgpuError(MT_ERR_INVALID): one rule at two granularities), nor
         with set_blobs, set_gmc or set_gmc_blobs (MtgpuError(MT_ERR_UNSUPPORTED))."""
-        if report not in self._DIR_REPORTS:
-            raise ValueError(f"report is {report!r}, not 'centres' or 'sectors'")
+        code = _report_code("plane", report)
         p = self._scanner.params
         a = np.asarray(plane)
         if a.dtype != np.uint8:
@@ -1530,7 +1355,7 @@ class ScanPipe:
         if a.shape != (p.grid_h, p.grid_w):
             raise ValueError(f"plane has shape {a.shape}, not {(p.grid_h, p.grid_w)}")
         a = np.ascontiguousarray(a)
-        check(self._lib.mtgpu_pipe_set_plane(self._pipe, _ptr(a), self._DIR_REPORTS[report]))
+        check(self._lib.mtgpu_pipe_set_plane(self._pipe, _ptr(a), code))
 
     def clear_plane(self):
         """The direction plane off (mtgpu_pipe_set_plane with NULL): the pipe is the plain or masked pipe it was before."""
@@ -1543,7 +1368,7 @@ class ScanPipe:
         a, r = np.zeros((p.grid_h, p.grid_w), np.uint8), C.c_int()
         if self._lib.mtgpu_pipe_plane(self._pipe, _ptr(a), C.byref(r)) != 1:
             return None
-        return a, ("sectors" if r.value == _abi.MT_PIPE_REPORT_SECTORS else "centres")
+        return a, _report_name("plane", r.value)
 
     @staticmethod
     def unpack_gmc_vector(word: int) -> Tuple[int, int]:
