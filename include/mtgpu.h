@@ -511,6 +511,11 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * declared the same way. */
 #include "mtgpu_pipe_lanes.h"
 
+/* Object lists: the K largest blobs of every frame, ranked and boxed, and a count of the blobs of a minimum size
+ * (src/motion_scanner.cpp:272-294, then the components of the centres) — three more entry points, declared the same
+ * way. */
+#include "mtgpu_objects.h"
+
 /* Temporal persistence: the runs of consecutive motion frames per stream — across the key frames that were never
  * analysed, with a bounded dropout and, given the blob boxes, only while the object stays in place — and every frame's
  * run length and place in its run (the frames src/motion_scanner.cpp:382-383 pools, before src/pipeline.cpp:328-344

@@ -35,6 +35,10 @@ MV_DTYPE = np.dtype(
 SEGMENT_DTYPE = np.dtype([("start", "<f8"), ("end", "<f8")])
 # mt_blob_box (include/mtgpu_blobs.h): inclusive cell bounds of a frame's largest blob, all 0xFFFF: no blob
 BLOB_BOX_DTYPE = np.dtype([("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2")])
+# mt_object (include/mtgpu_objects.h): one blob of a frame's list — its cell count (0: no such blob), the smallest
+# y * grid_w + x of its cells, its inclusive cell bounds; an empty entry reads {0, 0xFFFFFFFF, 0xFFFF x 4}
+OBJECT_DTYPE = np.dtype([("cells", "<u4"), ("first", "<u4"), ("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2")])
+OBJECTS_MAX, OBJECT_TABLE_BYTES = 16, 24
 # mt_gmc_info (include/mtgpu_gmc.h): the applied vector, the modes of the two axes, the counted records, the modes' counts
 GMC_INFO_DTYPE = np.dtype([("gx", "<i2"), ("gy", "<i2"), ("mode_x", "<i2"), ("mode_y", "<i2"), ("n_in", "<u4"), ("n_x", "<u4"),
                            ("n_y", "<u4")])
@@ -86,6 +90,11 @@ class ZonesPlanC(C.Structure):
 
 
 class BlobsPlanC(C.Structure):
+    _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("keep_words_per_row", C.c_int32),
+                ("keep_words_per_stream", C.c_int32)]
+
+
+class ObjectsPlanC(C.Structure):
     _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("keep_words_per_row", C.c_int32),
                 ("keep_words_per_stream", C.c_int32)]
 
@@ -332,10 +341,21 @@ ABI_PIPE_LANES = {
     "mtgpu_pipe_plane": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_objects.h declares (object lists; mtgpu.h includes it).
+ABI_OBJECTS = {
+    "mtgpu_objects_preview": (C.c_int, [C.POINTER(ScanParamsC), C.c_int, C.c_int, C.POINTER(ObjectsPlanC)]),
+    "mtgpu_scan_objects_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtgpu_scan_frames_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+}
+
 # every table above, in header order: what load_library() binds
 ABI_TABLES = (ABI, ABI_MOTION, ABI_SWEEP, ABI_ACTIVITY, ABI_ZONES, ABI_PIPE_ZONES, ABI_BLOBS, ABI_PIPE_BLOBS, ABI_GMC,
               ABI_PIPE_GMC, ABI_GMC_BLOBS, ABI_PIPE_GMC_BLOBS, ABI_PERSIST, ABI_PIPE_BOXES, ABI_DIR, ABI_PIPE_DIR, ABI_LANES,
-              ABI_PIPE_LANES)
+              ABI_PIPE_LANES, ABI_OBJECTS)
 
 _lib = None
 

@@ -31,6 +31,7 @@
 #include "persist_kernels.h"
 #include "dir_kernels.h"
 #include "lanes_kernels.h"
+#include "objects_kernels.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -2599,6 +2600,137 @@ int mtgpu_flow_map(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, con
   MT_TRY(sg.upload());
   MT_TRY(flow_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff), n_streams,
                  sg.at<uint32_t>(o_flow), sg.st));
+  return sg.download();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- object lists (src/motion_scanner.cpp:272-294 per frame,
+// then the connected components of the centres, ranked; include/mtgpu_objects.h)
+
+namespace {
+
+static_assert(sizeof(mt_object) == sizeof(mtgpu::ObjectWord4) && sizeof(mt_object) == 16, "mt_object is one 16-byte store");
+static_assert(MT_OBJECTS_MAX == mtgpu::kObjectsMax && MT_OBJECT_TABLE_BYTES == mtgpu::kObjectTableBytes, "the kernel's limits are the ABI's");
+
+int check_top_k(int32_t k) {
+  if (k < 1 || k > MT_OBJECTS_MAX) return fail(MT_ERR_INVALID, "k is %d, outside 1 .. %d", (int)k, MT_OBJECTS_MAX);
+  return MT_OK;
+}
+
+// One form: the blob scan's layout and the ranking table for k entries.  It fits or the grid is unsupported.
+int objects_plan(const mt_scan_params &p, int k, int lds_max, mtgpu_objects_plan *out) {
+  const int R = analysed_rows(p);
+  const long long need = (long long)mtgpu::objects_lds_bytes(p.grid_w, R, k);
+  if (need > (long long)lds_max)
+    return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows, the keep rows, one mask plane and the "
+                "ranking table for %d objects (%lld bytes) do not fit %d bytes of LDS; the object scan has no banded form", p.grid_w,
+                p.grid_h, R + 2, k, need, lds_max);
+  const long long W = ((long long)p.grid_w + 63) / 64;
+  out->lds_bytes = (int32_t)need;
+  out->workgroup = mtgpu::kObjectsBlock;
+  out->keep_words_per_row = (int32_t)W;
+  out->keep_words_per_stream = (int32_t)(W * (long long)p.grid_h);
+  return MT_OK;
+}
+
+// The object scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
+int objects_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
+               const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, const uint64_t *d_keep,
+               int32_t k, int32_t min_blob_cells, int32_t min_objects, uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_blobs,
+               uint32_t *d_objects, mt_object *d_list, hipStream_t st) {
+  mtgpu_objects_plan op;
+  MT_TRY(objects_plan(c->params, k, c->lds_max, &op));
+  mtgpu::ObjLaunch L;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, op.lds_bytes, st);
+  L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
+  L.n_streams = n_streams;
+  L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
+  L.flags = d_flags; L.centres = d_centres; L.blobs = d_blobs; L.objects = d_objects;
+  L.list = reinterpret_cast<mtgpu::ObjectWord4 *>(d_list);
+  L.topk = k;
+  L.obj_need = min_objects < 1 ? 1u : (unsigned int)min_objects;
+  fill_tile(L.k, c->k, mtgpu::blob_tile_words);
+  L.k.clust_need = c->k.clust_need;
+  L.k.blob_need = min_blob_cells < 1 ? 1u : (unsigned int)min_blob_cells;
+  PlanWs ws(c, st, nullptr, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_object_scan, "object scan launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtgpu_objects_preview(const mt_scan_params *p, int k, int lds_bytes_per_workgroup, mtgpu_objects_plan *out) {
+  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
+  MT_TRY(check_top_k(k));
+  MT_TRY(validate_params(p));
+  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
+  mtgpu_objects_plan pl;
+  MT_TRY(objects_plan(*p, k, lds_bytes_per_workgroup, &pl));
+  *out = pl;
+  return MT_OK;
+}
+
+int mtgpu_scan_objects_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
+                              const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
+                              const uint64_t *d_keep, int32_t k, int32_t min_blob_cells, int32_t min_objects, uint8_t *d_flags,
+                              uint32_t *d_centres, uint32_t *d_blobs, uint32_t *d_objects, mt_object *d_list, void *stream) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  MT_TRY(check_top_k(k));
+  MT_TRY(check_rec_bytes(rec_bytes));
+  MT_TRY(check_any_output("d_", {{"flags", d_flags}, {"centres", d_centres}, {"blobs", d_blobs}, {"objects", d_objects}, {"list", d_list}}));
+  if (n_frames > 0 && !d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
+  MT_TRY(check_stream_table("d_", d_stream_off, n_streams, d_keep));
+  MT_TRY(check_aligned("d_", {{"frame_off", d_frame_off, 8}, {"stream_off", d_stream_off, 8}, {"keep", d_keep, 8}}));
+  if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
+  MT_TRY(check_rec("d_", rec_bytes, d_rec));
+  // (one 16-byte store per entry)
+  MT_TRY(check_aligned("d_", {{"centres", d_centres, 4}, {"blobs", d_blobs, 4}, {"objects", d_objects, 4}, {"list", d_list, 16}}));
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  mtgpu_objects_plan op;
+  MT_TRY(objects_plan(c->params, k, c->lds_max, &op));       // a grid without a form: before any HIP call
+  if (n_frames == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  MT_TRY(check_on_device(c, {{"d_keep", d_keep}, {"d_flags", d_flags}, {"d_centres", d_centres}, {"d_blobs", d_blobs},
+                             {"d_objects", d_objects}, {"d_list", d_list}}));
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
+  return objects_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_keep, k,
+                    min_blob_cells, min_objects, d_flags, d_centres, d_blobs, d_objects, d_list, static_cast<hipStream_t>(stream));
+}
+
+int mtgpu_scan_frames_objects(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
+                              const uint64_t *stream_off, uint32_t n_streams, const uint64_t *keep, int32_t k, int32_t min_blob_cells,
+                              int32_t min_objects, uint8_t *flags, uint32_t *centres, uint32_t *blobs, uint32_t *objects,
+                              mt_object *list) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  MT_TRY(check_top_k(k));
+  MT_TRY(check_any_output("", {{"flags", flags}, {"centres", centres}, {"blobs", blobs}, {"objects", objects}, {"list", list}}));
+  if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
+  MT_TRY(check_stream_table("", stream_off, n_streams, keep));
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  if (keep) MT_TRY(check_stream_off(stream_off, n_streams, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  mtgpu_objects_plan op;
+  MT_TRY(objects_plan(c->params, k, c->lds_max, &op));       // a grid without a form: before anything is staged
+  if (n_frames == 0) return MT_OK;
+
+  // (without a mask stream_off and keep are null and n_streams is 0: no room, null device pointers; every slot of the
+  // block begins at a multiple of 256 bytes, so the device list is 16-byte aligned whatever `list` is)
+  const size_t words = sizeof(uint32_t) * (size_t)n_frames;
+  Staged sg(c, c->d_misc, false, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int i_soff = sg.in(stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1));
+  const int i_keep = sg.in(keep, sizeof(uint64_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.W);
+  const int o_fl = sg.out(flags, n_frames), o_cen = sg.out(centres, words), o_bl = sg.out(blobs, words), o_ob = sg.out(objects, words);
+  const int o_list = sg.out(list, sizeof(mt_object) * (size_t)n_frames * (size_t)k);
+  MT_TRY(sg.upload());
+  MT_TRY(objects_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff), n_streams,
+                    sg.at<const uint64_t>(i_keep), k, min_blob_cells, min_objects, sg.at<uint8_t>(o_fl), sg.at<uint32_t>(o_cen),
+                    sg.at<uint32_t>(o_bl), sg.at<uint32_t>(o_ob), sg.at<mt_object>(o_list), sg.st));
   return sg.download();
 }
 

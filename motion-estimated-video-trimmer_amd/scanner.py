@@ -20,7 +20,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi, config
-from ._abi import (BLOB_BOX_DTYPE, BlobsPlanC, COMPACT_DTYPE, DIR_ALL, DirPlanC, LanesPlanC, LAYOUT_AOS40, LAYOUT_BOXES, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
+from ._abi import (BLOB_BOX_DTYPE, OBJECT_DTYPE, BlobsPlanC, COMPACT_DTYPE, DIR_ALL, DirPlanC, LanesPlanC, LAYOUT_AOS40, LAYOUT_BOXES, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
                    GMC_DEFAULT_MAX_SHIFT, GMC_DEFAULT_MIN_SHARE_Q8, GMC_INFO_DTYPE, GmcBlobsPlanC, GmcPlanC,
                    MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PersistPlanC, PlanC, ScanParamsC, SweepPlanC, ZonesPlanC, check,
                    load_library)
@@ -280,15 +280,16 @@ DIR_OUTPUTS = ("flags", "centres", "rose")
 
 # Every named output of the scans: name -> (torch element type, trailing shape on the device, numpy dtype on the host,
 # the byte a host array is filled with).  A structured numpy dtype takes the trailing shape into its element; a trailing
-# shape of None is the caller's (the grid of an activity map).  The *_OUTPUTS tuples above are the public lists of names
+# shape of None is the caller's (the grid of an activity map, the k entries of an object list: objects.py).  The *_OUTPUTS tuples above are the public lists of names
 # and the order of the library's arguments.
 _COUNT = ("int32", (), np.uint32, 0)
 _OUTPUTS = {
     "flags": ("uint8", (), np.uint8, 0),
-    "centres": _COUNT, "blobs": _COUNT, "largest": _COUNT, "run": _COUNT, "pos": _COUNT, "frames": _COUNT,
+    "centres": _COUNT, "blobs": _COUNT, "largest": _COUNT, "objects": _COUNT, "run": _COUNT, "pos": _COUNT, "frames": _COUNT,
     "rose": ("int32", (8,), np.uint32, 0),
     "box": ("int16", (4,), BLOB_BOX_DTYPE, 0xFF),
     "info": ("int32", (5,), GMC_INFO_DTYPE, 0),
+    "list": ("int32", None, OBJECT_DTYPE, 0),
     "active": ("int32", None, np.uint32, 0), "centre": ("int32", None, np.uint32, 0),
 }
 
@@ -308,7 +309,7 @@ def _host_outputs(names, n, want=None, grid=()) -> dict:
         _, trail, dtype, fill = _OUTPUTS[name]
         out[name] = None
         if want is None or name in want:
-            out[name] = np.empty((n,) + (() if np.dtype(dtype).names else grid if trail is None else trail), dtype=dtype)
+            out[name] = np.empty((n,) + (grid if trail is None else () if np.dtype(dtype).names else trail), dtype=dtype)
             out[name].view(np.uint8)[...] = fill
     return out
 
