@@ -516,6 +516,10 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * way. */
 #include "mtgpu_objects.h"
 
+/* Object tracks: which entry of the previous motion frame's list each listed object continues, its age, its track and
+ * the track's length — three more entry points, declared the same way. */
+#include "mtgpu_tracks.h"
+
 /* Temporal persistence: the runs of consecutive motion frames per stream — across the key frames that were never
  * analysed, with a bounded dropout and, given the blob boxes, only while the object stays in place — and every frame's
  * run length and place in its run (the frames src/motion_scanner.cpp:382-383 pools, before src/pipeline.cpp:328-344

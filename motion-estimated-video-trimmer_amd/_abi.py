@@ -112,6 +112,10 @@ class PersistPlanC(C.Structure):
     _fields_ = [("workgroup", C.c_int32), ("frames_per_tile", C.c_int32)]
 
 
+class TracksPlanC(C.Structure):
+    _fields_ = [("workgroup", C.c_int32), ("frames_per_tile", C.c_int32), ("work_words_per_entry", C.c_int32)]
+
+
 class DirPlanC(C.Structure):
     _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("sectors", C.c_int32), ("rose_bytes", C.c_int32)]
 
@@ -352,10 +356,23 @@ ABI_OBJECTS = {
                                             C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes): every symbol include/mtgpu_tracks.h declares (object tracks; mtgpu.h includes it).
+ABI_TRACKS = {
+    "mtgpu_tracks_preview": (C.c_int, [C.c_int, C.POINTER(TracksPlanC)]),
+    "mtgpu_track_objects_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtgpu_track_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+}
+TRACK_NO_PRED, TRACK_NO_ID = 0xFF, 0xFFFFFFFF
+TRACK_WORK_WORDS = 2                                 # mtgpu_tracks_plan.work_words_per_entry: uint32 words of d_work per list entry
+
 # every table above, in header order: what load_library() binds
 ABI_TABLES = (ABI, ABI_MOTION, ABI_SWEEP, ABI_ACTIVITY, ABI_ZONES, ABI_PIPE_ZONES, ABI_BLOBS, ABI_PIPE_BLOBS, ABI_GMC,
               ABI_PIPE_GMC, ABI_GMC_BLOBS, ABI_PIPE_GMC_BLOBS, ABI_PERSIST, ABI_PIPE_BOXES, ABI_DIR, ABI_PIPE_DIR, ABI_LANES,
-              ABI_PIPE_LANES, ABI_OBJECTS)
+              ABI_PIPE_LANES, ABI_OBJECTS, ABI_TRACKS)
 
 _lib = None
 

@@ -29,6 +29,7 @@
 #include "gmc_kernels.h"
 #include "gmc_blobs_kernels.h"
 #include "persist_kernels.h"
+#include "tracks_kernels.h"
 #include "dir_kernels.h"
 #include "lanes_kernels.h"
 #include "objects_kernels.h"
@@ -2242,6 +2243,151 @@ int mtgpu_persist_flags(mtgpu_ctx *c, const uint8_t *flags, const uint8_t *has_s
   if (flags_out) HIP_TRY(hipMemcpyAsync(flags_out, d + o_out, n, hipMemcpyDeviceToHost, st));
   if (run) HIP_TRY(hipMemcpyAsync(run, d + o_run, words, hipMemcpyDeviceToHost, st));
   if (pos) HIP_TRY(hipMemcpyAsync(pos, d + o_pos, words, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return MT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- object tracks (include/mtgpu_tracks.h)
+
+namespace {
+
+static_assert(sizeof(mtgpu::TrackObject) == sizeof(mt_object) && sizeof(mt_object) == 16, "the kernel's list entry is the ABI's");
+static_assert(mtgpu::kTracksGroup == MT_OBJECTS_MAX, "one lane per list entry");
+
+struct TracksRange { const char *name; const void *p; size_t bytes; };
+
+// What the arguments of a tracks call decide alone (`d`: "d_" for the device entry point, "" for the host one): no
+// context, no device.  The rungs are persistence's, with k and the size limit in front of what they size.
+int tracks_check_args(const char *d, const void *flags, const void *has_sd, const void *list, int32_t k, uint32_t n_frames,
+                      const void *stream_off, uint32_t n_streams, uint32_t reach, const void *work, bool device, const void *pred,
+                      const void *age, const void *id, const void *len, const void *track, const void *flags_out) {
+  MT_TRY(check_any_output(d, {{"pred", pred}, {"age", age}, {"id", id}, {"len", len}, {"track", track}, {"flags_out", flags_out}}));
+  if (k < 1 || k > MT_OBJECTS_MAX) return fail(MT_ERR_INVALID, "k is %d, outside [1,%d]", k, MT_OBJECTS_MAX);
+  if ((uint64_t)n_frames * (uint64_t)k >= 0xFFFFFFFFull)
+    return fail(MT_ERR_INVALID, "n_frames %u x k %d is not below 4294967295", n_frames, k);
+  if (reach > 65535u) return fail(MT_ERR_INVALID, "reach %u outside [0,65535]", reach);
+  if (n_frames > 0 && !flags) return fail(MT_ERR_INVALID, "%sflags is NULL", d);
+  if (n_frames > 0 && !list) return fail(MT_ERR_INVALID, "%slist is NULL", d);
+  if (n_frames > 0 && !stream_off) return fail(MT_ERR_INVALID, "%sstream_off is NULL", d);
+  if (n_frames > 0 && device && !work) return fail(MT_ERR_INVALID, "%swork is NULL", d);
+  if (n_frames > 0 && n_streams == 0) return fail(MT_ERR_INVALID, "n_streams is 0 with n_frames %u", n_frames);
+  MT_TRY(check_aligned(d, {{"stream_off", stream_off, 8}, {"list", device ? list : nullptr, 16}, {"work", work, 4}, {"age", age, 4},
+                           {"id", id, 4}, {"len", len, 4}, {"track", track, 4}}));
+  // no in-place form: an output or the workspace shares no byte with an input or with another of them
+  const size_t n = n_frames, nk = n * (size_t)k;
+  const TracksRange r[11] = {{"flags", flags, n}, {"has_sd", has_sd, n}, {"list", list, nk * sizeof(mt_object)},
+                             {"stream_off", stream_off, ((size_t)n_streams + 1) * sizeof(uint64_t)},
+                             {"work", work, nk * sizeof(uint32_t) * mtgpu::kTracksWorkWords}, {"pred", pred, nk},
+                             {"age", age, nk * sizeof(uint32_t)}, {"id", id, nk * sizeof(uint32_t)}, {"len", len, nk * sizeof(uint32_t)},
+                             {"track", track, n * sizeof(uint32_t)}, {"flags_out", flags_out, n}};
+  for (int i = 4; i < 11 && n > 0; ++i) {                     // r[4 ..]: the workspace and the outputs
+    if (!r[i].p) continue;
+    for (int j = 0; j < i; ++j) {
+      if (!r[j].p) continue;
+      const uintptr_t a0 = (uintptr_t)r[i].p, a1 = a0 + r[i].bytes, b0 = (uintptr_t)r[j].p, b1 = b0 + r[j].bytes;
+      if (a0 < b1 && b0 < a1) return fail(MT_ERR_INVALID, "%s%s overlaps %s%s: there is no in-place form", d, r[i].name, d, r[j].name);
+    }
+  }
+  return MT_OK;
+}
+
+int tracks_on(const uint8_t *d_flags, const uint8_t *d_sd, const mt_object *d_list, int32_t k, uint32_t n_frames, const uint64_t *d_stream_off,
+              uint32_t n_streams, uint32_t min_cells, uint32_t max_dropout, uint32_t reach, uint32_t min_track, uint32_t *d_work,
+              uint8_t *d_pred, uint32_t *d_age, uint32_t *d_id, uint32_t *d_len, uint32_t *d_track, uint8_t *d_flags_out, hipStream_t st) {
+  mtgpu::TracksLaunch L;
+  L.flags = d_flags;
+  L.has_sd = d_sd;
+  L.list = reinterpret_cast<const mtgpu::TrackObject *>(d_list);
+  L.k = (unsigned int)k;
+  L.n_frames = n_frames;
+  L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
+  L.n_streams = n_streams;
+  L.need_cells = min_cells < 1u ? 1u : min_cells;
+  L.max_dropout = max_dropout;
+  L.reach = reach;
+  L.need_track = min_track < 1u ? 1u : min_track;
+  L.work = d_work;
+  L.pred = d_pred;
+  L.age = d_age;
+  L.id = d_id;
+  L.len = d_len;
+  L.track = d_track;
+  L.flags_out = d_flags_out;
+  L.stream = st;
+  const hipError_t e = mtgpu::launch_tracks(L);
+  if (e != hipSuccess) return hip_fail(e, "tracks launch");
+  return MT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtgpu_tracks_preview(int k, mtgpu_tracks_plan *out) {
+  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
+  if (k < 1 || k > MT_OBJECTS_MAX) return fail(MT_ERR_INVALID, "k is %d, outside [1,%d]", k, MT_OBJECTS_MAX);
+  out->workgroup = mtgpu::kTracksBlock;
+  out->frames_per_tile = mtgpu::kTracksTile;
+  out->work_words_per_entry = mtgpu::kTracksWorkWords;
+  return MT_OK;
+}
+
+int mtgpu_track_objects_device(mtgpu_ctx *c, const uint8_t *d_flags, const uint8_t *d_has_sd, const mt_object *d_list, int32_t k,
+                               uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, uint32_t min_cells, uint32_t max_dropout,
+                               uint32_t reach, uint32_t min_track, uint32_t *d_work, uint8_t *d_pred, uint32_t *d_age, uint32_t *d_id,
+                               uint32_t *d_len, uint32_t *d_track, uint8_t *d_flags_out, void *stream) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  MT_TRY(tracks_check_args("d_", d_flags, d_has_sd, d_list, k, n_frames, d_stream_off, n_streams, reach, d_work, true, d_pred, d_age, d_id,
+                           d_len, d_track, d_flags_out));
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  if (n_frames == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  MT_TRY(check_on_device(c, {{"d_work", d_work}, {"d_pred", d_pred}, {"d_age", d_age}, {"d_id", d_id}, {"d_len", d_len}, {"d_track", d_track},
+                             {"d_flags_out", d_flags_out}}));
+  return tracks_on(d_flags, d_has_sd, d_list, k, n_frames, d_stream_off, n_streams, min_cells, max_dropout, reach, min_track, d_work, d_pred,
+                   d_age, d_id, d_len, d_track, d_flags_out, static_cast<hipStream_t>(stream));
+}
+
+int mtgpu_track_objects(mtgpu_ctx *c, const uint8_t *flags, const uint8_t *has_sd, const mt_object *list, int32_t k, uint32_t n_frames,
+                        const uint64_t *stream_off, uint32_t n_streams, uint32_t min_cells, uint32_t max_dropout, uint32_t reach,
+                        uint32_t min_track, uint8_t *pred, uint32_t *age, uint32_t *id, uint32_t *len, uint32_t *track, uint8_t *flags_out) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  MT_TRY(tracks_check_args("", flags, has_sd, list, k, n_frames, stream_off, n_streams, reach, nullptr, false, pred, age, id, len, track,
+                           flags_out));
+  if (n_frames > 0) {
+    MT_TRY(check_monotonic("stream_off", "stream", stream_off, n_streams));
+    if (stream_off[n_streams] > (uint64_t)n_frames)
+      return fail(MT_ERR_INVALID, "stream_off[%u] is %llu, above n_frames %u", n_streams, (unsigned long long)stream_off[n_streams], n_frames);
+  }
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  if (n_frames == 0) return MT_OK;
+
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  // one block of d_misc, laid out by api_common.h's stage_layout: four inputs, the workspace, six outputs
+  const size_t n = n_frames, nk = n * (size_t)k, words = sizeof(uint32_t) * nk;
+  constexpr int kSlots = 11;
+  void *const host[kSlots] = {const_cast<uint64_t *>(stream_off), const_cast<uint8_t *>(flags), const_cast<uint8_t *>(has_sd),
+                              const_cast<mt_object *>(list), nullptr, pred, age, id, len, track, flags_out};
+  const mtgpu::StageSlot slot[kSlots] = {{sizeof(uint64_t) * ((size_t)n_streams + 1), true}, {n, true}, {n, has_sd != nullptr},
+                                         {sizeof(mt_object) * nk, true}, {words * mtgpu::kTracksWorkWords, true}, {nk, pred != nullptr},
+                                         {words, age != nullptr}, {words, id != nullptr}, {words, len != nullptr},
+                                         {sizeof(uint32_t) * n, track != nullptr}, {n, flags_out != nullptr}};
+  size_t off[kSlots];
+  MT_TRY(c->d_misc.reserve(mtgpu::stage_layout(slot, kSlots, false, off)));
+  unsigned char *const d = static_cast<unsigned char *>(c->d_misc.p);
+  const auto at = [&](int i) -> unsigned char * { return off[i] == mtgpu::kNoSlot ? nullptr : d + off[i]; };
+  hipStream_t st = c->stream;
+  DrainOnExit drain{st};
+  for (int i = 0; i < 4; ++i)
+    if (at(i)) HIP_TRY(hipMemcpyAsync(at(i), host[i], slot[i].bytes, hipMemcpyHostToDevice, st));
+  MT_TRY(tracks_on(at(1), at(2), reinterpret_cast<const mt_object *>(at(3)), k, n_frames, reinterpret_cast<const uint64_t *>(at(0)), n_streams,
+                   min_cells, max_dropout, reach, min_track, reinterpret_cast<uint32_t *>(at(4)), at(5), reinterpret_cast<uint32_t *>(at(6)),
+                   reinterpret_cast<uint32_t *>(at(7)), reinterpret_cast<uint32_t *>(at(8)), reinterpret_cast<uint32_t *>(at(9)), at(10), st));
+  for (int i = 5; i < kSlots; ++i)
+    if (at(i)) HIP_TRY(hipMemcpyAsync(host[i], at(i), slot[i].bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return MT_OK;
 }

@@ -290,6 +290,9 @@ _OUTPUTS = {
     "box": ("int16", (4,), BLOB_BOX_DTYPE, 0xFF),
     "info": ("int32", (5,), GMC_INFO_DTYPE, 0),
     "list": ("int32", None, OBJECT_DTYPE, 0),
+    # object tracks (tracks.py): per list entry, the trailing shape is the caller's k
+    "pred": ("uint8", None, np.uint8, 0xFF), "age": ("int32", None, np.uint32, 0), "id": ("int32", None, np.uint32, 0xFF),
+    "len": ("int32", None, np.uint32, 0), "track": _COUNT,
     "active": ("int32", None, np.uint32, 0), "centre": ("int32", None, np.uint32, 0),
 }
 
