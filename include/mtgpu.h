@@ -48,6 +48,8 @@
  *                  MTGPU_ITEM_CHUNK, MTGPU_MERGE_LARGE_MIN (reach every kernel form on small inputs),
  *                  MTGPU_WG_PER_CU=1|2|-1 (scan workgroups per CU: at most one / two on every launch, -1 = never
  *                  fewer than the tile allows; default: one per CU for launches of large frames),
+ *                  MTGPU_EARLY_EXIT=0|2 (0: a flags-only scan reads every frame to its last record; 2: the early exit on
+ *                  launches of any size; mtgpu_plan, "Early exit"),
  *                  MTGPU_INJECT_SUBMIT_FAIL / _GROW_FAIL / _COLLECT_FAIL / MTGPU_INJECT_ONCE (pipe error paths)
  */
 #ifndef MTGPU_H
@@ -145,8 +147,16 @@ typedef struct mtgpu_plan {
   int32_t cu_count;
   int32_t chunk_rows;      /* centre rows per cluster-test chunk (mask buffer rows - 2) */
   int32_t counter_mode;    /* 0 = 32-bit add, 1 = thermometer (OR), 2 = 8-bit binary (CAS) */
-  int32_t _pad;
+  int32_t early_exit;      /* 1: flags-only scans of 40-byte records may stop early (below); 2: at any launch size; 0: never */
 } mtgpu_plan;
+/* Early exit.  A flags-only scan may stop reading a frame's records once its flag is proven: votes only ever add, so
+ * when the vote that makes a cell active finds an active 4-neighbour (both in columns 1 .. grid_w - 2) the frame has
+ * two centres and its flag is 1 whatever its remaining records hold.  Taken where the plan has one 32-bit tile
+ * (bands == 1, counter_bits == 32), vectors_needed >= 1 and clusters_needed <= 2, on unsliced launches over 40-byte
+ * records that hold at least eight frames per CU, by frames longer than one streaming step (4 x block_threads records);
+ * never by the centre-count entry points.  A smaller launch reads every frame once, to its end.  Results never depend on it; the time of a batch now depends on
+ * where in record order its motion starts.  MTGPU_EARLY_EXIT=0 in the environment (read once per context, like
+ * MTGPU_WG_PER_CU; for tests and A/B runs) switches it off, =2 takes it on launches of any size. */
 int mtgpu_get_plan(const mtgpu_ctx *ctx, mtgpu_plan *out);
 /* The plan mtgpu_create would choose on a device with `lds_bytes_per_workgroup` of LDS (gfx950:
  * 163840) and `cu_count` CUs — pure host arithmetic, no device needed (capacity planning, tests). */

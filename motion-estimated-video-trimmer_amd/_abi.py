@@ -72,6 +72,9 @@ class PlanC(C.Structure):
     _fields_ = [("block_threads", C.c_int32), ("bands", C.c_int32), ("band_rows", C.c_int32),
                 ("lds_bytes", C.c_int32), ("counter_bits", C.c_int32), ("device", C.c_int32),
                 ("cu_count", C.c_int32), ("chunk_rows", C.c_int32),
+                # _pad: mtgpu_plan::early_exit.  It keeps the name it had as padding: MotionScanner.plan and plan_preview
+                # list the fields without an underscore, and what they hand the library and return is a recorded surface
+                # (tests/golden/scanner_calls.json); early_exit.py reads it.
                 ("counter_mode", C.c_int32), ("_pad", C.c_int32)]
 
 

@@ -99,6 +99,8 @@ struct mtgpu_ctx {
   int group_request = 0; // MTGPU_GROUP: frames per workgroup, 0 = automatic
   int per_cu_request = 0; // MTGPU_WG_PER_CU: 1 | 2 = at most that many scan workgroups per CU on every launch, -1 = never
                           // fewer than the tile allows, 0 = automatic (choose_lds_floor)
+  int early_exit = 0;    // the plan allows the scan's early exit (make_plan; MTGPU_EARLY_EXIT=0 switches it off): launch_scan_on
+                         // then sets ScanK::early on every launch that qualifies — 1: with eight frames per CU or more, 2: any size
   int check_offsets = 0; // MTGPU_CHECK_OFFSETS=1: the device entry points verify "frame_off non-decreasing" first (one sync per call)
   // Launch scratch (work lists of the device entry points, spill queues, slice tiles, merge workspaces): a ring of
   // device blocks, each with the event of its last user.  Whoever takes a block makes ITS stream wait for that event,
@@ -311,6 +313,15 @@ int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
   k.group = 1;
   k.sys_flags = 0;                                            // per launch: launch_scan_on
   k.sys_centres = 0;
+  k.early = 0;                                                // per launch: launch_scan_on
+  // The early exit (scan_kernels.hip, vote_and_prove): its proof counts two centres, found by single 32-bit adds on a
+  // tile that tracks every analysed row, with cells that are inactive until they are voted for.  MTGPU_EARLY_EXIT=0
+  // (tests, A/B runs) switches it off, =2 takes it on launches of any size (launch_scan_on).
+  {
+    const int want = env_int("MTGPU_EARLY_EXIT", 1);
+    const bool can = k.bands == 1 && fb == 32 && mode == 0 && k.vec_need >= 1u && k.clust_need <= 2u;
+    c->early_exit = !can || want == 0 ? 0 : (want == 2 ? 2 : 1);
+  }
   c->group_request = env_int("MTGPU_GROUP", 0);
   c->per_cu_request = env_int("MTGPU_WG_PER_CU", 0);
   c->check_offsets = env_int("MTGPU_CHECK_OFFSETS", 0) != 0;
@@ -321,7 +332,7 @@ int make_plan(mtgpu_ctx *c, int lds_max, int cu_count) {
     if (lm > 0) c->merge_large_min = (uint64_t)lm;
   }
   c->plan.counter_mode = mode;
-  c->plan._pad = 0;
+  c->plan.early_exit = c->early_exit;
   return MT_OK;
 }
 
@@ -546,6 +557,17 @@ int launch_scan_on(mtgpu_ctx *c, const void *d_mv, uint64_t n_records, const uin
   L.k.sys_centres = centres_sys;
   L.k.slices = choose_slices(c, n_records - rebase, n_frames);
   L.k.group = choose_group(c, n_records - rebase, n_frames, rec_bytes, L.k.slices);
+  // the early exit: where the plan allows it (make_plan), on unsliced launches over 40-byte records that ask for the
+  // flags alone — a centre count needs every record, a slice sees only its share of the votes — and that give every CU
+  // at least eight frames (the bound of choose_lds_floor and choose_group: launches that fill the chip several times
+  // over).  Every figure of the exit was taken there; a smaller launch reads each of its frames exactly once, as it
+  // always did (its traffic is its algorithmic bytes), unless MTGPU_EARLY_EXIT=2 asks for the exit at any size.
+  {
+    const uint64_t cus = (uint64_t)(c->plan.cu_count > 0 ? c->plan.cu_count : 256);
+    const bool large = c->early_exit == 2 || (uint64_t)n_frames >= cus * 8ull;
+    L.k.early = (c->early_exit && large && rec_bytes == MT_MV_BYTES && L.k.bands == 1 && L.k.slices == 1 && L.k.fb == 32 &&
+                 L.k.mode == 0 && L.k.vec_need >= 1u && L.k.clust_need <= 2u && d_flags != nullptr && d_centres == nullptr) ? 1 : 0;
+  }
   if ((uint64_t)n_frames * (uint64_t)L.k.slices >= (1ull << 32))
     return fail(MT_ERR_INVALID, "%u frames x %d slices: work items must stay below 2^32 per call", n_frames, L.k.slices);
   L.block = c->plan.block_threads;

@@ -34,7 +34,11 @@ struct ScanK {
   int sys_flags;           // flags do not live in device memory (pinned host memory: the pipe's zero-copy staging, a caller's
                            // hipHostMalloc'ed buffer): result bytes leave with system-scope write-through stores
   int sys_centres;         // the same for the centre counts (ScanLaunch::centres)
+  int early;               // 1: a frame's records are no longer read once a vote has proven its flag (scan_kernels.hip, `vote`).
+                           // Per launch (launch_scan_on): 40-byte records on one ADD32 tile, slices == 1, flags only,
+                           // vec_need >= 1, clust_need <= 2.  (Fills the block's tail padding: its size stays 96 bytes.)
 };
+static_assert(sizeof(ScanK) == 96, "ScanK is a kernel argument: `early` takes what was tail padding");
 
 // One frame WITH motion-vector side data, as the scan's workgroups see it.  plan_frames (two small kernels ahead of
 // every scan) writes the frames that have side data, in stream order, to the front of the launch's work list and

@@ -34,6 +34,12 @@
 //   every record is read from HBM once.
 // The early `return true` (:288-289) does not change the value:
 // result = (#centre cells >= max(1, clusters_needed)).
+// A flags-only scan of 40-byte records on a single ADD32 tile takes an early return of its own (ScanK::early,
+// vote_and_prove): votes only add, so as soon as the vote that makes a cell active finds an active neighbour — two
+// centres, with clusters_needed <= 2 — the flag is 1 whatever the frame's remaining records hold.  The workgroup then
+// stops reading them (one look at an LDS word per wave and streaming step, stream_mv40) and skips phase 2.  Frames with
+// motion are cut short where the motion starts in record order; still frames are read to the end as before.  The
+// centre-count entry points, sliced launches, packed counters, banded plans and compact records never take it.
 //
 // Grids whose counters do not fit one LDS tile even packed are cut into ROW BANDS that the
 // SAME workgroup handles one after the other (template SPILL): the records are streamed from
@@ -473,15 +479,57 @@ __device__ __forceinline__ void queue_append(const bool qv, const unsigned int k
   else if (single) q_push_single(sq, base_1 + (unsigned int)__popcll(singles & below), e);
 }
 
+// ---- the early exit of a flags-only scan (ScanK::early: 40-byte records, one ADD32 tile, no slices, vec_need >= 1,
+// clust_need <= 2, no centre counts asked for).  Votes only ever add, so once a frame provably has two centres its flag
+// is 1 whatever the rest of its records hold, and the workgroup stops reading them.
+// The per-frame `decided` word lives in LDS: SpillQ::tail[1], which single-tile kernels do not use otherwise and
+// zero_tile clears with the frame's total.
+constexpr bool early_form(int FB, int MODE, int REC, bool SPILL) { return !SPILL && MODE == MODE_ADD32 && FB == 32 && REC == 40; }
+
+__device__ __forceinline__ unsigned int lds_peek(const unsigned int *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// One vote that may prove the flag.  The add returns the count before it; votes are single adds, so exactly ONE lane
+// per cell and frame takes the cell from active_min - 1 to active_min, and that lane looks at the cell's four grid
+// neighbours.  An active neighbour makes two centres, this cell and that one: both are active with an active
+// 4-neighbour, both lie in analysed rows (no other row ever receives a vote, keep_and_cell, and with vec_need >= 1 a
+// cell without votes is inactive), and both lie in columns [1, gw - 2] — the reference's cluster loop (:280) never
+// visits column 0 or gw - 1, so a cell there is nobody's centre and a pair that touches an edge column proves nothing.
+// Two centres >= clust_need: the flag is 1.  Whichever of two neighbouring cells becomes active last sees the other
+// (the LDS serialises the adds and the reads that follow them); a proof that is missed costs nothing but the rest of
+// the frame, the cluster test still runs.  Cells (gw - 1, y) and (0, y + 1) are adjacent in memory and no neighbours;
+// the rows above the first and below the last tracked row are not in the tile.
+// Lane-local — no ballot, shuffle or readlane: the head records and stream_tail call it under divergence.
+__device__ __forceinline__ void vote_and_prove(const ScanK &k, const Band &b, unsigned int *cnt, unsigned int *decided,
+                                               const int gx, const int gy) {
+  unsigned int *c = cnt + cell_of(b, k, gy, gx);
+  const unsigned int before = atomicAdd(c, 1u);
+  if (before + 1u != k.active_min || gx < 1 || gx > k.gw - 2) return;
+  const unsigned int am = k.active_min;
+  bool nb = false;
+  if (gx >= 2) nb |= lds_peek(c - 1) >= am;
+  if (gx <= k.gw - 3) nb |= lds_peek(c + 1) >= am;
+  if (gy - 1 >= b.t0) nb |= lds_peek(c - k.gw) >= am;
+  if (gy + 1 < b.t1) nb |= lds_peek(c + k.gw) >= am;
+  if (nb) __hip_atomic_store(decided, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 // Threshold + cell mapping + vote for one record (src/motion_scanner.cpp:246-267).
 // DENSE: try the dense-wave shortcut first — only the main streaming loop over 40-byte records asks for it (whole
 // waves, one record per lane in stream order; the compact loop holds two records per lane, head and tail calls run
 // under divergence): compiled into every call site it tripled the library's code size.
-template <int FB, int MODE, bool SPILL, bool DENSE = false>
+// EARLY: the launch takes the early exit (ScanK::early; early_form kernels only) — scan_item picks the streamer once per
+// frame, so a launch without it runs the loop it always ran, with no test per vote.
+template <int FB, int MODE, bool SPILL, bool DENSE = false, bool EARLY = false>
 __device__ __forceinline__ void vote(const MvFields m, const ScanK &k, const Band &b, unsigned int *cnt, const SpillQ &sq) {
   int gx, gy;
   const bool in = keep_and_cell(m, k, gx, gy);
   if constexpr (!SPILL && (MODE == MODE_ADD32 || (MODE == MODE_UNARY && FB == 1))) {
+    if constexpr (EARLY && MODE == MODE_ADD32) {
+      if (in) vote_and_prove(k, b, cnt, sq.tail + 1, gx, gy);
+      return;
+    }
     // fire-and-forget LDS atomics (32-bit add, 1-bit or): a single tile tracks every analysed row
     if (in) bump<FB, MODE>(cnt, cell_of(b, k, gy, gx), k.vec_need);
   } else {
@@ -600,7 +648,8 @@ __device__ __forceinline__ void slice_records(const ScanK &k, int slice, unsigne
   r1 = b;
 }
 
-// ---- phase 0: zero counters (and, once per item, the centre total and the queue tails)
+// ---- phase 0: zero counters (and, once per item, the centre total and the queue tails; tail[1] is the early exit's
+// `decided` word on a single tile)
 template <int BLOCK>
 __device__ __forceinline__ void zero_tile(const Tile &t, const ScanK &k, bool first_band) {
   const int tid = threadIdx.x;
@@ -615,10 +664,11 @@ __device__ __forceinline__ void zero_tile(const Tile &t, const ScanK &k, bool fi
 // The rest of a stream (fewer than one step: at most UNROLL units per lane, from unit i on), every load issued before
 // the first vote — a frame smaller than one step (SD streams) costs ONE memory round trip, not one per unit.  Unit: the
 // fields of a 40-byte record (u32x3) or a pair of compact records (u32x4).
-template <typename Unit, int BLOCK, int UNROLL, int FB, int MODE, bool SPILL>
+template <typename Unit, int BLOCK, int UNROLL, int FB, int MODE, bool SPILL, bool EARLY = false>
 __device__ __forceinline__ void stream_tail(const unsigned char *base, unsigned long long i, unsigned long long n, const ScanK &k,
                                             const Band &b, unsigned int *cnt, const SpillQ &sq) {
   constexpr bool PAIRS = std::is_same<Unit, u32x4>::value;
+  static_assert(!EARLY || (!PAIRS && early_form(FB, MODE, 40, SPILL)), "the early exit: 40-byte records on one ADD32 tile");
   Unit d[UNROLL];
   bool ok[UNROLL];
 #pragma unroll
@@ -631,14 +681,15 @@ __device__ __forceinline__ void stream_tail(const unsigned char *base, unsigned 
 #pragma unroll
   for (int u = 0; u < UNROLL; ++u) {
     if constexpr (PAIRS) { if (ok[u]) vote_pair<FB, MODE, SPILL>(d[u], k, b, cnt, sq); }
-    else { if (ok[u]) vote<FB, MODE, SPILL>(decode(d[u]), k, b, cnt, sq); }
+    else { if (ok[u]) vote<FB, MODE, SPILL, false, EARLY>(decode(d[u]), k, b, cnt, sq); }
   }
 }
 
 // 40-byte records [base, base + 40 n): lane i of a step takes record i, UNROLL independent loads in flight per lane.
-template <int BLOCK, int UNROLL, int FB, int MODE, bool SPILL>
+template <int BLOCK, int UNROLL, int FB, int MODE, bool SPILL, bool EARLY = false>
 __device__ __forceinline__ void stream_mv40(const unsigned char *base, unsigned long long n, const ScanK &k, const Band &b,
                                             unsigned int *cnt, const SpillQ &sq) {
+  static_assert(!EARLY || early_form(FB, MODE, 40, SPILL), "the early exit: 40-byte records on one ADD32 tile");
   const int tid = threadIdx.x;
   // Line alignment.  A wave instruction of the loops below covers 64 records = 2560 bytes = exactly 20
   // 128-byte lines IF the stream starts on a line; a frame that starts mid-line (real footage: every
@@ -650,7 +701,8 @@ __device__ __forceinline__ void stream_mv40(const unsigned char *base, unsigned 
   if ((r & 7u) == 0u) {
     unsigned long long h = (unsigned long long)((13u * ((16u - (r >> 3)) & 15u)) & 15u);
     h = h < n ? h : n;
-    if ((unsigned long long)tid < h) vote<FB, MODE, SPILL>(decode(load_fields(base + (unsigned long long)tid * 40ull)), k, b, cnt, sq);
+    if ((unsigned long long)tid < h)
+      vote<FB, MODE, SPILL, false, EARLY>(decode(load_fields(base + (unsigned long long)tid * 40ull)), k, b, cnt, sq);
     base += h * 40ull;
     n -= h;
   }
@@ -664,9 +716,16 @@ __device__ __forceinline__ void stream_mv40(const unsigned char *base, unsigned 
     // (the scheduler sinks loads 2..UNROLL below the wait for load 1; forcing them up front with
     //  a sched_barrier measured -1..-2 % here, +7 % in the compact loop: left as it is)
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) vote<FB, MODE, SPILL, true>(decode(d[u]), k, b, cnt, sq);
+    for (int u = 0; u < UNROLL; ++u) vote<FB, MODE, SPILL, true, EARLY>(decode(d[u]), k, b, cnt, sq);
+    if constexpr (EARLY) {
+      // The early exit: once per wave and step, behind the step's votes — a proof found in this step, by this wave
+      // or by one that runs level with it, saves the next step's loads.  Every lane reads the same word: the branch
+      // is wave-uniform.  No barrier: a wave that leaves goes on to the one behind phase 1 (scan_item) and waits there
+      // for the waves that have not looked yet.  The rest of the frame, stream_tail included, is skipped.
+      if (__builtin_amdgcn_readfirstlane((int)lds_peek(sq.tail + 1)) != 0) return;
+    }
   }
-  if (i < n) stream_tail<u32x3, BLOCK, UNROLL, FB, MODE, SPILL>(base, i, n, k, b, cnt, sq);
+  if (i < n) stream_tail<u32x3, BLOCK, UNROLL, FB, MODE, SPILL, EARLY>(base, i, n, k, b, cnt, sq);
 }
 
 // Compact records [base, base + 8 n): 16-byte loads of TWO records per lane (a wave instruction covers 1 KB),
@@ -956,6 +1015,10 @@ __device__ __forceinline__ void scan_item(
 
   const int n_bands = SPILL ? k.bands : 1;
   unsigned int local = 0;
+  bool proven = false;                                             // workgroup-uniform (ScanK::early)
+  // The exit can only save what comes behind a frame's first streaming step: a frame that fits into the head records
+  // plus one step has every load issued before its first vote (480p frames: 1200 records), so it takes the plain votes.
+  const bool early = early_form(FB, MODE, REC, SPILL) && k.early && r1 - r0 > (unsigned long long)UNROLL * BLOCK + 15ull;
   for (int band = 0; band < n_bands; ++band) {
     const Band b = band_rows(k, band);
     const bool votes = b.t1 > b.t0 && k.vec_need != 0u;            // vec_need == 0: every cell is active anyway
@@ -969,6 +1032,7 @@ __device__ __forceinline__ void scan_item(
     if (band == 0) {
       if (votes) {
         if constexpr (REC == 8) stream_compact<BLOCK, UNROLL, FB, MODE, SPILL>(mv + r0 * 8ull, r1 - r0, k, b, t.cnt, sq, ns);
+        else if (early) stream_mv40<BLOCK, UNROLL, FB, MODE, SPILL, early_form(FB, MODE, REC, SPILL)>(mv + r0 * 40ull, r1 - r0, k, b, t.cnt, sq);
         else stream_mv40<BLOCK, UNROLL, FB, MODE, SPILL>(mv + r0 * 40ull, r1 - r0, k, b, t.cnt, sq);
       }
       if constexpr (REC == 8 && !SPILL) {                          // (exactly when the next frame's phase 1 runs)
@@ -986,8 +1050,12 @@ __device__ __forceinline__ void scan_item(
     if (sliced && !hand_over_slices<BLOCK, FB, MODE>(t, k, f, slice, slice_ws, tickets)) { PT_ADD(3); PT_FLUSH(); return; }
     PT_ADD(3);
 
-    // ---- phase 2
-    local += cluster_count<BLOCK, FB, MODE>(t, k, b);
+    // ---- phase 2 — unless a vote has proven the flag (vote_and_prove).  Nobody writes `decided` behind the barrier of
+    // phase 1, every wave reads it here, ahead of the barrier below, and the next frame's zeroing comes behind that one.
+    if constexpr (early_form(FB, MODE, REC, SPILL)) {
+      if (early) proven = __builtin_amdgcn_readfirstlane((int)lds_peek(t.tail + 1)) != 0;
+    }
+    if (!proven) local += cluster_count<BLOCK, FB, MODE>(t, k, b);
     PT_ADD(4);
   }
   if (local) atomicAdd(t.total, local);
@@ -996,7 +1064,7 @@ __device__ __forceinline__ void scan_item(
   // (sliced frames: only the last arriver gets here, with the frame's summed tile; bands: t.total is the sum over bands)
   if (threadIdx.x == 0) {
     const unsigned int n = *t.total;
-    if (flags) store_flag(flags, f, (n >= k.clust_need) ? 1 : 0, k.sys_flags);
+    if (flags) store_flag(flags, f, (proven || n >= k.clust_need) ? 1 : 0, k.sys_flags);
     if (centres) store_centres(centres, f, n, k.sys_centres);
   }
   PT_FLUSH();
