@@ -530,6 +530,11 @@ int mtgpu_gather_segments(mtgpu_comm *comm, const void *d_send, uint64_t bytes_p
  * the track's length — three more entry points, declared the same way. */
 #include "mtgpu_tracks.h"
 
+/* Object headings: the object scan plus, for each listed blob, the rose and the summed displacement of the records that
+ * land in it, and a count of the objects whose heading is allowed (src/motion_scanner.cpp:246-294, then the components
+ * of the centres) — three more entry points, declared the same way. */
+#include "mtgpu_headings.h"
+
 /* Temporal persistence: the runs of consecutive motion frames per stream — across the key frames that were never
  * analysed, with a bounded dropout and, given the blob boxes, only while the object stays in place — and every frame's
  * run length and place in its run (the frames src/motion_scanner.cpp:382-383 pools, before src/pipeline.cpp:328-344

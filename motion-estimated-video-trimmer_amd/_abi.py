@@ -39,6 +39,12 @@ BLOB_BOX_DTYPE = np.dtype([("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "
 # y * grid_w + x of its cells, its inclusive cell bounds; an empty entry reads {0, 0xFFFFFFFF, 0xFFFF x 4}
 OBJECT_DTYPE = np.dtype([("cells", "<u4"), ("first", "<u4"), ("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2")])
 OBJECTS_MAX, OBJECT_TABLE_BYTES = 16, 24
+# mt_heading (include/mtgpu_headings.h): the motion of one list entry — the belonging records per sector (0 = E,
+# clockwise), all belonging records, the heading (HEADING_NONE: every bin is 0), the summed displacement; an empty entry
+# reads zeros with heading = HEADING_NONE
+HEADING_DTYPE = np.dtype([("n", "<u4", (8,)), ("records", "<u4"), ("heading", "<u4"), ("sum_dx", "<i8"), ("sum_dy", "<i8"),
+                          ("reserved", "<u8")])
+HEADING_NONE, HEADING_TABLE_BYTES = 0xFFFFFFFF, 56
 # mt_gmc_info (include/mtgpu_gmc.h): the applied vector, the modes of the two axes, the counted records, the modes' counts
 GMC_INFO_DTYPE = np.dtype([("gx", "<i2"), ("gy", "<i2"), ("mode_x", "<i2"), ("mode_y", "<i2"), ("n_in", "<u4"), ("n_x", "<u4"),
                            ("n_y", "<u4")])
@@ -98,6 +104,11 @@ class BlobsPlanC(C.Structure):
 
 
 class ObjectsPlanC(C.Structure):
+    _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("keep_words_per_row", C.c_int32),
+                ("keep_words_per_stream", C.c_int32)]
+
+
+class HeadingsPlanC(C.Structure):
     _fields_ = [("lds_bytes", C.c_int32), ("workgroup", C.c_int32), ("keep_words_per_row", C.c_int32),
                 ("keep_words_per_stream", C.c_int32)]
 
@@ -372,10 +383,22 @@ ABI_TRACKS = {
 TRACK_NO_PRED, TRACK_NO_ID = 0xFF, 0xFFFFFFFF
 TRACK_WORK_WORDS = 2                                 # mtgpu_tracks_plan.work_words_per_entry: uint32 words of d_work per list entry
 
+# name -> (restype, argtypes): every symbol include/mtgpu_headings.h declares (object headings; mtgpu.h includes it).
+ABI_HEADINGS = {
+    "mtgpu_headings_preview": (C.c_int, [C.POINTER(ScanParamsC), C.c_int, C.c_int, C.POINTER(HeadingsPlanC)]),
+    "mtgpu_scan_headings_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "mtgpu_scan_frames_headings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 # every table above, in header order: what load_library() binds
 ABI_TABLES = (ABI, ABI_MOTION, ABI_SWEEP, ABI_ACTIVITY, ABI_ZONES, ABI_PIPE_ZONES, ABI_BLOBS, ABI_PIPE_BLOBS, ABI_GMC,
               ABI_PIPE_GMC, ABI_GMC_BLOBS, ABI_PIPE_GMC_BLOBS, ABI_PERSIST, ABI_PIPE_BOXES, ABI_DIR, ABI_PIPE_DIR, ABI_LANES,
-              ABI_PIPE_LANES, ABI_OBJECTS, ABI_TRACKS)
+              ABI_PIPE_LANES, ABI_OBJECTS, ABI_TRACKS, ABI_HEADINGS)
 
 _lib = None
 

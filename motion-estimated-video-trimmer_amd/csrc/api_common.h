@@ -17,7 +17,7 @@ namespace mtgpu {
 //
 // The extra inputs of a host form and then its outputs lie in one device block, every slot at the next multiple of 256
 // bytes.  A slot that is not present takes no room; a present slot of 0 bytes takes none either.
-constexpr int kStageMaxSlots = 8;
+constexpr int kStageMaxSlots = 10;      // the heading scan's host form: two inputs, seven outputs
 constexpr size_t kNoSlot = ~(size_t)0;
 struct StageSlot { size_t bytes; bool present; };
 inline size_t stage_up(size_t v) { return (v + 255u) & ~(size_t)255u; }

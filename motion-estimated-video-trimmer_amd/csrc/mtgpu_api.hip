@@ -33,6 +33,7 @@
 #include "dir_kernels.h"
 #include "lanes_kernels.h"
 #include "objects_kernels.h"
+#include "headings_kernels.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -2899,6 +2900,153 @@ int mtgpu_scan_frames_objects(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *fra
   MT_TRY(objects_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff), n_streams,
                     sg.at<const uint64_t>(i_keep), k, min_blob_cells, min_objects, sg.at<uint8_t>(o_fl), sg.at<uint32_t>(o_cen),
                     sg.at<uint32_t>(o_bl), sg.at<uint32_t>(o_ob), sg.at<mt_object>(o_list), sg.st));
+  return sg.download();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- object headings (the object scan, then the records of
+// src/motion_scanner.cpp:246-268 once more, per listed blob; include/mtgpu_headings.h)
+
+namespace {
+
+static_assert(sizeof(mt_heading) == 4 * sizeof(mtgpu::ObjectWord4) && sizeof(mt_heading) == 64, "mt_heading is four 16-byte stores");
+static_assert(offsetof(mt_heading, records) == 32 && offsetof(mt_heading, heading) == 36 && offsetof(mt_heading, sum_dx) == 40 &&
+              offsetof(mt_heading, sum_dy) == 48 && offsetof(mt_heading, reserved) == 56, "the kernel stores the fields in this order");
+static_assert(MT_HEADING_TABLE_BYTES == mtgpu::kHeadingTableBytes && MT_HEADING_NONE == mtgpu::kNoHeading, "the kernel's limits are the ABI's");
+
+// What the heading scan's own scalars decide: k, min_objects against k, the allow byte.
+int check_heading_args(int32_t k, int32_t min_objects, int32_t allow) {
+  MT_TRY(check_top_k(k));
+  if (min_objects > k) return fail(MT_ERR_INVALID, "min_objects is %d, above k = %d", (int)min_objects, (int)k);
+  if (allow < 0 || allow > 255) return fail(MT_ERR_INVALID, "allow %d outside [0,255]", (int)allow);
+  return MT_OK;
+}
+
+// One form: the object scan's layout and the motion table for k entries.  It fits or the grid is unsupported.
+int headings_plan(const mt_scan_params &p, int k, int lds_max, mtgpu_headings_plan *out) {
+  const int R = analysed_rows(p);
+  const long long need = (long long)mtgpu::headings_lds_bytes(p.grid_w, R, k);
+  if (need > (long long)lds_max)
+    return fail(MT_ERR_UNSUPPORTED, "grid %dx%d: one tile of 32-bit counters for %d rows, the keep rows, one mask plane, the "
+                "ranking table and the motion table for %d objects (%lld bytes) do not fit %d bytes of LDS; the heading scan has no "
+                "banded form", p.grid_w, p.grid_h, R + 2, k, need, lds_max);
+  const long long W = ((long long)p.grid_w + 63) / 64;
+  out->lds_bytes = (int32_t)need;
+  out->workgroup = mtgpu::kHeadingsBlock;
+  out->keep_words_per_row = (int32_t)W;
+  out->keep_words_per_stream = (int32_t)(W * (long long)p.grid_h);
+  return MT_OK;
+}
+
+// The heading scan of a device-resident batch on `st`.  The arguments have been validated; n_frames > 0.
+int headings_on(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, uint64_t rebase, const uint64_t *d_off,
+                const uint8_t *d_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams, const uint64_t *d_keep,
+                int32_t k, int32_t min_blob_cells, int32_t min_objects, int32_t allow, uint8_t *d_flags, uint32_t *d_centres,
+                uint32_t *d_blobs, uint32_t *d_objects, mt_object *d_list, mt_heading *d_motion, uint32_t *d_allowed, hipStream_t st) {
+  mtgpu_headings_plan hp;
+  MT_TRY(headings_plan(c->params, k, c->lds_max, &hp));
+  mtgpu::HeadLaunch L;
+  fill_batch(L, c, d_rec, rec_bytes, n_records, rebase, d_off, d_sd, n_frames, hp.lds_bytes, st);
+  L.stream_off = reinterpret_cast<const unsigned long long *>(d_stream_off);
+  L.n_streams = n_streams;
+  L.keep = reinterpret_cast<const unsigned long long *>(d_keep);
+  L.flags = d_flags; L.centres = d_centres; L.blobs = d_blobs; L.objects = d_objects;
+  L.list = reinterpret_cast<mtgpu::ObjectWord4 *>(d_list);
+  L.motion = reinterpret_cast<mtgpu::ObjectWord4 *>(d_motion);
+  L.allowed = d_allowed;
+  L.allow = (unsigned int)allow;
+  L.topk = k;
+  L.obj_need = min_objects < 1 ? 1u : (unsigned int)min_objects;
+  fill_tile(L.k, c->k, mtgpu::blob_tile_words);
+  L.k.clust_need = c->k.clust_need;
+  L.k.blob_need = min_blob_cells < 1 ? 1u : (unsigned int)min_blob_cells;
+  PlanWs ws(c, st, nullptr, mtgpu::ctx_plan_ws_bytes(n_frames));
+  if (ws.rc != MT_OK) return ws.rc;
+  L.plan_ws = ws.p;
+  return profiled_launch(c, st, L, mtgpu::launch_heading_scan, "heading scan launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtgpu_headings_preview(const mt_scan_params *p, int k, int lds_bytes_per_workgroup, mtgpu_headings_plan *out) {
+  if (!out) return fail(MT_ERR_INVALID, "out is NULL");
+  MT_TRY(check_top_k(k));
+  MT_TRY(validate_params(p));
+  if (lds_bytes_per_workgroup < 1024) return fail(MT_ERR_INVALID, "LDS size out of range");
+  mtgpu_headings_plan pl;
+  MT_TRY(headings_plan(*p, k, lds_bytes_per_workgroup, &pl));
+  *out = pl;
+  return MT_OK;
+}
+
+int mtgpu_scan_headings_device(mtgpu_ctx *c, const void *d_rec, int rec_bytes, uint64_t n_records, const uint64_t *d_frame_off,
+                               const uint8_t *d_has_sd, uint32_t n_frames, const uint64_t *d_stream_off, uint32_t n_streams,
+                               const uint64_t *d_keep, int32_t k, int32_t min_blob_cells, int32_t min_objects, int32_t allow,
+                               uint8_t *d_flags, uint32_t *d_centres, uint32_t *d_blobs, uint32_t *d_objects, mt_object *d_list,
+                               mt_heading *d_motion, uint32_t *d_allowed, void *stream) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  MT_TRY(check_heading_args(k, min_objects, allow));
+  MT_TRY(check_rec_bytes(rec_bytes));
+  MT_TRY(check_any_output("d_", {{"flags", d_flags}, {"centres", d_centres}, {"blobs", d_blobs}, {"objects", d_objects}, {"list", d_list},
+                                 {"motion", d_motion}, {"allowed", d_allowed}}));
+  if (n_frames > 0 && !d_frame_off) return fail(MT_ERR_INVALID, "d_frame_off is NULL");
+  MT_TRY(check_stream_table("d_", d_stream_off, n_streams, d_keep));
+  MT_TRY(check_aligned("d_", {{"frame_off", d_frame_off, 8}, {"stream_off", d_stream_off, 8}, {"keep", d_keep, 8}}));
+  if (n_frames > 0 && n_records > 0 && !d_rec) return fail(MT_ERR_INVALID, "d_rec is NULL with n_records > 0");
+  MT_TRY(check_rec("d_", rec_bytes, d_rec));
+  // (one 16-byte store per list entry, four per motion entry)
+  MT_TRY(check_aligned("d_", {{"centres", d_centres, 4}, {"blobs", d_blobs, 4}, {"objects", d_objects, 4}, {"allowed", d_allowed, 4},
+                              {"list", d_list, 16}, {"motion", d_motion, 16}}));
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  mtgpu_headings_plan hp;
+  MT_TRY(headings_plan(c->params, k, c->lds_max, &hp));      // a grid without a form: before any HIP call
+  if (n_frames == 0) return MT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  MT_TRY(check_on_device(c, {{"d_keep", d_keep}, {"d_flags", d_flags}, {"d_centres", d_centres}, {"d_blobs", d_blobs},
+                             {"d_objects", d_objects}, {"d_list", d_list}, {"d_motion", d_motion}, {"d_allowed", d_allowed}}));
+  MT_TRY(check_offsets_on(c, d_frame_off, n_frames, stream));
+  return headings_on(c, d_rec, rec_bytes, n_records, 0, d_frame_off, d_has_sd, n_frames, d_stream_off, n_streams, d_keep, k,
+                     min_blob_cells, min_objects, allow, d_flags, d_centres, d_blobs, d_objects, d_list, d_motion, d_allowed,
+                     static_cast<hipStream_t>(stream));
+}
+
+int mtgpu_scan_frames_headings(mtgpu_ctx *c, const mt_mv *mv, const uint64_t *frame_off, const uint8_t *has_sd, uint32_t n_frames,
+                               const uint64_t *stream_off, uint32_t n_streams, const uint64_t *keep, int32_t k, int32_t min_blob_cells,
+                               int32_t min_objects, int32_t allow, uint8_t *flags, uint32_t *centres, uint32_t *blobs,
+                               uint32_t *objects, mt_object *list, mt_heading *motion, uint32_t *allowed) {
+  // what the arguments alone decide comes first: these answers need neither a context nor a device
+  MT_TRY(check_heading_args(k, min_objects, allow));
+  MT_TRY(check_any_output("", {{"flags", flags}, {"centres", centres}, {"blobs", blobs}, {"objects", objects}, {"list", list},
+                               {"motion", motion}, {"allowed", allowed}}));
+  if (n_frames > 0 && !frame_off) return fail(MT_ERR_INVALID, "frame_off is NULL");
+  MT_TRY(check_stream_table("", stream_off, n_streams, keep));
+  MT_TRY(check_monotonic("frame_off", "frame", frame_off, n_frames));
+  if (keep) MT_TRY(check_stream_off(stream_off, n_streams, n_frames));
+  uint64_t r_begin, r_end;
+  MT_TRY(check_window(mv, frame_off, n_frames, &r_begin, &r_end));
+  if (!c) return fail(MT_ERR_INVALID, "ctx is NULL");
+  mtgpu_headings_plan hp;
+  MT_TRY(headings_plan(c->params, k, c->lds_max, &hp));      // a grid without a form: before anything is staged
+  if (n_frames == 0) return MT_OK;
+
+  // (without a mask stream_off and keep are null and n_streams is 0: no room, null device pointers; every slot of the
+  // block begins at a multiple of 256 bytes, so the device list and motion are 16-byte aligned whatever the caller's are)
+  const size_t words = sizeof(uint32_t) * (size_t)n_frames;
+  Staged sg(c, c->d_misc, false, mv, r_begin, r_end, frame_off, has_sd, n_frames);
+  const int i_soff = sg.in(stream_off, sizeof(uint64_t) * ((size_t)n_streams + 1));
+  const int i_keep = sg.in(keep, sizeof(uint64_t) * (size_t)n_streams * (size_t)c->k.gh * (size_t)c->k.W);
+  const int o_fl = sg.out(flags, n_frames), o_cen = sg.out(centres, words), o_bl = sg.out(blobs, words), o_ob = sg.out(objects, words);
+  const int o_list = sg.out(list, sizeof(mt_object) * (size_t)n_frames * (size_t)k);
+  const int o_mot = sg.out(motion, sizeof(mt_heading) * (size_t)n_frames * (size_t)k);
+  const int o_al = sg.out(allowed, words);
+  MT_TRY(sg.upload());
+  MT_TRY(headings_on(c, sg.d_mv(), MT_MV_BYTES, r_end, r_begin, sg.d_off(), sg.d_sd(), n_frames, sg.at<const uint64_t>(i_soff), n_streams,
+                     sg.at<const uint64_t>(i_keep), k, min_blob_cells, min_objects, allow, sg.at<uint8_t>(o_fl), sg.at<uint32_t>(o_cen),
+                     sg.at<uint32_t>(o_bl), sg.at<uint32_t>(o_ob), sg.at<mt_object>(o_list), sg.at<mt_heading>(o_mot),
+                     sg.at<uint32_t>(o_al), sg.st));
   return sg.download();
 }
 

@@ -20,7 +20,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi, config
-from ._abi import (BLOB_BOX_DTYPE, OBJECT_DTYPE, BlobsPlanC, COMPACT_DTYPE, DIR_ALL, DirPlanC, LanesPlanC, LAYOUT_AOS40, LAYOUT_BOXES, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
+from ._abi import (BLOB_BOX_DTYPE, HEADING_DTYPE, OBJECT_DTYPE, BlobsPlanC, COMPACT_DTYPE, DIR_ALL, DirPlanC, LanesPlanC, LAYOUT_AOS40, LAYOUT_BOXES, LAYOUT_CENTRES, LAYOUT_COMPACT8, LAYOUT_ZERO_COPY, MERGE_PARAMS_DTYPE, MERGE_RESULT_DTYPE,
                    GMC_DEFAULT_MAX_SHIFT, GMC_DEFAULT_MIN_SHARE_Q8, GMC_INFO_DTYPE, GmcBlobsPlanC, GmcPlanC,
                    MV_DTYPE, SEGMENT_DTYPE, ActivityPlanC, MergeParamsC, MergeResultC, PersistPlanC, PlanC, ScanParamsC, SweepPlanC, ZonesPlanC, check,
                    load_library)
@@ -293,6 +293,8 @@ _OUTPUTS = {
     # object tracks (tracks.py): per list entry, the trailing shape is the caller's k
     "pred": ("uint8", None, np.uint8, 0xFF), "age": ("int32", None, np.uint32, 0), "id": ("int32", None, np.uint32, 0xFF),
     "len": ("int32", None, np.uint32, 0), "track": _COUNT,
+    # object headings (headings.py): per list entry; the empty entry's heading word is the library's to write
+    "motion": ("int32", None, HEADING_DTYPE, 0), "allowed": _COUNT,
     "active": ("int32", None, np.uint32, 0), "centre": ("int32", None, np.uint32, 0),
 }
 
